@@ -1,7 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's headline metric on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|5] [--batch B] [--t T] [--signers N]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|5] [--batch B] [--t T] [--signers N] [--full] [--dump-outputs DIR]
+
+A plain run is lean: it sets up the workload, warms up, times the K steps, writes the outputs of the last step when
+--dump-outputs is given and prints the result line (`metric`, `value`, `unit`, `ms_per_step`, ...; `roofline` and
+`cpu_baseline` are null).  Everything else described below -- the live roofline peak, the per-launch kernel times and
+rooflines, the `streaming` / `sustained` / `general_path` legs, configs 3 and 4, the wire-level leg, the extras and the CPU
+baselines (Oracle B, rebuilt for the host's cores) -- runs only with --full.
+
+--dump-outputs DIR (config 2): after the timed steps, the arrays the last step returned to its caller -- `signatures`
+(batch x 192 bytes of the uncompressed G2 points) and `status` (batch) -- as float32 DIR/<name>.npy.  The workload is
+derived from a fixed seed, so the same arguments give the same inputs in every run; above 60 MB in all, the same seeded
+sample of jobs is kept of every array and its job numbers go to DIR/rows.npy (float64).  With N ranks, rank 0 writes its
+own jobs.
 
 --gpus N with N > 1 STARTS N ranks: when the process was not itself started by torch.distributed.run (no
 WORLD_SIZE in the environment) it re-executes itself under `python -m torch.distributed.run --nnodes=1
@@ -241,6 +253,10 @@ def parse_args(argv=None):
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo: CPU ranks, only with --test-engine")
     ap.add_argument("--test-engine", default=None, choices=[None, "hostsim"],
                     help="TEST HARNESS: tests/hostsim (g++ build of the device source) instead of the GPU; needs --backend gloo")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: live peak, rooflines, the secondary legs and configurations, the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as float32 DIR/<name>.npy (config 2)")
     args = ap.parse_args(argv)
     if args.steps is None:
         args.steps = 20 if args.config == 2 else 6
@@ -250,6 +266,8 @@ def parse_args(argv=None):
         ap.error("--gpus must be >= 1")
     if args.emulate_world and (args.config != 5 or args.gpus != 1):
         ap.error("--emulate-world belongs to --config 5 on one GPU")
+    if args.dump_outputs and (args.config != 2 or args.latency_table):
+        ap.error("--dump-outputs writes the outputs of the config-2 step")
     return args
 
 
@@ -312,7 +330,7 @@ def main(argv=None):
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
     # (the CPU legs run on rank 0 of a one-GPU run only: N ranks would rebuild and time N oracles against each other on one host)
-    if not args.no_cpu_baseline and not args.test_engine and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
+    if args.full and not args.no_cpu_baseline and not args.test_engine and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         oracle_for_this_host()
 
     import torch
@@ -368,13 +386,13 @@ def main(argv=None):
         # tests a context runs by default are switched off -- the reference's combine_signatures / verify do not repeat
         # from_bytes either.  `extras.combine_with_input_checks_per_s` is the same step with them on.
         eng.set_input_checks(False)
-        peak = measure_peak() if rank == 0 else dict(PEAK_RECORDED)
+        peak = measure_peak() if (rank == 0 and args.full) else dict(PEAK_RECORDED)
     if args.latency_table:
         latency_table(eng)
         return None
     if args.config == 5:
         from threshold_crypto_amd import config5
-        result = config5.run_bench(args, eng, dev, rank, world, peak, roofline, cpu_baseline=cpu_baseline_config5)
+        result = config5.run_bench(args, eng, dev, rank, world, peak, roofline, cpu_baseline=cpu_baseline_config5 if args.full else None)
     else:
         result = run_config2(args, eng, dev, rank, world, peak)
     if rank == 0:
@@ -510,6 +528,29 @@ def emit(result):
     sys.stdout.flush()
 
 
+DUMP_LIMIT = 60 * 10 ** 6    # data bytes of one --dump-outputs (the .npy headers stay well inside 64 MB with it)
+DUMP_SEED = 0
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: `arrays` (name -> one row per job, host or device) as float32 DIR/<name>.npy.  Above DUMP_LIMIT the same
+    seeded sample of jobs is kept of every array, and their job numbers go to DIR/rows.npy (float64)."""
+    import numpy as np
+    arrays = {k: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(4 * (a.size // max(n, 1)) for a in arrays.values())
+    os.makedirs(directory, exist_ok=True)
+    rows_file = os.path.join(directory, "rows.npy")
+    rows = None
+    if n * row_bytes > DUMP_LIMIT:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_LIMIT // (row_bytes + 8), replace=False))
+        np.save(rows_file, rows.astype(np.float64))
+    elif os.path.exists(rows_file):
+        os.remove(rows_file)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), (a if rows is None else a[rows]).astype(np.float32))
+
+
 def _device_identity(torch, i):
     p = torch.cuda.get_device_properties(i)
     tag = getattr(p, "uuid", None)
@@ -573,16 +614,17 @@ def run_config2(args, eng, dev, rank, world, peak):
         eng.set_stream(stream.cuda_stream)
     for _ in range(max(1, args.warmup)):
         sig, st = eng.combine_g2(t, d_idx, d_shares)
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)] if cuda else []
+    # (--full: HIP events around every timed step give the roofline its per-launch kernel time)
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)] if (cuda and args.full) else []
     step_no = [0]
 
     def headline_step():
         i = step_no[0]
         step_no[0] += 1
-        if cuda:
+        if ev:
             ev[i][0].record(stream)
         o = eng.combine_g2(t, d_idx, d_shares)
-        if cuda:
+        if ev:
             ev[i][1].record(stream)
         return o
 
@@ -590,6 +632,26 @@ def run_config2(args, eng, dev, rank, world, peak):
     ms_per_step = dt / args.steps * 1e3
     value = B * world / (dt / args.steps)
     assert int(st.to(torch.int32).sum().item()) == 0, "combine reported per-job errors"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"signatures": sig, "status": st})
+    headline = {
+        "metric": "combine_signatures/sec", "value": round(value, 1), "unit": "combine_signatures/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "i32 limbs (Fq = 14 x 28-bit signed, Montgomery R=2^392; 64-bit column accumulators; one Fq2 coefficient per lane of a lane pair)",
+        "data": "synthetic",
+        "config": {"workload": "t=%d,N=%d,batch=%d threshold signatures (combine_signatures, G2), per GPU" % (t, N, B),
+                   "t": t, "N": N, "batch_per_gpu": B, "parallelism": "jobs sharded, dp%d" % world,
+                   "fast_path": 1 <= t <= 3, "steps_in_flight": 1, "overlapped": False,
+                   "input_checks": "off: every operand is an output of the library's own kernels (known members); "
+                                   "extras.combine_with_input_checks_per_s has them on",
+                   "timed_region_is": "K steps queued on ONE context (one HIP stream: launches do not overlap), barrier + "
+                                      "synchronize on both sides, MAX over ranks",
+                   "comparable_with": "round 2's BENCH value (17.6 M) was the two-contexts figure: compare it with streaming.value; "
+                                      "round 2's sequential.value (13.3 M) is what `value` is now"},
+    }
+    if not args.full:
+        return dict(headline, roofline=None, cpu_baseline=None) if rank == 0 else None
     kernel_ms = [a.elapsed_time(b) for a, b in ev] if cuda else [0.0]
     avg_kernel_ms = sum(kernel_ms) / len(kernel_ms)
     assert avg_kernel_ms <= ms_per_step * 1.001 or not cuda, "per-launch event time exceeds the step time on one stream"
@@ -884,7 +946,6 @@ def run_config2(args, eng, dev, rank, world, peak):
 
     if rank != 0:
         return None
-    fast = 1 <= t <= 3
     unit_key = "combine_g2_t3_fast" if t == 3 else None
     head = None
     if unit_key and not harness:
@@ -925,20 +986,7 @@ def run_config2(args, eng, dev, rank, world, peak):
             leg["kernel_clock"] = clock
             leg["frac_at_kernel_clock"] = round(leg["frac"] * leg["peak_clock_GHz"] / clock["sclk_GHz"], 4)
     return {
-        "metric": "combine_signatures/sec", "value": round(value, 1), "unit": "combine_signatures/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "i32 limbs (Fq = 14 x 28-bit signed, Montgomery R=2^392; 64-bit column accumulators; one Fq2 coefficient per lane of a lane pair)",
-        "data": "synthetic",
-        "config": {"workload": "t=%d,N=%d,batch=%d threshold signatures (combine_signatures, G2), per GPU" % (t, N, B),
-                   "t": t, "N": N, "batch_per_gpu": B, "parallelism": "jobs sharded, dp%d" % world,
-                   "fast_path": fast, "steps_in_flight": 1, "overlapped": False,
-                   "input_checks": "off: every operand is an output of the library's own kernels (known members); "
-                                   "extras.combine_with_input_checks_per_s has them on",
-                   "timed_region_is": "K steps queued on ONE context (one HIP stream: launches do not overlap), barrier + "
-                                      "synchronize on both sides, MAX over ranks",
-                   "comparable_with": "round 2's BENCH value (17.6 M) was the two-contexts figure: compare it with streaming.value; "
-                                      "round 2's sequential.value (13.3 M) is what `value` is now"},
+        **headline,
         "streaming": streaming,
         "sustained": sustained,
         "general_path": general,

@@ -275,7 +275,7 @@ def test_bench_line_contract():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "1", "--batch", "8192",
-                          "--no-extras", "--cpu-seconds", "1", "--sustain-seconds", "0.2"], capture_output=True, text=True, timeout=600, cwd=root)
+                          "--no-extras", "--cpu-seconds", "1", "--sustain-seconds", "0.2", "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     # what the driver keeps is the LAST line of the last 8 000 bytes of stdout -- one compact JSON object
     # (tests/benchline.py reads it that way); the explanatory detail object is in bench_detail.json and, tagged, on stderr
@@ -313,6 +313,31 @@ def test_bench_line_contract():
     assert 0 < r["frac_useful"] <= r["frac"] and 0 < d["config3"]["roofline"]["frac_useful"] <= d["config3"]["roofline"]["frac"]
 
 
+def test_plain_bench_run_dumps_what_its_last_step_computed(engine, tmp_path):
+    """A plain run (no --full): the headline line alone, exactly --steps timed steps, and --dump-outputs writes the combined
+    signatures of the timed batch, which agree bit for bit with Oracle B on a sample of the seeded workload's jobs."""
+    import subprocess
+    import sys
+    import c_oracle
+    from threshold_crypto_amd.workload import ThresholdSigWorkload
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d_out = str(tmp_path / "out")
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8192",
+                          "--dump-outputs", d_out], capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    sys.path.insert(0, os.path.join(root, "tests"))
+    import benchline
+    line, d = benchline.parse(out.stdout, out.stderr)
+    assert line["steps"] == 3 and line["config"]["batch_per_gpu"] == 8192 and line["roofline"] is None and line["cpu_baseline"] is None
+    assert abs(d["value"] - 8192 / (d["ms_per_step"] * 1e-3)) / d["value"] < 0.01 and "config3" not in d and "streaming" not in d
+    sig, st = np.load(os.path.join(d_out, "signatures.npy")), np.load(os.path.join(d_out, "status.npy"))
+    assert sig.dtype == np.float32 and sig.shape == (8192, 192) and st.shape == (8192,) and not st.any()
+    wl = ThresholdSigWorkload(engine, 3, 10, 8192)
+    for j in range(0, 8192, 911):
+        rc, want = c_oracle.combine_g2(3, [int(x) for x in wl.idx[j]], [bytes(wl.shares[j, k]) for k in range(4)])
+        assert rc == 0 and bytes(sig[j].astype(np.uint8)) == want, j
+
+
 @pytest.mark.parametrize("config", [2, 5])
 def test_bench_under_the_launcher_runs_its_collectives_over_rccl(config):
     """The driver's multi-GPU command shape with the one GPU this box has: `python -m torch.distributed.run --nproc-per-node 1
@@ -329,7 +354,7 @@ def test_bench_under_the_launcher_runs_its_collectives_over_rccl(config):
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
-    extra = ["--batch", "8192", "--no-extras", "--sustain-seconds", "0.2"] if config == 2 else ["--config", "5", "--batch", "2048"]
+    extra = ["--batch", "8192", "--no-extras", "--sustain-seconds", "0.2", "--full"] if config == 2 else ["--config", "5", "--batch", "2048"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)

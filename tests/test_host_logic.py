@@ -388,7 +388,7 @@ def test_bench_gpus_2_starts_two_ranks_by_itself():
     device source standing in for the GPU (bench.py --test-engine: a test harness, marked in the line), and the line's
     n_gpus is the world size the ranks really joined."""
     out, lines = _run_bench("--gpus", "2", "--backend", "gloo", "--test-engine", "hostsim", "--batch", "3", "--t", "1", "--signers", "3",
-                            "--steps", "2", "--warmup", "1", "--no-cpu-baseline")
+                            "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full")
     assert out.returncode == 0, out.stderr[-3000:]
     assert len(lines) == 1                                    # ONE JSON line, rank 0's
     d = lines[0]
@@ -413,7 +413,7 @@ def test_bench_gpus_8_rank_logic_on_gloo():
     """The driver's largest shape, `bench.py --gpus 8`: eight ranks (gloo, host build) -- contiguous shards of the global job range, one
     record per rank gathered in rank order, counts summed over all eight, for config 2 and config 5."""
     out, lines = _run_bench("--gpus", "8", "--backend", "gloo", "--test-engine", "hostsim", "--batch", "2", "--t", "1", "--signers", "3",
-                            "--steps", "1", "--warmup", "0", "--no-cpu-baseline")
+                            "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--full")
     assert out.returncode == 0, out.stderr[-3000:]
     d = lines[0]
     assert len(lines) == 1 and d["n_gpus"] == 8 and d["ranks"]["devices"] == ["cpu:%d" % r for r in range(8)]
@@ -460,7 +460,7 @@ def test_bench_under_a_launcher_joins_the_rendezvous_even_as_the_only_rank():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(root, "bench.py"), "--gpus", "1", "--backend", "gloo", "--test-engine", "hostsim", "--batch", "3", "--t", "1", "--signers", "3",
-           "--steps", "1", "--warmup", "0", "--no-cpu-baseline"]
+           "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     import benchline
@@ -468,6 +468,59 @@ def test_bench_under_a_launcher_joins_the_rendezvous_even_as_the_only_rank():
     assert line["ranks"] == {"world_size": 1, "backend": "gloo", "rccl_version": None, "distinct_devices": 1, "launched_by": line["ranks"]["launched_by"]}
     assert d["n_gpus"] == 1 and d["ranks"]["backend"] == "gloo" and d["ranks"]["devices"] == ["cpu:0"]
     assert "external launcher" in d["ranks"]["launched_by"] and d["verified_all"] is True
+
+
+def test_plain_bench_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and carries the headline alone (no rooflines, legs or CPU baseline);
+    --dump-outputs writes what the last timed step returned -- the same arrays in every run of the same arguments, and the
+    combination of the seeded workload's jobs."""
+    dumps = []
+    for run in range(2):
+        d_out = str(tmp_path / ("run%d" % run))
+        out, lines = _run_bench("--gpus", "1", "--backend", "gloo", "--test-engine", "hostsim", "--batch", "3", "--t", "1", "--signers", "3",
+                                "--steps", "3", "--warmup", "1", "--dump-outputs", d_out)
+        assert out.returncode == 0, out.stderr[-3000:]
+        d = lines[0]
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["metric"] == "combine_signatures/sec" and d["unit"] == "combine_signatures/s"
+        assert d["higher_is_better"] is True and "i32 limbs" in d["dtype"] and abs(d["value"] - 3 / (d["ms_per_step"] * 1e-3)) / d["value"] < 0.01
+        assert d["roofline"] is None and d["cpu_baseline"] is None and out.compact["roofline"] is None
+        for k in ("streaming", "sustained", "general_path", "config3", "config4", "wire", "extras", "secondary_rooflines", "verified_all"):
+            assert k not in d, k
+        assert sorted(os.listdir(d_out)) == ["signatures.npy", "status.npy"]
+        dumps.append({k: np.load(os.path.join(d_out, k + ".npy")) for k in ("signatures", "status")})
+    sig, st = dumps[0]["signatures"], dumps[0]["status"]
+    assert sig.dtype == np.float32 and sig.shape == (3, 192) and st.dtype == np.float32 and st.shape == (3,) and not st.any()
+    assert all((dumps[1][k] == dumps[0][k]).all() for k in dumps[0])
+    eng = HostSimEngine()
+    wl = workload.ThresholdSigWorkload(eng, 1, 3, 3)
+    want, want_st = eng.combine_g2(1, wl.idx, wl.shares)
+    assert (sig == np.asarray(want, dtype=np.float32)).all() and not np.asarray(want_st).any()
+
+
+def test_bench_dump_keeps_a_seeded_sample_of_large_outputs(tmp_path):
+    """Above the size limit --dump-outputs keeps the same seeded sample of jobs of every array and writes their job numbers."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    bench.DUMP_LIMIT = 4000
+    sig = np.arange(100 * 12, dtype=np.uint8).reshape(100, 12)
+    st = np.arange(100, dtype=np.uint8) % 3
+    got = []
+    for run in range(2):
+        d_out = str(tmp_path / ("run%d" % run))
+        bench.dump_outputs(d_out, {"signatures": sig, "status": st})
+        got.append({k: np.load(os.path.join(d_out, k + ".npy")) for k in ("rows", "signatures", "status")})
+    rows = got[0]["rows"]
+    assert rows.dtype == np.float64 and 0 < len(rows) < 100 and (np.diff(rows) > 0).all()
+    assert len(rows) * (4 * 13 + 8) <= bench.DUMP_LIMIT
+    r = rows.astype(np.int64)
+    assert (got[0]["signatures"] == sig[r].astype(np.float32)).all() and (got[0]["status"] == st[r].astype(np.float32)).all()
+    assert all((got[1][k] == got[0][k]).all() for k in got[0])
+    bench.DUMP_LIMIT = 10 ** 6                     # small enough to keep whole: no stale row list is left behind
+    bench.dump_outputs(str(tmp_path / "run0"), {"signatures": sig, "status": st})
+    assert sorted(os.listdir(str(tmp_path / "run0"))) == ["signatures.npy", "status.npy"]
 
 
 def test_bench_refuses_more_gpus_than_the_node_has():
