@@ -1,0 +1,322 @@
+// Conformance ops: ONE shipped primitive of threshold_crypto_amd/csrc per op, applied to operands handed in as raw
+// signed limbs (14 x int32, radix 2^28, Montgomery R = 2^392), so that lazy, non-canonical representations reach the
+// primitive exactly as the caller built them and the output representation can be checked, not only its residue.
+//
+// Written once as TC_HD code: tests/device/conformance.hip compiles it with hipcc for gfx950 (the lane-pair Fq2 of the
+// product, TC_PAIR = 1), tests/device_conformance.py compiles it with g++ -DTC_BOUND_CHECK (the host Fq2, with the
+// declared input intervals loaded into the interval bookkeeping).  Test code only: never part of libtc_amd.so.
+//
+// Per job:  in    CONF_IN  Fq slots (14 limbs each; a canonical integer in 12 u32 words, or 13 x 30-bit limbs, where an
+//                  op says so)
+//           aux   CONF_AUX int32 parameters (point-at-infinity flags, the Frobenius power, "also compare")
+//           out   CONF_OUT Fq slots
+//           flags CONF_FLAGS int32: slots [0, 4) written by the job's first lane, [4, 8) by its second lane (lane-pair
+//                  ops; the one-lane and host forms write both halves), so a pair that disagrees on a predicate shows
+//           range CONF_IN x {lo, hi, val}: the declared interval of every input slot (units of 2^28 for limbs, of p for
+//                  the value), read by the bound-check build only
+#pragma once
+#include "../../threshold_crypto_amd/csrc/tc_pairing.h"
+#include "../../threshold_crypto_amd/csrc/tc_sqrt.h"
+
+namespace tc {
+namespace conf {
+
+constexpr int CONF_IN = 24, CONF_OUT = 36, CONF_AUX = 4, CONF_FLAGS = 8;
+
+enum Op {
+  // Fq, one lane per job
+  FQ_MUL = 0, FQ_SQR, FQ_REDC_FULL, FQ_FROM_CANONICAL, FQ_TO_CANONICAL, FQ_FROM_MONT384, FQ_GT_HALF, FQ_NORM,
+  FQ_REDUCE_VALUE, FQ_ZERO, FQ_INV, FQ_INV_FERMAT, FQ_INV30, FQ_LEGENDRE, FQ_SQRT,
+  // Fq2 (lane pair on the device)
+  FQ2_MUL = 20, FQ2_SQR, FQ2_CONJ, FQ2_MUL_XI, FQ2_NORM_FQ, FQ2_INV, FQ2_ZERO, FQ2_SQRT, FQ2_SQRT_X2, FQ2_INV_X2,
+  // Fq6 / Fq12 (lane pair)
+  FQ6_MUL = 40, FQ6_SQR, FQ6_INV, FQ12_MUL, FQ12_SQR, FQ12_INV, FQ12_FROB, FQ12_CONJ, FQ12_LINE_PRODUCT,
+  FQ12_CYCLO_SQR, CYCLO_CHAIN,
+  // G1, one lane per job
+  G1_DBL = 60, G1_ADD_MIXED, G1_ADD, G1_ADD_MIXED_GENERIC, G1_ADD_GENERIC, G1_TO_AFFINE, G1_ON_CURVE, G1_IN_SUBGROUP,
+  // G2 (lane pair)
+  G2_DBL = 70, G2_ADD_MIXED, G2_ADD, G2_ADD_MIXED_GENERIC, G2_ADD_GENERIC, G2_TO_AFFINE, G2_TO_AFFINE_X2, G2_ON_CURVE,
+  G2_IN_SUBGROUP, G2_PSI,
+};
+
+// lanes per job on the device: Fq and G1 ops one, everything that holds Fq2 values a lane pair
+TC_HD constexpr int conf_lanes(int op) { return (op >= FQ2_MUL && op < G1_DBL) || op >= G2_DBL ? kG2Lanes : 1; }
+
+struct Ctx {
+  const int32_t* in;
+  const int32_t* aux;
+  int32_t* out;
+  int32_t* flags;
+  const float* range;  // bound-check build: declared input intervals
+  bool live;           // a real job (lanes past the end of the batch run a copy of the last job and store nothing)
+  int lane;            // 0 / 1 within the job's lanes
+  bool pair;           // the job runs on a lane pair
+
+  TC_HD Fq fq(int s) const {
+    Fq r;
+    TC_UNROLL for (int i = 0; i < FQ_LIMBS; i++) r.l[i] = in[s * FQ_LIMBS + i];
+#if defined(TC_BOUND_CHECK)
+    r.set_range(range[3 * s], range[3 * s + 1]);
+    r.set_val(range[3 * s + 2]);
+#endif
+    return r;
+  }
+  TC_HD Fq2 fq2(int s) const { return Fq2::make(fq(s), fq(s + 1)); }
+  TC_HD Fq6 fq6(int s) const { return Fq6{fq2(s), fq2(s + 2), fq2(s + 4)}; }
+  TC_HD Fq12 fq12(int s) const { return Fq12{fq6(s), fq6(s + 6)}; }
+  template <class F>
+  TC_HD F field(int s) const;
+  TC_HD const uint32_t* words(int s) const { return (const uint32_t*)(in + s * FQ_LIMBS); }
+
+  TC_HD bool writer() const { return live && lane == 0; }
+  TC_HD void put_raw(int s, const int32_t* v, int n) {
+    if (writer()) TC_UNROLL for (int i = 0; i < n; i++) out[s * FQ_LIMBS + i] = v[i];
+  }
+  TC_HD void put(int s, const Fq& v) { put_raw(s, v.l, FQ_LIMBS); }
+  // (both coefficients are gathered by both lanes first: re() / im() exchange values over the pair)
+  TC_HD void put(int s, const Fq2& v) {
+    const Fq re = v.re(), im = v.im();
+    put(s, re);
+    put(s + 1, im);
+  }
+  TC_HD void put(int s, const Fq6& v) {
+    put(s, v.c0);
+    put(s + 2, v.c1);
+    put(s + 4, v.c2);
+  }
+  TC_HD void put(int s, const Fq12& v) {
+    put(s, v.c0);
+    put(s + 6, v.c1);
+  }
+  TC_HD void flag(int i, int v) {
+    if (!live) return;
+    flags[lane * 4 + i] = v;
+    if (!pair) flags[4 + i] = v;
+  }
+};
+template <>
+TC_HD Fq Ctx::field<Fq>(int s) const { return fq(s); }
+template <>
+TC_HD Fq2 Ctx::field<Fq2>(int s) const { return fq2(s); }
+
+// coordinates per field element: 1 slot (Fq) or 2 (Fq2)
+template <class F>
+struct Width;
+template <>
+struct Width<Fq> { static constexpr int n = 1; };
+template <>
+struct Width<Fq2> { static constexpr int n = 2; };
+
+template <class F>
+TC_HD Jac<F> jac_at(const Ctx& c, int s) {
+  constexpr int w = Width<F>::n;
+  return Jac<F>{c.field<F>(s), c.field<F>(s + w), c.field<F>(s + 2 * w)};
+}
+template <class F>
+TC_HD Affine<F> aff_at(const Ctx& c, int s, int inf) {
+  constexpr int w = Width<F>::n;
+  return Affine<F>{c.field<F>(s), c.field<F>(s + w), inf != 0};
+}
+template <class F>
+TC_HD void put_jac(Ctx& c, int s, const Jac<F>& p) {
+  constexpr int w = Width<F>::n;
+  c.put(s, p.x);
+  c.put(s + w, p.y);
+  c.put(s + 2 * w, p.z);
+}
+template <class F>
+TC_HD void put_aff(Ctx& c, int s, const Affine<F>& p) {
+  constexpr int w = Width<F>::n;
+  c.put(s, p.x);
+  c.put(s + w, p.y);
+}
+
+template <class F>
+TC_HD F curve_b();
+template <>
+TC_HD Fq curve_b<Fq>() { return g1_b(); }
+template <>
+TC_HD Fq2 curve_b<Fq2>() { return g2_b(); }
+
+// the group ops, for F = Fq (G1) and F = Fq2 (G2): slots P = [0, 3w), Q = [3w, 6w) (affine Q: [3w, 5w), aux[0] = Q at infinity)
+template <class F, int K>
+TC_HD void conf_curve(Ctx& c) {
+  constexpr int w = Width<F>::n;
+  if constexpr (K == 0) {
+    put_jac(c, 0, jac_dbl(jac_at<F>(c, 0)));
+  } else if constexpr (K == 1) {
+    put_jac(c, 0, jac_add_mixed(jac_at<F>(c, 0), aff_at<F>(c, 3 * w, c.aux[0])));
+  } else if constexpr (K == 2) {
+    put_jac(c, 0, jac_add(jac_at<F>(c, 0), jac_at<F>(c, 3 * w)));
+  } else if constexpr (K == 3) {
+    bool exc = false;
+    const Jac<F> r = jac_add_mixed_generic(jac_at<F>(c, 0), aff_at<F>(c, 3 * w, c.aux[0]), exc);
+    put_jac(c, 0, r);
+    c.flag(0, exc);
+  } else if constexpr (K == 4) {
+    bool exc = false;
+    const Jac<F> r = jac_add_generic(jac_at<F>(c, 0), jac_at<F>(c, 3 * w), exc);
+    put_jac(c, 0, r);
+    c.flag(0, exc);
+  } else if constexpr (K == 5) {
+    const Affine<F> a = jac_to_affine(jac_at<F>(c, 0));
+    put_aff(c, 0, a);
+    c.flag(0, a.inf);
+  } else if constexpr (K == 6) {
+    c.flag(0, affine_on_curve(aff_at<F>(c, 0, c.aux[0]), curve_b<F>()));
+  }
+}
+
+template <int OP>
+TC_HD void conf_op(Ctx& c) {
+  // ---- Fq ---------------------------------------------------------------------------------------------------------
+  if constexpr (OP == FQ_MUL) {
+    c.put(0, c.fq(0) * c.fq(1));
+  } else if constexpr (OP == FQ_SQR) {
+    c.put(0, c.fq(0).sqr());
+  } else if constexpr (OP == FQ_REDC_FULL) {
+    int32_t t[FQ_LIMBS];
+    fq_redc_full(c.fq(0), t);
+    c.put_raw(0, t, FQ_LIMBS);
+  } else if constexpr (OP == FQ_FROM_CANONICAL) {
+    c.put(0, Fq::from_canonical(c.words(0)));
+  } else if constexpr (OP == FQ_TO_CANONICAL) {
+    uint32_t w[12];
+    c.fq(0).to_canonical(w);
+    c.put_raw(0, (const int32_t*)w, 12);
+  } else if constexpr (OP == FQ_FROM_MONT384) {
+    c.put(0, Fq::from_mont384(c.words(0)));
+  } else if constexpr (OP == FQ_GT_HALF) {
+    c.flag(0, fq_canonical_gt_half(c.words(0)));
+  } else if constexpr (OP == FQ_NORM) {
+    c.put(0, c.fq(0).norm());
+  } else if constexpr (OP == FQ_REDUCE_VALUE) {
+    c.put(0, c.fq(0).reduce_value());
+  } else if constexpr (OP == FQ_ZERO) {
+    const Fq a = c.fq(0), b = c.fq(1);
+    c.flag(0, a.maybe_zero());
+    c.flag(1, a.maybe_zero56());
+    c.flag(2, a.is_zero());
+    if (c.aux[0]) c.flag(3, a == b);  // (only where a - b is inside the input contract)
+  } else if constexpr (OP == FQ_INV) {
+    c.put(0, c.fq(0).inv());
+  } else if constexpr (OP == FQ_INV_FERMAT) {
+    c.put(0, fq_inv_fermat(c.fq(0)));
+  } else if constexpr (OP == FQ_INV30) {
+    int32_t r[FQ_INV_LIMBS];
+    fq_inv_limbs30(c.in, r);
+    c.put_raw(0, r, FQ_INV_LIMBS);
+  } else if constexpr (OP == FQ_LEGENDRE) {
+    c.flag(0, fq_legendre(c.fq(0)));
+  } else if constexpr (OP == FQ_SQRT) {
+    Fq root, inv_root;
+    const bool ok = fq_sqrt(c.fq(0), root, &inv_root);
+    c.put(0, root);
+    c.put(1, inv_root);
+    c.flag(0, ok);
+  // ---- Fq2 --------------------------------------------------------------------------------------------------------
+  } else if constexpr (OP == FQ2_MUL) {
+    c.put(0, c.fq2(0) * c.fq2(2));
+  } else if constexpr (OP == FQ2_SQR) {
+    c.put(0, c.fq2(0).sqr());
+  } else if constexpr (OP == FQ2_CONJ) {
+    c.put(0, c.fq2(0).conj());
+  } else if constexpr (OP == FQ2_MUL_XI) {
+    c.put(0, c.fq2(0).mul_xi());
+  } else if constexpr (OP == FQ2_NORM_FQ) {
+    c.put(0, c.fq2(0).norm_fq());
+  } else if constexpr (OP == FQ2_INV) {
+    c.put(0, c.fq2(0).inv());
+  } else if constexpr (OP == FQ2_ZERO) {
+    const Fq2 a = c.fq2(0), b = c.fq2(2);
+    c.flag(0, a.is_zero());
+    c.flag(1, maybe_zero56(a));
+    if (c.aux[0]) c.flag(2, a == b);
+  } else if constexpr (OP == FQ2_SQRT) {
+    const Fq2 a = c.fq2(0);
+    Fq2 r = Fq2::zero();
+    c.flag(1, fq2_is_square(a, a.norm_fq()));
+    const bool ok = fq2_sqrt(a, r);
+    c.put(0, r);
+    c.flag(0, ok);
+  } else if constexpr (OP == FQ2_SQRT_X2) {
+    Fq2 ya, yb;
+    bool oka, okb;
+    fq2_sqrt_x2(c.fq2(0), c.fq2(2), ya, yb, oka, okb);
+    c.put(0, ya);
+    c.put(2, yb);
+    c.flag(0, oka);
+    c.flag(1, okb);
+  } else if constexpr (OP == FQ2_INV_X2) {
+    Fq2 ia, ib;
+    fq2_inv_x2(c.fq2(0), c.fq2(2), ia, ib);
+    c.put(0, ia);
+    c.put(2, ib);
+  // ---- Fq6 / Fq12 -------------------------------------------------------------------------------------------------
+  } else if constexpr (OP == FQ6_MUL) {
+    c.put(0, c.fq6(0) * c.fq6(6));
+  } else if constexpr (OP == FQ6_SQR) {
+    c.put(0, c.fq6(0).sqr());
+  } else if constexpr (OP == FQ6_INV) {
+    c.put(0, c.fq6(0).inv());
+  } else if constexpr (OP == FQ12_MUL) {
+    c.put(0, c.fq12(0) * c.fq12(12));
+  } else if constexpr (OP == FQ12_SQR) {
+    c.put(0, c.fq12(0).sqr());
+  } else if constexpr (OP == FQ12_INV) {
+    c.put(0, c.fq12(0).inv());
+  } else if constexpr (OP == FQ12_FROB) {
+    c.put(0, c.fq12(0).frobenius(c.aux[0]));
+  } else if constexpr (OP == FQ12_CONJ) {
+    c.put(0, c.fq12(0).conj());
+  } else if constexpr (OP == FQ12_LINE_PRODUCT) {
+    c.put(0, Fq12::line_product(c.fq2(0), c.fq2(2), c.fq2(4), c.fq2(6), c.fq2(8), c.fq2(10)));
+  } else if constexpr (OP == FQ12_CYCLO_SQR) {
+    c.put(0, c.fq12(0).cyclotomic_sqr());
+  } else if constexpr (OP == CYCLO_CHAIN) {
+    // three compressed elements (z2, z3, z4, z5 at slots 8 i), kCycloReduceEvery squarings each -- the last one reducing,
+    // as in the chain of cyclotomic_exp_by_x --, then decompressed together
+    CycloCompressed z[3];
+    TC_UNROLL for (int i = 0; i < 3; i++) {
+      CycloCompressed t{c.fq2(8 * i), c.fq2(8 * i + 2), c.fq2(8 * i + 4), c.fq2(8 * i + 6)};
+      TC_NOUNROLL for (int s = 0; s < kCycloReduceEvery - 1; s++) t = t.sqr_t<false>();
+      z[i] = t.sqr_t<true>();
+    }
+    Fq12 f[3];
+    cyclotomic_decompress3(z, f);
+    TC_UNROLL for (int i = 0; i < 3; i++) c.put(12 * i, f[i]);
+  // ---- G1 / G2 ----------------------------------------------------------------------------------------------------
+  } else if constexpr (OP >= G1_DBL && OP <= G1_ON_CURVE) {
+    conf_curve<Fq, OP - G1_DBL>(c);
+  } else if constexpr (OP == G1_IN_SUBGROUP) {
+    c.flag(0, g1_in_subgroup(aff_at<Fq>(c, 0, c.aux[0])));
+  } else if constexpr (OP >= G2_DBL && OP <= G2_TO_AFFINE) {
+    conf_curve<Fq2, OP - G2_DBL>(c);
+  } else if constexpr (OP == G2_TO_AFFINE_X2) {
+    G2Affine pa, qa;
+    jac_to_affine_x2(jac_at<Fq2>(c, 0), jac_at<Fq2>(c, 6), pa, qa);
+    put_aff(c, 0, pa);
+    put_aff(c, 4, qa);
+    c.flag(0, pa.inf);
+    c.flag(1, qa.inf);
+  } else if constexpr (OP == G2_ON_CURVE) {
+    conf_curve<Fq2, 6>(c);
+  } else if constexpr (OP == G2_IN_SUBGROUP) {
+    c.flag(0, g2_in_subgroup(aff_at<Fq2>(c, 0, c.aux[0])));
+  } else if constexpr (OP == G2_PSI) {
+    put_aff(c, 0, g2_psi(aff_at<Fq2>(c, 0, c.aux[0])));
+  }
+}
+
+// every op, for the launchers' switch
+#define TC_CONF_OPS(X)                                                                                                  \
+  X(FQ_MUL) X(FQ_SQR) X(FQ_REDC_FULL) X(FQ_FROM_CANONICAL) X(FQ_TO_CANONICAL) X(FQ_FROM_MONT384) X(FQ_GT_HALF)          \
+  X(FQ_NORM) X(FQ_REDUCE_VALUE) X(FQ_ZERO) X(FQ_INV) X(FQ_INV_FERMAT) X(FQ_INV30) X(FQ_LEGENDRE) X(FQ_SQRT)            \
+  X(FQ2_MUL) X(FQ2_SQR) X(FQ2_CONJ) X(FQ2_MUL_XI) X(FQ2_NORM_FQ) X(FQ2_INV) X(FQ2_ZERO) X(FQ2_SQRT) X(FQ2_SQRT_X2)     \
+  X(FQ2_INV_X2) X(FQ6_MUL) X(FQ6_SQR) X(FQ6_INV) X(FQ12_MUL) X(FQ12_SQR) X(FQ12_INV) X(FQ12_FROB) X(FQ12_CONJ)         \
+  X(FQ12_LINE_PRODUCT) X(FQ12_CYCLO_SQR) X(CYCLO_CHAIN) X(G1_DBL) X(G1_ADD_MIXED) X(G1_ADD) X(G1_ADD_MIXED_GENERIC)    \
+  X(G1_ADD_GENERIC) X(G1_TO_AFFINE) X(G1_ON_CURVE) X(G1_IN_SUBGROUP) X(G2_DBL) X(G2_ADD_MIXED) X(G2_ADD)               \
+  X(G2_ADD_MIXED_GENERIC) X(G2_ADD_GENERIC) X(G2_TO_AFFINE) X(G2_TO_AFFINE_X2) X(G2_ON_CURVE) X(G2_IN_SUBGROUP) X(G2_PSI)
+
+}  // namespace conf
+}  // namespace tc

@@ -1,0 +1,68 @@
+// Device conformance kernels (test code only: never linked into libtc_amd.so, never run by bench.py).
+// One kernel per op of conformance.h, each applying one shipped primitive of threshold_crypto_amd/csrc as the product
+// compiles it (gfx950, the product's flags, lane-pair Fq2), in 64-lane workgroups like the product's kernels.
+//   build: tests/device_conformance.py (hipcc, keyed by a hash of the sources)
+#include <hip/hip_runtime.h>
+#include "conformance.h"
+
+using namespace tc;
+using namespace tc::conf;
+
+constexpr int kBlock = 64;
+
+template <int OP>
+__global__ __launch_bounds__(kBlock) void k_conf(const int32_t* in, const int32_t* aux, int32_t* out, int32_t* flags, int n) {
+  constexpr int lanes = conf_lanes(OP);
+  const int t = blockIdx.x * kBlock + threadIdx.x;
+  int job = t / lanes;
+  const bool live = job < n;
+  if (!live) job = n - 1;  // lanes past the end run a copy of the last job (the pair exchanges and ballots need every lane)
+  Ctx c{in + (size_t)job * CONF_IN * FQ_LIMBS, aux + (size_t)job * CONF_AUX, out + (size_t)job * CONF_OUT * FQ_LIMBS,
+        flags + (size_t)job * CONF_FLAGS, nullptr, live, t % lanes, lanes == 2};
+  conf_op<OP>(c);
+}
+
+template <int OP>
+static hipError_t launch(const int32_t* in, const int32_t* aux, int32_t* out, int32_t* flags, int n) {
+  const int threads = n * conf_lanes(OP);
+  hipLaunchKernelGGL(k_conf<OP>, dim3((threads + kBlock - 1) / kBlock), dim3(kBlock), 0, 0, in, aux, out, flags, n);
+  return hipGetLastError();
+}
+
+static hipError_t dispatch(int op, const int32_t* in, const int32_t* aux, int32_t* out, int32_t* flags, int n) {
+  switch (op) {
+#define TC_CONF_CASE(name) \
+  case name:               \
+    return launch<name>(in, aux, out, flags, n);
+    TC_CONF_OPS(TC_CONF_CASE)
+#undef TC_CONF_CASE
+  }
+  return hipErrorInvalidValue;
+}
+
+// n jobs of op `op` on the current device.  Host buffers in (n x CONF_IN x 14), aux (n x CONF_AUX), out (n x CONF_OUT x 14)
+// and flags (n x CONF_FLAGS); out and flags are copied in first, so entries an op does not write keep the caller's value.
+// Returns the first HIP error (hipSuccess = 0).
+extern "C" int tc_conf_run(int op, int n, const int32_t* in, const int32_t* aux, int32_t* out, int32_t* flags) {
+  if (n <= 0) return (int)hipErrorInvalidValue;
+  const size_t sin = (size_t)n * CONF_IN * FQ_LIMBS * 4, saux = (size_t)n * CONF_AUX * 4;
+  const size_t sout = (size_t)n * CONF_OUT * FQ_LIMBS * 4, sfl = (size_t)n * CONF_FLAGS * 4;
+  int32_t *din = nullptr, *daux = nullptr, *dout = nullptr, *dfl = nullptr;
+  hipError_t e = hipMalloc(&din, sin);
+  if (e == hipSuccess) e = hipMalloc(&daux, saux);
+  if (e == hipSuccess) e = hipMalloc(&dout, sout);
+  if (e == hipSuccess) e = hipMalloc(&dfl, sfl);
+  if (e == hipSuccess) e = hipMemcpy(din, in, sin, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(daux, aux, saux, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dout, out, sout, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dfl, flags, sfl, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = dispatch(op, din, daux, dout, dfl, n);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(out, dout, sout, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(flags, dfl, sfl, hipMemcpyDeviceToHost);
+  hipFree(din);
+  hipFree(daux);
+  hipFree(dout);
+  hipFree(dfl);
+  return (int)e;
+}

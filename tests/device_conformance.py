@@ -1,0 +1,1437 @@
+"""Device conformance suite: builders, operand generator, references and case tables.
+
+tests/device/conformance.h applies ONE shipped primitive of threshold_crypto_amd/csrc per op to operands given as raw
+signed limbs (14 x int32, radix 2^28, Montgomery R = 2^392).  The same case tables run through
+
+  * the gfx950 build (tests/device/conformance.hip, hipcc with the product's flags): tests/test_gpu_conformance.py, and
+  * the host build (tests/device/conformance_host.cpp, g++ -DTC_BOUND_CHECK, the declared input intervals loaded into the
+    interval bookkeeping): tests/test_conformance_host.py, in a child process per op (a bound violation aborts it).
+
+Every result is compared with Python big integers (oracle/tc_oracle.py) AND checked against the primitive's output
+contract (limb ranges, value bound), which is what the next operation relies on.
+
+    python tests/device_conformance.py host OPNAME      (the host leg of one op; exit status 0 = every case passed)
+"""
+import ctypes
+import hashlib
+import os
+import random
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, ROOT)
+import tc_oracle as o  # noqa: E402
+
+DEV = os.path.join(HERE, "device")
+CSRC = os.path.join(ROOT, "threshold_crypto_amd", "csrc")
+BUILD = os.path.join(DEV, "_build")
+
+P = o.Q
+RB = 28
+NL = 14
+MASK = (1 << RB) - 1
+RM = 1 << 392  # Montgomery R
+RINV = pow(RM, -1, P)
+CONF_IN, CONF_OUT, CONF_AUX, CONF_FLAGS = 24, 36, 4, 8
+# input contract of the primitives (tc_field.h): |limb| <= 7.9 * 2^28, |value| <= 300 p, B_a * B_b <= 8.14 at a product
+LIMB_MAX = 7.9
+VAL_MAX = 300
+PRODUCT_MAX = 8.14
+NORM_LO, NORM_HI = -0.001, 1.001  # the limb interval of norm() / reduce_value() / point coordinates (units of 2^28)
+CYCLO_REDUCE_EVERY = 3  # tc_tower.h kCycloReduceEvery (the product builds with the default)
+
+# op ids: tests/device/conformance.h enum Op
+OPS = dict(
+    FQ_MUL=0, FQ_SQR=1, FQ_REDC_FULL=2, FQ_FROM_CANONICAL=3, FQ_TO_CANONICAL=4, FQ_FROM_MONT384=5, FQ_GT_HALF=6, FQ_NORM=7,
+    FQ_REDUCE_VALUE=8, FQ_ZERO=9, FQ_INV=10, FQ_INV_FERMAT=11, FQ_INV30=12, FQ_LEGENDRE=13, FQ_SQRT=14,
+    FQ2_MUL=20, FQ2_SQR=21, FQ2_CONJ=22, FQ2_MUL_XI=23, FQ2_NORM_FQ=24, FQ2_INV=25, FQ2_ZERO=26, FQ2_SQRT=27, FQ2_SQRT_X2=28,
+    FQ2_INV_X2=29,
+    FQ6_MUL=40, FQ6_SQR=41, FQ6_INV=42, FQ12_MUL=43, FQ12_SQR=44, FQ12_INV=45, FQ12_FROB=46, FQ12_CONJ=47,
+    FQ12_LINE_PRODUCT=48, FQ12_CYCLO_SQR=49, CYCLO_CHAIN=50,
+    G1_DBL=60, G1_ADD_MIXED=61, G1_ADD=62, G1_ADD_MIXED_GENERIC=63, G1_ADD_GENERIC=64, G1_TO_AFFINE=65, G1_ON_CURVE=66,
+    G1_IN_SUBGROUP=67,
+    G2_DBL=70, G2_ADD_MIXED=71, G2_ADD=72, G2_ADD_MIXED_GENERIC=73, G2_ADD_GENERIC=74, G2_TO_AFFINE=75, G2_TO_AFFINE_X2=76,
+    G2_ON_CURVE=77, G2_IN_SUBGROUP=78, G2_PSI=79)
+
+
+def lanes(op):
+    i = OPS[op]
+    return 2 if (20 <= i < 60 or i >= 70) else 1
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# builds
+# ---------------------------------------------------------------------------------------------------------------------
+def _digest(extra, srcs):
+    h = hashlib.sha256()
+    for d in (CSRC, DEV):
+        for name in sorted(os.listdir(d)):
+            if name.endswith((".h", ".hip", ".cpp")) and (d == CSRC or name in srcs or name.endswith(".h")):
+                with open(os.path.join(d, name), "rb") as f:
+                    h.update(name.encode())
+                    h.update(f.read())
+    h.update(" ".join(extra).encode())
+    return h.hexdigest()[:16]
+
+
+def _build(name, cmd_of, srcs):
+    os.makedirs(BUILD, exist_ok=True)
+    probe = cmd_of("X")
+    lib = os.path.join(BUILD, "%s-%s.so" % (name, _digest(probe, srcs)))
+    if not os.path.exists(lib):
+        subprocess.run(cmd_of(lib + ".tmp"), check=True, timeout=900)
+        os.replace(lib + ".tmp", lib)
+        for old in os.listdir(BUILD):  # stale builds of earlier sources
+            if old.startswith(name + "-") and old != os.path.basename(lib):
+                os.remove(os.path.join(BUILD, old))
+    return lib
+
+
+def hipcc():
+    for cand in (os.environ.get("HIPCC"), shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
+        if cand and os.path.exists(cand):
+            return cand
+    raise RuntimeError("hipcc not found")
+
+
+def build_device():
+    """tests/device/conformance.hip -> a gfx950 shared object, with the product's compiler flags (build.py FLAGS)."""
+    from threshold_crypto_amd import build as tcb
+    src = os.path.join(DEV, "conformance.hip")
+    return _build("libtc_conformance", lambda out: [hipcc()] + tcb.FLAGS + ["-w", "-shared", src, "-o", out], {"conformance.hip"})
+
+
+def build_host():
+    """The same op bodies for the host (host Fq2 form), under the interval analysis."""
+    src = os.path.join(DEV, "conformance_host.cpp")
+    return _build("libtc_conformance_host_bc",
+                  lambda out: ["g++", "-O1", "-std=c++17", "-w", "-DTC_BOUND_CHECK", "-shared", "-fPIC", src, "-o", out],
+                  {"conformance_host.cpp"})
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# operands
+# ---------------------------------------------------------------------------------------------------------------------
+def value(limbs):
+    """The integer a limb vector holds (limb i has weight 2^(28 i); limbs are signed)."""
+    return sum(int(x) << (RB * i) for i, x in enumerate(limbs))
+
+
+def residue(limbs):
+    """The field element a Montgomery representation stands for."""
+    return value(limbs) * RINV % P
+
+
+def mont(v):
+    return v * RM % P
+
+
+class Operand:
+    """One input slot: raw limbs plus the interval declared for them (lo, hi in units of 2^28; val: |value| <= val * p)."""
+
+    def __init__(self, limbs, lo, hi, val):
+        self.limbs, self.lo, self.hi, self.val = list(limbs), lo, hi, val
+
+    @property
+    def bound(self):
+        return max(-self.lo, self.hi)
+
+
+def encode(v, k=0, interval=(0.0, 1.0), push=None):
+    """Limbs whose integer is  v R mod p + k p,  inside `interval` (units of 2^28).  push: None (plain digits), "hi" / "lo"
+    (every limb moved toward that end of the interval by borrowing from its upper neighbour) or "alt" (alternating).
+    The result is checked against the input contract before anything is launched."""
+    x = mont(v % P) + k * P
+    lo, hi = interval
+    LO, HI = int(lo * (1 << RB)), int(hi * (1 << RB))
+    l = [(x >> (RB * i)) & MASK for i in range(NL - 1)] + [x >> (RB * (NL - 1))]
+    if hi < 1.0:  # balanced digits in [-2^27, 2^27) first
+        for i in range(NL - 1):
+            if l[i] >= 1 << (RB - 1):
+                l[i] -= 1 << RB
+                l[i + 1] += 1
+    if push:
+        for i in range(NL - 1):
+            up = push == "hi" or (push == "alt" and i % 2 == 0)
+            if up:
+                c = (HI - l[i]) >> RB
+                if c > 0:
+                    l[i] += c << RB
+                    l[i + 1] -= c
+            else:
+                c = (l[i] - LO) >> RB
+                if c > 0:
+                    l[i] -= c << RB
+                    l[i + 1] += c
+    assert value(l) == x
+    val = max(1, -(-abs(x) // P))
+    op = Operand(l, lo, hi, val)
+    check_input(op)
+    return op
+
+
+def encode_int(x, interval=(0.0, 1.0)):
+    """Plain digits of an integer (not a Montgomery form): the representative p of zero, R itself, ..."""
+    l = [(x >> (RB * i)) & MASK for i in range(NL - 1)] + [x >> (RB * (NL - 1))]
+    op = Operand(l, interval[0], interval[1], max(1, -(-abs(x) // P)))
+    check_input(op)
+    return op
+
+
+def check_input(op):
+    """The documented input contract (tc_field.h): every limb inside its declared interval, |limb| <= 7.9 * 2^28,
+    |value| <= 300 p.  A case that violates it is a bug of the test, never a finding."""
+    lo, hi = op.lo * (1 << RB), op.hi * (1 << RB)
+    assert -LIMB_MAX <= op.lo <= op.hi <= LIMB_MAX, (op.lo, op.hi)
+    assert all(lo <= x <= hi for x in op.limbs), ("limb outside its interval", op.lo, op.hi, op.limbs)
+    assert all(-2 ** 31 <= x < 2 ** 31 for x in op.limbs)
+    assert abs(value(op.limbs)) <= op.val * P and op.val <= VAL_MAX, op.val
+
+
+def check_product_operands(a, b):
+    assert a.bound * b.bound <= PRODUCT_MAX, ("operands beyond the column limit", a.bound, b.bound)
+
+
+def words(x):
+    """A canonical integer as the 12 little-endian u32 words the codecs use (in the first 12 ints of a slot)."""
+    w = [(x >> (32 * i)) & 0xffffffff for i in range(12)]
+    return Operand([c - (1 << 32) if c >= 1 << 31 else c for c in w] + [0, 0], 0, 1, 1)
+
+
+def words_value(op):
+    return sum((int(c) & 0xffffffff) << (32 * i) for i, c in enumerate(op.limbs[:12]))
+
+
+def limbs30(x):
+    return Operand([(x >> (30 * i)) & ((1 << 30) - 1) for i in range(13)] + [0], 0, 4, 1)
+
+
+class Case:
+    def __init__(self, slots, aux=(), tag=""):
+        self.slots, self.aux, self.tag = slots, list(aux), tag
+
+
+def eq_ok(a, b):
+    """a - b (the first step of a == b) inside the input contract: declared limb intervals and value bound."""
+    return a.lo - b.hi >= -LIMB_MAX and a.hi - b.lo <= LIMB_MAX and a.val + b.val <= VAL_MAX
+
+
+def zero_case(slots, tag, eq_pairs):
+    return Case(slots, aux=[int(all(eq_ok(slots[i], slots[j]) for i, j in eq_pairs))], tag=tag)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# launching
+# ---------------------------------------------------------------------------------------------------------------------
+SENTINEL = 0x5A5A5A5A
+FLAG_SENTINEL = -77
+
+
+def pack(cases):
+    n = len(cases)
+    inp = np.zeros((n, CONF_IN, NL), np.int32)
+    rng = np.zeros((n, CONF_IN, 3), np.float32)
+    rng[:, :, 1] = 1.0
+    rng[:, :, 2] = 1.0
+    aux = np.zeros((n, CONF_AUX), np.int32)
+    for j, c in enumerate(cases):
+        for s, op in enumerate(c.slots):
+            inp[j, s] = op.limbs
+            rng[j, s] = (op.lo, op.hi, op.val)
+        aux[j, :len(c.aux)] = c.aux
+    out = np.full((n, CONF_OUT, NL), SENTINEL, np.int32)
+    flags = np.full((n, CONF_FLAGS), FLAG_SENTINEL, np.int32)
+    return inp, rng, aux, out, flags
+
+
+def _p(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def run_device(lib, op, cases):
+    inp, _, aux, out, flags = pack(cases)
+    rc = lib.tc_conf_run(OPS[op], len(cases), _p(inp), _p(aux), _p(out), _p(flags))
+    assert rc == 0, "HIP error %d in op %s" % (rc, op)
+    return out, flags
+
+
+def run_host(lib, op, cases):
+    inp, rng, aux, out, flags = pack(cases)
+    rc = lib.tc_conf_host_run(OPS[op], len(cases), _p(inp), _p(rng), _p(aux), _p(out), _p(flags))
+    assert rc == 0
+    return out, flags
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# output contracts
+# ---------------------------------------------------------------------------------------------------------------------
+class Fail(AssertionError):
+    pass
+
+
+def expect(cond, case, what):
+    if not cond:
+        raise Fail("%s [case %s]" % (what, case.tag))
+
+
+def out_limbs(out, s):
+    return [int(x) for x in out[s]]
+
+
+def check_carried(case, l, what):
+    """A product's / redc's output: limbs 0..12 fully carried into [0, 2^28), the top limb holds the rest."""
+    expect(all(0 <= x <= MASK for x in l[:NL - 1]), case, "%s: limbs not carried %s" % (what, l))
+
+
+def check_product(case, l, x, what="product"):
+    """The Montgomery product's contract: out = (x + m p) / R exactly, with 0 <= m < R (so the value lies in
+    (x / R, x / R + p)), limbs carried."""
+    check_carried(case, l, what)
+    t = value(l) * RM - x
+    expect(t % P == 0 and 0 <= t // P < RM, case, "%s: out R - x = %s p is not m p with 0 <= m < R" % (what, t / P))
+
+
+def check_normed(case, l, what, val_bound=VAL_MAX, lo=NORM_LO, hi=NORM_HI):
+    L, H = lo * (1 << RB), hi * (1 << RB)
+    expect(all(L <= x <= H for x in l[:NL - 1]), case, "%s: limbs outside [%g, %g] 2^28: %s" % (what, lo, hi, l))
+    expect(abs(l[NL - 1]) <= max(-L, H), case, "%s: top limb %d" % (what, l[NL - 1]))
+    expect(abs(value(l)) <= val_bound * P, case, "%s: |value| = %.3f p > %g p" % (what, abs(value(l)) / P, val_bound))
+
+
+def f2_res(out, s):
+    return (residue(out[s]), residue(out[s + 1]))
+
+
+def f6_res(out, s):
+    return (f2_res(out, s), f2_res(out, s + 2), f2_res(out, s + 4))
+
+
+def f12_res(out, s):
+    return (f6_res(out, s), f6_res(out, s + 6))
+
+
+def check_bounded(case, out, s, n, what, limb=NORM_HI, val_bound=VAL_MAX, lo=None):
+    for i in range(n):
+        check_normed(case, out_limbs(out, s + i), "%s[%d]" % (what, i), val_bound, -limb if lo is None else lo, limb)
+
+
+def flags_agree(case, flags, nflags):
+    """Both lanes of a pair hold the same predicate (the one-lane and host forms write both halves)."""
+    expect(list(flags[:nflags]) == list(flags[4:4 + nflags]), case,
+           "the lanes of the pair disagree: %s vs %s" % (list(flags[:nflags]), list(flags[4:4 + nflags])))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the edge values
+# ---------------------------------------------------------------------------------------------------------------------
+HALF = (P - 1) // 2
+
+
+def fq_edges():
+    """The field elements where carries, signs and reductions turn: 0, 1, 2, p-1, p-2, (p +- 1)/2, 2^k and p - 2^k for k
+    around every multiple of 28 and up to 380, 2^381 mod p, R, R^-1, R^2 mod p."""
+    e = [0, 1, 2, P - 1, P - 2, HALF, HALF + 1, HALF - 1, (1 << 381) % P, RM % P, RINV, RM * RM % P]
+    for m in range(0, 392, 28):
+        for k in (m - 1, m, m + 1):
+            if 0 <= k <= 380:
+                e += [(1 << k) % P, (P - (1 << k)) % P]
+    e += [(1 << 380) % P, P - (1 << 380)]
+    out = []
+    for v in e:
+        if v not in out:
+            out.append(v)
+    return out
+
+
+def g1_point(rnd, in_group=True):
+    if in_group:
+        return o.E1.mul(o.G1_GEN, rnd.randrange(1, o.R))
+    while True:
+        x = rnd.randrange(P)
+        y2 = (x ** 3 + 4) % P
+        y = pow(y2, (P + 1) // 4, P)
+        if y * y % P == y2:
+            pt = (x, y)
+            if o.E1.mul(pt, o.R) is not None:
+                return pt
+
+
+def g2_point(rnd, in_group=True):
+    if in_group:
+        return o.E2.mul(o.G2_GEN, rnd.randrange(1, o.R))
+    while True:
+        pt = o.g2_get_point_from_x((rnd.randrange(P), rnd.randrange(P)), rnd.random() < 0.5)
+        if pt is not None and o.E2.mul(pt, o.R) is not None:
+            return pt
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# op specs: cases(rnd) -> [Case], check(case, out, flags) raises Fail
+# ---------------------------------------------------------------------------------------------------------------------
+SPECS = {}
+
+
+def spec(name, random_case, nflags=0):
+    def deco(fn):
+        SPECS[name] = (fn, random_case, nflags)
+        return fn
+    return deco
+
+
+PRODUCT_PAIRS = [(1.0, 1.0), (1.03, 7.9), (7.9, 1.03), (2.0, 4.07), (4.07, 2.0), (2.85, 2.85)]
+PUSHES = (None, "hi", "lo", "alt")
+
+
+def _mul_case(a, b, tag, square=False):
+    check_product_operands(a, b)
+    return Case([a] if square else [a, b], tag=tag)
+
+
+# ---- Fq -----------------------------------------------------------------------------------------------------------
+def _fq_mul_cases(rnd, square):
+    cases = []
+    for v in fq_edges():
+        w = rnd.choice(fq_edges())
+        a = encode(v)
+        cases.append(_mul_case(a, encode(w), "edge %x*%x" % (v, w), square))
+    # the representative p of zero
+    cases.append(_mul_case(encode_int(P), encode(rnd.randrange(P)), "p*x", square))
+    # lazy inputs at k = +-300, +-299, +-1, limbs at their interval ends; operand pairs at the column limit
+    for ba, bb in PRODUCT_PAIRS:
+        for push in PUSHES:
+            for k in (299, -300, -299, 1, -1, 0):
+                if abs(k) > 30 and min(ba, bb) < 0.5:
+                    continue
+                va = 0 if abs(k) == 300 else rnd.choice(fq_edges() + [rnd.randrange(P)])
+                a = encode(va, k, (-ba, ba), push)
+                b = a if square else encode(rnd.randrange(P), -k if k != -300 else 3, (-bb, bb), push)
+                if square and ba != bb:
+                    continue
+                cases.append(_mul_case(a, b, "lazy k=%d B=(%g,%g) %s" % (k, ba, bb, push), square))
+    return cases
+
+
+def _rand_mul(rnd, square):
+    ba, bb = rnd.choice(PRODUCT_PAIRS)
+    if square:
+        ba = bb = rnd.choice([1.0, 2.0, 2.85])
+    a = encode(rnd.randrange(P), rnd.randint(-3, 3), (-ba, ba), rnd.choice(PUSHES))
+    b = a if square else encode(rnd.randrange(P), rnd.randint(-3, 3), (-bb, bb), rnd.choice(PUSHES))
+    return _mul_case(a, b, "random", square)
+
+
+def _check_mul(case, out, flags, square):
+    a = value(case.slots[0].limbs)
+    b = a if square else value(case.slots[1].limbs)
+    l = out_limbs(out, 0)
+    check_product(case, l, a * b)
+    expect(residue(l) == residue(case.slots[0].limbs) * residue(case.slots[-1].limbs) % P, case, "residue")
+
+
+@spec("FQ_MUL", lambda rnd: _rand_mul(rnd, False))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _fq_mul_cases(rnd, False)
+    _check_mul(case, out, flags, False)
+
+
+@spec("FQ_SQR", lambda rnd: _rand_mul(rnd, True))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _fq_mul_cases(rnd, True)
+    _check_mul(case, out, flags, True)
+
+
+def _lazy_value_cases(rnd, kinds=(299, -300, -299, 1, -1, 0, 150, -150)):
+    cases = [Case([encode(v)], tag="edge %x" % v) for v in fq_edges()]
+    cases.append(Case([encode_int(P)], tag="p"))
+    for k in kinds:
+        for push in PUSHES:
+            for iv in ((-7.9, 7.9), (-1.0, 1.0), (-0.001, 1.001)):
+                v = 0 if abs(k) == 300 else rnd.choice(fq_edges())
+                try:
+                    cases.append(Case([encode(v, k, iv, push)], tag="lazy k=%d %s %s" % (k, iv, push)))
+                except AssertionError:
+                    pass  # (a push that cannot keep the top limb inside a narrow interval)
+    return cases
+
+
+def _rand_lazy(rnd):
+    return Case([encode(rnd.randrange(P), rnd.randint(-300, 299), (-7.9, 7.9), rnd.choice(PUSHES))], tag="random")
+
+
+@spec("FQ_REDC_FULL", _rand_lazy)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _lazy_value_cases(rnd)
+    l = out_limbs(out, 0)
+    expect(all(0 <= x <= MASK for x in l), case, "redc_full: limbs not in [0, 2^28): %s" % l)
+    v = value(l)
+    expect(0 <= v <= P, case, "redc_full: value outside [0, p]")
+    expect(v % P == residue(case.slots[0].limbs), case, "redc_full: residue")
+
+
+@spec("FQ_FROM_CANONICAL", lambda rnd: Case([words(rnd.randrange(P))], tag="random"))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return [Case([words(v)], tag="edge %x" % v) for v in fq_edges()]
+    l = out_limbs(out, 0)
+    x = words_value(case.slots[0])
+    check_product(case, l, x * (RM * RM % P))
+    expect(residue(l) == x, case, "from_canonical: residue")
+
+
+@spec("FQ_FROM_MONT384", lambda rnd: Case([words(rnd.randrange(P))], tag="random"))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return [Case([words(v)], tag="edge %x" % v) for v in fq_edges()]
+    l = out_limbs(out, 0)
+    x = words_value(case.slots[0])
+    check_carried(case, l, "from_mont384")
+    expect(residue(l) == x * pow(2, -384, P) % P, case, "from_mont384: residue")
+    expect(-P // 4 < value(l) < 5 * P // 4, case, "from_mont384: value outside (-p/4, 5p/4)")
+
+
+@spec("FQ_TO_CANONICAL", _rand_lazy)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _lazy_value_cases(rnd)
+    w = sum((int(c) & 0xffffffff) << (32 * i) for i, c in enumerate(out[0][:12]))
+    expect(w == residue(case.slots[0].limbs), case, "to_canonical: %x" % w)
+
+
+@spec("FQ_GT_HALF", lambda rnd: Case([words(rnd.randrange(P))], tag="random"), nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        vs = fq_edges() + [HALF - 2, HALF + 2, P - 3]
+        return [Case([words(v)], tag="%x" % v) for v in vs]
+    x = words_value(case.slots[0])
+    expect(flags[0] == int(x > HALF), case, "gt_half(%x) = %d" % (x, flags[0]))
+
+
+@spec("FQ_NORM", _rand_lazy)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _lazy_value_cases(rnd)
+    l = out_limbs(out, 0)
+    expect(value(l) == value(case.slots[0].limbs), case, "norm changed the value")
+    check_normed(case, l, "norm")
+
+
+def _reduce_value_cases(rnd):
+    cases = _lazy_value_cases(rnd)
+    # values where floorf(top / p_top) in reduce_value sits at an integer boundary: k p + (small) and k p - (small), with
+    # the top limb of the carried value exactly k * p_top, just below it and just above it
+    ptop = P >> (RB * (NL - 1))
+    for k in list(range(-300, 301, 23)) + [-300, -299, -1, 0, 1, 2, 3, 150, 299, 300]:
+        for d in (-2, -1, 0, 1, 2):
+            for x in (k * P + d, (k * ptop) << (RB * (NL - 1)), ((k * ptop) << (RB * (NL - 1))) - 1 + d,
+                      ((k * ptop + 1) << (RB * (NL - 1))) + d):
+                if abs(x) > 300 * P:
+                    continue
+                for push in (None, "hi", "lo"):
+                    try:
+                        cases.append(Case([_encode_raw(x, (-7.9, 7.9), push)], tag="floor k=%d d=%d %s" % (k, d, push)))
+                    except AssertionError:
+                        pass
+    return cases
+
+
+def _encode_raw(x, interval, push):
+    """encode() for an integer given directly (not v R + k p)."""
+    k, r = divmod(x, P)
+    op = encode(r * RINV % P, k, interval, push)
+    assert value(op.limbs) == x
+    return op
+
+
+@spec("FQ_REDUCE_VALUE", _rand_lazy)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _reduce_value_cases(rnd)
+    l = out_limbs(out, 0)
+    expect((value(l) - value(case.slots[0].limbs)) % P == 0, case, "reduce_value changed the residue")
+    check_normed(case, l, "reduce_value", val_bound=2.1)
+    expect(value(l) > -P // 64, case, "reduce_value: value %.4f p below 0" % (value(l) / P))
+
+
+def _mz(limbs, bits):
+    t = (value(limbs) % (1 << bits)) * (-pow(P, -1, 1 << bits)) % (1 << bits)
+    return int(((t + 300) % (1 << bits)) <= 600)
+
+
+def _zero_cases(rnd):
+    cases = []
+    # EVERY representation k p of zero, k in [-300, 300], with lazy limbs
+    for k in range(-300, 301):
+        push = PUSHES[k % 4]
+        iv = (-7.9, 7.9) if k % 3 else (-1.0, 1.0)
+        try:
+            a = encode(0, k, iv, push)
+        except AssertionError:
+            a = encode(0, k, (-7.9, 7.9), push)
+        b = encode(0, rnd.randint(-3, 3), (-1.0, 1.0), rnd.choice(PUSHES))
+        cases.append(zero_case([a, b], "zero k=%d" % k, [(0, 1)]))
+    # near misses: k p + 1, k p - 1, and the values the filter lets through (t within 300 of zero but not a multiple of p)
+    for k in (-300, -299, -1, 0, 1, 299):
+        for d in (1, -1, 2 ** 28, -(2 ** 28)):
+            x = k * P + d
+            if abs(x) <= 300 * P:
+                cases.append(zero_case([_encode_raw(x, (-7.9, 7.9), "alt"), encode(1)], "near k=%d d=%d" % (k, d), [(0, 1)]))
+    for j in (-300, -299, 299, 300, 301, -301):
+        # value = j (mod 2^56) * ... : low bits equal those of j p, residue non-zero
+        x = j * P + (1 << 60) * rnd.randrange(1, 1 << 100)
+        if abs(x) <= 300 * P:
+            cases.append(zero_case([_encode_raw(x, (-7.9, 7.9), None), encode(0)], "filter edge j=%d" % j, [(0, 1)]))
+    # a == b with b a different representation of the same element
+    for v in fq_edges()[:20]:
+        cases.append(zero_case([encode(v, 5, (-2.0, 2.0), "hi"), encode(v, -7, (-2.0, 2.0), "lo")], "eq %x" % v, [(0, 1)]))
+    return cases
+
+
+@spec("FQ_ZERO", lambda rnd: zero_case([encode(rnd.randrange(P), rnd.randint(-290, 290), (-6.9, 6.9), "alt"),
+                                        encode(rnd.randrange(P))], "random", [(0, 1)]), nflags=4)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _zero_cases(rnd)
+    a, b = case.slots[0].limbs, case.slots[1].limbs
+    z = residue(a) == 0
+    if z:
+        expect(flags[0] == 1 and flags[1] == 1, case, "the zero filter missed a zero: %s" % list(flags[:2]))
+    expect(flags[0] == _mz(a, 28), case, "maybe_zero = %d" % flags[0])
+    expect(flags[1] == _mz(a, 56), case, "maybe_zero56 = %d" % flags[1])
+    expect(flags[2] == int(z), case, "is_zero = %d" % flags[2])
+    if case.aux[0]:
+        expect(flags[3] == int(residue(a) == residue(b)), case, "== gave %d" % flags[3])
+
+
+# Operands whose binary GCD (tc_field.h fq_inv_limbs30) needs the most steps before b = 1, the point after which v holds
+# the inverse: c 2^k mod p with a small odd c near the top (3 * 2^379: 760 exact steps, all 26 rounds of 30; random
+# operands: 540-580 steps, about 20 rounds).  2^380 runs all 26 rounds too but is correct after 381 steps.  A lower round
+# cap breaks the former, and only rare random operands.
+SLOW_INV = [3 * 2 ** 379 % P, 7 * 2 ** 377 % P, 3 * 2 ** 378 % P, 45 * 2 ** 375 % P, 5 * 2 ** 336]
+
+
+def _inv_edges(rnd):
+    vs = [0, 1, 2, 3, P - 1, P - 2, HALF, HALF + 1] + SLOW_INV
+    vs += [1 << k for k in (100, 200, 250, 300, 330, 350, 360, 370, 375, 378, 379, 380)]
+    vs += [P - (1 << k) for k in (200, 300, 379, 380)]
+    vs += [(1 << 381) % P, RM % P, RINV]
+    return vs
+
+
+def _inv_cases(rnd):
+    cases = [Case([encode(v)], tag="inv %x" % v) for v in _inv_edges(rnd)]
+    cases.append(Case([encode_int(P)], tag="inv of p (zero)"))
+    for k in (-300, 300, -1, 7):
+        cases.append(Case([encode(0, k, (-7.9, 7.9), "alt")], tag="inv of %d p" % k))
+    for v in (1 << 380, 1, P - 1):
+        cases.append(Case([encode(v, 250, (-7.9, 7.9), "hi")], tag="lazy inv %x" % v))
+    return cases
+
+
+def _check_inv(case, out, what):
+    l = out_limbs(out, 0)
+    v = residue(case.slots[0].limbs)
+    check_carried(case, l, what)
+    expect(residue(l) == (pow(v, P - 2, P)), case, "%s: residue" % what)
+    expect(-P // 4 < value(l) < 5 * P // 4, case, "%s: value %.3f p" % (what, value(l) / P))
+
+
+@spec("FQ_INV", _rand_lazy)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _inv_cases(rnd)
+    _check_inv(case, out, "inv")
+
+
+@spec("FQ_INV_FERMAT", lambda rnd: Case([encode(rnd.randrange(P), rnd.randint(0, 2), (0.0, 1.0))], tag="random"))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return [Case([encode(v, k % 3, (0.0, 1.0))], tag="inv %x" % v) for k, v in enumerate(_inv_edges(rnd))] + [
+            Case([encode_int(P)], tag="p")]
+    _check_inv(case, out, "fq_inv_fermat")
+
+
+@spec("FQ_INV30", lambda rnd: Case([limbs30(rnd.randrange(P))], tag="random"))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        # 2^380 needs all 26 rounds of 30 steps, random operands about 18; both kinds share the wave
+        return [Case([limbs30(v)], tag="inv30 %x" % v) for v in _inv_edges(rnd)] + [
+            Case([limbs30(1 << k)], tag="2^%d" % k) for k in range(181, 381, 11)]
+    l = [int(x) for x in out[0][:13]]
+    r = sum(x << (30 * i) for i, x in enumerate(l))
+    y = sum(x << (30 * i) for i, x in enumerate(case.slots[0].limbs[:13]))
+    expect(all(0 <= x < (1 << 30) for x in l[:12]), case, "inv30: limbs")
+    expect(-2 * P < r < P, case, "inv30: value %.3f p outside (-2p, p)" % (r / P))
+    expect(r % P == (pow(y, P - 2, P)), case, "inv30: residue")
+
+
+@spec("FQ_LEGENDRE", lambda rnd: Case([encode(rnd.randrange(P), rnd.randint(-2, 2), (-1.0, 1.0), "alt")], tag="random"),
+      nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        cases = [Case([encode(v)], tag="%x" % v) for v in fq_edges()]
+        cases += [Case([encode(0, k, (-7.9, 7.9), "alt")], tag="zero k=%d" % k) for k in (-300, -1, 1, 300)]
+        cases += [Case([encode(rnd.randrange(1, 1 << (k + 1)))], tag="small %d" % k) for k in range(0, 380, 19)]
+        return cases
+    v = residue(case.slots[0].limbs)
+    want = 0 if v == 0 else (1 if pow(v, HALF, P) == 1 else -1)
+    expect(flags[0] == want, case, "legendre = %d, want %d" % (flags[0], want))
+
+
+@spec("FQ_SQRT", lambda rnd: Case([encode(rnd.randrange(P), rnd.randint(0, 2), (0.0, 1.0))], tag="random"), nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        cases = [Case([encode(v)], tag="%x" % v) for v in fq_edges()]
+        cases += [Case([encode(rnd.randrange(P) ** 2 % P, 1, (0.0, 1.0), "hi")], tag="square")]
+        return cases
+    v = residue(case.slots[0].limbs)
+    sq = v == 0 or pow(v, HALF, P) == 1
+    expect(flags[0] == int(sq), case, "fq_sqrt ok = %d" % flags[0])
+    if sq:
+        r, w = residue(out[0]), residue(out[1])
+        expect(r * r % P == v, case, "fq_sqrt: root^2 != a")
+        expect(v == 0 or r * w % P == 1, case, "fq_sqrt: inv_root")
+    check_bounded(case, out, 0, 2, "fq_sqrt", val_bound=2)
+
+
+# ---- Fq2 ----------------------------------------------------------------------------------------------------------
+def f2_operand(rnd, v=None, k=(0, 0), iv=(0.0, 1.0), push=(None, None)):
+    v = v if v is not None else (rnd.randrange(P), rnd.randrange(P))
+    return [encode(v[0], k[0], iv, push[0]), encode(v[1], k[1], iv, push[1])]
+
+
+def f2_edges():
+    e = fq_edges()
+    out = [(v, 0) for v in e[:8]] + [(0, v) for v in e[:8]]
+    out += [(v, w) for v, w in zip(e, reversed(e))]
+    return out
+
+
+def f2_val(case, s):
+    return (value(case.slots[s].limbs), value(case.slots[s + 1].limbs))
+
+
+def f2_in(case, s):
+    return (residue(case.slots[s].limbs), residue(case.slots[s + 1].limbs))
+
+
+def _f2_mul_cases(rnd, square):
+    cases = []
+    e = f2_edges()
+    for i, v in enumerate(e):
+        w = e[(i * 7 + 3) % len(e)]
+        # only one lane holds an edge value: the other coefficient random
+        a = f2_operand(rnd, v)
+        b = f2_operand(rnd, w)
+        cases.append(Case(a + ([] if square else b), tag="edge %s" % (v,)))
+    for ba, bb in PRODUCT_PAIRS:
+        # the lane pair's column bound is Bx By + Bz Bw <= 8.14: each coefficient product takes half
+        ba2, bb2 = ba / 2 ** 0.5, bb / 2 ** 0.5
+        if square:
+            # c0 = (a0 + a1)(a0 - a1): sums of the two coefficients -> B (2 b)^2 <= 8.14
+            ba2 = bb2 = 1.42
+        for push in PUSHES:
+            for k in (0, 1, -1, 100, -100):
+                a = f2_operand(rnd, None, (k, -k), (-ba2, ba2), (push, "alt"))
+                b = f2_operand(rnd, None, (-k, k), (-bb2, bb2), ("alt", push))
+                cases.append(Case(a + ([] if square else b), tag="lazy k=%d B=%g,%g %s" % (k, ba2, bb2, push)))
+    return cases
+
+
+def _check_f2_mul(case, out, square):
+    a0, a1 = f2_val(case, 0)
+    if square:
+        x0, x1 = (a0 + a1) * (a0 - a1), 2 * a1 * a0
+        want = o.f2_sqr(f2_in(case, 0))
+    else:
+        b0, b1 = f2_val(case, 2)
+        x0, x1 = a0 * b0 - a1 * b1, a1 * b0 + a0 * b1
+        want = o.f2_mul(f2_in(case, 0), f2_in(case, 2))
+    check_product(case, out_limbs(out, 0), x0, "c0")
+    check_product(case, out_limbs(out, 1), x1, "c1")
+    expect(f2_res(out, 0) == want, case, "fq2 residue")
+
+
+def _rand_f2(rnd, n=1, iv=(-1.0, 1.0), kmax=2):
+    ops = []
+    for _ in range(n):
+        ops += f2_operand(rnd, None, (rnd.randint(-kmax, kmax), rnd.randint(-kmax, kmax)), iv, (rnd.choice(PUSHES), rnd.choice(PUSHES)))
+    return Case(ops, tag="random")
+
+
+@spec("FQ2_MUL", lambda rnd: _rand_f2(rnd, 2, (-1.4, 1.4)))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _f2_mul_cases(rnd, False)
+    _check_f2_mul(case, out, False)
+
+
+@spec("FQ2_SQR", lambda rnd: _rand_f2(rnd, 1, (-1.4, 1.4)))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _f2_mul_cases(rnd, True)
+    _check_f2_mul(case, out, True)
+
+
+def _f2_lazy_cases(rnd, iv=(-3.9, 3.9), kmax=150):
+    cases = [Case(f2_operand(rnd, v), tag="edge %s" % (v,)) for v in f2_edges()]
+    for k in (0, 1, -1, kmax, -kmax):
+        for push in PUSHES:
+            cases.append(Case(f2_operand(rnd, None, (k, -k), iv, (push, "alt")), tag="lazy k=%d %s" % (k, push)))
+    return cases
+
+
+@spec("FQ2_CONJ", lambda rnd: _rand_f2(rnd, 1, (-3.9, 3.9), 100))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _f2_lazy_cases(rnd)
+    a0, a1 = case.slots[0].limbs, case.slots[1].limbs
+    expect(out_limbs(out, 0) == a0 and out_limbs(out, 1) == [-x for x in a1], case, "conj is not (c0, -c1) limb for limb")
+
+
+@spec("FQ2_MUL_XI", lambda rnd: _rand_f2(rnd, 1, (-3.9, 3.9), 100))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _f2_lazy_cases(rnd)
+    a0, a1 = case.slots[0].limbs, case.slots[1].limbs
+    expect(out_limbs(out, 0) == [x - y for x, y in zip(a0, a1)] and out_limbs(out, 1) == [x + y for x, y in zip(a0, a1)],
+           case, "mul_xi is not (c0 - c1, c0 + c1) limb for limb")
+
+
+@spec("FQ2_NORM_FQ", lambda rnd: _rand_f2(rnd, 1, (-2.0, 2.0), 100))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _f2_lazy_cases(rnd, (-2.0, 2.0), 100)
+    a0, a1 = f2_in(case, 0)
+    l = out_limbs(out, 0)
+    expect(residue(l) == (a0 * a0 + a1 * a1) % P, case, "norm_fq residue")
+    x0, x1 = f2_val(case, 0)
+    t = value(l) * RM - x0 * x0 - x1 * x1
+    expect(t % P == 0 and 0 <= t // P < 2 * RM, case, "norm_fq: not a sum of two products")
+
+
+def _f2_inv_check(case, out, s_in, s_out, what):
+    want = o.f2_inv(f2_in(case, s_in)) if f2_in(case, s_in) != (0, 0) else (0, 0)
+    expect(f2_res(out, s_out) == want, case, "%s residue" % what)
+    check_bounded(case, out, s_out, 2, what, limb=1.0, val_bound=1.25)
+
+
+@spec("FQ2_INV", lambda rnd: _rand_f2(rnd, 1, (-1.0, 1.0), 2))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        cases = [Case(f2_operand(rnd, v), tag="edge %s" % (v,)) for v in f2_edges()]
+        cases += [Case([encode(0, 3, (-1.0, 1.0), "hi"), encode(0, -2, (-1.0, 1.0), "lo")], tag="zero")]
+        cases += [Case(f2_operand(rnd, (1 << 380, 0)), tag="2^380"), Case(f2_operand(rnd, (0, 1 << 380)), tag="2^380 u")]
+        # norms a0^2 + a1^2 equal to the slow operands of the inverse: (s, 0) with s^2 = v where v is a square
+        for v in SLOW_INV:
+            if pow(v, HALF, P) == 1:
+                cases.append(Case(f2_operand(rnd, (pow(v, (P + 1) // 4, P), 0)), tag="slow norm"))
+        return cases
+    _f2_inv_check(case, out, 0, 0, "fq2 inv")
+
+
+def _f2_zero_cases(rnd):
+    cases = []
+    for k in range(-300, 301, 3):
+        a = [encode(0, k, (-7.9, 7.9), PUSHES[k % 4]), encode(0, -k, (-7.9, 7.9), PUSHES[(k + 1) % 4])]
+        cases.append(zero_case(a + f2_operand(rnd, (0, 0)), "zero k=%d" % k, [(0, 2), (1, 3)]))
+    # one zero coefficient and one non-zero in the same pair, both ways round; near misses k p + 1
+    for k in (-300, -1, 0, 1, 300):
+        for nz in (1, P - 1, rnd.randrange(P)):
+            z = encode(0, k, (-7.9, 7.9), "alt")
+            n = encode(nz, 0 if abs(k) == 300 else k, (-7.9, 7.9), "hi")
+            cases.append(zero_case([z, n] + f2_operand(rnd, (0, nz)), "(0, x) k=%d" % k, [(0, 2), (1, 3)]))
+            cases.append(zero_case([n, z] + f2_operand(rnd, (nz, 0)), "(x, 0) k=%d" % k, [(0, 2), (1, 3)]))
+            if abs(k) < 300:
+                near = _encode_raw(k * P + 1, (-7.9, 7.9), None)
+                cases.append(zero_case([z, near] + f2_operand(rnd, (0, 0)), "(0, kp+1) k=%d" % k, [(0, 2), (1, 3)]))
+                cases.append(zero_case([near, z] + f2_operand(rnd, (0, 0)), "(kp+1, 0) k=%d" % k, [(0, 2), (1, 3)]))
+    for v in f2_edges()[:24]:
+        cases.append(zero_case(f2_operand(rnd, v, (3, -4), (-2.0, 2.0), ("hi", "lo")) + f2_operand(rnd, v, (-5, 6), (-2.0, 2.0), ("lo", "hi")),
+                               "eq %s" % (v,), [(0, 2), (1, 3)]))
+    return cases
+
+
+@spec("FQ2_ZERO", lambda rnd: _rand_zero2(rnd), nflags=3)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _f2_zero_cases(rnd)
+    flags_agree(case, flags, 3 if case.aux[0] else 2)
+    a = f2_in(case, 0)
+    z = a == (0, 0)
+    expect(flags[0] == int(z), case, "fq2 is_zero = %d" % flags[0])
+    mz = _mz(case.slots[0].limbs, 56) & _mz(case.slots[1].limbs, 56)
+    expect(flags[1] == mz, case, "maybe_zero56(fq2) = %d, want %d" % (flags[1], mz))
+    if z:
+        expect(flags[1] == 1, case, "maybe_zero56(fq2) missed a zero")
+    if case.aux[0]:
+        expect(flags[2] == int(a == f2_in(case, 2)), case, "fq2 == gave %d" % flags[2])
+
+
+def _rand_zero2(rnd):
+    c = _rand_f2(rnd, 2, (-3.0, 3.0), 100)
+    return zero_case(c.slots, "random", [(0, 2), (1, 3)])
+
+
+def _f2_is_square(a):
+    if a == (0, 0):
+        return True
+    n = (a[0] * a[0] + a[1] * a[1]) % P
+    return n == 0 or pow(n, HALF, P) == 1
+
+
+def _f2_sqrt_cases(rnd, n_ops=1):
+    vals = [(0, 0), (1, 0), (P - 1, 0), (0, 1), (0, P - 1), (2, 0), (0, 2), (HALF, 0), (0, HALF + 1), (4, 4)]
+    vals += [o.f2_sqr((rnd.randrange(P), rnd.randrange(P))) for _ in range(6)]
+    vals += [(rnd.randrange(P), rnd.randrange(P)) for _ in range(6)]
+    vals += [(o.f2_sqr((rnd.randrange(P), 0))[0], 0), (0, rnd.randrange(P)), (rnd.randrange(P), 0)]
+    cases = []
+    for i, v in enumerate(vals):
+        ops = f2_operand(rnd, v, (i % 2, 0), (NORM_LO, 1.0), ("hi" if i % 3 == 0 else None, None))
+        if n_ops == 2:
+            ops += f2_operand(rnd, vals[(i * 5 + 1) % len(vals)])
+        cases.append(Case(ops, tag="sqrt %s" % (v,)))
+    return cases
+
+
+def _check_f2_root(case, out, s, ok, a, what):
+    sq = _f2_is_square(a)
+    expect(ok == int(sq), case, "%s: ok = %d, is square %s" % (what, ok, sq))
+    if sq:
+        expect(o.f2_sqr(f2_res(out, s)) == a, case, "%s: root^2 != a" % what)
+
+
+@spec("FQ2_SQRT", lambda rnd: Case(f2_operand(rnd, None), tag="random"), nflags=2)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _f2_sqrt_cases(rnd)
+    flags_agree(case, flags, 2)
+    a = f2_in(case, 0)
+    expect(flags[1] == int(_f2_is_square(a)), case, "fq2_is_square = %d" % flags[1])
+    _check_f2_root(case, out, 0, flags[0], a, "fq2_sqrt")
+
+
+@spec("FQ2_SQRT_X2", lambda rnd: Case(f2_operand(rnd, None) + f2_operand(rnd, o.f2_sqr((rnd.randrange(P), rnd.randrange(P)))),
+                                      tag="random"), nflags=2)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _f2_sqrt_cases(rnd, 2)
+    flags_agree(case, flags, 2)
+    _check_f2_root(case, out, 0, flags[0], f2_in(case, 0), "fq2_sqrt_x2 a")
+    _check_f2_root(case, out, 2, flags[1], f2_in(case, 2), "fq2_sqrt_x2 b")
+
+
+@spec("FQ2_INV_X2", lambda rnd: _rand_f2(rnd, 2, (-1.0, 1.0), 2))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        e = f2_edges()
+        return [Case(f2_operand(rnd, v) + f2_operand(rnd, e[(i * 3 + 5) % len(e)]), tag="edge %s" % (v,)) for i, v in enumerate(e)]
+    _f2_inv_check(case, out, 0, 0, "fq2_inv_x2 a")
+    _f2_inv_check(case, out, 2, 2, "fq2_inv_x2 b")
+
+
+# ---- Fq6 / Fq12 ---------------------------------------------------------------------------------------------------
+TOWER_IV = (-0.01, NORM_HI)  # a normalised coefficient (norm / reduce_value output; the top limb may be negative)
+
+
+def _tower_operand(rnd, vals, kmax=1):
+    ops = []
+    for v in vals:
+        k = rnd.randint(-kmax, kmax)
+        ops.append(encode(v, k, TOWER_IV, rnd.choice(PUSHES)))
+    return ops
+
+
+def _flat6(a):
+    return [c for f2 in a for c in f2]
+
+
+def _flat12(a):
+    return _flat6(a[0]) + _flat6(a[1])
+
+
+def _rand_f12(rnd):
+    return tuple(tuple((rnd.randrange(P), rnd.randrange(P)) for _ in range(3)) for _ in range(2))
+
+
+def _cyclotomic(rnd):
+    """An element of the cyclotomic subgroup: f^((p^6 - 1)(p^2 + 1))."""
+    f = _rand_f12(rnd)
+    g = o.f12_mul(o.f12_conj(f), o.f12_inv(f))
+    return o.f12_mul(o.f12_frobenius(g, 2), g)
+
+
+def _special_f12(rnd):
+    z = (0, 0)
+    one6 = ((1, 0), z, z)
+    zero6 = (z, z, z)
+    e = fq_edges()
+    return [(one6, zero6), (((e[3], e[4]), z, z), (z, (1, 0), z)),
+            (((P - 1, 0), (0, P - 1), (1, 1)), (((1 << 380) % P, 0), z, (HALF, HALF + 1)))]
+
+
+def _check_tower(case, out, s, want, n, what, limb=NORM_HI, val_bound=VAL_MAX, lo=-0.05):
+    got = [residue(out[s + i]) for i in range(n)]
+    expect(got == want, case, "%s: residue mismatch" % what)
+    check_bounded(case, out, s, n, what, limb=limb, val_bound=val_bound, lo=lo)
+
+
+def _f6_cases(rnd, nops):
+    cases = []
+    z = (0, 0)
+    specials = [((1, 0), z, z), (z, (1, 0), z), (z, z, (1, 0)), ((P - 1, P - 1), (P - 1, 0), (0, P - 1)),
+                (((1 << 380) % P, HALF), (HALF + 1, 1), (2, P - 2))]
+    for sp in specials:
+        b = tuple((rnd.randrange(P), rnd.randrange(P)) for _ in range(3))
+        cases.append(Case(_tower_operand(rnd, _flat6(sp)) + (_tower_operand(rnd, _flat6(b)) if nops == 2 else []), tag="special"))
+    return cases
+
+
+def _rand_f6(rnd, nops, kmax=1):
+    ops = []
+    for _ in range(nops):
+        ops += _tower_operand(rnd, [rnd.randrange(P) for _ in range(6)], kmax)
+    return Case(ops, tag="random")
+
+
+def _f6_of(case, s):
+    return tuple(f2_in(case, s + 2 * i) for i in range(3))
+
+
+def _f12_of(case, s):
+    return (_f6_of(case, s), _f6_of(case, s + 6))
+
+
+@spec("FQ6_MUL", lambda rnd: _rand_f6(rnd, 2))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _f6_cases(rnd, 2)
+    _check_tower(case, out, 0, _flat6(o.f6_mul(_f6_of(case, 0), _f6_of(case, 6))), 6, "fq6 mul")
+
+
+@spec("FQ6_SQR", lambda rnd: _rand_f6(rnd, 1))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _f6_cases(rnd, 1)
+    a = _f6_of(case, 0)
+    _check_tower(case, out, 0, _flat6(o.f6_mul(a, a)), 6, "fq6 sqr")
+
+
+@spec("FQ6_INV", lambda rnd: _rand_f6(rnd, 1))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _f6_cases(rnd, 1)
+    _check_tower(case, out, 0, _flat6(o.f6_inv(_f6_of(case, 0))), 6, "fq6 inv")
+
+
+def _f12_cases(rnd, nops, cyclo=False):
+    cases = []
+    elems = [_cyclotomic(rnd) for _ in range(4)] + ([] if cyclo else _special_f12(rnd))
+    for f in elems:
+        g = _cyclotomic(rnd) if cyclo else _rand_f12(rnd)
+        cases.append(Case(_tower_operand(rnd, _flat12(f)) + (_tower_operand(rnd, _flat12(g)) if nops == 2 else []), tag="special"))
+    return cases
+
+
+def _rand_f12_case(rnd, nops, cyclo=False):
+    ops = []
+    for _ in range(nops):
+        ops += _tower_operand(rnd, _flat12(_cyclotomic(rnd) if cyclo else _rand_f12(rnd)))
+    return Case(ops, tag="random")
+
+
+@spec("FQ12_MUL", lambda rnd: _rand_f12_case(rnd, 2))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _f12_cases(rnd, 2)
+    _check_tower(case, out, 0, _flat12(o.f12_mul(_f12_of(case, 0), _f12_of(case, 12))), 12, "fq12 mul", val_bound=2.1)
+
+
+@spec("FQ12_SQR", lambda rnd: _rand_f12_case(rnd, 1))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _f12_cases(rnd, 1)
+    _check_tower(case, out, 0, _flat12(o.f12_sqr(_f12_of(case, 0))), 12, "fq12 sqr")
+
+
+@spec("FQ12_INV", lambda rnd: _rand_f12_case(rnd, 1))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _f12_cases(rnd, 1)
+    _check_tower(case, out, 0, _flat12(o.f12_inv(_f12_of(case, 0))), 12, "fq12 inv", limb=1.01, lo=-1.01)
+
+
+def _frob_case(rnd, k):
+    c = _rand_f12_case(rnd, 1)
+    c.aux = [k]
+    c.tag = "frobenius %d" % k
+    return c
+
+
+@spec("FQ12_FROB", lambda rnd: _frob_case(rnd, rnd.randint(1, 3)))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        cases = []
+        for k in (1, 2, 3):
+            for c in _f12_cases(rnd, 1):
+                c.aux = [k]
+                c.tag = "frobenius %d" % k
+                cases.append(c)
+        return cases
+    _check_tower(case, out, 0, _flat12(o.f12_frobenius(_f12_of(case, 0), case.aux[0])), 12, "fq12 frobenius", limb=1.01, lo=-1.01)
+
+
+@spec("FQ12_CONJ", lambda rnd: _rand_f12_case(rnd, 1))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _f12_cases(rnd, 1)
+    _check_tower(case, out, 0, _flat12(o.f12_conj(_f12_of(case, 0))), 12, "fq12 conj", limb=1.01)
+
+
+def _line_case(rnd, vals, tag):
+    return Case(_tower_operand(rnd, vals), tag=tag)
+
+
+@spec("FQ12_LINE_PRODUCT", lambda rnd: _line_case(rnd, [rnd.randrange(P) for _ in range(12)], "random"))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        e = fq_edges()
+        return [_line_case(rnd, [e[(i * 5 + j) % len(e)] for j in range(12)], "edges %d" % i) for i in range(8)] + [
+            _line_case(rnd, [0] * 12, "zero"), _line_case(rnd, [1, 0] * 6, "ones")]
+    d0, d1, d4, e0, e1, e4 = (f2_in(case, 2 * i) for i in range(6))
+    z = (0, 0)
+    want = o.f12_mul(((d0, d1, z), (z, d4, z)), ((e0, e1, z), (z, e4, z)))
+    # t2, u are lazy differences of products (limbs in about [-2, 1] 2^28); the rest carried or normalised
+    _check_tower(case, out, 0, _flat12(want), 12, "line_product", limb=2.01, lo=-2.01)
+
+
+@spec("FQ12_CYCLO_SQR", lambda rnd: _rand_f12_case(rnd, 1, True))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _f12_cases(rnd, 1, True) + [Case(_tower_operand(rnd, _flat12(_special_f12(rnd)[0])), tag="one")]
+    _check_tower(case, out, 0, _flat12(o.f12_sqr(_f12_of(case, 0))), 12, "cyclotomic_sqr", val_bound=2.1)
+
+
+def _compressed(f):
+    # (z2, z3, z4, z5) = (c1.c0, c0.c2, c0.c1, c1.c2)
+    return [f[1][0], f[0][2], f[0][1], f[1][2]]
+
+
+def _cyclo_chain_case(rnd, fs, tag):
+    vals = []
+    for f in fs:
+        vals += [c for f2 in _compressed(f) for c in f2]
+    ops = [encode(v, rnd.randint(0, 1), TOWER_IV, rnd.choice(PUSHES)) for v in vals]
+    for op in ops:
+        op.val = 2.1 if op.val <= 2 else op.val  # the output bound of reduce_value, the step before
+    c = Case(ops, tag=tag)
+    c.fs = fs
+    return c
+
+
+@spec("CYCLO_CHAIN", lambda rnd: _cyclo_chain_case(rnd, [_cyclotomic(rnd) for _ in range(3)], "random"))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        one = _special_f12(rnd)[0]
+        return [_cyclo_chain_case(rnd, [one, _cyclotomic(rnd), one], "with the identity"),
+                _cyclo_chain_case(rnd, [one, one, one], "identities")]
+    for i in range(3):
+        want = case.fs[i]  # the full element behind compressed input i
+        for _ in range(CYCLO_REDUCE_EVERY):
+            want = o.f12_sqr(want)
+        _check_tower(case, out, 12 * i, _flat12(want), 12, "cyclo chain %d" % i, limb=1.01)
+
+
+# ---- points -------------------------------------------------------------------------------------------------------
+PT_IV = (NORM_LO, NORM_HI)  # coord_out / coord_norm outputs; values up to ~14 p (the doubling's x3)
+
+
+class Field:
+    def __init__(self, w):
+        self.w = w
+        self.F = o._Fq if w == 1 else o._Fq2
+        self.E = o.E1 if w == 1 else o.E2
+
+    def enc(self, rnd, v, k=None, push=None):
+        vs = [v] if self.w == 1 else list(v)
+        out = []
+        for c in vs:
+            kk = rnd.randint(0, 13) if k is None else k
+            out.append(encode(c, kk, PT_IV, push or rnd.choice(PUSHES)))
+        return out
+
+    def rand(self, rnd):
+        return rnd.randrange(1, P) if self.w == 1 else (rnd.randrange(P), rnd.randrange(1, P))
+
+    def dec(self, case, s):
+        return residue(case.slots[s].limbs) if self.w == 1 else f2_in(case, s)
+
+    def res(self, out, s):
+        return residue(out[s]) if self.w == 1 else f2_res(out, s)
+
+    def jac(self, rnd, pt, lam=None):
+        """A point as Jacobian (x l^2, y l^3, l) in lazy limbs; None = infinity (Z a representation k p of zero)."""
+        F = self.F
+        if pt is None:
+            x, y = self.rand(rnd), self.rand(rnd)
+            return self.enc(rnd, x) + self.enc(rnd, y) + self.enc(rnd, F.zero)
+        lam = lam if lam is not None else self.rand(rnd)
+        l2 = F.sqr(lam)
+        return self.enc(rnd, F.mul(pt[0], l2)) + self.enc(rnd, F.mul(pt[1], F.mul(l2, lam))) + self.enc(rnd, lam)
+
+    def aff(self, rnd, pt):
+        if pt is None:
+            return self.enc(rnd, self.F.zero) + self.enc(rnd, self.F.one)
+        return self.enc(rnd, pt[0]) + self.enc(rnd, pt[1])
+
+    def jac_to_aff(self, case, out, s):
+        F = self.F
+        w = self.w
+        X, Y, Z = self.res(out, s), self.res(out, s + w), self.res(out, s + 2 * w)
+        if F.is_zero(Z):
+            return None
+        zi = F.inv(Z)
+        return (F.mul(X, F.sqr(zi)), F.mul(Y, F.mul(F.sqr(zi), zi)))
+
+
+G1F, G2F = Field(1), Field(2)
+
+
+def _pt(fld, rnd, in_group=True):
+    return g1_point(rnd, in_group) if fld.w == 1 else g2_point(rnd, in_group)
+
+
+def _pair_cases(fld, rnd, mixed):
+    """(P, Q) pairs at the exceptions of the addition: P = O, Q = O, P = Q, P = -Q, P = +-Q in different lazy
+    representations, and Q = 2P / generic pairs."""
+    E = fld.E
+    out = []
+    for _ in range(3):
+        p = _pt(fld, rnd)
+        q = _pt(fld, rnd)
+        out += [(None, q, "P=O"), (p, None, "Q=O"), (p, p, "P=Q"), (p, E.neg(p), "P=-Q"), (p, q, "generic"),
+                (p, E.dbl(p), "Q=2P"), (None, None, "P=Q=O")]
+    cases = []
+    for p, q, tag in out:
+        slots = fld.jac(rnd, p) + (fld.aff(rnd, q) if mixed else fld.jac(rnd, q))
+        cases.append(Case(slots, aux=[int(q is None)] if mixed else [], tag=tag))
+        cases[-1].pts = (p, q)
+    return cases
+
+
+def _rand_pair(fld, rnd, mixed):
+    p, q = _pt(fld, rnd), _pt(fld, rnd)
+    c = Case(fld.jac(rnd, p) + (fld.aff(rnd, q) if mixed else fld.jac(rnd, q)), aux=[0] if mixed else [], tag="random")
+    c.pts = (p, q)
+    return c
+
+
+def _check_point_out(fld, case, out, want, what):
+    got = fld.jac_to_aff(case, out, 0)
+    expect(got == want, case, "%s: wrong point" % what)
+    check_bounded(case, out, 0, 3 * fld.w, what, lo=-0.05)
+
+
+def _point_specs(prefix, fld):
+    def dbl(case=None, out=None, flags=None, rnd=None):
+        if rnd is not None:
+            cases = []
+            for p in [None, _pt(fld, rnd), _pt(fld, rnd)]:
+                for _ in range(2):
+                    c = Case(fld.jac(rnd, p), tag="dbl %s" % ("O" if p is None else "P"))
+                    c.pts = (p, None)
+                    cases.append(c)
+            return cases
+        _check_point_out(fld, case, out, fld.E.dbl(case.pts[0]), "jac_dbl")
+
+    def rand_dbl(rnd):
+        p = _pt(fld, rnd)
+        c = Case(fld.jac(rnd, p), tag="random")
+        c.pts = (p, None)
+        return c
+
+    def add_mixed(case=None, out=None, flags=None, rnd=None):
+        if rnd is not None:
+            return _pair_cases(fld, rnd, True)
+        _check_point_out(fld, case, out, fld.E.add(*case.pts), "jac_add_mixed")
+
+    def add(case=None, out=None, flags=None, rnd=None):
+        if rnd is not None:
+            return _pair_cases(fld, rnd, False)
+        _check_point_out(fld, case, out, fld.E.add(*case.pts), "jac_add")
+
+    def generic(mixed):
+        def fn(case=None, out=None, flags=None, rnd=None):
+            if rnd is not None:
+                return _pair_cases(fld, rnd, mixed)
+            flags_agree(case, flags, 1)
+            p, q = case.pts
+            special = p is None or q is None or p[0] == q[0]
+            if special:
+                expect(flags[0] == 1, case, "the generic addition did not raise its exception flag")
+            else:
+                expect(flags[0] == 0, case, "exception flag raised for a generic pair")
+                _check_point_out(fld, case, out, fld.E.add(p, q), "jac_add_generic")
+        return fn
+
+    def to_affine(case=None, out=None, flags=None, rnd=None):
+        if rnd is not None:
+            return [dbl_case for dbl_case in dbl(rnd=rnd)]
+        flags_agree(case, flags, 1)
+        p = case.pts[0]
+        expect(flags[0] == int(p is None), case, "to_affine inf flag")
+        if p is not None:
+            expect((fld.res(out, 0), fld.res(out, fld.w)) == p, case, "to_affine: wrong point")
+            check_bounded(case, out, 0, 2 * fld.w, "to_affine", val_bound=1.25)
+
+    def on_curve(case=None, out=None, flags=None, rnd=None):
+        if rnd is not None:
+            cases = []
+            for p in [None, _pt(fld, rnd), _pt(fld, rnd, False), (fld.rand(rnd), fld.rand(rnd))]:
+                c = Case(fld.aff(rnd, p), aux=[int(p is None)], tag="on_curve")
+                c.pts = (p, None)
+                cases.append(c)
+            return cases
+        flags_agree(case, flags, 1)
+        expect(flags[0] == int(fld.E.on_curve(case.pts[0])), case, "affine_on_curve")
+
+    def rand_on_curve(rnd):
+        p = _pt(fld, rnd) if rnd.random() < 0.5 else (fld.rand(rnd), fld.rand(rnd))
+        c = Case(fld.aff(rnd, p), aux=[0], tag="random")
+        c.pts = (p, None)
+        return c
+
+    def subgroup(case=None, out=None, flags=None, rnd=None):
+        if rnd is not None:
+            cases = []
+            for p in [None, _pt(fld, rnd), _pt(fld, rnd, False), _pt(fld, rnd, False)]:
+                c = Case(fld.aff(rnd, p), aux=[int(p is None)], tag="subgroup")
+                c.pts = (p, None)
+                cases.append(c)
+            return cases
+        flags_agree(case, flags, 1)
+        p = case.pts[0]
+        expect(flags[0] == int(fld.E.mul(p, o.R) is None), case, "in_subgroup")
+
+    def rand_subgroup(rnd):
+        p = _pt(fld, rnd, rnd.random() < 0.5)
+        c = Case(fld.aff(rnd, p), aux=[0], tag="random")
+        c.pts = (p, None)
+        return c
+
+    spec(prefix + "_DBL", rand_dbl)(dbl)
+    spec(prefix + "_ADD_MIXED", lambda rnd: _rand_pair(fld, rnd, True))(add_mixed)
+    spec(prefix + "_ADD", lambda rnd: _rand_pair(fld, rnd, False))(add)
+    spec(prefix + "_ADD_MIXED_GENERIC", lambda rnd: _rand_pair(fld, rnd, True), nflags=1)(generic(True))
+    spec(prefix + "_ADD_GENERIC", lambda rnd: _rand_pair(fld, rnd, False), nflags=1)(generic(False))
+    spec(prefix + "_TO_AFFINE", rand_dbl, nflags=1)(to_affine)
+    spec(prefix + "_ON_CURVE", rand_on_curve, nflags=1)(on_curve)
+    spec(prefix + "_IN_SUBGROUP", rand_subgroup, nflags=1)(subgroup)
+
+
+_point_specs("G1", G1F)
+_point_specs("G2", G2F)
+
+
+def _x2_case(rnd, p, q, tag):
+    c = Case(G2F.jac(rnd, p) + G2F.jac(rnd, q), tag=tag)
+    c.pts = (p, q)
+    return c
+
+
+@spec("G2_TO_AFFINE_X2", lambda rnd: _x2_case(rnd, _pt(G2F, rnd), _pt(G2F, rnd), "random"), nflags=2)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        p = _pt(G2F, rnd)
+        return [_x2_case(rnd, None, p, "O, P"), _x2_case(rnd, p, None, "P, O"), _x2_case(rnd, None, None, "O, O"),
+                _x2_case(rnd, p, p, "P, P")]
+    flags_agree(case, flags, 2)
+    for i, p in enumerate(case.pts):
+        expect(flags[i] == int(p is None), case, "to_affine_x2 inf flag %d" % i)
+        if p is not None:
+            expect((G2F.res(out, 4 * i), G2F.res(out, 4 * i + 2)) == p, case, "to_affine_x2: wrong point %d" % i)
+
+
+def _psi_ref(p):
+    # psi(P) = [x] P on G2, x = -|x| (M. Scott's membership test, tc_sqrt.h g2_in_subgroup)
+    return o.E2.neg(o.E2.mul(p, o.BLS_X))
+
+
+@spec("G2_PSI", lambda rnd: _psi_case(rnd, _pt(G2F, rnd)))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return [_psi_case(rnd, _pt(G2F, rnd)) for _ in range(4)]
+    p = case.pts[0]
+    expect((G2F.res(out, 0), G2F.res(out, 2)) == _psi_ref(p), case, "g2_psi")
+
+
+def _psi_case(rnd, p):
+    c = Case(G2F.aff(rnd, p), aux=[0], tag="psi")
+    c.pts = (p, None)
+    return c
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# tables and sizes
+# ---------------------------------------------------------------------------------------------------------------------
+def table(op, seed=1):
+    """The op's case table: the directed edge cases interleaved with random ones (so that adversarial lanes share a wave
+    with ordinary ones), padded with random cases to several workgroups and a ragged tail."""
+    fn, rand_case, _ = SPECS[op]
+    rnd = random.Random("%s-%d" % (op, seed))
+    edges = fn(rnd=rnd)
+    wave = 64 // lanes(op)
+    n = max(2 * len(edges), 3 * wave + 5)
+    if n % wave == 0:
+        n += 1
+    cases = []
+    e = list(edges)
+    while len(cases) < n:
+        if e and (len(cases) % 2 == 0 or len(cases) + len(e) >= n):
+            cases.append(e.pop(0))
+        else:
+            cases.append(rand_case(rnd))
+    return cases
+
+
+def sizes(op, n):
+    """Launch sizes: one job, a partial wave, exactly one wave, and the whole table (several workgroups, ragged tail)."""
+    wave = 64 // lanes(op)
+    return [1, wave // 2 + 3, wave, n]
+
+
+def check(op, cases, out, flags):
+    fn, _, _ = SPECS[op]
+    bad = []
+    for j, c in enumerate(cases):
+        try:
+            fn(case=c, out=out[j], flags=flags[j])
+        except Fail as e:
+            bad.append("job %d: %s" % (j, e))
+    return bad
+
+
+def _host_main(op):
+    lib = ctypes.CDLL(build_host())
+    cases = table(op)
+    out, flags = run_host(lib, op, cases)
+    bad = check(op, cases, out, flags)
+    for b in bad[:20]:
+        print(b)
+    print("%s: %d cases, %d failed" % (op, len(cases), len(bad)))
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 3 and sys.argv[1] == "host":
+        sys.exit(_host_main(sys.argv[2]))
+    print(__doc__)
+    sys.exit(2)

@@ -1,0 +1,74 @@
+"""CPU leg of the device conformance suite (tests/device_conformance.py).
+
+(a) tests/device/conformance.hip cross-compiles for gfx950 with the product's flags, so a break of the device form shows
+    here, without a GPU.
+(b) The same op bodies, built by g++ with -DTC_BOUND_CHECK (the host Fq2 form), run THE SAME case tables as the GPU leg
+    against the same big-integer references and output contracts, with every input slot's declared interval loaded into
+    the interval bookkeeping: this proves that the operands lie inside the input contract and that the encoder and the
+    references are right before any GPU time is spent.  Each op runs in a child process: a bound violation aborts it.
+"""
+import os
+import subprocess
+import sys
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import device_conformance as dc  # noqa: E402
+
+
+def test_conformance_kernels_cross_compile_for_gfx950():
+    lib = dc.build_device()
+    assert os.path.getsize(lib) > 0
+
+
+@pytest.fixture(scope="module")
+def host_lib():
+    return dc.build_host()
+
+
+@pytest.mark.parametrize("op", sorted(dc.SPECS, key=lambda k: dc.OPS[k]))
+def test_case_table_under_the_bound_analysis(host_lib, op):
+    r = subprocess.run([sys.executable, os.path.join(HERE, "device_conformance.py"), "host", op], capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, (r.stdout[-3000:] + r.stderr[-3000:])
+
+
+def test_every_op_has_a_case_table():
+    """Every op of conformance.h has a table, and every table holds its directed edges plus random cases."""
+    import re
+    with open(os.path.join(HERE, "device", "conformance.h")) as f:
+        src = f.read()
+    enum = re.search(r"enum Op \{(.*?)\};", src, re.S).group(1)
+    names = re.findall(r"\b([A-Z][A-Z0-9_]+)\b(?:\s*=\s*(\d+))?", re.sub(r"//[^\n]*", "", enum))
+    ids, nxt = {}, 0
+    for name, val in names:
+        nxt = int(val) if val else nxt
+        ids[name] = nxt
+        nxt += 1
+    assert ids == dc.OPS
+    assert set(dc.SPECS) == set(dc.OPS)
+
+
+def test_encoder_hits_the_declared_limits():
+    """encode() returns v R + k p with limbs at the interval ends it was asked for, and refuses what breaks the contract."""
+    import random
+    rnd = random.Random(3)
+    for k in (-300, -1, 0, 1, 299):
+        for push, iv in (("hi", (-7.9, 7.9)), ("lo", (-7.9, 7.9)), ("alt", (-2.85, 2.85)), (None, (0.0, 1.0))):
+            if push is None and k:
+                continue
+            v = rnd.randrange(dc.P)
+            op = dc.encode(v, k, iv, push)
+            assert dc.value(op.limbs) == dc.mont(v) + k * dc.P and dc.residue(op.limbs) == v
+            if push == "hi":
+                assert max(op.limbs[:13]) > (iv[1] - 1) * 2 ** 28
+            if push == "lo":
+                assert min(op.limbs[:13]) < (iv[0] + 1) * 2 ** 28
+    with pytest.raises(AssertionError):
+        dc.encode(5, 300, (-7.9, 7.9))  # value above 300 p
+    with pytest.raises(AssertionError):
+        dc.encode(5, 0, (-8.5, 8.5))  # limb interval beyond 7.9 * 2^28
+    with pytest.raises(AssertionError):
+        dc.check_product_operands(dc.encode(1, 0, (-3.0, 3.0)), dc.encode(1, 0, (-3.0, 3.0)))

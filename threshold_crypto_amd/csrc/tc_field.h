@@ -269,7 +269,7 @@ TC_HD Fq fq_sqr(const Fq& a);
 struct Fq {
   int32_t l[FQ_LIMBS];
 #if defined(TC_BOUND_CHECK)
-  // host-only static-analysis aid: every limb lies in [blo, bhi] * 2^26.  The interval is data
+  // host-only static-analysis aid: every limb lies in [blo, bhi] * 2^28.  The interval is data
   // independent (it follows the operation sequence), so any test that walks a code path
   // proves that path never overflows a column accumulator.
   // bval: |value| <= bval * p.  Lazy sums also grow the VALUE; only a multiplication (or
@@ -278,7 +278,7 @@ struct Fq {
   TC_HD void set_range(float lo, float hi) {
     blo = lo;
     bhi = hi;
-    // the limbs themselves are int32: |l_i| < 2^31 = 32 * 2^26 (keep a margin for norm()'s carry-in)
+    // the limbs themselves are int32: |l_i| < 2^31 = 8 * 2^28 (keep a margin for norm()'s carry-in)
     if (lo < -7.9f || hi > 7.9f) tc_bound_fail(lo, hi);
   }
   TC_HD void set_val(float v) { bval = v; }
@@ -340,7 +340,7 @@ struct Fq {
     r.set_val(2.f * val());
     return r;
   }
-  // one parallel carry pass: limbs back to [0, 2^26) + a carry of a few units; the top limb
+  // one parallel carry pass: limbs back to [0, 2^28) + a carry of a few units; the top limb
   // keeps the sign.  The value is unchanged.
   TC_HD Fq norm() const {
     Fq r;
@@ -350,7 +350,7 @@ struct Fq {
     r.set_range(-0.001f, 1.001f);
     r.set_val(val());
 #if defined(TC_BOUND_CHECK)
-    if (val() > 300.f) tc_bound_fail(val(), -1.f);  // the top limb (~ V * 2^17.7) must stay below 2^26 too
+    if (val() > 300.f) tc_bound_fail(val(), -1.f);  // the top limb (~ V * 2^16.7) must stay well below 2^28 too
 #endif
     return r;
   }
@@ -396,15 +396,15 @@ struct Fq {
   }
 
   // Zero test in two steps.  value = k p with |k| <= 300 (the value bound every operand
-  // obeys) forces the low 26 bits of the value -- l[0] & mask, whatever the lazy upper limbs
-  // hold -- to be k p mod 2^26, i.e. (l[0] * p^-1) mod 2^26 must land within 300 of zero.
-  // Four VALU instructions reject all but ~2^-16 of the non-zero inputs; only survivors pay for
+  // obeys) forces the low 28 bits of the value -- l[0] & mask, whatever the lazy upper limbs
+  // hold -- to be k p mod 2^28, i.e. (l[0] * p^-1) mod 2^28 must land within 300 of zero.
+  // Four VALU instructions reject all but ~2^-18.8 (601 / 2^28) of the non-zero inputs; only survivors pay for
   // the full reduction.  (Point additions test three coordinates per call.)
   TC_HD bool maybe_zero() const {
 #if defined(TC_BOUND_CHECK)
     if (val() > 300.f) tc_bound_fail(val(), -2.f);
 #endif
-    const uint32_t t = ((uint32_t)l[0] * FQL_INV) & (uint32_t)FQ_MASK;  // = -k mod 2^26
+    const uint32_t t = ((uint32_t)l[0] * FQL_INV) & (uint32_t)FQ_MASK;  // = -k mod 2^28
     return ((t + 300u) & (uint32_t)FQ_MASK) <= 600u;
   }
   // the same test on the low TWO limbs (56 bits of k p): no call needed afterwards, false positives ~2^-46
@@ -427,7 +427,8 @@ struct Fq {
 // ---- the multiplier ----------------------------------------------------------------------
 // Product-scanning Montgomery multiplication.  Column k gathers the carry from column k-1, sum a_i b_{k-i} and
 // sum m_i p_{k-i} in one v_mad chain (see TC_PIN).
-//   T = a*b + m*p,  T = 0 mod R,  result = T / R  in (-p/4, 5p/4)
+//   T = a*b + m*p,  T = 0 mod R,  result = T / R  with 0 <= m < R: in (a b / R, a b / R + p) exactly, limbs 0..12 in
+//   [0, 2^28) and the top limb signed (for canonical-sized operands: in (-p/4, 5p/4))
 // TC_PIN(sum) gives a partial column sum a second (ephemeral) use, so LLVM's reassociation pass treats it as a leaf
 // and keeps the accumulation order written here -- carry first.  Left alone it sorts the carry (the deepest value) to
 // the END of the column: the products then start from zero and the carry costs one v_lshl_add_u64 per column.
@@ -635,7 +636,7 @@ __device__ __forceinline__ FqRaw fq2p_sqr_inl(const int32_t* a, int32_t odd) {
 TC_HD Fq fq_mul(const Fq& a, const Fq& b) {
 #if defined(TC_BOUND_CHECK)
   if (a.bound() * b.bound() > (float)FQ_MAX_BOUND_PRODUCT) tc_bound_fail(a.bound(), b.bound());
-  if (a.val() > 300.f || b.val() > 300.f) tc_bound_fail(-a.val(), -b.val());  // top limb < 2^26
+  if (a.val() > 300.f || b.val() > 300.f) tc_bound_fail(-a.val(), -b.val());  // top limb well below 2^28
 #endif
   Fq r;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -696,14 +697,14 @@ TC_HD Fq fq_mul2(const Fq& x, const Fq& y, const Fq& z, const Fq& w) {
   return r;
 }
 
-// a / R mod p as the UNIQUE representative in [0, p]: limbs fully carried, all in [0, 2^26).
+// a / R mod p as the UNIQUE representative in [0, p]: limbs fully carried, all in [0, 2^28).
 // (T = a + m p with m in [0, R): T / R > -1 and <= p for |a| < R.)
 TC_HD void fq_redc_full(const Fq& a, int32_t* out) {
   int32_t one[FQ_LIMBS];
   TC_UNROLL for (int i = 0; i < FQ_LIMBS; i++) one[i] = (i == 0) ? 1 : 0;
-  Fq an = a.norm();  // any lazily grown input is fine: bring limbs back below 2^27 first
+  Fq an = a.norm();  // any lazily grown input is fine: bring limbs back to about [0, 2^28] first
   // the column loop masks limbs 0..13 and carries into the next column, so the output is
-  // already fully carried: digits in [0, 2^26), top limb >= 0
+  // already fully carried: digits in [0, 2^28), top limb >= 0
   fq_mul_body<false>(an.l, one, out);
 }
 
