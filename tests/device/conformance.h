@@ -14,14 +14,21 @@
 //                  ops; the one-lane and host forms write both halves), so a pair that disagrees on a predicate shows
 //           range CONF_IN x {lo, hi, val}: the declared interval of every input slot (units of 2^28 for limbs, of p for
 //                  the value), read by the bound-check build only
+//
+// The scalar block (ops 100 on, one lane per job) applies the integer and Fr code that decides WHICH multiple of a point
+// is computed.  Its operands are raw u32 words, not limbs: a scalar fills the first 8 words of a slot (little-endian), a
+// u64 two words, and an index list runs across consecutive slots as raw words (in words(0)); t, i, K and nbits go in aux.
 #pragma once
 #include "../../threshold_crypto_amd/csrc/tc_pairing.h"
 #include "../../threshold_crypto_amd/csrc/tc_sqrt.h"
+#include "../../threshold_crypto_amd/csrc/tc_msm.h"
 
 namespace tc {
 namespace conf {
 
-constexpr int CONF_IN = 24, CONF_OUT = 36, CONF_AUX = 4, CONF_FLAGS = 8;
+// (CONF_IN and CONF_OUT hold the 68 abscissae / coefficients of t = 67 as 8-word scalars: 544 words)
+constexpr int CONF_IN = 40, CONF_OUT = 40, CONF_AUX = 4, CONF_FLAGS = 8;
+constexpr int CONF_MAX_N = 68;  // t + 1 of the scalar block's index lists
 
 enum Op {
   // Fq, one lane per job
@@ -37,10 +44,18 @@ enum Op {
   // G2 (lane pair)
   G2_DBL = 70, G2_ADD_MIXED, G2_ADD, G2_ADD_MIXED_GENERIC, G2_ADD_GENERIC, G2_TO_AFFINE, G2_TO_AFFINE_X2, G2_ON_CURVE,
   G2_IN_SUBGROUP, G2_PSI,
+  // Fr and the scalar layer, one lane per job
+  FR_ADD = 100, FR_SUB, FR_MUL, FR_SQR, FR_INV, FR_FROM_CANONICAL, FR_TO_CANONICAL, FR_FROM_U64, FR_FROM_LE32,
+  FR_SCALE_COFACTOR_FIX,
+  DIV_BY_X_ABS = 110, GLS_DECOMPOSE, GLS_DECOMPOSE_ODD, SAC_RECODE4, GLV_DECOMPOSE, GLV_RECODE_SIGN_ALIGNED, MSM_G1_RECODE,
+  LAGRANGE_COEFF = 120, LAGRANGE_COEFF_FR, LAGRANGE_ALL, LAGRANGE_SPLIT, LAGRANGE_SMALL_COEFFS, COMBINE_CLASS,
+  FR_INVERSE_OF_SMALL, GCD_U64,
 };
 
-// lanes per job on the device: Fq and G1 ops one, everything that holds Fq2 values a lane pair
-TC_HD constexpr int conf_lanes(int op) { return (op >= FQ2_MUL && op < G1_DBL) || op >= G2_DBL ? kG2Lanes : 1; }
+// lanes per job on the device: Fq, G1 and the scalar block one, everything that holds Fq2 values a lane pair
+TC_HD constexpr int conf_lanes(int op) {
+  return (op >= FQ2_MUL && op < G1_DBL) || (op >= G2_DBL && op < FR_ADD) ? kG2Lanes : 1;
+}
 
 struct Ctx {
   const int32_t* in;
@@ -67,12 +82,32 @@ struct Ctx {
   template <class F>
   TC_HD F field(int s) const;
   TC_HD const uint32_t* words(int s) const { return (const uint32_t*)(in + s * FQ_LIMBS); }
+  // the scalar block: u64 k of the raw words from slot 0 on (two words each, low word first)
+  TC_HD uint64_t u64(int k) const {
+    const uint32_t* w = words(0);
+    return (uint64_t)w[2 * k] | ((uint64_t)w[2 * k + 1] << 32);
+  }
+  TC_HD Fr fr(int s) const {  // a Montgomery-form Fr, raw words
+    Fr r;
+    TC_UNROLL for (int i = 0; i < 8; i++) r.v.l[i] = words(s)[i];
+    return r;
+  }
 
   TC_HD bool writer() const { return live && lane == 0; }
   TC_HD void put_raw(int s, const int32_t* v, int n) {
     if (writer()) TC_UNROLL for (int i = 0; i < n; i++) out[s * FQ_LIMBS + i] = v[i];
   }
   TC_HD void put(int s, const Fq& v) { put_raw(s, v.l, FQ_LIMBS); }
+  TC_HD void put_words(int s, const uint32_t* v, int n) { put_raw(s, (const int32_t*)v, n); }
+  TC_HD void put(int s, const Fr& v) { put_words(s, v.v.l, 8); }
+  TC_HD void put_u64(int s, int k, uint64_t v) {  // word pair k of slot s (and on)
+    const uint32_t w[2] = {(uint32_t)v, (uint32_t)(v >> 32)};
+    if (writer()) TC_UNROLL for (int i = 0; i < 2; i++) out[s * FQ_LIMBS + 2 * k + i] = (int32_t)w[i];
+  }
+  TC_HD void put_u128(int s, int k, tc_u128 v) {  // words 4 k .. 4 k + 3 of slot s (and on)
+    put_u64(s, 2 * k, (uint64_t)v);
+    put_u64(s, 2 * k + 1, (uint64_t)(v >> 64));
+  }
   // (both coefficients are gathered by both lanes first: re() / im() exchange values over the pair)
   TC_HD void put(int s, const Fq2& v) {
     const Fq re = v.re(), im = v.im();
@@ -164,6 +199,145 @@ TC_HD void conf_curve(Ctx& c) {
     c.flag(0, a.inf);
   } else if constexpr (K == 6) {
     c.flag(0, affine_on_curve(aff_at<F>(c, 0, c.aux[0]), curve_b<F>()));
+  }
+}
+
+// ---- the scalar block: Fr, the base-|x| / GLV decompositions and their recodings, Lagrange coefficients ------------------
+template <int OP>
+TC_HD void conf_scalar(Ctx& c) {
+  if constexpr (OP == FR_ADD) {
+    c.put(0, c.fr(0) + c.fr(1));
+  } else if constexpr (OP == FR_SUB) {
+    c.put(0, c.fr(0) - c.fr(1));
+  } else if constexpr (OP == FR_MUL) {
+    c.put(0, c.fr(0) * c.fr(1));
+  } else if constexpr (OP == FR_SQR) {
+    c.put(0, c.fr(0).sqr());
+  } else if constexpr (OP == FR_INV) {
+    c.put(0, c.fr(0).inv());
+  } else if constexpr (OP == FR_FROM_CANONICAL) {
+    c.put(0, Fr::from_canonical(c.words(0)));
+  } else if constexpr (OP == FR_TO_CANONICAL) {
+    uint32_t w[8];
+    c.fr(0).to_canonical(w);
+    c.put_words(0, w, 8);
+  } else if constexpr (OP == FR_FROM_U64) {
+    c.put(0, fr_from_u64(c.u64(0)));
+  } else if constexpr (OP == FR_FROM_LE32) {
+    uint32_t w[8];
+    const bool ok = fr_from_le32((const uint8_t*)c.words(0), w);
+    c.put_words(0, w, 8);
+    c.flag(0, ok);
+  } else if constexpr (OP == FR_SCALE_COFACTOR_FIX) {
+    uint8_t b[32];
+    job_fr_scale_cofactor_fix((const uint8_t*)c.words(0), b);
+    uint32_t w[8];
+    TC_UNROLL for (int i = 0; i < 8; i++)
+      w[i] = (uint32_t)b[4 * i] | ((uint32_t)b[4 * i + 1] << 8) | ((uint32_t)b[4 * i + 2] << 16) | ((uint32_t)b[4 * i + 3] << 24);
+    c.put_words(0, w, 8);
+  } else if constexpr (OP == DIV_BY_X_ABS) {
+    uint64_t rem = 0;
+    const uint64_t q = div_by_x_abs(c.u64(0), c.u64(1), &rem);  // (u1 : u0)
+    c.put_u64(0, 0, q);
+    c.put_u64(0, 1, rem);
+  } else if constexpr (OP == GLS_DECOMPOSE || OP == GLS_DECOMPOSE_ODD) {
+    uint64_t d[4];
+    if constexpr (OP == GLS_DECOMPOSE) {
+      gls_decompose(c.words(0), d);
+    } else {
+      c.flag(0, gls_decompose_odd(c.words(0), d));
+    }
+    TC_UNROLL for (int j = 0; j < 4; j++) c.put_u64(0, j, d[j]);
+  } else if constexpr (OP == SAC_RECODE4) {
+    const uint64_t d[4] = {c.u64(0), c.u64(1), c.u64(2), c.u64(3)};
+    const SacDigits sd = sac_recode4(d, c.aux[0]);
+    c.put_u64(0, 0, sd.neg);
+    TC_UNROLL for (int j = 0; j < 3; j++) c.put_u64(0, j + 1, sd.u[j]);
+    c.flag(0, (int)sd.top);
+    c.flag(1, sd.fix);
+  } else if constexpr (OP == GLV_DECOMPOSE) {
+    tc_u128 k1, k2;
+    glv_decompose(c.words(0), &k1, &k2);
+    c.put_u128(0, 0, k1);
+    c.put_u128(0, 1, k2);
+  } else if constexpr (OP == GLV_RECODE_SIGN_ALIGNED) {
+    tc_u128 neg, u;
+    bool top = false;
+    const bool flip = glv_recode_sign_aligned(c.words(0), &neg, &u, &top);
+    c.put_u128(0, 0, neg);
+    c.put_u128(0, 1, u);
+    c.flag(0, flip);
+    c.flag(1, top);
+  } else if constexpr (OP == MSM_G1_RECODE) {
+    uint8_t codes[65];
+    TC_UNROLL for (int i = 0; i < 65; i++) codes[i] = 0xee;  // (a column the recoding leaves alone keeps this)
+    bool fits = false;
+    const bool flip = msm_g1_recode(c.words(0), codes, 1, c.aux[0], &fits);
+    uint32_t w[65];
+    TC_UNROLL for (int i = 0; i < 65; i++) w[i] = codes[i];
+    c.put_words(0, w, 65);
+    c.flag(0, flip);
+    c.flag(1, fits);
+  } else if constexpr (OP == LAGRANGE_COEFF || OP == LAGRANGE_ALL || OP == LAGRANGE_SPLIT) {
+    const int t = c.aux[0], n = t + 1;
+    uint64_t idx[CONF_MAX_N];
+    TC_NOUNROLL for (int j = 0; j < n; j++) idx[j] = c.u64(j);
+    if constexpr (OP == LAGRANGE_COEFF) {
+      uint32_t w[8];
+      c.flag(0, job_lagrange(idx, t, c.aux[1], w));
+      c.put_words(0, w, 8);
+    } else {
+      uint32_t ws[4 * CONF_MAX_N * 8], w[CONF_MAX_N * 8];
+      uint8_t st;
+      if constexpr (OP == LAGRANGE_ALL) {
+        st = lagrange_all_at_zero(idx, t, w, ws);
+      } else {  // k_lagrange_den (every i), then k_lagrange_finish
+        uint32_t* xm = ws;
+        uint32_t* den = ws + CONF_MAX_N * 8;
+        TC_NOUNROLL for (int i = 0; i < n; i++) {
+          const Fr x = fr_from_u64(idx[i]) + Fr::one();
+          TC_UNROLL for (int k = 0; k < 8; k++) xm[i * 8 + k] = x.v.l[k];
+        }
+        TC_NOUNROLL for (int i = 0; i < n; i++) {
+          const Fr d = lagrange_denominator(idx, n, i);
+          TC_UNROLL for (int k = 0; k < 8; k++) den[i * 8 + k] = d.v.l[k];
+        }
+        st = lagrange_finish(n, xm, den, ws + 2 * CONF_MAX_N * 8, w);
+      }
+      c.flag(0, st);
+      c.put_words(0, w, 8 * n);
+    }
+  } else if constexpr (OP == LAGRANGE_COEFF_FR) {
+    Fr lam = Fr::zero();
+    const bool ok = lagrange_coeff_at_zero_fr(c.words(0), c.aux[0], c.aux[1], lam);
+    uint32_t w[8];
+    lam.to_canonical(w);
+    c.put_words(0, w, 8);
+    c.flag(0, ok);
+  } else if constexpr (OP == LAGRANGE_SMALL_COEFFS || OP == COMBINE_CLASS) {
+    const uint64_t idx[4] = {c.u64(0), c.u64(1), c.u64(2), c.u64(3)};
+    if constexpr (OP == LAGRANGE_SMALL_COEFFS) {
+      uint64_t c_abs[4] = {0, 0, 0, 0}, d_abs = 0;
+      bool c_neg[4] = {false, false, false, false}, d_neg = false;
+      bool ok = false;
+      if (c.aux[0] == 2) ok = lagrange_small_coeffs<2>(idx, c_abs, c_neg, &d_abs, &d_neg);
+      if (c.aux[0] == 3) ok = lagrange_small_coeffs<3>(idx, c_abs, c_neg, &d_abs, &d_neg);
+      if (c.aux[0] == 4) ok = lagrange_small_coeffs<4>(idx, c_abs, c_neg, &d_abs, &d_neg);
+      TC_UNROLL for (int k = 0; k < 4; k++) c.put_u64(0, k, c_abs[k]);
+      c.put_u64(0, 4, d_abs);
+      c.flag(0, ok);
+      c.flag(1, d_neg);
+      c.flag(2, (int)c_neg[0] | ((int)c_neg[1] << 1) | ((int)c_neg[2] << 2) | ((int)c_neg[3] << 3));
+    } else {
+      c.flag(0, combine_job_class(idx, c.aux[0]));
+      c.flag(1, combine_small_applies(idx, c.aux[0]));
+    }
+  } else if constexpr (OP == FR_INVERSE_OF_SMALL) {
+    uint32_t w[8];
+    fr_inverse_of_small(c.u64(0), c.aux[0] != 0, w);
+    c.put_words(0, w, 8);
+  } else if constexpr (OP == GCD_U64) {
+    c.put_u64(0, 0, gcd_u64(c.u64(0), c.u64(1)));
   }
 }
 
@@ -305,6 +479,9 @@ TC_HD void conf_op(Ctx& c) {
     c.flag(0, g2_in_subgroup(aff_at<Fq2>(c, 0, c.aux[0])));
   } else if constexpr (OP == G2_PSI) {
     put_aff(c, 0, g2_psi(aff_at<Fq2>(c, 0, c.aux[0])));
+  // ---- the scalar block -------------------------------------------------------------------------------------------
+  } else if constexpr (OP >= FR_ADD) {
+    conf_scalar<OP>(c);
   }
 }
 
@@ -316,7 +493,11 @@ TC_HD void conf_op(Ctx& c) {
   X(FQ2_INV_X2) X(FQ6_MUL) X(FQ6_SQR) X(FQ6_INV) X(FQ12_MUL) X(FQ12_SQR) X(FQ12_INV) X(FQ12_FROB) X(FQ12_CONJ)         \
   X(FQ12_LINE_PRODUCT) X(FQ12_CYCLO_SQR) X(CYCLO_CHAIN) X(G1_DBL) X(G1_ADD_MIXED) X(G1_ADD) X(G1_ADD_MIXED_GENERIC)    \
   X(G1_ADD_GENERIC) X(G1_TO_AFFINE) X(G1_ON_CURVE) X(G1_IN_SUBGROUP) X(G2_DBL) X(G2_ADD_MIXED) X(G2_ADD)               \
-  X(G2_ADD_MIXED_GENERIC) X(G2_ADD_GENERIC) X(G2_TO_AFFINE) X(G2_TO_AFFINE_X2) X(G2_ON_CURVE) X(G2_IN_SUBGROUP) X(G2_PSI)
+  X(G2_ADD_MIXED_GENERIC) X(G2_ADD_GENERIC) X(G2_TO_AFFINE) X(G2_TO_AFFINE_X2) X(G2_ON_CURVE) X(G2_IN_SUBGROUP) X(G2_PSI) \
+  X(FR_ADD) X(FR_SUB) X(FR_MUL) X(FR_SQR) X(FR_INV) X(FR_FROM_CANONICAL) X(FR_TO_CANONICAL) X(FR_FROM_U64) X(FR_FROM_LE32)   \
+  X(FR_SCALE_COFACTOR_FIX) X(DIV_BY_X_ABS) X(GLS_DECOMPOSE) X(GLS_DECOMPOSE_ODD) X(SAC_RECODE4) X(GLV_DECOMPOSE)              \
+  X(GLV_RECODE_SIGN_ALIGNED) X(MSM_G1_RECODE) X(LAGRANGE_COEFF) X(LAGRANGE_COEFF_FR) X(LAGRANGE_ALL) X(LAGRANGE_SPLIT)      \
+  X(LAGRANGE_SMALL_COEFFS) X(COMBINE_CLASS) X(FR_INVERSE_OF_SMALL) X(GCD_U64)
 
 }  // namespace conf
 }  // namespace tc

@@ -10,10 +10,16 @@ signed limbs (14 x int32, radix 2^28, Montgomery R = 2^392).  The same case tabl
 Every result is compared with Python big integers (oracle/tc_oracle.py) AND checked against the primitive's output
 contract (limb ranges, value bound), which is what the next operation relies on.
 
+The scalar block (ops 100 on) takes its operands as raw u32 words instead (raw_words): scalars, u64 digits and index
+lists, with t, i, K and nbits in aux.  Where the device makes a decision once per wave (wave_any), the op's table is laid
+out by a hook (LAYOUTS): whole waves that take one path, then waves that mix them.
+
     python tests/device_conformance.py host OPNAME      (the host leg of one op; exit status 0 = every case passed)
 """
 import ctypes
 import hashlib
+import itertools
+import math
 import os
 import random
 import shutil
@@ -38,7 +44,8 @@ NL = 14
 MASK = (1 << RB) - 1
 RM = 1 << 392  # Montgomery R
 RINV = pow(RM, -1, P)
-CONF_IN, CONF_OUT, CONF_AUX, CONF_FLAGS = 24, 36, 4, 8
+CONF_IN, CONF_OUT, CONF_AUX, CONF_FLAGS = 40, 40, 4, 8
+CONF_MAX_N = 68  # t + 1 of the scalar block's index lists
 # input contract of the primitives (tc_field.h): |limb| <= 7.9 * 2^28, |value| <= 300 p, B_a * B_b <= 8.14 at a product
 LIMB_MAX = 7.9
 VAL_MAX = 300
@@ -57,12 +64,18 @@ OPS = dict(
     G1_DBL=60, G1_ADD_MIXED=61, G1_ADD=62, G1_ADD_MIXED_GENERIC=63, G1_ADD_GENERIC=64, G1_TO_AFFINE=65, G1_ON_CURVE=66,
     G1_IN_SUBGROUP=67,
     G2_DBL=70, G2_ADD_MIXED=71, G2_ADD=72, G2_ADD_MIXED_GENERIC=73, G2_ADD_GENERIC=74, G2_TO_AFFINE=75, G2_TO_AFFINE_X2=76,
-    G2_ON_CURVE=77, G2_IN_SUBGROUP=78, G2_PSI=79)
+    G2_ON_CURVE=77, G2_IN_SUBGROUP=78, G2_PSI=79,
+    FR_ADD=100, FR_SUB=101, FR_MUL=102, FR_SQR=103, FR_INV=104, FR_FROM_CANONICAL=105, FR_TO_CANONICAL=106, FR_FROM_U64=107,
+    FR_FROM_LE32=108, FR_SCALE_COFACTOR_FIX=109,
+    DIV_BY_X_ABS=110, GLS_DECOMPOSE=111, GLS_DECOMPOSE_ODD=112, SAC_RECODE4=113, GLV_DECOMPOSE=114,
+    GLV_RECODE_SIGN_ALIGNED=115, MSM_G1_RECODE=116,
+    LAGRANGE_COEFF=120, LAGRANGE_COEFF_FR=121, LAGRANGE_ALL=122, LAGRANGE_SPLIT=123, LAGRANGE_SMALL_COEFFS=124,
+    COMBINE_CLASS=125, FR_INVERSE_OF_SMALL=126, GCD_U64=127)
 
 
 def lanes(op):
     i = OPS[op]
-    return 2 if (20 <= i < 60 or i >= 70) else 1
+    return 2 if (20 <= i < 60 or 70 <= i < 100) else 1
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -202,6 +215,15 @@ def words(x):
     """A canonical integer as the 12 little-endian u32 words the codecs use (in the first 12 ints of a slot)."""
     w = [(x >> (32 * i)) & 0xffffffff for i in range(12)]
     return Operand([c - (1 << 32) if c >= 1 << 31 else c for c in w] + [0, 0], 0, 1, 1)
+
+
+def raw_words(ws):
+    """Raw u32 words across consecutive slots (14 words each, zero-padded): scalars, u64 digits, index lists.  They are
+    not limbs, so they are not held to the limb contract (check_input)."""
+    ws = [int(w) & 0xffffffff for w in ws]
+    assert len(ws) <= CONF_IN * NL
+    ws += [0] * (-len(ws) % NL)
+    return [Operand([c - (1 << 32) if c >= 1 << 31 else c for c in ws[k:k + NL]], 0, 1, 1) for k in range(0, len(ws), NL)]
 
 
 def words_value(op):
@@ -1380,6 +1402,763 @@ def _psi_case(rnd, p):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the scalar block: Fr, the base-|x| and GLV decompositions and their recodings, Lagrange coefficients
+# ---------------------------------------------------------------------------------------------------------------------
+R = o.R
+X = o.BLS_X  # |x|
+X2 = X * X
+RF = 1 << 256  # Montgomery R of Fr
+RF_INV = pow(RF, -1, R)
+M64 = (1 << 64) - 1
+X_RECIP = ((1 << 128) - 1) // X - (1 << 64)  # tc_constants.h BLS_X_RECIP
+COFACTOR_FIX = pow(3 * (X2 - 1), -1, R)  # tc_constants.h FR_COFACTOR_FIX: (3 (x^2 - 1))^-1 mod r
+LAYOUTS = {}  # op -> (path of a case, {path: random case of that path}): the wave layout of ops with per-wave decisions
+
+
+def u32s(x, n=8):
+    """x as n little-endian u32 words (a scalar: 8; n = NL pads it to a whole slot)."""
+    return [(x >> (32 * i)) & 0xffffffff for i in range(n)]
+
+
+def u64_words(vals):
+    return [w for v in vals for w in u32s(v, 2)]
+
+
+def out_words(out):
+    return [int(x) & 0xffffffff for x in np.asarray(out).reshape(-1)]
+
+
+def out_int(out, w0, nw):
+    ws = out_words(out)[w0:w0 + nw]
+    return sum(w << (32 * i) for i, w in enumerate(ws))
+
+
+def out_u64(out, k):
+    return out_int(out, 2 * k, 2)
+
+
+def scase(words, aux=(), tag="", **kw):
+    c = Case(raw_words(words), aux=aux, tag=tag)
+    c.__dict__.update(kw)
+    return c
+
+
+def fr_edges():
+    """Where carries and reductions turn in 8 x u32: 0, 1, 2, r-1, r-2, (r +- 1)/2, 2^k and r - 2^k around every word
+    boundary, 2^254, R mod r, R^-1, R^2 mod r."""
+    e = [0, 1, 2, R - 1, R - 2, (R - 1) // 2, (R + 1) // 2, RF % R, RF_INV, RF * RF % R, 1 << 254, R - (1 << 254)]
+    for m in range(0, 256, 32):
+        for k in (m - 1, m, m + 1):
+            if 0 <= k < 255:
+                e += [(1 << k) % R, (R - (1 << k)) % R]
+    out = []
+    for v in e:
+        if v not in out:
+            out.append(v)
+    return out
+
+
+def _check_fr(case, out, want, what):
+    got = out_int(out, 0, 8)
+    expect(got < R, case, "%s: not canonical (%x)" % (what, got))
+    expect(got == want % R, case, "%s: %x != %x" % (what, got, want % R))
+
+
+# ---- Fr arithmetic: Montgomery words in, Montgomery words out -------------------------------------------------------
+def _fr_pair_cases(rnd):
+    cases = []
+    e = fr_edges()
+    for a in e:
+        partners = rnd.sample(e, 4) + [(R - a) % R, a, (a + 1) % R, (R - 1 - a) % R]
+        for b in partners:
+            cases.append(scase(u32s(a, NL) + u32s(b), tag="%x, %x" % (a, b), a=a, b=b))
+    return cases
+
+
+def _rand_fr_pair(rnd):
+    a, b = rnd.randrange(R), rnd.randrange(R)
+    return scase(u32s(a, NL) + u32s(b), tag="random", a=a, b=b)
+
+
+def _fr_unary_cases(rnd):
+    return [scase(u32s(a), tag="%x" % a, a=a) for a in fr_edges()]
+
+
+def _rand_fr(rnd):
+    a = rnd.randrange(R)
+    return scase(u32s(a), tag="random", a=a)
+
+
+@spec("FR_ADD", _rand_fr_pair)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _fr_pair_cases(rnd)
+    _check_fr(case, out, case.a + case.b, "a + b")
+
+
+@spec("FR_SUB", _rand_fr_pair)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _fr_pair_cases(rnd)
+    _check_fr(case, out, case.a - case.b, "a - b")
+
+
+@spec("FR_MUL", _rand_fr_pair)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _fr_pair_cases(rnd)
+    _check_fr(case, out, case.a * case.b * RF_INV, "a b / R")
+
+
+@spec("FR_SQR", _rand_fr)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _fr_unary_cases(rnd)
+    _check_fr(case, out, case.a * case.a * RF_INV, "a^2 / R")
+
+
+@spec("FR_INV", _rand_fr)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _fr_unary_cases(rnd)
+    # residue a / R -> its inverse, in Montgomery form: R^2 / a  (0 -> 0)
+    _check_fr(case, out, pow(case.a, -1, R) * RF * RF if case.a else 0, "inv")
+
+
+@spec("FR_FROM_CANONICAL", _rand_fr)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _fr_unary_cases(rnd)
+    _check_fr(case, out, case.a * RF, "from_canonical")
+
+
+@spec("FR_TO_CANONICAL", _rand_fr)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _fr_unary_cases(rnd)
+    _check_fr(case, out, case.a * RF_INV, "to_canonical")
+
+
+def _u64_edges():
+    e = [0, 1, 2, M64, M64 - 1, 1 << 63, (1 << 63) - 1]
+    for k in (31, 32, 33, 62, 63):
+        e += [(1 << k) - 1, 1 << k, (1 << k) + 1]
+    return sorted(set(x for x in e if 0 <= x <= M64))
+
+
+@spec("FR_FROM_U64", lambda rnd: (lambda a: scase(u32s(a, 2), tag="random", a=a))(rnd.getrandbits(64)))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return [scase(u32s(a, 2), tag="%x" % a, a=a) for a in _u64_edges()]
+    _check_fr(case, out, case.a * RF, "fr_from_u64")
+
+
+def _le32_cases():
+    vs = [0, 1, R - 1, R, R + 1, R - 2, (1 << 255) - 1, (1 << 256) - 1, 1 << 255, 1 << 254]
+    for i in range(8):  # r with one word moved by one, both ways (where the word does not wrap)
+        w = u32s(R)
+        for d in (-1, 1):
+            if 0 <= w[i] + d <= 0xffffffff:
+                vs.append(R + d * (1 << (32 * i)))
+    return [scase(u32s(v), tag="%x" % v, a=v) for v in vs]
+
+
+def _rand_le32(rnd):
+    a = rnd.choice([rnd.randrange(R), rnd.randrange(R, 1 << 256), R + rnd.randrange(-(1 << 64), 1 << 64)])
+    return scase(u32s(a), tag="random", a=a)
+
+
+@spec("FR_FROM_LE32", _rand_le32, nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _le32_cases()
+    expect(flags[0] == int(case.a < R), case, "fr_from_le32 accepts %d" % flags[0])
+    expect(out_int(out, 0, 8) == case.a, case, "fr_from_le32: words")
+
+
+@spec("FR_SCALE_COFACTOR_FIX", _rand_le32)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _le32_cases() + [scase(u32s(v), tag="%x" % v, a=v) for v in fr_edges()]
+    got = out_int(out, 0, 8)
+    if case.a >= R:
+        expect(got == (1 << 256) - 1, case, "non-canonical input: not all ones")
+    else:
+        expect(got == case.a * COFACTOR_FIX % R, case, "k c mod r")
+
+
+# ---- the base-|x| division and decompositions ----------------------------------------------------------------------
+def div_by_x_abs_model(u1, u0):
+    """tc_gls.h div_by_x_abs step by step: (quotient, remainder, first correction taken, second correction taken).
+
+    The second correction (r >= |x|) cannot fire for this |x|.  With v = floor((2^128 - 1) / |x|) - 2^64 the estimate
+    q = v u1 + u1 2^64 + u0 satisfies  U / |x| - q / 2^64 = u0 (2^64 - |x|) / (|x| 2^64) + u1 / (|x| 2^64) + u1 e / 2^64
+    (U = u1 2^64 + u0, e = the fraction dropped from (2^128 - 1) / |x|), which is below 0.39 for u1 < |x|, u0 < 2^64
+    (div_second_correction_bound).  So floor(U / |x|) <= floor(q / 2^64) + 1 = q1: the candidate remainder is U - q1 |x|
+    or U - (q1 - 1) |x| < |x|, and after the first correction it is always below |x|."""
+    q = (X_RECIP * u1 + ((u1 << 64) | u0)) & ((1 << 128) - 1)
+    q1 = ((q >> 64) + 1) & M64
+    q0 = q & M64
+    r = (u0 - q1 * X) & M64
+    c1 = r > q0
+    if c1:
+        q1 = (q1 - 1) & M64
+        r = (r + X) & M64
+    c2 = r >= X
+    if c2:
+        q1 = (q1 + 1) & M64
+        r -= X
+    return q1, r, c1, c2
+
+
+def div_second_correction_bound():
+    """The largest U / |x| - q / 2^64 over u1 < |x|, u0 < 2^64 (see div_by_x_abs_model), exactly."""
+    from fractions import Fraction
+    B = 1 << 64
+    e = Fraction(B * B - 1, X) - (B + X_RECIP)
+    return Fraction((B - 1) * (B - X), X * B) + Fraction(X - 1, X * B) + Fraction(X - 1, B) * e
+
+
+def _div_cases(rnd):
+    u1s = [0, 1, 2, X - 1, X - 2, X // 2, X >> 16, (1 << 63) - 1, 1 << 63]
+    u0s = [0, 1, 2, M64, M64 - 1, X - 1, X, X + 1, (1 << 63), 2 * X - (1 << 64) if 2 * X > 1 << 64 else 0]
+    cases = [(a, b) for a in u1s for b in u0s if a < X]
+    # quotients and remainders at their ends: U = q |x| + rem
+    for q in [0, 1, 2, M64, M64 - 1, 1 << 63, (1 << 63) + 1, 1 << 32]:
+        for rem in [0, 1, X - 1, X - 2, X // 2]:
+            U = q * X + rem
+            if U >> 64 < X:
+                cases.append((U >> 64, U & M64))
+    return [scase(u64_words([a, b]), tag="u1=%x u0=%x" % (a, b), u1=a, u0=b) for a, b in cases]
+
+
+def _rand_div(rnd):
+    a, b = rnd.randrange(X), rnd.getrandbits(64)
+    return scase(u64_words([a, b]), tag="random", u1=a, u0=b)
+
+
+@spec("DIV_BY_X_ABS", _rand_div)
+def _(case=None, out=None, flags=None, rnd=None):
+    """(u1 : u0) / |x| for u1 < |x|, against divmod.  The table holds divisions that take no correction and ones that
+    take the first (r > q0); the second (r >= |x|) cannot fire for this |x| (div_by_x_abs_model)."""
+    if rnd is not None:
+        return _div_cases(rnd)
+    q, rem = divmod((case.u1 << 64) | case.u0, X)
+    expect((out_u64(out, 0), out_u64(out, 1)) == (q, rem), case, "div_by_x_abs: (%x, %x) != (%x, %x)" % (
+        out_u64(out, 0), out_u64(out, 1), q, rem))
+
+
+def _gls_edges(rnd):
+    """tests/test_hostsim.py's edge list of gls_decompose."""
+    ks = [0, 1, X - 1, X, X + 1, X2 - 1, X2, X ** 3 - 1, X ** 3, R - 1, R - 2, (1 << 255) - 19, (1 << 64) - 1, 1 << 64,
+          (1 << 128) - 1, 1 << 128, (X - 1) * (1 + X + X2 + X ** 3) % (X ** 4)]
+    ks += [(rnd.getrandbits(64) * X + rnd.choice([0, 1, X - 1])) % R for _ in range(20)]
+    return ks
+
+
+def _check_digits(case, out, k, what):
+    d = [out_u64(out, j) for j in range(4)]
+    expect(all(x < X for x in d[:3]), case, "%s: digit >= |x|: %s" % (what, [hex(x) for x in d]))
+    expect(sum(x * X ** j for j, x in enumerate(d)) == k, case, "%s: sum d_i |x|^i != %x" % (what, k))
+
+
+def _rand_k(rnd):
+    k = rnd.randrange(R)
+    return scase(u32s(k), tag="random", k=k)
+
+
+@spec("GLS_DECOMPOSE", _rand_k)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return [scase(u32s(k), tag="%x" % k, k=k) for k in _gls_edges(rnd) if k < X ** 4]
+    _check_digits(case, out, case.k, "gls_decompose")
+
+
+@spec("GLS_DECOMPOSE_ODD", _rand_k, nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return [scase(u32s(k), tag="%x" % k, k=k) for k in _gls_edges(rnd) if k < R]
+    flip = case.k % 2 == 0
+    expect(flags[0] == int(flip), case, "gls_decompose_odd: flip flag")
+    _check_digits(case, out, R - case.k if flip else case.k, "gls_decompose_odd")
+
+
+def _sac_cases(rnd):
+    cases = []
+    for nb in (64, 32, 16):
+        top = (1 << nb) - 1
+        vals = [0, 1, 2, top, top - 1, 1 << (nb - 1), (1 << (nb - 1)) - 1] + ([X - 1, X - 2] if nb == 64 else [])
+        for d0 in vals:
+            for rest in ([top, top, top], [0, 0, 0], [1, top, 0], [top - 1, 1, 1 << (nb - 1)]):
+                cases.append(_sac_case([d0] + rest, nb, "d0=%x %s" % (d0, rest)))
+        for _ in range(6):
+            cases.append(_sac_case([rnd.choice(vals)] + [rnd.choice(vals + [rnd.getrandbits(nb)]) for _ in range(3)], nb, "mixed"))
+    return cases
+
+
+def _sac_case(d, nb, tag):
+    return scase(u64_words(d), aux=[nb], tag="nbits=%d %s" % (nb, tag), d=d, nbits=nb)
+
+
+def _rand_sac(rnd):
+    nb = rnd.choice([64, 32, 16])
+    return _sac_case([rnd.getrandbits(nb) for _ in range(4)], nb, "random")
+
+
+@spec("SAC_RECODE4", _rand_sac, nflags=2)
+def _(case=None, out=None, flags=None, rnd=None):
+    """d0 | 1 = sum_{i < n} s_i 2^i + 2^n and d_j = sum_{i < n} s_i u_j[i] 2^i + top_j 2^n (s_i = -1 where neg has bit i)."""
+    if rnd is not None:
+        return _sac_cases(rnd)
+    n, d = case.nbits, case.d
+    neg = out_u64(out, 0)
+    u = [out_u64(out, j) for j in (1, 2, 3)]
+    s = [-1 if (neg >> i) & 1 else 1 for i in range(n)]
+    expect(flags[1] == int(d[0] % 2 == 0), case, "sac_recode4: fix != (d0 even)")
+    expect(sum(s[i] << i for i in range(n)) + (1 << n) == d[0] | 1, case, "sac_recode4: the signs do not give d0 | 1")
+    for j in range(3):
+        expect(u[j] >> n == 0, case, "sac_recode4: u_%d has bits above nbits" % (j + 1))
+        topj = (int(flags[0]) >> j) & 1
+        rec = sum(s[i] * ((u[j] >> i) & 1) << i for i in range(n)) + (topj << n)
+        expect(rec == d[j + 1], case, "sac_recode4: d_%d = %x, recoded %x" % (j + 1, d[j + 1], rec))
+    expect(flags[0] >> 3 == 0, case, "sac_recode4: top has bits above 2")
+
+
+def _g1_edges(rnd):
+    """tests/test_hostsim.py's edge list of the base-4 G1 ladder."""
+    return [0, 1, 2, 3, 4, 5, 6, 7, 8, 15, 16, 17, R - 1, R - 2, R - 3, R - 4, X2 - 2, X2 - 1, X2, X2 + 1, X2 + 2, 2 * X2, 3 * X2,
+            3 * X2 + 3, X2 * X2 % R, (1 << 128) - 1, 1 << 128, (1 << 128) + 1, 1 << 127, (1 << 127) - 1, X, X + 1, X - 1,
+            (R - 1) // 2, (R + 1) // 2, R - X2, R - X2 - 1, R - X2 + 1]
+
+
+@spec("GLV_DECOMPOSE", _rand_k)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return [scase(u32s(k), tag="%x" % k, k=k) for k in _g1_edges(rnd) + _gls_edges(rnd) if k < R]
+    k1, k2 = out_int(out, 0, 4), out_int(out, 4, 4)
+    expect(k1 < X2 and k2 < X2, case, "glv_decompose: half >= x^2")
+    expect(k1 + k2 * X2 == case.k, case, "glv_decompose: k1 + k2 x^2 != k")
+
+
+def _glv_prime(k):
+    flip = k % 2 == 0
+    return flip, (R - k if flip else k)
+
+
+def _check_glv_columns(case, k1, k2, kp, ncol, what):
+    expect(k1 % 2 == 1, case, "%s: k1 even" % what)
+    expect(k1 + k2 * X2 == kp, case, "%s: k1 + k2 x^2 != k' (= %x)" % (what, kp))
+    if ncol == 128:
+        expect((k1, k2) == (kp % X2, kp // X2), case, "%s: not the decomposition k' = (k' mod x^2) + (k' div x^2) x^2" % what)
+
+
+@spec("GLV_RECODE_SIGN_ALIGNED", _rand_k, nflags=2)
+def _(case=None, out=None, flags=None, rnd=None):
+    """k1 = sum_{i < 128} s_i 2^i + 2^128 and k2 = sum_{i < 128} s_i u_i 2^i + top 2^128 (the 129 columns)."""
+    if rnd is not None:
+        return [scase(u32s(k), tag="%x" % k, k=k) for k in _g1_edges(rnd) + [R]]
+    flip, kp = _glv_prime(case.k)
+    expect(flags[0] == int(flip), case, "glv_recode_sign_aligned: flip")
+    neg, u = out_int(out, 0, 4), out_int(out, 4, 4)
+    k1 = sum((-1 if (neg >> i) & 1 else 1) << i for i in range(128)) + (1 << 128)
+    k2 = sum((-1 if (neg >> i) & 1 else 1) * ((u >> i) & 1) << i for i in range(128)) + (int(flags[1]) << 128)
+    _check_glv_columns(case, k1, k2, kp, 128, "glv_recode_sign_aligned")
+
+
+def _msm_short(k1, k2, nb, tag):
+    k = k1 + k2 * X2
+    return scase(u32s(k), aux=[nb], tag="nbits=%d %s" % (nb, tag), k=k, nbits=nb)
+
+
+def _msm_cases(rnd):
+    cases = [scase(u32s(k), aux=[128], tag="nbits=128 %x" % k, k=k, nbits=128) for k in _g1_edges(rnd) + [R]]
+    for nb in (32, 16):
+        top = (1 << nb) - 1
+        for k1, k2, tag in [(1, 0, "1"), (top, top, "all ones"), (top, 0, "k2 = 0"), (1, top, "k1 = 1"),
+                            (2, 5, "k1 even"), (0, 1, "k1 = 0"), (top - 1, top, "k1 even, long"), ((1 << nb) + 1, 3, "k1 of nbits + 1 bits"),
+                            (3, 1 << nb, "k2 of nbits + 1 bits"), ((1 << nb) + 1, 1 << nb, "both nbits + 1 bits"),
+                            (1 << (nb - 1) | 1, 1 << (nb - 1), "top bits")]:
+            cases.append(_msm_short(k1, k2, nb, tag))
+        cases += [scase(u32s(k), aux=[nb], tag="nbits=%d full %x" % (nb, k), k=k, nbits=nb) for k in (R - 1, R - 2, X2 * X2 % R)]
+    return cases
+
+
+def _rand_msm(rnd):
+    nb = rnd.choice([128, 32, 16])
+    if nb == 128:
+        k = rnd.randrange(R)
+        return scase(u32s(k), aux=[128], tag="random", k=k, nbits=128)
+    return _msm_short(rnd.getrandbits(nb) | 1, rnd.getrandbits(nb), nb, "random")
+
+
+@spec("MSM_G1_RECODE", _rand_msm, nflags=2)
+def _(case=None, out=None, flags=None, rnd=None):
+    """The column codes decoded back to k1 and k2 (column c: bits 0, 1 = u_{2c}, u_{2c+1}; bit 2: s_{2c} = s_{2c+1}; bit 3:
+    s_{2c+1} = -1), the starting entry (0: P, 3: P + phi') included."""
+    if rnd is not None:
+        return _msm_cases(rnd)
+    n = case.nbits
+    nc = n // 2
+    codes = out_words(out)[:65]
+    expect(all(c == 0xee for c in codes[nc + 1:]), case, "msm_g1_recode: codes written past column %d" % nc)
+    k1, k2 = 1 << n, 0
+    expect(codes[nc] in (0, 3), case, "msm_g1_recode: starting entry %d" % codes[nc])
+    if codes[nc] == 3:
+        k2 += 1 << n
+    for c in range(nc):
+        code = codes[c]
+        expect(code < 16, case, "msm_g1_recode: code %x" % code)
+        s1 = -1 if code & 8 else 1
+        s0 = s1 if code & 4 else -s1
+        k1 += (s0 << (2 * c)) + (s1 << (2 * c + 1))
+        k2 += (s0 * (code & 1) << (2 * c)) + (s1 * ((code >> 1) & 1) << (2 * c + 1))
+    if n == 128:
+        flip, kp = _glv_prime(case.k)
+        expect(flags[0] == int(flip) and flags[1] == 1, case, "msm_g1_recode: flip / fits")
+        _check_glv_columns(case, k1, k2, kp, 128, "msm_g1_recode")
+        return
+    h1, h2 = case.k % X2, case.k // X2
+    fits = h1 % 2 == 1 and h1 >> n == 0 and h2 >> n == 0
+    expect(flags[0] == 0, case, "msm_g1_recode: short mode flipped")
+    expect(flags[1] == int(fits), case, "msm_g1_recode: fits = %d" % flags[1])
+    expect((k1, k2) == ((h1, h2) if fits else (1, 0)), case, "msm_g1_recode: codes give (%x, %x)" % (k1, k2))
+
+
+# ---- Lagrange coefficients -----------------------------------------------------------------------------------------
+_LAGRANGE_REF = {}
+
+
+def lagrange_ref(ids):
+    key = tuple(ids)
+    if key not in _LAGRANGE_REF:
+        _LAGRANGE_REF[key] = o.lagrange_coeffs(len(ids) - 1, [o.into_fr_plus_1(i) for i in ids])
+    return _LAGRANGE_REF[key]
+
+
+def _chunk_bits(ids):
+    """True when lagrange_denominator closes a 64-bit chunk for some i (the product of the |differences| it has gathered
+    would leave 64 bits)."""
+    for i, vi in enumerate(ids):
+        chunk = 1
+        for vj in ids:
+            m = abs(vj - vi) or 1
+            if chunk.bit_length() + m.bit_length() > 64:
+                return True
+            chunk *= m
+    return False
+
+
+def lagrange_index_sets(rnd):
+    """t = 0; t = 67 over range(200); repeated indices; 0, 2^63, 2^64 - 1; random 33- and 64-bit indices; and sets where a
+    running chunk of lagrange_denominator and the next difference have bit lengths that sum to exactly 64 (no close), and
+    to exactly 65 with a true product >= 2^64 (the chunk must close)."""
+    a, b = 2 ** 32 - 1, 2 ** 32 + 5
+    sets = [[5], [0], [M64], sorted(rnd.sample(range(200), 68)), rnd.sample(range(200), 68), [5, 9, 5, 7, 9, 11, 2, 40, 41],
+            [3, 3], [0, 1 << 63, M64, 1, 3, 9, 27], [M64, 0], [M64 - 1, M64, 0, 1 << 63],
+            [rnd.getrandbits(33) for _ in range(12)] + [7, 7], [rnd.getrandbits(64) for _ in range(10)],
+            # (i = 0: the differences are the other indices themselves)
+            [0, a, a],                       # a repeated difference (factor 1 for the equal pair)
+            [0, a, M64 - a],                 # 32 + 64 bits
+            [0, a, 2 ** 32 - 2],             # 32 + 32 = 64 bits: the chunk stays open, the product < 2^64
+            [0, b, a],                       # 33 + 32 = 65 bits, product >= 2^64: the chunk must close
+            [0, a, b],                       # 32 + 33 = 65, the other order
+            [0, 2 ** 40 + 1, 2 ** 24 + 2 ** 23],  # 41 + 25 = 66
+            [0, 2 ** 40 + 3, 2 ** 24 - 1],   # 41 + 24 = 65, product >= 2^64
+            [0, 2 ** 40 + 3, 2 ** 23 + 1],   # 41 + 24 = 65, product < 2^64
+            [10, 10 + b, 10 - 9, 10 + a], list(range(10)), [rnd.randrange(70000) for _ in range(40)]]
+    return [s for s in sets if len(s) <= CONF_MAX_N]
+
+
+def _idx_case(ids, aux, tag, **kw):
+    return scase(u64_words(ids), aux=aux, tag=tag, ids=list(ids), **kw)
+
+
+def _rand_ids(rnd, big=None):
+    n = rnd.randint(1, 6)
+    big = rnd.random() < 0.5 if big is None else big
+    return [rnd.getrandbits(64) if big else rnd.randrange(300) for _ in range(n)]
+
+
+def _coeff_case(ids, i, tag):
+    return _idx_case(ids, [len(ids) - 1, i], "%s i=%d" % (tag, i), i=i)
+
+
+@spec("LAGRANGE_COEFF", lambda rnd: (lambda ids: _coeff_case(ids, rnd.randrange(len(ids)), "random"))(_rand_ids(rnd)), nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return [_coeff_case(ids, i, "set %d" % k) for k, ids in enumerate(lagrange_index_sets(rnd)) for i in range(len(ids))]
+    expect(flags[0] == 0, case, "lagrange_coeff_at_zero: status %d" % flags[0])
+    expect(out_int(out, 0, 8) == lagrange_ref(case.ids)[case.i], case, "lagrange_coeff_at_zero")
+
+
+def _fr_abscissae(rnd):
+    return [[rnd.randrange(R) for _ in range(4)], [R - 1, R - 2, 5, 1 << 64], [R - 1, 0, 1, 2], [3, 3, 9, 11], [0, 1, 2, 3],
+            [rnd.randrange(R) for _ in range(9)], [R - (1 << 63), 1 << 63, 7], [R - 1], [R - 1, R - 1, 4],
+            sorted(rnd.sample(range(200), 68))]
+
+
+def _fr_coeff_case(xs, i, tag):
+    c = scase([w for x in xs for w in u32s(x)], aux=[len(xs) - 1, i], tag="%s i=%d" % (tag, i), i=i)
+    c.ids = list(xs)
+    return c
+
+
+@spec("LAGRANGE_COEFF_FR", lambda rnd: (lambda xs: _fr_coeff_case(xs, rnd.randrange(len(xs)), "random"))(
+    [rnd.randrange(R) for _ in range(rnd.randint(1, 6))]), nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return [_fr_coeff_case(xs, i, "set %d" % k) for k, xs in enumerate(_fr_abscissae(rnd)) for i in range(len(xs))]
+    expect(flags[0] == 1, case, "lagrange_coeff_at_zero_fr: refused")
+    expect(out_int(out, 0, 8) == lagrange_ref(case.ids)[case.i], case, "lagrange_coeff_at_zero_fr")
+
+
+def _lagrange_all(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return [_idx_case(ids, [len(ids) - 1], "set %d" % k) for k, ids in enumerate(lagrange_index_sets(rnd))]
+    expect(flags[0] == 0, case, "status %d" % flags[0])
+    n = len(case.ids)
+    got = [out_int(out, 8 * i, 8) for i in range(n)]
+    want = lagrange_ref(case.ids)
+    bad = [i for i in range(n) if got[i] != want[i]]
+    expect(not bad, case, "coefficients %s wrong" % bad[:8])
+
+
+def _lagrange_path(case):
+    return "chunks" if _chunk_bits(case.ids) else "one chunk"
+
+
+def _lagrange_random_of_path(path):
+    def make(rnd):
+        ids = _rand_ids(rnd, big=path == "chunks")
+        if path == "chunks":
+            ids += [rnd.getrandbits(64) for _ in range(2)]
+        return _idx_case(ids, [len(ids) - 1], "random %s" % path)
+    return make
+
+
+for _name in ("LAGRANGE_ALL", "LAGRANGE_SPLIT"):
+    spec(_name, lambda rnd: _idx_case(*(lambda ids: (ids, [len(ids) - 1], "random"))(_rand_ids(rnd))), nflags=1)(_lagrange_all)
+    LAYOUTS[_name] = (_lagrange_path, {p: _lagrange_random_of_path(p) for p in ("one chunk", "chunks")})
+
+
+# ---- the small-index fast path -------------------------------------------------------------------------------------
+def small_coeffs_model(ids):
+    """tc_threshold.h lagrange_small_coeffs step by step, with its overflow tests: (c_abs, c_neg, D) or None."""
+    if any(i >= 65535 for i in ids):
+        return None
+    K = len(ids)
+    x = [i + 1 for i in ids]
+    den, den_neg = [], []
+    for i in range(K):
+        d = 1
+        for j in range(K):
+            if j == i:
+                continue
+            if x[j] == x[i]:
+                return None
+            d *= x[j] - x[i]
+            if not -(1 << 63) <= d < 1 << 63:
+                return None
+        den_neg.append(d < 0)
+        den.append(abs(d))
+    D = 1
+    for i in range(K):
+        D = D // math.gcd(D, den[i]) * den[i]
+        if D >> 62:
+            return None
+    c = []
+    for i in range(K):
+        v = D // den[i]
+        for j in range(K):
+            if j != i:
+                v *= x[j]
+                if v >> 64:
+                    return None
+        if v >> 63:
+            return None
+        c.append(v)
+    g = D
+    for v in c:
+        g = math.gcd(g, v)
+    return [v // g for v in c], den_neg, D // g
+
+
+def small_index_sets(rnd):
+    sets = [list(s) for K in (2, 3, 4) for s in itertools.combinations(range(10), K)]
+    sets += [[65534, 3, 9, 11], [65535, 3, 9, 11], [3, 65535], [65534, 0], [65533, 65534], [0, 65534, 1, 65533],
+             [60000, 61000, 62000, 63000], [4, 4, 6, 8], [7, 7], [1, 2, 1], [0, 1, 2, 65535], [2 ** 40, 1, 2, 3],
+             [M64, 0, 1], [0, 30000, 65000, 1], [0, 1, 65533, 65534], [0, 20000, 40000, 60000], [1, 2, 64000, 65000]]
+    return sets
+
+
+def _small_case(ids, tag):
+    return _idx_case(ids, [len(ids)], tag)
+
+
+def _class_case(ids, tag):
+    return _idx_case(ids, [len(ids) - 1], tag)
+
+
+def _small_path(case):
+    if any(i >= 65535 for i in case.ids):
+        return "index"
+    return "fast" if small_coeffs_model(case.ids) else "late"
+
+
+def _small_random_of_path(path):
+    def make(rnd):
+        K = rnd.choice([2, 3, 4])
+        if path == "index":
+            ids = [rnd.randrange(65535, 1 << 64) if k == 0 else rnd.randrange(100) for k in range(K)]
+            rnd.shuffle(ids)
+        elif path == "fast":
+            ids = rnd.sample(range(rnd.choice([12, 300, 5000])), K)
+        else:
+            ids = rnd.sample(range(200), K - 1)
+            ids.append(rnd.choice(ids))
+        return _small_case(ids, "random %s" % path)
+    return make
+
+
+@spec("LAGRANGE_SMALL_COEFFS", lambda rnd: _small_random_of_path(rnd.choice(["fast", "index", "late"]))(rnd), nflags=3)
+def _(case=None, out=None, flags=None, rnd=None):
+    """Returns false exactly where the model does (an index >= 65535, a repeated index, an overflow); when true,
+    lambda_i = +-c_i / D (mod r) for every i, D < 2^62, and no common factor is left in the c_i and D."""
+    if rnd is not None:
+        return [_small_case(ids, "%s" % ids) for ids in small_index_sets(rnd)]
+    K = len(case.ids)
+    m = small_coeffs_model(case.ids)
+    expect(flags[0] == int(m is not None), case, "lagrange_small_coeffs returned %d" % flags[0])
+    if m is None:
+        return
+    c_abs = [out_u64(out, k) for k in range(K)]
+    D = out_u64(out, 4)
+    c_neg = [(flags[2] >> k) & 1 for k in range(K)]
+    expect(flags[1] == 0, case, "d_neg set")
+    expect((c_abs, [int(v) for v in m[1]], D) == (m[0], [int(v) for v in m[1]], m[2]), case,
+           "c = %s %s, D = %d; model %s" % (c_abs, c_neg, D, m))
+    expect(0 < D < 1 << 62, case, "D = %d" % D)
+    g = D
+    for v in c_abs:
+        g = math.gcd(g, v)
+    expect(g == 1, case, "common factor %d left" % g)
+    lam = lagrange_ref(case.ids)
+    for i in range(K):
+        expect(lam[i] * D % R == (-c_abs[i] if c_neg[i] else c_abs[i]) % R, case, "lambda_%d != +-c_%d / D" % (i, i))
+
+
+def _class_ref(ids, t):
+    if not 1 <= t <= 3:
+        return 0, False
+    m = small_coeffs_model(ids[:t + 1])
+    if m is None:
+        return 0, False
+    D = m[2]
+    return (1 if D == 1 else 2 if D & (D - 1) == 0 and D <= 1 << 16 else 0), True
+
+
+def _class_random_of_path(path):
+    return lambda rnd: (lambda c: _class_case(c.ids, c.tag))(_small_random_of_path(path)(rnd))
+
+
+@spec("COMBINE_CLASS", lambda rnd: _class_random_of_path(rnd.choice(["fast", "index", "late"]))(rnd), nflags=2)
+def _(case=None, out=None, flags=None, rnd=None):
+    """combine_job_class / combine_small_applies: D = 1 -> 1, D = 2^a (a <= 16) -> 2, everything else -> 0 (generic)."""
+    if rnd is not None:
+        cases = [_class_case(ids, "%s" % ids) for ids in small_index_sets(rnd)]
+        cases += [_idx_case([0, 1], [0], "t = 0"), _idx_case([0, 1, 2, 3], [4], "t = 4"), _idx_case([0, 1], [1], "D = 1"),
+                  _idx_case([0, 2], [1], "D = 2"), _idx_case([0, 1 << 15], [1], "D = 2^15"), _idx_case([0, 1 << 16], [1], "D = 2^16"),
+                  _idx_case([5, 5 + (1 << 16)], [1], "D = 2^16 (shifted)"), _idx_case([0, 3], [1], "D = 3")]
+        return cases
+    t = case.aux[0]
+    cls, applies = _class_ref(case.ids, t)
+    expect((flags[0], flags[1]) == (cls, int(applies)), case, "class %d applies %d, want %d %d" % (flags[0], flags[1], cls, applies))
+
+
+def _inv_small_case(d, neg, tag=""):
+    return scase(u32s(d, 2), aux=[int(neg)], tag="%s%d %s" % ("-" if neg else "", d, tag), d=d, neg=neg)
+
+
+def _inv_small_path(case):
+    return "word" if case.d < 1 << 32 else "bit"
+
+
+def _inv_small_random_of_path(path):
+    def make(rnd):
+        d = rnd.randrange(2, 1 << 32) if path == "word" else rnd.randrange(1 << 32, 1 << 63)
+        return _inv_small_case(d, rnd.random() < 0.5, "random")
+    return make
+
+
+@spec("FR_INVERSE_OF_SMALL", lambda rnd: _inv_small_random_of_path(rnd.choice(["word", "bit"]))(rnd))
+def _(case=None, out=None, flags=None, rnd=None):
+    """(+-D)^-1 mod r, 0 < D < 2^63.  The 32-bit word path runs only when every lane of the wave has D < 2^32."""
+    if rnd is not None:
+        ds = [1, 2, 3, 2 ** 32 - 1, 2 ** 32, 2 ** 32 + 1, 2 ** 62 - 1, 2 ** 62, 2 ** 63 - 1, 2 ** 63 - 25, 65521, 4294967291,
+              2 ** 61 - 1, 1000000007, 999999999989, 6, 255, 1 << 16, 3 ** 39]
+        return [_inv_small_case(d, neg) for d in ds for neg in (False, True)]
+    want = pow(-case.d if case.neg else case.d, -1, R)
+    _check_fr(case, out, want, "fr_inverse_of_small")
+
+
+LAYOUTS["FR_INVERSE_OF_SMALL"] = (_inv_small_path, {p: _inv_small_random_of_path(p) for p in ("word", "bit")})
+
+
+def _fib(n):
+    a, b = 0, 1
+    for _ in range(n):
+        a, b = b, a + b
+    return a
+
+
+def _gcd_case(a, b, tag):
+    return scase(u64_words([a, b]), tag="%s (%x, %x)" % (tag, a, b), a=a, b=b)
+
+
+def _gcd_steps(a, b):
+    n = 0
+    while b:
+        a, b = b, a % b
+        n += 1
+    return n
+
+
+def _gcd_path(case):
+    return _gcd_steps(case.a, case.b)
+
+
+def _gcd_random_of_path(steps):
+    def make(rnd):
+        if steps == 0:
+            return _gcd_case(rnd.getrandbits(64), 0, "b = 0")
+        # (F_{n+1} m, F_n m) takes n - 1 Euclid steps for every multiplier m
+        n = steps + 1
+        m = rnd.randrange(1, M64 // _fib(n + 1))
+        return _gcd_case(_fib(n + 1) * m, _fib(n) * m, "fibonacci multiple")
+    return make
+
+
+@spec("GCD_U64", lambda rnd: _gcd_case(rnd.getrandbits(64), rnd.getrandbits(rnd.choice([8, 32, 64])), "random"))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        F = [_fib(n) for n in range(95) if _fib(n) <= M64]
+        cases = [_gcd_case(0, 0, "zeros"), _gcd_case(0, 7, "a = 0"), _gcd_case(7, 0, "b = 0"), _gcd_case(M64, 0, "b = 0"),
+                 _gcd_case(0, M64, "a = 0"), _gcd_case(M64, M64, "equal"), _gcd_case(12, 12, "equal"), _gcd_case(1, M64, "1"),
+                 _gcd_case(M64, M64 - 1, "consecutive"), _gcd_case(1 << 63, 1 << 62, "powers of two")]
+        cases += [_gcd_case(F[n + 1], F[n], "fibonacci") for n in range(len(F) - 1)]
+        cases += [_gcd_case(F[n], F[n + 1], "fibonacci, swapped") for n in range(len(F) - 3, len(F) - 1)]
+        return cases
+    got = out_u64(out, 0)
+    expect(got == math.gcd(case.a, case.b), case, "gcd_u64 = %x" % got)
+
+
+# a wave where no lane enters the loop, and one where every lane runs 59 steps (on different values)
+LAYOUTS["GCD_U64"] = (_gcd_path, {p: _gcd_random_of_path(p) for p in (0, 59)})
+LAYOUTS["LAGRANGE_SMALL_COEFFS"] = (_small_path, {p: _small_random_of_path(p) for p in ("fast", "index", "late")})
+LAYOUTS["COMBINE_CLASS"] = (_small_path, {p: _class_random_of_path(p) for p in ("fast", "index")})
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # tables and sizes
 # ---------------------------------------------------------------------------------------------------------------------
 def table(op, seed=1):
@@ -1388,6 +2167,8 @@ def table(op, seed=1):
     fn, rand_case, _ = SPECS[op]
     rnd = random.Random("%s-%d" % (op, seed))
     edges = fn(rnd=rnd)
+    if op in LAYOUTS:
+        return _wave_layout(op, edges, rnd)
     wave = 64 // lanes(op)
     n = max(2 * len(edges), 3 * wave + 5)
     if n % wave == 0:
@@ -1399,6 +2180,31 @@ def table(op, seed=1):
             cases.append(e.pop(0))
         else:
             cases.append(rand_case(rnd))
+    return cases
+
+
+def _wave_layout(op, edges, rnd):
+    """The table of an op that decides once per wave (LAYOUTS): first, for every path, one full wave of 64 jobs that all
+    take it (its directed cases, then random ones of that path); then the other directed cases interleaved with random
+    cases of every path in turn, so that the later waves mix the paths (lanes that return early next to lanes that
+    finish), up to a ragged tail."""
+    path_of, makers = LAYOUTS[op]
+    pool, cases = list(edges), []
+    for p, make in makers.items():
+        mine = [c for c in pool if path_of(c) == p][:64]
+        pool = [c for c in pool if not any(c is m for m in mine)]
+        cases += mine + [make(rnd) for _ in range(64 - len(mine))]
+    paths = list(makers)
+    n = len(cases) + max(2 * len(pool), 2 * 64 + 5)
+    if n % 64 == 0:
+        n += 1
+    k = 0
+    while len(cases) < n:
+        if pool and (len(cases) % 2 == 0 or len(cases) + len(pool) >= n):
+            cases.append(pool.pop(0))
+        else:
+            cases.append(makers[paths[k % len(paths)]](rnd))
+            k += 1
     return cases
 
 

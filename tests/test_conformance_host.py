@@ -72,3 +72,32 @@ def test_encoder_hits_the_declared_limits():
         dc.encode(5, 0, (-8.5, 8.5))  # limb interval beyond 7.9 * 2^28
     with pytest.raises(AssertionError):
         dc.check_product_operands(dc.encode(1, 0, (-3.0, 3.0)), dc.encode(1, 0, (-3.0, 3.0)))
+
+
+def test_div_by_x_abs_table_takes_both_outcomes():
+    """DIV_BY_X_ABS: a Python model of div_by_x_abs classifies the table's divisions.  Both reachable outcomes occur (no
+    correction; the first correction, r > q0), and the model agrees with divmod on each.  The second correction
+    (r >= |x|) cannot fire for this |x|: U / |x| exceeds the reciprocal's estimate q / 2^64 by less than 1 (exact bound)."""
+    seen = {}
+    for c in dc.table("DIV_BY_X_ABS"):
+        q, r, c1, c2 = dc.div_by_x_abs_model(c.u1, c.u0)
+        assert (q, r) == divmod((c.u1 << 64) | c.u0, dc.X), c.tag
+        seen[(c1, c2)] = seen.get((c1, c2), 0) + 1
+    assert seen.get((False, False), 0) > 0 and seen.get((True, False), 0) > 0, seen
+    assert dc.div_second_correction_bound() < 1
+    assert not any(c2 for c1, c2 in seen)
+
+
+@pytest.mark.parametrize("op", sorted(dc.LAYOUTS, key=lambda k: dc.OPS[k]))
+def test_wave_layout_of_per_wave_decisions(op):
+    """Ops whose device form decides once per wave: the table opens with one full wave per path (every lane takes it),
+    and later waves mix the paths.  n = 1, a partial wave and one wave still run (sizes)."""
+    path_of, makers = dc.LAYOUTS[op]
+    cases = dc.table(op)
+    waves = [cases[k:k + 64] for k in range(0, len(cases), 64)]
+    for w, p in zip(waves, makers):
+        assert len(w) == 64 and all(path_of(c) == p for c in w), (op, p)
+    mixed = [w for w in waves[len(makers):] if len({path_of(c) for c in w}) > 1]
+    assert len(mixed) >= 2, op
+    assert {path_of(c) for w in mixed for c in w} >= set(makers)
+    assert len(cases) % 64 and dc.sizes(op, len(cases))[:3] == [1, 35, 64]

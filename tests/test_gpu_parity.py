@@ -78,6 +78,24 @@ def test_g1_mul_matches_oracle(engine, rnd):
         assert bytes(out[j, 1]) == o.g1_uncompressed(None)
 
 
+def test_g1_mul_edge_scalars_of_the_base4_ladder(engine, rnd):
+    """tc_gls.h g1_mul_glv on gfx950 at the edge scalars of the base-4 sign-aligned ladder (tests/test_hostsim.py): tiny
+    scalars, even ones (run as r - k), the neighbours of x^2, 2 x^2 and 3 x^2 + 3, 2^127 / 2^128, r - small.  One call,
+    so that the edge scalars share waves, on a random point and on the identity."""
+    X = o.BLS_X
+    x2 = X * X
+    ks = [0, 1, 2, 3, 4, 5, 6, 7, 8, 15, 16, 17, o.R - 1, o.R - 2, o.R - 3, o.R - 4, x2 - 2, x2 - 1, x2, x2 + 1, x2 + 2, 2 * x2,
+          3 * x2, 3 * x2 + 3, x2 * x2 % o.R, (1 << 128) - 1, 1 << 128, (1 << 128) + 1, 1 << 127, (1 << 127) - 1, X, X + 1, X - 1,
+          (o.R - 1) // 2, (o.R + 1) // 2, o.R - x2, o.R - x2 - 1, o.R - x2 + 1]
+    ks += [rnd.randrange(o.R) for _ in range(4)]
+    pts = [o.E1.mul(o.G1_GEN, rnd.randrange(1, o.R)), None]
+    out, st = engine.g1_mul(frs(ks), g1s(pts))
+    assert st.shape == (len(pts), len(ks)) and not st.any()
+    for j, P in enumerate(pts):
+        for s, k in enumerate(ks):
+            assert bytes(out[j, s]) == o.g1_uncompressed(o.E1.mul(P, k)), (j, hex(k))
+
+
 def test_mul_rejects_bad_encodings(engine):
     pt = bytearray(o.g2_uncompressed(o.G2_GEN))
     pt[191] ^= 1  # off the curve
