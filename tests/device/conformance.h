@@ -10,16 +10,22 @@
 //                  op says so)
 //           aux   CONF_AUX int32 parameters (point-at-infinity flags, the Frobenius power, "also compare")
 //           out   CONF_OUT Fq slots
-//           flags CONF_FLAGS int32: slots [0, 4) written by the job's first lane, [4, 8) by its second lane (lane-pair
-//                  ops; the one-lane and host forms write both halves), so a pair that disagrees on a predicate shows
+//           flags CONF_FLAGS int32: slots [4 l, 4 l + 4) written by lane l of the job (the one-lane and host forms write
+//                  [0, 8) as a lane pair would; a host quad writes all four lanes), so lanes that disagree on a predicate show
 //           range CONF_IN x {lo, hi, val}: the declared interval of every input slot (units of 2^28 for limbs, of p for
 //                  the value), read by the bound-check build only
 //
 // The scalar block (ops 100 on, one lane per job) applies the integer and Fr code that decides WHICH multiple of a point
 // is computed.  Its operands are raw u32 words, not limbs: a scalar fills the first 8 words of a slot (little-endian), a
 // u64 two words, and an index list runs across consecutive slots as raw words (in words(0)); t, i, K and nbits go in aux.
+//
+// The pairing block (ops 80 on) applies the Miller steps, loops, exponentiations and checks of tc_pairing.h (a lane pair
+// per job) and tc_quad.h (ops 90 on: a quad of four lanes per job, pair A lanes 0, 1 and pair B lanes 2, 3).  A check's
+// operands: G1 point k at slots 6 k, 6 k + 1 and G2 point k at slots 6 k + 2 .. 6 k + 5 (k = 0, 1), aux[2 k] and
+// aux[2 k + 1] their point-at-infinity flags.  MILLER_LINES also hands back the row block of miller_prepare_lines.
 #pragma once
-#include "../../threshold_crypto_amd/csrc/tc_pairing.h"
+#include "../../threshold_crypto_amd/csrc/tc_codec.h"  // (tc_quad.h job_pairing_check_quad_io decodes)
+#include "../../threshold_crypto_amd/csrc/tc_quad.h"
 #include "../../threshold_crypto_amd/csrc/tc_sqrt.h"
 #include "../../threshold_crypto_amd/csrc/tc_msm.h"
 
@@ -27,7 +33,7 @@ namespace tc {
 namespace conf {
 
 // (CONF_IN and CONF_OUT hold the 68 abscissae / coefficients of t = 67 as 8-word scalars: 544 words)
-constexpr int CONF_IN = 40, CONF_OUT = 40, CONF_AUX = 4, CONF_FLAGS = 8;
+constexpr int CONF_IN = 40, CONF_OUT = 40, CONF_AUX = 4, CONF_FLAGS = 16;
 constexpr int CONF_MAX_N = 68;  // t + 1 of the scalar block's index lists
 
 enum Op {
@@ -44,6 +50,11 @@ enum Op {
   // G2 (lane pair)
   G2_DBL = 70, G2_ADD_MIXED, G2_ADD, G2_ADD_MIXED_GENERIC, G2_ADD_GENERIC, G2_TO_AFFINE, G2_TO_AFFINE_X2, G2_ON_CURVE,
   G2_IN_SUBGROUP, G2_PSI,
+  // the pairing (lane pair)
+  MILLER_DBL_STEP = 80, MILLER_ADD_STEP, MILLER_LOOP2, MILLER_LINES, CYCLO_EXP_BY_X, CYCLO_EXP_BY_X_HALF, FINAL_EXP,
+  PAIRING_CHECK,
+  // the pairing on a quad (four lanes)
+  Q_MILLER_LOOP = 90, Q_EXP_BY_X, Q_EXP_BY_X_HALF, Q_FINAL_EXP, Q_PAIRING_CHECK,
   // Fr and the scalar layer, one lane per job
   FR_ADD = 100, FR_SUB, FR_MUL, FR_SQR, FR_INV, FR_FROM_CANONICAL, FR_TO_CANONICAL, FR_FROM_U64, FR_FROM_LE32,
   FR_SCALE_COFACTOR_FIX,
@@ -52,10 +63,16 @@ enum Op {
   FR_INVERSE_OF_SMALL, GCD_U64,
 };
 
+// the quad ops (tc_quad.h): four lanes per job on the device, two threads per job on the host
+TC_HD constexpr bool conf_quad(int op) { return op >= Q_MILLER_LOOP && op < FR_ADD; }
 // lanes per job on the device: Fq, G1 and the scalar block one, everything that holds Fq2 values a lane pair
 TC_HD constexpr int conf_lanes(int op) {
-  return (op >= FQ2_MUL && op < G1_DBL) || (op >= G2_DBL && op < FR_ADD) ? kG2Lanes : 1;
+  return conf_quad(op) ? kQuadLanes : (op >= FQ2_MUL && op < G1_DBL) || (op >= G2_DBL && op < FR_ADD) ? kG2Lanes : 1;
 }
+// ops that take a row block (tc_pairing.h Fq2Rows): device, kConfLineWords words per lane in the row layout of
+// k_miller_lines; host, kMillerRowSlots Fq2 per job
+TC_HD constexpr bool conf_needs_rows(int op) { return op == MILLER_LINES; }
+constexpr int kConfLineWords = kMillerRowSlots * FQ_LIMBS;
 
 struct Ctx {
   const int32_t* in;
@@ -64,8 +81,9 @@ struct Ctx {
   int32_t* flags;
   const float* range;  // bound-check build: declared input intervals
   bool live;           // a real job (lanes past the end of the batch run a copy of the last job and store nothing)
-  int lane;            // 0 / 1 within the job's lanes
-  bool pair;           // the job runs on a lane pair
+  int lane;            // 0 .. 3 within the job's lanes (a host quad thread: 0 for pair A, 2 for pair B)
+  bool pair;           // every lane of the job runs on its own lane (device lane-pair and quad forms)
+  void* rows = nullptr;  // conf_needs_rows: this lane's column of the row block (device) / the job's Fq2 rows (host)
 
   TC_HD Fq fq(int s) const {
     Fq r;
@@ -126,7 +144,7 @@ struct Ctx {
   TC_HD void flag(int i, int v) {
     if (!live) return;
     flags[lane * 4 + i] = v;
-    if (!pair) flags[4 + i] = v;
+    if (!pair) flags[(lane + 1) * 4 + i] = v;  // one lane, or a host thread that stands for a lane pair: both halves
   }
 };
 template <>
@@ -199,6 +217,66 @@ TC_HD void conf_curve(Ctx& c) {
     c.flag(0, a.inf);
   } else if constexpr (K == 6) {
     c.flag(0, affine_on_curve(aff_at<F>(c, 0, c.aux[0]), curve_b<F>()));
+  }
+}
+
+// ---- the pairing: Miller steps and loops, the cyclotomic exponentiation, the final exponentiation, the check ----------
+// G1 / G2 operand k of a check (slots 6 k .. 6 k + 5, aux[2 k], aux[2 k + 1])
+TC_HD G1Affine conf_g1(const Ctx& c, int k) { return aff_at<Fq>(c, 6 * k, c.aux[2 * k]); }
+TC_HD G2Affine conf_g2(const Ctx& c, int k) { return aff_at<Fq2>(c, 6 * k + 2, c.aux[2 * k + 1]); }
+
+template <int OP>
+TC_HD void conf_pairing(Ctx& c) {
+  if constexpr (OP == MILLER_DBL_STEP || OP == MILLER_ADD_STEP) {
+    // T = (X : Y : zt) at slots 0 .. 5, the affine Q at 6 .. 9; out: T' at 0 .. 5, the line (c0, c1, c2) at 6 .. 11
+    G2Jac t = jac_at<Fq2>(c, 0);
+    LineCoeffs l;
+    if constexpr (OP == MILLER_DBL_STEP) {
+      l = miller_doubling_step(t);
+    } else {
+      l = miller_addition_step(t, aff_at<Fq2>(c, 6, 0));
+    }
+    put_jac(c, 0, t);
+    c.put(6, l.c0);
+    c.put(8, l.c1);
+    c.put(10, l.c2);
+  } else if constexpr (OP == MILLER_LOOP2 || OP == MILLER_LINES || OP == PAIRING_CHECK) {
+    const G1Affine ps[2] = {conf_g1(c, 0), conf_g1(c, 1)};
+    const G2Affine qs[2] = {conf_g2(c, 0), conf_g2(c, 1)};
+    if constexpr (OP == MILLER_LOOP2) {
+      c.put(0, miller_loop<2>(ps, qs));
+    } else if constexpr (OP == MILLER_LINES) {  // k_miller_lines, then k_miller_accumulate on the same rows
+      const bool skip[2] = {ps[0].inf || qs[0].inf, ps[1].inf || qs[1].inf};
+#if TC_PAIR
+      const Fq2Rows rows = Fq2Rows::at(static_cast<int32_t*>(c.rows));
+#else
+      const Fq2Rows rows = Fq2Rows::at(static_cast<Fq2*>(c.rows));
+#endif
+      miller_prepare_lines(ps, qs, skip, rows);
+      c.put(0, miller_accumulate(rows));
+    } else {  // (a, b, c, d) = (P0, Q0, P1, Q1): pairing_check negates c itself
+      c.flag(0, pairing_check(ps[0], qs[0], ps[1], qs[1]));
+    }
+  } else if constexpr (OP == CYCLO_EXP_BY_X || OP == CYCLO_EXP_BY_X_HALF) {
+    // (the exponent is fixed per op: cyclotomic_exp_by_x reads it from the wave's first lane)
+    c.put(0, cyclotomic_exp_by_x(c.fq12(0), OP == CYCLO_EXP_BY_X ? BLS_X_ABS : BLS_X_ABS >> 1));
+  } else if constexpr (OP == FINAL_EXP) {
+    const Fq12 r = final_exponentiation(c.fq12(0));
+    c.put(0, r);
+    c.flag(0, r == Fq12::one());  // the comparison of pairing_check / job_final_exp_is_one
+  // ---- the quad forms: pair A (lanes 0, 1) gets pair 0 of the operands, pair B (lanes 2, 3) pair 1 ----
+  } else if constexpr (OP == Q_MILLER_LOOP) {
+    const int k = quad_hi() ? 1 : 0;
+    c.put(0, q_miller_loop(conf_g1(c, k), conf_g2(c, k)).gather());
+  } else if constexpr (OP == Q_EXP_BY_X || OP == Q_EXP_BY_X_HALF) {
+    c.put(0, q_exp_by_x(QFq12::from(c.fq12(0)), OP == Q_EXP_BY_X ? BLS_X_ABS : BLS_X_ABS >> 1).gather());
+  } else if constexpr (OP == Q_FINAL_EXP) {
+    const QFq12 r = q_final_exponentiation(QFq12::from(c.fq12(0)));
+    c.put(0, r.gather());
+    c.flag(0, r.is_one());
+  } else if constexpr (OP == Q_PAIRING_CHECK) {  // pair A brings (a, b), pair B (c, d)
+    const int k = quad_hi() ? 1 : 0;
+    c.flag(0, q_pairing_check(conf_g1(c, k), conf_g2(c, k)));
   }
 }
 
@@ -479,6 +557,9 @@ TC_HD void conf_op(Ctx& c) {
     c.flag(0, g2_in_subgroup(aff_at<Fq2>(c, 0, c.aux[0])));
   } else if constexpr (OP == G2_PSI) {
     put_aff(c, 0, g2_psi(aff_at<Fq2>(c, 0, c.aux[0])));
+  // ---- the pairing ------------------------------------------------------------------------------------------------
+  } else if constexpr (OP >= MILLER_DBL_STEP && OP < FR_ADD) {
+    conf_pairing<OP>(c);
   // ---- the scalar block -------------------------------------------------------------------------------------------
   } else if constexpr (OP >= FR_ADD) {
     conf_scalar<OP>(c);
@@ -494,6 +575,8 @@ TC_HD void conf_op(Ctx& c) {
   X(FQ12_LINE_PRODUCT) X(FQ12_CYCLO_SQR) X(CYCLO_CHAIN) X(G1_DBL) X(G1_ADD_MIXED) X(G1_ADD) X(G1_ADD_MIXED_GENERIC)    \
   X(G1_ADD_GENERIC) X(G1_TO_AFFINE) X(G1_ON_CURVE) X(G1_IN_SUBGROUP) X(G2_DBL) X(G2_ADD_MIXED) X(G2_ADD)               \
   X(G2_ADD_MIXED_GENERIC) X(G2_ADD_GENERIC) X(G2_TO_AFFINE) X(G2_TO_AFFINE_X2) X(G2_ON_CURVE) X(G2_IN_SUBGROUP) X(G2_PSI) \
+  X(MILLER_DBL_STEP) X(MILLER_ADD_STEP) X(MILLER_LOOP2) X(MILLER_LINES) X(CYCLO_EXP_BY_X) X(CYCLO_EXP_BY_X_HALF)           \
+  X(FINAL_EXP) X(PAIRING_CHECK) X(Q_MILLER_LOOP) X(Q_EXP_BY_X) X(Q_EXP_BY_X_HALF) X(Q_FINAL_EXP) X(Q_PAIRING_CHECK)     \
   X(FR_ADD) X(FR_SUB) X(FR_MUL) X(FR_SQR) X(FR_INV) X(FR_FROM_CANONICAL) X(FR_TO_CANONICAL) X(FR_FROM_U64) X(FR_FROM_LE32)   \
   X(FR_SCALE_COFACTOR_FIX) X(DIV_BY_X_ABS) X(GLS_DECOMPOSE) X(GLS_DECOMPOSE_ODD) X(SAC_RECODE4) X(GLV_DECOMPOSE)              \
   X(GLV_RECODE_SIGN_ALIGNED) X(MSM_G1_RECODE) X(LAGRANGE_COEFF) X(LAGRANGE_COEFF_FR) X(LAGRANGE_ALL) X(LAGRANGE_SPLIT)      \

@@ -5,35 +5,41 @@
 #include <hip/hip_runtime.h>
 #include "conformance.h"
 
+#include <vector>
+
 using namespace tc;
 using namespace tc::conf;
 
 constexpr int kBlock = 64;
 
+static int conf_grid(int op, int n) { return (n * conf_lanes(op) + kBlock - 1) / kBlock; }
+
+// rows (conf_needs_rows ops): the row block of the workgroup, laid out as k_pairing.hip k_miller_lines lays out its lines
 template <int OP>
-__global__ __launch_bounds__(kBlock) void k_conf(const int32_t* in, const int32_t* aux, int32_t* out, int32_t* flags, int n) {
+__global__ __launch_bounds__(kBlock) void k_conf(const int32_t* in, const int32_t* aux, int32_t* out, int32_t* flags,
+                                                 int32_t* rows, int n) {
   constexpr int lanes = conf_lanes(OP);
   const int t = blockIdx.x * kBlock + threadIdx.x;
   int job = t / lanes;
   const bool live = job < n;
   if (!live) job = n - 1;  // lanes past the end run a copy of the last job (the pair exchanges and ballots need every lane)
   Ctx c{in + (size_t)job * CONF_IN * FQ_LIMBS, aux + (size_t)job * CONF_AUX, out + (size_t)job * CONF_OUT * FQ_LIMBS,
-        flags + (size_t)job * CONF_FLAGS, nullptr, live, t % lanes, lanes == 2};
+        flags + (size_t)job * CONF_FLAGS, nullptr, live, t % lanes, lanes >= 2};
+  if (rows) c.rows = rows + (size_t)blockIdx.x * kConfLineWords * 64 + threadIdx.x;
   conf_op<OP>(c);
 }
 
 template <int OP>
-static hipError_t launch(const int32_t* in, const int32_t* aux, int32_t* out, int32_t* flags, int n) {
-  const int threads = n * conf_lanes(OP);
-  hipLaunchKernelGGL(k_conf<OP>, dim3((threads + kBlock - 1) / kBlock), dim3(kBlock), 0, 0, in, aux, out, flags, n);
+static hipError_t launch(const int32_t* in, const int32_t* aux, int32_t* out, int32_t* flags, int32_t* rows, int n) {
+  hipLaunchKernelGGL(k_conf<OP>, dim3(conf_grid(OP, n)), dim3(kBlock), 0, 0, in, aux, out, flags, rows, n);
   return hipGetLastError();
 }
 
-static hipError_t dispatch(int op, const int32_t* in, const int32_t* aux, int32_t* out, int32_t* flags, int n) {
+static hipError_t dispatch(int op, const int32_t* in, const int32_t* aux, int32_t* out, int32_t* flags, int32_t* rows, int n) {
   switch (op) {
 #define TC_CONF_CASE(name) \
   case name:               \
-    return launch<name>(in, aux, out, flags, n);
+    return launch<name>(in, aux, out, flags, rows, n);
     TC_CONF_OPS(TC_CONF_CASE)
 #undef TC_CONF_CASE
   }
@@ -42,27 +48,45 @@ static hipError_t dispatch(int op, const int32_t* in, const int32_t* aux, int32_
 
 // n jobs of op `op` on the current device.  Host buffers in (n x CONF_IN x 14), aux (n x CONF_AUX), out (n x CONF_OUT x 14)
 // and flags (n x CONF_FLAGS); out and flags are copied in first, so entries an op does not write keep the caller's value.
-// Returns the first HIP error (hipSuccess = 0).
-extern "C" int tc_conf_run(int op, int n, const int32_t* in, const int32_t* aux, int32_t* out, int32_t* flags) {
+// rows (conf_needs_rows ops, else unused): n x kMillerRowSlots x 2 x 14 -- slot k of job j as (re, im) limbs, gathered
+// from the device row block (re on the even lane of the pair, im on the odd one), which is filled with a poison pattern
+// before the launch so that a row read before it is written gives a wrong result.  Returns the first HIP error (0 = none).
+extern "C" int tc_conf_run(int op, int n, const int32_t* in, const int32_t* aux, int32_t* out, int32_t* flags, int32_t* rows) {
   if (n <= 0) return (int)hipErrorInvalidValue;
   const size_t sin = (size_t)n * CONF_IN * FQ_LIMBS * 4, saux = (size_t)n * CONF_AUX * 4;
   const size_t sout = (size_t)n * CONF_OUT * FQ_LIMBS * 4, sfl = (size_t)n * CONF_FLAGS * 4;
-  int32_t *din = nullptr, *daux = nullptr, *dout = nullptr, *dfl = nullptr;
+  const size_t nrow = conf_needs_rows(op) ? (size_t)conf_grid(op, n) * kConfLineWords * 64 : 0;
+  int32_t *din = nullptr, *daux = nullptr, *dout = nullptr, *dfl = nullptr, *drows = nullptr;
   hipError_t e = hipMalloc(&din, sin);
   if (e == hipSuccess) e = hipMalloc(&daux, saux);
   if (e == hipSuccess) e = hipMalloc(&dout, sout);
   if (e == hipSuccess) e = hipMalloc(&dfl, sfl);
+  if (e == hipSuccess && nrow) e = hipMalloc(&drows, nrow * 4);
+  if (e == hipSuccess && nrow) e = hipMemset(drows, 0x5A, nrow * 4);
   if (e == hipSuccess) e = hipMemcpy(din, in, sin, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(daux, aux, saux, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(dout, out, sout, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(dfl, flags, sfl, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = dispatch(op, din, daux, dout, dfl, n);
+  if (e == hipSuccess) e = dispatch(op, din, daux, dout, dfl, drows, n);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e == hipSuccess) e = hipMemcpy(out, dout, sout, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(flags, dfl, sfl, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && nrow && rows) {
+    std::vector<int32_t> raw(nrow);
+    e = hipMemcpy(raw.data(), drows, nrow * 4, hipMemcpyDeviceToHost);
+    for (int j = 0; e == hipSuccess && j < n; j++)
+      for (int part = 0; part < 2; part++) {
+        const int t = kG2Lanes * j + part;  // the job's lane pair
+        const int32_t* col = raw.data() + (size_t)(t / kBlock) * kConfLineWords * 64 + t % kBlock;
+        for (int k = 0; k < kMillerRowSlots; k++)
+          for (int i = 0; i < FQ_LIMBS; i++)
+            rows[(((size_t)j * kMillerRowSlots + k) * 2 + part) * FQ_LIMBS + i] = col[(size_t)(k * FQ_LIMBS + i) * 64];
+      }
+  }
   hipFree(din);
   hipFree(daux);
   hipFree(dout);
   hipFree(dfl);
+  if (drows) hipFree(drows);
   return (int)e;
 }

@@ -14,6 +14,11 @@ The scalar block (ops 100 on) takes its operands as raw u32 words instead (raw_w
 lists, with t, i, K and nbits in aux.  Where the device makes a decision once per wave (wave_any), the op's table is laid
 out by a hook (LAYOUTS): whole waves that take one path, then waves that mix them.
 
+The pairing block (ops 80 on; 90 on run four lanes per job, tc_quad.h) checks Miller steps, loops, the cyclotomic and the
+final exponentiation and the check itself against the oracle's pairing: a Miller value must equal the product's own
+(dev_miller_loop: the shipped step formulas on residues) and differ from the oracle's by a factor in Fq2; GT values and
+check bits must equal the oracle's exactly.  MILLER_LINES also hands back its row block (prepared lines, line products).
+
     python tests/device_conformance.py host OPNAME      (the host leg of one op; exit status 0 = every case passed)
 """
 import ctypes
@@ -44,7 +49,7 @@ NL = 14
 MASK = (1 << RB) - 1
 RM = 1 << 392  # Montgomery R
 RINV = pow(RM, -1, P)
-CONF_IN, CONF_OUT, CONF_AUX, CONF_FLAGS = 40, 40, 4, 8
+CONF_IN, CONF_OUT, CONF_AUX, CONF_FLAGS = 40, 40, 4, 16
 CONF_MAX_N = 68  # t + 1 of the scalar block's index lists
 # input contract of the primitives (tc_field.h): |limb| <= 7.9 * 2^28, |value| <= 300 p, B_a * B_b <= 8.14 at a product
 LIMB_MAX = 7.9
@@ -65,6 +70,9 @@ OPS = dict(
     G1_IN_SUBGROUP=67,
     G2_DBL=70, G2_ADD_MIXED=71, G2_ADD=72, G2_ADD_MIXED_GENERIC=73, G2_ADD_GENERIC=74, G2_TO_AFFINE=75, G2_TO_AFFINE_X2=76,
     G2_ON_CURVE=77, G2_IN_SUBGROUP=78, G2_PSI=79,
+    MILLER_DBL_STEP=80, MILLER_ADD_STEP=81, MILLER_LOOP2=82, MILLER_LINES=83, CYCLO_EXP_BY_X=84, CYCLO_EXP_BY_X_HALF=85,
+    FINAL_EXP=86, PAIRING_CHECK=87,
+    Q_MILLER_LOOP=90, Q_EXP_BY_X=91, Q_EXP_BY_X_HALF=92, Q_FINAL_EXP=93, Q_PAIRING_CHECK=94,
     FR_ADD=100, FR_SUB=101, FR_MUL=102, FR_SQR=103, FR_INV=104, FR_FROM_CANONICAL=105, FR_TO_CANONICAL=106, FR_FROM_U64=107,
     FR_FROM_LE32=108, FR_SCALE_COFACTOR_FIX=109,
     DIV_BY_X_ABS=110, GLS_DECOMPOSE=111, GLS_DECOMPOSE_ODD=112, SAC_RECODE4=113, GLV_DECOMPOSE=114,
@@ -75,7 +83,10 @@ OPS = dict(
 
 def lanes(op):
     i = OPS[op]
-    return 2 if (20 <= i < 60 or 70 <= i < 100) else 1
+    return 4 if 90 <= i < 100 else 2 if (20 <= i < 60 or 70 <= i < 90) else 1
+
+
+NEEDS_ROWS = {"MILLER_LINES"}  # conformance.h conf_needs_rows
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -124,7 +135,7 @@ def build_host():
     """The same op bodies for the host (host Fq2 form), under the interval analysis."""
     src = os.path.join(DEV, "conformance_host.cpp")
     return _build("libtc_conformance_host_bc",
-                  lambda out: ["g++", "-O1", "-std=c++17", "-w", "-DTC_BOUND_CHECK", "-shared", "-fPIC", src, "-o", out],
+                  lambda out: ["g++", "-O1", "-std=c++17", "-w", "-DTC_BOUND_CHECK", "-shared", "-fPIC", "-pthread", src, "-o", out],
                   {"conformance_host.cpp"})
 
 
@@ -276,18 +287,26 @@ def _p(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _rows_buf(op, n):
+    """The row block of conf_needs_rows ops, per job: MILLER_ROW_SLOTS x (re, im) x 14 limbs (None for other ops)."""
+    return np.zeros((n, MILLER_ROW_SLOTS, 2, NL), np.int32) if op in NEEDS_ROWS else None
+
+
 def run_device(lib, op, cases):
     inp, _, aux, out, flags = pack(cases)
-    rc = lib.tc_conf_run(OPS[op], len(cases), _p(inp), _p(aux), _p(out), _p(flags))
+    rows = _rows_buf(op, len(cases))
+    rc = lib.tc_conf_run(OPS[op], len(cases), _p(inp), _p(aux), _p(out), _p(flags), None if rows is None else _p(rows))
     assert rc == 0, "HIP error %d in op %s" % (rc, op)
-    return out, flags
+    return out, flags, rows
 
 
 def run_host(lib, op, cases):
     inp, rng, aux, out, flags = pack(cases)
-    rc = lib.tc_conf_host_run(OPS[op], len(cases), _p(inp), _p(rng), _p(aux), _p(out), _p(flags))
+    rows = _rows_buf(op, len(cases))
+    rc = lib.tc_conf_host_run(OPS[op], len(cases), _p(inp), _p(rng), _p(aux), _p(out), _p(flags),
+                              None if rows is None else _p(rows))
     assert rc == 0
-    return out, flags
+    return out, flags, rows
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -2159,6 +2178,546 @@ LAYOUTS["COMBINE_CLASS"] = (_small_path, {p: _class_random_of_path(p) for p in (
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the pairing: Miller steps and loops, the cyclotomic exponentiation, the final exponentiation, the check
+# ---------------------------------------------------------------------------------------------------------------------
+# A check's operands (conformance.h conf_g1 / conf_g2): G1 point k at slots 6 k, 6 k + 1, G2 point k at 6 k + 2 .. 6 k + 5,
+# aux = (P0 at infinity, Q0 at infinity, P1 at infinity, Q1 at infinity).  A point at infinity travels as (0, 1).
+BTW = o.f2_scale(o.XI, 4)  # the twist constant b' = 4 (1 + u)
+F2Z, F2O = o.F2_ZERO, o.F2_ONE
+# The Miller point T = (X : Y : zt) (tc_pairing.h: homogeneous, third coordinate doubled; affine (2 X / zt, 2 Y / zt)).
+# Its declared interval is what the step functions leave in it (coord norm() outputs), so that consecutive steps compose.
+MPT_IV, MPT_VAL = (NORM_LO, NORM_HI), 16
+# The Miller loop's output contract (the operand of the final exponentiation): normalised limbs, |value| <= MF_VAL p.
+MF_IV, MF_VAL = (NORM_LO, NORM_HI), 8
+# The final exponentiation's output: the operand of "== Fq12::one()" (Fq2 ==: a difference inside the zero filter).
+FE_LIMB, FE_VAL = 1.01, 2.1
+
+
+def _line014(d0, d1, d4):
+    """d0 + d1 v + d4 v w as an Fq12 (the sparse line of mul_by_014)."""
+    return ((d0, d1, F2Z), (F2Z, d4, F2Z))
+
+
+def dev_doubling_step(T):
+    """tc_pairing.h miller_doubling_step on residues: (T', (c0, c1, c2))."""
+    X, Y, Z = T
+    B, C = o.f2_sqr(Y), o.f2_sqr(Z)
+    E = o.f2_scale(o.f2_mul_xi(C), 3)
+    F = o.f2_scale(E, 3)
+    XY = o.f2_mul(X, Y)
+    H = o.f2_sub(o.f2_sub(o.f2_sqr(o.f2_add(Y, Z)), B), C)
+    J = o.f2_sqr(X)
+    line = (H, o.f2_neg(o.f2_scale(J, 6)), o.f2_scale(o.f2_sub(B, E), 2))
+    X3 = o.f2_scale(o.f2_mul(XY, o.f2_sub(B, F)), 2)
+    Y3 = o.f2_sub(o.f2_sqr(o.f2_add(B, F)), o.f2_scale(o.f2_sqr(E), 12))
+    Z3 = o.f2_scale(o.f2_mul(B, H), 4)
+    return (X3, Y3, Z3), line
+
+
+def dev_addition_step(T, q):
+    """tc_pairing.h miller_addition_step on residues."""
+    X, Y, Z = T
+    X2, Y2 = o.f2_scale(X, 2), o.f2_scale(Y, 2)
+    theta = o.f2_sub(Y2, o.f2_mul(q[1], Z))
+    lam = o.f2_sub(X2, o.f2_mul(q[0], Z))
+    C, D = o.f2_sqr(theta), o.f2_sqr(lam)
+    E = o.f2_mul(lam, D)
+    F = o.f2_mul(Z, C)
+    G = o.f2_mul(X2, D)
+    Hh = o.f2_sub(o.f2_add(E, F), o.f2_scale(G, 2))
+    line = (lam, o.f2_neg(theta), o.f2_sub(o.f2_mul(theta, q[0]), o.f2_mul(lam, q[1])))
+    X3 = o.f2_mul(lam, Hh)
+    Y3 = o.f2_sub(o.f2_mul(theta, o.f2_sub(G, Hh)), o.f2_mul(E, Y2))
+    Z3 = o.f2_scale(o.f2_mul(Z, E), 2)
+    return (X3, Y3, Z3), line
+
+
+def miller_affine(T):
+    X, Y, Z = T
+    zi = o.f2_inv(Z)
+    return (o.f2_scale(o.f2_mul(X, zi), 2), o.f2_scale(o.f2_mul(Y, zi), 2))
+
+
+def dev_scaled_lines(P, Qp):
+    """The 68 lines of one pair as the product evaluates them, (c2, c1 xP, c0 yP); the unit line for a skipped pair."""
+    if P is None or Qp is None:
+        return [(F2O, F2Z, F2Z)] * 68
+    T = (Qp[0], Qp[1], (2, 0))
+    out = []
+
+    def step(line):
+        c0, c1, c2 = line
+        out.append((c2, o.f2_scale(c1, P[0]), o.f2_scale(c0, P[1])))
+    for bit in bin(X >> 1)[3:]:
+        T, line = dev_doubling_step(T)
+        step(line)
+        if bit == "1":
+            T, line = dev_addition_step(T, Qp)
+            step(line)
+    T, line = dev_doubling_step(T)
+    step(line)
+    return out
+
+
+def oracle_scaled_lines(P, Qp):
+    """The oracle's (g2_prepare) lines of one pair scaled at P, in the same (d0, d1, d4) order; unit lines if skipped."""
+    if P is None or Qp is None:
+        return [(F2O, F2Z, F2Z)] * 68
+    return [(c2, o.f2_scale(c1, P[0]), o.f2_scale(c0, P[1])) for c0, c1, c2 in o.g2_prepare(Qp)]
+
+
+def line_product5(d, e):
+    """The five coefficients (a0, a1, a2, b1, b2) of (d0 + d1 v + d4 v w)(e0 + e1 v + e4 v w), as the rows hold them."""
+    m = o.f12_mul(_line014(*d), _line014(*e))
+    assert m[1][0] == F2Z
+    return [m[0][0], m[0][1], m[0][2], m[1][1], m[1][2]]
+
+
+def dev_miller_loop(pairs):
+    """The product Miller loop of tc_pairing.h miller_loop<2> on residues: the same lines, line products and squarings
+    (miller_prepare_lines + miller_accumulate and q_miller_loop compute the same value)."""
+    lines = [dev_scaled_lines(P, Qp) for P, Qp in pairs]
+    f = o.F12_ONE
+    s = 0
+    for bit in bin(X >> 1)[3:]:
+        for _ in range(2 if bit == "1" else 1):
+            for ls in lines:
+                f = o.f12_mul(f, _line014(*ls[s]))
+            s += 1
+        f = o.f12_sqr(f)
+    for ls in lines:
+        f = o.f12_mul(f, _line014(*ls[s]))
+    return o.f12_conj(f)
+
+
+def f12_is_fq2(f):
+    """f lies in Fq2 (every coefficient but c0.c0 zero)."""
+    return f[0][1] == F2Z and f[0][2] == F2Z and f[1] == o.F6_ZERO
+
+
+def f2_multiple(a, b):
+    """a = mu b for some NONZERO mu in Fq2 (a, b: tuples of Fq2 values, b not all zero)."""
+    k = next((i for i, v in enumerate(b) if v != F2Z), None)
+    if k is None or a[k] == F2Z:
+        return False
+    mu = o.f2_mul(a[k], o.f2_inv(b[k]))
+    return all(x == o.f2_mul(mu, y) for x, y in zip(a, b))
+
+
+_REF = {}
+
+
+def cached(kind, key, fn):
+    """Each reference once per process (the GPU leg checks every table at four launch sizes)."""
+    k = (kind, key)
+    if k not in _REF:
+        _REF[k] = fn()
+    return _REF[k]
+
+
+def g1_slots(P, neg_y=False):
+    """A G1 operand as the decoder leaves it: canonical coordinates; neg_y: (x, -y) with -y the limb-wise negation of y,
+    as pairing_check forms its second G1 operand (not normalised)."""
+    if P is None:
+        return [encode(0), encode(1)]
+    y = encode(P[1])
+    if neg_y:
+        y = Operand([-x for x in y.limbs], -y.hi, -y.lo, y.val)
+        check_input(y)
+    return [encode(P[0]), y]
+
+
+def g2_slots(Q):
+    if Q is None:
+        return [encode(0), encode(0), encode(1), encode(0)]
+    return [encode(Q[0][0]), encode(Q[0][1]), encode(Q[1][0]), encode(Q[1][1])]
+
+
+def check_case(pts, tag, neg1=False):
+    """pts = (P0, Q0, P1, Q1).  neg1: P1's y given as the raw negation of the canonical y of -P1 (the oracle sees P1)."""
+    P0, Q0, P1, Q1 = pts
+    slots = g1_slots(P0) + g2_slots(Q0) + g1_slots(P1 if not neg1 or P1 is None else o.E1.neg(P1), neg1) + g2_slots(Q1)
+    c = Case(slots, aux=[int(P0 is None), int(Q0 is None), int(P1 is None), int(Q1 is None)], tag=tag)
+    c.pts = pts
+    return c
+
+
+def _skip_of(pts):
+    return (pts[0] is None or pts[1] is None, pts[2] is None or pts[3] is None)
+
+
+def loop_pairs(rnd):
+    """Operand sets of the Miller loops: every skip pattern (either operand of pair 0, of pair 1, of both at infinity),
+    P1 = -P0 with Q1 = Q0 (a trivial product pairing whose f is not 1), Q1 = psi(Q0), the generators, P next to -P
+    (canonical y and p - y), and the negated y of pairing_check's second operand."""
+    g1, g2 = (lambda: g1_point(rnd)), (lambda: g2_point(rnd))
+    out = []
+    for p0, p1 in [(True, True), (False, True), (True, False), (False, False)]:
+        for which in ("P", "Q", "PQ"):
+            a, b = g1(), g2()
+            c, d = g1(), g2()
+            if not p0:
+                a = None if "P" in which else a
+                b = None if "Q" in which else b
+            if not p1:
+                c = None if "P" in which else c
+                d = None if "Q" in which else d
+            if p0 and p1 and which != "P":
+                continue
+            out.append(((a, b, c, d), "skip %s%s %s" % ("" if p0 else "0", "" if p1 else "1", which), False))
+    a, b = g1(), g2()
+    out.append(((a, b, o.E1.neg(a), b), "P1 = -P0, Q1 = Q0", False))
+    out.append(((a, b, g1(), _psi_ref(b)), "Q1 = psi(Q0)", False))
+    out.append(((o.G1_GEN, o.G2_GEN, o.G1_GEN, o.G2_GEN), "generators", False))
+    out.append(((o.G1_GEN, o.G2_GEN, o.E1.neg(o.G1_GEN), o.E2.neg(o.G2_GEN)), "-generators", False))
+    out.append(((a, b, o.E1.neg(a), g2()), "P, -P", False))
+    out.append(((a, b, a, b), "P1 = P0 negated as pairing_check does", True))
+    out.append(((a, b, g1(), g2()), "negated c.y", True))
+    return out
+
+
+def _rand_loop_case(rnd):
+    return check_case((g1_point(rnd), g2_point(rnd), g1_point(rnd), g2_point(rnd)), "random", rnd.random() < 0.3)
+
+
+def _loop_cases(rnd):
+    return [check_case(pts, tag, neg) for pts, tag, neg in loop_pairs(rnd)]
+
+
+def _dev_ml(case):
+    return cached("dev_ml", case.pts, lambda: dev_miller_loop([(case.pts[0], case.pts[1]), (case.pts[2], case.pts[3])]))
+
+
+def _oracle_ml(case):
+    return cached("o_ml", case.pts, lambda: o.miller_loop([(case.pts[0], case.pts[1]), (case.pts[2], case.pts[3])]))
+
+
+def _check_miller_value(case, out, what):
+    """f: the product's own Miller value exactly (dev_miller_loop), nonzero, an Fq2 multiple of the oracle's -- the
+    lines differ from pairing 0.16's only by Fq2 factors (projective scalings by powers of the Miller points' Fq2
+    coordinates), a factor the final exponentiation removes; no wider subfield: Fq2 is where those factors live --, and
+    exactly 1 when both pairs are skipped.  Coefficients inside the Miller-output contract."""
+    f = f12_res(out, 0)
+    expect(f != ((F2Z,) * 3, (F2Z,) * 3), case, "%s: f = 0" % what)
+    expect(f == _dev_ml(case), case, "%s: not the product's Miller value" % what)
+    ratio = o.f12_mul(f, o.f12_inv(_oracle_ml(case)))
+    expect(f12_is_fq2(ratio), case, "%s: f / oracle is not in Fq2" % what)
+    if all(_skip_of(case.pts)):
+        expect(f == o.F12_ONE, case, "%s: both pairs skipped, f != 1" % what)
+    check_bounded(case, out, 0, 12, what, limb=MF_IV[1], val_bound=MF_VAL, lo=MF_IV[0])
+
+
+@spec("MILLER_LOOP2", _rand_loop_case)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _loop_cases(rnd)
+    _check_miller_value(case, out, "miller_loop<2>")
+
+
+@spec("Q_MILLER_LOOP", _rand_loop_case)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _loop_cases(rnd)
+    _check_miller_value(case, out, "q_miller_loop")
+
+
+ROW_FIRST, ROW_PRODUCTS, MILLER_ROW_SLOTS = 8, 8 + 3 * 68, 8 + 3 * 68 + 68 * 5  # tc_pairing.h kRowFirst, ...
+
+
+def _row(rows, k):
+    return (residue(rows[k][0]), residue(rows[k][1]))
+
+
+@spec("MILLER_LINES", _rand_loop_case)
+def _(case=None, out=None, flags=None, rnd=None, rows=None):
+    """The prepared form: f as MILLER_LOOP2; every parked first-pair line an Fq2 multiple of the oracle's line of that
+    step at P0; every step's five product coefficients one Fq2 multiple of the product of the two oracle lines (a
+    skipped pair: the unit line, and the product rows of a check with both pairs skipped exactly (1, 0, 0, 0, 0))."""
+    if rnd is not None:
+        return _loop_cases(rnd)
+    _check_miller_value(case, out, "miller_prepare_lines + miller_accumulate")
+    P0, Q0, P1, Q1 = case.pts
+    l0 = cached("o_lines", (P0, Q0), lambda: oracle_scaled_lines(P0, Q0))
+    l1 = cached("o_lines", (P1, Q1), lambda: oracle_scaled_lines(P1, Q1))
+    skip = _skip_of(case.pts)
+    for s in range(68):
+        e = tuple(_row(rows, ROW_FIRST + 3 * s + i) for i in range(3))
+        if skip[0]:
+            expect(e == (F2O, F2Z, F2Z), case, "step %d: the skipped first pair's line is not the unit" % s)
+        else:
+            expect(f2_multiple(e, l0[s]), case, "step %d: parked line is not an Fq2 multiple of the oracle's" % s)
+        prod = tuple(_row(rows, ROW_PRODUCTS + 5 * s + i) for i in range(5))
+        want = line_product5(l0[s], l1[s])
+        if all(skip):
+            expect(prod == tuple(want), case, "step %d: product rows of an empty check are not 1" % s)
+        else:
+            expect(f2_multiple(prod, want), case, "step %d: product rows are not one Fq2 multiple of the oracle's" % s)
+    for k, (pt, co) in enumerate([(P0, 0), (P0, 1), (P1, 0), (P1, 1)]):
+        slot = (0 if co == 0 else 2) + (k >= 2)
+        if pt is not None:
+            expect(_row(rows, slot)[0] == pt[co], case, "row %d does not hold the G1 operand" % slot)
+
+
+def _check_bit(case, flags, nlanes):
+    want = cached("o_check", case.pts, lambda: int(o.pairing_check(*case.pts)))
+    got = [flags[4 * l] for l in range(nlanes)]
+    expect(all(g == want for g in got), case, "pairing check %s, oracle %d" % (got, want))
+
+
+def check_relations(rnd):
+    """True and false relations: e([s]P, Q) = e(P, [s]Q) and the same against s + 1; a or c at infinity; all four at
+    infinity (true); the same pair on both sides (true)."""
+    out = []
+    for _ in range(2):
+        s = rnd.randrange(1, R)
+        p, q = g1_point(rnd), g2_point(rnd)
+        sp, sq, s1q = o.E1.mul(p, s), o.E2.mul(q, s), o.E2.mul(q, s + 1)
+        out += [((sp, q, p, sq), "[s]P, Q vs P, [s]Q"), ((sp, q, p, s1q), "[s]P, Q vs P, [s+1]Q"),
+                ((None, q, p, sq), "a = O"), ((sp, q, None, sq), "c = O"), ((None, q, None, sq), "a = c = O"),
+                ((p, q, p, q), "same pair"), ((p, None, p, q), "b = O"), ((p, q, o.E1.neg(p), o.E2.neg(q)), "-P, -Q")]
+    out.append(((None, None, None, None), "all at infinity"))
+    return [check_case(pts, tag) for pts, tag in out]
+
+
+def _rand_check(rnd):
+    s = rnd.randrange(1, R)
+    p, q = g1_point(rnd), g2_point(rnd)
+    return check_case((o.E1.mul(p, s), q, p, o.E2.mul(q, s + (rnd.random() < 0.5))), "random")
+
+
+@spec("PAIRING_CHECK", _rand_check, nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return check_relations(rnd)
+    _check_bit(case, flags, 2)
+
+
+@spec("Q_PAIRING_CHECK", _rand_check, nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return check_relations(rnd)
+    _check_bit(case, flags, 4)
+
+
+# ---- the Miller steps -----------------------------------------------------------------------------------------------
+def _enc_f2(v, k, iv, push):
+    return [encode(v[0], k[0], iv, push[0]), encode(v[1], k[1], iv, push[1])]
+
+
+def miller_point_slots(rnd, T, kind):
+    """T = (X, Y, zt) residues in lazy limbs: kind "canonical", "hi" / "lo" / "alt" (every limb at that end of MPT_IV, the
+    value at k = MPT_VAL - 1 or -MPT_VAL + 1), or "random"."""
+    out = []
+    for v in T:
+        if kind == "canonical":
+            out += _enc_f2(v, (0, 0), (0.0, 1.0), (None, None))
+        elif kind == "random":
+            out += _enc_f2(v, (rnd.randint(0, MPT_VAL - 1), rnd.randint(0, MPT_VAL - 1)), MPT_IV,
+                           (rnd.choice(PUSHES), rnd.choice(PUSHES)))
+        else:
+            k = MPT_VAL - 1 if kind == "hi" else 0 if kind == "alt" else -1
+            out += _enc_f2(v, (k, k), MPT_IV, (kind, kind))
+    return out
+
+
+def _lambdas(rnd):
+    """Projective factors of T: random, 2 (zt = 2: the first step), 1, -1, u, 2^380, p - 1 + u, R^-1 (Montgomery form 1)."""
+    return [("random", (rnd.randrange(P), rnd.randrange(P))), ("2", (2, 0)), ("1", (1, 0)), ("-1", (P - 1, 0)),
+            ("u", (0, 1)), ("2^380", (1 << 380, 0)), ("p-1+u", (P - 1, 1)), ("R^-1", (RINV, RINV))]
+
+
+def miller_T(pt, lam):
+    """(lam x / 2 : lam y / 2 : lam) for the affine pt."""
+    h = o.f2_scale(lam, (P + 1) // 2)
+    return (o.f2_mul(pt[0], h), o.f2_mul(pt[1], h), lam)
+
+
+def _step_case(rnd, pt, lam, kind, q, tag):
+    T = miller_T(pt, lam)
+    slots = miller_point_slots(rnd, T, kind) + (g2_slots(q) if q is not None else [])
+    c = Case(slots, tag="%s %s" % (tag, kind))
+    c.T, c.q = T, q
+    return c
+
+
+def _step_cases(rnd, add):
+    cases = []
+    for name, lam in _lambdas(rnd):
+        for kind in ("canonical", "hi", "lo", "alt", "random"):
+            pt = g2_point(rnd)
+            q = g2_point(rnd) if add else None
+            cases.append(_step_case(rnd, pt, lam, kind, q, "lambda %s" % name))
+    # the first steps of a real loop: T = Q (zt = 2), then the points the loop reaches
+    q = g2_point(rnd)
+    T = (q[0], q[1], (2, 0))
+    for s in range(6):
+        T, _ = dev_doubling_step(T)
+        c = Case(miller_point_slots(rnd, T, "random") + (g2_slots(q) if add else []), tag="loop point %d" % s)
+        c.T, c.q = T, q if add else None
+        cases.append(c)
+    return cases
+
+
+def _rand_step(rnd, add):
+    return _step_case(rnd, g2_point(rnd), (rnd.randrange(P), rnd.randrange(P)), rnd.choice(("random", "hi", "lo")),
+                      g2_point(rnd) if add else None, "random")
+
+
+def _check_step(case, out, add):
+    T2 = tuple(f2_res(out, 2 * i) for i in range(3))
+    line = tuple(f2_res(out, 6 + 2 * i) for i in range(3))
+    x, y = miller_affine(case.T)
+    if add:
+        x2, y2 = case.q
+        want_pt = o.E2.add((x, y), case.q)
+        dx, dy = o.f2_sub(x, x2), o.f2_sub(y, y2)
+        want_line = (dx, o.f2_neg(dy), o.f2_sub(o.f2_mul(dy, x2), o.f2_mul(dx, y2)))
+    else:
+        want_pt = o.E2.dbl((x, y))
+        want_line = (o.f2_scale(y, 2), o.f2_neg(o.f2_scale(o.f2_sqr(x), 3)), o.f2_sub(o.f2_sqr(y), o.f2_scale(BTW, 3)))
+    expect(T2[2] != F2Z and miller_affine(T2) == want_pt, case, "T' is not the affine %s" % ("T + Q" if add else "2T"))
+    expect(f2_multiple(line, want_line), case, "the line is not an Fq2 multiple of the reference line")
+    # T' inside the interval declared for T: the next step takes it as it is
+    check_bounded(case, out, 0, 6, "T'", limb=MPT_IV[1], val_bound=MPT_VAL, lo=MPT_IV[0])
+    # the line goes into scale() by a canonical G1 coordinate (a product: limb bound <= PRODUCT_MAX) and into the line
+    # products: limbs of -6 J (the doubling's c1) down to -6 2^28, values up to |2 X| + |x2 zt| (the addition's lambda)
+    check_bounded(case, out, 6, 6, "line", limb=1.01, val_bound=2 * MPT_VAL + 2, lo=-6.01)
+
+
+@spec("MILLER_DBL_STEP", lambda rnd: _rand_step(rnd, False))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _step_cases(rnd, False)
+    _check_step(case, out, False)
+
+
+@spec("MILLER_ADD_STEP", lambda rnd: _rand_step(rnd, True))
+def _(case=None, out=None, flags=None, rnd=None):
+    """T + Q for T != +-Q: T = +-Q is out of contract (for subgroup points the loop's T = [k] Q with 1 < k < r - 1)."""
+    if rnd is not None:
+        return _step_cases(rnd, True)
+    _check_step(case, out, True)
+
+
+# ---- the cyclotomic exponentiation and the final exponentiation -------------------------------------------------------
+def f12_slots(rnd, f, k=None, iv=TOWER_IV, val=None):
+    """An Fq12 in 12 slots: k None (random k in {0, 1}, random pushes) or an int (every coefficient v + k p, limbs pushed
+    to alternating ends of iv)."""
+    ops = []
+    for i, v in enumerate(_flat12(f)):
+        if k is None:
+            ops.append(encode(v, rnd.randint(0, 1), iv, rnd.choice(PUSHES)))
+        else:
+            ops.append(encode(v, k, iv, ("hi", "lo", "alt")[i % 3]))
+    return ops
+
+
+def _cyclo_case(rnd, f, tag, k=None):
+    c = Case(f12_slots(rnd, f, k), tag=tag)
+    c.f = f
+    return c
+
+
+def _cyclo_elements(rnd):
+    """Cyclotomic elements: 1, a random one and its conjugate, the easy part of a real Miller value and its Frobenius image.  (The z2 = 0, z3 != 0 branch of cyclotomic_decompress3 is
+    still unexercised: no construction of a cyclotomic element with c1.c0 = 0 and c0.c2 != 0 is known here.)"""
+    one = o.F12_ONE
+    g = _cyclotomic(rnd)
+    ml = o.miller_loop([(g1_point(rnd), g2_point(rnd))])
+    e = _easy_part(ml)
+    return [("one", one), ("random", g), ("conj", o.f12_conj(g)), ("easy part of a Miller value", e),
+            ("frobenius", o.f12_frobenius(e, 1)), ("square of one", o.f12_sqr(one))]
+
+
+def _easy_part(f):
+    r = o.f12_mul(o.f12_conj(f), o.f12_inv(f))
+    return o.f12_mul(o.f12_frobenius(r, 2), r)
+
+
+def _expx_cases(rnd):
+    cases = []
+    for tag, f in _cyclo_elements(rnd):
+        cases.append(_cyclo_case(rnd, f, tag))
+        cases.append(_cyclo_case(rnd, f, tag + " k = 1", 1))
+    return cases
+
+
+def _expx_spec(name, e):
+    def fn(case=None, out=None, flags=None, rnd=None):
+        if rnd is not None:
+            return _expx_cases(rnd)
+        want = cached("expx", (case.f, e), lambda: o.f12_conj(o.f12_pow(case.f, e)))
+        _check_tower(case, out, 0, _flat12(want), 12, name, limb=FE_LIMB, val_bound=FE_VAL, lo=-FE_LIMB)
+    spec(name, lambda rnd: _cyclo_case(rnd, _cyclotomic(rnd), "random"))(fn)
+
+
+_expx_spec("CYCLO_EXP_BY_X", X)
+_expx_spec("CYCLO_EXP_BY_X_HALF", X >> 1)
+_expx_spec("Q_EXP_BY_X", X)
+_expx_spec("Q_EXP_BY_X_HALF", X >> 1)
+
+
+def _fe_case(rnd, f, tag, k=None, cube=False):
+    """f at the Miller-output contract: k None (canonical), or every coefficient v + k p with limbs pushed to the ends of
+    MF_IV."""
+    if k is None:
+        ops = [encode(v) for v in _flat12(f)]
+    else:
+        ops = [encode(v, k, MF_IV, ("hi", "lo", "alt")[i % 3]) for i, v in enumerate(_flat12(f))]
+    c = Case(ops, tag=tag)
+    c.f, c.cube = f, cube
+    return c
+
+
+def _fe_cases(rnd):
+    z6 = o.F6_ZERO
+    r6 = tuple((rnd.randrange(P), rnd.randrange(P)) for _ in range(3))
+    ml = o.miller_loop([(g1_point(rnd), g2_point(rnd))])
+    a, b = g1_point(rnd), g2_point(rnd)
+    ml_trivial = dev_miller_loop([(a, b), (o.E1.neg(a), b)])
+    fs = [("1", o.F12_ONE), ("-1", ((o.f2_neg(F2O), F2Z, F2Z), z6)), ("in Fq2", (((rnd.randrange(P), rnd.randrange(P)), F2Z, F2Z), z6)),
+          ("in Fq", (((rnd.randrange(P), 0), F2Z, F2Z), z6)), ("in Fq6", (r6, z6)), ("c1 w", (z6, r6)),
+          ("oracle Miller value", ml), ("product Miller value, P1 = -P0", ml_trivial),
+          ("product Miller value", dev_miller_loop([(g1_point(rnd), g2_point(rnd)), (g1_point(rnd), g2_point(rnd))]))]
+    cases = []
+    for i, (tag, f) in enumerate(fs):
+        cases.append(_fe_case(rnd, f, tag, cube=i in (6, 8)))
+        for k in (MF_VAL - 1, 1):
+            cases.append(_fe_case(rnd, f, "%s, v + %d p" % (tag, k), k))
+    return cases
+
+
+def _check_fe(case, out, flags, nlanes, what):
+    want = cached("fe", case.f, lambda: o.final_exponentiation_chain(case.f))
+    got = f12_res(out, 0)
+    expect(got == want, case, "%s: not the oracle's chain" % what)
+    if case.cube:  # the factor 3 of the source comment
+        plain = cached("fe_plain", case.f, lambda: o.final_exponentiation(case.f))
+        expect(got == o.f12_mul(plain, o.f12_sqr(plain)), case, "%s: not the pairing cubed" % what)
+    check_bounded(case, out, 0, 12, what, limb=FE_LIMB, val_bound=FE_VAL, lo=-FE_LIMB)
+    is_one = [flags[4 * l] for l in range(nlanes)]
+    expect(all(v == int(want == o.F12_ONE) for v in is_one), case, "%s: == 1 gave %s" % (what, is_one))
+
+
+def _rand_fe(rnd):
+    return _fe_case(rnd, _rand_f12(rnd), "random", rnd.choice([None, 1, MF_VAL - 1]))
+
+
+@spec("FINAL_EXP", _rand_fe, nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _fe_cases(rnd)
+    _check_fe(case, out, flags, 2, "final_exponentiation")
+
+
+@spec("Q_FINAL_EXP", _rand_fe, nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return _fe_cases(rnd)
+    _check_fe(case, out, flags, 4, "q_final_exponentiation")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # tables and sizes
 # ---------------------------------------------------------------------------------------------------------------------
 def table(op, seed=1):
@@ -2214,12 +2773,12 @@ def sizes(op, n):
     return [1, wave // 2 + 3, wave, n]
 
 
-def check(op, cases, out, flags):
+def check(op, cases, out, flags, rows=None):
     fn, _, _ = SPECS[op]
     bad = []
     for j, c in enumerate(cases):
         try:
-            fn(case=c, out=out[j], flags=flags[j])
+            fn(case=c, out=out[j], flags=flags[j], **({} if rows is None else {"rows": rows[j]}))
         except Fail as e:
             bad.append("job %d: %s" % (j, e))
     return bad
@@ -2228,8 +2787,8 @@ def check(op, cases, out, flags):
 def _host_main(op):
     lib = ctypes.CDLL(build_host())
     cases = table(op)
-    out, flags = run_host(lib, op, cases)
-    bad = check(op, cases, out, flags)
+    out, flags, rows = run_host(lib, op, cases)
+    bad = check(op, cases, out, flags, rows)
     for b in bad[:20]:
         print(b)
     print("%s: %d cases, %d failed" % (op, len(cases), len(bad)))

@@ -101,3 +101,33 @@ def test_wave_layout_of_per_wave_decisions(op):
     assert len(mixed) >= 2, op
     assert {path_of(c) for w in mixed for c in w} >= set(makers)
     assert len(cases) % 64 and dc.sizes(op, len(cases))[:3] == [1, 35, 64]
+
+
+def test_miller_reference_model_agrees_with_the_oracle():
+    """dev_miller_loop -- the product's step formulas on residues, the exact reference of MILLER_LOOP2, MILLER_LINES and
+    Q_MILLER_LOOP -- differs from the oracle's Miller loop by a factor in Fq2 (and with a conjugation dropped it would
+    not), gives the same pairing after the final exponentiation, and is 1 for an empty product.  Its lines are Fq2
+    multiples of the oracle's, step by step."""
+    import random
+    o = dc.o
+    rnd = random.Random(5)
+    p0, q0, p1, q1 = dc.g1_point(rnd), dc.g2_point(rnd), dc.g1_point(rnd), dc.g2_point(rnd)
+    f = dc.dev_miller_loop([(p0, q0), (p1, q1)])
+    g = o.miller_loop([(p0, q0), (p1, q1)])
+    assert dc.f12_is_fq2(o.f12_mul(f, o.f12_inv(g))) and not dc.f12_is_fq2(f)
+    assert not dc.f12_is_fq2(o.f12_mul(o.f12_conj(f), o.f12_inv(g)))
+    assert o.final_exponentiation_chain(f) == o.final_exponentiation_chain(g)
+    assert dc.dev_miller_loop([(None, q0), (p1, None)]) == o.F12_ONE
+    assert all(dc.f2_multiple(a, b) for a, b in zip(dc.dev_scaled_lines(p0, q0), dc.oracle_scaled_lines(p0, q0)))
+
+
+def test_pairing_tables_mix_skip_patterns_and_quad_sizes():
+    """The Miller-loop tables hold every skip pattern (pair 0, pair 1, both, none), and the first wave already mixes all
+    four (skip is per-lane data that miller_apply_lines branches on).  Quad ops run four lanes per job: 16 per wave."""
+    for op in ("MILLER_LOOP2", "MILLER_LINES", "Q_MILLER_LOOP"):
+        cases = dc.table(op)
+        wave = 64 // dc.lanes(op)
+        assert {dc._skip_of(c.pts) for c in cases[:wave]} == {(a, b) for a in (False, True) for b in (False, True)}, op
+    assert [dc.lanes(op) for op in ("MILLER_LOOP2", "FINAL_EXP", "Q_MILLER_LOOP", "Q_PAIRING_CHECK")] == [2, 2, 4, 4]
+    n = len(dc.table("Q_FINAL_EXP"))
+    assert n % 16 and dc.sizes("Q_FINAL_EXP", n)[:3] == [1, 11, 16]

@@ -31,9 +31,9 @@ def test_device_primitive_conforms(lib, op):
     cases = dc.table(op)
     for n in dc.sizes(op, len(cases)):
         try:
-            out, flags = dc.run_device(lib, op, cases[:n])
+            out, flags, rows = dc.run_device(lib, op, cases[:n])
         except AssertionError as e:
             _state["hip_error"] = str(e)
             raise
-        bad = dc.check(op, cases[:n], out, flags)
+        bad = dc.check(op, cases[:n], out, flags, rows)
         assert not bad, "%s at n = %d: %d of %d jobs wrong\n%s" % (op, n, len(bad), n, "\n".join(bad[:12]))
