@@ -23,11 +23,20 @@
 // per job) and tc_quad.h (ops 90 on: a quad of four lanes per job, pair A lanes 0, 1 and pair B lanes 2, 3).  A check's
 // operands: G1 point k at slots 6 k, 6 k + 1 and G2 point k at slots 6 k + 2 .. 6 k + 5 (k = 0, 1), aux[2 k] and
 // aux[2 k + 1] their point-at-infinity flags.  MILLER_LINES also hands back the row block of miller_prepare_lines.
+//
+// The point-multiplication block (ops 140 on: G1, one lane per job; ops 160 on: G2, a lane pair per job) applies the code
+// that turns digits and group operations into a multiple: table builders, common-Z bookkeeping, the branch-free ladders with
+// their safe twins, GLS / GLV multiplication, cofactor clearing, the Straus combiners and the [1 / D] step of the share
+// combiner.  Points go in as limbs (affine: x, y; Jacobian: x, y, z; infinity flags as bit masks in aux), scalars as raw
+// words in the slot after the points.  An op hands back the Jacobian result as the routine returns it (slot 0 on), then
+// jac_to_affine of it (what every shipped job body does next) with the infinity bit in flag 0.  Ops whose routine keeps
+// a table in the arena of tc_table.h (conf_needs_table) run with a table slot held, as the product's kernels do.
 #pragma once
 #include "../../threshold_crypto_amd/csrc/tc_codec.h"  // (tc_quad.h job_pairing_check_quad_io decodes)
 #include "../../threshold_crypto_amd/csrc/tc_quad.h"
 #include "../../threshold_crypto_amd/csrc/tc_sqrt.h"
 #include "../../threshold_crypto_amd/csrc/tc_msm.h"
+#include "../../threshold_crypto_amd/csrc/tc_dkg.h"
 
 namespace tc {
 namespace conf {
@@ -61,13 +70,25 @@ enum Op {
   DIV_BY_X_ABS = 110, GLS_DECOMPOSE, GLS_DECOMPOSE_ODD, SAC_RECODE4, GLV_DECOMPOSE, GLV_RECODE_SIGN_ALIGNED, MSM_G1_RECODE,
   LAGRANGE_COEFF = 120, LAGRANGE_COEFF_FR, LAGRANGE_ALL, LAGRANGE_SPLIT, LAGRANGE_SMALL_COEFFS, COMBINE_CLASS,
   FR_INVERSE_OF_SMALL, GCD_U64,
+  // point multiplication on G1, one lane per job
+  G1_ADD_AFFINE = 140, G1_COMMON_Z, G1_MUL_BY_X_ABS, G1_MUL_GLV, G1_MUL_GLV_JAC, G1_MUL_GLV_ARENA, G1_LINCOMB_CHUNK4,
+  G1_STRAUS_SMALL, G1_STRAUS_SMALL_INLINE, G1_COMBINE_DIVIDE, G1_COMBINE_DIVIDE_ARENA, G1_MUL_U64,
+  // point multiplication on G2 (lane pair)
+  G2_ADD_AFFINE = 160, G2_COMMON_Z, G2_MUL_BY_X_ABS, G2_PSI_JAC, G2_GLS_BASES, G2_SAC_TABLE, G2_JOINT_MUL4, G2_MUL_GLS,
+  G2_MUL_GLS_JAC, G2_CLEAR_COFACTOR, G2_STRAUS_SMALL, G2_COMBINE_DIVIDE,
 };
 
 // the quad ops (tc_quad.h): four lanes per job on the device, two threads per job on the host
 TC_HD constexpr bool conf_quad(int op) { return op >= Q_MILLER_LOOP && op < FR_ADD; }
 // lanes per job on the device: Fq, G1 and the scalar block one, everything that holds Fq2 values a lane pair
 TC_HD constexpr int conf_lanes(int op) {
-  return conf_quad(op) ? kQuadLanes : (op >= FQ2_MUL && op < G1_DBL) || (op >= G2_DBL && op < FR_ADD) ? kG2Lanes : 1;
+  return conf_quad(op) ? kQuadLanes
+         : (op >= FQ2_MUL && op < G1_DBL) || (op >= G2_DBL && op < FR_ADD) || op >= G2_ADD_AFFINE ? kG2Lanes : 1;
+}
+// ops whose routine keeps a table in the arena (tc_table.h): the kernel holds a table slot while the op runs
+TC_HD constexpr bool conf_needs_table(int op) {
+  return op == G1_MUL_GLV_ARENA || op == G1_COMBINE_DIVIDE_ARENA || op == G2_SAC_TABLE || op == G2_JOINT_MUL4 ||
+         op == G2_MUL_GLS || op == G2_MUL_GLS_JAC || op == G2_COMBINE_DIVIDE;
 }
 // ops that take a row block (tc_pairing.h Fq2Rows): device, kConfLineWords words per lane in the row layout of
 // k_miller_lines; host, kMillerRowSlots Fq2 per job
@@ -103,6 +124,10 @@ struct Ctx {
   // the scalar block: u64 k of the raw words from slot 0 on (two words each, low word first)
   TC_HD uint64_t u64(int k) const {
     const uint32_t* w = words(0);
+    return (uint64_t)w[2 * k] | ((uint64_t)w[2 * k + 1] << 32);
+  }
+  TC_HD uint64_t u64_at(int s, int k) const {  // u64 k of the raw words from slot s on
+    const uint32_t* w = words(s);
     return (uint64_t)w[2 * k] | ((uint64_t)w[2 * k + 1] << 32);
   }
   TC_HD Fr fr(int s) const {  // a Montgomery-form Fr, raw words
@@ -419,6 +444,163 @@ TC_HD void conf_scalar(Ctx& c) {
   }
 }
 
+// ---- the point-multiplication block: table builders, ladders, GLS / GLV, cofactor clearing, Straus, [1 / D] ----------
+// the Jacobian result as the routine returns it (slots 0 .. 3w), jac_to_affine of it (3w .. 5w), flag 0 = infinity
+template <class F>
+TC_HD void put_result(Ctx& c, const Jac<F>& r) {
+  constexpr int w = Width<F>::n;
+  put_jac(c, 0, r);
+  const Affine<F> a = jac_to_affine(r);
+  put_aff(c, 3 * w, a);
+  c.flag(0, a.inf);
+}
+// N affine points at slots 2w k, bit k of mask = point k at infinity
+template <class F, int N>
+TC_HD void affs_at(const Ctx& c, int mask, Affine<F>* pts) {
+  constexpr int w = Width<F>::n;
+  TC_UNROLL for (int k = 0; k < N; k++) pts[k] = aff_at<F>(c, 2 * w * k, (mask >> k) & 1);
+}
+// a point (x, y) of the curve scaled by zc, back on the original curve and affine
+template <class F>
+TC_HD Affine<F> conf_unscale(const Affine<F>& p, const F& zc) {
+  Jac<F> j{p.x, p.y, zc};
+  if (p.inf) j = Jac<F>::infinity();
+  return jac_to_affine(j);
+}
+
+// jac_batch_to_common_z on aux[0] = n Jacobian points (slots 3w i) + affine_scale_z of one more affine point (slot 3w NMAX,
+// aux[1] = at infinity).  out: (x_i, y_i) at 2w i, zc at 2w NMAX, the scaled point after it, then point n - 1 and the scaled
+// point brought back to the original curve; flag 0 = the infinity bits of the n points, flag 1 = the extra point's
+// (G2: n <= 6 -- seven Jacobian points would need 42 input slots; G2_SAC_TABLE runs the routine at n = 7)
+template <class F>
+TC_HD void conf_common_z(Ctx& c) {
+  constexpr int w = Width<F>::n, NMAX = w == 1 ? 7 : 6;
+  const int n = c.aux[0];
+  Jac<F> in[NMAX];
+  Affine<F> out[NMAX];
+  TC_NOUNROLL for (int i = 0; i < n; i++) in[i] = jac_at<F>(c, 3 * w * i);
+  const F zc = jac_batch_to_common_z(in, out, n);
+  const F zc2 = zc.sqr();
+  const Affine<F> e = affine_scale_z(aff_at<F>(c, 3 * w * NMAX, c.aux[1]), zc2, zc2 * zc);
+  int inf = 0;
+  TC_NOUNROLL for (int i = 0; i < n; i++) {
+    put_aff(c, 2 * w * i, out[i]);
+    inf |= (int)out[i].inf << i;
+  }
+  c.put(2 * w * NMAX, zc);
+  put_aff(c, 2 * w * NMAX + w, e);
+  put_aff(c, 2 * w * NMAX + 3 * w, conf_unscale(out[n - 1], zc));
+  put_aff(c, 2 * w * NMAX + 5 * w, conf_unscale(e, zc));
+  c.flag(0, inf);
+  c.flag(1, e.inf);
+}
+
+// straus_small on aux[0] = K points (slots 2w k, aux[1] their infinity bits) and K u64 (the words of slot 8w); G2 through
+// straus_small_call, as job_combine_small_io calls it
+template <class F, int K, bool INLINE_SAFE>
+TC_HD Jac<F> conf_straus_k(const Ctx& c) {
+  constexpr int w = Width<F>::n;
+  Affine<F> pts[K];
+  uint64_t cs[K];
+  affs_at<F, K>(c, c.aux[1], pts);
+  TC_UNROLL for (int k = 0; k < K; k++) cs[k] = c.u64_at(8 * w, k);
+  if constexpr (w > 1) {
+    return straus_small_call<F, K>(pts, cs);
+  } else {
+    return straus_small<F, K, INLINE_SAFE>(pts, cs);
+  }
+}
+template <class F, bool INLINE_SAFE>
+TC_HD void conf_straus(Ctx& c) {
+  Jac<F> r = Jac<F>::infinity();
+  if (c.aux[0] == 2) r = conf_straus_k<F, 2, INLINE_SAFE>(c);
+  if (c.aux[0] == 3) r = conf_straus_k<F, 3, INLINE_SAFE>(c);
+  if (c.aux[0] == 4) r = conf_straus_k<F, 4, INLINE_SAFE>(c);
+  put_result(c, r);
+}
+
+template <int OP>
+TC_HD void conf_mul(Ctx& c) {
+  if constexpr (OP == G1_ADD_AFFINE) {
+    put_result(c, jac_add_affine(aff_at<Fq>(c, 0, c.aux[0]), aff_at<Fq>(c, 2, c.aux[1])));
+  } else if constexpr (OP == G2_ADD_AFFINE) {
+    put_result(c, jac_add_affine(aff_at<Fq2>(c, 0, c.aux[0]), aff_at<Fq2>(c, 4, c.aux[1])));
+  } else if constexpr (OP == G1_COMMON_Z) {
+    conf_common_z<Fq>(c);
+  } else if constexpr (OP == G2_COMMON_Z) {
+    conf_common_z<Fq2>(c);
+  } else if constexpr (OP == G1_MUL_BY_X_ABS) {
+    put_result(c, g1_mul_by_x_abs(jac_at<Fq>(c, 0)));
+  } else if constexpr (OP == G2_MUL_BY_X_ABS) {
+    put_result(c, g2_mul_by_x_abs(jac_at<Fq2>(c, 0)));
+  } else if constexpr (OP == G2_PSI_JAC) {
+    put_result(c, g2_psi(jac_at<Fq2>(c, 0)));
+  } else if constexpr (OP == G2_GLS_BASES) {  // out: the four bases at 4 k, flag 0 = their infinity bits
+    G2Affine base[4];
+    g2_gls_bases(aff_at<Fq2>(c, 0, c.aux[0]), base);
+    int inf = 0;
+    TC_UNROLL for (int k = 0; k < 4; k++) {
+      put_aff(c, 4 * k, base[k]);
+      inf |= (int)base[k].inf << k;
+    }
+    c.flag(0, inf);
+  } else if constexpr (OP == G2_SAC_TABLE) {
+    // four affine bases (slots 4 k, aux[0] their infinity bits); out: entry m at 4 m, read back through entry(m), zc at 32,
+    // entry 7 brought back to the original curve at 34; flag 0 = the entries' infinity bits
+    G2Affine base[4];
+    affs_at<Fq2, 4>(c, c.aux[0], base);
+    G2SacTable t;
+    g2_sac_table(base, t);
+    int inf = 0;
+    TC_NOUNROLL for (int m = 0; m < 8; m++) {
+      const G2Affine e = t.entry(m);
+      put_aff(c, 4 * m, e);
+      inf |= (int)e.inf << m;
+    }
+    c.put(32, t.zc);
+    put_aff(c, 34, conf_unscale(t.entry(7), t.zc));
+    c.flag(0, inf);
+  } else if constexpr (OP == G2_JOINT_MUL4) {  // four independent bases, four u64 digits (the words of slot 16)
+    G2Affine base[4];
+    affs_at<Fq2, 4>(c, c.aux[0], base);
+    const uint64_t d[4] = {c.u64_at(16, 0), c.u64_at(16, 1), c.u64_at(16, 2), c.u64_at(16, 3)};
+    put_result(c, g2_joint_mul4(base, d));
+  } else if constexpr (OP == G2_MUL_GLS) {
+    put_result(c, g2_mul_gls(aff_at<Fq2>(c, 0, c.aux[0]), c.words(4)));
+  } else if constexpr (OP == G2_MUL_GLS_JAC) {
+    put_result(c, g2_mul_gls(jac_at<Fq2>(c, 0), c.words(6)));
+  } else if constexpr (OP == G2_CLEAR_COFACTOR) {
+    put_result(c, g2_clear_cofactor(aff_at<Fq2>(c, 0, c.aux[0]), c.aux[1] != 0));
+  } else if constexpr (OP == G1_MUL_GLV) {
+    put_result(c, g1_mul_glv(aff_at<Fq>(c, 0, c.aux[0]), c.words(2)));
+  } else if constexpr (OP == G1_MUL_GLV_JAC) {
+    put_result(c, g1_mul_glv(jac_at<Fq>(c, 0), c.words(3)));
+  } else if constexpr (OP == G1_MUL_GLV_ARENA) {
+    put_result(c, g1_mul_glv_arena(aff_at<Fq>(c, 0, c.aux[0]), c.words(2)));
+  } else if constexpr (OP == G1_LINCOMB_CHUNK4) {  // four points (aux[0] their infinity bits), scalar k in slot 8 + k
+    G1Affine pts[4];
+    affs_at<Fq, 4>(c, c.aux[0], pts);
+    uint32_t sc[4][8];
+    TC_UNROLL for (int k = 0; k < 4; k++)
+      TC_UNROLL for (int i = 0; i < 8; i++) sc[k][i] = c.words(8 + k)[i];
+    put_result(c, lincomb_chunk4(pts, sc));
+  } else if constexpr (OP == G1_STRAUS_SMALL) {
+    conf_straus<Fq, false>(c);
+  } else if constexpr (OP == G1_STRAUS_SMALL_INLINE) {
+    conf_straus<Fq, true>(c);
+  } else if constexpr (OP == G2_STRAUS_SMALL) {
+    conf_straus<Fq2, false>(c);
+  } else if constexpr (OP == G1_COMBINE_DIVIDE) {  // Q, D in the words of the next slot, aux[0] = d_neg
+    put_result(c, combine_divide(jac_at<Fq>(c, 0), c.u64_at(3, 0), c.aux[0] != 0));
+  } else if constexpr (OP == G1_COMBINE_DIVIDE_ARENA) {
+    put_result(c, combine_divide_arena(jac_at<Fq>(c, 0), c.u64_at(3, 0), c.aux[0] != 0));
+  } else if constexpr (OP == G2_COMBINE_DIVIDE) {
+    put_result(c, combine_divide(jac_at<Fq2>(c, 0), c.u64_at(6, 0), c.aux[0] != 0));
+  } else if constexpr (OP == G1_MUL_U64) {
+    put_result(c, g1_mul_u64(jac_at<Fq>(c, 0), c.u64_at(3, 0)));
+  }
+}
+
 template <int OP>
 TC_HD void conf_op(Ctx& c) {
   // ---- Fq ---------------------------------------------------------------------------------------------------------
@@ -561,8 +743,11 @@ TC_HD void conf_op(Ctx& c) {
   } else if constexpr (OP >= MILLER_DBL_STEP && OP < FR_ADD) {
     conf_pairing<OP>(c);
   // ---- the scalar block -------------------------------------------------------------------------------------------
-  } else if constexpr (OP >= FR_ADD) {
+  } else if constexpr (OP >= FR_ADD && OP < G1_ADD_AFFINE) {
     conf_scalar<OP>(c);
+  // ---- the point-multiplication block -------------------------------------------------------------------------------
+  } else if constexpr (OP >= G1_ADD_AFFINE) {
+    conf_mul<OP>(c);
   }
 }
 
@@ -580,7 +765,11 @@ TC_HD void conf_op(Ctx& c) {
   X(FR_ADD) X(FR_SUB) X(FR_MUL) X(FR_SQR) X(FR_INV) X(FR_FROM_CANONICAL) X(FR_TO_CANONICAL) X(FR_FROM_U64) X(FR_FROM_LE32)   \
   X(FR_SCALE_COFACTOR_FIX) X(DIV_BY_X_ABS) X(GLS_DECOMPOSE) X(GLS_DECOMPOSE_ODD) X(SAC_RECODE4) X(GLV_DECOMPOSE)              \
   X(GLV_RECODE_SIGN_ALIGNED) X(MSM_G1_RECODE) X(LAGRANGE_COEFF) X(LAGRANGE_COEFF_FR) X(LAGRANGE_ALL) X(LAGRANGE_SPLIT)      \
-  X(LAGRANGE_SMALL_COEFFS) X(COMBINE_CLASS) X(FR_INVERSE_OF_SMALL) X(GCD_U64)
+  X(LAGRANGE_SMALL_COEFFS) X(COMBINE_CLASS) X(FR_INVERSE_OF_SMALL) X(GCD_U64)                                           \
+  X(G1_ADD_AFFINE) X(G1_COMMON_Z) X(G1_MUL_BY_X_ABS) X(G1_MUL_GLV) X(G1_MUL_GLV_JAC) X(G1_MUL_GLV_ARENA)                \
+  X(G1_LINCOMB_CHUNK4) X(G1_STRAUS_SMALL) X(G1_STRAUS_SMALL_INLINE) X(G1_COMBINE_DIVIDE) X(G1_COMBINE_DIVIDE_ARENA)     \
+  X(G1_MUL_U64) X(G2_ADD_AFFINE) X(G2_COMMON_Z) X(G2_MUL_BY_X_ABS) X(G2_PSI_JAC) X(G2_GLS_BASES) X(G2_SAC_TABLE)        \
+  X(G2_JOINT_MUL4) X(G2_MUL_GLS) X(G2_MUL_GLS_JAC) X(G2_CLEAR_COFACTOR) X(G2_STRAUS_SMALL) X(G2_COMBINE_DIVIDE)
 
 }  // namespace conf
 }  // namespace tc

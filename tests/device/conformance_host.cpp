@@ -5,6 +5,7 @@
 //     hs_pairing_check_quad); the thread of pair B stands for lanes 2, 3
 //   rows (conf_needs_rows ops): kMillerRowSlots Fq2 per job, poisoned before the job, handed back in the device leg's
 //     per-job layout (n x kMillerRowSlots x 2 x 14 limbs)
+//   tables (conf_needs_table ops): tc_table.h gives the thread a table; it is poisoned before every job
 #include "conformance.h"
 
 #include <string.h>
@@ -26,6 +27,10 @@ static void run(int n, const int32_t* in, const float* range, const int32_t* aux
       conf_op<OP>(c);
     };
     if (!mem.empty()) memset((void*)mem.data(), 0x5A, mem.size() * sizeof(Fq2));
+    if (conf_needs_table(OP)) {
+      memset(pair_table(), 0x5A, kPairTableWords * sizeof(tbl_word));
+      memset(lane_table(), 0x5A, kLaneTableWords * sizeof(tbl_word));
+    }
     if constexpr (conf_quad(OP)) {
       QuadSim sim;
       auto pair = [&](int hi) {

@@ -19,6 +19,13 @@ final exponentiation and the check itself against the oracle's pairing: a Miller
 (dev_miller_loop: the shipped step formulas on residues) and differ from the oracle's by a factor in Fq2; GT values and
 check bits must equal the oracle's exactly.  MILLER_LINES also hands back its row block (prepared lines, line products).
 
+The point-multiplication block (ops 140 on: G1, one lane per job; 160 on: G2, a lane pair) checks the routines that turn
+digits and group operations into a multiple -- table builders, common-Z bookkeeping, the branch-free ladders and their
+safe twins, GLS / GLV, cofactor clearing, the Straus combiners, the [1 / D] step -- against E.mul / E.add of the oracle.
+Which path a case takes (the branch-free pass alone, or the safe ladder after a special case) comes from a Python model
+that walks the ladder's columns on the oracle's group law (the *_model functions); ops with a table in the arena of
+tc_table.h (NEEDS_TABLE) run with a slot held, and the device leg fails if a slot stays marked in use.
+
     python tests/device_conformance.py host OPNAME      (the host leg of one op; exit status 0 = every case passed)
 """
 import ctypes
@@ -78,15 +85,25 @@ OPS = dict(
     DIV_BY_X_ABS=110, GLS_DECOMPOSE=111, GLS_DECOMPOSE_ODD=112, SAC_RECODE4=113, GLV_DECOMPOSE=114,
     GLV_RECODE_SIGN_ALIGNED=115, MSM_G1_RECODE=116,
     LAGRANGE_COEFF=120, LAGRANGE_COEFF_FR=121, LAGRANGE_ALL=122, LAGRANGE_SPLIT=123, LAGRANGE_SMALL_COEFFS=124,
-    COMBINE_CLASS=125, FR_INVERSE_OF_SMALL=126, GCD_U64=127)
+    COMBINE_CLASS=125, FR_INVERSE_OF_SMALL=126, GCD_U64=127,
+    G1_ADD_AFFINE=140, G1_COMMON_Z=141, G1_MUL_BY_X_ABS=142, G1_MUL_GLV=143, G1_MUL_GLV_JAC=144, G1_MUL_GLV_ARENA=145,
+    G1_LINCOMB_CHUNK4=146, G1_STRAUS_SMALL=147, G1_STRAUS_SMALL_INLINE=148, G1_COMBINE_DIVIDE=149,
+    G1_COMBINE_DIVIDE_ARENA=150, G1_MUL_U64=151,
+    G2_ADD_AFFINE=160, G2_COMMON_Z=161, G2_MUL_BY_X_ABS=162, G2_PSI_JAC=163, G2_GLS_BASES=164, G2_SAC_TABLE=165,
+    G2_JOINT_MUL4=166, G2_MUL_GLS=167, G2_MUL_GLS_JAC=168, G2_CLEAR_COFACTOR=169, G2_STRAUS_SMALL=170,
+    G2_COMBINE_DIVIDE=171)
 
 
 def lanes(op):
     i = OPS[op]
-    return 4 if 90 <= i < 100 else 2 if (20 <= i < 60 or 70 <= i < 90) else 1
+    return 4 if 90 <= i < 100 else 2 if (20 <= i < 60 or 70 <= i < 90 or i >= 160) else 1
 
 
 NEEDS_ROWS = {"MILLER_LINES"}  # conformance.h conf_needs_rows
+# conformance.h conf_needs_table: the device leg runs these with a slot of a table arena held (tc_table.h)
+NEEDS_TABLE = {"G1_MUL_GLV_ARENA", "G1_COMBINE_DIVIDE_ARENA", "G2_SAC_TABLE", "G2_JOINT_MUL4", "G2_MUL_GLS", "G2_MUL_GLS_JAC",
+               "G2_COMBINE_DIVIDE"}
+SLOT_LEAK = -2  # conformance.hip kConfSlotLeak: a table slot was still marked in use after the run
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -296,6 +313,7 @@ def run_device(lib, op, cases):
     inp, _, aux, out, flags = pack(cases)
     rows = _rows_buf(op, len(cases))
     rc = lib.tc_conf_run(OPS[op], len(cases), _p(inp), _p(aux), _p(out), _p(flags), None if rows is None else _p(rows))
+    assert rc != SLOT_LEAK, "op %s left a table slot marked in use" % op
     assert rc == 0, "HIP error %d in op %s" % (rc, op)
     return out, flags, rows
 
@@ -2718,6 +2736,783 @@ def _(case=None, out=None, flags=None, rnd=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the point-multiplication block: table builders, ladders, GLS / GLV, cofactor clearing, Straus, the [1 / D] step
+# ---------------------------------------------------------------------------------------------------------------------
+H1, H2 = o.H1, o.H2
+SMALL_ORDERS = {1: (3, 11, 10177, 859267, 52437899), 2: (13, 23, 2713, 11953, 262069)}  # small prime factors of the cofactors
+assert all(H1 % l == 0 for l in SMALL_ORDERS[1]) and all(H2 % l == 0 for l in SMALL_ORDERS[2])
+PSI_CX = o.f2_inv(o.f2_pow(o.XI, (P - 1) // 3))  # tc_constants.h PSI_CX / PSI_CY
+PSI_CY = o.f2_inv(o.f2_pow(o.XI, (P - 1) // 2))
+COFACTOR_FIX_SHORT = (X + 1) // 3  # tc_constants.h G2_COFACTOR_FIX_SHORT
+CLEAR_NOFIX = 3 * (X2 - 1) * H2  # g2_clear_cofactor(fix = false) = [3 (x^2 - 1) h2] P
+
+
+def psi(p):
+    """psi on ALL of E'(Fq2) (untwist, Frobenius, twist); on G2 it is [x] (_psi_ref)."""
+    return None if p is None else (o.f2_mul(o.f2_conj(p[0]), PSI_CX), o.f2_mul(o.f2_conj(p[1]), PSI_CY))
+
+
+def curve_point(fld, rnd):
+    """A point of the curve outside the order-r subgroup."""
+    return _pt(fld, rnd, False)
+
+
+def small_order_point(fld, rnd, l):
+    """A point of prime order l (l a factor of the cofactor): a random point's l-primary part, brought down to order l."""
+    n = (H1 if fld.w == 1 else H2) * R
+    while n % l == 0:
+        n //= l
+    while True:
+        p = fld.E.mul(curve_point(fld, rnd), n)
+        while p is not None and fld.E.mul(p, l) is not None:
+            p = fld.E.mul(p, l)
+        if p is not None:
+            return p
+
+
+_SMALL = {}
+
+
+def small_points(fld):
+    """One point of every small order (cached), and for G1 the order-3 points (0, +-2)."""
+    if fld.w not in _SMALL:
+        rnd = random.Random("small-%d" % fld.w)
+        pts = [small_order_point(fld, rnd, l) for l in SMALL_ORDERS[fld.w]]
+        if fld.w == 1:
+            pts += [(0, 2), (0, P - 2)]
+        _SMALL[fld.w] = pts
+    return _SMALL[fld.w]
+
+
+def whole_curve_points(fld, rnd):
+    """Operands of the routines defined on the whole curve: infinity, subgroup, outside it, small order."""
+    return [None, _pt(fld, rnd), curve_point(fld, rnd), curve_point(fld, rnd)] + small_points(fld)
+
+
+def aff_slots(fld, rnd, pt, canon=False):
+    """An affine operand: canonical (a decoded point) or lazy inside the coordinate contract (values up to 2 p + v, what
+    products and table loads hand on); infinity as (0, 1) with its flag in aux."""
+    pt = pt if pt is not None else (fld.F.zero, fld.F.one)
+    cs = [pt[0], pt[1]] if fld.w == 1 else list(pt[0]) + list(pt[1])
+    if canon:
+        return [encode(c) for c in cs]
+    return [encode(c, rnd.randint(0, 2), PT_IV, rnd.choice(PUSHES)) for c in cs]
+
+
+def inf_mask(pts):
+    return sum(1 << i for i, p in enumerate(pts) if p is None)
+
+
+def mcase(slots, words=(), aux=(), tag="", **kw):
+    c = Case(list(slots) + (raw_words(list(words)) if words else []), aux=aux, tag=tag)
+    c.__dict__.update(kw)
+    return c
+
+
+def check_result(fld, case, out, flags, want, what):
+    """The Jacobian result (slot 0 on) is `want` as residues -- Z = 0 exactly when want is infinity --, and jac_to_affine of it
+    (slot 3w on) is want's coordinates inside the normalised-coordinate contract, with the infinity bit in flag 0."""
+    w = fld.w
+    flags_agree(case, flags, 1)
+    expect(fld.jac_to_aff(case, out, 0) == want, case, "%s: wrong point" % what)
+    check_bounded(case, out, 0, 3 * w, what + " (Jacobian)")
+    expect(flags[0] == int(want is None), case, "%s: infinity flag %d" % (what, flags[0]))
+    if want is not None:
+        expect((fld.res(out, 3 * w), fld.res(out, 4 * w)) == want, case, "%s: wrong affine point" % what)
+        check_bounded(case, out, 3 * w, 2 * w, what + " (affine)", val_bound=1.25)
+
+
+# ---- the path models: a ladder's columns walked on the oracle's group law -------------------------------------------------
+def _walk_add(E, acc, e):
+    """acc (Jacobian, the oracle's) + e (affine or None): the sum, and whether the branch-free generic addition cannot do
+    it (an operand at infinity, or equal x: P = +-Q) -- the condition the device's `exc` must catch."""
+    F = E.F
+    if e is None:
+        return acc, True
+    if F.is_zero(acc[2]):
+        return (e[0], e[1], F.one), True
+    return E._jadd_affine(acc, e), F.mul(e[0], F.sqr(acc[2])) == acc[0]
+
+
+def _jac_of(E, p):
+    return (E.F.one, E.F.one, E.F.zero) if p is None else (p[0], p[1], E.F.one)
+
+
+def ladder_uniform_model(E, p, k, top):
+    """jac_ladder_uniform: [k] p for the leading one at bit `top`; (result, a special case occurred)."""
+    acc, special = _jac_of(E, p), p is None
+    for bit in range(top - 1, -1, -1):
+        acc = E._jdbl(acc)
+        if (k >> bit) & 1:
+            acc, s = _walk_add(E, acc, p)
+            special |= s
+    return E._to_affine(acc), special
+
+
+def sac_model(d):
+    """sac_recode4 (the SAC_RECODE4 op pins the device's): signs s_i, bits u_j[i] (i < 64), the top bits and fix."""
+    d0 = d[0] | 1
+    s = [1 if (d0 >> (i + 1)) & 1 else -1 for i in range(64)]
+    u, top = [], []
+    for j in (1, 2, 3):
+        k, uj = d[j], []
+        for i in range(64):
+            uj.append(k & 1)
+            k = (k - s[i] * (k & 1)) >> 1
+        u.append(uj)
+        top.append(k)
+    return s, u, top, d[0] % 2 == 0
+
+
+def subset_table(E, pts, with_first):
+    """with_first: entry m = B0 + sum_j bit_j(m) B_{j+1} (g2_sac_table); else entry m = sum_k bit_k(m) P_k (Straus)."""
+    rest = pts[1:] if with_first else pts
+    tbl = []
+    for m in range(1 << len(rest)):
+        e = pts[0] if with_first else None
+        for j, b in enumerate(rest):
+            if (m >> j) & 1:
+                e = E.add(e, b)
+        tbl.append(e)
+    return tbl
+
+
+def joint_mul4_model(bases, d):
+    """g2_joint_mul4: (sum d_i B_i, special, fix)."""
+    E = o.E2
+    s, u, top, fix = sac_model(d)
+    tbl = subset_table(E, bases, True)
+    e = tbl[top[0] | top[1] << 1 | top[2] << 2]
+    acc, special = _jac_of(E, e), e is None
+    for i in range(63, -1, -1):
+        acc = E._jdbl(acc)
+        e = tbl[u[0][i] | u[1][i] << 1 | u[2][i] << 2]
+        acc, sp = _walk_add(E, acc, e if s[i] > 0 else E.neg(e))
+        special |= sp
+    r = E._to_affine(acc)
+    if fix:
+        r = E.add(r, E.neg(bases[0]))
+    return r, special, fix
+
+
+def gls_digits(k):
+    return [k // X ** j % X for j in range(3)] + [k // X ** 3]
+
+
+def gls_bases(p):
+    p1 = psi(p)
+    p2 = psi(p1)
+    return [p, o.E2.neg(p1), p2, o.E2.neg(psi(p2))]
+
+
+def mul_gls_model(p, k):
+    """g2_mul_gls: ([k] p, special).  An even k runs as r - k and the result is negated."""
+    flip = k % 2 == 0
+    r, special, fix = joint_mul4_model(gls_bases(p), gls_digits(R - k if flip else k))
+    assert not fix
+    return (o.E2.neg(r) if flip else r), special
+
+
+def straus_model(E, pts, cs, nbits):
+    """straus_chunk / straus_small: the joint ladder over the subset sums from the identity with a `started` flag."""
+    tbl = subset_table(E, pts, False)
+    acc, started, special = _jac_of(E, None), False, False
+    for bit in range(nbits - 1, -1, -1):
+        acc = E._jdbl(acc)
+        m = sum(((c >> bit) & 1) << k for k, c in enumerate(cs))
+        if m:
+            if started:
+                acc, sp = _walk_add(E, acc, tbl[m])
+                special |= sp
+            else:
+                acc, started = _jac_of(E, tbl[m]), True
+                special |= tbl[m] is None
+    return E._to_affine(acc), special
+
+
+def clear_cofactor_model(p, fix):
+    """g2_clear_cofactor: its two (fix: three) uniform ladders; (result, special in any of them)."""
+    E = o.E2
+    xp, s1 = ladder_uniform_model(E, p, X, 63)
+    t1 = E.neg(xp)
+    t2 = psi(p)
+    t3 = E.add(psi(psi(E.dbl(p))), E.neg(t2))
+    xt, s2 = ladder_uniform_model(E, E.add(t1, t2), X, 63)
+    t3 = E.add(E.add(E.add(t3, E.neg(xt)), E.neg(t1)), E.neg(p))
+    if not fix:
+        return t3, s1 or s2
+    s = E.neg(psi(psi(psi(psi(E.add(t3, psi(t3)))))))
+    r, s3 = ladder_uniform_model(E, s, COFACTOR_FIX_SHORT, 62)
+    return r, s1 or s2 or s3
+
+
+def combine_class(d):
+    """tc_jobs.h combine_denominator_class."""
+    return "one" if d == 1 else "pow2" if d & (d - 1) == 0 and d <= 1 << 16 else "generic"
+
+
+def _path(case, fn):
+    if not hasattr(case, "path"):
+        case.path = fn(case)
+    return case.path
+
+
+def _of_path(make, path_of):
+    """path -> a maker of random cases that the model puts on that path."""
+    def of(path):
+        def maker(rnd):
+            for _ in range(200):
+                c = make(rnd, path)
+                if path_of(c) == path:
+                    return c
+            raise AssertionError("no random case of path %s" % path)
+        return maker
+    return of
+
+
+def layout(op, path_of, make, paths):
+    LAYOUTS[op] = (path_of, {p: _of_path(make, path_of)(p) for p in paths})
+
+
+def _any_path(op):
+    return lambda rnd: LAYOUTS[op][1][rnd.choice(list(LAYOUTS[op][1]))](rnd)
+
+
+MUL_SCALARS = [0, 1, 2, 3, R - 1, R - 2] + [X ** j + e for j in (1, 2, 3) for e in (0, 1, -1)]
+# the largest digits gls_decompose returns: d0 .. d2 = |x| - 1 below the largest d3, and r - 1 = (|x| - 1) (|x|^3 + |x|^2)
+GLS_SCALARS = MUL_SCALARS + [((R - 1) // X ** 3 - 1) * X ** 3 + X ** 3 - 1, X ** 3 - 2, (X - 1) * X2, (X - 2) * X + 4, X2 * X2 % R]
+
+
+# ---- jac_add_affine ---------------------------------------------------------------------------------------------------
+def _add_affine_case(fld, rnd, p, q, tag, canon=False):
+    w = fld.w
+    return mcase(aff_slots(fld, rnd, p, canon) + aff_slots(fld, rnd, q, canon), aux=[int(p is None), int(q is None)],
+                 tag=tag + (" canonical" if canon else ""), pts=(p, q))
+
+
+def _add_affine_spec(op, fld):
+    def fn(case=None, out=None, flags=None, rnd=None):
+        if rnd is not None:
+            E, cases = fld.E, []
+            for p in whole_curve_points(fld, rnd)[1:]:
+                q = _pt(fld, rnd, rnd.random() < 0.5)
+                for a, b, tag in [(None, q, "P=O"), (p, None, "Q=O"), (None, None, "P=Q=O"), (p, p, "P=Q"), (p, E.neg(p), "P=-Q"),
+                                  (p, q, "generic"), (p, E.dbl(p), "Q=2P")]:
+                    cases.append(_add_affine_case(fld, rnd, a, b, tag, canon=len(cases) % 2 == 0))
+            return cases
+        check_result(fld, case, out, flags, fld.E.add(*case.pts), "jac_add_affine")
+    spec(op, lambda rnd: _add_affine_case(fld, rnd, _pt(fld, rnd, rnd.random() < 0.5), _pt(fld, rnd), "random", rnd.random() < 0.5),
+         nflags=1)(fn)
+
+
+_add_affine_spec("G1_ADD_AFFINE", G1F)
+_add_affine_spec("G2_ADD_AFFINE", G2F)
+
+
+# ---- jac_batch_to_common_z + affine_scale_z ------------------------------------------------------------------------------
+def _common_z_case(fld, rnd, pts, extra, tag):
+    w = fld.w
+    nmax = 7 if w == 1 else 6
+    slots, lams = [], []
+    for p in pts:
+        lam = fld.rand(rnd)
+        lams.append(lam)
+        slots += fld.jac(rnd, p, lam)
+    slots += [encode(0)] * (3 * w * (nmax - len(pts)))
+    slots += aff_slots(fld, rnd, extra, rnd.random() < 0.5)
+    return mcase(slots, aux=[len(pts), int(extra is None)], tag=tag, pts=pts, lams=lams, extra=extra)
+
+
+def _common_z_spec(op, fld):
+    w = fld.w
+    nmax = 7 if w == 1 else 6
+    F = fld.F
+
+    def rand_case(rnd):
+        n = rnd.randint(1, nmax)
+        return _common_z_case(fld, rnd, [_pt(fld, rnd) if rnd.random() < 0.85 else None for _ in range(n)], _pt(fld, rnd), "random n=%d" % n)
+
+    def fn(case=None, out=None, flags=None, rnd=None):
+        if rnd is not None:
+            pool = whole_curve_points(fld, rnd)
+            cases = []
+            for n in range(1, nmax + 1):
+                p = _pt(fld, rnd)
+                cases.append(_common_z_case(fld, rnd, [rnd.choice(pool[1:]) for _ in range(n)], rnd.choice(pool[1:]), "n=%d finite" % n))
+                cases.append(_common_z_case(fld, rnd, [None] * n, p, "n=%d all at infinity" % n))
+                cases.append(_common_z_case(fld, rnd, [p] * n, None, "n=%d equal points, extra at infinity" % n))
+                for hole in {0, n // 2, n - 1}:
+                    pts = [rnd.choice(pool[1:]) for _ in range(n)]
+                    pts[hole] = None
+                    cases.append(_common_z_case(fld, rnd, pts, fld.E.neg(p), "n=%d infinity at %d" % (n, hole)))
+            return cases
+        n = len(case.pts)
+        flags_agree(case, flags, 2)
+        expect(flags[0] == inf_mask(case.pts), case, "common_z: infinity flags %x" % flags[0])
+        expect(flags[1] == int(case.extra is None), case, "affine_scale_z: infinity flag")
+        zc = fld.res(out, 2 * w * nmax)
+        want_zc = F.one
+        for p, lam in zip(case.pts, case.lams):
+            if p is not None:
+                want_zc = F.mul(want_zc, lam)
+        expect(zc == want_zc, case, "common_z: zc is not the product of the finite points' Z")
+        zi = F.inv(zc)
+        zi2, zi3 = F.sqr(zi), F.mul(F.sqr(zi), zi)
+
+        def back(s):
+            return (F.mul(fld.res(out, s), zi2), F.mul(fld.res(out, s + w), zi3))
+        for i, p in enumerate(case.pts):
+            if p is not None:
+                expect(back(2 * w * i) == p, case, "common_z: (x_%d, y_%d, zc) is not input %d" % (i, i, i))
+                check_bounded(case, out, 2 * w * i, 2 * w, "common_z entry %d" % i)
+        check_bounded(case, out, 2 * w * nmax, w, "common_z zc")
+        s = 2 * w * nmax + w
+        if case.extra is not None:
+            expect(back(s) == case.extra, case, "affine_scale_z: not the same point at Z = zc")
+            check_bounded(case, out, s, 2 * w, "affine_scale_z")
+        for k, p in ((1, case.pts[n - 1]), (2, case.extra)):  # brought back to the original curve by jac_to_affine
+            if p is not None:
+                t = s + 2 * w * k
+                expect((fld.res(out, t), fld.res(out, t + w)) == p, case, "common_z: jac_to_affine of (x, y, zc) %d" % k)
+                check_bounded(case, out, t, 2 * w, "common_z to_affine", val_bound=1.25)
+    spec(op, rand_case, nflags=2)(fn)
+
+
+_common_z_spec("G1_COMMON_Z", G1F)
+_common_z_spec("G2_COMMON_Z", G2F)
+
+
+# ---- [|x|] P by jac_ladder_uniform ---------------------------------------------------------------------------------------
+def _jac_case(fld, rnd, p, tag, words=(), aux=(), **kw):
+    return mcase(fld.jac(rnd, p), words, aux, tag, p=p, **kw)
+
+
+def _x_abs_spec(op, fld):
+    def path_of(case):
+        return _path(case, lambda c: "special" if ladder_uniform_model(fld.E, c.p, X, 63)[1] else "generic")
+
+    def make(rnd, path):
+        if path == "generic":
+            return _jac_case(fld, rnd, _pt(fld, rnd, rnd.random() < 0.5), "random")
+        p = rnd.choice([None] + small_points(fld)[:3] + small_points(fld)[5:])
+        k = rnd.randrange(1, 1 << 20)
+        return _jac_case(fld, rnd, fld.E.mul(p, k), "random small order")
+
+    def fn(case=None, out=None, flags=None, rnd=None):
+        if rnd is not None:
+            return [_jac_case(fld, rnd, p, "point %d" % i) for i, p in enumerate(whole_curve_points(fld, rnd) * 2)]
+        check_result(fld, case, out, flags, fld.E.mul(case.p, X), "mul_by_x_abs")
+    layout(op, path_of, make, ("generic", "special"))
+    spec(op, _any_path(op), nflags=1)(fn)
+
+
+_x_abs_spec("G1_MUL_BY_X_ABS", G1F)
+_x_abs_spec("G2_MUL_BY_X_ABS", G2F)
+
+
+# ---- psi on Jacobian points, the GLS bases ---------------------------------------------------------------------------------
+@spec("G2_PSI_JAC", lambda rnd: _jac_case(G2F, rnd, _pt(G2F, rnd, rnd.random() < 0.5), "random"), nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return [_jac_case(G2F, rnd, p, "point %d" % i) for i, p in enumerate(whole_curve_points(G2F, rnd))]
+    check_result(G2F, case, out, flags, psi(case.p), "g2_psi(G2Jac)")
+
+
+def _bases_case(rnd, p, tag, canon=False):
+    return mcase(aff_slots(G2F, rnd, p, canon), aux=[int(p is None)], tag=tag, p=p)
+
+
+@spec("G2_GLS_BASES", lambda rnd: _bases_case(rnd, _pt(G2F, rnd), "random", rnd.random() < 0.5), nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return [_bases_case(rnd, p, "point %d" % i, i % 2 == 0) for i, p in enumerate(whole_curve_points(G2F, rnd) * 2)]
+    flags_agree(case, flags, 1)
+    expect(flags[0] == (15 if case.p is None else 0), case, "g2_gls_bases: infinity flags %x" % flags[0])
+    if case.p is not None:
+        for k, b in enumerate(gls_bases(case.p)):
+            expect((G2F.res(out, 4 * k), G2F.res(out, 4 * k + 2)) == b, case, "g2_gls_bases: base %d" % k)
+            check_bounded(case, out, 4 * k, 4, "g2_gls_bases %d" % k)
+
+
+# ---- g2_sac_table, g2_joint_mul4 -------------------------------------------------------------------------------------------
+def _base_sets(rnd):
+    """Four independent bases, and the sets whose subset sums meet the special cases of the table builder."""
+    E = o.E2
+    b = [_pt(G2F, rnd) for _ in range(4)]
+    c = curve_point(G2F, rnd)
+    sets = [("independent", b), ("outside the subgroup", [c, b[1], curve_point(G2F, rnd), b[3]]),
+            ("B1 = B0", [b[0], b[0], b[2], b[3]]), ("B1 = -B0", [b[0], E.neg(b[0]), b[2], b[3]]),
+            ("B2 = -B1", [b[0], b[1], E.neg(b[1]), b[3]]), ("B3 = B2 = B1 = B0", [b[0]] * 4),
+            ("B0 + B1 + B2 + B3 = O", [E.neg(E.add(E.add(b[1], b[2]), b[3])), b[1], b[2], b[3]]),
+            ("B3 = -(B0 + B1)", [b[0], b[1], b[2], E.neg(E.add(b[0], b[1]))]), ("all at infinity", [None] * 4)]
+    for j in range(4):
+        sets.append(("B%d at infinity" % j, [None if i == j else b[i] for i in range(4)]))
+    return sets
+
+
+def _bases_slots(rnd, bases, canon):
+    return sum((aff_slots(G2F, rnd, p, canon) for p in bases), [])
+
+
+def _sac_table_case(rnd, bases, tag, canon=False):
+    return mcase(_bases_slots(rnd, bases, canon), aux=[inf_mask(bases)], tag=tag, bases=bases)
+
+
+@spec("G2_SAC_TABLE", lambda rnd: _sac_table_case(rnd, [_pt(G2F, rnd) for _ in range(4)], "random", rnd.random() < 0.5), nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return [_sac_table_case(rnd, bs, tag, c) for tag, bs in _base_sets(rnd) for c in (False, True)]
+    F = G2F.F
+    want = subset_table(o.E2, case.bases, True)
+    flags_agree(case, flags, 1)
+    expect(flags[0] == inf_mask(want), case, "g2_sac_table: infinity flags %x, want %x" % (flags[0], inf_mask(want)))
+    zi = F.inv(G2F.res(out, 32))
+    zi2, zi3 = F.sqr(zi), F.mul(F.sqr(zi), zi)
+    for m, e in enumerate(want):
+        if e is not None:
+            got = (F.mul(G2F.res(out, 4 * m), zi2), F.mul(G2F.res(out, 4 * m + 2), zi3))
+            expect(got == e, case, "g2_sac_table: entry %d is not B0 + sum u_j B_j at Z = zc" % m)
+            check_bounded(case, out, 4 * m, 4, "g2_sac_table entry %d" % m, val_bound=2.1)
+    if want[7] is not None:
+        expect((G2F.res(out, 34), G2F.res(out, 36)) == want[7], case, "g2_sac_table: jac_to_affine of entry 7")
+        check_bounded(case, out, 34, 4, "g2_sac_table to_affine", val_bound=1.25)
+
+
+def _joint_case(rnd, bases, d, tag, canon=False):
+    return mcase(_bases_slots(rnd, bases, canon), u64_words(d), [inf_mask(bases)], "%s d=%s" % (tag, [hex(x) for x in d]), bases=bases, d=d)
+
+
+def _joint_path(case):
+    def model(c):
+        _, special, fix = joint_mul4_model(c.bases, c.d)
+        return "special" if special else "fix" if fix else "generic"
+    return _path(case, model)
+
+
+def _joint_make(rnd, path):
+    b = [_pt(G2F, rnd) for _ in range(4)]
+    d = [rnd.getrandbits(64) for _ in range(4)]
+    if path == "generic":
+        d[0] |= 1
+    elif path == "fix":
+        d[0] &= ~1
+    else:
+        kind = rnd.randrange(3)
+        if kind == 0:
+            b[1] = o.E2.neg(b[0]) if rnd.random() < 0.5 else b[0]
+        elif kind == 1:
+            b[rnd.randrange(4)] = None
+        else:
+            d = [rnd.randrange(4), 0, 0, 0]
+    return _joint_case(rnd, b, d, "random")
+
+
+JOINT_DIGITS = [[1, 0, 0, 0], [0, 0, 0, 0], [2, 0, 0, 0], [1, 1, 1, 1], [3, 0, 5, 0], [M64, M64, M64, M64], [M64 - 1, M64, 0, M64],
+                [X - 1, X - 1, X - 1, X - 1], [X - 2, 0, X - 1, 1], [1 << 63, 1 << 63, 1, 0], [0, X - 1, 0, 0], [0, 0, 0, 1], [5, 0, 0, M64]]
+
+
+@spec("G2_JOINT_MUL4", lambda rnd: _any_path("G2_JOINT_MUL4")(rnd), nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        sets = _base_sets(rnd)
+        cases = [_joint_case(rnd, sets[i % 2][1], d, sets[i % 2][0], i % 3 == 0) for i, d in enumerate(JOINT_DIGITS)]
+        for i, (tag, bs) in enumerate(sets[2:]):
+            d = [rnd.getrandbits(64) | 1 for _ in range(4)]
+            cases.append(_joint_case(rnd, bs, d, tag, i % 2 == 0))
+            cases.append(_joint_case(rnd, bs, [d[0] - 1, d[1], 0, d[3]], tag))
+        return cases
+    E = o.E2
+    want = None
+    for b, d in zip(case.bases, case.d):
+        want = E.add(want, E.mul(b, d))
+    check_result(G2F, case, out, flags, want, "g2_joint_mul4")
+
+
+layout("G2_JOINT_MUL4", _joint_path, _joint_make, ("generic", "fix", "special"))
+
+
+# ---- g2_mul_gls (affine and Jacobian; the second covers g2_gls_digits_mul) ---------------------------------------------------
+def _scalar_point_case(fld, rnd, p, k, jac, tag, canon=False):
+    slots = fld.jac(rnd, p) if jac else aff_slots(fld, rnd, p, canon)
+    return mcase(slots, u32s(k), [int(p is None)], "%s k=%x" % (tag, k), p=p, k=k)
+
+
+def _gls_path(case):
+    return _path(case, lambda c: "special" if mul_gls_model(c.p, c.k)[1] else "generic")
+
+
+def _mul_gls_spec(op, jac):
+    def make(rnd, path):
+        p, k = _pt(G2F, rnd), rnd.randrange(R)
+        if path == "special":
+            if rnd.random() < 0.6:
+                p = None
+            else:
+                k = 0
+        return _scalar_point_case(G2F, rnd, p, k, jac, "random", rnd.random() < 0.5)
+
+    def fn(case=None, out=None, flags=None, rnd=None):
+        if rnd is not None:
+            p = _pt(G2F, rnd)
+            cases = [_scalar_point_case(G2F, rnd, p if i % 3 else _pt(G2F, rnd), k, jac, "edge", i % 2 == 0) for i, k in enumerate(GLS_SCALARS)]
+            cases += [_scalar_point_case(G2F, rnd, None, k, jac, "P = O") for k in (0, 1, 2, R - 1, rnd.randrange(R))]
+            return cases
+        check_result(G2F, case, out, flags, o.E2.mul(case.p, case.k), "g2_mul_gls")
+    layout(op, _gls_path, make, ("generic", "special"))
+    spec(op, lambda rnd: _any_path(op)(rnd), nflags=1)(fn)
+
+
+_mul_gls_spec("G2_MUL_GLS", False)
+_mul_gls_spec("G2_MUL_GLS_JAC", True)
+
+
+# ---- g2_clear_cofactor -------------------------------------------------------------------------------------------------------
+def _clear_case(rnd, p, fix, tag, canon=False):
+    return mcase(aff_slots(G2F, rnd, p, canon), aux=[int(p is None), int(fix)], tag="%s fix=%d" % (tag, fix), p=p, fix=fix)
+
+
+def _clear_path(case):
+    return _path(case, lambda c: "special" if clear_cofactor_model(c.p, c.fix)[1] else "generic")
+
+
+def _clear_make(rnd, path):
+    if path == "generic":
+        p = _pt(G2F, rnd, rnd.random() < 0.2)
+    else:
+        p = o.E2.mul(rnd.choice([None] + small_points(G2F)), rnd.randrange(1, 1 << 20))
+    return _clear_case(rnd, p, rnd.random() < 0.5, "random", rnd.random() < 0.5)
+
+
+@spec("G2_CLEAR_COFACTOR", lambda rnd: _any_path("G2_CLEAR_COFACTOR")(rnd), nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return [_clear_case(rnd, p, fix, "point %d" % i, i % 2 == 0) for i, p in enumerate(whole_curve_points(G2F, rnd)) for fix in (1, 0)]
+    want = cached("clear", (case.p, case.fix), lambda: o.E2.mul(case.p, H2 if case.fix else CLEAR_NOFIX))
+    check_result(G2F, case, out, flags, want, "g2_clear_cofactor")
+
+
+layout("G2_CLEAR_COFACTOR", _clear_path, _clear_make, ("generic", "special"))
+
+
+# ---- g1_mul_glv: affine, Jacobian, arena (no per-wave decision: every addition of the ladder is the safe one) --------------------
+def _mul_glv_spec(op, jac):
+    def fn(case=None, out=None, flags=None, rnd=None):
+        if rnd is not None:
+            p = _pt(G1F, rnd)
+            ks = _g1_edges(rnd) + MUL_SCALARS
+            cases = [_scalar_point_case(G1F, rnd, p if i % 3 else _pt(G1F, rnd), k, jac, "edge", i % 2 == 0) for i, k in enumerate(ks)]
+            cases += [_scalar_point_case(G1F, rnd, None, k, jac, "P = O") for k in (0, 1, 2, R - 1, rnd.randrange(R))]
+            return cases
+        check_result(G1F, case, out, flags, o.E1.mul(case.p, case.k), "g1_mul_glv")
+    spec(op, lambda rnd: _scalar_point_case(G1F, rnd, _pt(G1F, rnd), rnd.randrange(R), jac, "random", rnd.random() < 0.5), nflags=1)(fn)
+
+
+_mul_glv_spec("G1_MUL_GLV", False)
+_mul_glv_spec("G1_MUL_GLV_JAC", True)
+_mul_glv_spec("G1_MUL_GLV_ARENA", False)
+
+
+# ---- lincomb_chunk4 = straus_chunk<Fq, 4> ------------------------------------------------------------------------------------
+def _point_sets(fld, rnd, n):
+    """n points: independent, and the sets whose subset sums meet infinity or a doubling."""
+    E = fld.E
+    b = [_pt(fld, rnd) for _ in range(n)]
+    sets = [("independent", b), ("P1 = P0", [b[0], b[0]] + b[2:]), ("P1 = -P0", [b[0], E.neg(b[0])] + b[2:]), ("all equal", [b[0]] * n),
+            ("P0 at infinity", [None] + b[1:]), ("last at infinity", b[:-1] + [None]), ("all at infinity", [None] * n)]
+    if n >= 3:
+        sets.append(("P2 = -(P0 + P1)", b[:2] + [E.neg(E.add(b[0], b[1]))] + b[3:]))
+    return sets
+
+
+def _lincomb_case(rnd, pts, sc, tag, canon=False):
+    ws = sum((u32s(s, NL) for s in sc), [])
+    return mcase(sum((aff_slots(G1F, rnd, p, canon) for p in pts), []), ws, [inf_mask(pts)], tag, pts=pts, cs=sc)
+
+
+def _lincomb_path(case):
+    return _path(case, lambda c: "special" if straus_model(o.E1, c.pts, c.cs, 255)[1] else "generic")
+
+
+def _lincomb_make(rnd, path):
+    pts = [_pt(G1F, rnd) for _ in range(4)]
+    sc = [rnd.randrange(R) for _ in range(4)]
+    if path == "special":
+        kind = rnd.randrange(3)
+        if kind == 0:
+            pts[1] = o.E1.neg(pts[0]) if rnd.random() < 0.5 else pts[0]
+        elif kind == 1:
+            pts[rnd.randrange(4)] = None
+        else:
+            sc[1] = sc[0]
+            pts[1] = o.E1.neg(pts[0])
+            sc[2] = sc[3] = 0
+    return _lincomb_case(rnd, pts, sc, "random", rnd.random() < 0.5)
+
+
+@spec("G1_LINCOMB_CHUNK4", lambda rnd: _any_path("G1_LINCOMB_CHUNK4")(rnd), nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        sets = _point_sets(G1F, rnd, 4)
+        scs = [[0, 0, 0, 0], [1, 0, 0, 0], [0, 0, 0, 1], [1, 1, 1, 1], [R - 1, R - 1, R - 1, R - 1], [R - 1, 1, R - 2, 2], [1 << 254, 0, 3, 0],
+               [X2, X2 + 1, X, 1 << 128]]
+        cases = [_lincomb_case(rnd, sets[0][1], sc, "scalars %d" % i, i % 2 == 0) for i, sc in enumerate(scs)]
+        for i, (tag, pts) in enumerate(sets[1:]):
+            sc = [rnd.randrange(R) for _ in range(4)]
+            cases.append(_lincomb_case(rnd, pts, sc, tag, i % 2 == 0))
+            cases.append(_lincomb_case(rnd, pts, [sc[0], sc[0], 0, 5], tag + ", equal scalars"))
+        return cases
+    want = None
+    for p, s in zip(case.pts, case.cs):
+        want = o.E1.add(want, o.E1.mul(p, s))
+    check_result(G1F, case, out, flags, want, "lincomb_chunk4")
+
+
+layout("G1_LINCOMB_CHUNK4", _lincomb_path, _lincomb_make, ("generic", "special"))
+
+
+# ---- straus_small -----------------------------------------------------------------------------------------------------------
+def _small_mul_case(fld, rnd, pts, cs, tag, canon=False):
+    K = len(pts)
+    w = fld.w
+    slots = sum((aff_slots(fld, rnd, p, canon) for p in pts), []) + [encode(0)] * (2 * w * (4 - K))
+    return mcase(slots, u64_words(cs), [K, inf_mask(pts)], "K=%d %s c=%s" % (K, tag, [hex(c) for c in cs]), pts=pts, cs=cs)
+
+
+def _straus_small_spec(op, fld):
+    E = fld.E
+
+    def path_of(case):
+        return _path(case, lambda c: "special" if straus_model(E, c.pts, c.cs, 64)[1] else "generic")
+
+    def coeffs(rnd, K):
+        # the shapes lagrange_small_coeffs hands on: a few bits to a few tens of bits, now and then one of 63 bits beside tiny ones
+        kind = rnd.randrange(4)
+        if kind == 0:
+            return [rnd.getrandbits(rnd.choice([3, 9, 14])) for _ in range(K)]
+        if kind == 1:
+            return [rnd.getrandbits(63) | 1 << 62] + [rnd.getrandbits(4) for _ in range(K - 1)]
+        if kind == 2:
+            return [rnd.getrandbits(rnd.randint(1, 63)) for _ in range(K)]
+        return [1 << rnd.randrange(20) for _ in range(K)]
+
+    def make(rnd, path):
+        K = rnd.choice([2, 3, 4])
+        pts = [_pt(fld, rnd) for _ in range(K)]
+        cs = coeffs(rnd, K)
+        if path == "special":
+            kind = rnd.randrange(3)
+            if kind == 0:
+                pts[1] = E.neg(pts[0]) if rnd.random() < 0.5 else pts[0]
+                cs[0] |= 1
+                cs[1] |= 3
+            elif kind == 1:
+                j = rnd.randrange(K)
+                pts[j] = None
+                cs[j] |= 1
+            else:
+                pts[1] = E.neg(pts[0])
+                cs = [cs[0] | 1, cs[0] | 1] + [0] * (K - 2)
+        return _small_mul_case(fld, rnd, pts, cs, "random", rnd.random() < 0.5)
+
+    def fn(case=None, out=None, flags=None, rnd=None):
+        if rnd is not None:
+            cases = []
+            for K in (2, 3, 4):
+                sets = _point_sets(fld, rnd, K)
+                big = (1 << 63) - 1
+                css = [[0] * K, [1] + [0] * (K - 1), [0] * (K - 1) + [1], [1] * K, [big] * K, [big - 1] + [1] * (K - 1), [1 << 62] + [2] * (K - 1),
+                       [3] * (K - 1) + [(1 << 62) + 1], [2, 1] + [0] * (K - 2)]
+                cases += [_small_mul_case(fld, rnd, sets[0][1], cs, "coefficients %d" % i, i % 2 == 0) for i, cs in enumerate(css)]
+                for i, (tag, pts) in enumerate(sets[1:]):
+                    cases.append(_small_mul_case(fld, rnd, pts, coeffs(rnd, K), tag, i % 2 == 0))
+                    cases.append(_small_mul_case(fld, rnd, pts, [7] * K, tag + ", equal coefficients"))
+            return cases
+        want = None
+        for p, c in zip(case.pts, case.cs):
+            want = E.add(want, E.mul(p, c))
+        check_result(fld, case, out, flags, want, "straus_small")
+    layout(op, path_of, make, ("generic", "special"))
+    spec(op, lambda rnd: _any_path(op)(rnd), nflags=1)(fn)
+
+
+_straus_small_spec("G1_STRAUS_SMALL", G1F)
+_straus_small_spec("G1_STRAUS_SMALL_INLINE", G1F)
+_straus_small_spec("G2_STRAUS_SMALL", G2F)
+
+
+# ---- combine_divide, combine_divide_arena: [+-1 / D] Q --------------------------------------------------------------------------
+DIVIDE_DS = [1] + [1 << a for a in range(1, 18)] + [3, 5, 6, 255, 65521, 3 << 15, (1 << 32) - 1, 1 << 32, (1 << 32) + 15, 3 ** 39,
+                                                    (1 << 61) - 1, (1 << 62) - 1, (1 << 62) - 57, 1 << 61]
+
+
+def _divide_case(fld, rnd, q, d, neg, tag=""):
+    return _jac_case(fld, rnd, q, "%s D=%s%d" % (tag, "-" if neg else "", d), u32s(d, 2), [int(neg)], d=d, neg=neg)
+
+
+def _divide_random_d(rnd, path):
+    if path == "one":
+        return 1
+    if path == "pow2":
+        return 1 << rnd.randint(1, 16)
+    if path == "word":
+        return rnd.randrange(2, 1 << 32)
+    if path == "bit":
+        return rnd.randrange(1 << 32, 1 << 62)
+    while True:
+        d = rnd.choice([rnd.randrange(2, 1 << 20), rnd.randrange(2, 1 << 62), 1 << rnd.randint(17, 61)])
+        if combine_class(d) == "generic":
+            return d
+
+
+def _divide_spec(op, fld, paths):
+    def path_of(case):
+        def model(c):
+            if fld.w == 1:  # (G1: g1_mul_glv has no branch-free pass; the per-wave decisions are D = 1 and fr_inverse_of_small's)
+                return "one" if c.d == 1 else "word" if c.d < 1 << 32 else "bit"
+            cls = combine_class(c.d)
+            if cls == "pow2" and c.p is None:
+                return "special"
+            if cls == "generic" and mul_gls_model(c.p, pow(c.d, -1, R))[1]:
+                return "special"
+            return cls
+        return _path(case, model)
+
+    def make(rnd, path):
+        if path == "special":
+            return _divide_case(fld, rnd, None, _divide_random_d(rnd, rnd.choice(["pow2", "generic"])), rnd.random() < 0.5, "random Q = O")
+        return _divide_case(fld, rnd, _pt(fld, rnd), _divide_random_d(rnd, path), rnd.random() < 0.5, "random")
+
+    def fn(case=None, out=None, flags=None, rnd=None):
+        if rnd is not None:
+            q = _pt(fld, rnd)
+            cases = [_divide_case(fld, rnd, q if i % 4 else _pt(fld, rnd), d, neg) for i, d in enumerate(DIVIDE_DS) for neg in (False, True)]
+            cases += [_divide_case(fld, rnd, None, d, neg, "Q = O") for d in (1, 2, 1 << 16, 1 << 17, 3, (1 << 62) - 1) for neg in (False, True)]
+            return cases
+        k = pow(-case.d if case.neg else case.d, -1, R)
+        check_result(fld, case, out, flags, fld.E.mul(case.p, k), "combine_divide")
+    layout(op, path_of, make, paths)
+    spec(op, lambda rnd: _any_path(op)(rnd), nflags=1)(fn)
+
+
+_divide_spec("G1_COMBINE_DIVIDE", G1F, ("one", "word", "bit"))
+_divide_spec("G1_COMBINE_DIVIDE_ARENA", G1F, ("one", "word", "bit"))
+_divide_spec("G2_COMBINE_DIVIDE", G2F, ("one", "pow2", "generic", "special"))
+
+
+# ---- g1_mul_u64 ---------------------------------------------------------------------------------------------------------------
+@spec("G1_MUL_U64", lambda rnd: _jac_case(G1F, rnd, _pt(G1F, rnd), "random", u32s(rnd.getrandbits(rnd.choice([8, 33, 64])), 2)), nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        xs = [0, 1, 2, 3, 1 << 63, M64, 1 << 32, (1 << 32) - 1, M64 - 1, (1 << 63) + 1]
+        pts = whole_curve_points(G1F, rnd)
+        cases = [_jac_case(G1F, rnd, pts[1 + i % 3], "edge x=%x" % x, u32s(x, 2)) for i, x in enumerate(xs)]
+        cases += [_jac_case(G1F, rnd, p, "point %d x=%x" % (i, x), u32s(x, 2)) for i, p in enumerate(pts) for x in (3, M64, rnd.getrandbits(64))]
+        return cases
+    x = words_value(case.slots[3]) & M64
+    check_result(G1F, case, out, flags, o.E1.mul(case.p, x), "g1_mul_u64")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # tables and sizes
 # ---------------------------------------------------------------------------------------------------------------------
 def table(op, seed=1):
@@ -2743,19 +3538,20 @@ def table(op, seed=1):
 
 
 def _wave_layout(op, edges, rnd):
-    """The table of an op that decides once per wave (LAYOUTS): first, for every path, one full wave of 64 jobs that all
-    take it (its directed cases, then random ones of that path); then the other directed cases interleaved with random
+    """The table of an op that decides once per wave (LAYOUTS): first, for every path, one full wave (64 // lanes(op)
+    jobs) that all take it (its directed cases, then random ones of that path); then the other directed cases interleaved with random
     cases of every path in turn, so that the later waves mix the paths (lanes that return early next to lanes that
     finish), up to a ragged tail."""
     path_of, makers = LAYOUTS[op]
+    wave = 64 // lanes(op)
     pool, cases = list(edges), []
     for p, make in makers.items():
-        mine = [c for c in pool if path_of(c) == p][:64]
+        mine = [c for c in pool if path_of(c) == p][:wave]
         pool = [c for c in pool if not any(c is m for m in mine)]
-        cases += mine + [make(rnd) for _ in range(64 - len(mine))]
+        cases += mine + [make(rnd) for _ in range(wave - len(mine))]
     paths = list(makers)
-    n = len(cases) + max(2 * len(pool), 2 * 64 + 5)
-    if n % 64 == 0:
+    n = len(cases) + max(2 * len(pool), 2 * wave + 5)
+    if n % wave == 0:
         n += 1
     k = 0
     while len(cases) < n:

@@ -91,16 +91,90 @@ def test_div_by_x_abs_table_takes_both_outcomes():
 @pytest.mark.parametrize("op", sorted(dc.LAYOUTS, key=lambda k: dc.OPS[k]))
 def test_wave_layout_of_per_wave_decisions(op):
     """Ops whose device form decides once per wave: the table opens with one full wave per path (every lane takes it),
-    and later waves mix the paths.  n = 1, a partial wave and one wave still run (sizes)."""
+    and later waves mix the paths.  n = 1, a partial wave and one wave still run (sizes).  A wave holds 64 jobs of a
+    one-lane op and 32 of a lane-pair op."""
     path_of, makers = dc.LAYOUTS[op]
     cases = dc.table(op)
-    waves = [cases[k:k + 64] for k in range(0, len(cases), 64)]
+    wave = 64 // dc.lanes(op)
+    waves = [cases[k:k + wave] for k in range(0, len(cases), wave)]
     for w, p in zip(waves, makers):
-        assert len(w) == 64 and all(path_of(c) == p for c in w), (op, p)
+        assert len(w) == wave and all(path_of(c) == p for c in w), (op, p)
     mixed = [w for w in waves[len(makers):] if len({path_of(c) for c in w}) > 1]
     assert len(mixed) >= 2, op
     assert {path_of(c) for w in mixed for c in w} >= set(makers)
-    assert len(cases) % 64 and dc.sizes(op, len(cases))[:3] == [1, 35, 64]
+    assert len(cases) % wave and dc.sizes(op, len(cases))[:3] == [1, wave // 2 + 3, wave]
+    assert [1, wave // 2 + 3, wave] == ([1, 35, 64] if dc.lanes(op) == 1 else [1, 19, 32])
+
+
+def test_point_multiplication_models_agree_with_the_oracle():
+    """The path models of the point-multiplication block walk the ladders on the oracle's group law.  Their results equal
+    E.mul / E.add (so the walk is the ladder the routine runs), psi on the whole curve is [x] on G2, and the models see
+    the special cases they are there to see: a generic case is not special, a case built on an exception is."""
+    import random
+    o = dc.o
+    rnd = random.Random(11)
+    p, q = dc.g2_point(rnd), dc.curve_point(dc.G2F, rnd)
+    assert dc.psi(p) == dc._psi_ref(p) and dc.psi(q) != dc._psi_ref(q) and o.E2.on_curve(dc.psi(q))
+    for E, fld in ((o.E1, dc.G1F), (o.E2, dc.G2F)):
+        a = dc._pt(fld, rnd)
+        assert dc.ladder_uniform_model(E, a, dc.X, 63) == (E.mul(a, dc.X), False)
+        for s in dc.small_points(fld):
+            assert dc.ladder_uniform_model(E, s, dc.X, 63)[0] == E.mul(s, dc.X)
+        assert dc.ladder_uniform_model(E, None, dc.X, 63) == (None, True)
+    assert dc.ladder_uniform_model(o.E1, (0, 2), dc.X, 63)[1]  # order 3: 2 P = -P, the first addition is P = -Q
+    for k in (0, 1, 2, dc.R - 1, rnd.randrange(dc.R), 2 * rnd.randrange(dc.R // 2)):
+        r, special = dc.mul_gls_model(p, k)
+        assert r == o.E2.mul(p, k) and special == (k == 0), hex(k)  # (k = 0 runs as r: the last addition is P = -Q)
+    bases = [dc.g2_point(rnd) for _ in range(4)]
+    for d in ([5, 7, 9, 11], [4, 7, 0, 11], [rnd.getrandbits(64) for _ in range(4)]):
+        want = None
+        for b, x in zip(bases, d):
+            want = o.E2.add(want, o.E2.mul(b, x))
+        assert dc.joint_mul4_model(bases, d)[0] == want and dc.joint_mul4_model(bases, d)[2] == (d[0] % 2 == 0)
+    assert dc.joint_mul4_model([bases[0], o.E2.neg(bases[0])] + bases[2:], [3, 1, 0, 0])[1]
+    for fix in (True, False):
+        assert dc.clear_cofactor_model(q, fix) == (o.E2.mul(q, dc.H2 if fix else dc.CLEAR_NOFIX), False)
+        assert dc.clear_cofactor_model(dc.small_points(dc.G2F)[0], fix) == (None, True)
+    pts = [dc.g1_point(rnd) for _ in range(3)]
+    cs = [rnd.getrandbits(40), 3, 1 << 62]
+    want = None
+    for b, x in zip(pts, cs):
+        want = o.E1.add(want, o.E1.mul(b, x))
+    assert dc.straus_model(o.E1, pts, cs, 64) == (want, False)
+    assert dc.straus_model(o.E1, [pts[0], o.E1.neg(pts[0])], [3, 3], 64) == (None, True)
+    assert dc.straus_model(o.E1, pts, [0, 0, 0], 64) == (None, False)
+
+
+def test_point_multiplication_tables_hold_every_path():
+    """Every op of the point-multiplication block with a per-wave decision: the Python model finds cases of every path it
+    knows among the DIRECTED cases or the table, and the block's tables hold the edges the routines turn on."""
+    new = [op for op in dc.LAYOUTS if dc.OPS[op] >= dc.OPS["G1_ADD_AFFINE"]]
+    assert len(new) == 13
+    for op in new:
+        path_of, makers = dc.LAYOUTS[op]
+        cases = dc.table(op)
+        seen = {}
+        for c in cases:
+            seen[path_of(c)] = seen.get(path_of(c), 0) + 1
+        assert set(seen) == set(makers) and min(seen.values()) >= 64 // dc.lanes(op), (op, seen)
+    assert set(dc.NEEDS_TABLE) <= set(dc.OPS) and all(dc.lanes(op) == (1 if op.startswith("G1") else 2) for op in dc.OPS if dc.OPS[op] >= 140)
+    # combine_divide: D = 1, every 2^a (a = 1 .. 16), 2^17, odd, >= 2^32, near 2^62, each with both signs, and Q = O
+    for op in ("G1_COMBINE_DIVIDE", "G1_COMBINE_DIVIDE_ARENA", "G2_COMBINE_DIVIDE"):
+        ds = {(c.d, c.neg) for c in dc.table(op)}
+        for d in [1, 3, 1 << 17, (1 << 32) + 15, (1 << 62) - 1] + [1 << a for a in range(1, 17)]:
+            assert (d, False) in ds and (d, True) in ds, (op, d)
+        assert any(c.p is None for c in dc.table(op))
+    # g2_joint_mul4 / g2_mul_gls: even and odd d0 / k, zero digits, the largest digits
+    ds = [c.d for c in dc.table("G2_JOINT_MUL4")]
+    assert any(d[0] % 2 for d in ds) and any(d[0] % 2 == 0 for d in ds) and any(d[1:] == [0, 0, 0] for d in ds)
+    ks = {c.k for c in dc.table("G2_MUL_GLS")}
+    assert ks >= set(dc.MUL_SCALARS) and any(max(dc.gls_digits(k)[:3]) == dc.X - 1 for k in ks)
+    # straus_small: all zero, a single one, a 63-bit coefficient beside tiny ones, for K = 2, 3, 4
+    for K in (2, 3, 4):
+        cs = [c.cs for c in dc.table("G2_STRAUS_SMALL") if len(c.cs) == K]
+        assert [0] * K in cs and [1] + [0] * (K - 1) in cs and any(max(c) >> 62 and min(c) < 16 for c in cs)
+    xs = {dc.words_value(c.slots[3]) & dc.M64 for c in dc.table("G1_MUL_U64")}
+    assert xs >= {0, 1, 1 << 63, dc.M64}
 
 
 def test_miller_reference_model_agrees_with_the_oracle():
