@@ -204,6 +204,11 @@ int tc_xor_with_hash_batch(tc_ctx* ctx, const uint8_t* g1, const uint8_t* data, 
 int tc_pairing_check_batch(tc_ctx* ctx, const uint8_t* a_g1, size_t a_stride, const uint8_t* b_g2, size_t b_stride,
                            const uint8_t* c_g1, size_t c_stride, const uint8_t* d_g2, size_t d_stride, size_t B,
                            uint8_t* ok);
+/* ok[j] = ( prod_{k<n} e(a[j*n+k], b[j*n+k]) == 1 ): the product of n >= 1 pairings per job with ONE final exponentiation --
+ * the multi-pairing that PEngine::pairing(..) == PEngine::pairing(..) of src/lib.rs:109, :185, :511 is the n = 2 case of (with
+ * one G1 operand negated).  a_g1: B x n x 96 B, b_g2: B x n x 192 B, packed.  A pair with an identity operand contributes the
+ * factor 1; an undecodable operand gives ok[j] = 0, and so does, in checked-input mode, an operand outside G1 / G2. */
+int tc_pairing_product_check_batch(tc_ctx* ctx, const uint8_t* a_g1, const uint8_t* b_g2, size_t n, size_t B, uint8_t* ok);
 /* ok[j] = pk.verify_g2(sig[j], hash[j]) = e(pk, hash[j]) == e(g1, sig[j])     src/lib.rs:108-110,170-172 */
 int tc_verify_g2_batch(tc_ctx* ctx, const uint8_t* pk_g1, size_t pk_stride, const uint8_t* sig_g2,
                        const uint8_t* hash_g2, size_t B, uint8_t* ok);
@@ -245,6 +250,18 @@ int tc_verify_decryption_shares_rlc_batch(tc_ctx* ctx, const uint8_t* pk_shares,
 /* ok[j] = Ciphertext(u[j], v[j], w[j]).verify() = e(g1, w) == e(u, hash_g1_g2(u, v))   src/lib.rs:508-512 */
 int tc_ciphertext_verify_batch(tc_ctx* ctx, const uint8_t* u_g1, const uint8_t* v, const uint64_t* off,
                                const uint8_t* w_g2, size_t B, uint8_t* ok);
+/* Ciphertext::verify (src/lib.rs:508-512) for a batch by random linear combination (opt-in).  The batch is cut into groups of
+ * `group` ciphertexts (0 = the default, 64; at most 1024; the last group may be short); a group passes with ONE check
+ *     e(g1, sum_j r_j w_j) == prod_j e(r_j u_j, hash_g1_g2(u_j, v_j))
+ * -- `group` pairings sharing their Miller-loop squarings two by two and ONE final exponentiation -- instead of `group` checks
+ * of two pairings each.  r_j = 2^63 secret values from ChaCha20(seed32, j), pairwise distinct mod r; groups that fail -- or
+ * hold an undecodable or, in checked-input mode, non-member operand -- are re-checked ciphertext by ciphertext, so ok[] equals
+ * tc_ciphertext_verify_batch's up to the 2^-63 of a wrongly passing group.  The bound assumes u_j in G1 and w_j in G2 (what
+ * checked-input mode tests, and what the reference's checked decode guarantees).  *n_fallback (optional, host) = ciphertexts
+ * that went through the per-ciphertext checks.  seed32: 32 secret random bytes in HOST memory in both I/O modes, drawn after
+ * the ciphertexts were received. */
+int tc_ciphertext_verify_rlc_batch(tc_ctx* ctx, const uint8_t* u_g1, const uint8_t* v, const uint64_t* off, const uint8_t* w_g2,
+                                   size_t B, size_t group, const uint8_t* seed32, uint8_t* ok, uint64_t* n_fallback);
 /* SecretKeyShare::decrypt_share src/lib.rs:452-457 for ONE key share and B ciphertexts: Ciphertext::verify, then [sk] u.
  * ok[j] = 1 and out_g1[j] = the DecryptionShare when ciphertext j is valid; ok[j] = 0 and the identity's encoding when it is
  * not (the reference returns None: an invalid ciphertext never yields a share).  sk_fr: 32 B LE, wiped from the staging

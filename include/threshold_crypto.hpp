@@ -664,6 +664,44 @@ inline std::vector<std::vector<bool>> verify_decryption_shares_rlc_batch(const s
   return out;
 }
 
+// Ciphertext::verify (src/lib.rs:508-512) for many ciphertexts through one random linear combination per group of ciphertexts
+// (tc_ciphertext_verify_rlc_batch, opt-in: one product of pairings and ONE final exponentiation per group; groups that fail
+// are re-checked one by one).  group = 0: the library's default.  seed: 32 bytes of fresh secret randomness.
+inline std::vector<bool> ciphertext_verify_rlc_batch(const std::vector<Ciphertext>& cts, const std::array<std::uint8_t, 32>& seed,
+                                                     std::size_t group = 0, std::uint64_t* n_fallback = nullptr,
+                                                     Engine& e = Engine::instance()) {
+  const std::size_t B = cts.size();
+  std::vector<std::uint8_t> u(B * 96 + 1), w(B * 192 + 1), ok(B + 1);
+  Messages v;
+  for (std::size_t j = 0; j < B; j++) {
+    std::memcpy(&u[j * 96], cts[j].u.data(), 96);
+    std::memcpy(&w[j * 192], cts[j].w.data(), 192);
+    v.push(cts[j].v.data(), cts[j].v.size());
+  }
+  std::uint64_t nfb = 0;
+  if (B) e.check(tc_ciphertext_verify_rlc_batch(e.ctx(), u.data(), v.data(), v.off.data(), w.data(), B, group, seed.data(), ok.data(), &nfb));
+  if (n_fallback) *n_fallback = nfb;
+  std::vector<bool> out(B);
+  for (std::size_t j = 0; j < B; j++) out[j] = ok[j] != 0;
+  return out;
+}
+// out[j] = ( prod_{k < n} e(a[j * n + k], b[j * n + k]) == 1 ): the multi-pairing behind the checks of src/lib.rs:109, :185, :511
+// (tc_pairing_product_check_batch), n pairs per job sharing ONE final exponentiation
+inline std::vector<bool> pairing_product_check_batch(const std::vector<G1Bytes>& a, const std::vector<G2Bytes>& b, std::size_t n,
+                                                     Engine& e = Engine::instance()) {
+  if (n == 0 || a.size() != b.size() || a.size() % n) throw std::invalid_argument("n pairs per job");
+  const std::size_t B = a.size() / n;
+  std::vector<std::uint8_t> pa(a.size() * 96 + 1), pb(b.size() * 192 + 1), ok(B + 1);
+  for (std::size_t i = 0; i < a.size(); i++) {
+    std::memcpy(&pa[i * 96], a[i].data(), 96);
+    std::memcpy(&pb[i * 192], b[i].data(), 192);
+  }
+  if (B) e.check(tc_pairing_product_check_batch(e.ctx(), pa.data(), pb.data(), n, B, ok.data()));
+  std::vector<bool> out(B);
+  for (std::size_t j = 0; j < B; j++) out[j] = ok[j] != 0;
+  return out;
+}
+
 // Poly::commitment (src/poly.rs:372-377) / BivarPoly::commitment (:625-632): coefficient * g1 for every Fr
 // coefficient, fixed-base on the device (LDS window table of the generator)
 inline std::vector<G1Bytes> commitment(const std::vector<FrBytes>& coeff, Engine& e = Engine::instance()) {

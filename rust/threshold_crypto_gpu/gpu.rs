@@ -25,7 +25,7 @@
 //!   A6/A7 PublicKeySet::combine_signatures  PublicKeySet::combine_signatures_batch
 //!   A8  PublicKeySet::decrypt           PublicKeySet::decrypt_batch
 //!   A9  PublicKey::verify / verify_g2   PublicKey::verify_batch, verify_g2_batch, verify_rlc_batch (opt-in)
-//!   A10 Ciphertext::verify              Ciphertext::verify_batch
+//!   A10 Ciphertext::verify              Ciphertext::verify_batch, verify_rlc_batch (opt-in); pairing_product_check_batch
 //!   A11 PublicKeyShare::verify_decryption_share  PublicKeyShare::verify_decryption_share_batch
 //!   A12 PublicKeySet::public_key_share  PublicKeySet::public_key_shares
 //!   A13 to_bytes / from_bytes           g1_to_bytes_batch, g2_to_bytes_batch, g1_from_bytes_batch, g2_from_bytes_batch
@@ -623,6 +623,44 @@ impl Ciphertext {
         gpu.check(unsafe { tc_ciphertext_verify_batch(gpu.0, u.as_ptr(), flat.as_ptr(), off.as_ptr(), w.as_ptr(), cts.len(), ok.as_mut_ptr()) })?;
         Ok(ok.into_iter().map(|b| b == 1).collect())
     }
+
+    /// The same through one random linear combination per group of ciphertexts (opt-in, tc_ciphertext_verify_rlc_batch): a group
+    /// passes with one product of pairings and ONE final exponentiation, groups that fail are re-checked one by one, so the
+    /// booleans are `verify_batch`'s up to 2^-63.  `group` = 0: the library's default.  `seed`: 32 fresh secret random bytes.
+    /// The C entry's count of ciphertexts that were re-checked one by one is not returned, as in the other `*_rlc_batch` mirrors
+    /// here; the C++ header and the Python engine expose it.
+    pub fn verify_rlc_batch(gpu: &Gpu, cts: &[Ciphertext], group: usize, seed: &[u8; 32]) -> GpuResult<Vec<bool>> {
+        let (mut u, mut w) = (Vec::with_capacity(cts.len() * G1_BYTES), Vec::with_capacity(cts.len() * G2_BYTES));
+        for ct in cts {
+            u.extend_from_slice(&g1_bytes(&ct.0));
+            w.extend_from_slice(&g2_bytes(&ct.2));
+        }
+        let vs: Vec<&[u8]> = cts.iter().map(|c| c.1.as_slice()).collect();
+        let (flat, off) = pack_messages(&vs);
+        let mut ok = vec![0u8; cts.len()];
+        let mut fallback = 0u64;
+        gpu.check(unsafe { tc_ciphertext_verify_rlc_batch(gpu.0, u.as_ptr(), flat.as_ptr(), off.as_ptr(), w.as_ptr(), cts.len(), group, seed.as_ptr(), ok.as_mut_ptr(), &mut fallback) })?;
+        Ok(ok.into_iter().map(|b| b == 1).collect())
+    }
+}
+
+/// `prod_k e(a[j][k], b[j][k]) == 1` for every job `j` (tc_pairing_product_check_batch): the multi-pairing behind the checks of
+/// src/lib.rs:109, :185, :511, the pairs of a job sharing ONE final exponentiation.  Every job holds the same number of pairs.
+pub fn pairing_product_check_batch(gpu: &Gpu, jobs: &[Vec<(G1, G2)>]) -> GpuResult<Vec<bool>> {
+    let n = jobs.first().map_or(0, |j| j.len());
+    if n == 0 || jobs.iter().any(|j| j.len() != n) {
+        return Err(shape_error("every job needs the same, non-zero number of pairs"));
+    }
+    let (mut a, mut b) = (Vec::with_capacity(jobs.len() * n * G1_BYTES), Vec::with_capacity(jobs.len() * n * G2_BYTES));
+    for job in jobs {
+        for (p, q) in job {
+            a.extend_from_slice(&g1_bytes(p));
+            b.extend_from_slice(&g2_bytes(q));
+        }
+    }
+    let mut ok = vec![0u8; jobs.len()];
+    gpu.check(unsafe { tc_pairing_product_check_batch(gpu.0, a.as_ptr(), b.as_ptr(), n, jobs.len(), ok.as_mut_ptr()) })?;
+    Ok(ok.into_iter().map(|b| b == 1).collect())
 }
 impl PublicKeyShare {
     /// Batch form of `verify_decryption_share` (src/lib.rs:182-186): one key share, B (share, ciphertext) pairs.

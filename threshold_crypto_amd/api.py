@@ -223,9 +223,14 @@ class Ciphertext:
         return bool(Ciphertext.verify_batch([self])[0])
 
     @staticmethod
-    def verify_batch(cts, engine=None):
+    def verify_batch(cts, engine=None, rlc=False, seed=None):
+        """Ciphertext::verify for many ciphertexts.  rlc=True: the opt-in random linear combination per group of ciphertexts
+        (tc_ciphertext_verify_rlc_batch; groups that fail are re-checked one by one, so the booleans are the per-ciphertext
+        ones up to 2^-63); `seed`: 32 secret random bytes drawn after the ciphertexts arrived."""
         e = engine or default_engine()
         v, off = pack_messages([c.v for c in cts])
+        if rlc:
+            return e.ciphertext_verify_rlc(_stack([c.u for c in cts], 96), v, off, _stack([c.w for c in cts], 192), seed=seed)[0].astype(bool)
         return e.ciphertext_verify(_stack([c.u for c in cts], 96), v, off, _stack([c.w for c in cts], 192)).astype(bool)
 
 

@@ -191,6 +191,8 @@ struct Call {
   // the Miller values between the two kernels of a pairing check (k_pairing.hip)
   // (+ the line buffer of the prepared form, one tile of checks sized to the memory this call may spend: msm_table_budget)
   tc::PairingWs pairing_ws(size_t B);
+  // the Miller values and the partial products of an n-pair product check (k_pairing.hip launch_pairing_product_check)
+  int32_t* pairing_product_ws(size_t n, size_t B, bool rhs) { return temp<int32_t>(tc::pairing_product_ws_words(n, B, rhs)); }
   // Checked-input mode (tc_ctx_set_input_checks): validate the first `take` points of `records` records of
   // n_per_job points each (stride 0 = ONE point shared by every job); job j owns record j / group.
   // always: the test runs whatever the context's switch says (entries that multiply a SECRET by the operand)
@@ -1095,6 +1097,29 @@ int tc_pairing_check_batch(tc_ctx* ctx, const uint8_t* a, size_t sa, const uint8
   return on_exception((tc_ctx*)ctx);
 }
 
+// ok[j] = ( prod_{k < n} e(a[j n + k], b[j n + k]) == 1 ): the multi-pairing behind every check of the reference
+// (src/lib.rs:109, :185, :511 are n = 2 with one G1 operand negated), n pairs sharing ONE final exponentiation.
+int tc_pairing_product_check_batch(tc_ctx* ctx, const uint8_t* a, const uint8_t* b, size_t n, size_t B, uint8_t* ok) try {
+  TC_REQUIRE(ctx);
+  if (B == 0) return TC_OK;
+  TC_REQUIRE(ctx && a && b && ok && n >= 1);
+  TC_REQUIRE(n < (1ull << 32) && B < (1ull << 32) && n * B < (1ull << 32));
+  Call k(ctx);
+  const uint8_t* da = k.in(a, B * n * 96);
+  const uint8_t* db = k.in(b, B * n * 192);
+  uint8_t* d_ok = k.out(ok, B);
+  int32_t* ws = k.pairing_product_ws(n, B, false);
+  k.begin_timing();
+  k.check_points(false, da, 96, n, n, B, 1);
+  k.check_points(true, db, 192, n, n, B, 1);
+  if (!k.failed) tc::launch_pairing_product_check(ctx->stream, da, 96, db, 192, n, B, nullptr, 0, nullptr, 0, d_ok, ws);
+  k.apply_checks(B, nullptr, nullptr, 0, d_ok);
+  k.end_timing();
+  return k.finish();
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
 int tc_verify_g2_batch(tc_ctx* ctx, const uint8_t* pk, size_t pk_stride, const uint8_t* sig, const uint8_t* hash,
                        size_t B, uint8_t* ok) try {
   TC_REQUIRE(ctx);
@@ -1431,6 +1456,139 @@ int tc_ciphertext_verify_batch(tc_ctx* ctx, const uint8_t* u, const uint8_t* v, 
     tc::launch_pairing_check(ctx->stream, ctx->g1_gen_unfix, 0, d_w, 192, d_u, 96, d_hash, 192, B, d_ok, k.pairing_ws(B));
   }
   k.apply_checks(B, nullptr, nullptr, 0, d_ok);
+  k.end_timing();
+  return k.finish();
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+// Ciphertext::verify (src/lib.rs:508-512) for a batch by random linear combination, opt-in: the batch is cut into groups of
+// `group` ciphertexts, and a group passes with ONE product check
+//     e(g1, sum_j r_j w_j) == prod_j e(r_j u_j, H_j)          (H_j = hash_g1_g2(u_j, v_j); bilinearity; r_j secret)
+// -- `group` pairs, two per Miller loop, and ONE final exponentiation instead of `group` checks of two pairs each.  u_j and
+// H_j both differ per ciphertext, so nothing folds into a group sum on that side: the SAME r_j multiplies u_j in G1 and
+// enters the sum over w_j in G2.  The scalars are k_rlc_scalars' (k_check.hip): d0 + d1 |x| + d2 |x|^2 + d3 |x|^3 with four
+// 16-bit digits, d0 odd -- 2^63 values, pairwise distinct mod r, so for members of G1 / G2 a group holding an invalid
+// ciphertext passes with probability <= 2^-63.  That shape keeps the G2 sum (per point the dearer of the two ladders: Fq2
+// arithmetic on a lane pair, one table of psi-images per w_j) in its 16-column mode; in G1 the same value is
+// (d0 + d1 |x|) + (d2 + d3 |x|) x^2, two 80-bit halves: the short-scalar mode of k_msm_*_g1 with 40 base-4 steps instead of 64.
+// (k_rlc_scalars_g1's a + b x^2 would give G1 16 steps and G2 32 columns of 4 additions per chunk: more Fq2 additions than
+// the G1 steps it saves -- an operation count, NOT a measurement; msm_g1 with one point per job also fills three of the four
+// places of its chunk with the identity.)  A group that fails -- or whose sums report an error, or that holds an undecodable or, in
+// checked-input mode, non-member operand -- is re-checked ciphertext by ciphertext, so ok[] equals
+// tc_ciphertext_verify_batch's up to that 2^-63.
+int tc_ciphertext_verify_rlc_batch(tc_ctx* ctx, const uint8_t* u, const uint8_t* v, const uint64_t* off, const uint8_t* w, size_t B,
+                                   size_t group, const uint8_t* seed32, uint8_t* ok, uint64_t* n_fallback) try {
+  TC_REQUIRE(ctx);
+  if (n_fallback) *n_fallback = 0;
+  if (B == 0) return TC_OK;
+  TC_REQUIRE(ctx && u && off && w && seed32 && ok);
+  TC_REQUIRE(B < (1ull << 32));
+  if (group == 0) group = 64;
+  if (group > 1024) group = 1024;
+  if (group > B) group = B;
+  Call k(ctx);
+  uint64_t total = 0;
+  if (!total_bytes(k, off, B, &total)) return k.finish();
+  TC_REQUIRE(total == 0 || v);
+  const uint8_t* d_u = k.in(u, B * 96);
+  const uint8_t* d_v = k.in(v, (size_t)total);
+  const uint64_t* d_off = k.in(off, B + 1);
+  const uint8_t* d_w = k.in(w, B * 192);
+  uint8_t* d_seed = k.temp<uint8_t>(32);
+  if (d_seed) {
+    k.check(hipMemcpyAsync(d_seed, seed32, 32, hipMemcpyHostToDevice, ctx->stream), "seed copy");
+    ctx->h2d_bytes += 32;
+    k.wipe.emplace_back(d_seed, 32);
+  }
+  uint8_t* d_r = k.temp<uint8_t>(B * 32);
+  if (d_r) k.wipe.emplace_back(d_r, B * 32);
+  const size_t G = B / group, tail = B % group, NG = G + (tail ? 1 : 0);
+  uint8_t* d_hash = k.temp<uint8_t>(B * 192);
+  uint8_t* d_ru = k.temp<uint8_t>(B * 96);     // r_j u_j
+  uint8_t* d_W = k.temp<uint8_t>(NG * 192);    // sum_j r_j w_j per group
+  uint8_t* d_st = k.temp<uint8_t>(2 * B + NG); // hash | r_j u_j | group sums
+  uint8_t* d_okg = k.temp<uint8_t>(NG);
+  uint8_t* d_ok = k.out(ok, B);
+  int32_t* ws_groups = G ? k.pairing_product_ws(group, G, true) : nullptr;
+  int32_t* ws_tail = tail ? k.pairing_product_ws(tail, 1, true) : nullptr;
+  k.begin_timing();
+  k.check_points(false, d_u, 96, 1, 1, B, 1);
+  k.check_points(true, d_w, 192, 1, 1, B, 1);
+  std::vector<uint8_t> h_okg(NG), h_st(2 * B + NG), h_valid;
+  if (!k.failed) {
+    k.check(hipMemsetAsync(d_st, 0, 2 * B + NG, ctx->stream), "memset");
+    // an undecodable u leaves a hash that does not decode either (and a status): its group falls back
+    tc::launch_hash_g1_g2(ctx->tuning, ctx->stream, d_u, d_v, d_off, B, d_hash, d_st, /*fix=*/false);
+    tc::launch_rlc_scalars(ctx->stream, d_seed, B, d_r);
+    const uint32_t* rr = reinterpret_cast<const uint32_t*>(d_r);
+    msm_g1(k, 1, 96, d_u, rr, B, d_ru, d_st + B, /*nbits=*/80, /*secret_scalars=*/true);
+    if (G) msm_g2(k, group, group * 192, d_w, rr, G, d_W, d_st + 2 * B, /*nbits=*/16, tc::MsmFilter(), /*secret_scalars=*/true);
+    if (tail) msm_g2(k, tail, tail * 192, d_w + G * group * 192, rr + G * group * 8, 1, d_W + G * 192, d_st + 2 * B + G, 16, tc::MsmFilter(), true);
+    // prod_j e(r_j u_j, [c] Q'_j) == e(g1, W)  <=>  prod_j e(r_j u_j, Q'_j) == e([1/c] g1, W)   (the folded hash constant of
+    // tc_ciphertext_verify_batch)
+    if (G) tc::launch_pairing_product_check(ctx->stream, d_ru, 96, d_hash, 192, group, G, ctx->g1_gen_unfix, 0, d_W, 192, d_okg, ws_groups);
+    if (tail)
+      tc::launch_pairing_product_check(ctx->stream, d_ru + G * group * 96, 96, d_hash + G * group * 192, 192, tail, 1, ctx->g1_gen_unfix, 0,
+                                       d_W + G * 192, 192, d_okg + G, ws_tail);
+    k.check(hipMemsetAsync(d_ok, 1, B, ctx->stream), "memset");
+    k.check(hipMemcpyAsync(h_okg.data(), d_okg, NG, hipMemcpyDeviceToHost, ctx->stream), "ok readback");
+    k.check(hipMemcpyAsync(h_st.data(), d_st, 2 * B + NG, hipMemcpyDeviceToHost, ctx->stream), "status readback");
+    ctx->d2h_bytes += 2 * NG + 2 * B;
+    // checked-input mode: a group that owns a non-member operand goes to the per-ciphertext path as well
+    std::vector<const uint8_t*> valid_ptrs;
+    k.run_checks();  // (the membership tests ran beside the sums and the group checks; their verdicts are read back below)
+    for (auto& p : k.checks) valid_ptrs.push_back(p.valid);
+    const size_t n_checks = k.checks.size();
+    k.checks.clear();
+    if (n_checks) {
+      h_valid.resize(n_checks * B);
+      for (size_t q = 0; q < n_checks; q++)
+        k.check(hipMemcpyAsync(h_valid.data() + q * B, valid_ptrs[q], B, hipMemcpyDeviceToHost, ctx->stream), "valid readback");
+      ctx->d2h_bytes += n_checks * B;
+    }
+    k.check(hipStreamSynchronize(ctx->stream), "stream sync");
+    std::vector<uint32_t> failed;
+    if (!k.failed) {
+      for (size_t g = 0; g < NG; g++) {
+        bool bad = !h_okg[g] || h_st[2 * B + g] != TC_JOB_OK;
+        const size_t lo = g * group, hi = (lo + group < B) ? lo + group : B;
+        for (size_t j = lo; j < hi && !bad; j++) bad = h_st[j] != TC_JOB_OK || h_st[B + j] != TC_JOB_OK;
+        for (size_t q = 0; q < n_checks && !bad; q++)
+          for (size_t j = lo; j < hi && !bad; j++) bad = h_valid[q * B + j] == 0;
+        if (bad)
+          for (size_t j = lo; j < hi; j++) failed.push_back((uint32_t)j);
+      }
+    }
+    if (!k.failed && !failed.empty()) {
+      // the per-ciphertext check of tc_ciphertext_verify_batch for every ciphertext of the failed groups, on compacted operands
+      const size_t R = failed.size();
+      uint32_t* d_map = k.temp<uint32_t>(R);
+      uint8_t* c_u = k.temp<uint8_t>(R * 96);
+      uint8_t* c_hash = k.temp<uint8_t>(R * 192);
+      uint8_t* c_w = k.temp<uint8_t>(R * 192);
+      uint8_t* c_ok = k.temp<uint8_t>(R);
+      uint8_t* vv = ctx->input_checks ? k.temp<uint8_t>(R) : nullptr;
+      const tc::PairingWs pws = k.pairing_ws(R);
+      if (!k.failed) {
+        k.check(hipMemcpyAsync(d_map, failed.data(), R * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
+        ctx->h2d_bytes += 4 * R;
+        tc::launch_gather_rows(ctx->stream, d_u, 96, d_map, R, c_u);
+        tc::launch_gather_rows(ctx->stream, d_hash, 192, d_map, R, c_hash);
+        tc::launch_gather_rows(ctx->stream, d_w, 192, d_map, R, c_w);
+        tc::launch_pairing_check(ctx->stream, ctx->g1_gen_unfix, 0, c_w, 192, c_u, 96, c_hash, 192, R, c_ok, pws);  // src/lib.rs:511
+        if (ctx->input_checks) {  // members only, as the per-ciphertext path would require
+          tc::launch_subgroup_check_g1(ctx->stream, c_u, 96, 1, 1, R, vv);
+          tc::launch_invalidate_jobs(ctx->stream, vv, 1, 1, R, nullptr, nullptr, 0, c_ok);
+          tc::launch_subgroup_check_g2(ctx->stream, c_w, 192, 1, 1, R, vv);
+          tc::launch_invalidate_jobs(ctx->stream, vv, 1, 1, R, nullptr, nullptr, 0, c_ok);
+        }
+        tc::launch_scatter_bytes(ctx->stream, c_ok, d_map, R, d_ok);
+        k.check(hipStreamSynchronize(ctx->stream), "stream sync");  // the host map goes out of scope
+      }
+      if (n_fallback) *n_fallback = R;
+    }
+  }
   k.end_timing();
   return k.finish();
 } catch (...) {

@@ -444,6 +444,34 @@ TC_HD bool job_miller_io(bool live, IOA& a, IOB& b, IOC& c, IOD& d, Fq12& f) {
   f = miller_loop<2>(ps, qs);
   return ok;
 }
+// The Miller value of TWO pairs of an n-pair product  prod_k e(a_k, b_k)  (k_pairing.hip k_miller_pairs): no operand is negated
+// (NEG: both G1 operands are, for a pair that stands on the other side of the equation); has1 = false: the job's odd last pair,
+// whose partner is empty.  Every lane of the wave calls the four operand() functions.  false: an operand did not decode -- the
+// value is the empty product and the caller marks the job failed.
+template <bool NEG, class IOA, class IOB>
+TC_HD bool job_miller_pairs_io(bool has0, bool has1, IOA& a0, IOB& b0, IOA& a1, IOB& b1, Fq12& f) {
+  G1Affine ps[2] = {G1Affine::infinity(), G1Affine::infinity()};
+  G2Affine qs[2] = {G2Affine::infinity(), G2Affine::infinity()};
+  bool ok = true;
+  const uint8_t* e = a0.operand(0);
+  if (has0) ok &= g1_decode_uncompressed(e, ps[0]);
+  e = b0.operand(0);
+  if (has0) ok &= g2_decode_uncompressed(e, qs[0]);
+  e = a1.operand(0);
+  if (has1) ok &= g1_decode_uncompressed(e, ps[1]);
+  e = b1.operand(0);
+  if (has1) ok &= g2_decode_uncompressed(e, qs[1]);
+  if (!ok) {
+    ps[0] = ps[1] = G1Affine::infinity();
+    qs[0] = qs[1] = G2Affine::infinity();
+  }
+  if (NEG) {
+    ps[0].y = -ps[0].y;
+    ps[1].y = -ps[1].y;
+  }
+  f = miller_loop<2>(ps, qs);
+  return ok;
+}
 // The Miller loop itself in two stages that meet in memory (tc_pairing.h: prepared line products): stage P ...
 template <class IOA, class IOB, class IOC, class IOD>
 TC_HD bool job_miller_lines_io(bool live, IOA& a, IOB& b, IOC& c, IOD& d, const Fq2Rows& rows) {

@@ -187,6 +187,12 @@ size_t pairing_tile(size_t B, size_t budget_bytes);    // checks per pass of the
 size_t pairing_ws_words(size_t B, size_t tile);
 void launch_pairing_check(hipStream_t st, const uint8_t* a, size_t sa, const uint8_t* b, size_t sb, const uint8_t* c,
                           size_t sc, const uint8_t* d, size_t sd, size_t B, uint8_t* ok, PairingWs ws);
+// ok[j] = ( prod_{k < n} e(a[j n + k], b[j n + k]) == e(c[j], d[j]) ), or == 1 when c is null: two pairs per lane pair through
+// one Miller loop, the values of a job multiplied across lane pairs, ONE final exponentiation per job (k_pairing.hip).
+// Strides in bytes per pair, 0 broadcasts one operand.  ws: pairing_product_ws_words(n, B, c != nullptr) words.
+size_t pairing_product_ws_words(size_t n, size_t B, bool rhs);
+void launch_pairing_product_check(hipStream_t st, const uint8_t* a, size_t sa, const uint8_t* b, size_t sb, size_t n, size_t B, const uint8_t* c,
+                                  size_t sc, const uint8_t* d, size_t sd, uint8_t* ok, int32_t* ws);
 
 // fix = false: the hash point WITHOUT its last constant multiplication (tc_gls.h g2_clear_cofactor); the
 // caller folds the constant into a scalar (launch_fr_scale_cofactor_fix) or a G1 operand

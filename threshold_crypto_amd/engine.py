@@ -437,6 +437,40 @@ class Engine:
         self._call("tc_ciphertext_verify_batch", _ptr(u), _ptr(v), _ptr(off), _ptr(w), B, _ptr(ok))
         return ok
 
+    def ciphertext_verify_rlc(self, u, v, off, w, group=0, seed=None):
+        """Ciphertext::verify for a batch by random linear combination (opt-in; see tc_amd.h): groups of `group` ciphertexts
+        (0 = the default) pass with one product of pairings and ONE final exponentiation.  Returns (ok (B,), number of
+        ciphertexts that fell back to per-ciphertext checks).  `seed`: 32 secret random bytes (os.urandom when omitted)."""
+        import os
+        dev = self._mode(u, v, off, w)
+        self._arg(u, (None, G1_BYTES), "u8", "u")
+        B = u.shape[0]
+        self._msgs(v, off, B)
+        self._arg(w, (B, G2_BYTES), "u8", "w")
+        seed = bytes(seed) if seed is not None else os.urandom(32)
+        if len(seed) != 32:
+            raise ValueError("seed: 32 bytes")
+        ok = self._empty(dev, (B,), ref=u)
+        nfb = ctypes.c_uint64(0)
+        self._call("tc_ciphertext_verify_rlc_batch", _ptr(u), _ptr(v), _ptr(off), _ptr(w), B, int(group), seed, _ptr(ok), ctypes.byref(nfb))
+        return ok, int(nfb.value)
+
+    def pairing_product_check(self, a, b, n):
+        """ok[j] = ( prod_{k < n} e(a[j * n + k], b[j * n + k]) == 1 ): a (B * n, 96) G1 points, b (B * n, 192) G2 points, job by
+        job; an identity operand contributes the factor 1, an undecodable one gives 0."""
+        n = int(n)
+        if n < 1:
+            raise ValueError("n: at least one pair per job")
+        dev = self._mode(a, b)
+        self._arg(a, (None, G1_BYTES), "u8", "a")
+        if a.shape[0] % n:
+            raise ValueError("a: a multiple of n points")
+        self._arg(b, (a.shape[0], G2_BYTES), "u8", "b")
+        B = a.shape[0] // n
+        ok = self._empty(dev, (B,), ref=a)
+        self._call("tc_pairing_product_check_batch", _ptr(a), _ptr(b), n, B, _ptr(ok))
+        return ok
+
     def decrypt_share(self, fr, u, v, off, w):
         """SecretKeyShare::decrypt_share (src/lib.rs:452-457) for one key share and B ciphertexts -> (shares (B, 96), ok (B,)):
         ok[j] = Ciphertext::verify, the share of a ciphertext that fails it is the identity (the reference returns None)."""
