@@ -31,12 +31,22 @@
 // words in the slot after the points.  An op hands back the Jacobian result as the routine returns it (slot 0 on), then
 // jac_to_affine of it (what every shipped job body does next) with the infinity bit in flag 0.  Ops whose routine keeps
 // a table in the arena of tc_table.h (conf_needs_table) run with a table slot held, as the product's kernels do.
+//
+// The byte layer (ops 180 on: hash primitives and G1, one lane per job; ops 200 on: everything that holds Fq2 or calls
+// duo_each, a lane pair per job) applies the code on either side of the arithmetic: SHA3-256, the ChaCha20 word stream,
+// the rejection samplers and the hash onto G2 of tc_hash.h, the wire codecs of tc_codec.h / tc_sqrt.h and the job_*
+// wrappers of tc_jobs.h around them.  Byte operands go in as raw words (in_bytes: byte k of the job's input row,
+// little-endian), a length in aux.  Byte results are written by the shipped routine itself, through Ctx::bytes (the
+// job's output row as bytes) from EVERY lane of the job -- in the lane-pair build each lane stores its own 48-byte half
+// --, so lanes past the end of the batch get a spare row from the launcher.  Status bytes and verdicts go in flags.
 #pragma once
 #include "../../threshold_crypto_amd/csrc/tc_codec.h"  // (tc_quad.h job_pairing_check_quad_io decodes)
 #include "../../threshold_crypto_amd/csrc/tc_quad.h"
 #include "../../threshold_crypto_amd/csrc/tc_sqrt.h"
 #include "../../threshold_crypto_amd/csrc/tc_msm.h"
 #include "../../threshold_crypto_amd/csrc/tc_dkg.h"
+#include "../../threshold_crypto_amd/csrc/tc_hash.h"
+#include "../../threshold_crypto_amd/csrc/tc_jobs.h"
 
 namespace tc {
 namespace conf {
@@ -76,6 +86,13 @@ enum Op {
   // point multiplication on G2 (lane pair)
   G2_ADD_AFFINE = 160, G2_COMMON_Z, G2_MUL_BY_X_ABS, G2_PSI_JAC, G2_GLS_BASES, G2_SAC_TABLE, G2_JOINT_MUL4, G2_MUL_GLS,
   G2_MUL_GLS_JAC, G2_CLEAR_COFACTOR, G2_STRAUS_SMALL, G2_COMBINE_DIVIDE,
+  // the byte layer: hash primitives and G1, one lane per job
+  SHA3_256 = 180, CHACHA_WORDS, FQ_RANDOM, XOR_WITH_HASH, FQ_FROM_BE48, FQ_TO_BE48, FQ_LEX_LARGEST, G1_DECODE_UNCOMPRESSED,
+  G1_ENCODE_UNCOMPRESSED, G1_ENCODE_COMPRESSED, G1_DECODE_COMPRESSED,
+  // the byte layer on Fq2 / two jobs per pair (lane pair)
+  G2_RANDOM_FROM_SEED = 200, G2_RANDOM_FROM_SEED_X2, HASH_G2, HASH_G2_X2, HASH_G1_G2, HASH_G1_G2_X2, FQ2_FROM_BE96,
+  FQ2_TO_BE96, FQ2_LEX_LARGEST, G2_DECODE_UNCOMPRESSED, G2_ENCODE_UNCOMPRESSED, G2_ENCODE_COMPRESSED, G2_DECODE_COMPRESSED,
+  G2_DECODE_COMPRESSED_X2,
 };
 
 // the quad ops (tc_quad.h): four lanes per job on the device, two threads per job on the host
@@ -83,7 +100,10 @@ TC_HD constexpr bool conf_quad(int op) { return op >= Q_MILLER_LOOP && op < FR_A
 // lanes per job on the device: Fq, G1 and the scalar block one, everything that holds Fq2 values a lane pair
 TC_HD constexpr int conf_lanes(int op) {
   return conf_quad(op) ? kQuadLanes
-         : (op >= FQ2_MUL && op < G1_DBL) || (op >= G2_DBL && op < FR_ADD) || op >= G2_ADD_AFFINE ? kG2Lanes : 1;
+         : (op >= FQ2_MUL && op < G1_DBL) || (op >= G2_DBL && op < FR_ADD) || (op >= G2_ADD_AFFINE && op < SHA3_256) ||
+                 op >= G2_RANDOM_FROM_SEED
+             ? kG2Lanes
+             : 1;
 }
 // ops whose routine keeps a table in the arena (tc_table.h): the kernel holds a table slot while the op runs
 TC_HD constexpr bool conf_needs_table(int op) {
@@ -121,6 +141,10 @@ struct Ctx {
   template <class F>
   TC_HD F field(int s) const;
   TC_HD const uint32_t* words(int s) const { return (const uint32_t*)(in + s * FQ_LIMBS); }
+  // the byte layer: byte k of the job's input row (raw words, little-endian) / of its output row.  The shipped routines
+  // store through bytes() from every lane of the job; a lane past the end of the batch has a spare row behind `out`
+  TC_HD const uint8_t* in_bytes(int k) const { return (const uint8_t*)in + k; }
+  TC_HD uint8_t* bytes(int k) const { return (uint8_t*)out + k; }
   // the scalar block: u64 k of the raw words from slot 0 on (two words each, low word first)
   TC_HD uint64_t u64(int k) const {
     const uint32_t* w = words(0);
@@ -601,6 +625,173 @@ TC_HD void conf_mul(Ctx& c) {
   }
 }
 
+// ---- the byte layer: SHA3, ChaCha20, the samplers and the hash onto G2; the wire codecs and their job_* wrappers --------
+// byte offsets inside the job's rows (the case tables of tests/device_conformance.py use the same)
+constexpr int kConfG1B = 96, kConfMsg = 96;                    // HASH_G1_G2 / XOR_WITH_HASH: g1 at 0, the message at 96
+constexpr int kConfMsgB2 = 1120;                               // HASH_G2_X2: message A at 0, B at 1120
+constexpr int kConfMsgA4 = 192, kConfMsgB4 = 1216;             // HASH_G1_G2_X2: g1 A at 0, g1 B at 96, messages at 192 / 1216
+constexpr int kConfWrap = 10 * FQ_LIMBS * 4;                   // decode ops: the wrapper's output bytes, from slot 10 on
+
+// the stream words an rng has handed out so far (ChaChaRng: `counter` blocks refilled, `idx` words of the last one used)
+TC_HD uint32_t conf_words_used(const ChaChaRng& rng) { return (uint32_t)rng.counter * 16u + (uint32_t)rng.idx - 16u; }
+
+template <class F>
+TC_HD void put_decoded(Ctx& c, bool ok, const Affine<F>& p) {
+  put_aff(c, 0, p);
+  c.flag(0, ok);
+  c.flag(1, p.inf);
+}
+
+template <int OP>
+TC_HD void conf_bytes(Ctx& c) {
+  if constexpr (OP == SHA3_256) {  // aux[0] = len, aux[1]: the out-of-line form
+    uint32_t w[8];
+    if (c.aux[1]) {
+      sha3_256_words_call(c.in_bytes(0), (size_t)c.aux[0], w);
+    } else {
+      sha3_256_words(c.in_bytes(0), (size_t)c.aux[0], w);
+    }
+    c.put_words(0, w, 8);
+  } else if constexpr (OP == CHACHA_WORDS) {
+    // key = the words of slot 0; aux[1]: start at the counter in the words of slot 1; aux[0] <= 64 words, then idx and counter
+    ChaChaRng rng;
+    rng.init(c.words(0));
+    if (c.aux[1]) rng.counter = c.u64_at(1, 0);
+    const int n = c.aux[0];
+    TC_NOUNROLL for (int i = 0; i < 64; i++) {
+      if (i < n) {
+        const uint32_t w = rng.next_u32();
+        if (c.writer()) c.out[i] = (int32_t)w;
+      }
+    }
+    const uint32_t tail[3] = {(uint32_t)rng.idx, (uint32_t)rng.counter, (uint32_t)(rng.counter >> 32)};
+    c.put_words(5, tail, 3);
+  } else if constexpr (OP == FQ_RANDOM) {
+    // seed = the words of slot 0; aux[0] <= 8 draws (slot k), the stream words used after each (the words of slot 8)
+    ChaChaRng rng;
+    rng.init(c.words(0));
+    const int n = c.aux[0];
+    TC_NOUNROLL for (int k = 0; k < 8; k++) {  // (every lane draws eight times: fq_random decides per wave)
+      const Fq v = fq_random(rng);
+      const uint32_t used = conf_words_used(rng);
+      if (k < n) {
+        c.put(k, v);
+        if (c.writer()) c.out[8 * FQ_LIMBS + k] = (int32_t)used;
+      }
+    }
+  } else if constexpr (OP == XOR_WITH_HASH) {
+    c.flag(0, job_xor_with_hash(c.in_bytes(0), c.in_bytes(kConfMsg), (size_t)c.aux[0], c.bytes(0)));
+  } else if constexpr (OP == FQ_FROM_BE48) {
+    Fq v;
+    const bool ok = fq_from_be48(c.in_bytes(0), c.aux[0] != 0, v);
+    c.put(0, v);
+    c.flag(0, ok);
+  } else if constexpr (OP == FQ_TO_BE48) {
+    fq_to_be48(c.fq(0), c.bytes(0));
+  } else if constexpr (OP == FQ_LEX_LARGEST) {
+    c.flag(0, fq_lex_largest(c.fq(0)));
+  } else if constexpr (OP == FQ2_FROM_BE96) {
+    Fq2 v;
+    const bool ok = fq2_from_be96(c.in_bytes(0), c.aux[0] != 0, v);
+    c.put(0, v);
+    c.flag(0, ok);
+  } else if constexpr (OP == FQ2_TO_BE96) {
+    fq2_to_be96(c.fq2(0), c.bytes(0));
+  } else if constexpr (OP == FQ2_LEX_LARGEST) {
+    c.flag(0, fq2_lex_largest(c.fq2(0)));
+  // ---- decode: the routine (point at slot 0, flag 0 = verdict, flag 1 = infinity), then its wrapper (bytes from slot 10 on,
+  // flag 2 = status) ----
+  } else if constexpr (OP == G1_DECODE_UNCOMPRESSED) {
+    G1Affine p = G1Affine::infinity();
+    const bool ok = g1_decode_uncompressed(c.in_bytes(0), p);
+    put_decoded(c, ok, p);
+    c.flag(2, job_compress<Fq>(c.in_bytes(0), c.bytes(kConfWrap)));
+  } else if constexpr (OP == G2_DECODE_UNCOMPRESSED) {
+    G2Affine p = G2Affine::infinity();
+    const bool ok = g2_decode_uncompressed(c.in_bytes(0), p);
+    put_decoded(c, ok, p);
+    c.flag(2, job_compress<Fq2>(c.in_bytes(0), c.bytes(kConfWrap)));
+  } else if constexpr (OP == G1_DECODE_COMPRESSED) {
+    G1Affine p = G1Affine::infinity();
+    const bool ok = g1_decode_compressed(c.in_bytes(0), p);
+    put_decoded(c, ok, p);
+    c.flag(2, job_decompress<Fq>(c.in_bytes(0), c.bytes(kConfWrap)));
+  } else if constexpr (OP == G2_DECODE_COMPRESSED) {
+    G2Affine p = G2Affine::infinity();
+    const bool ok = g2_decode_compressed(c.in_bytes(0), p);
+    put_decoded(c, ok, p);
+    c.flag(2, job_decompress<Fq2>(c.in_bytes(0), c.bytes(kConfWrap)));
+  } else if constexpr (OP == G2_DECODE_COMPRESSED_X2) {
+    // encodings at bytes 0 and 96; points at slots 0 and 4, flags 0 / 1 = verdict + 2 * infinity of A / B; the wrapper's
+    // outputs from slot 10 on (A, then B unless aux[0]: out_b null), flags 2 / 3 = its statuses
+    G2Affine pa, pb;
+    bool oka, okb;
+    g2_decode_compressed_x2(c.in_bytes(0), c.in_bytes(96), pa, pb, oka, okb);
+    put_aff(c, 0, pa);
+    put_aff(c, 4, pb);
+    c.flag(0, (int)oka | ((int)pa.inf << 1));
+    c.flag(1, (int)okb | ((int)pb.inf << 1));
+    uint8_t sa = 0xee, sb = 0xee;
+    job_decompress_g2_x2(c.in_bytes(0), c.in_bytes(96), c.bytes(kConfWrap), c.aux[0] ? nullptr : c.bytes(kConfWrap + 192), sa, sb);
+    c.flag(2, sa);
+    c.flag(3, sb);
+  // ---- encode: an affine point in limbs (aux[0] = at infinity) to bytes ----
+  } else if constexpr (OP == G1_ENCODE_UNCOMPRESSED) {
+    g1_encode_uncompressed(aff_at<Fq>(c, 0, c.aux[0]), c.bytes(0));
+  } else if constexpr (OP == G1_ENCODE_COMPRESSED) {
+    g1_encode_compressed(aff_at<Fq>(c, 0, c.aux[0]), c.bytes(0));
+  } else if constexpr (OP == G2_ENCODE_UNCOMPRESSED) {
+    g2_encode_uncompressed(aff_at<Fq2>(c, 0, c.aux[0]), c.bytes(0));
+  } else if constexpr (OP == G2_ENCODE_COMPRESSED) {
+    g2_encode_compressed(aff_at<Fq2>(c, 0, c.aux[0]), c.bytes(0));
+  // ---- the hash onto G2 ----
+  } else if constexpr (OP == G2_RANDOM_FROM_SEED || OP == G2_RANDOM_FROM_SEED_X2) {
+    // seed(s) = the words of slot 0 (and 1); aux[0] = fix; aux[1] = outer rounds to force (a build with TC_TEST_HOOKS only:
+    // the last flag says how many were forced, so the check knows which candidate it is looking at)
+    int forced = 0;
+#if defined(TC_TEST_HOOKS)
+    forced = g_tc_force_extra_rounds = c.aux[1];
+#endif
+    if constexpr (OP == G2_RANDOM_FROM_SEED) {
+      put_result(c, g2_random_from_seed(c.words(0), c.aux[0] != 0));
+      c.flag(1, forced);
+    } else {
+      Seed8 sa, sb;
+      TC_UNROLL for (int i = 0; i < 8; i++) {
+        sa.w[i] = c.words(0)[i];
+        sb.w[i] = c.words(1)[i];
+      }
+      G2Jac ra, rb;
+      g2_random_from_seed_x2(duo_pick(sa, sb), c.aux[0] != 0, ra, rb);
+      put_jac(c, 0, ra);
+      put_jac(c, 6, rb);
+      G2Affine pa, pb;
+      jac_to_affine_x2(ra, rb, pa, pb);
+      put_aff(c, 12, pa);
+      put_aff(c, 16, pb);
+      c.flag(0, pa.inf);
+      c.flag(1, pb.inf);
+      c.flag(2, forced);
+    }
+#if defined(TC_TEST_HOOKS)
+    g_tc_force_extra_rounds = 0;
+#endif
+  } else if constexpr (OP == HASH_G2) {  // aux[0] = len, aux[1] = fix
+    job_hash_g2(c.in_bytes(0), (size_t)c.aux[0], c.bytes(0), c.aux[1] != 0);
+  } else if constexpr (OP == HASH_G2_X2) {  // aux[0], aux[1] = lengths, aux[2] = fix + 2 * (out_b null)
+    job_hash_g2_x2(c.in_bytes(0), (size_t)c.aux[0], c.in_bytes(kConfMsgB2), (size_t)c.aux[1], c.bytes(0),
+                   (c.aux[2] & 2) ? nullptr : c.bytes(192), (c.aux[2] & 1) != 0);
+  } else if constexpr (OP == HASH_G1_G2) {
+    c.flag(0, job_hash_g1_g2(c.in_bytes(0), c.in_bytes(kConfMsg), (size_t)c.aux[0], c.bytes(0), c.aux[1] != 0));
+  } else if constexpr (OP == HASH_G1_G2_X2) {
+    uint8_t sa = 0xee, sb = 0xee;
+    job_hash_g1_g2_x2(c.in_bytes(0), c.in_bytes(kConfMsgA4), (size_t)c.aux[0], c.in_bytes(kConfG1B), c.in_bytes(kConfMsgB4),
+                      (size_t)c.aux[1], c.bytes(0), (c.aux[2] & 2) ? nullptr : c.bytes(192), (c.aux[2] & 1) != 0, sa, sb);
+    c.flag(0, sa);
+    c.flag(1, sb);
+  }
+}
+
 template <int OP>
 TC_HD void conf_op(Ctx& c) {
   // ---- Fq ---------------------------------------------------------------------------------------------------------
@@ -746,8 +937,11 @@ TC_HD void conf_op(Ctx& c) {
   } else if constexpr (OP >= FR_ADD && OP < G1_ADD_AFFINE) {
     conf_scalar<OP>(c);
   // ---- the point-multiplication block -------------------------------------------------------------------------------
-  } else if constexpr (OP >= G1_ADD_AFFINE) {
+  } else if constexpr (OP >= G1_ADD_AFFINE && OP < SHA3_256) {
     conf_mul<OP>(c);
+  // ---- the byte layer -------------------------------------------------------------------------------------------------
+  } else if constexpr (OP >= SHA3_256) {
+    conf_bytes<OP>(c);
   }
 }
 
@@ -769,7 +963,12 @@ TC_HD void conf_op(Ctx& c) {
   X(G1_ADD_AFFINE) X(G1_COMMON_Z) X(G1_MUL_BY_X_ABS) X(G1_MUL_GLV) X(G1_MUL_GLV_JAC) X(G1_MUL_GLV_ARENA)                \
   X(G1_LINCOMB_CHUNK4) X(G1_STRAUS_SMALL) X(G1_STRAUS_SMALL_INLINE) X(G1_COMBINE_DIVIDE) X(G1_COMBINE_DIVIDE_ARENA)     \
   X(G1_MUL_U64) X(G2_ADD_AFFINE) X(G2_COMMON_Z) X(G2_MUL_BY_X_ABS) X(G2_PSI_JAC) X(G2_GLS_BASES) X(G2_SAC_TABLE)        \
-  X(G2_JOINT_MUL4) X(G2_MUL_GLS) X(G2_MUL_GLS_JAC) X(G2_CLEAR_COFACTOR) X(G2_STRAUS_SMALL) X(G2_COMBINE_DIVIDE)
+  X(G2_JOINT_MUL4) X(G2_MUL_GLS) X(G2_MUL_GLS_JAC) X(G2_CLEAR_COFACTOR) X(G2_STRAUS_SMALL) X(G2_COMBINE_DIVIDE)      \
+  X(SHA3_256) X(CHACHA_WORDS) X(FQ_RANDOM) X(XOR_WITH_HASH) X(FQ_FROM_BE48) X(FQ_TO_BE48) X(FQ_LEX_LARGEST)             \
+  X(G1_DECODE_UNCOMPRESSED) X(G1_ENCODE_UNCOMPRESSED) X(G1_ENCODE_COMPRESSED) X(G1_DECODE_COMPRESSED)                   \
+  X(G2_RANDOM_FROM_SEED) X(G2_RANDOM_FROM_SEED_X2) X(HASH_G2) X(HASH_G2_X2) X(HASH_G1_G2) X(HASH_G1_G2_X2)              \
+  X(FQ2_FROM_BE96) X(FQ2_TO_BE96) X(FQ2_LEX_LARGEST) X(G2_DECODE_UNCOMPRESSED) X(G2_ENCODE_UNCOMPRESSED)                \
+  X(G2_ENCODE_COMPRESSED) X(G2_DECODE_COMPRESSED) X(G2_DECODE_COMPRESSED_X2)
 
 }  // namespace conf
 }  // namespace tc

@@ -26,7 +26,8 @@ __global__ __launch_bounds__(kBlock) void k_conf(const int32_t* in, const int32_
   int job = t / lanes;
   const bool live = job < n;
   if (!live) job = n - 1;  // lanes past the end run a copy of the last job (the pair exchanges and ballots need every lane)
-  Ctx c{in + (size_t)job * CONF_IN * FQ_LIMBS, aux + (size_t)job * CONF_AUX, out + (size_t)job * CONF_OUT * FQ_LIMBS,
+  // (the byte layer's routines store through the output row from every lane: a lane past the end gets the spare row n)
+  Ctx c{in + (size_t)job * CONF_IN * FQ_LIMBS, aux + (size_t)job * CONF_AUX, out + (size_t)(live ? job : n) * CONF_OUT * FQ_LIMBS,
         flags + (size_t)job * CONF_FLAGS, nullptr, live, t % lanes, lanes >= 2};
   if (rows) c.rows = rows + (size_t)blockIdx.x * kConfLineWords * 64 + threadIdx.x;
   conf_op<OP>(c);
@@ -54,6 +55,7 @@ static hipError_t dispatch(int op, const int32_t* in, const int32_t* aux, int32_
 
 // n jobs of op `op` on the current device.  Host buffers in (n x CONF_IN x 14), aux (n x CONF_AUX), out (n x CONF_OUT x 14)
 // and flags (n x CONF_FLAGS); out and flags are copied in first, so entries an op does not write keep the caller's value.
+// The device's out has one row more than the host's: the spare row that lanes past the end of the batch store into.
 // rows (conf_needs_rows ops, else unused): n x kMillerRowSlots x 2 x 14 -- slot k of job j as (re, im) limbs, gathered
 // from the device row block (re on the even lane of the pair, im on the odd one), which is filled with a poison pattern
 // before the launch so that a row read before it is written gives a wrong result.  conf_needs_table ops get a table arena
@@ -63,7 +65,7 @@ constexpr int kConfSlotLeak = -2;
 extern "C" int tc_conf_run(int op, int n, const int32_t* in, const int32_t* aux, int32_t* out, int32_t* flags, int32_t* rows) {
   if (n <= 0) return (int)hipErrorInvalidValue;
   const size_t sin = (size_t)n * CONF_IN * FQ_LIMBS * 4, saux = (size_t)n * CONF_AUX * 4;
-  const size_t sout = (size_t)n * CONF_OUT * FQ_LIMBS * 4, sfl = (size_t)n * CONF_FLAGS * 4;
+  const size_t srow = (size_t)CONF_OUT * FQ_LIMBS * 4, sout = (size_t)n * srow, sfl = (size_t)n * CONF_FLAGS * 4;
   const size_t nrow = conf_needs_rows(op) ? (size_t)conf_grid(op, n) * kConfLineWords * 64 : 0;
   int32_t *din = nullptr, *daux = nullptr, *dout = nullptr, *dfl = nullptr, *drows = nullptr;
   TableArena ta{nullptr, nullptr};
@@ -71,7 +73,7 @@ extern "C" int tc_conf_run(int op, int n, const int32_t* in, const int32_t* aux,
   bool leak = false;
   hipError_t e = hipMalloc(&din, sin);
   if (e == hipSuccess) e = hipMalloc(&daux, saux);
-  if (e == hipSuccess) e = hipMalloc(&dout, sout);
+  if (e == hipSuccess) e = hipMalloc(&dout, sout + srow);
   if (e == hipSuccess) e = hipMalloc(&dfl, sfl);
   if (e == hipSuccess && nrow) e = hipMalloc(&drows, nrow * 4);
   if (e == hipSuccess && nrow) e = hipMemset(drows, 0x5A, nrow * 4);

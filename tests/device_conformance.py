@@ -26,7 +26,13 @@ Which path a case takes (the branch-free pass alone, or the safe ladder after a 
 that walks the ladder's columns on the oracle's group law (the *_model functions); ops with a table in the arena of
 tc_table.h (NEEDS_TABLE) run with a slot held, and the device leg fails if a slot stays marked in use.
 
-    python tests/device_conformance.py host OPNAME      (the host leg of one op; exit status 0 = every case passed)
+The byte layer (ops 180 on: hash primitives and G1, one lane per job; 200 on: a lane pair) checks the code on either side of
+the arithmetic -- SHA3-256, the ChaCha20 word stream, the rejection samplers, the hash onto G2, the wire codecs and the job_*
+wrappers around them -- against hashlib, the oracle's ChaCha and samplers, and its decoders.  Byte operands go in as raw
+words (raw_bytes), byte results are read back from the output row, which stays filled with the sentinel wherever the
+routine's documented length ends (check_row).  byte_cases() is the one shared table of encodings, each with the oracle's verdict.
+
+    python tests/device_conformance.py host OPNAME     (the host leg of one op; exit status 0 = every case passed)
 """
 import ctypes
 import hashlib
@@ -91,12 +97,17 @@ OPS = dict(
     G1_COMBINE_DIVIDE_ARENA=150, G1_MUL_U64=151,
     G2_ADD_AFFINE=160, G2_COMMON_Z=161, G2_MUL_BY_X_ABS=162, G2_PSI_JAC=163, G2_GLS_BASES=164, G2_SAC_TABLE=165,
     G2_JOINT_MUL4=166, G2_MUL_GLS=167, G2_MUL_GLS_JAC=168, G2_CLEAR_COFACTOR=169, G2_STRAUS_SMALL=170,
-    G2_COMBINE_DIVIDE=171)
+    G2_COMBINE_DIVIDE=171,
+    SHA3_256=180, CHACHA_WORDS=181, FQ_RANDOM=182, XOR_WITH_HASH=183, FQ_FROM_BE48=184, FQ_TO_BE48=185, FQ_LEX_LARGEST=186,
+    G1_DECODE_UNCOMPRESSED=187, G1_ENCODE_UNCOMPRESSED=188, G1_ENCODE_COMPRESSED=189, G1_DECODE_COMPRESSED=190,
+    G2_RANDOM_FROM_SEED=200, G2_RANDOM_FROM_SEED_X2=201, HASH_G2=202, HASH_G2_X2=203, HASH_G1_G2=204, HASH_G1_G2_X2=205,
+    FQ2_FROM_BE96=206, FQ2_TO_BE96=207, FQ2_LEX_LARGEST=208, G2_DECODE_UNCOMPRESSED=209, G2_ENCODE_UNCOMPRESSED=210,
+    G2_ENCODE_COMPRESSED=211, G2_DECODE_COMPRESSED=212, G2_DECODE_COMPRESSED_X2=213)
 
 
 def lanes(op):
     i = OPS[op]
-    return 4 if 90 <= i < 100 else 2 if (20 <= i < 60 or 70 <= i < 90 or i >= 160) else 1
+    return 4 if 90 <= i < 100 else 2 if (20 <= i < 60 or 70 <= i < 90 or 160 <= i < 180 or i >= 200) else 1
 
 
 NEEDS_ROWS = {"MILLER_LINES"}  # conformance.h conf_needs_rows
@@ -152,7 +163,8 @@ def build_host():
     """The same op bodies for the host (host Fq2 form), under the interval analysis."""
     src = os.path.join(DEV, "conformance_host.cpp")
     return _build("libtc_conformance_host_bc",
-                  lambda out: ["g++", "-O1", "-std=c++17", "-w", "-DTC_BOUND_CHECK", "-shared", "-fPIC", "-pthread", src, "-o", out],
+                  lambda out: ["g++", "-O1", "-std=c++17", "-w", "-DTC_BOUND_CHECK", "-DTC_TEST_HOOKS", "-shared", "-fPIC", "-pthread", src,
+                               "-o", out],
                   {"conformance_host.cpp"})
 
 
@@ -3513,6 +3525,851 @@ def _(case=None, out=None, flags=None, rnd=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the byte layer (ops 180 on): SHA3, ChaCha20, the samplers and the hash onto G2; the wire codecs and their wrappers
+# ---------------------------------------------------------------------------------------------------------------------
+ROW_BYTES = CONF_OUT * NL * 4  # 2240: a job's row as bytes
+SLOT_BYTES = NL * 4
+WRAP = 10 * SLOT_BYTES  # conformance.h kConfWrap: where the decode ops put their wrapper's bytes
+MSG_B2, MSG_A4, MSG_B4 = 1120, 192, 1216  # conformance.h kConfMsgB2, kConfMsgA4, kConfMsgB4
+SENT_ROW = bytes([SENTINEL & 0xff]) * ROW_BYTES
+TABLES = {}  # op -> (edges, rnd) -> the whole table, for ops whose wave layout the generic hooks cannot express
+BYTE_OPS_FROM = 180
+
+
+def raw_bytes(parts):
+    """Byte operands [(byte offset in the job's input row, bytes)] as raw little-endian words (beside raw_words)."""
+    end = max([off + len(b) for off, b in parts] + [0])
+    buf = bytearray(-(-end // 4) * 4)
+    for off, b in parts:
+        buf[off:off + len(b)] = b
+    return raw_words([int.from_bytes(buf[k:k + 4], "little") for k in range(0, len(buf), 4)]) if buf else []
+
+
+def bcase(parts, aux=(), tag="", **kw):
+    c = Case(raw_bytes(parts), aux=aux, tag=tag)
+    c.__dict__.update(kw)
+    return c
+
+
+def _sl(s, n=1):
+    return (SLOT_BYTES * s, SLOT_BYTES * (s + n))
+
+
+def check_row(case, out, want, regions, what):
+    """want: [(byte offset, bytes)] the row must hold; outside `regions` (and the wanted bytes) every byte still holds
+    the sentinel the row was filled with: the routine wrote exactly its documented length."""
+    row = bytearray(out.tobytes())
+    for off, b in want:
+        got = bytes(row[off:off + len(b)])
+        expect(got == bytes(b), case, "%s: bytes at %d: %s, want %s" % (what, off, got.hex(), bytes(b).hex()))
+    for a, b in list(regions) + [(off, off + len(b)) for off, b in want]:
+        row[a:b] = SENT_ROW[a:b]
+    if bytes(row) != SENT_ROW:
+        k = next(i for i in range(ROW_BYTES) if row[i] != SENT_ROW[i])
+        expect(False, case, "%s: byte %d past the documented output was written (%02x)" % (what, k, row[k]))
+
+
+def fixed_layout(op, uniform, mixed):
+    """TABLES hook: one full wave per maker of `uniform` (every job of the wave from that maker), then the directed cases
+    interleaved with cases of the `mixed` makers in turn, to three waves and a ragged tail at least."""
+    def build(edges, rnd):
+        wave = 64 // lanes(op)
+        cases = []
+        for make in uniform:
+            cases += [make(rnd) for _ in range(wave)]
+        pool = list(edges)
+        n = max(len(cases) + 2 * len(pool), 3 * wave + 5)
+        if n % wave == 0:
+            n += 1
+        k = 0
+        while len(cases) < n:
+            if pool and (len(cases) % 2 == 0 or len(cases) + len(pool) >= n):
+                cases.append(pool.pop(0))
+            else:
+                cases.append(mixed[k % len(mixed)](rnd))
+                k += 1
+        return cases
+    TABLES[op] = build
+
+
+# ---- SHA3-256 ----------------------------------------------------------------------------------------------------------
+SHA3_RATE = 136
+SHA3_LENGTHS = [0, 1, 135, 136, 137, 271, 272, 273, 408, 2240]
+
+
+def sha3_blocks(n):
+    return n // SHA3_RATE + 1
+
+
+def _sha_case(msg, call, tag):
+    pad = bytes([0xa5]) * min(8, ROW_BYTES - len(msg))  # (bytes past the end that must not be read into the digest)
+    return bcase([(0, bytes(msg) + pad)], [len(msg), call], "%s len=%d call=%d" % (tag, len(msg), call), msg=bytes(msg))
+
+
+def _sha_rand(blocks):
+    def make(rnd):
+        n = rnd.randrange(SHA3_RATE * (blocks - 1), min(SHA3_RATE * blocks, ROW_BYTES + 1))
+        return _sha_case(rnd.randbytes(n), rnd.randrange(2), "random")
+    return make
+
+
+@spec("SHA3_256", _sha_rand(1))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        cases = [_sha_case(rnd.randbytes(n), call, "length") for n in SHA3_LENGTHS for call in (0, 1)]
+        cases += [_sha_case(bytes([0xff]) * n, n % 2, "all ff") for n in (1, 135, 136, 137, 272, 2240)]
+        cases += [_sha_case(rnd.randbytes(n - 1) + bytes([last]), (n + last) % 2, "last byte %02x" % last)
+                  for n in (1, 135, 136, 137, 272) for last in (0x06, 0x80)]
+        return cases
+    d = hashlib.sha3_256(case.msg).digest()
+    check_row(case, out, [(0, d)], [], "sha3_256")
+
+
+fixed_layout("SHA3_256", [_sha_rand(1), _sha_rand(2)], [_sha_rand(b) for b in (1, 2, 3, 17)])
+
+
+# ---- ChaCha20 word stream ------------------------------------------------------------------------------------------------
+CHACHA_COUNTS = [0, 1, 15, 16, 17, 32, 33, 64]
+CHACHA_ZERO_KEY_BLOCK = ("76b8e0ada0f13d90405d6ae55386bd28bdd219b8a08ded1aa836efcc8b770dc7"
+                         "da41597c5157488d7724e03fb8d84a376a43b8f41518a11cc387b669b2ee6586")  # the published all-zero-key block
+
+
+def chacha_words(key, ctr, n):
+    ws = []
+    for b in range(-(-n // 16)):
+        ws += o.chacha20_block(key, (ctr + b) & M64)
+    return ws[:n]
+
+
+def _chacha_case(key, n, ctr, tag=""):
+    use = ctr is not None
+    ws = list(key) + [0] * (NL - 8) + u32s(ctr or 0, 2)
+    return scase(ws, [n, int(use)], "%s n=%d ctr=%s" % (tag, n, ctr), key=list(key), n=n, ctr=ctr or 0)
+
+
+def _rand_chacha(rnd):
+    return _chacha_case([rnd.getrandbits(32) for _ in range(8)], rnd.randint(0, 64),
+                        rnd.choice([None, 0, (1 << 32) - 1, rnd.getrandbits(64) >> rnd.choice([0, 31, 40])]), "random")
+
+
+@spec("CHACHA_WORDS", _rand_chacha)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        key = [rnd.getrandbits(32) for _ in range(8)]
+        cases = [_chacha_case(k, n, ctr, "edge") for n in CHACHA_COUNTS for ctr in (None, (1 << 32) - 1) for k in ([0] * 8, key)]
+        return cases + [_chacha_case(key, 33, M64, "counter wraps"), _chacha_case(key, 17, 0, "explicit zero")]
+    n, blocks = case.n, -(-case.n // 16)
+    ws = chacha_words(case.key, case.ctr, n)
+    ctr = (case.ctr + blocks) & M64
+    tail = [n - 16 * (blocks - 1) if n else 16, ctr & 0xffffffff, ctr >> 32]
+    check_row(case, out, [(0, b"".join(w.to_bytes(4, "little") for w in ws)),
+                          (_sl(5)[0], b"".join(w.to_bytes(4, "little") for w in tail))], [], "chacha words")
+
+
+# ---- fq_random ------------------------------------------------------------------------------------------------------------
+def fq_seed(i):
+    return o.sha3_256(b"conf-fq-%d" % i)
+
+
+def fq_draws(seed, n=8):
+    """[(value, stream words used so far, rejections of this draw)] of n successive o.fq_random draws."""
+    rng = o.ChaChaRng(seed)
+    res, used = [], 0
+    for _ in range(n):
+        v = o.fq_random(rng)
+        res.append((v, rng.words_used, (rng.words_used - used) // 12 - 1))
+        used = rng.words_used
+    return res
+
+
+def _fq_random_path(case):
+    """The wave sees all eight draws of every lane (the op draws eight times whatever aux[0] says)."""
+    m = max(r for _, _, r in cached("fqdraws", case.seed, lambda: fq_draws(case.seed)))
+    return "none" if m == 0 else "one" if m == 1 else "many" if m >= 3 else "two"
+
+
+def _fq_random_case(i, n, tag=""):
+    seed = fq_seed(i)
+    return scase(u32s(int.from_bytes(seed, "little")), [n], "%s seed %d n=%d" % (tag, i, n), seed=seed, n=n)
+
+
+def _fq_random_of(path):
+    def make(rnd):
+        for _ in range(2000):
+            c = _fq_random_case(rnd.randrange(1 << 16), 8, "random")
+            if _fq_random_path(c) == path:
+                return c
+        raise AssertionError("no seed of path %s" % path)
+    return make
+
+
+@spec("FQ_RANDOM", _fq_random_of("none"))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return [_fq_random_case(i, n, "edge") for i, n in enumerate([0, 1, 2, 3, 4, 5, 6, 7, 8, 8, 8, 8])]
+    draws = cached("fqdraws", case.seed, lambda: fq_draws(case.seed))[:case.n]
+    for k, (v, used, _) in enumerate(draws):
+        l = out_limbs(out, k)
+        check_carried(case, l, "fq_random")
+        expect(residue(l) == v, case, "fq_random: draw %d" % k)
+        expect(-P // 4 < value(l) < 5 * P // 4, case, "fq_random: value outside (-p/4, 5p/4)")
+    check_row(case, out, [(_sl(8)[0], b"".join(u.to_bytes(4, "little") for _, u, _ in draws))], [_sl(0, case.n)], "fq_random")
+
+
+fixed_layout("FQ_RANDOM", [_fq_random_of("none")], [_fq_random_of(p) for p in ("none", "one", "many")])
+
+
+# ---- the candidates of G2::random ----------------------------------------------------------------------------------------
+def hash_seed(i):
+    return o.sha3_256(b"conf-hash-%d" % i)
+
+
+def f2_is_square(a):
+    """Euler's criterion on the norm."""
+    n = (a[0] * a[0] + a[1] * a[1]) % P
+    return n == 0 or pow(n, (P - 1) // 2, P) == 1
+
+
+def g2_candidates(seed, upto):
+    """The stream's candidates (x, greatest, x^3 + b a square) until `upto` of them were accepted."""
+    rng = o.ChaChaRng(seed)
+    cands, acc = [], 0
+    while acc < upto:
+        c0 = o.fq_random(rng)
+        c1 = o.fq_random(rng)
+        x = (c0, c1)
+        g = rng.next_u32() % 2 != 0
+        sq = f2_is_square(o.f2_add(o.f2_mul(o.f2_sqr(x), x), o._Fq2.b))
+        cands.append((x, g, sq))
+        acc += sq
+    return cands
+
+
+def seed_class(seed):
+    """Which candidate of the stream (1, 2, ...) is the first accepted one."""
+    return cached("class", seed, lambda: len(g2_candidates(seed, 1)))
+
+
+def seed_classes():
+    """class -> the indices i < 300 of that class, by the bounded search."""
+    def search():
+        found = {}
+        for i in range(300):
+            found.setdefault(seed_class(hash_seed(i)), []).append(i)
+        return found
+    return cached("classes", 0, search)
+
+
+def g2_random_ref(seed, fix, nth=0):
+    """G2::random of the seed's stream -- its (nth + 1)-th accepted candidate, cofactor cleared (fix = 0: by the multiple
+    g2_clear_cofactor(fix = false) applies, the reference of G2_CLEAR_COFACTOR)."""
+    def ref():
+        x, g, _ = [c for c in g2_candidates(seed, nth + 1) if c[2]][nth]
+        return o.E2.mul(o.g2_get_point_from_x(x, g), H2 if fix else CLEAR_NOFIX)
+    return cached("g2random", (seed, int(bool(fix)), nth), ref)
+
+
+def class_seed(rnd, k, pool=4):
+    """A seed index of class k (one of the first `pool` found, so that the references are shared)."""
+    return rnd.choice(seed_classes()[k][:pool])
+
+
+def _seed_words(seed):
+    return u32s(int.from_bytes(seed, "little"))
+
+
+def _g2_random_case(i, fix, forced=0, tag=""):
+    seed = hash_seed(i)
+    return scase(_seed_words(seed), [int(fix), forced], "%s seed %d class %d fix=%d forced=%d" % (tag, i, seed_class(seed), fix, forced),
+                 seed=seed, fix=int(fix), forced=forced)
+
+
+@spec("G2_RANDOM_FROM_SEED", lambda rnd: _any_path("G2_RANDOM_FROM_SEED")(rnd), nflags=2)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        cls = seed_classes()
+        assert all(cls.get(k) for k in range(1, 11)), sorted(cls)
+        cases = [_g2_random_case(cls[k][0], fix, 0, "class") for k in range(1, 11) for fix in (1, 0)]
+        # a second outer round (the host build forces it): the stream is re-read past the candidates already consumed
+        cases += [_g2_random_case(cls[k][0], 1, 1, "second round") for k in (1, 2, 3, 4)]
+        return cases
+    flags_agree(case, flags, 2)
+    expect(flags[1] in (0, case.forced), case, "forced rounds %d" % flags[1])
+    check_result(G2F, case, out, flags, g2_random_ref(case.seed, case.fix, int(flags[1])), "g2_random_from_seed")
+    check_row(case, out, [], [_sl(0, 10)], "g2_random_from_seed")
+
+
+layout("G2_RANDOM_FROM_SEED", lambda c: str(seed_class(c.seed)),
+       lambda rnd, path: _g2_random_case(class_seed(rnd, int(path), 6), rnd.randrange(2), 0, "random"), ("1", "2"))
+
+
+def _g2_random_x2_case(ia, ib, fix, forced=0, tag=""):
+    sa, sb = hash_seed(ia), hash_seed(ib)
+    return scase(_seed_words(sa) + [0] * (NL - 8) + _seed_words(sb), [int(fix), forced],
+                 "%s seeds %d, %d classes (%d, %d) fix=%d forced=%d" % (tag, ia, ib, seed_class(sa), seed_class(sb), fix, forced),
+                 seeds=(sa, sb), fix=int(fix), forced=forced)
+
+
+def _x2_of_classes(ka, kb, tag="random"):
+    return lambda rnd: _g2_random_x2_case(class_seed(rnd, ka), class_seed(rnd, kb), rnd.randrange(2), 0, tag)
+
+
+X2_PAIRS = [(1, 1), (1, 10), (10, 1), (2, 9)]
+
+
+@spec("G2_RANDOM_FROM_SEED_X2", _x2_of_classes(1, 1), nflags=3)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        cls = seed_classes()
+        cases = [_g2_random_x2_case(cls[a][0], cls[b][-1], fix, 0, "pair") for a, b in X2_PAIRS for fix in (1, 0)]
+        cases += [_g2_random_x2_case(cls[a][0], cls[b][0], 1, 1, "second round") for a, b in ((1, 2), (3, 1))]
+        return cases
+    flags_agree(case, flags, 3)
+    expect(flags[2] in (0, case.forced), case, "forced rounds %d" % flags[2])
+    for s, seed in enumerate(case.seeds):
+        want = g2_random_ref(seed, case.fix, int(flags[2]))
+        what = "g2_random_from_seed_x2 slot %d" % s
+        expect(G2F.jac_to_aff(case, out, 6 * s) == want, case, what + ": wrong point")
+        check_bounded(case, out, 6 * s, 6, what + " (Jacobian)")
+        expect(flags[s] == 0, case, what + ": infinity flag")
+        expect((f2_res(out, 12 + 4 * s), f2_res(out, 14 + 4 * s)) == want, case, what + ": wrong affine point")
+        check_bounded(case, out, 12 + 4 * s, 4, what + " (affine)", val_bound=1.25)
+    check_row(case, out, [], [_sl(0, 20)], "g2_random_from_seed_x2")
+
+
+def _x2_table(edges, rnd):
+    """Wave 0: every pair (1, 1) but one, whose slot B needs ten candidates; wave 1: the same with slot A; then the directed
+    pairs interleaved with random pairs of the classes 1, 2, 3, 4, 9, 10."""
+    wave = 32
+    cases = []
+    for at, (a, b) in ((13, (1, 10)), (6, (10, 1))):
+        w = [_x2_of_classes(1, 1, "calm wave")(rnd) for _ in range(wave)]
+        w[at] = _x2_of_classes(a, b, "the one slow slot")(rnd)
+        cases += w
+    pool = list(edges)
+    mixed = (1, 2, 3, 4, 9, 10)
+    n = max(len(cases) + 2 * len(pool), 3 * wave + 5)
+    while len(cases) < n:
+        if pool and (len(cases) % 2 == 0 or len(cases) + len(pool) >= n):
+            cases.append(pool.pop(0))
+        else:
+            cases.append(_x2_of_classes(rnd.choice(mixed), rnd.choice(mixed))(rnd))
+    return cases
+
+
+TABLES["G2_RANDOM_FROM_SEED_X2"] = _x2_table
+
+
+# ---- job_hash_g2, job_hash_g2_x2 ----------------------------------------------------------------------------------------------
+def hash_msg(i):
+    return b"conf-hash-%d" % i
+
+
+LONG_MSGS = [bytes([65 + n % 7]) * n for n in (135, 136, 137, 192, 300)]
+
+
+def _pad(msg):
+    return bytes(msg) + bytes([0xa5]) * 4
+
+
+def _hash_g2_case(msg, fix, tag=""):
+    return bcase([(0, _pad(msg))], [len(msg), int(fix)], "%s len=%d fix=%d" % (tag, len(msg), fix), msg=bytes(msg), fix=int(fix))
+
+
+def hash_g2_ref(msg, fix):
+    return o.g2_uncompressed(g2_random_ref(o.sha3_256(msg), fix))
+
+
+def _rand_hash_msg(rnd):
+    return hash_msg(class_seed(rnd, rnd.choice([1, 1, 2, 3])))
+
+
+@spec("HASH_G2", lambda rnd: _hash_g2_case(_rand_hash_msg(rnd), rnd.randrange(2), "random"))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        cls = seed_classes()
+        cases = [_hash_g2_case(hash_msg(cls[k][0]), 1, "class %d" % k) for k in range(1, 11)]
+        cases += [_hash_g2_case(hash_msg(cls[k][0]), 0, "class %d" % k) for k in (1, 2, 10)]
+        cases += [_hash_g2_case(m, i % 2, "long") for i, m in enumerate(LONG_MSGS)] + [_hash_g2_case(b"", 1, "empty")]
+        return cases
+    check_row(case, out, [(0, hash_g2_ref(case.msg, case.fix))], [], "job_hash_g2")
+
+
+def _hash_g2_x2_case(ma, mb, fix, null_b, tag=""):
+    return bcase([(0, _pad(ma)), (MSG_B2, _pad(mb))], [len(ma), len(mb), int(fix) | (int(null_b) << 1)],
+                 "%s len=(%d, %d) fix=%d null_b=%d" % (tag, len(ma), len(mb), fix, null_b), msgs=(bytes(ma), bytes(mb)), fix=int(fix),
+                 null_b=int(null_b))
+
+
+@spec("HASH_G2_X2", lambda rnd: _hash_g2_x2_case(_rand_hash_msg(rnd), _rand_hash_msg(rnd), rnd.randrange(2), rnd.random() < 0.2, "random"))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        cls = seed_classes()
+        cases = [_hash_g2_x2_case(hash_msg(cls[a][0]), hash_msg(cls[b][-1]), fix, 0, "pair (%d, %d)" % (a, b))
+                 for a, b in X2_PAIRS for fix in (1, 0)]
+        cases += [_hash_g2_x2_case(hash_msg(cls[a][0]), hash_msg(cls[b][0]), 1, 1, "out_b null (%d, %d)" % (a, b)) for a, b in ((1, 10), (10, 1), (2, 2))]
+        cases += [_hash_g2_x2_case(LONG_MSGS[i], LONG_MSGS[j], 1, 0, "long") for i, j in ((0, 1), (2, 0), (3, 4))]
+        cases += [_hash_g2_x2_case(b"", LONG_MSGS[1], 1, 0, "empty beside two blocks")]
+        return cases
+    want = [(0, hash_g2_ref(case.msgs[0], case.fix))]
+    if not case.null_b:
+        want.append((192, hash_g2_ref(case.msgs[1], case.fix)))
+    check_row(case, out, want, [], "job_hash_g2_x2")
+
+
+# ---- hash_g1_g2, xor_with_hash -------------------------------------------------------------------------------------------------
+IDENTITY = {(1, "unc"): o.g1_uncompressed(None), (1, "comp"): o.g1_compressed(None), (2, "unc"): o.g2_uncompressed(None),
+            (2, "comp"): o.g2_compressed(None)}
+SIZE = {(1, "unc"): 96, (1, "comp"): 48, (2, "unc"): 192, (2, "comp"): 96}
+
+
+def byte_ref(g, form, b):
+    """(verdict, point) of an encoding by the oracle: the checked decode of a compressed form; parse + on-curve (no
+    subgroup test, EncodedPoint::into_affine_unchecked + is_on_curve) of an uncompressed one."""
+    def ref():
+        E = o.E1 if g == 1 else o.E2
+        try:
+            if form == "comp":
+                return True, (o.g1_from_compressed if g == 1 else o.g2_from_compressed)(bytes(b))
+            p = (o.g1_from_uncompressed if g == 1 else o.g2_from_uncompressed)(bytes(b), check=False)
+            return (True, p) if p is None or E.on_curve(p) else (False, None)
+        except o.DecodeError:
+            return False, None
+    return cached("byteref", (g, form, bytes(b)), ref)
+
+
+def _g1_operands():
+    """G1 operands of the hash jobs (uncompressed): (kind, bytes); two valid points, the identity, three that do not decode."""
+    def make():
+        rnd = random.Random("g1-operands")
+        p, q = g1_point(rnd), g1_point(rnd, False)  # (the uncompressed decode has no subgroup test: q is accepted)
+        off = bytearray(o.g1_uncompressed(p))
+        off[95] ^= 1
+        flag = bytearray(o.g1_uncompressed(p))
+        flag[0] |= 0x80
+        return [("valid", o.g1_uncompressed(p)), ("valid", o.g1_uncompressed(q)), ("identity", o.g1_uncompressed(None)),
+                ("bad", bytes(off)), ("bad", bytes(flag)), ("bad", bytes([0xff]) * 96)]
+    return cached("g1operands", 0, make)
+
+
+def _g1_operand(rnd, kind):
+    return rnd.choice([b for k, b in _g1_operands() if k == kind])
+
+
+HASH_LENS = [0, 63, 64, 65, 200]
+MSG_POOL = [bytes([33 + (7 * n + i) % 90 for i in range(n)]) for n in HASH_LENS + [1, 32, 136]]
+
+
+def hash_g1_g2_ref(g1, msg, fix):
+    """(status, 192 bytes) of job_hash_g1_g2."""
+    ok, p = byte_ref(1, "unc", g1)
+    if not ok:
+        return 3, (IDENTITY[(2, "unc")] if fix else bytes([0xff]) * 192)
+    m = o.sha3_256(msg) if len(msg) > 64 else bytes(msg)
+    return 0, o.g2_uncompressed(g2_random_ref(o.sha3_256(m + o.g1_compressed(p)), fix))
+
+
+def _hash_g1_g2_case(g1, msg, fix, tag=""):
+    return bcase([(0, g1), (96, _pad(msg))], [len(msg), int(fix)], "%s len=%d fix=%d" % (tag, len(msg), fix), g1=bytes(g1), msg=bytes(msg),
+                 fix=int(fix))
+
+
+def _rand_hash_g1_g2(rnd):
+    kind = rnd.choice(["valid", "valid", "valid", "identity", "bad"])
+    return _hash_g1_g2_case(_g1_operand(rnd, kind), rnd.choice(MSG_POOL), rnd.randrange(2), "random " + kind)
+
+
+@spec("HASH_G1_G2", _rand_hash_g1_g2, nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        ops = _g1_operands()
+        return [_hash_g1_g2_case(ops[i][1], MSG_POOL[j], fix, ops[i][0]) for i in (0, 2, 3) for j in range(len(HASH_LENS)) for fix in (1, 0)] + \
+               [_hash_g1_g2_case(ops[i][1], MSG_POOL[1], fix, ops[i][0]) for i in (1, 4, 5) for fix in (1, 0)]
+    flags_agree(case, flags, 1)
+    st, want = hash_g1_g2_ref(case.g1, case.msg, case.fix)
+    expect(flags[0] == st, case, "job_hash_g1_g2: status %d, want %d" % (flags[0], st))
+    check_row(case, out, [(0, want)], [], "job_hash_g1_g2")
+
+
+def _hash_g1_g2_x2_case(a, b, fix, null_b, tag=""):
+    return bcase([(0, a[0]), (96, b[0]), (MSG_A4, _pad(a[1])), (MSG_B4, _pad(b[1]))], [len(a[1]), len(b[1]), int(fix) | (int(null_b) << 1)],
+                 "%s len=(%d, %d) fix=%d null_b=%d" % (tag, len(a[1]), len(b[1]), fix, null_b), ops=((bytes(a[0]), bytes(a[1])), (bytes(b[0]), bytes(b[1]))),
+                 fix=int(fix), null_b=int(null_b))
+
+
+def _rand_hash_g1_g2_x2(rnd):
+    def operand():
+        return (_g1_operand(rnd, rnd.choice(["valid", "valid", "valid", "identity", "bad"])), rnd.choice(MSG_POOL))
+    return _hash_g1_g2_x2_case(operand(), operand(), rnd.randrange(2), rnd.random() < 0.2, "random")
+
+
+@spec("HASH_G1_G2_X2", _rand_hash_g1_g2_x2, nflags=2)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        ops = _g1_operands()
+        v, idn, bad = ops[0][1], ops[2][1], ops[3][1]
+        m = MSG_POOL
+        cases = []
+        for fix in (1, 0):
+            cases += [_hash_g1_g2_x2_case((v, m[1]), (bad, m[2]), fix, 0, "valid, bad"), _hash_g1_g2_x2_case((bad, m[1]), (v, m[2]), fix, 0, "bad, valid"),
+                      _hash_g1_g2_x2_case((bad, m[3]), (ops[5][1], m[0]), fix, 0, "bad, bad"), _hash_g1_g2_x2_case((idn, m[4]), (v, m[0]), fix, 0, "identity, valid"),
+                      _hash_g1_g2_x2_case((v, m[1]), (v, m[3]), fix, 0, "63 beside 65"), _hash_g1_g2_x2_case((v, m[3]), (v, m[2]), fix, 0, "65 beside 64"),
+                      _hash_g1_g2_x2_case((v, m[2]), (idn, m[4]), fix, 0, "64 beside 200"), _hash_g1_g2_x2_case((bad, m[2]), (v, m[1]), fix, 1, "bad A, out_b null"),
+                      _hash_g1_g2_x2_case((v, m[4]), (bad, m[1]), fix, 1, "bad B, out_b null")]
+        return cases
+    flags_agree(case, flags, 2)
+    want = []
+    for s, (g1, msg) in enumerate(case.ops):
+        st, enc = hash_g1_g2_ref(g1, msg, case.fix)
+        expect(flags[s] == st, case, "job_hash_g1_g2_x2: status %d of slot %d, want %d" % (flags[s], s, st))
+        if s == 0 or not case.null_b:
+            want.append((192 * s, enc))
+    check_row(case, out, want, [], "job_hash_g1_g2_x2")
+
+
+XOR_LENS = [0, 1, 15, 16, 17, 31, 32, 33, 1000]
+
+
+def _xor_case(g1, data, tag=""):
+    return bcase([(0, g1), (96, _pad(data))], [len(data)], "%s len=%d" % (tag, len(data)), g1=bytes(g1), data=bytes(data))
+
+
+def _rand_xor(rnd):
+    kind = rnd.choice(["valid", "valid", "valid", "identity", "bad"])
+    return _xor_case(_g1_operand(rnd, kind), rnd.randbytes(rnd.choice([rnd.randrange(0, 70), rnd.randrange(0, 70), rnd.randrange(70, 300)])), "random " + kind)
+
+
+@spec("XOR_WITH_HASH", _rand_xor, nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        ops = _g1_operands()
+        cases = [_xor_case(ops[i % 3][1], rnd.randbytes(n), ops[i % 3][0]) for i, n in enumerate(XOR_LENS)]
+        cases += [_xor_case(b, rnd.randbytes(n), k) for (k, b), n in zip(ops[3:], (17, 1000, 0))]
+        cases += [_xor_case(ops[0][1], bytes(33), "zero data"), _xor_case(ops[0][1], bytes([0xff]) * 64, "ff data")]
+        return cases
+    flags_agree(case, flags, 1)
+    ok, p = byte_ref(1, "unc", case.g1)
+    expect(flags[0] == (0 if ok else 3), case, "job_xor_with_hash: status %d" % flags[0])
+    check_row(case, out, [(0, o.xor_with_hash(p, case.data))] if ok else [], [], "job_xor_with_hash")
+
+
+# ---- field codecs -----------------------------------------------------------------------------------------------------------
+BE_VALUES = [0, 1, P - 1, P, P + 1, (1 << 381) - 1]
+
+
+def _be48(v, top=0):
+    return (v | (top << 381)).to_bytes(48, "big")
+
+
+def _check_from_be(case, out, s, raw, what):
+    l = out_limbs(out, s)
+    check_product(case, l, raw * (RM * RM % P), what)
+    expect(residue(l) == raw, case, what + ": residue")
+
+
+def _from_be48_case(v, top, mask, tag=""):
+    return bcase([(0, _be48(v, top))], [int(mask)], "%s v=%x top=%d mask=%d" % (tag, v, top, mask), v=v, top=top, mask=int(mask))
+
+
+@spec("FQ_FROM_BE48", lambda rnd: _from_be48_case(rnd.randrange(P), rnd.choice([0, 0, rnd.randrange(8)]), rnd.randrange(2), "random"), nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return [_from_be48_case(v, top, mask, "edge") for v in BE_VALUES for top in range(8) for mask in (0, 1)]
+    raw = case.v if case.mask else case.v | (case.top << 381)
+    flags_agree(case, flags, 1)
+    expect(flags[0] == int(raw < P), case, "fq_from_be48: verdict %d" % flags[0])
+    if raw < P:
+        _check_from_be(case, out, 0, raw, "fq_from_be48")
+    check_row(case, out, [], [_sl(0)], "fq_from_be48")
+
+
+def _lazy_fq(rnd, v):
+    """A lazy in-contract representation, as FQ_TO_CANONICAL takes them."""
+    return rnd.choice([lambda: encode(v), lambda: encode(v, rnd.randint(0, 13), PT_IV, rnd.choice(PUSHES)),
+                       lambda: encode(v, rnd.randint(-299, 299), (-7.9, 7.9), rnd.choice(PUSHES))])()
+
+
+@spec("FQ_TO_BE48", lambda rnd: Case([_lazy_fq(rnd, rnd.randrange(P))], tag="random"))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return [Case([_lazy_fq(rnd, v)], tag="edge %x" % v) for v in (0, 1, P - 1, HALF, HALF + 1, (1 << 380), 255, 256 << 376) for _ in range(3)] + \
+               [Case([encode_int(P)], tag="p"), Case([encode(0, -300, (-7.9, 7.9))], tag="-300 p")]
+    check_row(case, out, [(0, residue(case.slots[0].limbs).to_bytes(48, "big"))], [], "fq_to_be48")
+
+
+LEX_VALUES = [0, HALF, HALF + 1, P - 1, 1, HALF - 1]
+
+
+@spec("FQ_LEX_LARGEST", lambda rnd: Case([_lazy_fq(rnd, rnd.randrange(P))], tag="random"), nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        return [Case([_lazy_fq(rnd, v)], tag="edge %x" % v) for v in LEX_VALUES for _ in range(3)] + [Case([encode_int(P)], tag="p")]
+    flags_agree(case, flags, 1)
+    v = residue(case.slots[0].limbs)
+    expect(flags[0] == int(v > HALF), case, "fq_lex_largest(%x) = %d" % (v, flags[0]))
+    check_row(case, out, [], [], "fq_lex_largest")
+
+
+def _from_be96_case(c1, c0, top1, top0, mask, tag=""):
+    return bcase([(0, _be48(c1, top1) + _be48(c0, top0))], [int(mask)], "%s c1=%x top %d c0=%x top %d mask=%d" % (tag, c1, top1, c0, top0, mask),
+                 c=(c0, c1), tops=(top0, top1), mask=int(mask))
+
+
+def _rand_from_be96(rnd):
+    return _from_be96_case(rnd.randrange(P), rnd.randrange(P), rnd.choice([0, 0, rnd.randrange(8)]), rnd.choice([0, 0, 0, rnd.randrange(8)]), rnd.randrange(2),
+                           "random")
+
+
+@spec("FQ2_FROM_BE96", _rand_from_be96, nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        good = rnd.randrange(P)
+        cases = [_from_be96_case(v, good, top, 0, mask, "c1") for v in BE_VALUES for top in (0, 5) for mask in (0, 1)]
+        cases += [_from_be96_case(good, v, 0, 0, mask, "c0") for v in BE_VALUES for mask in (0, 1)]
+        cases += [_from_be96_case(good, 1, top1, top0, 1, "flag bits in c0") for top0 in (1, 2, 4, 7) for top1 in (0, 7)]
+        cases += [_from_be96_case(P, P, 0, 0, 1, "both out of range"), _from_be96_case(P - 1, P - 1, 7, 0, 1, "both q - 1")]
+        return cases
+    (c0, c1), (top0, top1) = case.c, case.tops
+    raw1 = c1 if case.mask else c1 | (top1 << 381)
+    raw0 = c0 | (top0 << 381)  # (the mask applies to c1, the half that carries the flags, only)
+    ok = raw0 < P and raw1 < P
+    flags_agree(case, flags, 1)
+    expect(flags[0] == int(ok), case, "fq2_from_be96: verdict %d" % flags[0])
+    if ok:
+        _check_from_be(case, out, 0, raw0, "fq2_from_be96 c0")
+        _check_from_be(case, out, 1, raw1, "fq2_from_be96 c1")
+    check_row(case, out, [], [_sl(0, 2)], "fq2_from_be96")
+
+
+def _lazy_fq2(rnd, v):
+    return [_lazy_fq(rnd, v[0]), _lazy_fq(rnd, v[1])]
+
+
+@spec("FQ2_TO_BE96", lambda rnd: Case(_lazy_fq2(rnd, (rnd.randrange(P), rnd.randrange(P))), tag="random"))
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        vs = [(a, b) for a in (0, 1, P - 1, HALF + 1) for b in (0, 1, P - 1, 1 << 380)]
+        return [Case(_lazy_fq2(rnd, v), tag="edge %x, %x" % v) for v in vs] + [Case([encode_int(P), encode(0, -300, (-7.9, 7.9))], tag="p, -300 p")]
+    c0, c1 = f2_in(case, 0)
+    check_row(case, out, [(0, c1.to_bytes(48, "big") + c0.to_bytes(48, "big"))], [], "fq2_to_be96")
+
+
+@spec("FQ2_LEX_LARGEST", lambda rnd: Case(_lazy_fq2(rnd, (rnd.randrange(P), rnd.choice([0, rnd.randrange(P)]))), tag="random"), nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        cases = [Case(_lazy_fq2(rnd, (v, 0)), tag="c1 = 0, c0 = %x" % v) for v in LEX_VALUES for _ in range(2)]
+        cases += [Case([_lazy_fq(rnd, v), encode_int(P)], tag="c1 = p, c0 = %x" % v) for v in (HALF, HALF + 1)]
+        cases += [Case(_lazy_fq2(rnd, (v, w)), tag="c1 = %x, c0 = %x" % (w, v)) for w in (HALF, HALF + 1, 1, P - 1) for v in (0, P - 1, HALF + 1)]
+        return cases
+    flags_agree(case, flags, 1)
+    c0, c1 = f2_in(case, 0)
+    expect(flags[0] == int(c1 > HALF if c1 else c0 > HALF), case, "fq2_lex_largest = %d" % flags[0])
+    check_row(case, out, [], [], "fq2_lex_largest")
+
+
+# ---- point encodings: one shared table of byte strings per group and form ------------------------------------------------------
+KINDS = ("valid", "identity", "bad flags", "x out of range", "non-square", "outside subgroup")
+
+
+def _enc_x(g, x, form, y=None):
+    """The bytes of a finite point's coordinates, flags not yet set (compressed: x alone)."""
+    fe = (lambda v: v.to_bytes(48, "big")) if g == 1 else (lambda v: v[1].to_bytes(48, "big") + v[0].to_bytes(48, "big"))
+    return fe(x) + (fe(y) if form == "unc" else b"")
+
+
+def _set_top(b, top):
+    b = bytearray(b)
+    b[0] = (b[0] & 0x1f) | (top << 5)
+    return bytes(b)
+
+
+def _or_byte(b, k, v):
+    b = bytearray(b)
+    b[k] |= v
+    return bytes(b)
+
+
+def _non_square_x(g, rnd):
+    while True:
+        x = rnd.randrange(P) if g == 1 else (rnd.randrange(P), rnd.randrange(P))
+        if g == 1 and pow((x ** 3 + 4) % P, (P - 1) // 2, P) == P - 1:
+            return x
+        if g == 2 and not f2_is_square(o.f2_add(o.f2_mul(o.f2_sqr(x), x), o._Fq2.b)):
+            return x
+
+
+def byte_cases(g, form):
+    """The shared table of encodings of group g in form "unc" / "comp": [(tag, kind, bytes)], kind one of KINDS or None.
+    The expected verdict of each is byte_ref's, that is the oracle's."""
+    def make():
+        rnd = random.Random("byte-cases-%d-%s" % (g, form))
+        fld, E = (G1F, o.E1) if g == 1 else (G2F, o.E2)
+        F = fld.F
+        n = SIZE[(g, form)]
+        flag = 0x80 if form == "comp" else 0
+        enc = (o.g1_uncompressed, o.g1_compressed, o.g2_uncompressed, o.g2_compressed)[2 * (g - 1) + (form == "comp")]
+        p = _pt(fld, rnd)
+        q = _pt(fld, rnd, False)
+        valid, ident = enc(p), IDENTITY[(g, form)]
+        cs = []
+        for top in range(8):  # all eight values of the top three bits
+            want_top = (valid[0] >> 5)
+            cs.append(("top bits %d on a valid payload" % top, "valid" if top == want_top else "bad flags" if form == "unc" or not top & 4 else None,
+                       _set_top(valid, top)))
+            cs.append(("top bits %d on a zero payload" % top, "identity" if top == ident[0] >> 5 else None, _set_top(bytes(n), top)))
+        strays = [(0, 0x01), (0, 0x10), (n - 1, 0x01), (n // 2 - 5, 0x40)]
+        if g == 2:
+            strays += [(50, 0x02), (95, 0x80)]  # the half of the first 96 bytes that the other lane of the pair owns
+        if form == "unc":
+            strays += [(n // 2 + 3, 0x04), (n // 2, 0x20)]  # the y half
+        cs += [("identity with a stray bit %02x in byte %d" % (v, k), "bad flags" if k == 0 else None, _or_byte(ident, k, v)) for k, v in strays]
+        if form == "comp":
+            cs.append(("identity with the sort bit", "bad flags", _or_byte(ident, 0, 0x20)))
+        y = p[1]
+        for v in (P, P + 1, (1 << 381) - 1):  # x out of range (G2: c1 alone, c0 alone, both)
+            xs = [("x", v)] if g == 1 else [("x.c1", (p[0][0], v)), ("x.c0", (v, p[0][1])), ("x.c0 and x.c1", (v, v))]
+            cs += [("%s = %x" % (t, v), "x out of range", _or_byte(_enc_x(g, x, form, y), 0, flag)) for t, x in xs]
+        if form == "unc":
+            ys = [("y", y + P)] if g == 1 else [("y.c1", (y[0], y[1] + P)), ("y.c0", (y[0] + P, y[1]))]
+            cs += [("%s + q" % t, None, _enc_x(g, p[0], form, yy)) for t, yy in ys if max(yy if g == 2 else [yy]) < 1 << 384]
+            cs.append(("(x, -y)", "valid", enc(E.neg(p))))
+            cs.append(("off the curve", None, _enc_x(g, p[0], form, F.add(y, F.one))))
+            cs.append(("on the curve, outside the subgroup", "outside subgroup", enc(q)))
+            if g == 1:
+                cs.append(("x = 0: (0, 2)", None, enc((0, 2))))
+            else:
+                y0 = o.f2_sqrt(o._Fq2.b)
+                cs.append(("x = 0", None, _enc_x(g, (0, 0), form, y0 if y0 is not None else (2, 0))))
+            cs.append(("flag bits in y's top byte", None, _or_byte(valid, n // 2, 0x80)))
+        else:
+            cs.append(("non-square right-hand side", "non-square", _or_byte(_enc_x(g, _non_square_x(g, rnd), form), 0, 0x80)))
+            cs.append(("non-square right-hand side, sort bit", "non-square", _or_byte(_enc_x(g, _non_square_x(g, rnd), form), 0, 0xa0)))
+            cs.append(("outside the subgroup", "outside subgroup", enc(q)))
+            cs.append(("the other sort bit", "valid", _or_byte(valid, 0, 0x20) if not valid[0] & 0x20 else _set_top(valid, 4)))
+            cs.append(("x = 0", None, _or_byte(bytes(n), 0, 0x80)))
+            cs.append(("x = 0, sort bit", None, _or_byte(bytes(n), 0, 0xa0)))
+            if g == 1:
+                cs.append(("x = 0 of (0, 2): outside G1", None, o.g1_compressed((0, 2))))
+        for tag, kind, b in cs:
+            assert len(b) == n, tag
+            if kind in ("valid", "identity"):
+                assert byte_ref(g, form, b)[0], tag
+            elif kind is not None and not (kind == "outside subgroup" and form == "unc"):
+                assert not byte_ref(g, form, b)[0], tag
+        return cs
+    return cached("bytecases", (g, form), make)
+
+
+def _decode_spec(op, g, form):
+    fld = G1F if g == 1 else G2F
+    w = fld.w
+    other = "comp" if form == "unc" else "unc"
+    enc_other = (o.g1_uncompressed, o.g1_compressed, o.g2_uncompressed, o.g2_compressed)[2 * (g - 1) + (other == "comp")]
+    enc_same = (o.g1_uncompressed, o.g1_compressed, o.g2_uncompressed, o.g2_compressed)[2 * (g - 1) + (form == "comp")]
+
+    def rand_case(rnd):
+        p = _pt(fld, rnd)
+        b = enc_same(p if rnd.random() < 0.5 else fld.E.neg(p))
+        return bcase([(0, b)], [], "random valid", b=b)
+
+    def fn(case=None, out=None, flags=None, rnd=None):
+        if rnd is not None:
+            return [bcase([(0, b)], [], tag, b=b) for tag, _, b in byte_cases(g, form)]
+        ok, p = byte_ref(g, form, case.b)
+        what = op.lower()
+        flags_agree(case, flags, 3)
+        expect(flags[0] == int(ok), case, "%s: verdict %d, the oracle's %d" % (what, flags[0], ok))
+        if ok:
+            expect(flags[1] == int(p is None), case, "%s: infinity flag %d" % (what, flags[1]))
+            if p is not None:
+                expect((fld.res(out, 0), fld.res(out, w)) == p, case, what + ": wrong point")
+                check_bounded(case, out, 0, 2 * w, what, limb=LIMB_MAX)
+        expect(flags[2] == (0 if ok else 3), case, "%s wrapper: status %d" % (what, flags[2]))
+        check_row(case, out, [(WRAP, enc_other(p) if ok else IDENTITY[(g, other)])], [_sl(0, 2 * w)], what + " wrapper")
+    spec(op, rand_case, nflags=3)(fn)
+
+
+_decode_spec("G1_DECODE_UNCOMPRESSED", 1, "unc")
+_decode_spec("G1_DECODE_COMPRESSED", 1, "comp")
+_decode_spec("G2_DECODE_UNCOMPRESSED", 2, "unc")
+_decode_spec("G2_DECODE_COMPRESSED", 2, "comp")
+
+
+def kind_encoding(kind, which=0):
+    """An encoding of the shared compressed G2 table of that kind."""
+    return [b for _, k, b in byte_cases(2, "comp") if k == kind][which]
+
+
+def _decode_x2_case(a, b, null_b, tag=""):
+    return bcase([(0, a), (96, b)], [int(null_b)], "%s null_b=%d" % (tag, null_b), encs=(bytes(a), bytes(b)), null_b=int(null_b))
+
+
+def _rand_decode_x2(rnd):
+    def one():
+        p = g2_point(rnd)
+        return o.g2_compressed(p if rnd.random() < 0.5 else o.E2.neg(p))
+    return _decode_x2_case(one(), one(), rnd.random() < 0.15, "random valid")
+
+
+@spec("G2_DECODE_COMPRESSED_X2", _rand_decode_x2, nflags=4)
+def _(case=None, out=None, flags=None, rnd=None):
+    if rnd is not None:
+        cases = [_decode_x2_case(kind_encoding(ka), kind_encoding(kb, -1), 0, "%s, %s" % (ka, kb)) for ka in KINDS for kb in KINDS]
+        cases += [_decode_x2_case(kind_encoding(ka), kind_encoding("valid"), 1, "%s, out_b null" % ka) for ka in KINDS]
+        # the identity with a stray bit (either lane's half), in each slot beside a valid point
+        tbl = [(tag, b) for tag, _, b in byte_cases(2, "comp") if tag.startswith("identity with")]
+        cases += [_decode_x2_case(b, kind_encoding("valid"), 0, tag + " in slot A") if i % 2 else _decode_x2_case(kind_encoding("valid"), b, 0, tag + " in slot B")
+                  for i, (tag, b) in enumerate(tbl)]
+        return cases
+    flags_agree(case, flags, 4)
+    want = []
+    for s, b in enumerate(case.encs):
+        ok, p = byte_ref(2, "comp", b)
+        what = "g2_decode_compressed_x2 slot %d" % s
+        expect(flags[s] & 1 == int(ok), case, "%s: verdict %d, the oracle's %d" % (what, flags[s] & 1, ok))
+        expect(flags[s] >> 1 == int(p is None), case, "%s: infinity flag (a failed decode leaves the identity)" % what)
+        if p is not None:
+            expect((f2_res(out, 4 * s), f2_res(out, 4 * s + 2)) == p, case, what + ": wrong point")
+            check_bounded(case, out, 4 * s, 4, what, limb=LIMB_MAX)
+        expect(flags[2 + s] == (0 if ok else 3), case, "%s wrapper: status %d" % (what, flags[2 + s]))
+        if s == 0 or not case.null_b:
+            want.append((WRAP + 192 * s, o.g2_uncompressed(p)))
+    check_row(case, out, want, [_sl(0, 8)], "job_decompress_g2_x2")
+
+
+def _encode_spec(op, g, form):
+    fld = G1F if g == 1 else G2F
+    enc = (o.g1_uncompressed, o.g1_compressed, o.g2_uncompressed, o.g2_compressed)[2 * (g - 1) + (form == "comp")]
+
+    def make(rnd, p, tag, canon=False):
+        return mcase(aff_slots(fld, rnd, p, canon), aux=[int(p is None)], tag=tag, p=p)
+
+    def rand_case(rnd):
+        return make(rnd, _pt(fld, rnd, rnd.random() < 0.8), "random", rnd.random() < 0.3)
+
+    def fn(case=None, out=None, flags=None, rnd=None):
+        if rnd is not None:
+            F = fld.F
+            pts = whole_curve_points(fld, rnd)
+            pts += [fld.E.neg(p) for p in pts[1:4]]
+            cases = [make(rnd, p, "point %d" % i, i % 2 == 0) for i, p in enumerate(pts)]
+            # y at the turn of the lexicographic order (not curve points: the encoders do not look)
+            ys = [HALF, HALF + 1, 0, P - 1] if g == 1 else [(0, HALF), (0, HALF + 1), (HALF, 0), (HALF + 1, 0), (P - 1, HALF), (0, 0), (5, HALF + 1)]
+            x = pts[1][0]
+            cases += [make(rnd, (x, y), "y = %s" % (y,), i % 2 == 0) for i, y in enumerate(ys)]
+            cases += [make(rnd, (F.zero, pts[1][1]), "x = 0"), make(rnd, (fld.F.sub(F.zero, F.one), pts[1][1]), "x = q - 1")]
+            return cases
+        check_row(case, out, [(0, enc(case.p))], [], op.lower())
+    spec(op, rand_case)(fn)
+
+
+_encode_spec("G1_ENCODE_UNCOMPRESSED", 1, "unc")
+_encode_spec("G1_ENCODE_COMPRESSED", 1, "comp")
+_encode_spec("G2_ENCODE_UNCOMPRESSED", 2, "unc")
+_encode_spec("G2_ENCODE_COMPRESSED", 2, "comp")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # tables and sizes
 # ---------------------------------------------------------------------------------------------------------------------
 def table(op, seed=1):
@@ -3521,6 +4378,8 @@ def table(op, seed=1):
     fn, rand_case, _ = SPECS[op]
     rnd = random.Random("%s-%d" % (op, seed))
     edges = fn(rnd=rnd)
+    if op in TABLES:
+        return TABLES[op](edges, rnd)
     if op in LAYOUTS:
         return _wave_layout(op, edges, rnd)
     wave = 64 // lanes(op)

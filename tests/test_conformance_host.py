@@ -148,7 +148,7 @@ def test_point_multiplication_models_agree_with_the_oracle():
 def test_point_multiplication_tables_hold_every_path():
     """Every op of the point-multiplication block with a per-wave decision: the Python model finds cases of every path it
     knows among the DIRECTED cases or the table, and the block's tables hold the edges the routines turn on."""
-    new = [op for op in dc.LAYOUTS if dc.OPS[op] >= dc.OPS["G1_ADD_AFFINE"]]
+    new = [op for op in dc.LAYOUTS if dc.OPS["G1_ADD_AFFINE"] <= dc.OPS[op] < dc.BYTE_OPS_FROM]
     assert len(new) == 13
     for op in new:
         path_of, makers = dc.LAYOUTS[op]
@@ -157,7 +157,7 @@ def test_point_multiplication_tables_hold_every_path():
         for c in cases:
             seen[path_of(c)] = seen.get(path_of(c), 0) + 1
         assert set(seen) == set(makers) and min(seen.values()) >= 64 // dc.lanes(op), (op, seen)
-    assert set(dc.NEEDS_TABLE) <= set(dc.OPS) and all(dc.lanes(op) == (1 if op.startswith("G1") else 2) for op in dc.OPS if dc.OPS[op] >= 140)
+    assert set(dc.NEEDS_TABLE) <= set(dc.OPS) and all(dc.lanes(op) == (1 if op.startswith("G1") else 2) for op in dc.OPS if 140 <= dc.OPS[op] < dc.BYTE_OPS_FROM)
     # combine_divide: D = 1, every 2^a (a = 1 .. 16), 2^17, odd, >= 2^32, near 2^62, each with both signs, and Q = O
     for op in ("G1_COMBINE_DIVIDE", "G1_COMBINE_DIVIDE_ARENA", "G2_COMBINE_DIVIDE"):
         ds = {(c.d, c.neg) for c in dc.table(op)}

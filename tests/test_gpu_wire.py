@@ -649,3 +649,71 @@ def test_in_place_device_calls_keep_the_tests_in_front(engine, rnd):
     engine._call("tc_verify_g2_batch", _ptr(d_pk), 0, _ptr(d_sig), _ptr(d_h), B, _ptr(d_sig))          # ok == sig
     engine.sync()
     assert (d_sig.reshape(-1)[:B].cpu().numpy() == want).all()
+
+
+def test_shared_table_of_encodings_through_the_entry_points(engine, rnd):
+    """The shared table of encodings of the device conformance suite (device_conformance.byte_cases: every value of the top
+    three bits, the identity with a stray bit in either lane's half, x = q, q + 1, 2^381 - 1 in c1 alone and in c0 alone, a
+    non-canonical y, a point off the curve, outside the subgroup, x = 0, both sort bits) through the public entry points:
+    g1 / g2_decompress (the latter in both forms, forced as above, at an odd and at an even count, so a bad encoding sits in
+    either slot of a pair and in a last pair whose second slot is absent), g1 / g2_compress, and the wire-level G2 combiner
+    with one malformed share among the t + 1 taken.  Status and bytes equal Oracle A's for every entry."""
+    import device_conformance as dc
+    from conftest import engine_with_env
+    enc = {(1, "unc"): o.g1_uncompressed, (1, "comp"): o.g1_compressed, (2, "unc"): o.g2_uncompressed, (2, "comp"): o.g2_compressed}
+
+    def want(g, form, rows):
+        other = "unc" if form == "comp" else "comp"
+        refs = [dc.byte_ref(g, form, bytes(b)) for b in rows]
+        return [0 if ok else 3 for ok, _ in refs], [enc[(g, other)](p) if ok else dc.IDENTITY[(g, other)] for ok, p in refs]
+
+    def rows_of(g, form, extra):
+        tbl = [b for _, _, b in dc.byte_cases(g, form)]
+        valid = [b for _, k, b in dc.byte_cases(g, form) if k == "valid"]
+        rows = tbl + [valid[0]] * extra
+        return np.frombuffer(b"".join(rows), np.uint8).reshape(len(rows), dc.SIZE[(g, form)]).copy()
+
+    def check(fn, g, form, rows):
+        out, st = fn(rows)
+        wst, wout = want(g, form, rows)
+        assert st.tolist() == wst, [i for i in range(len(rows)) if int(st[i]) != wst[i]]
+        for i in range(len(rows)):
+            assert bytes(out[i]) == wout[i], (g, form, i)
+
+    check(engine.g1_decompress, 1, "comp", rows_of(1, "comp", 0))
+    check(engine.g1_compress, 1, "unc", rows_of(1, "unc", 0))
+    check(engine.g2_compress, 2, "unc", rows_of(2, "unc", 0))
+    n2 = len(dc.byte_cases(2, "comp"))
+    for form, minimum in (("two", 1), ("one", 10 ** 12)):
+        with engine_with_env(TC_DUO_MIN=minimum) as eng:
+            assert eng.tuning()["duo_min_decode"] == minimum
+            for extra in (0, 1):  # an even and an odd count
+                rows = rows_of(2, "comp", extra)
+                assert len(rows) == n2 + extra and (n2 + extra) % 2 == extra ^ (n2 % 2)
+                check(eng.g2_decompress, 2, "comp", rows)
+                shifted = np.concatenate([rows[-1:], rows[:-1]])  # every entry in the other slot of its pair
+                check(eng.g2_decompress, 2, "comp", shifted)
+    # the wire-level combiner: job j takes entry j of the table as share j % (t + 1) of its t + 1, the others valid
+    t, n = 2, 3
+    tbl = dc.byte_cases(2, "comp")
+    B = len(tbl)
+    poly = [rnd.randrange(o.R) for _ in range(t + 1)]
+    H = o.E2.mul(o.G2_GEN, rnd.randrange(1, o.R))
+    idx = np.tile(np.arange(n, dtype=np.uint64), (B, 1))
+    good = [u8(o.g2_compressed(o.E2.mul(H, o.poly_evaluate(poly, k + 1)))) for k in range(n)]
+    sh = np.stack([np.stack(good)] * B)
+    for j, (_, _, b) in enumerate(tbl):
+        sh[j, j % n] = u8(b)
+    out, st = engine.combine_signatures_wire(t, idx, sh)
+    malformed = 0
+    for j, (tag, _, b) in enumerate(tbl):
+        ok, p = dc.byte_ref(2, "comp", b)
+        malformed += not ok
+        assert int(st[j]) == (0 if ok else 3), (j, tag)
+        if ok:
+            pts = [o.g2_from_compressed(bytes(sh[j, k])) for k in range(n)]
+            expect = o.g2_compressed(o.interpolate(o.E2, t, list(zip(range(n), pts))))
+        else:
+            expect = dc.IDENTITY[(2, "comp")]
+        assert bytes(out[j]) == expect, (j, tag)
+    assert malformed >= 25
