@@ -155,6 +155,130 @@ __global__ __launch_bounds__(kGroupBlock) void k_combine_scatter(const uint8_t* 
   }
 }
 
+// ---- grouping the G2 jobs by index tuple (tc_jobs.h combine_tuple_key) --------------------------------
+// Three kernels, no host decision in between (the mode is chosen on the device):
+//   k_combine_keys    per job: its key into the open-addressing table (64-bit atomicCAS, probing bounded by the table
+//                     size), its group = the table entry, its rank inside the group (one atomic per distinct key and
+//                     wave); and, for the fallback, its denominator class and its rank inside the class
+//   k_combine_plan    one workgroup: subset mode or class mode (tc_jobs.h combine_subset_mode), the first slot of every group
+//   k_combine_place   perm[start[group] + rank] = job
+// Workspace words (ws): keys, counts, starts of the table entries, then kGwsMisc; zeroed by the launcher for every call.
+constexpr uint32_t kGwsCount = 2 * kSubsetSlots, kGwsStart = 3 * kSubsetSlots, kGwsMisc = 4 * kSubsetSlots;
+constexpr uint32_t kGwsClassCount = kGwsMisc, kGwsClassStart = kGwsMisc + 4, kGwsGroups = kGwsMisc + 8, kGwsOverflow = kGwsMisc + 9,
+                   kGwsMode = kGwsMisc + 10, kGwsZeroWords = kGwsMisc + 16;
+struct GroupWs {
+  uint32_t* ws;     // kGwsZeroWords words, zeroed
+  uint32_t* rank;   // B: rank inside the tuple's group
+  uint32_t* crank;  // B: rank inside the class
+  uint16_t* grp;    // B: table entry of the job's key
+  uint8_t* cls;     // B: kCombineClass*
+};
+TC_D GroupWs group_ws(uint32_t* ws, size_t B) {
+  GroupWs g;
+  g.ws = ws;
+  g.rank = ws + kGwsZeroWords;
+  g.crank = g.rank + B;
+  g.grp = reinterpret_cast<uint16_t*>(g.crank + B);
+  g.cls = reinterpret_cast<uint8_t*>(g.crank + B + (B + 1) / 2);
+  return g;
+}
+__global__ __launch_bounds__(kGroupBlock) void k_combine_keys(const uint64_t* __restrict__ idx, size_t n_per_job, size_t t, size_t B,
+                                                          uint32_t* __restrict__ ws_words) {
+  __shared__ uint32_t wave_count[kGroupBlock / 64][kCombineClasses];
+  __shared__ uint32_t wg_base[kCombineClasses];
+  const GroupWs g = group_ws(ws_words, B);
+  const size_t j = (size_t)blockIdx.x * kGroupBlock + threadIdx.x;
+  const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool live = j < B;
+  int c = -1;
+  const uint64_t key = live ? combine_tuple_key(idx + j * n_per_job, (int)t, &c) : 0;
+  if (!live) c = -1;
+  // the class and the rank inside it: one atomic per workgroup and class (as k_combine_classify / k_combine_scatter)
+  uint64_t mine = 0;
+  for (int k = 0; k < kCombineClasses; k++) {
+    const uint64_t m = __builtin_amdgcn_ballot_w64(c == k);
+    if (lane == 0) wave_count[wave][k] = (uint32_t)__builtin_popcountll(m);
+    if (c == k) mine = m;
+  }
+  __syncthreads();
+  if (threadIdx.x < kCombineClasses) {
+    uint32_t total = 0;
+    for (int w = 0; w < kGroupBlock / 64; w++) total += wave_count[w][threadIdx.x];
+    wg_base[threadIdx.x] = total ? atomicAdd(&g.ws[kGwsClassCount + threadIdx.x], total) : 0;
+  }
+  __syncthreads();
+  if (live) {
+    uint32_t pos = wg_base[c];
+    for (unsigned w = 0; w < wave; w++) pos += wave_count[w][c];
+    g.cls[j] = (uint8_t)c;
+    g.crank[j] = pos + (uint32_t)__builtin_popcountll(mine & ((1ull << lane) - 1ull));
+  }
+  // the key's table entry
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(g.ws);
+  uint32_t h = 0;
+  bool found = false;
+  if (live && __hip_atomic_load(&g.ws[kGwsOverflow], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
+    h = combine_key_hash(key) & (kSubsetSlots - 1);
+    for (uint32_t probe = 0; probe < kSubsetSlots && !found; probe++) {
+      unsigned long long cur = __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (cur == 0) {
+        cur = atomicCAS(&keys[h], 0ull, (unsigned long long)key);
+        if (cur == 0) {  // a new group
+          cur = key;
+          if (atomicAdd(&g.ws[kGwsGroups], 1u) >= kSubsetMaxGroups) atomicExch(&g.ws[kGwsOverflow], 1u);
+        }
+      }
+      if (cur == key) found = true;
+      else h = (h + 1) & (kSubsetSlots - 1);
+    }
+    if (!found) atomicExch(&g.ws[kGwsOverflow], 1u);  // the table is full
+  }
+  // rank inside the group: the lanes of the wave that hold one key share one atomic
+  uint32_t rank = 0;
+  uint64_t todo = __builtin_amdgcn_ballot_w64(found);
+  while (todo) {
+    const int leader = __builtin_ctzll(todo);
+    const uint32_t hl = (uint32_t)__builtin_amdgcn_readlane((int)h, leader);
+    const bool same = found && h == hl;
+    const uint64_t m = __builtin_amdgcn_ballot_w64(same);
+    uint32_t base = 0;
+    if ((int)lane == leader) base = atomicAdd(&g.ws[kGwsCount + hl], (uint32_t)__builtin_popcountll(m));
+    base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
+    if (same) rank = base + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+    todo &= ~m;
+  }
+  if (found) {
+    g.grp[j] = (uint16_t)h;
+    g.rank[j] = rank;
+  }
+}
+__global__ __launch_bounds__(kSubsetSlots) void k_combine_plan(size_t t, size_t B, uint32_t* __restrict__ ws_words) {
+  __shared__ uint32_t count[kSubsetSlots];
+  __shared__ uint8_t order[kSubsetSlots];
+  __shared__ uint32_t ccount[kCombineClasses];
+  __shared__ uint8_t corder[kCombineClasses];
+  const uint32_t s = threadIdx.x;
+  const unsigned long long key = reinterpret_cast<const unsigned long long*>(ws_words)[s];
+  count[s] = ws_words[kGwsCount + s];
+  order[s] = key ? (uint8_t)combine_key_order(key, (int)t) : (uint8_t)(kGroupOrders - 1);
+  if (s < kCombineClasses) {
+    ccount[s] = ws_words[kGwsClassCount + s];
+    corder[s] = (uint8_t)combine_class_order((int)s);
+  }
+  __syncthreads();
+  const bool subset = combine_subset_mode(ws_words[kGwsOverflow] != 0, ws_words[kGwsGroups], B);
+  ws_words[kGwsStart + s] = subset ? combine_group_start(count, order, kSubsetSlots, s, kSubsetPad) : 0;
+  if (s < kCombineClasses) ws_words[kGwsClassStart + s] = combine_group_start(ccount, corder, kCombineClasses, s, kClassPad);
+  if (s == 0) ws_words[kGwsMode] = subset ? 1u : 0u;
+}
+__global__ __launch_bounds__(kGroupBlock) void k_combine_place(size_t B, uint32_t* __restrict__ ws_words, size_t slots, uint32_t* __restrict__ perm) {
+  const GroupWs g = group_ws(ws_words, B);
+  const size_t j = (size_t)blockIdx.x * kGroupBlock + threadIdx.x;
+  if (j >= B) return;
+  const size_t pos = g.ws[kGwsMode] ? (size_t)g.ws[kGwsStart + g.grp[j]] + g.rank[j] : (size_t)g.ws[kGwsClassStart + g.cls[j]] + g.crank[j];
+  if (pos < slots) perm[pos] = (uint32_t)j;  // (always: the launcher sizes perm for the largest padding either mode can need)
+}
+
 template <class F, class IO, bool ARENA = false>
 TC_D bool combine_fast(size_t t, const uint64_t* idx, bool live, IO& io, uint8_t* st) {
   if (t == 1) return job_combine_small_io<F, 2, IO, ARENA>(idx, live, io, st);
@@ -181,12 +305,14 @@ __global__ __launch_bounds__(kBlock, (JobLanes<F>::N > 1 ? TC_WAVES_G2 : TC_WAVE
   constexpr int L = JobLanes<F>::N;
   using IO = WaveRowIO<PB, L>;
   __shared__ __attribute__((aligned(16))) uint8_t lds[IO::BYTES];
+  const size_t slot = ((size_t)blockIdx.x * kBlock + threadIdx.x) / L;
+  size_t j = B;                                            // B = no job on this lane (past the end, or group padding)
+  if (slot < slots) j = perm ? (size_t)perm[slot] : slot;  // grouped by index tuple or denominator class, or the identity
+  const bool live = j < B;
+  // (G2: the grid covers the largest padding the grouping can need; a wave of nothing but padding leaves before it claims a slot)
+  if (L > 1 && !wave_any(live)) return;
   uint32_t tslot = 0;
   if (L > 1) tslot = table_slot_acquire(ta);  // the G2 ladders keep their tables in the arena (tc_table.h)
-  const size_t slot = ((size_t)blockIdx.x * kBlock + threadIdx.x) / L;
-  size_t j = B;                                            // B = no job on this lane (past the end, or class padding)
-  if (slot < slots) j = perm ? (size_t)perm[slot] : slot;  // grouped by denominator class, or the identity
-  const bool live = j < B;
   const size_t jj = live ? j : 0;
   IO io{lds, live ? shares + jj * n_per_job * PB : nullptr, (size_t)PB, live ? out + jj * PB : nullptr};
   uint8_t st = TC_JOB_OK;
@@ -328,21 +454,27 @@ void launch_combine_g1(hipStream_t st, size_t t, size_t n_per_job, const uint64_
   hipLaunchKernelGGL(k_combine_general<Fq>, dim3(grid_for(B)), dim3(kBlock), 0, st, t, n_per_job, idx, shares, lam, B, out, status, need_general, TableArena{nullptr, nullptr});
 }
 size_t combine_group_slots(size_t B) { return B + (size_t)kCombineClasses * kCombinePad; }
-// cls: B bytes, counters: 8 words, perm: combine_group_slots(B) words (scratch of the caller); pass
+// G2: every group padded to a whole wave -- at most kSubsetMaxGroups of them in subset mode, the classes otherwise
+size_t combine_group_slots_g2(size_t B) { return B + (size_t)kSubsetMaxGroups * (kSubsetPad - 1); }
+size_t combine_group_ws_words(size_t B) { return (size_t)kGwsZeroWords + 2 * B + (B + 1) / 2 + (B + 3) / 4; }
+// gws: combine_group_ws_words(B) words, perm: combine_group_slots_g2(B) words (scratch of the caller, 8-byte aligned); pass
 // perm = nullptr to run the jobs in their own order
 void launch_combine_g2(hipStream_t st, TableArena ta, size_t t, size_t n_per_job, const uint64_t* idx, const uint8_t* shares,
-                       const uint32_t* lam, size_t B, uint8_t* out, uint8_t* status, uint8_t* cls, uint32_t* counters,
+                       const uint32_t* lam, size_t B, uint8_t* out, uint8_t* status, uint32_t* gws,
                        uint32_t* perm, const uint32_t* need_general, hipEvent_t before_main) {
   if (!B || !ta.mem || !ta.flags) return;
   if (t >= 1 && t <= 3) {
     size_t slots = B;
-    if (perm) {
-      slots = combine_group_slots(B);
-      (void)hipMemsetAsync(counters, 0, 8 * sizeof(uint32_t), st);
+    if (perm && gws) {
+      slots = combine_group_slots_g2(B);
+      (void)hipMemsetAsync(gws, 0, kGwsZeroWords * sizeof(uint32_t), st);
       (void)hipMemsetAsync(perm, 0xff, slots * sizeof(uint32_t), st);
       const unsigned gb = (unsigned)((B + kGroupBlock - 1) / kGroupBlock);
-      hipLaunchKernelGGL(k_combine_classify, dim3(gb), dim3(kGroupBlock), 0, st, idx, n_per_job, t, B, cls, counters);
-      hipLaunchKernelGGL(k_combine_scatter, dim3(gb), dim3(kGroupBlock), 0, st, cls, B, counters, perm);
+      hipLaunchKernelGGL(k_combine_keys, dim3(gb), dim3(kGroupBlock), 0, st, idx, n_per_job, t, B, gws);
+      hipLaunchKernelGGL(k_combine_plan, dim3(1), dim3(kSubsetSlots), 0, st, t, B, gws);
+      hipLaunchKernelGGL(k_combine_place, dim3(gb), dim3(kGroupBlock), 0, st, B, gws, slots, perm);
+    } else {
+      perm = nullptr;
     }
     // before_main: recorded where the stream reaches the ONE long kernel of the call -- work the caller runs beside this call on
     // another stream (the membership tests of checked-input mode, tc_api.hip Call::run_checks) waits for it, so that it starts

@@ -778,16 +778,18 @@ static void combine_launch(Call& k, bool g2, size_t t, size_t n, const uint64_t*
   // the cheap forms of the final division (tc_jobs.h combine_divide); not worth three launches for a
   // batch that fills a fraction of the machine anyway
   const bool group = !d_idx_fr && t >= 1 && t <= 3 && (g2 ? B >= 4096 : B >= tc::kG1GroupMinJobs);
-  uint8_t* d_cls = group ? k.temp<uint8_t>(B) : nullptr;
-  uint32_t* d_counters = group ? k.temp<uint32_t>(8) : nullptr;
-  uint32_t* d_perm = group ? k.temp<uint32_t>(tc::combine_group_slots(B)) : nullptr;
+  // (G2 groups by index tuple, or by class where the tuples are too many: k_combine.hip k_combine_keys)
+  uint8_t* d_cls = group && !g2 ? k.temp<uint8_t>(B) : nullptr;
+  uint32_t* d_counters = group && !g2 ? k.temp<uint32_t>(8) : nullptr;
+  uint32_t* d_gws = group && g2 ? k.temp<uint32_t>(tc::combine_group_ws_words(B)) : nullptr;
+  uint32_t* d_perm = group ? k.temp<uint32_t>(g2 ? tc::combine_group_slots_g2(B) : tc::combine_group_slots(B)) : nullptr;
   uint32_t* d_need = (t > 0 && !d_idx_fr) ? k.temp<uint32_t>(1, /*zero=*/true) : nullptr;
   if (k.failed) return;
   if (d_idx_fr) {
     // `T: IntoFr` abscissae beyond u64 (src/into_fr.rs:10-14, 28-56): no small-index fast path, no integer differences
     if (t > 0) tc::launch_lagrange_fr(ctx->stream, d_idx_fr, n, t, B, d_lam, d_st);
     if (g2 && t >= 1) msm_g2(k, t + 1, n * PB, d_sh, d_lam, B, d_pt, d_st);
-    else if (g2) tc::launch_combine_g2(ctx->stream, k.tables(), t, n, nullptr, d_sh, d_lam, B, d_pt, d_st, nullptr, nullptr, nullptr, nullptr);
+    else if (g2) tc::launch_combine_g2(ctx->stream, k.tables(), t, n, nullptr, d_sh, d_lam, B, d_pt, d_st, nullptr, nullptr, nullptr);
     else if (t + 1 >= tc::kMsmMinPoints) msm_g1(k, t + 1, n * PB, d_sh, d_lam, B, d_pt, d_st);
     else tc::launch_combine_g1(ctx->stream, t, n, nullptr, d_sh, d_lam, B, d_pt, d_st, nullptr);
     return;
@@ -802,7 +804,7 @@ static void combine_launch(Call& k, bool g2, size_t t, size_t n, const uint64_t*
     msm_g2(k, t + 1, n * PB, d_sh, d_lam, B, d_pt, d_st);  // large thresholds: every job, coefficients from the one-inversion kernels
   } else if (g2) {
     // t <= 3: small-index fast path first; then (t >= 1) the jobs it left, through the two-stage kernels
-    tc::launch_combine_g2(ctx->stream, k.tables(), t, n, d_idx, d_sh, d_lam, B, d_pt, d_st, d_cls, d_counters, d_perm, d_need,
+    tc::launch_combine_g2(ctx->stream, k.tables(), t, n, d_idx, d_sh, d_lam, B, d_pt, d_st, d_gws, d_perm, d_need,
                           k.fork_event());
     if (t >= 1) {
       tc::MsmFilter f;

@@ -226,6 +226,95 @@ TC_HD G2Jac g2_mul_gls(const G2Jac& p, const uint32_t* k) {
   return r;
 }
 
+// ---- the same multiplication for a WAVE-UNIFORM scalar -----------------------------------------
+// When every lane of the wave multiplies by the same k (the [1 / D] step of a wave of share combinations over ONE signer
+// subset, tc_jobs.h), the digits steer scalar branches, and a column without a digit costs no addition: the sign-aligned
+// recoding above (no empty column, for lanes that disagree) gives way to the width-4 NAF of each base-|x| digit,
+//     d_j = sum_{i <= 64} e_j[i] 2^i,   e_j[i] in {0, +-1, +-3, +-5, +-7},  nonzero digits at least 4 columns apart,
+// over the table P, 3P, 5P, 7P and their psi-images (8 entries, the arena layout of the table above).  psi^2 and
+// psi^3 come from those at the look-up: psi^2(x, y) = (PSI2_CX x, -y) with PSI2_CX in Fq.  About 13 additions per digit
+// instead of 64 for the four together: 30 to 57 over the denominators of the 4-of-10 subsets.
+constexpr int kWnafCols = 65;
+TC_HD void wnaf4_recode(uint64_t d, int8_t* dig) {
+  unsigned __int128 k = d;
+  TC_NOUNROLL for (int i = 0; i < kWnafCols; i++) {
+    int m = 0;
+    if ((uint64_t)k & 1ull) {
+      m = (int)((uint64_t)k & 15ull);
+      if (m > 8) m -= 16;
+      k = (unsigned __int128)((__int128)k - m);
+    }
+    dig[i] = (int8_t)m;
+    k >>= 1;
+  }
+}
+struct G2WnafTable {
+  tbl_word* mem;  // entries 0..3: P, 3P, 5P, 7P; 4..7: their psi-images -- affine on ONE curve scaled by a real Z
+  Fq zn;          // that Z
+  TC_HD G2Affine entry(uint32_t m) const { return tbl_load_g2(mem + m * kTblEntryWords); }
+};
+// exc: the lane's table may be unusable (P at infinity or of order two); an entry at infinity (P of small order) carries
+// its flag into the ladder, which raises exc when it meets it
+TC_HD void g2_wnaf_table(const G2Jac& p, G2WnafTable& t, bool& exc) {
+  const G2Affine p1{p.x, p.y, false};                // affine on the curve scaled by p.z
+  const G2Jac d2 = jac_dbl(G2Jac::from_affine(p1));  // 2P there
+  // scaled once more by d2.z, P and 2P are both affine: the odd multiples cost one affine and two mixed additions
+  const Fq2 s2 = d2.z.sqr();
+  const G2Affine q1 = affine_scale_z(p1, s2, s2 * d2.z);
+  const G2Affine q2{d2.x, d2.y, false};
+  G2Jac odd[3];
+  odd[0] = jac_add_affine(q1, q2);
+  odd[1] = jac_add_mixed(odd[0], q2);
+  odd[2] = jac_add_mixed(odd[1], q2);
+  G2Affine aff[4];
+  const Fq2 zc = jac_batch_to_common_z<Fq2, 4>(odd, aff + 1, 3);
+  const Fq2 zc2 = zc.sqr();
+  aff[0] = affine_scale_z(q1, zc2, zc2 * zc);
+  // the four are affine on the curve scaled by zt; times conj(zt) that Z is the norm, an element of Fq, and psi maps
+  // the curve to itself (g2_gls_digits_mul above)
+  const Fq2 zt = coord_norm(coord_norm(p.z * d2.z) * zc);
+  exc = exc || maybe_zero56(zt);
+  const Fq2 l = zt.conj();
+  const Fq2 l2 = l.sqr();
+  const Fq2 l3 = l2 * l;
+  t.mem = pair_table();
+  t.zn = zt.norm_fq();
+  TC_NOUNROLL for (int m = 0; m < 4; m++) {
+    const G2Affine e = affine_scale_z(aff[m], l2, l3);
+    tbl_store_g2(t.mem + m * kTblEntryWords, e);
+    tbl_store_g2(t.mem + (4 + m) * kTblEntryWords, g2_psi(e));
+  }
+}
+// [d0] P - [d1] psi(P) + [d2] psi^2(P) - [d3] psi^3(P) for wave-uniform digits; generic additions only: a lane that may
+// have met a special case raises exc and the caller redoes its multiplication with the complete form
+TC_HD G2Jac g2_wnaf_ladder(const G2WnafTable& t, const uint64_t* d, bool& exc) {
+  int8_t dig[4][kWnafCols];
+  TC_NOUNROLL for (int j = 0; j < 4; j++) wnaf4_recode(d[j], dig[j]);
+  const Fq w = Fq::from_limbs(PSI2_CX);
+  G2Jac acc = G2Jac::infinity();
+  bool started = false;
+  TC_NOUNROLL for (int col = kWnafCols - 1; col >= 0; col--) {
+    tc_fair();
+    if (started) acc = jac_dbl(acc);
+    TC_NOUNROLL for (int j = 0; j < 4; j++) {
+      const int m = (int)(int64_t)wave_uniform((uint64_t)(int64_t)dig[j][col]);
+      if (m == 0) continue;
+      G2Affine e = t.entry((uint32_t)((m < 0 ? -m : m) >> 1) + ((j & 1) ? 4u : 0u));
+      if (j >= 2) e.x = e.x.scale(w);
+      if ((m < 0) != (j == 1 || j == 2)) e.y = (-e.y).norm();  // -psi, psi^2 = (w x, -y), -psi^3 = (w psi.x, +psi.y)
+      if (started) {
+        acc = jac_add_mixed_generic(acc, e, exc);
+      } else {
+        exc = exc || e.inf;
+        acc = G2Jac{e.x, e.y, Fq2::one()};
+        started = true;
+      }
+    }
+  }
+  acc.z = coord_norm(acc.z.scale(t.zn));
+  return acc;
+}
+
 // [|x|] P by the 64-bit ladder (|x| has Hamming weight 6: 63 doublings, 5 additions)
 // (the base enters as the affine point (X, Y) of the isomorphic curve y^2 = x^3 + b Z^6, so the five
 // additions are mixed ones; the result's Z is multiplied by the base's)

@@ -284,6 +284,60 @@ TC_HD G2Jac combine_divide(const G2Jac& q, uint64_t d_abs, bool d_neg) {
   return r;
 }
 TC_HD G2Jac combine_divide_arena(const G2Jac& q, uint64_t d_abs, bool d_neg) { return combine_divide(q, d_abs, d_neg); }  // (G2: always in the arena)
+TC_HD_NOINLINE G2Jac combine_divide_call(const G2Jac& q, uint64_t d_abs, bool d_neg) { return combine_divide(q, d_abs, d_neg); }
+// [1 / d_abs] q for a WAVE-UNIFORM denominator of the generic class (a wave of jobs over one signer subset): D^-1 mod r is
+// the wave's, so its base-|x| digits steer the width-4 NAF ladder of tc_gls.h (no odd first digit needed: no flip).
+// exc: the lane may have met a special case of the addition and its result is to be recomputed by combine_divide.
+TC_HD_NOINLINE G2Jac combine_divide_uniform(const G2Jac& q, uint64_t d_abs, bool& exc) {
+  uint32_t dinv[8];
+  fr_inverse_of_small(d_abs, false, dinv);
+  uint64_t d[4];
+  gls_decompose(dinv, d);
+  TC_UNROLL for (int j = 0; j < 4; j++) d[j] = wave_uniform(d[j]);
+  G2WnafTable t;
+  exc = exc || q.is_inf();
+  g2_wnaf_table(q, t, exc);
+  return g2_wnaf_ladder(t, d, exc);
+}
+
+template <class F>
+struct IsG2 {
+  static constexpr bool V = false;
+};
+template <>
+struct IsG2<Fq2> {
+  static constexpr bool V = true;
+};
+// The combination of a wave whose live jobs all have ONE index tuple (G2; the coefficients c_k and D are then the wave's):
+// the table-free short ladder (tc_threshold.h straus_small_uniform) and, for a generic denominator, the width-4 NAF
+// [1 / D] ladder.  Lanes that raise an exception flag are recomputed by the forms every other wave runs.
+#if !defined(__HIPCC__)
+inline int g_tc_force_mixed_combine = 0;  // host test build: 1 = take the forms of a mixed wave (on the host one job is a wave)
+#endif
+template <int K>
+TC_HD G2Jac combine_uniform_wave(const G2Affine* pts, const uint64_t* c_abs, uint64_t d_abs, bool d_neg) {
+  bool exc = false;
+  G2Jac a = straus_small_uniform<Fq2, K>(pts, c_abs, exc);
+  if (wave_any(exc)) a = G2Jac::select(exc, straus_small_call<Fq2, K>(pts, c_abs), a);
+  TC_MARK(2);
+  const uint64_t du = wave_uniform(d_abs);
+  if (combine_denominator_class(du) != kCombineClassGeneric) return combine_divide_call(a, d_abs, d_neg);
+  exc = false;
+  G2Jac q = combine_divide_uniform(a, du, exc);
+  q.y = Fq2::select(d_neg, -q.y, q.y);
+  if (wave_any(exc)) q = G2Jac::select(exc, combine_divide_call(a, d_abs, d_neg), q);
+  return q;
+}
+// every lane that reaches this (the wave's live jobs with decodable shares) holds the same tuple?
+template <int K>
+TC_HD bool combine_wave_is_uniform(const uint64_t* idx) {
+#if !defined(__HIPCC__)
+  if (g_tc_force_mixed_combine) return false;
+#endif
+  uint64_t key = 0;
+  TC_UNROLL for (int k = 0; k < K; k++) key |= (idx[k] & 0xffffull) << (16 * k);  // (the fast path took the job: every index < 65 535)
+  return !wave_any(key != wave_uniform(key));
+}
 
 // Where a job body finds the encodings of its operands and where its result goes.  DirectIO addresses global
 // memory as it is (one job per lane: 96/192-byte records `stride` apart); the kernels pass tc_stage.h's WaveRowIO
@@ -328,14 +382,31 @@ TC_HD bool job_combine_small_io(const uint64_t* idx, bool live, IO& io, uint8_t*
     } else {
       // (G2: out of line -- its own register allocation: the kernel's private segment drops from 8.0 to 5.6 KB at the
       // same speed; the one-lane G1 kernel measured 3 % slower that way)
-      Jac<F> a = (JobLanes<F>::N > 1) ? straus_small_call<F, K>(pts, c_abs) : straus_small<F, K, ARENA>(pts, c_abs);
-      TC_MARK(2);
-      const Jac<F> q = ARENA ? combine_divide_arena(a, d_abs, d_neg) : combine_divide(a, d_abs, d_neg);
-      TC_MARK(4);
-      const Affine<F> qa = jac_to_affine(q);
-      TC_MARK(5);
-      PointIO<F>::encode(qa, dst);
-      *status = TC_JOB_OK;
+      if constexpr (IsG2<F>::V) {
+        // a wave of one index tuple (the launch groups them so, k_combine.hip) takes the wave-uniform forms
+        Jac<F> q;
+        if (combine_wave_is_uniform<K>(idx)) {
+          q = combine_uniform_wave<K>(pts, c_abs, d_abs, d_neg);
+        } else {
+          const Jac<F> a = straus_small_call<F, K>(pts, c_abs);
+          TC_MARK(2);
+          q = combine_divide(a, d_abs, d_neg);
+        }
+        TC_MARK(4);
+        const Affine<F> qa = jac_to_affine(q);
+        TC_MARK(5);
+        PointIO<F>::encode(qa, dst);
+        *status = TC_JOB_OK;
+      } else {
+        Jac<F> a = (JobLanes<F>::N > 1) ? straus_small_call<F, K>(pts, c_abs) : straus_small<F, K, ARENA>(pts, c_abs);
+        TC_MARK(2);
+        const Jac<F> q = ARENA ? combine_divide_arena(a, d_abs, d_neg) : combine_divide(a, d_abs, d_neg);
+        TC_MARK(4);
+        const Affine<F> qa = jac_to_affine(q);
+        TC_MARK(5);
+        PointIO<F>::encode(qa, dst);
+        *status = TC_JOB_OK;
+      }
     }
   }
   io.commit(applies);
@@ -368,6 +439,53 @@ TC_HD bool combine_small_applies(const uint64_t* idx, int t) {
   if (t == 2) return lagrange_small_coeffs<3>(idx, c_abs, c_neg, &d_abs, &d_neg);
   if (t == 3) return lagrange_small_coeffs<4>(idx, c_abs, c_neg, &d_abs, &d_neg);
   return false;
+}
+
+// ---- grouping the G2 fast path's jobs by index tuple (k_combine.hip) ---------------------------------
+// A wave whose jobs all combine over ONE signer subset takes the wave-uniform forms above, so from 4096 jobs on the G2
+// launch is ordered by the job's first t + 1 indices: a key of 16 bits per index (the fast path only takes indices below
+// 65 535; the jobs it leaves share the key "none"), found in a small open-addressing table in the call's workspace.
+// Subset mode needs few enough distinct tuples that padding every group to a whole wave stays cheap; otherwise the
+// groups are the three denominator classes, as in G1.
+constexpr uint32_t kSubsetSlots = 512;      // table entries (a power of two, twice the groups subset mode allows)
+constexpr uint32_t kSubsetMaxGroups = 256;
+constexpr uint32_t kSubsetPad = 32;         // jobs of a G2 wave
+constexpr uint32_t kClassPad = 64;
+constexpr uint64_t kTupleKeyNone = ~0ull;
+constexpr int kGroupOrders = 4;             // generic, 2^a, 1, none: the expensive waves start first
+// the job's key, and the class of its denominator (generic when the fast path does not take it)
+TC_HD uint64_t combine_tuple_key(const uint64_t* idx, int t, int* cls) {
+  uint64_t c_abs[4], d_abs = 0;
+  bool c_neg[4], d_neg;
+  bool applies = false;
+  if (t == 1) applies = lagrange_small_coeffs<2>(idx, c_abs, c_neg, &d_abs, &d_neg);
+  if (t == 2) applies = lagrange_small_coeffs<3>(idx, c_abs, c_neg, &d_abs, &d_neg);
+  if (t == 3) applies = lagrange_small_coeffs<4>(idx, c_abs, c_neg, &d_abs, &d_neg);
+  *cls = applies ? combine_denominator_class(d_abs) : kCombineClassGeneric;
+  if (!applies) return kTupleKeyNone;
+  uint64_t key = 0;
+  for (int k = 0; k <= t; k++) key |= idx[k] << (16 * k);  // distinct indices: never zero, the table's "empty"
+  return key;
+}
+TC_HD int combine_class_order(int cls) { return cls == kCombineClassGeneric ? 0 : cls == kCombineClassPow2 ? 1 : 2; }
+TC_HD int combine_key_order(uint64_t key, int t) {
+  if (key == kTupleKeyNone) return 3;
+  uint64_t idx[4];
+  for (int k = 0; k < 4; k++) idx[k] = (key >> (16 * k)) & 0xffffull;
+  return combine_class_order(combine_job_class(idx, t));
+}
+TC_HD uint32_t combine_key_hash(uint64_t key) { return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 40); }
+TC_HD bool combine_subset_mode(bool overflow, uint32_t groups, size_t B) {
+  return !overflow && groups <= kSubsetMaxGroups && (size_t)kSubsetPad * groups <= B / 8;  // padding: at most an eighth of the slots
+}
+// first slot of group s: the groups sorted by (order, number), each padded to a multiple of `pad` (an empty one takes nothing)
+TC_HD uint32_t combine_group_start(const uint32_t* count, const uint8_t* order, uint32_t n, uint32_t s, uint32_t pad) {
+  uint32_t start = 0;
+  for (uint32_t g = 0; g < n; g++) {
+    const bool before = order[g] < order[s] || (order[g] == order[s] && g < s);
+    if (before) start += (count[g] + pad - 1) / pad * pad;
+  }
+  return start;
 }
 
 // out = sum_{i <= t} lambda_i * share_i over the FIRST t+1 samples of the job

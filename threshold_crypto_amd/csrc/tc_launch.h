@@ -125,8 +125,12 @@ void launch_fr_idx_narrow(hipStream_t st, const uint32_t* idx_fr, size_t n_per_j
                           uint8_t* valid);
 void launch_lagrange_fr(hipStream_t st, const uint32_t* idx_fr, size_t n_per_job, size_t t, size_t B, uint32_t* lam, uint8_t* status);
 size_t combine_group_slots(size_t B);
+// G2 groups its fast-path jobs by index tuple (k_combine.hip): gws = combine_group_ws_words(B) words and perm =
+// combine_group_slots_g2(B) words of the caller's scratch, both or neither
+size_t combine_group_slots_g2(size_t B);
+size_t combine_group_ws_words(size_t B);
 void launch_combine_g2(hipStream_t st, TableArena ta, size_t t, size_t n_per_job, const uint64_t* idx, const uint8_t* shares,
-                       const uint32_t* lam, size_t B, uint8_t* out, uint8_t* status, uint8_t* cls, uint32_t* counters,
+                       const uint32_t* lam, size_t B, uint8_t* out, uint8_t* status, uint32_t* gws,
                        uint32_t* perm, const uint32_t* need_general, hipEvent_t before_main = nullptr);
 // shared_points: every job combines the SAME n points (points holds n of them) with its own n scalars
 void launch_lincomb_g1(hipStream_t st, size_t n, const uint8_t* scalars, const uint8_t* points, size_t B, uint8_t* out,

@@ -449,4 +449,44 @@ TC_HD Jac<F> straus_small(const Affine<F>* pts, const uint64_t* c) {
 template <class F, int K>
 TC_HD_NOINLINE Jac<F> straus_small_call(const Affine<F>* pts, const uint64_t* c) { return straus_small<F, K>(pts, c); }
 
+// non-adjacent form of c < 2^63:  c = sum_i (bit_i(pos) - bit_i(neg)) 2^i, no two adjacent nonzero digits
+TC_HD void naf_recode(uint64_t c, uint64_t* pos, uint64_t* neg) {
+  const unsigned __int128 c1 = c, c3 = c1 * 3;
+  *pos = (uint64_t)((c3 & ~c1) >> 1);
+  *neg = (uint64_t)((c1 & ~c3) >> 1);
+}
+// The same sum when the c_k are WAVE-UNIFORM (every job of the wave combines over one signer subset: the combine kernels
+// group them so, k_combine.hip): the digits steer scalar branches, so the ladder needs no subset-sum table (11 additions
+// for K = 4) and no full Jacobian additions -- the NAF of each c_k, one doubling per column of THIS subset's longest c_k,
+// one mixed addition of +-P_k per nonzero digit (9.6 on average over the generic 4-of-10 subsets).  Generic additions
+// only: a lane that may have met a special case raises exc and the caller redoes it with straus_small_call.
+template <class F, int K>
+TC_HD_NOINLINE Jac<F> straus_small_uniform(const Affine<F>* pts, const uint64_t* c, bool& exc) {
+  uint64_t pos[K], neg[K], any = 0;
+  TC_UNROLL for (int k = 0; k < K; k++) {
+    naf_recode(wave_uniform(c[k]), &pos[k], &neg[k]);
+    any |= pos[k] | neg[k];
+  }
+  Jac<F> acc = Jac<F>::infinity();
+  bool started = false;
+  TC_NOUNROLL for (int bit = any ? 63 - (int)__builtin_clzll(any) : -1; bit >= 0; bit--) {
+    tc_fair();
+    if (started) acc = jac_dbl(acc);
+    TC_NOUNROLL for (int k = 0; k < K; k++) {
+      const bool plus = (pos[k] >> bit) & 1ull, minus = (neg[k] >> bit) & 1ull;
+      if (!plus && !minus) continue;
+      Affine<F> e = pts[k];
+      if (minus) e.y = (-e.y).norm();
+      if (started) {
+        acc = jac_add_mixed_generic(acc, e, exc);
+      } else {
+        exc = exc || e.inf;
+        acc = Jac<F>{e.x, e.y, F::one()};
+        started = true;
+      }
+    }
+  }
+  return acc;
+}
+
 }  // namespace tc
