@@ -235,44 +235,62 @@ TC_HD G2Jac g2_mul_gls(const G2Jac& p, const uint32_t* k) {
 // psi^3 come from those at the look-up: psi^2(x, y) = (PSI2_CX x, -y) with PSI2_CX in Fq.  About 13 additions per digit
 // instead of 64 for the four together: 30 to 57 over the denominators of the 4-of-10 subsets.
 constexpr int kWnafCols = 65;
-TC_HD void wnaf4_recode(uint64_t d, int8_t* dig) {
+// width-W NAF of d: digits in {0, +-1, +-3, .. +-(2^(W-1) - 1)}, nonzero digits at least W columns apart
+template <int W>
+TC_HD void wnaf_recode(uint64_t d, int8_t* dig) {
   unsigned __int128 k = d;
   TC_NOUNROLL for (int i = 0; i < kWnafCols; i++) {
     int m = 0;
     if ((uint64_t)k & 1ull) {
-      m = (int)((uint64_t)k & 15ull);
-      if (m > 8) m -= 16;
+      m = (int)((uint64_t)k & ((1ull << W) - 1));
+      if (m > (1 << (W - 1))) m -= 1 << W;
       k = (unsigned __int128)((__int128)k - m);
     }
     dig[i] = (int8_t)m;
     k >>= 1;
   }
 }
+TC_HD void wnaf4_recode(uint64_t d, int8_t* dig) { wnaf_recode<4>(d, dig); }
+// non-adjacent form of c < 2^63:  c = sum_i (bit_i(pos) - bit_i(neg)) 2^i, no two adjacent nonzero digits
+TC_HD void naf_recode(uint64_t c, uint64_t* pos, uint64_t* neg) {
+  const unsigned __int128 c1 = c, c3 = c1 * 3;
+  *pos = (uint64_t)((c3 & ~c1) >> 1);
+  *neg = (uint64_t)((c1 & ~c3) >> 1);
+}
 struct G2WnafTable {
   tbl_word* mem;  // entries 0..3: P, 3P, 5P, 7P; 4..7: their psi-images -- affine on ONE curve scaled by a real Z
   Fq zn;          // that Z
   TC_HD G2Affine entry(uint32_t m) const { return tbl_load_g2(mem + m * kTblEntryWords); }
 };
-// exc: the lane's table may be unusable (P at infinity or of order two); an entry at infinity (P of small order) carries
-// its flag into the ladder, which raises exc when it meets it
-TC_HD void g2_wnaf_table(const G2Jac& p, G2WnafTable& t, bool& exc) {
-  const G2Affine p1{p.x, p.y, false};                // affine on the curve scaled by p.z
-  const G2Jac d2 = jac_dbl(G2Jac::from_affine(p1));  // 2P there
-  // scaled once more by d2.z, P and 2P are both affine: the odd multiples cost one affine and two mixed additions
+// the odd multiples P, 3P .. (2N - 1)P of an affine point (N = 2 or 4) as affine points of ONE curve: the one of p1 scaled by
+// the value returned
+template <int N>
+TC_HD Fq2 g2_odd_multiples(const G2Affine& p1, G2Affine* aff) {
+  const G2Jac d2 = jac_dbl(G2Jac::from_affine(p1));  // 2P
+  // scaled by d2.z, P and 2P are both affine: the odd multiples cost one affine and N - 2 mixed additions
   const Fq2 s2 = d2.z.sqr();
   const G2Affine q1 = affine_scale_z(p1, s2, s2 * d2.z);
   const G2Affine q2{d2.x, d2.y, false};
-  G2Jac odd[3];
+  G2Jac odd[N - 1];
   odd[0] = jac_add_affine(q1, q2);
-  odd[1] = jac_add_mixed(odd[0], q2);
-  odd[2] = jac_add_mixed(odd[1], q2);
-  G2Affine aff[4];
-  const Fq2 zc = jac_batch_to_common_z<Fq2, 4>(odd, aff + 1, 3);
+  TC_NOUNROLL for (int m = 1; m < N - 1; m++) odd[m] = jac_add_mixed(odd[m - 1], q2);
+  Fq2 zc = odd[0].z;
+  // (one entry: no product brings the sums of the addition back to a table entry's range, tc_field.h reduce_value; 3P at
+  // infinity: zc = 0, which the caller flags)
+  if constexpr (N == 2) aff[1] = G2Affine{odd[0].x.reduce_value(), odd[0].y.reduce_value(), false};
+  else zc = jac_batch_to_common_z<Fq2, 4>(odd, aff + 1, N - 1);
   const Fq2 zc2 = zc.sqr();
   aff[0] = affine_scale_z(q1, zc2, zc2 * zc);
+  return coord_norm(d2.z * zc);
+}
+// exc: the lane's table may be unusable (P at infinity or of order two); an entry at infinity (P of small order) carries
+// its flag into the ladder, which raises exc when it meets it
+TC_HD void g2_wnaf_table(const G2Jac& p, G2WnafTable& t, bool& exc) {
+  G2Affine aff[4];
+  const Fq2 zs = g2_odd_multiples<4>(G2Affine{p.x, p.y, false}, aff);  // (p.x, p.y): affine on the curve scaled by p.z
   // the four are affine on the curve scaled by zt; times conj(zt) that Z is the norm, an element of Fq, and psi maps
   // the curve to itself (g2_gls_digits_mul above)
-  const Fq2 zt = coord_norm(coord_norm(p.z * d2.z) * zc);
+  const Fq2 zt = coord_norm(p.z * zs);
   exc = exc || maybe_zero56(zt);
   const Fq2 l = zt.conj();
   const Fq2 l2 = l.sqr();
@@ -312,6 +330,186 @@ TC_HD G2Jac g2_wnaf_ladder(const G2WnafTable& t, const uint64_t* d, bool& exc) {
     }
   }
   acc.z = coord_norm(acc.z.scale(t.zn));
+  return acc;
+}
+
+// ---- [1 / D] for a small wave-uniform D through the quotient of |x| by D ------------------------------------------
+// With X = |x| and r = X^4 - X^2 + 1:  for k = -r^-1 mod D the integer N = 1 + k r = k X^4 - k X^2 + (k + 1) is a multiple
+// of D, and N / D = D^-1 (mod r).  Write X = D q + x0 and divide the base-X digits (k, 0, -k, 0, k + 1) of N by D from the
+// top: a carry c entering a digit g leaves the quotient digit c q + e, e = round((c x0 + g) / D), and the carry
+// c x0 + g - e D.  The division is exact, so
+//     D^-1 = sum_{j < 4} (T_j q + E_j) psi^j  (mod r)        (psi = [-X] on G2; the signs (-1)^j are folded into T_j, E_j)
+// with T_j the carries and E_j the small quotients:  [1 / D] Q = [q] P1 + P2,  P1 = T(psi) Q,  P2 = E(psi) Q  --  ONE ladder
+// over the 57 to 62 bits of q on a point made from coefficients of a few bits, instead of four 64-bit digits.
+// (D = 3: T = E = psi^2 + psi^3, the (|x| + 1) / 3 of g2_clear_cofactor below.)
+//
+// floor(n / d) for d < 2^63: the 64-bit divide when n fits it, bit by bit otherwise (a D above 2^32: the form is not taken
+// for those, only offered)
+TC_HD unsigned __int128 udiv_u128_u64(unsigned __int128 n, uint64_t d) {
+  if ((uint64_t)(n >> 64) == 0) return (uint64_t)n / d;
+  unsigned __int128 quo = 0;
+  uint64_t rem = 0;
+  TC_NOUNROLL for (int bit = 127; bit >= 0; bit--) {
+    rem = (rem << 1) | (uint64_t)((n >> bit) & 1);
+    if (rem >= d) {
+      rem -= d;
+      quo |= (unsigned __int128)1 << bit;
+    }
+  }
+  return quo;
+}
+TC_HD uint64_t mulmod_u64(uint64_t a, uint64_t b, uint64_t d) {
+  const unsigned __int128 n = (unsigned __int128)a * b;
+  return (uint64_t)(n - udiv_u128_u64(n, d) * d);
+}
+// D -> q = floor(|x| / D) and the coefficients above.  Succeeds for every D in [3, 2^62) that is not a power of two and
+// promises  q >= 3,  |T_j| <= D / 2,  |E_j| <= D / 2 + 2,  D * sum_j (T_j q + E_j) (-|x|)^j = 1 (mod r);  false otherwise
+// (the caller then keeps the 4-dimensional ladder).  Wave-uniform input: scalar work, a few hundred instructions.
+TC_HD bool combine_quotient_decompose(uint64_t D, uint64_t* q, int64_t* T, int64_t* E) {
+  if (D < 3 || (D & (D - 1)) == 0 || (D >> 62) != 0) return false;
+  const uint64_t qq = BLS_X_ABS / D, x0 = BLS_X_ABS - qq * D;
+  // r mod D = x0^4 - x0^2 + 1
+  const uint64_t x2 = mulmod_u64(x0, x0, D), x4 = mulmod_u64(x2, x2, D);
+  uint64_t r1 = x4 + (D - x2);
+  if (r1 >= D) r1 -= D;
+  r1 += 1;
+  if (r1 >= D) r1 -= D;
+  // r1^-1 mod D (r is prime and D < r: the gcd is 1)
+  int64_t t = 0, newt = 1;
+  uint64_t a = D, b = r1;
+  TC_NOUNROLL while (b != 0) {
+    const uint64_t quo = a / b;
+    const uint64_t nb = a - quo * b;
+    const int64_t nt = t - (int64_t)quo * newt;
+    a = b;
+    b = nb;
+    t = newt;
+    newt = nt;
+  }
+  if (a != 1) return false;
+  const uint64_t inv = t < 0 ? (uint64_t)(t + (int64_t)D) : (uint64_t)t;
+  const int64_t k = (int64_t)(D - inv);  // -r^-1 mod D, in [1, D)
+  const int64_t dig[5] = {k, 0, -k, 0, k + 1};  // of X^4 .. X^0
+  int64_t c = 0, cs[5], es[5];
+  TC_NOUNROLL for (int i = 0; i < 5; i++) {
+    const __int128 v = (__int128)c * (__int128)x0 + dig[i];
+    const __int128 n = 2 * v + (__int128)D;  // e = floor(n / 2D): v / D rounded to nearest
+    const int64_t e = n >= 0 ? (int64_t)udiv_u128_u64((unsigned __int128)n, 2 * D)
+                             : -(int64_t)udiv_u128_u64((unsigned __int128)(-n) + 2 * D - 1, 2 * D);
+    cs[i] = c;
+    es[i] = e;
+    c = (int64_t)(v - (__int128)e * (__int128)D);
+  }
+  if (c != 0) return false;
+  TC_UNROLL for (int j = 0; j < 4; j++) {
+    T[j] = cs[4 - j];
+    E[j] = es[4 - j];
+  }
+  // the top digit rounds to 0 or 1 (k / D): X^4 = X^2 - 1 (mod r)
+  E[2] += es[0];
+  E[0] -= es[0];
+  T[1] = -T[1];  // X = -psi
+  T[3] = -T[3];
+  E[1] = -E[1];
+  E[3] = -E[3];
+  *q = qq;
+  return true;
+}
+// the NAF of four signed coefficients, as bit masks
+struct QuotNaf {
+  uint64_t pos[4], neg[4];
+  TC_HD uint64_t any() const { return pos[0] | neg[0] | pos[1] | neg[1] | pos[2] | neg[2] | pos[3] | neg[3]; }
+};
+TC_HD QuotNaf quot_naf(const int64_t* c) {
+  QuotNaf n;
+  TC_UNROLL for (int j = 0; j < 4; j++) {
+    const bool minus = c[j] < 0;
+    uint64_t p, m;
+    naf_recode((uint64_t)(minus ? -c[j] : c[j]), &p, &m);
+    n.pos[j] = minus ? m : p;
+    n.neg[j] = minus ? p : m;
+  }
+  return n;
+}
+// (measured over the 138 generic 4-of-10 subsets, multiply-adds of the division: plain NAF 752 k, width 3 702 k, width 4 713 k)
+constexpr int kQuotWidth = 3;                      // of the NAF of q: the odd multiples P1 .. (2^(W-1) - 1) P1
+constexpr int kQuotTable = 1 << (kQuotWidth - 2);  // entries 2 .. of the lane pair's arena table; 0, 1: Q and psi(Q)
+// column `bit` of sum_j c_j psi^j(B) into acc, B and psi(B) in entries 0 and 1:  psi^2(x, y) = (PSI2_CX x, -y)
+TC_HD void quot_add_bases(G2Jac& acc, bool& started, bool& exc, const tbl_word* mem, const QuotNaf& n, int bit) {
+  TC_NOUNROLL for (int j = 0; j < 4; j++) {
+    const bool plus = (n.pos[j] >> bit) & 1ull, minus = (n.neg[j] >> bit) & 1ull;
+    if (!plus && !minus) continue;
+    G2Affine e = tbl_load_g2(mem + (j & 1) * kTblEntryWords);
+    if (j >= 2) e.x = e.x.scale(Fq::from_limbs(PSI2_CX));
+    if (minus != (j >= 2)) e.y = (-e.y).norm();
+    if (started) {
+      acc = jac_add_mixed_generic(acc, e, exc);
+    } else {
+      exc = exc || e.inf;
+      acc = G2Jac{e.x, e.y, Fq2::one()};
+      started = true;
+    }
+  }
+}
+// [q] T(psi) P + E(psi) P for wave-uniform q, T, E (combine_quotient_decompose).  Generic additions only: a lane that may
+// have met a special case raises exc and the caller redoes its multiplication with the complete form.
+TC_HD G2Jac g2_quotient_mul(const G2Jac& p, uint64_t q, const int64_t* T, const int64_t* E, bool& exc) {
+  // a real Z (g2_gls_digits_mul above): P and psi(P) are affine points of one curve
+  const Fq2 l = p.z.conj();
+  const Fq2 l2 = l.sqr();
+  const G2Affine b0{coord_norm(p.x * l2), coord_norm(p.y * (l2 * l)), p.is_inf()};
+  const Fq zn = p.z.norm_fq();
+  tbl_word* mem = pair_table();
+  tbl_store_g2(mem, b0);
+  tbl_store_g2(mem + kTblEntryWords, g2_psi(b0));
+  // P1 = T(psi) P: one doubling per column of THIS denominator's longest T_j, one mixed addition per nonzero digit
+  const QuotNaf nt = quot_naf(T);
+  G2Jac acc = G2Jac::infinity();
+  bool started = false;
+  const uint64_t any_t = nt.any();
+  TC_NOUNROLL for (int bit = any_t ? 63 - (int)__builtin_clzll(any_t) : -1; bit >= 0; bit--) {
+    tc_fair();
+    if (started) acc = jac_dbl(acc);
+    quot_add_bases(acc, started, exc, mem, nt, bit);
+  }
+  exc = exc || !started;
+  // (X, Y) of P1 is an affine point of the curve scaled once more by its Z; its odd multiples by a further factor
+  G2Affine tab[kQuotTable];
+  const Fq2 s = coord_norm(acc.z * g2_odd_multiples<kQuotTable>(G2Affine{acc.x, acc.y, false}, tab));
+  exc = exc || maybe_zero56(s);
+  TC_NOUNROLL for (int m = 0; m < kQuotTable; m++) tbl_store_g2(mem + (2 + m) * kTblEntryWords, tab[m]);
+  // the bases move onto that curve for the digits of E, which join the low columns of the ladder of q
+  const Fq2 s2 = s.sqr();
+  const Fq2 s3 = s2 * s;
+  TC_NOUNROLL for (int m = 0; m < 2; m++) tbl_store_g2(mem + m * kTblEntryWords, affine_scale_z(tbl_load_g2(mem + m * kTblEntryWords), s2, s3));
+  const QuotNaf ne = quot_naf(E);
+  const uint64_t any_e = ne.any();
+  int8_t dig[kWnafCols];
+  wnaf_recode<kQuotWidth>(q, dig);
+  int top = any_e ? 63 - (int)__builtin_clzll(any_e) : 0;
+  TC_NOUNROLL for (int col = kWnafCols - 1; col > top; col--)
+    if (dig[col]) top = col;
+  acc = G2Jac::infinity();
+  started = false;
+  TC_NOUNROLL for (int col = top; col >= 0; col--) {
+    tc_fair();
+    if (started) acc = jac_dbl(acc);
+    const int m = (int)(int64_t)wave_uniform((uint64_t)(int64_t)dig[col]);
+    if (m != 0) {
+      G2Affine e = tbl_load_g2(mem + (2 + ((m < 0 ? -m : m) >> 1)) * kTblEntryWords);
+      if (m < 0) e.y = (-e.y).norm();
+      if (started) {
+        acc = jac_add_mixed_generic(acc, e, exc);
+      } else {
+        acc = G2Jac{e.x, e.y, Fq2::one()};
+        started = true;
+      }
+    }
+    if (col < 64) quot_add_bases(acc, started, exc, mem, ne, col);
+  }
+  exc = exc || !started;
+  acc.z = coord_norm(acc.z * s);
+  acc.z = coord_norm(acc.z.scale(zn));
   return acc;
 }
 

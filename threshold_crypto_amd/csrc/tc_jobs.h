@@ -300,6 +300,72 @@ TC_HD_NOINLINE G2Jac combine_divide_uniform(const G2Jac& q, uint64_t d_abs, bool
   return g2_wnaf_ladder(t, d, exc);
 }
 
+// The same through the quotient of |x| by D (tc_gls.h combine_quotient_decompose): one ladder over q = |x| / D on a point
+// made from coefficients as short as D.  d_abs must be one the decomposition takes (combine_divide_takes_quotient).
+TC_HD_NOINLINE G2Jac combine_divide_quotient(const G2Jac& q, uint64_t d_abs, bool& exc) {
+  uint64_t qq = 0;
+  int64_t T[4] = {0, 0, 0, 0}, E[4] = {0, 0, 0, 0};
+  exc = exc || q.is_inf() || !combine_quotient_decompose(d_abs, &qq, T, E);
+  TC_UNROLL for (int j = 0; j < 4; j++) {
+    T[j] = (int64_t)wave_uniform((uint64_t)T[j]);
+    E[j] = (int64_t)wave_uniform((uint64_t)E[j]);
+  }
+  return g2_quotient_mul(q, wave_uniform(qq), T, E, exc);
+}
+// Which of the two forms a wave takes: the multiply-adds of both, predicted from the digits -- the doublings and the
+// additions of each ladder times what a doubling and a mixed addition execute (two lanes, tests/count_ops.py), plus what
+// each form executes besides (the tables, the common Z, the bases).  The quotient form wins for every D below 2^13 or so
+// and loses from 2^16 on, where T and E are as long as a fifth of q.
+constexpr uint32_t kMacsDbl = 6272, kMacsAdd = 11368, kMacsPsi2 = 784, kMacsUniformFixed = 91938, kMacsQuotientFixed = 39410;
+TC_HD uint32_t combine_divide_uniform_macs(uint64_t d_abs) {
+  uint32_t dinv[8];
+  fr_inverse_of_small(d_abs, false, dinv);
+  uint64_t d[4];
+  gls_decompose(dinv, d);
+  int top = 0, nz = 0, nz2 = 0;  // nz2: look-ups that take psi^2 of an entry
+  TC_NOUNROLL for (int j = 0; j < 4; j++) {
+    int8_t dig[kWnafCols];
+    wnaf4_recode(d[j], dig);
+    TC_NOUNROLL for (int col = 0; col < kWnafCols; col++)
+      if (dig[col]) {
+        nz++;
+        nz2 += j >> 1;
+        if (col > top) top = col;
+      }
+  }
+  return kMacsUniformFixed + (uint32_t)top * kMacsDbl + (uint32_t)(nz - 1) * kMacsAdd + (uint32_t)nz2 * kMacsPsi2;
+}
+TC_HD uint32_t combine_divide_quotient_macs(uint64_t q, const int64_t* T, const int64_t* E) {
+  const QuotNaf nt = quot_naf(T), ne = quot_naf(E);
+  int8_t dig[kWnafCols];
+  wnaf_recode<kQuotWidth>(q, dig);
+  int top = ne.any() ? 63 - (int)__builtin_clzll(ne.any()) : 0, nz = 0, nz2 = 0;
+  TC_NOUNROLL for (int col = 0; col < kWnafCols; col++)
+    if (dig[col]) {
+      nz++;
+      if (col > top) top = col;
+    }
+  TC_UNROLL for (int j = 0; j < 4; j++) {
+    const int n = __builtin_popcountll(nt.pos[j] | nt.neg[j]) + __builtin_popcountll(ne.pos[j] | ne.neg[j]);
+    nz += n;
+    nz2 += (j >> 1) * n;
+  }
+  top += nt.any() ? 63 - (int)__builtin_clzll(nt.any()) : 0;
+  return kMacsQuotientFixed + (uint32_t)top * kMacsDbl + (uint32_t)(nz - 2) * kMacsAdd + (uint32_t)nz2 * kMacsPsi2;
+}
+#if !defined(__HIPCC__)
+inline int g_tc_force_divide_form = 0;  // host test build: 1 = the 4-dimensional ladder, 2 = the quotient form wherever it exists
+#endif
+TC_HD bool combine_divide_takes_quotient(uint64_t d_abs) {
+  uint64_t q;
+  int64_t T[4], E[4];
+  if (!combine_quotient_decompose(d_abs, &q, T, E)) return false;
+#if !defined(__HIPCC__)
+  if (g_tc_force_divide_form) return g_tc_force_divide_form == 2;
+#endif
+  return combine_divide_quotient_macs(q, T, E) < combine_divide_uniform_macs(d_abs);
+}
+
 template <class F>
 struct IsG2 {
   static constexpr bool V = false;
@@ -309,8 +375,9 @@ struct IsG2<Fq2> {
   static constexpr bool V = true;
 };
 // The combination of a wave whose live jobs all have ONE index tuple (G2; the coefficients c_k and D are then the wave's):
-// the table-free short ladder (tc_threshold.h straus_small_uniform) and, for a generic denominator, the width-4 NAF
-// [1 / D] ladder.  Lanes that raise an exception flag are recomputed by the forms every other wave runs.
+// the table-free short ladder (tc_threshold.h straus_small_uniform) and, for a generic denominator, the cheaper of the two
+// [1 / D] forms above (the ladder over |x| / D for the small denominators of node numbers, the width-4 NAF ladder otherwise).
+// Lanes that raise an exception flag are recomputed by the forms every other wave runs.
 #if !defined(__HIPCC__)
 inline int g_tc_force_mixed_combine = 0;  // host test build: 1 = take the forms of a mixed wave (on the host one job is a wave)
 #endif
@@ -323,7 +390,7 @@ TC_HD G2Jac combine_uniform_wave(const G2Affine* pts, const uint64_t* c_abs, uin
   const uint64_t du = wave_uniform(d_abs);
   if (combine_denominator_class(du) != kCombineClassGeneric) return combine_divide_call(a, d_abs, d_neg);
   exc = false;
-  G2Jac q = combine_divide_uniform(a, du, exc);
+  G2Jac q = combine_divide_takes_quotient(du) ? combine_divide_quotient(a, du, exc) : combine_divide_uniform(a, du, exc);
   q.y = Fq2::select(d_neg, -q.y, q.y);
   if (wave_any(exc)) q = G2Jac::select(exc, combine_divide_call(a, d_abs, d_neg), q);
   return q;

@@ -449,12 +449,6 @@ TC_HD Jac<F> straus_small(const Affine<F>* pts, const uint64_t* c) {
 template <class F, int K>
 TC_HD_NOINLINE Jac<F> straus_small_call(const Affine<F>* pts, const uint64_t* c) { return straus_small<F, K>(pts, c); }
 
-// non-adjacent form of c < 2^63:  c = sum_i (bit_i(pos) - bit_i(neg)) 2^i, no two adjacent nonzero digits
-TC_HD void naf_recode(uint64_t c, uint64_t* pos, uint64_t* neg) {
-  const unsigned __int128 c1 = c, c3 = c1 * 3;
-  *pos = (uint64_t)((c3 & ~c1) >> 1);
-  *neg = (uint64_t)((c1 & ~c3) >> 1);
-}
 // The same sum when the c_k are WAVE-UNIFORM (every job of the wave combines over one signer subset: the combine kernels
 // group them so, k_combine.hip): the digits steer scalar branches, so the ladder needs no subset-sum table (11 additions
 // for K = 4) and no full Jacobian additions -- the NAF of each c_k, one doubling per column of THIS subset's longest c_k,
