@@ -313,6 +313,53 @@ int tc_bivar_commitment_row_batch(tc_ctx* ctx, const uint8_t* commit, size_t deg
 int tc_fr_interpolate_batch(tc_ctx* ctx, size_t n, const uint8_t* xs, const uint8_t* ys, size_t B, uint8_t* out_coeff,
                             uint8_t* status);
 
+/* ---- DKG verification: the secret side and the two checks of `distributed_key_generation` (src/poly.rs:838-878) ----
+ * Common to the five entries below.  Abscissae are u64 values taken BY VALUE (the `IntoFr` image of a u64; rows and
+ * values are addressed as 1 .. N, 0 and 2^64 - 1 are as good as any).  A non-canonical Fr operand (>= r) fails the
+ * outputs that depend on it: TC_JOB_INVALID_ENCODING and a zero output in the two Fr entries, ok = 0 for that value in
+ * the check entries (a non-canonical ROW coefficient fails its whole job).  An undecodable point operand fails its whole
+ * job, and so does, in checked-input mode (tc_ctx_set_input_checks), a point outside the order-r subgroup.  A size of
+ * zero is a no-op (n = 0 in tc_fr_poly_evaluate_batch: the zero polynomial); NULL data pointers with non-zero sizes
+ * answer TC_ERR_INVALID_ARG.  The polynomial coefficients, the rows and the values are SECRETS: their staging copies
+ * and every temporary derived from them are zeroed before the call returns, and in host-I/O mode so are the staged Fr
+ * outputs once they have been copied back.  All five work in device-I/O mode like every other entry. */
+/* out[j*M + m] = Poly(coeff[j]).evaluate(xs[m]): Horner in Fr.  src/poly.rs:358-369; SecretKeySet::secret_key_share
+ * src/lib.rs:670-673 is evaluate(i + 1).  coeff_fr: B x n x 32 B LE (low degree first), xs_fr: M x 32 B LE shared by
+ * every polynomial, out_fr: B x M x 32, status: B x M (optional). */
+int tc_fr_poly_evaluate_batch(tc_ctx* ctx, const uint8_t* coeff_fr, size_t n, const uint8_t* xs_fr, size_t M, size_t B,
+                              uint8_t* out_fr, uint8_t* status);
+/* out[m*(degree+1) + i] = BivarPoly::row(xs[m])[i] = sum_j coeff[pos(i,j)] * xs[m]^j.  src/poly.rs:607-622.
+ * coeff_fr: the (degree+1)(degree+2)/2 coefficients in coeff_pos order (src/poly.rs:746-750), 32 B LE each;
+ * out_fr: M x (degree+1) x 32; status: M x (degree+1) (optional). */
+int tc_bivar_poly_row_batch(tc_ctx* ctx, const uint8_t* coeff_fr, size_t degree, const uint64_t* xs, size_t M, uint8_t* out_fr,
+                            uint8_t* status);
+/* `row_poly.commitment() == bi_commit.row(m)`, src/poly.rs:841-843, for B parts at once.  Job j: R_j =
+ * commit_j.row(xs[j]) (BivarCommitment::row :713-727; written to out_rows, B x (degree+1) x 96, when non-NULL) and
+ * ok[j] = 1 iff row_fr[j][i] * g1 == R_j[i] for every i (group elements compare as elements: the identity equals the
+ * identity).  commits: job j's (degree+1)(degree+2)/2 x 96 B commitment starts commit_stride BYTES after job j-1's
+ * (a multiple of 96, at least the size of one commitment); commit_stride 0 = ONE commitment for every job.
+ * row_fr: B x (degree+1) x 32 B LE.  The rows of a failed job with an invalid commitment are the identity's encoding. */
+int tc_dkg_verify_rows_batch(tc_ctx* ctx, const uint8_t* commits, size_t commit_stride, size_t degree, const uint64_t* xs,
+                             const uint8_t* row_fr, size_t B, uint8_t* out_rows, uint8_t* ok);
+/* `bi_commit.evaluate(m, s) == g1 * val`, src/poly.rs:846-848, with evaluate(m, s) = row(m).evaluate(s) (:694-710,
+ * :497-508), for B parts of n values each.  Job j holds the row commitment rows[j] ((degree+1) x 96 B, e.g. out_rows
+ * above): ok[j*n + k] = 1 iff Commitment(rows[j]).evaluate(xs[j*n + k]) == vals_fr[j*n + k] * g1.
+ * xs: B x n, vals_fr: B x n x 32 B LE, ok: B x n. */
+int tc_dkg_verify_values_batch(tc_ctx* ctx, const uint8_t* rows, size_t degree, const uint64_t* xs, const uint8_t* vals_fr,
+                               size_t n, size_t B, uint8_t* ok);
+/* The same ok[] by ONE random linear combination per part (opt-in).  With rho_{j,k} = the first two words of
+ * ChaCha20(seed32, block counter j*n + k), low bit set (2^63 equally likely values, pairwise distinct mod r) job j passes
+ * -- ok = 1 for all its n values -- when
+ *     sum_i (sum_k rho_{j,k} xs_{j,k}^i) * rows[j][i]  -  (sum_k rho_{j,k} vals_{j,k}) * g1  ==  0      (0^0 = 1)
+ * which is one G1 linear combination of degree+2 points instead of n Horner chains and n fixed-base multiplications.
+ * A job that does not pass -- or holds a non-canonical value or an invalid point -- is re-checked value by value, so its
+ * ok[] is tc_dkg_verify_values_batch's; *n_fallback (optional, host) = the number of such jobs.  With rows[j] in G1 a job
+ * holding a wrong value passes with probability <= 2^-63; with input checks off the bound assumes members, as for the
+ * other combined entries.  seed32: 32 secret random bytes in HOST memory in both I/O modes, drawn after the values were
+ * received. */
+int tc_dkg_verify_values_rlc_batch(tc_ctx* ctx, const uint8_t* rows, size_t degree, const uint64_t* xs, const uint8_t* vals_fr,
+                                   size_t n, size_t B, const uint8_t* seed32, uint8_t* ok, uint64_t* n_fallback);
+
 /* ---- membership tests ------------------------------------------------------------------------ */
 /* ok[j] = 1 iff pts[j] decodes (range, flags, curve equation) and lies in the order-r subgroup: the
  * CHECKED half of `into_affine` (from_bytes, src/lib.rs:140-146, 246-252) for values that arrive

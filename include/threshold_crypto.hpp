@@ -730,6 +730,108 @@ inline std::vector<G1Bytes> bivar_commitment_row(const std::vector<G1Bytes>& coe
   return res;
 }
 
+// ---- DKG verification: the secret side and the two checks of distributed_key_generation (src/poly.rs:838-878) ----
+// Poly::evaluate (src/poly.rs:358-369) for B polynomials of n coefficients each at M shared abscissae: out[j][m]
+inline std::vector<std::vector<FrBytes>> fr_poly_evaluate(const std::vector<std::vector<FrBytes>>& polys, const std::vector<FrBytes>& xs,
+                                                          Engine& e = Engine::instance()) {
+  const std::size_t B = polys.size(), M = xs.size(), n = B ? polys[0].size() : 0;
+  std::vector<std::uint8_t> c(B * n * 32 + 1), x(M * 32 + 1), out(B * M * 32 + 1), st(B * M + 1);
+  for (std::size_t j = 0; j < B; j++) {
+    if (polys[j].size() != n) throw std::invalid_argument("all polynomials of one batch hold the same number of coefficients");
+    for (std::size_t k = 0; k < n; k++) std::memcpy(&c[(j * n + k) * 32], polys[j][k].data(), 32);
+  }
+  for (std::size_t m = 0; m < M; m++) std::memcpy(&x[m * 32], xs[m].data(), 32);
+  if (B && M) e.check(tc_fr_poly_evaluate_batch(e.ctx(), c.data(), n, x.data(), M, B, out.data(), st.data()));
+  std::vector<std::vector<FrBytes>> res(B, std::vector<FrBytes>(M));
+  for (std::size_t j = 0; j < B; j++)
+    for (std::size_t m = 0; m < M; m++) {
+      raise_status(st[j * M + m]);
+      std::memcpy(res[j][m].data(), &out[(j * M + m) * 32], 32);
+    }
+  return res;
+}
+// BivarPoly::row (src/poly.rs:607-622) for several u64 abscissae: coeff holds the (degree+1)(degree+2)/2 coefficients in
+// coeff_pos order; out[m] = the degree+1 coefficients of row(xs[m])
+inline std::vector<std::vector<FrBytes>> bivar_poly_rows(const std::vector<FrBytes>& coeff, std::size_t degree, const std::vector<std::uint64_t>& xs,
+                                                         Engine& e = Engine::instance()) {
+  if (coeff.size() != (degree + 1) * (degree + 2) / 2) throw std::invalid_argument("bivariate polynomial size");
+  const std::size_t M = xs.size(), n = degree + 1;
+  std::vector<std::uint8_t> c(coeff.size() * 32), out(M * n * 32 + 1), st(M * n + 1);
+  for (std::size_t i = 0; i < coeff.size(); i++) std::memcpy(&c[i * 32], coeff[i].data(), 32);
+  if (M) e.check(tc_bivar_poly_row_batch(e.ctx(), c.data(), degree, xs.data(), M, out.data(), st.data()));
+  std::vector<std::vector<FrBytes>> res(M, std::vector<FrBytes>(n));
+  for (std::size_t m = 0; m < M; m++)
+    for (std::size_t i = 0; i < n; i++) {
+      raise_status(st[m * n + i]);
+      std::memcpy(res[m][i].data(), &out[(m * n + i) * 32], 32);
+    }
+  return res;
+}
+// `row_poly.commitment() == bi_commit.row(m)` (src/poly.rs:841-843) for B parts: commits holds ONE bivariate commitment
+// (shared by every part) or one per part; rows_out (optional) receives the B row commitments
+inline std::vector<bool> dkg_verify_rows(const std::vector<std::vector<G1Bytes>>& commits, std::size_t degree, const std::vector<std::uint64_t>& xs,
+                                         const std::vector<std::vector<FrBytes>>& row_polys,
+                                         std::vector<std::vector<G1Bytes>>* rows_out = nullptr, Engine& e = Engine::instance()) {
+  const std::size_t B = xs.size(), n = degree + 1, nco = n * (n + 1) / 2;
+  if (row_polys.size() != B || (commits.size() != 1 && commits.size() != B)) throw std::invalid_argument("one row per abscissa, one commitment or one per abscissa");
+  std::vector<std::uint8_t> c(commits.size() * nco * 96 + 1), r(B * n * 32 + 1), rows(B * n * 96 + 1), ok(B + 1);
+  for (std::size_t j = 0; j < commits.size(); j++) {
+    if (commits[j].size() != nco) throw std::invalid_argument("bivariate commitment size");
+    for (std::size_t i = 0; i < nco; i++) std::memcpy(&c[(j * nco + i) * 96], commits[j][i].data(), 96);
+  }
+  for (std::size_t j = 0; j < B; j++) {
+    if (row_polys[j].size() != n) throw std::invalid_argument("a row polynomial holds degree+1 coefficients");
+    for (std::size_t i = 0; i < n; i++) std::memcpy(&r[(j * n + i) * 32], row_polys[j][i].data(), 32);
+  }
+  if (B) e.check(tc_dkg_verify_rows_batch(e.ctx(), c.data(), commits.size() == 1 ? 0 : nco * 96, degree, xs.data(), r.data(), B, rows.data(), ok.data()));
+  if (rows_out) {
+    rows_out->assign(B, std::vector<G1Bytes>(n));
+    for (std::size_t j = 0; j < B; j++)
+      for (std::size_t i = 0; i < n; i++) std::memcpy((*rows_out)[j][i].data(), &rows[(j * n + i) * 96], 96);
+  }
+  std::vector<bool> out(B);
+  for (std::size_t j = 0; j < B; j++) out[j] = ok[j] != 0;
+  return out;
+}
+// `bi_commit.evaluate(m, s) == g1 * val` (src/poly.rs:846-848) for B row commitments and n (abscissa, value) pairs each:
+// value by value (tc_dkg_verify_values_batch), or -- with a seed of 32 fresh secret random bytes -- by one random linear
+// combination per part (tc_dkg_verify_values_rlc_batch, opt-in; parts that fail are re-checked value by value)
+inline std::vector<std::vector<bool>> dkg_verify_values_impl(const std::vector<std::vector<G1Bytes>>& rows, const std::vector<std::vector<std::uint64_t>>& xs,
+                                                             const std::vector<std::vector<FrBytes>>& vals, const std::uint8_t* seed32,
+                                                             std::uint64_t* n_fallback, Engine& e) {
+  const std::size_t B = rows.size(), n = B ? xs.at(0).size() : 0, np = B ? rows[0].size() : 0;
+  if (xs.size() != B || vals.size() != B || (B && np == 0)) throw std::invalid_argument("one row commitment, abscissa list and value list per part");
+  std::vector<std::uint8_t> r(B * np * 96 + 1), v(B * n * 32 + 1), ok(B * n + 1);
+  std::vector<std::uint64_t> x(B * n + 1);
+  for (std::size_t j = 0; j < B; j++) {
+    if (rows[j].size() != np || xs[j].size() != n || vals[j].size() != n) throw std::invalid_argument("all parts of one batch have the same sizes");
+    for (std::size_t i = 0; i < np; i++) std::memcpy(&r[(j * np + i) * 96], rows[j][i].data(), 96);
+    for (std::size_t k = 0; k < n; k++) {
+      x[j * n + k] = xs[j][k];
+      std::memcpy(&v[(j * n + k) * 32], vals[j][k].data(), 32);
+    }
+  }
+  std::uint64_t nfb = 0;
+  if (B && n) {
+    if (seed32) e.check(tc_dkg_verify_values_rlc_batch(e.ctx(), r.data(), np - 1, x.data(), v.data(), n, B, seed32, ok.data(), &nfb));
+    else e.check(tc_dkg_verify_values_batch(e.ctx(), r.data(), np - 1, x.data(), v.data(), n, B, ok.data()));
+  }
+  if (n_fallback) *n_fallback = nfb;
+  std::vector<std::vector<bool>> out(B, std::vector<bool>(n));
+  for (std::size_t j = 0; j < B; j++)
+    for (std::size_t k = 0; k < n; k++) out[j][k] = ok[j * n + k] != 0;
+  return out;
+}
+inline std::vector<std::vector<bool>> dkg_verify_values(const std::vector<std::vector<G1Bytes>>& rows, const std::vector<std::vector<std::uint64_t>>& xs,
+                                                        const std::vector<std::vector<FrBytes>>& vals, Engine& e = Engine::instance()) {
+  return dkg_verify_values_impl(rows, xs, vals, nullptr, nullptr, e);
+}
+inline std::vector<std::vector<bool>> dkg_verify_values_rlc(const std::vector<std::vector<G1Bytes>>& rows, const std::vector<std::vector<std::uint64_t>>& xs,
+                                                            const std::vector<std::vector<FrBytes>>& vals, const std::array<std::uint8_t, 32>& seed,
+                                                            std::uint64_t* n_fallback = nullptr, Engine& e = Engine::instance()) {
+  return dkg_verify_values_impl(rows, xs, vals, seed.data(), n_fallback, e);
+}
+
 // Several GPUs of one node from this process (tc_group_*): contiguous job sharding, RCCL broadcast of the key set
 class Group {
  public:

@@ -1,5 +1,6 @@
 // gfx950 kernels: DKG algebra (tc_dkg.h) -- fixed-base commitments from an LDS-resident window table of the
-// G1 generator, rows of bivariate commitments, Fr interpolation.
+// G1 generator, rows of bivariate commitments, Fr interpolation, and the DKG verification kernels: Fr rows and values, the
+// per-job forms of the two G1 Horner kernels, the comparisons and the scalars of the combined values check.
 #include "tc_dkg.h"
 #include "tc_launch.h"
 
@@ -72,6 +73,151 @@ void launch_bivar_commitment_row(hipStream_t st, const uint8_t* commit, size_t d
 void launch_fr_interpolate(hipStream_t st, size_t n, const uint32_t* xs, const uint32_t* ys, size_t B, uint32_t* out, uint32_t* ws,
                            uint8_t* status) {
   if (B) hipLaunchKernelGGL(k_fr_interpolate, dim3(grid_for(B)), dim3(kBlock), 0, st, n, xs, ys, B, out, ws, status);
+}
+
+// ---- DKG verification (tc_dkg.h) ------------------------------------------------------------------------------
+// the secret side: every coefficient to Montgomery form ONCE, then one lane per output scalar
+__global__ __launch_bounds__(kBlock) void k_fr_to_mont(const uint8_t* __restrict__ fr, size_t count, uint32_t* __restrict__ mont,
+                                                       uint8_t* __restrict__ valid) {
+  const size_t t = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (t >= count) return;
+  valid[t] = fr_mont_from_le32(fr + t * 32, mont + t * 8) ? 1 : 0;
+}
+// sq[i][j] = coeff[pos(i, j)]: the symmetric matrix in full, so that row i is a contiguous polynomial
+__global__ __launch_bounds__(kBlock) void k_bivar_to_mont(const uint8_t* __restrict__ coeff, size_t degree, uint32_t* __restrict__ mont,
+                                                          uint8_t* __restrict__ valid) {
+  const size_t t = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  const size_t n = degree + 1;
+  if (t >= n * n) return;
+  valid[t] = fr_mont_from_le32(coeff + bivar_coeff_pos(t / n, t % n) * 32, mont + t * 8) ? 1 : 0;
+}
+// out[j * M + m] = Poly(coeff[j]).evaluate(xs[m])
+__global__ __launch_bounds__(kBlock) void k_fr_poly_evaluate(const uint32_t* __restrict__ coeff_mont, const uint8_t* __restrict__ coeff_valid,
+                                                             size_t n, const uint8_t* __restrict__ xs, size_t M, size_t B,
+                                                             uint8_t* __restrict__ out, uint8_t* __restrict__ status) {
+  const size_t t = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (t >= B * M) return;
+  const size_t j = t / M, m = t % M;
+  const uint8_t st = job_fr_poly_evaluate(coeff_mont + j * n * 8, coeff_valid + j * n, n, xs + m * 32, out + t * 32);
+  if (status) status[t] = st;
+}
+// out[m * (degree + 1) + i] = BivarPoly::row(xs[m])[i]
+__global__ __launch_bounds__(kBlock) void k_bivar_poly_row(const uint32_t* __restrict__ sq_mont, const uint8_t* __restrict__ sq_valid, size_t degree,
+                                                           const uint64_t* __restrict__ xs, size_t M, uint8_t* __restrict__ out,
+                                                           uint8_t* __restrict__ status) {
+  const size_t t = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  const size_t n = degree + 1;
+  if (t >= M * n) return;
+  const uint8_t st = job_bivar_poly_row(sq_mont, sq_valid, degree, t % n, xs[t / n], out + t * 32);
+  if (status) status[t] = st;
+}
+
+// k_bivar_commitment_row with one commitment and one abscissa PER JOB: out[j * (degree + 1) + i] = commit_j.row(xs[j])[i]
+__global__ __launch_bounds__(kBlock, TC_WAVES_G1_AUX) void k_bivar_commitment_row_jobs(const uint8_t* __restrict__ commits, size_t stride,
+                                                                                      size_t degree, const uint64_t* __restrict__ xs, size_t B,
+                                                                                      uint8_t* __restrict__ out, uint8_t* __restrict__ status) {
+  const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  const size_t n = degree + 1;
+  if (tid >= B * n) return;
+  const size_t j = tid / n, i = tid % n;
+  status[tid] = job_bivar_commitment_row(commits + j * stride, degree, i, xs[j], out + tid * 96);
+}
+// k_commitment_evaluate (k_hash.hip) with one commitment per job and the abscissa by value:
+// out[j * n + k] = Commitment(rows[j]).evaluate(xs[j * n + k])
+__global__ __launch_bounds__(kBlock, TC_WAVES_G1_AUX) void k_commitment_evaluate_jobs(const uint8_t* __restrict__ rows, size_t degree,
+                                                                                     const uint64_t* __restrict__ xs, size_t n, size_t B,
+                                                                                     uint8_t* __restrict__ out, uint8_t* __restrict__ status) {
+  const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (tid >= B * n) return;
+  status[tid] = job_commitment_evaluate_at(rows + (tid / n) * (degree + 1) * 96, degree, xs[tid], out + tid * 96);
+}
+// ok[j] = the per_job points of job j are the same group elements in a and b.  Both sides are this library's own canonical
+// encodings (the identity: 0x40 and zeros), so equal elements are equal bytes; a failed status on either side is "not equal".
+__global__ __launch_bounds__(kBlock) void k_g1_equal(const uint8_t* __restrict__ a, const uint8_t* __restrict__ st_a, const uint8_t* __restrict__ b,
+                                                     const uint8_t* __restrict__ st_b, size_t per_job, size_t B, uint8_t* __restrict__ ok) {
+  const size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (j >= B) return;
+  bool good = true;
+  for (size_t i = j * per_job; i < (j + 1) * per_job; i++) {
+    good = good && st_a[i] == TC_JOB_OK && st_b[i] == TC_JOB_OK;
+    const uint64_t* pa = reinterpret_cast<const uint64_t*>(a + i * 96);
+    const uint64_t* pb = reinterpret_cast<const uint64_t*>(b + i * 96);
+    for (int w = 0; w < 12; w++) good = good && pa[w] == pb[w];
+  }
+  ok[j] = good ? 1 : 0;
+}
+
+// the combined values check: one lane per scalar (job j, i = 0 .. degree + 1); the lane of c_g sees the values and owns valid[j]
+__global__ __launch_bounds__(kBlock) void k_dkg_rlc_scalars(const uint8_t* __restrict__ seed32, const uint64_t* __restrict__ xs,
+                                                            const uint8_t* __restrict__ vals, size_t n, size_t degree, size_t B,
+                                                            uint32_t* __restrict__ scalars, uint8_t* __restrict__ valid) {
+  const size_t t = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  const size_t per = degree + 2;
+  if (t >= B * per) return;
+  const size_t j = t / per, i = t % per;
+  uint32_t key[8];
+  for (int w = 0; w < 8; w++)
+    key[w] = (uint32_t)seed32[4 * w] | ((uint32_t)seed32[4 * w + 1] << 8) | ((uint32_t)seed32[4 * w + 2] << 16) | ((uint32_t)seed32[4 * w + 3] << 24);
+  const bool good = dkg_rlc_scalar(key, j, n, degree, xs + j * n, vals + j * n * 32, i, scalars + t * 8);
+  if (i == degree + 1) valid[j] = good ? 1 : 0;
+}
+// out[j] = rows[j] || g1, one 8-byte word per lane
+__global__ __launch_bounds__(kBlock) void k_dkg_rlc_points(const uint8_t* __restrict__ rows, size_t degree, const uint8_t* __restrict__ g1_gen, size_t B,
+                                                           uint8_t* __restrict__ out) {
+  const size_t t = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  const size_t row_words = (degree + 1) * 12, per = row_words + 12;
+  if (t >= B * per) return;
+  const size_t j = t / per, w = t % per;
+  reinterpret_cast<uint64_t*>(out)[t] = w < row_words ? reinterpret_cast<const uint64_t*>(rows)[j * row_words + w]
+                                                      : reinterpret_cast<const uint64_t*>(g1_gen)[w - row_words];
+}
+__global__ __launch_bounds__(kBlock) void k_g1_is_identity(const uint8_t* __restrict__ pts, const uint8_t* __restrict__ status,
+                                                           const uint8_t* __restrict__ valid, size_t B, uint8_t* __restrict__ ok) {
+  const size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (j >= B) return;
+  ok[j] = (status[j] == TC_JOB_OK && valid[j] != 0 && (pts[j * 96] & 0x40) != 0) ? 1 : 0;
+}
+
+void launch_fr_to_mont(hipStream_t st, const uint8_t* fr, size_t count, uint32_t* mont, uint8_t* valid) {
+  if (count) hipLaunchKernelGGL(k_fr_to_mont, dim3(grid_for(count)), dim3(kBlock), 0, st, fr, count, mont, valid);
+}
+void launch_bivar_to_mont(hipStream_t st, const uint8_t* coeff_fr, size_t degree, uint32_t* mont, uint8_t* valid) {
+  const size_t n = (degree + 1) * (degree + 1);
+  hipLaunchKernelGGL(k_bivar_to_mont, dim3(grid_for(n)), dim3(kBlock), 0, st, coeff_fr, degree, mont, valid);
+}
+void launch_fr_poly_evaluate(hipStream_t st, const uint32_t* coeff_mont, const uint8_t* coeff_valid, size_t n, const uint8_t* xs_fr, size_t M,
+                             size_t B, uint8_t* out_fr, uint8_t* status) {
+  if (B * M) hipLaunchKernelGGL(k_fr_poly_evaluate, dim3(grid_for(B * M)), dim3(kBlock), 0, st, coeff_mont, coeff_valid, n, xs_fr, M, B, out_fr, status);
+}
+void launch_bivar_poly_row(hipStream_t st, const uint32_t* sq_mont, const uint8_t* sq_valid, size_t degree, const uint64_t* xs, size_t M,
+                           uint8_t* out_fr, uint8_t* status) {
+  const size_t n = M * (degree + 1);
+  if (n) hipLaunchKernelGGL(k_bivar_poly_row, dim3(grid_for(n)), dim3(kBlock), 0, st, sq_mont, sq_valid, degree, xs, M, out_fr, status);
+}
+void launch_bivar_commitment_row_jobs(hipStream_t st, const uint8_t* commits, size_t stride, size_t degree, const uint64_t* xs, size_t B,
+                                      uint8_t* out, uint8_t* status) {
+  const size_t n = B * (degree + 1);
+  if (n) hipLaunchKernelGGL(k_bivar_commitment_row_jobs, dim3(grid_for(n)), dim3(kBlock), 0, st, commits, stride, degree, xs, B, out, status);
+}
+void launch_commitment_evaluate_jobs(hipStream_t st, const uint8_t* rows, size_t degree, const uint64_t* xs, size_t n, size_t B, uint8_t* out,
+                                     uint8_t* status) {
+  if (B * n) hipLaunchKernelGGL(k_commitment_evaluate_jobs, dim3(grid_for(B * n)), dim3(kBlock), 0, st, rows, degree, xs, n, B, out, status);
+}
+void launch_g1_equal(hipStream_t st, const uint8_t* a, const uint8_t* st_a, const uint8_t* b, const uint8_t* st_b, size_t per_job, size_t B,
+                     uint8_t* ok) {
+  if (B) hipLaunchKernelGGL(k_g1_equal, dim3(grid_for(B)), dim3(kBlock), 0, st, a, st_a, b, st_b, per_job, B, ok);
+}
+void launch_dkg_rlc_scalars(hipStream_t st, const uint8_t* seed32, const uint64_t* xs, const uint8_t* vals_fr, size_t n, size_t degree, size_t B,
+                            uint32_t* scalars, uint8_t* valid) {
+  const size_t lanes = B * (degree + 2);
+  if (lanes) hipLaunchKernelGGL(k_dkg_rlc_scalars, dim3(grid_for(lanes)), dim3(kBlock), 0, st, seed32, xs, vals_fr, n, degree, B, scalars, valid);
+}
+void launch_dkg_rlc_points(hipStream_t st, const uint8_t* rows, size_t degree, const uint8_t* g1_gen, size_t B, uint8_t* out) {
+  const size_t words = B * (degree + 2) * 12;
+  if (words) hipLaunchKernelGGL(k_dkg_rlc_points, dim3(grid_for(words)), dim3(kBlock), 0, st, rows, degree, g1_gen, B, out);
+}
+void launch_g1_is_identity(hipStream_t st, const uint8_t* pts, const uint8_t* status, const uint8_t* valid, size_t B, uint8_t* ok) {
+  if (B) hipLaunchKernelGGL(k_g1_is_identity, dim3(grid_for(B)), dim3(kBlock), 0, st, pts, status, valid, B, ok);
 }
 
 }  // namespace tc

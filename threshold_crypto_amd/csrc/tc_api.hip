@@ -1889,6 +1889,231 @@ int tc_fr_interpolate_batch(tc_ctx* ctx, size_t n, const uint8_t* xs, const uint
   return on_exception((tc_ctx*)ctx);
 }
 
+// ---- DKG verification: the secret side and the two checks of distributed_key_generation (src/poly.rs:838-878) ----------
+// the fixed-base window table of the G1 generator, built by the first call that multiplies by it
+static void need_fixed_base_table(Call& k) {
+  tc_ctx* ctx = k.c;
+  if (ctx->fb_table || k.failed) return;
+  if (k.check(hipMalloc((void**)&ctx->fb_table, tc::fixed_base_table_bytes()), "hipMalloc"))
+    tc::launch_fixed_base_table(ctx->stream, ctx->fb_table);
+  else
+    ctx->fb_table = nullptr;
+}
+
+int tc_fr_poly_evaluate_batch(tc_ctx* ctx, const uint8_t* coeff_fr, size_t n, const uint8_t* xs_fr, size_t M, size_t B, uint8_t* out_fr,
+                              uint8_t* status) try {
+  TC_REQUIRE(ctx);
+  if (B == 0 || M == 0) return TC_OK;
+  TC_REQUIRE(ctx && xs_fr && out_fr && (n == 0 || coeff_fr));
+  TC_REQUIRE(n < (1u << 20) && B * M < (1ull << 40));
+  Call k(ctx);
+  const uint8_t* d_c = k.in(coeff_fr, B * n * 32, /*secret=*/true);
+  const uint8_t* d_x = k.in(xs_fr, M * 32);
+  uint8_t* d_out = k.out(out_fr, B * M * 32);
+  // host-I/O mode: the (secret) values pass through a staging slot that outlives the call: wiped after the copy back
+  if (d_out && !ctx->device_io) k.wipe_after_copy.emplace_back(d_out, B * M * 32);
+  uint8_t* d_st = k.out(status, B * M);
+  uint32_t* d_mont = k.temp<uint32_t>(B * n * 8);
+  if (d_mont) k.wipe.emplace_back(d_mont, B * n * 8 * sizeof(uint32_t));
+  uint8_t* d_valid = k.temp<uint8_t>(B * n);
+  k.begin_timing();
+  if (!k.failed) {
+    tc::launch_fr_to_mont(ctx->stream, d_c, B * n, d_mont, d_valid);
+    tc::launch_fr_poly_evaluate(ctx->stream, d_mont, d_valid, n, d_x, M, B, d_out, d_st);
+  }
+  k.end_timing();
+  return k.finish();
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+int tc_bivar_poly_row_batch(tc_ctx* ctx, const uint8_t* coeff_fr, size_t degree, const uint64_t* xs, size_t M, uint8_t* out_fr,
+                            uint8_t* status) try {
+  TC_REQUIRE(ctx);
+  if (M == 0) return TC_OK;
+  TC_REQUIRE(ctx && coeff_fr && xs && out_fr);
+  TC_REQUIRE(degree < (1u << 12));
+  const size_t n = degree + 1, ncoeff = n * (n + 1) / 2;
+  Call k(ctx);
+  const uint8_t* d_c = k.in(coeff_fr, ncoeff * 32, /*secret=*/true);
+  const uint64_t* d_x = k.in(xs, M);
+  uint8_t* d_out = k.out(out_fr, M * n * 32);
+  if (d_out && !ctx->device_io) k.wipe_after_copy.emplace_back(d_out, M * n * 32);
+  uint8_t* d_st = k.out(status, M * n);
+  uint32_t* d_mont = k.temp<uint32_t>(n * n * 8);
+  if (d_mont) k.wipe.emplace_back(d_mont, n * n * 8 * sizeof(uint32_t));
+  uint8_t* d_valid = k.temp<uint8_t>(n * n);
+  k.begin_timing();
+  if (!k.failed) {
+    tc::launch_bivar_to_mont(ctx->stream, d_c, degree, d_mont, d_valid);
+    tc::launch_bivar_poly_row(ctx->stream, d_mont, d_valid, degree, d_x, M, d_out, d_st);
+  }
+  k.end_timing();
+  return k.finish();
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+int tc_dkg_verify_rows_batch(tc_ctx* ctx, const uint8_t* commits, size_t commit_stride, size_t degree, const uint64_t* xs,
+                             const uint8_t* row_fr, size_t B, uint8_t* out_rows, uint8_t* ok) try {
+  TC_REQUIRE(ctx);
+  if (B == 0) return TC_OK;
+  TC_REQUIRE(ctx && commits && xs && row_fr && ok);
+  TC_REQUIRE(degree < (1u << 12));
+  const size_t n = degree + 1, ncoeff = n * (n + 1) / 2;
+  TC_REQUIRE(commit_stride == 0 || (commit_stride % 96 == 0 && commit_stride >= ncoeff * 96));
+  TC_REQUIRE(B * n < (1ull << 32));
+  Call k(ctx);
+  need_fixed_base_table(k);
+  const uint8_t* d_c = k.in(commits, commit_stride ? (B - 1) * commit_stride + ncoeff * 96 : ncoeff * 96);
+  const uint64_t* d_x = k.in(xs, B);
+  const uint8_t* d_row = k.in(row_fr, B * n * 32, /*secret=*/true);
+  uint8_t* d_R = out_rows ? k.out(out_rows, B * n * 96) : k.temp<uint8_t>(B * n * 96);
+  uint8_t* d_ok = k.out(ok, B);
+  uint8_t* d_G = k.temp<uint8_t>(B * n * 96);
+  uint8_t* d_st = k.temp<uint8_t>(2 * B * n);
+  k.begin_timing();
+  // (job j * n + i of the row kernel owns commitment j: `group` = n row points per record)
+  if (commit_stride) k.check_points(false, d_c, 96, commit_stride / 96, ncoeff, B, n);
+  else k.check_points(false, d_c, 96, ncoeff, ncoeff, 1, (size_t)-1);
+  if (!k.failed) {
+    tc::launch_bivar_commitment_row_jobs(ctx->stream, d_c, commit_stride, degree, d_x, B, d_R, d_st);
+    tc::launch_g1_fixed_base(ctx->stream, ctx->fb_table, d_row, B * n, d_G, d_st + B * n, ctx->cus);
+  }
+  k.apply_checks(B * n, d_st, d_R, 96, nullptr);
+  if (!k.failed) tc::launch_g1_equal(ctx->stream, d_R, d_st, d_G, d_st + B * n, n, B, d_ok);
+  k.end_timing();
+  return k.finish();
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+// ok[j * n + k] = Commitment(rows[j]).evaluate(xs[j * n + k]) == vals[j * n + k] * g1 on device operands: the exact form, and the
+// per-value pass of the combined form's failed jobs.  `checked`: the row points are tested for membership here (the compacted
+// operands of a fallback; the exact entry registers its operands with Call::check_points instead)
+static void dkg_values_exact(Call& k, const uint8_t* d_rows, size_t degree, const uint64_t* d_x, const uint8_t* d_vals, size_t n, size_t B,
+                             uint8_t* d_ok, bool checked) {
+  tc_ctx* ctx = k.c;
+  const size_t V = B * n;
+  uint8_t* d_E = k.temp<uint8_t>(V * 96);
+  uint8_t* d_G = k.temp<uint8_t>(V * 96);
+  uint8_t* d_st = k.temp<uint8_t>(2 * V);
+  uint8_t* d_member = checked ? k.temp<uint8_t>(B * (degree + 1)) : nullptr;
+  if (k.failed) return;
+  tc::launch_commitment_evaluate_jobs(ctx->stream, d_rows, degree, d_x, n, B, d_E, d_st);
+  tc::launch_g1_fixed_base(ctx->stream, ctx->fb_table, d_vals, V, d_G, d_st + V, ctx->cus);
+  tc::launch_g1_equal(ctx->stream, d_E, d_st, d_G, d_st + V, 1, V, d_ok);
+  if (checked) {
+    tc::launch_subgroup_check_g1(ctx->stream, d_rows, 96, degree + 1, degree + 1, B * (degree + 1), d_member);
+    tc::launch_invalidate_jobs(ctx->stream, d_member, degree + 1, n, V, nullptr, nullptr, 0, d_ok);
+  }
+}
+
+int tc_dkg_verify_values_batch(tc_ctx* ctx, const uint8_t* rows, size_t degree, const uint64_t* xs, const uint8_t* vals_fr, size_t n,
+                               size_t B, uint8_t* ok) try {
+  TC_REQUIRE(ctx);
+  if (B == 0 || n == 0) return TC_OK;
+  TC_REQUIRE(ctx && rows && xs && vals_fr && ok);
+  TC_REQUIRE(degree < (1u << 20) && B * n < (1ull << 32));
+  Call k(ctx);
+  need_fixed_base_table(k);
+  const uint8_t* d_rows = k.in(rows, B * (degree + 1) * 96);
+  const uint64_t* d_x = k.in(xs, B * n);
+  const uint8_t* d_vals = k.in(vals_fr, B * n * 32, /*secret=*/true);
+  uint8_t* d_ok = k.out(ok, B * n);
+  k.begin_timing();
+  k.check_points(false, d_rows, 96, degree + 1, degree + 1, B, n);  // value j * n + k owns row commitment j
+  dkg_values_exact(k, d_rows, degree, d_x, d_vals, n, B, d_ok, /*checked=*/false);
+  k.apply_checks(B * n, nullptr, nullptr, 0, d_ok);
+  k.end_timing();
+  return k.finish();
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+// The n value checks of a part by ONE G1 linear combination of degree + 2 points (tc_dkg.h dkg_rlc_scalar): the scalars
+// c_0 .. c_degree, c_g of every job, the points R_j || g1, the existing linear-combination kernels, an is-identity test; jobs
+// that do not pass run the exact kernels on compacted operands, as the fallbacks of the other combined entries do.
+int tc_dkg_verify_values_rlc_batch(tc_ctx* ctx, const uint8_t* rows, size_t degree, const uint64_t* xs, const uint8_t* vals_fr, size_t n,
+                                   size_t B, const uint8_t* seed32, uint8_t* ok, uint64_t* n_fallback) try {
+  TC_REQUIRE(ctx);
+  if (n_fallback) *n_fallback = 0;
+  if (B == 0 || n == 0) return TC_OK;
+  TC_REQUIRE(ctx && rows && xs && vals_fr && seed32 && ok);
+  TC_REQUIRE(degree < (1u << 20) && B * n < (1ull << 32) && B * (degree + 2) < (1ull << 32));
+  const size_t np = degree + 2, row_bytes = (degree + 1) * 96;
+  Call k(ctx);
+  need_fixed_base_table(k);
+  const uint8_t* d_rows = k.in(rows, B * row_bytes);
+  const uint64_t* d_x = k.in(xs, B * n);
+  const uint8_t* d_vals = k.in(vals_fr, B * n * 32, /*secret=*/true);
+  // the seed is host memory in both I/O modes (32 bytes; it must stay secret until the call returns)
+  uint8_t* d_seed = k.temp<uint8_t>(32);
+  if (d_seed) {
+    k.check(hipMemcpyAsync(d_seed, seed32, 32, hipMemcpyHostToDevice, ctx->stream), "seed copy");
+    ctx->h2d_bytes += 32;
+    k.wipe.emplace_back(d_seed, 32);
+  }
+  uint32_t* d_sc = k.temp<uint32_t>(B * np * 8);
+  if (d_sc) k.wipe.emplace_back(d_sc, B * np * 8 * sizeof(uint32_t));
+  uint8_t* d_pts = k.temp<uint8_t>(B * np * 96);
+  uint8_t* d_sum = k.temp<uint8_t>(B * 96);
+  uint8_t* d_st = k.temp<uint8_t>(B);
+  uint8_t* d_valid = k.temp<uint8_t>(B);
+  uint8_t* d_okjob = k.temp<uint8_t>(B);
+  uint8_t* d_ok = k.out(ok, B * n);
+  k.begin_timing();
+  k.check_points(false, d_rows, 96, degree + 1, degree + 1, B, 1);
+  std::vector<uint8_t> h_okjob(B);
+  if (!k.failed) {
+    tc::launch_dkg_rlc_scalars(ctx->stream, d_seed, d_x, d_vals, n, degree, B, d_sc, d_valid);
+    tc::launch_dkg_rlc_points(ctx->stream, d_rows, degree, ctx->g1_gen, B, d_pts);
+    k.check(hipMemsetAsync(d_st, 0, B, ctx->stream), "memset");
+    if (np >= tc::kMsmMinPoints) msm_g1(k, np, np * 96, d_pts, d_sc, B, d_sum, d_st, 128, /*secret_scalars=*/true);
+    else tc::launch_lincomb_g1(ctx->stream, np, reinterpret_cast<const uint8_t*>(d_sc), d_pts, B, d_sum, d_st);
+    tc::launch_g1_is_identity(ctx->stream, d_sum, d_st, d_valid, B, d_okjob);
+    // checked-input mode: a job owning a non-member row point falls back (and fails there)
+    k.apply_checks(B, nullptr, nullptr, 0, d_okjob);
+    k.check(hipMemsetAsync(d_ok, 1, B * n, ctx->stream), "memset");
+    k.check(hipMemcpyAsync(h_okjob.data(), d_okjob, B, hipMemcpyDeviceToHost, ctx->stream), "ok readback");
+    ctx->d2h_bytes += B;
+    k.check(hipStreamSynchronize(ctx->stream), "stream sync");
+    std::vector<uint32_t> failed;
+    if (!k.failed)
+      for (size_t j = 0; j < B; j++)
+        if (!h_okjob[j]) failed.push_back((uint32_t)j);
+    if (!k.failed && !failed.empty()) {
+      // the exact kernels for every value of the failed jobs, on compacted operands
+      const size_t F = failed.size(), R = F * n;
+      std::vector<uint32_t> m_val(R);
+      for (size_t f = 0; f < F; f++)
+        for (size_t i = 0; i < n; i++) m_val[f * n + i] = (uint32_t)(failed[f] * n + i);
+      uint32_t* d_maps = k.temp<uint32_t>(F + R);
+      uint8_t* c_rows = k.temp<uint8_t>(F * row_bytes);
+      uint64_t* c_x = k.temp<uint64_t>(R);
+      uint8_t* c_vals = k.temp<uint8_t>(R * 32);
+      if (c_vals) k.wipe.emplace_back(c_vals, R * 32);
+      uint8_t* c_ok = k.temp<uint8_t>(R);
+      if (!k.failed) {
+        k.check(hipMemcpyAsync(d_maps, failed.data(), F * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
+        k.check(hipMemcpyAsync(d_maps + F, m_val.data(), R * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
+        ctx->h2d_bytes += 4 * (F + R);
+        tc::launch_gather_rows(ctx->stream, d_rows, row_bytes, d_maps, F, c_rows);
+        tc::launch_gather_rows(ctx->stream, reinterpret_cast<const uint8_t*>(d_x), n * 8, d_maps, F, reinterpret_cast<uint8_t*>(c_x));
+        tc::launch_gather_rows(ctx->stream, d_vals, n * 32, d_maps, F, c_vals);
+        dkg_values_exact(k, c_rows, degree, c_x, c_vals, n, F, c_ok, /*checked=*/ctx->input_checks);
+        if (!k.failed) tc::launch_scatter_bytes(ctx->stream, c_ok, d_maps + F, R, d_ok);
+        k.check(hipStreamSynchronize(ctx->stream), "stream sync");  // the host maps go out of scope
+      }
+      if (n_fallback) *n_fallback = F;
+    }
+  }
+  k.end_timing();
+  return k.finish();
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
 // ---- membership tests ---------------------------------------------------------------------------
 static int subgroup_check(tc_ctx* ctx, bool g2, const uint8_t* pts, size_t B, uint8_t* ok) {
   TC_REQUIRE(ctx);

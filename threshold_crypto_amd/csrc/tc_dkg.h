@@ -170,4 +170,115 @@ TC_HD uint8_t job_fr_interpolate(size_t n, const uint32_t* xs, const uint32_t* y
   return dup ? TC_JOB_DUPLICATE_ENTRY : TC_JOB_OK;
 }
 
+// ---- DKG verification: the secret side in Fr ------------------------------------------------------------------
+// Poly::evaluate (src/poly.rs:358-369) and BivarPoly::row (:607-622), one output scalar per call; the coefficients have
+// been brought to Montgomery form once (fr_mont_from_le32), with one validity byte each.
+// 32 B LE -> Montgomery words; a non-canonical value (>= r) gives zero and false
+TC_HD bool fr_mont_from_le32(const uint8_t* le32, uint32_t* mont8) {
+  uint32_t k[8];
+  const bool ok = fr_from_le32(le32, k);
+  const Fr v = ok ? Fr::from_canonical(k) : Fr::zero();
+  TC_UNROLL for (int i = 0; i < 8; i++) mont8[i] = v.v.l[i];
+  return ok;
+}
+TC_HD void fr_store_le32(const Fr& v, uint8_t* out32) {
+  uint32_t w[8];
+  v.to_canonical(w);
+  TC_UNROLL for (int i = 0; i < 8; i++) {
+    out32[4 * i] = (uint8_t)w[i];
+    out32[4 * i + 1] = (uint8_t)(w[i] >> 8);
+    out32[4 * i + 2] = (uint8_t)(w[i] >> 16);
+    out32[4 * i + 3] = (uint8_t)(w[i] >> 24);
+  }
+}
+// out = sum_k coeff[k] x^k (n = 0: the zero polynomial); fails -- zero output -- on a non-canonical coefficient or abscissa
+TC_HD uint8_t job_fr_poly_evaluate(const uint32_t* coeff_mont, const uint8_t* coeff_valid, size_t n, const uint8_t* x_le32, uint8_t* out32) {
+  uint32_t xw[8];
+  bool ok = fr_from_le32(x_le32, xw);
+  TC_NOUNROLL for (size_t k = 0; k < n; k++) ok &= coeff_valid[k] != 0;
+  const Fr r = ok ? fr_horner(coeff_mont, n, Fr::from_canonical(xw)) : Fr::zero();
+  fr_store_le32(r, out32);
+  return ok ? TC_JOB_OK : TC_JOB_INVALID_ENCODING;
+}
+// out = row(x)[i] = sum_j coeff[pos(i, j)] x^j over the (degree+1)^2 matrix sq[i][j] = coeff[pos(i, j)] (Montgomery form)
+TC_HD uint8_t job_bivar_poly_row(const uint32_t* sq_mont, const uint8_t* sq_valid, size_t degree, size_t i, uint64_t x, uint8_t* out32) {
+  const size_t n = degree + 1;
+  bool ok = true;
+  TC_NOUNROLL for (size_t j = 0; j < n; j++) ok &= sq_valid[i * n + j] != 0;
+  const Fr r = ok ? fr_horner(sq_mont + i * n * 8, n, fr_from_u64(x)) : Fr::zero();
+  fr_store_le32(r, out32);
+  return ok ? TC_JOB_OK : TC_JOB_INVALID_ENCODING;
+}
+
+// Commitment::evaluate(x) (src/poly.rs:497-508) at the u64 abscissa x BY VALUE -- 0 and 2^64 - 1 included; the idx + 1
+// form is job_commitment_evaluate (tc_jobs.h) -- Horner in G1 from the top coefficient down
+TC_HD uint8_t job_commitment_evaluate_at(const uint8_t* commit, size_t degree, uint64_t x, uint8_t* out96) {
+  G1Affine c;
+  bool ok = g1_decode_uncompressed(commit + degree * 96, c);
+  G1Jac res = G1Jac::from_affine(c);
+  TC_NOUNROLL for (size_t kk = degree; kk-- > 0;) {
+    G1Jac scaled = g1_mul_u64(res, x);
+    ok &= g1_decode_uncompressed(commit + kk * 96, c);
+    res = jac_add_mixed(scaled, c);
+  }
+  if (!ok) {
+    g1_encode_uncompressed(G1Affine::infinity(), out96);
+    return TC_JOB_INVALID_ENCODING;
+  }
+  g1_encode_uncompressed(jac_to_affine(res), out96);
+  return TC_JOB_OK;
+}
+
+// ---- the combined values check (tc_dkg_verify_values_rlc_batch) -------------------------------------------------
+// The n checks  R.evaluate(x_k) == v_k g1  of one part (R: its row commitment, degree+1 points) hold iff, up to 2^-63,
+//     sum_i c_i R_i + c_g g1 == 0,     c_i = sum_k rho_k x_k^i  (0^0 = 1),     c_g = - sum_k rho_k v_k
+// for secret rho_k: the sum is sum_k rho_k (R.evaluate(x_k) - v_k g1), and a non-zero combination of elements of a group of
+// prime order r with coefficients drawn from 2^63 values that are pairwise distinct mod r vanishes with probability <= 2^-63.
+// rho_{j,k}: the first two words of ChaCha20(key, block counter j n + k) with the low bit set
+TC_HD uint64_t dkg_rlc_rho(const uint32_t* key8, uint64_t counter) {
+  ChaChaRng rng;
+  rng.init(key8);
+  rng.counter = counter;
+  const uint32_t w0 = rng.next_u32(), w1 = rng.next_u32();
+  return ((uint64_t)w1 << 32) | (uint64_t)(w0 | 1u);
+}
+// scalar i of job j as 8 canonical words: c_i for i <= degree, c_g for i = degree + 1 (false, and zero, when one of the
+// values is not canonical).  xs, vals: the job's own n abscissae and n x 32 B LE values
+TC_HD bool dkg_rlc_scalar(const uint32_t* key8, size_t j, size_t n, size_t degree, const uint64_t* xs, const uint8_t* vals, size_t i,
+                          uint32_t* out8) {
+  Fr acc = Fr::zero();
+  bool ok = true;
+  int top = 0;  // the highest set bit of the exponent
+  TC_NOUNROLL for (int bit = 1; bit < 64; bit++)
+    if ((i >> bit) & 1) top = bit;
+  TC_NOUNROLL for (size_t k = 0; k < n; k++) {
+    const Fr rho = fr_from_u64(dkg_rlc_rho(key8, (uint64_t)j * n + k));
+    Fr term;
+    if (i > degree) {
+      uint32_t v[8];
+      ok &= fr_from_le32(vals + k * 32, v);
+      term = Fr::from_canonical(v);
+    } else {
+      // x_k^i, left-to-right square and multiply (i = 0: one)
+      const Fr x = fr_from_u64(xs[k]);
+      term = Fr::one();
+      TC_NOUNROLL for (int bit = top; bit >= 0; bit--) {
+        term = term.sqr();
+        if ((i >> bit) & 1) term = term * x;
+      }
+    }
+    acc = acc + rho * term;
+  }
+  if (i > degree) acc = Fr::zero() - acc;
+  if (!ok) acc = Fr::zero();
+  acc.to_canonical(out8);
+  return ok;
+}
+// the degree + 2 scalars of job j (out: (degree+2) x 8 words); false when a value is not canonical
+TC_HD bool job_dkg_rlc_scalars(const uint32_t* key8, size_t j, size_t n, size_t degree, const uint64_t* xs, const uint8_t* vals, uint32_t* out) {
+  bool ok = true;
+  TC_NOUNROLL for (size_t i = 0; i <= degree + 1; i++) ok &= dkg_rlc_scalar(key8, j, n, degree, xs, vals, i, out + i * 8);
+  return ok;
+}
+
 }  // namespace tc

@@ -220,6 +220,30 @@ void launch_bivar_commitment_row(hipStream_t st, const uint8_t* commit, size_t d
                                  uint8_t* status);
 void launch_fr_interpolate(hipStream_t st, size_t n, const uint32_t* xs, const uint32_t* ys, size_t B, uint32_t* out, uint32_t* ws,
                            uint8_t* status);
+// DKG verification (k_dkg.hip).  The secret side: coefficients to Montgomery form once (mont: count x 8 words, valid: count
+// bytes; the bivariate form expands the (degree+1)(degree+2)/2 coefficients to the full symmetric (degree+1)^2 matrix so
+// that every row is contiguous), then one lane per output scalar.
+void launch_fr_to_mont(hipStream_t st, const uint8_t* fr, size_t count, uint32_t* mont, uint8_t* valid);
+void launch_bivar_to_mont(hipStream_t st, const uint8_t* coeff_fr, size_t degree, uint32_t* mont, uint8_t* valid);
+void launch_fr_poly_evaluate(hipStream_t st, const uint32_t* coeff_mont, const uint8_t* coeff_valid, size_t n, const uint8_t* xs_fr, size_t M,
+                             size_t B, uint8_t* out_fr, uint8_t* status);
+void launch_bivar_poly_row(hipStream_t st, const uint32_t* sq_mont, const uint8_t* sq_valid, size_t degree, const uint64_t* xs, size_t M,
+                           uint8_t* out_fr, uint8_t* status);
+// the per-job forms of the two G1 Horner kernels: job j's commitment at commits + j * stride (stride 0: one for all) and its
+// one abscissa xs[j]; job j's row commitment at rows + j * (degree+1) * 96 and its n abscissae xs[j*n ..], taken by value
+void launch_bivar_commitment_row_jobs(hipStream_t st, const uint8_t* commits, size_t stride, size_t degree, const uint64_t* xs, size_t B,
+                                      uint8_t* out, uint8_t* status);
+void launch_commitment_evaluate_jobs(hipStream_t st, const uint8_t* rows, size_t degree, const uint64_t* xs, size_t n, size_t B, uint8_t* out,
+                                     uint8_t* status);
+// ok[j] = every one of the per_job points of job j is the same group element in a and b, and all their status bytes are OK
+void launch_g1_equal(hipStream_t st, const uint8_t* a, const uint8_t* st_a, const uint8_t* b, const uint8_t* st_b, size_t per_job, size_t B,
+                     uint8_t* ok);
+// the combined values check: scalars (B x (degree+2) x 8 canonical words; valid: B bytes, 0 = a non-canonical value) from
+// tc_dkg.h dkg_rlc_scalar, the points R_j || g1 (B x (degree+2) x 96), and ok[j] = status OK, valid and the sum the identity
+void launch_dkg_rlc_scalars(hipStream_t st, const uint8_t* seed32, const uint64_t* xs, const uint8_t* vals_fr, size_t n, size_t degree, size_t B,
+                            uint32_t* scalars, uint8_t* valid);
+void launch_dkg_rlc_points(hipStream_t st, const uint8_t* rows, size_t degree, const uint8_t* g1_gen, size_t B, uint8_t* out);
+void launch_g1_is_identity(hipStream_t st, const uint8_t* pts, const uint8_t* status, const uint8_t* valid, size_t B, uint8_t* ok);
 void launch_fill_g1_generator(hipStream_t st, uint8_t* out96, uint8_t* out96_unfix);
 
 }  // namespace tc

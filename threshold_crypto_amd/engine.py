@@ -630,6 +630,84 @@ class Engine:
         self._call("tc_fr_interpolate_batch", int(n), _ptr(xs), _ptr(ys), B, _ptr(out), _ptr(st))
         return out, st
 
+    # -- DKG verification: the secret side and the two checks (src/poly.rs:838-878) ---------------------------
+    def fr_poly_evaluate(self, coeff_fr, xs_fr):
+        """Poly::evaluate for B polynomials of n coefficients at M shared abscissae: coeff_fr (B, n, 32), xs_fr (M, 32) ->
+        values (B, M, 32), status (B, M)"""
+        dev = self._mode(coeff_fr, xs_fr)
+        self._arg(coeff_fr, (None, None, FR_BYTES), "u8", "coeff_fr")
+        B, n = coeff_fr.shape[0], coeff_fr.shape[1]
+        self._arg(xs_fr, (None, FR_BYTES), "u8", "xs_fr")
+        M = xs_fr.shape[0]
+        out = self._empty(dev, (B, M, FR_BYTES), ref=xs_fr)
+        st = self._empty(dev, (B, M), ref=xs_fr)
+        self._call("tc_fr_poly_evaluate_batch", _ptr(coeff_fr) if n else None, int(n), _ptr(xs_fr), M, B, _ptr(out), _ptr(st))
+        return out, st
+
+    def bivar_poly_rows(self, coeff_fr, degree, xs):
+        """BivarPoly::row(xs[m]) for every m: coeff_fr ((degree+1)(degree+2)/2, 32) -> rows (M, degree+1, 32), status (M, degree+1)"""
+        dev = self._mode(coeff_fr, xs)
+        self._arg(coeff_fr, ((degree + 1) * (degree + 2) // 2, FR_BYTES), "u8", "coeff_fr")
+        self._arg(xs, (None,), "u64", "xs")
+        M = xs.shape[0]
+        out = self._empty(dev, (M, degree + 1, FR_BYTES), ref=coeff_fr)
+        st = self._empty(dev, (M, degree + 1), ref=coeff_fr)
+        self._call("tc_bivar_poly_row_batch", _ptr(coeff_fr), int(degree), _ptr(xs), M, _ptr(out), _ptr(st))
+        return out, st
+
+    def dkg_verify_rows(self, commits, degree, xs, row_fr):
+        """`row_poly.commitment() == bi_commit.row(m)` for B parts: commits (B, ncoeff, 96), or (ncoeff, 96) for ONE commitment
+        shared by every job; xs (B,); row_fr (B, degree+1, 32) -> the row commitments (B, degree+1, 96), ok (B,)"""
+        dev = self._mode(commits, xs, row_fr)
+        ncoeff = (degree + 1) * (degree + 2) // 2
+        self._arg(xs, (None,), "u64", "xs")
+        B = xs.shape[0]
+        if len(commits.shape) == 2:
+            self._arg(commits, (ncoeff, G1_BYTES), "u8", "commits")
+            stride = 0
+        else:
+            self._arg(commits, (B, ncoeff, G1_BYTES), "u8", "commits")
+            stride = ncoeff * G1_BYTES
+        self._arg(row_fr, (B, degree + 1, FR_BYTES), "u8", "row_fr")
+        rows = self._empty(dev, (B, degree + 1, G1_BYTES), ref=commits)
+        ok = self._empty(dev, (B,), ref=commits)
+        self._call("tc_dkg_verify_rows_batch", _ptr(commits), stride, int(degree), _ptr(xs), _ptr(row_fr), B, _ptr(rows), _ptr(ok))
+        return rows, ok
+
+    def _dkg_values(self, rows, xs, vals_fr):
+        self._arg(rows, (None, None, G1_BYTES), "u8", "rows")
+        B, degree = rows.shape[0], rows.shape[1] - 1
+        if degree < 0:
+            raise ValueError("rows: a row commitment holds at least one point")
+        self._arg(xs, (B, None), "u64", "xs")
+        n = xs.shape[1]
+        self._arg(vals_fr, (B, n, FR_BYTES), "u8", "vals_fr")
+        return B, degree, n
+
+    def dkg_verify_values(self, rows, xs, vals_fr):
+        """`bi_commit.evaluate(m, s) == g1 * val` for B parts of n values: rows (B, degree+1, 96), xs (B, n), vals_fr (B, n, 32)
+        -> ok (B, n)"""
+        dev = self._mode(rows, xs, vals_fr)
+        B, degree, n = self._dkg_values(rows, xs, vals_fr)
+        ok = self._empty(dev, (B, n), ref=rows)
+        self._call("tc_dkg_verify_values_batch", _ptr(rows), int(degree), _ptr(xs), _ptr(vals_fr), n, B, _ptr(ok))
+        return ok
+
+    def dkg_verify_values_rlc(self, rows, xs, vals_fr, seed=None):
+        """The same ok (B, n) by one random linear combination per part (opt-in; see tc_amd.h): returns (ok, number of parts
+        that fell back to the value-by-value checks).  `seed`: 32 secret random bytes (os.urandom when omitted)."""
+        import os
+        dev = self._mode(rows, xs, vals_fr)
+        B, degree, n = self._dkg_values(rows, xs, vals_fr)
+        seed = bytes(seed) if seed is not None else os.urandom(32)
+        if len(seed) != 32:
+            raise ValueError("seed: 32 bytes")
+        ok = self._empty(dev, (B, n), ref=rows)
+        nfb = ctypes.c_uint64(0)
+        self._call("tc_dkg_verify_values_rlc_batch", _ptr(rows), int(degree), _ptr(xs), _ptr(vals_fr), n, B, seed, _ptr(ok),
+                   ctypes.byref(nfb))
+        return ok, int(nfb.value)
+
 
 class Group:
     """tc_group: several GPUs of one node driven from this process (one worker thread per GPU inside the library),

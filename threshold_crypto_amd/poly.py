@@ -5,11 +5,16 @@ method names, group work on the MI355X behind the C ABI.
   Commitment.evaluate                      tc_public_key_share_batch   (Horner in G1; src/poly.rs:497-508)
   BivarCommitment.row / evaluate           tc_bivar_commitment_row_batch (+ Horner in y)
   Poly.interpolate                         tc_fr_interpolate_batch
+  Poly.evaluate_batch                      tc_fr_poly_evaluate_batch   (Horner in Fr, one lane per value)
+  BivarPoly.row_batch                      tc_bivar_poly_row_batch
+  BivarCommitment.verify_rows              tc_dkg_verify_rows_batch    (`row_poly.commitment() == bi_commit.row(m)`)
+  Commitment.verify_values                 tc_dkg_verify_values_batch, or with a seed tc_dkg_verify_values_rlc_batch
+                                           (`bi_commit.evaluate(m, s) == g1 * val`)
 
-Secret polynomials (Poly, BivarPoly) are Fr coefficient lists; their Fr-only arithmetic (evaluate, row,
-add/mul) stays on the host exactly as in the reference, where it is key generation outside the hot path
-(SecretKeySet does the same in api.py).  Nothing here imports the oracle; there is no CPU fallback for the
-group operations.
+Secret polynomials (Poly, BivarPoly) are Fr coefficient lists.  Poly.evaluate, BivarPoly.row and add/mul keep their
+host form (key generation outside the hot path in the reference; SecretKeySet does the same in api.py); the batch
+methods above do the same arithmetic on the device, where every staged secret is wiped after the call.  Nothing here
+imports the oracle; there is no CPU fallback for the group operations.
 """
 import numpy as np
 
@@ -95,6 +100,33 @@ class Commitment:
                 out[k] = self.coeff[0]
         return out
 
+    def verify_values(self, xs, vals, seed=None, engine=None):
+        """`bi_commit.evaluate(m, s) == g1 * val` (src/poly.rs:846-848) with self = bi_commit.row(m): one bool per
+        (u64 abscissa, value) pair.  With a 32-byte secret `seed` the values are checked by one random linear
+        combination (tc_dkg_verify_values_rlc_batch) and value by value only when that fails: the same answers up to 2^-63."""
+        return Commitment.verify_values_batch([self], [xs], [vals], seed, engine)[0]
+
+    @staticmethod
+    def verify_values_batch(commits, xs, vals, seed=None, engine=None):
+        """verify_values for several row commitments of one degree, n values each, in one call"""
+        e = engine or default_engine()
+        if not commits:
+            return []
+        npts, n = len(commits[0].coeff), len(xs[0])
+        if npts == 0 or any(len(c.coeff) != npts for c in commits):
+            raise ValueError("all row commitments of one batch must hold the same, non-zero number of coefficients")
+        if len(xs) != len(commits) or len(vals) != len(commits) or any(len(x) != n for x in xs) or any(len(v) != n for v in vals):
+            raise ValueError("every commitment needs the same number of abscissae and values")
+        if n == 0:
+            return [[] for _ in commits]
+        if any(not 0 <= int(x) < 2 ** 64 for row in xs for x in row):
+            raise ValueError("values are addressed by u64 abscissae")
+        rows = np.stack([_stack(c.coeff, 96) for c in commits])
+        xa = np.array([[int(x) for x in row] for row in xs], dtype=np.uint64)
+        va = np.stack([_fr_rows(row) for row in vals])
+        ok = e.dkg_verify_values(rows, xa, va) if seed is None else e.dkg_verify_values_rlc(rows, xa, va, seed)[0]
+        return [[bool(b) for b in row] for row in ok]
+
 
 class Poly:
     """struct Poly { coeff: Vec<Fr> } (src/poly.rs:44-49)."""
@@ -119,6 +151,23 @@ class Poly:
         for c in reversed(self.coeff):
             res = (res * x + c) % _R
         return res
+
+    @staticmethod
+    def evaluate_batch(polys, xs, engine=None):
+        """Poly::evaluate (src/poly.rs:358-369) for every polynomial at every abscissa (IntoFr values) on the device:
+        a list of len(polys) lists of len(xs) integers"""
+        e = engine or default_engine()
+        if not polys or not xs:
+            return [[] for _ in polys]
+        n = max(len(p.coeff) for p in polys)
+        coeff = np.zeros((len(polys), n, 32), dtype=np.uint8)
+        for j, p in enumerate(polys):
+            if p.coeff:
+                coeff[j, :len(p.coeff)] = _fr_rows(p.coeff)
+        out, st = e.fr_poly_evaluate(coeff, _fr_rows(xs))
+        for s in st.reshape(-1):
+            _raise_status(s)
+        return [[int.from_bytes(bytes(out[j, m]), "little") for m in range(len(xs))] for j in range(len(polys))]
 
     def __add__(self, other):
         n = max(len(self.coeff), len(other.coeff))
@@ -200,6 +249,19 @@ class BivarPoly:
         xp, d = self._powers(x), self.degree_
         return Poly([sum(self.coeff[coeff_pos(i, j)] * xp[j] for j in range(d + 1)) % _R for i in range(d + 1)])
 
+    def row_batch(self, xs, engine=None):
+        """BivarPoly::row (src/poly.rs:606-622) for several u64 abscissae on the device"""
+        e = engine or default_engine()
+        xs = [int(x) for x in xs]
+        if any(x < 0 or x >= 2 ** 64 for x in xs):
+            raise ValueError("rows are addressed by u64 abscissae")
+        if not xs:
+            return []
+        out, st = e.bivar_poly_rows(_fr_rows(self.coeff), self.degree_, np.array(xs, dtype=np.uint64))
+        for s in st.reshape(-1):
+            _raise_status(s)
+        return [Poly([int.from_bytes(bytes(out[m, i]), "little") for i in range(self.degree_ + 1)]) for m in range(len(xs))]
+
     def commitment(self, engine=None):
         """BivarPoly::commitment (src/poly.rs:625-632)."""
         e = engine or default_engine()
@@ -243,3 +305,32 @@ class BivarCommitment:
     def evaluate(self, x, y, engine=None):
         """BivarCommitment::evaluate (src/poly.rs:694-710) = row(x).evaluate(y)."""
         return self.row(x, engine).evaluate(y, engine)
+
+    def verify_rows(self, xs, row_polys, engine=None):
+        """`row_poly.commitment() == bi_commit.row(m)` (src/poly.rs:841-843) for several (m, row_poly) pairs under this
+        commitment: (the row commitments, one bool per pair)"""
+        return BivarCommitment.verify_rows_batch([self], xs, row_polys, engine)
+
+    @staticmethod
+    def verify_rows_batch(commits, xs, row_polys, engine=None):
+        """the rows check for len(xs) parts: commits holds ONE commitment (shared by every part) or one per part"""
+        e = engine or default_engine()
+        xs = [int(x) for x in xs]
+        if any(x < 0 or x >= 2 ** 64 for x in xs):
+            raise ValueError("rows are addressed by u64 abscissae")
+        if len(row_polys) != len(xs) or len(commits) not in (1, len(xs)):
+            raise ValueError("one row polynomial per abscissa, and one commitment or one per abscissa")
+        if not xs:
+            return [], []
+        d = commits[0].degree_
+        if any(c.degree_ != d for c in commits):
+            raise ValueError("all commitments of one batch must have the same degree")
+        ok_len = [len(p.coeff) <= d + 1 for p in row_polys]            # a longer polynomial commits to something else
+        rows = np.zeros((len(xs), d + 1, 32), dtype=np.uint8)
+        for j, p in enumerate(row_polys):
+            if p.coeff and ok_len[j]:
+                rows[j, :len(p.coeff)] = _fr_rows(p.coeff)
+        blob = _stack(commits[0].coeff, 96) if len(commits) == 1 else np.stack([_stack(c.coeff, 96) for c in commits])
+        out, ok = e.dkg_verify_rows(blob, d, np.array(xs, dtype=np.uint64), rows)
+        rc = [Commitment([bytes(out[j, i]) for i in range(d + 1)], _trusted=True) for j in range(len(xs))]
+        return rc, [bool(ok[j]) and ok_len[j] for j in range(len(xs))]
