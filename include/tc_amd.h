@@ -360,6 +360,42 @@ int tc_dkg_verify_values_batch(tc_ctx* ctx, const uint8_t* rows, size_t degree, 
 int tc_dkg_verify_values_rlc_batch(tc_ctx* ctx, const uint8_t* rows, size_t degree, const uint64_t* xs, const uint8_t* vals_fr,
                                    size_t n, size_t B, const uint8_t* seed32, uint8_t* ok, uint64_t* n_fallback);
 
+/* ---- DKG finalisation: the accepted parts summed into the key set (src/poly.rs:870-876, 895-898) ----
+ * Common to the four entries below.  Strides are in BYTES, multiples of the element size (96 / 32) and at least B elements
+ * long.  mask / accept: one byte per term / part, in the same memory as the other data pointers; NULL = all.  A term whose
+ * byte is 0 is EXCLUDED: it is not decoded and touches neither output nor status, however malformed its bytes are -- a
+ * rejected dealer's commitment may be garbage -- also in checked-input mode.  An included point that does not decode, or, in
+ * checked-input mode, lies outside the order-r subgroup, fails its output: the identity's encoding and
+ * TC_JOB_INVALID_ENCODING; an included non-canonical Fr value: zero and TC_JOB_INVALID_ENCODING.  n = 0, or every term
+ * excluded: the identity / zero with status OK.  B = 0 or P = 0 is a no-op; NULL data pointers with non-zero sizes answer
+ * TC_ERR_INVALID_ARG; status is optional.  Fr operands are SECRETS: staging copies, temporaries derived from them and, in
+ * host-I/O mode, the staged Fr outputs are zeroed.  All four work in device-I/O mode.  A G1 output is split over the lanes
+ * of a wave when the batch alone would leave the GPU empty; the bytes do not depend on the split (TC_SUM_PARTS forces it). */
+/* out[j] = sum_{k<n, included} pts[k*term_stride + j*96]: Commitment::add_assign (src/poly.rs:462-471) folded over n
+ * commitments of B coefficients each (the caller pads a shorter one with the identity). */
+int tc_g1_sum_batch(tc_ctx* ctx, const uint8_t* pts, size_t term_stride, size_t n, const uint8_t* mask, size_t B, uint8_t* out,
+                    uint8_t* status);
+/* out[i] = sum_{p<P, included} commits[p][coeff_pos(i,0)], i <= degree: `sum_commit += bi_commit.row(0)` (src/poly.rs:895-898;
+ * row(0)[i] is coefficient (i,0): no multiplication).  commit_stride as in tc_dkg_verify_rows_batch (never 0 here).
+ * out: (degree+1) x 96, status: degree+1. */
+int tc_bivar_commitment_row0_sum_batch(tc_ctx* ctx, const uint8_t* commits, size_t commit_stride, size_t degree, size_t P,
+                                       const uint8_t* mask, uint8_t* out, uint8_t* status);
+/* out[j] = sum_{k<n, included} vals[k*term_stride + j*32] mod r: Poly::add_assign (src/poly.rs:68-80) per coefficient, and
+ * `sec_keys[m - 1].add_assign(..)` :876.  SECRET operands and outputs. */
+int tc_fr_sum_batch(tc_ctx* ctx, const uint8_t* vals_fr, size_t term_stride, size_t n, const uint8_t* mask, size_t B,
+                    uint8_t* out_fr, uint8_t* status);
+/* The finalisation in one call (src/poly.rs:870-876 and :895-898 over the accepted parts).  out_commit ((degree+1) x 96, may
+ * be NULL) = the row-0 sum of the accepted parts' commitments: the PublicKeySet's commitment.  out_share_fr (32 B, may be
+ * NULL: an observer without a secret; xs and vals_fr are then ignored) = sum over the accepted parts of
+ * `my_row.evaluate(0)`, my_row the polynomial through part p's n_v samples (xs[p*n_v + k] by value, vals_fr[(p*n_v + k)*32]):
+ * the node's SecretKeyShare.  part_status[p] (optional) of an accepted part: OK, TC_JOB_INVALID_ENCODING for a bad or
+ * non-member first-column point or a non-canonical value, TC_JOB_DUPLICATE_ENTRY for a repeated abscissa; a rejected part is
+ * OK and is never used.  If any accepted part fails, out_commit is degree+1 identity encodings and out_share_fr is zero --
+ * never a partial key -- and the call still returns TC_OK. */
+int tc_dkg_generate_batch(tc_ctx* ctx, const uint8_t* commits, size_t commit_stride, size_t degree, size_t P,
+                          const uint8_t* accept, const uint64_t* xs, const uint8_t* vals_fr, size_t n_v, uint8_t* out_commit,
+                          uint8_t* out_share_fr, uint8_t* part_status);
+
 /* ---- membership tests ------------------------------------------------------------------------ */
 /* ok[j] = 1 iff pts[j] decodes (range, flags, curve equation) and lies in the order-r subgroup: the
  * CHECKED half of `into_affine` (from_bytes, src/lib.rs:140-146, 246-252) for values that arrive

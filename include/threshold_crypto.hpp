@@ -12,6 +12,7 @@
 // Values are held in the reference's canonical encodings: G1 96 B, G2 192 B uncompressed
 // (into_affine().into_uncompressed()), Fr 32 B little-endian.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
@@ -830,6 +831,67 @@ inline std::vector<std::vector<bool>> dkg_verify_values_rlc(const std::vector<st
                                                             const std::vector<std::vector<FrBytes>>& vals, const std::array<std::uint8_t, 32>& seed,
                                                             std::uint64_t* n_fallback = nullptr, Engine& e = Engine::instance()) {
   return dkg_verify_values_impl(rows, xs, vals, seed.data(), n_fallback, e);
+}
+// Commitment::add_assign (src/poly.rs:462-471) folded over the included commitments (tc_g1_sum_batch): shorter ones are padded
+// with the identity; mask (empty = all) holds one entry per commitment, an excluded one is never decoded
+inline std::vector<G1Bytes> commitment_sum(const std::vector<std::vector<G1Bytes>>& commits, const std::vector<bool>& mask = {},
+                                           Engine& e = Engine::instance()) {
+  const std::size_t n = commits.size();
+  if (!mask.empty() && mask.size() != n) throw std::invalid_argument("one mask entry per commitment");
+  std::size_t B = 0;
+  for (auto& c : commits) B = std::max(B, c.size());
+  std::vector<std::uint8_t> pts(n * B * 96 + 1, 0), m(n + 1, 1), out(B * 96 + 1), st(B + 1);
+  for (std::size_t k = 0; k < n; k++) {
+    if (!mask.empty()) m[k] = mask[k] ? 1 : 0;
+    for (std::size_t j = 0; j < B; j++) {
+      if (j < commits[k].size()) std::memcpy(&pts[(k * B + j) * 96], commits[k][j].data(), 96);
+      else pts[(k * B + j) * 96] = 0x40;
+    }
+  }
+  if (B) e.check(tc_g1_sum_batch(e.ctx(), pts.data(), B * 96, n, mask.empty() ? nullptr : m.data(), B, out.data(), st.data()));
+  std::vector<G1Bytes> res(B);
+  for (std::size_t j = 0; j < B; j++) {
+    raise_status(st[j]);
+    std::memcpy(res[j].data(), &out[j * 96], 96);
+  }
+  return res;
+}
+// The end of `distributed_key_generation` (src/poly.rs:870-876, 895-898; tc_dkg_generate_batch): the key set's commitment
+// (degree+1 points) from the accepted dealers' bivariate commitments and, when share_out is given, this node's secret key
+// share from the (abscissa, value) samples it holds of every dealer's row (xs[p], vals[p]; a rejected dealer's are not read).
+// accepted: empty = all.  A failed accepted part throws.
+inline std::vector<G1Bytes> dkg_generate(const std::vector<std::vector<G1Bytes>>& bi_commits, std::size_t degree, const std::vector<bool>& accepted = {},
+                                         const std::vector<std::vector<std::uint64_t>>* xs = nullptr,
+                                         const std::vector<std::vector<FrBytes>>* vals = nullptr, FrBytes* share_out = nullptr,
+                                         Engine& e = Engine::instance()) {
+  const std::size_t P = bi_commits.size(), n = degree + 1, nco = n * (n + 1) / 2;
+  if (!accepted.empty() && accepted.size() != P) throw std::invalid_argument("one accepted entry per dealer");
+  if (share_out && (!xs || !vals || xs->size() != P || vals->size() != P)) throw std::invalid_argument("a share needs the samples of every dealer");
+  const std::size_t nv = (share_out && P) ? (*xs)[0].size() : 0;
+  std::vector<std::uint8_t> c(P * nco * 96 + 1), a(P + 1, 1), v(P * nv * 32 + 1), out(n * 96 + 1), st(P + 1);
+  std::vector<std::uint64_t> x(P * nv + 1);
+  for (std::size_t p = 0; p < P; p++) {
+    if (bi_commits[p].size() != nco) throw std::invalid_argument("bivariate commitment size");
+    if (!accepted.empty()) a[p] = accepted[p] ? 1 : 0;
+    for (std::size_t i = 0; i < nco; i++) std::memcpy(&c[(p * nco + i) * 96], bi_commits[p][i].data(), 96);
+    if (share_out && a[p]) {
+      if ((*xs)[p].size() != nv || (*vals)[p].size() != nv) throw std::invalid_argument("every accepted dealer needs the same number of samples");
+      for (std::size_t k = 0; k < nv; k++) {
+        x[p * nv + k] = (*xs)[p][k];
+        std::memcpy(&v[(p * nv + k) * 32], (*vals)[p][k].data(), 32);
+      }
+    }
+  }
+  for (std::size_t i = 0; i < n; i++) out[i * 96] = 0x40;  // P = 0: the empty sum
+  if (share_out) share_out->fill(0);
+  if (P)
+    e.check(tc_dkg_generate_batch(e.ctx(), c.data(), nco * 96, degree, P, accepted.empty() ? nullptr : a.data(), x.data(), v.data(), nv, out.data(),
+                                  share_out ? share_out->data() : nullptr, st.data()));
+  { volatile std::uint8_t* z = v.data(); for (std::size_t i = 0; i < v.size(); i++) z[i] = 0; }  // the staged values are secrets
+  for (std::size_t p = 0; p < P; p++) raise_status(st[p]);
+  std::vector<G1Bytes> res(n);
+  for (std::size_t i = 0; i < n; i++) std::memcpy(res[i].data(), &out[i * 96], 96);
+  return res;
 }
 
 // Several GPUs of one node from this process (tc_group_*): contiguous job sharding, RCCL broadcast of the key set

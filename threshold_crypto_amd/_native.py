@@ -68,6 +68,10 @@ PROTOTYPES = {
     "tc_dkg_verify_rows_batch": [_u8p, _sz, _sz, _u64p, _u8p, _sz, _u8p, _u8p],
     "tc_dkg_verify_values_batch": [_u8p, _sz, _u64p, _u8p, _sz, _sz, _u8p],
     "tc_dkg_verify_values_rlc_batch": [_u8p, _sz, _u64p, _u8p, _sz, _sz, ctypes.c_char_p, _u8p, ctypes.POINTER(ctypes.c_uint64)],
+    "tc_g1_sum_batch": [_u8p, _sz, _sz, _u8p, _sz, _u8p, _u8p],
+    "tc_bivar_commitment_row0_sum_batch": [_u8p, _sz, _sz, _sz, _u8p, _u8p, _u8p],
+    "tc_fr_sum_batch": [_u8p, _sz, _sz, _u8p, _sz, _u8p, _u8p],
+    "tc_dkg_generate_batch": [_u8p, _sz, _sz, _sz, _u8p, _u64p, _u8p, _sz, _u8p, _u8p, _u8p],
     "tc_g1_subgroup_check_batch": [_u8p, _sz, _u8p],
     "tc_g2_subgroup_check_batch": [_u8p, _sz, _u8p],
     "tc_g1_compress_batch": [_u8p, _sz, _u8p, _u8p],

@@ -1,6 +1,7 @@
 // gfx950 kernels: DKG algebra (tc_dkg.h) -- fixed-base commitments from an LDS-resident window table of the
 // G1 generator, rows of bivariate commitments, Fr interpolation, and the DKG verification kernels: Fr rows and values, the
-// per-job forms of the two G1 Horner kernels, the comparisons and the scalars of the combined values check.
+// per-job forms of the two G1 Horner kernels, the comparisons and the scalars of the combined values check, and the DKG
+// finalisation: sums of G1 points split over the lanes of a wave, sums of Fr values, interpolation at zero.
 #include "tc_dkg.h"
 #include "tc_launch.h"
 
@@ -218,6 +219,142 @@ void launch_dkg_rlc_points(hipStream_t st, const uint8_t* rows, size_t degree, c
 }
 void launch_g1_is_identity(hipStream_t st, const uint8_t* pts, const uint8_t* status, const uint8_t* valid, size_t B, uint8_t* ok) {
   if (B) hipLaunchKernelGGL(k_g1_is_identity, dim3(grid_for(B)), dim3(kBlock), 0, st, pts, status, valid, B, ok);
+}
+
+// ---- DKG finalisation (tc_dkg.h): sums of G1 points and of Fr values over the accepted parts ---------------------------
+// where output j finds its term 0: consecutive points, or the first column of a bivariate commitment (row(0)[j] = coefficient (j, 0))
+struct SumOffPlain {
+  __device__ __forceinline__ size_t operator()(size_t j) const { return j * 96; }
+};
+struct SumOffColumn0 {
+  __device__ __forceinline__ size_t operator()(size_t j) const { return bivar_coeff_pos(j, 0) * 96; }
+};
+// out[j] = sum_{k < n, included} pts[k * term_stride + off(j)].  `parts` (a power of two, 1 .. 64) adjacent lanes per output,
+// so an output never spans two waves; their partial sums meet in log2(parts) rounds of one __shfl_xor exchange of the 42
+// limbs + one complete addition, as in k_msm_ladder_g1.  No lane of a live output leaves before the last round; the lanes of
+// outputs >= B leave as whole groups (parts divides 64).  member: checked-input mode, member[k * B + j] (else null).
+template <class OFF>
+__global__ __launch_bounds__(kBlock, TC_WAVES_G1_AUX) void k_g1_sum(const uint8_t* __restrict__ pts, size_t term_stride, size_t n,
+                                                                    const uint8_t* __restrict__ mask, const uint8_t* __restrict__ member, size_t B,
+                                                                    size_t parts, uint8_t* __restrict__ out, uint8_t* __restrict__ status,
+                                                                    uint8_t* __restrict__ term_bad) {
+  const size_t lp = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  const size_t j = lp / parts, g = lp % parts;
+  if (j >= B) return;
+  bool ok;
+  G1Jac r = job_g1_sum_part(pts + OFF()(j), term_stride, mask, member ? member + j : nullptr, B, sum_part(n, g, parts), ok, term_bad);
+  int good = ok ? 1 : 0;
+  TC_NOUNROLL for (size_t d = 1; d < parts; d <<= 1) {
+    G1Jac o = r;
+    TC_UNROLL for (int i = 0; i < FQ_LIMBS; i++) {
+      o.x.l[i] = __shfl_xor(r.x.l[i], (int)d, 64);
+      o.y.l[i] = __shfl_xor(r.y.l[i], (int)d, 64);
+      o.z.l[i] = __shfl_xor(r.z.l[i], (int)d, 64);
+    }
+    good &= __shfl_xor(good, (int)d, 64);
+    r = jac_add(r, o);
+  }
+  if (g != 0) return;
+  g1_encode_uncompressed(good ? jac_to_affine(r) : G1Affine::infinity(), out + j * 96);
+  if (status) status[j] = good ? TC_JOB_OK : TC_JOB_INVALID_ENCODING;
+}
+__global__ __launch_bounds__(kBlock) void k_fr_sum(const uint8_t* __restrict__ vals, size_t term_stride, size_t n, const uint8_t* __restrict__ mask,
+                                                   size_t B, uint8_t* __restrict__ out, uint8_t* __restrict__ status) {
+  const size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (j >= B) return;
+  const uint8_t st = job_fr_sum(vals + j * 32, term_stride, n, mask, out + j * 32);
+  if (status) status[j] = st;
+}
+// out[p] = coefficient 0 of the polynomial through part p's n samples; a rejected part (accept[p] == 0) is not read: zero, OK
+__global__ __launch_bounds__(kBlock) void k_fr_interpolate_at_zero(size_t n, const uint64_t* __restrict__ xs, const uint8_t* __restrict__ vals,
+                                                                   const uint8_t* __restrict__ accept, size_t P, uint8_t* __restrict__ out,
+                                                                   uint8_t* __restrict__ status) {
+  const size_t p = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (p >= P) return;
+  if (accept && accept[p] == 0) {
+    for (int b = 0; b < 32; b++) out[p * 32 + b] = 0;
+    status[p] = TC_JOB_OK;
+    return;
+  }
+  status[p] = job_fr_interpolate_at_zero(n, xs + p * n, vals + p * n * 32, out + p * 32);
+}
+// the first column of P bivariate commitments as consecutive points: out[p * (degree+1) + i] = commits[p][pos(i, 0)], one
+// 8-byte word per lane (checked-input mode: what the membership test and the sum then read)
+__global__ __launch_bounds__(kBlock) void k_bivar_column0(const uint8_t* __restrict__ commits, size_t stride, size_t degree, size_t P,
+                                                          uint8_t* __restrict__ out) {
+  const size_t t = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  const size_t per = (degree + 1) * 12;
+  if (t >= P * per) return;
+  const size_t p = t / per, i = (t % per) / 12, w = t % 12;
+  reinterpret_cast<uint64_t*>(out)[t] = reinterpret_cast<const uint64_t*>(commits + p * stride + bivar_coeff_pos(i, 0) * 96)[w];
+}
+// tc_dkg_generate_batch's verdict.  Lane p < P: part_status[p] of an accepted part = INVALID_ENCODING for a bad first-column
+// point (point_bad, set by k_g1_sum) or a non-canonical value, DUPLICATE_ENTRY for a repeated abscissa (share_st, may be
+// null: an observer); a rejected part is OK.
+__global__ __launch_bounds__(kBlock) void k_dkg_part_status(const uint8_t* __restrict__ accept, const uint8_t* __restrict__ point_bad,
+                                                            const uint8_t* __restrict__ share_st, size_t P, uint8_t* __restrict__ part_status) {
+  const size_t p = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (p >= P) return;
+  uint8_t st = TC_JOB_OK;
+  if (!accept || accept[p] != 0) {
+    if (point_bad[p]) st = TC_JOB_INVALID_ENCODING;
+    else if (share_st) st = share_st[p];
+  }
+  part_status[p] = st;
+}
+// ... and never a partial key: when an accepted part failed, lane i <= degree writes the identity over out_commit[i] and lane
+// degree + 1 zero over the share (either may be null)
+__global__ __launch_bounds__(kBlock) void k_dkg_generate_guard(const uint8_t* __restrict__ part_status, size_t P, size_t degree,
+                                                               uint8_t* __restrict__ out_commit, uint8_t* __restrict__ out_share) {
+  const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i > degree + 1) return;
+  bool failed = false;
+  for (size_t p = 0; p < P; p++) failed = failed || part_status[p] != TC_JOB_OK;
+  if (!failed) return;
+  if (i <= degree) {
+    if (out_commit) g1_encode_uncompressed(G1Affine::infinity(), out_commit + i * 96);
+  } else if (out_share) {
+    for (int b = 0; b < 32; b++) out_share[b] = 0;
+  }
+}
+
+// lanes per output of k_g1_sum: TC_SUM_PARTS when set (forced), else the smallest power of two that gives the launch one wave
+// per SIMD (4 per CU), at most 64 and at most n / 2
+size_t g1_sum_parts(size_t B, size_t n, int cus, size_t forced) {
+  if (forced) return forced;
+  const size_t want = (size_t)(cus > 0 ? cus : 256) * 4 * kBlock;
+  size_t parts = 1;
+  while (parts < 64 && B * parts < want && parts * 2 * 2 <= n) parts *= 2;
+  return parts;
+}
+void launch_g1_sum(hipStream_t st, bool column0, const uint8_t* pts, size_t term_stride, size_t n, const uint8_t* mask, const uint8_t* member,
+                   size_t B, size_t parts, uint8_t* out, uint8_t* status, uint8_t* term_bad) {
+  if (!B) return;
+  if (parts < 1 || parts > 64 || (parts & (parts - 1))) parts = 1;
+  const dim3 grid(grid_for(B * parts));
+  if (column0)
+    hipLaunchKernelGGL(k_g1_sum<SumOffColumn0>, grid, dim3(kBlock), 0, st, pts, term_stride, n, mask, member, B, parts, out, status, term_bad);
+  else
+    hipLaunchKernelGGL(k_g1_sum<SumOffPlain>, grid, dim3(kBlock), 0, st, pts, term_stride, n, mask, member, B, parts, out, status, term_bad);
+}
+void launch_fr_sum(hipStream_t st, const uint8_t* vals_fr, size_t term_stride, size_t n, const uint8_t* mask, size_t B, uint8_t* out_fr,
+                   uint8_t* status) {
+  if (B) hipLaunchKernelGGL(k_fr_sum, dim3(grid_for(B)), dim3(kBlock), 0, st, vals_fr, term_stride, n, mask, B, out_fr, status);
+}
+void launch_fr_interpolate_at_zero(hipStream_t st, size_t n, const uint64_t* xs, const uint8_t* vals_fr, const uint8_t* accept, size_t P,
+                                   uint8_t* out_fr, uint8_t* status) {
+  if (P) hipLaunchKernelGGL(k_fr_interpolate_at_zero, dim3(grid_for(P)), dim3(kBlock), 0, st, n, xs, vals_fr, accept, P, out_fr, status);
+}
+void launch_bivar_column0(hipStream_t st, const uint8_t* commits, size_t stride, size_t degree, size_t P, uint8_t* out) {
+  const size_t words = P * (degree + 1) * 12;
+  if (words) hipLaunchKernelGGL(k_bivar_column0, dim3(grid_for(words)), dim3(kBlock), 0, st, commits, stride, degree, P, out);
+}
+void launch_dkg_generate_verdict(hipStream_t st, const uint8_t* accept, const uint8_t* point_bad, const uint8_t* share_st, size_t P, size_t degree,
+                                 uint8_t* part_status, uint8_t* out_commit, uint8_t* out_share) {
+  if (!P) return;
+  hipLaunchKernelGGL(k_dkg_part_status, dim3(grid_for(P)), dim3(kBlock), 0, st, accept, point_bad, share_st, P, part_status);
+  hipLaunchKernelGGL(k_dkg_generate_guard, dim3(grid_for(degree + 2)), dim3(kBlock), 0, st, (const uint8_t*)part_status, P, degree, out_commit,
+                     out_share);
 }
 
 }  // namespace tc

@@ -417,7 +417,7 @@ void msm_g1(Call& k, size_t n, size_t pts_stride, const uint8_t* d_pts, const ui
   }
 }
 
-// TC_DUO_MIN / TC_PAIRING_FORM / TC_PAIRING_BUDGET (tests, experiments): read here, once per context, never on the launch path
+// TC_DUO_MIN / TC_PAIRING_FORM / TC_PAIRING_BUDGET / TC_SUM_PARTS (tests, experiments): read here, once per context, never on the launch path
 tc::Tuning tuning_from_env() {
   tc::Tuning tn;
   if (const char* e = getenv("TC_DUO_MIN")) tn.duo_min_decode = tn.duo_min_hash = (size_t)strtoull(e, nullptr, 10);
@@ -425,6 +425,10 @@ tc::Tuning tuning_from_env() {
   if (const char* b = getenv("TC_PAIRING_BUDGET")) tn.pairing_budget = (size_t)strtoull(b, nullptr, 10);
   if (const char* m = getenv("TC_MSM_BUDGET")) tn.msm_budget = (size_t)strtoull(m, nullptr, 10);
   if (const char* r = getenv("TC_PRIVATE_RESERVE")) tn.private_reserve = (size_t)strtoull(r, nullptr, 10);
+  if (const char* q = getenv("TC_SUM_PARTS")) {
+    const size_t v = (size_t)strtoull(q, nullptr, 10);
+    if (v >= 1 && v <= 64 && (v & (v - 1)) == 0) tn.sum_parts = v;  // a power of two within one wave; anything else: the default rule
+  }
   if (const char* o = getenv("TC_CHECKS_BESIDE")) tn.checks_beside = (o[0] >= '0' && o[0] <= '2') ? o[0] - '0' : 1;  // 0 one stream, 1 low priority, 2 normal
   return tn;
 }
@@ -2108,6 +2112,136 @@ int tc_dkg_verify_values_rlc_batch(tc_ctx* ctx, const uint8_t* rows, size_t degr
       if (n_fallback) *n_fallback = F;
     }
   }
+  k.end_timing();
+  return k.finish();
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+// ---- DKG finalisation: the accepted parts summed into the key set (src/poly.rs:870-876, 895-898) --------------------------
+// out[j] = sum over the included terms of one point per term, on device operands.  Checked-input mode: Call::check_points
+// marks by record and cannot express the mask, so the membership test runs here and the sum kernel reads its verdicts for the
+// INCLUDED terms only (as dkg_values_exact(checked = true) does for its compacted operands).  column0: the terms are bivariate
+// commitments and output j is coefficient (j, 0); the test then reads a compact copy of the first columns.
+static void g1_sum(Call& k, bool column0, const uint8_t* d_pts, size_t term_stride, size_t n, const uint8_t* d_mask, size_t B, uint8_t* d_out,
+                   uint8_t* d_st, uint8_t* d_term_bad) {
+  tc_ctx* ctx = k.c;
+  const uint8_t* d_member = nullptr;
+  if (ctx->input_checks && n) {
+    uint8_t* d_valid = k.temp<uint8_t>(n * B);
+    uint8_t* d_col = column0 ? k.temp<uint8_t>(n * B * 96) : nullptr;
+    if (k.failed) return;
+    if (column0) {
+      tc::launch_bivar_column0(ctx->stream, d_pts, term_stride, B - 1, n, d_col);
+      d_pts = d_col;
+      term_stride = B * 96;
+      column0 = false;
+    }
+    tc::launch_subgroup_check_g1(ctx->stream, d_pts, 96, term_stride / 96, B, n * B, d_valid);
+    d_member = d_valid;
+  }
+  if (k.failed) return;
+  tc::launch_g1_sum(ctx->stream, column0, d_pts, term_stride, n, d_mask, d_member, B, tc::g1_sum_parts(B, n, ctx->cus, ctx->tuning.sum_parts), d_out,
+                    d_st, d_term_bad);
+}
+
+int tc_g1_sum_batch(tc_ctx* ctx, const uint8_t* pts, size_t term_stride, size_t n, const uint8_t* mask, size_t B, uint8_t* out,
+                    uint8_t* status) try {
+  TC_REQUIRE(ctx);
+  if (B == 0) return TC_OK;
+  TC_REQUIRE(ctx && out && (n == 0 || pts));
+  TC_REQUIRE(n == 0 || (term_stride % 96 == 0 && term_stride / 96 >= B));
+  TC_REQUIRE(B < (1ull << 26) && n < (1ull << 32) && B * n < (1ull << 40));
+  Call k(ctx);
+  const uint8_t* d_pts = k.in(pts, n ? (n - 1) * term_stride + B * 96 : 0);
+  const uint8_t* d_mask = k.in(mask, n);
+  uint8_t* d_out = k.out(out, B * 96);
+  uint8_t* d_st = k.out(status, B);
+  k.begin_timing();
+  g1_sum(k, false, d_pts, term_stride, n, d_mask, B, d_out, d_st, nullptr);
+  k.end_timing();
+  return k.finish();
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+int tc_bivar_commitment_row0_sum_batch(tc_ctx* ctx, const uint8_t* commits, size_t commit_stride, size_t degree, size_t P, const uint8_t* mask,
+                                       uint8_t* out, uint8_t* status) try {
+  TC_REQUIRE(ctx);
+  if (P == 0) return TC_OK;
+  TC_REQUIRE(ctx && commits && out);
+  TC_REQUIRE(degree < (1u << 12) && P < (1ull << 26));
+  const size_t n = degree + 1, ncoeff = n * (n + 1) / 2;
+  TC_REQUIRE(commit_stride % 96 == 0 && commit_stride >= ncoeff * 96);
+  Call k(ctx);
+  const uint8_t* d_c = k.in(commits, (P - 1) * commit_stride + ncoeff * 96);
+  const uint8_t* d_mask = k.in(mask, P);
+  uint8_t* d_out = k.out(out, n * 96);
+  uint8_t* d_st = k.out(status, n);
+  k.begin_timing();
+  g1_sum(k, true, d_c, commit_stride, P, d_mask, n, d_out, d_st, nullptr);
+  k.end_timing();
+  return k.finish();
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+int tc_fr_sum_batch(tc_ctx* ctx, const uint8_t* vals_fr, size_t term_stride, size_t n, const uint8_t* mask, size_t B, uint8_t* out_fr,
+                    uint8_t* status) try {
+  TC_REQUIRE(ctx);
+  if (B == 0) return TC_OK;
+  TC_REQUIRE(ctx && out_fr && (n == 0 || vals_fr));
+  TC_REQUIRE(n == 0 || (term_stride % 32 == 0 && term_stride / 32 >= B));
+  TC_REQUIRE(B < (1ull << 32) && n < (1ull << 32));
+  Call k(ctx);
+  const uint8_t* d_v = k.in(vals_fr, n ? (n - 1) * term_stride + B * 32 : 0, /*secret=*/true);
+  const uint8_t* d_mask = k.in(mask, n);
+  uint8_t* d_out = k.out(out_fr, B * 32);
+  // host-I/O mode: the (secret) sums pass through a staging slot that outlives the call: wiped after the copy back
+  if (d_out && !ctx->device_io) k.wipe_after_copy.emplace_back(d_out, B * 32);
+  uint8_t* d_st = k.out(status, B);
+  k.begin_timing();
+  if (!k.failed) tc::launch_fr_sum(ctx->stream, d_v, term_stride, n, d_mask, B, d_out, d_st);
+  k.end_timing();
+  return k.finish();
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+// The public side is the first-column sum with the accept bytes as its mask; the sum kernel marks the parts that own a bad
+// included point.  The secret side: every accepted part's interpolation at zero, then one Fr sum over the parts.  The verdict
+// kernels write part_status and, when an accepted part failed, the identity / zero over both outputs.
+int tc_dkg_generate_batch(tc_ctx* ctx, const uint8_t* commits, size_t commit_stride, size_t degree, size_t P, const uint8_t* accept,
+                          const uint64_t* xs, const uint8_t* vals_fr, size_t n_v, uint8_t* out_commit, uint8_t* out_share_fr,
+                          uint8_t* part_status) try {
+  TC_REQUIRE(ctx);
+  if (P == 0) return TC_OK;
+  TC_REQUIRE(ctx && commits);
+  TC_REQUIRE(degree < (1u << 12) && P < (1ull << 26) && n_v < (1u << 16));
+  const size_t n = degree + 1, ncoeff = n * (n + 1) / 2;
+  TC_REQUIRE(commit_stride % 96 == 0 && commit_stride >= ncoeff * 96);
+  const bool share = out_share_fr != nullptr;
+  TC_REQUIRE(!share || n_v == 0 || (xs && vals_fr));
+  Call k(ctx);
+  const uint8_t* d_c = k.in(commits, (P - 1) * commit_stride + ncoeff * 96);
+  const uint8_t* d_acc = k.in(accept, P);
+  const uint64_t* d_x = share ? k.in(xs, P * n_v) : nullptr;
+  const uint8_t* d_v = share ? k.in(vals_fr, P * n_v * 32, /*secret=*/true) : nullptr;
+  uint8_t* d_oc = out_commit ? k.out(out_commit, n * 96) : k.temp<uint8_t>(n * 96);
+  uint8_t* d_os = k.out(out_share_fr, 32);
+  if (d_os && !ctx->device_io) k.wipe_after_copy.emplace_back(d_os, 32);
+  uint8_t* d_ps = part_status ? k.out(part_status, P) : k.temp<uint8_t>(P);
+  uint8_t* d_bad = k.temp<uint8_t>(P, /*zero=*/true);
+  uint8_t* d_part = share ? k.temp<uint8_t>(P * 32) : nullptr;  // the parts' contributions to the share: secret
+  if (d_part) k.wipe.emplace_back(d_part, P * 32);
+  uint8_t* d_sst = share ? k.temp<uint8_t>(P) : nullptr;
+  k.begin_timing();
+  g1_sum(k, true, d_c, commit_stride, P, d_acc, n, d_oc, nullptr, d_bad);
+  if (!k.failed && share) {
+    tc::launch_fr_interpolate_at_zero(ctx->stream, n_v, d_x, d_v, d_acc, P, d_part, d_sst);
+    tc::launch_fr_sum(ctx->stream, d_part, 32, P, d_acc, 1, d_os, nullptr);
+  }
+  if (!k.failed) tc::launch_dkg_generate_verdict(ctx->stream, d_acc, d_bad, d_sst, P, degree, d_ps, d_oc, d_os);
   k.end_timing();
   return k.finish();
 } catch (...) {

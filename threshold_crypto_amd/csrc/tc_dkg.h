@@ -281,4 +281,91 @@ TC_HD bool job_dkg_rlc_scalars(const uint32_t* key8, size_t j, size_t n, size_t 
   return ok;
 }
 
+// ---- DKG finalisation: the accepted parts summed into the key set (src/poly.rs:870-876, 895-898) -----------------------
+// Commitment::add_assign (src/poly.rs:462-471) folded over n terms is, per coefficient, a sum of n points: few outputs and long
+// sums at the large shape (68 x 200), so an output is split over `parts` adjacent lanes (k_dkg.hip k_g1_sum), lane g summing
+// the terms [g n / parts, (g + 1) n / parts) -- msm_part's split (tc_msm.h): every k < n in exactly one lane, a lane with
+// parts > n may own nothing.
+struct SumPart {
+  size_t k0, k1;
+};
+TC_HD SumPart sum_part(size_t n, size_t g, size_t parts) { return SumPart{g * n / parts, (g + 1) * n / parts}; }
+
+// one lane's partial sum  sum_{k in part, included} pts[k * term_stride]  (pts: the address of term 0 of THIS output).  Term k
+// is included when mask is null or mask[k] != 0; an excluded term is not decoded and touches nothing, whatever its bytes.
+// member (checked-input mode, else null): member[k * member_stride] == 0 marks a term outside the order-r subgroup.  ok =
+// every included term decoded (and was a member); a bad one counts as the identity and, with term_bad, sets term_bad[k] = 1.
+// The additions are the complete ones: equal and opposite terms are ordinary inputs (one dealer's commitment twice, P and -P).
+TC_HD G1Jac job_g1_sum_part(const uint8_t* pts, size_t term_stride, const uint8_t* mask, const uint8_t* member, size_t member_stride,
+                            SumPart part, bool& ok, uint8_t* term_bad = nullptr) {
+  G1Jac acc = G1Jac::infinity();
+  ok = true;
+  TC_NOUNROLL for (size_t k = part.k0; k < part.k1; k++) {
+    if (mask && mask[k] == 0) continue;
+    G1Affine c;
+    bool good = g1_decode_uncompressed(pts + k * term_stride, c);
+    if (member) good = good && member[k * member_stride] != 0;
+    if (!good) {
+      c = G1Affine::infinity();
+      if (term_bad) term_bad[k] = 1;
+    }
+    ok = ok && good;
+    acc = jac_add_mixed(acc, c);
+  }
+  return acc;
+}
+
+// out = sum_{k < n, included} vals[k * term_stride] mod r  (Poly::add_assign src/poly.rs:68-80 per coefficient; :876).  The
+// terms are canonical residues and addition does not care about the Montgomery factor: no conversion either way.  A
+// non-canonical included value: zero output, TC_JOB_INVALID_ENCODING.
+TC_HD uint8_t job_fr_sum(const uint8_t* vals, size_t term_stride, size_t n, const uint8_t* mask, uint8_t* out32) {
+  Fr acc = Fr::zero();
+  bool ok = true;
+  TC_NOUNROLL for (size_t k = 0; k < n; k++) {
+    if (mask && mask[k] == 0) continue;
+    Fr t;
+    const bool good = fr_from_le32(vals + k * term_stride, t.v.l);
+    if (!good) t = Fr::zero();
+    ok = ok && good;
+    acc = acc + t;
+  }
+  if (!ok) acc = Fr::zero();
+  TC_UNROLL for (int i = 0; i < 8; i++) {
+    out32[4 * i] = (uint8_t)acc.v.l[i];
+    out32[4 * i + 1] = (uint8_t)(acc.v.l[i] >> 8);
+    out32[4 * i + 2] = (uint8_t)(acc.v.l[i] >> 16);
+    out32[4 * i + 3] = (uint8_t)(acc.v.l[i] >> 24);
+  }
+  return ok ? TC_JOB_OK : TC_JOB_INVALID_ENCODING;
+}
+
+// coefficient 0 of job_fr_interpolate's polynomial through the n samples (xs[k] by value, vals[k]): `my_row.evaluate(0)`
+// (src/poly.rs:870-876) without the row.  The Lagrange sum  sum_i y_i prod_{j != i} x_j / (x_j - x_i)  kept as ONE fraction
+// num / den (num/den + a/b = (num b + a den) / (den b)): no scratch, one inversion.  Statuses as job_fr_interpolate: a
+// non-canonical value INVALID_ENCODING, a repeated abscissa (some x_j - x_i = 0, so den = 0) DUPLICATE_ENTRY, n = 0 zero.
+TC_HD uint8_t job_fr_interpolate_at_zero(size_t n, const uint64_t* xs, const uint8_t* vals, uint8_t* out32) {
+  Fr num = Fr::zero(), den = Fr::one();
+  bool ok = true;
+  TC_NOUNROLL for (size_t i = 0; i < n; i++) {
+    uint32_t w[8];
+    const bool good = fr_from_le32(vals + i * 32, w);
+    ok = ok && good;
+    Fr a = good ? Fr::from_canonical(w) : Fr::zero();
+    Fr b = Fr::one();
+    const Fr xi = fr_from_u64(xs[i]);
+    TC_NOUNROLL for (size_t j = 0; j < n; j++) {
+      if (j == i) continue;
+      const Fr xj = fr_from_u64(xs[j]);
+      a = a * xj;
+      b = b * (xj - xi);
+    }
+    num = num * b + a * den;
+    den = den * b;
+  }
+  const bool dup = den.is_zero();
+  const Fr r = (ok && !dup) ? num * den.inv() : Fr::zero();
+  fr_store_le32(r, out32);
+  return !ok ? TC_JOB_INVALID_ENCODING : dup ? TC_JOB_DUPLICATE_ENTRY : TC_JOB_OK;
+}
+
 }  // namespace tc

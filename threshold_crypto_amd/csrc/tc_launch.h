@@ -55,6 +55,7 @@ struct Tuning {
   size_t private_reserve = (size_t)-1;
   size_t msm_budget = 0;      // bytes the per-share tables of the two-stage kernels may take per call; 0 = a third of the free HBM, 1-24 GiB (TC_MSM_BUDGET: tests)
   int checks_beside = 1;  // checked-input mode: the membership tests on a second stream beside the call's main kernels (TC_CHECKS_BESIDE=0: before them, one stream)
+  size_t sum_parts = 0;   // lanes per output of k_g1_sum (TC_SUM_PARTS=<1|2|4|...|64>: tests, tools/g1_sum_probe.py); 0 = by B, n and the CU count (g1_sum_parts)
 };
 
 // The G1 ladder kernels keep their per-lane table in the HBM arena and fit 256 registers (two waves per SIMD) at
@@ -245,5 +246,22 @@ void launch_dkg_rlc_scalars(hipStream_t st, const uint8_t* seed32, const uint64_
 void launch_dkg_rlc_points(hipStream_t st, const uint8_t* rows, size_t degree, const uint8_t* g1_gen, size_t B, uint8_t* out);
 void launch_g1_is_identity(hipStream_t st, const uint8_t* pts, const uint8_t* status, const uint8_t* valid, size_t B, uint8_t* ok);
 void launch_fill_g1_generator(hipStream_t st, uint8_t* out96, uint8_t* out96_unfix);
+// DKG finalisation (k_dkg.hip): out[j] = sum_{k < n, included} pts[k * term_stride + off(j)], off(j) = j * 96 or, column0, the
+// position of coefficient (j, 0) of a bivariate commitment; `parts` lanes per output (g1_sum_parts).  mask: n bytes or null;
+// member: n x B validity bytes of a membership test or null; term_bad: n zeroed bytes or null, [k] set when an included term k
+// is bad.  A failed output is the identity with status INVALID_ENCODING.
+size_t g1_sum_parts(size_t B, size_t n, int cus, size_t forced);
+void launch_g1_sum(hipStream_t st, bool column0, const uint8_t* pts, size_t term_stride, size_t n, const uint8_t* mask, const uint8_t* member,
+                   size_t B, size_t parts, uint8_t* out, uint8_t* status, uint8_t* term_bad);
+void launch_fr_sum(hipStream_t st, const uint8_t* vals_fr, size_t term_stride, size_t n, const uint8_t* mask, size_t B, uint8_t* out_fr,
+                   uint8_t* status);
+// out[p] = coefficient 0 of the polynomial through part p's n samples (xs: P x n by value, vals: P x n x 32); status: P bytes
+void launch_fr_interpolate_at_zero(hipStream_t st, size_t n, const uint64_t* xs, const uint8_t* vals_fr, const uint8_t* accept, size_t P,
+                                   uint8_t* out_fr, uint8_t* status);
+void launch_bivar_column0(hipStream_t st, const uint8_t* commits, size_t stride, size_t degree, size_t P, uint8_t* out);
+// part_status[p] from the accepted parts' bad points and share statuses (share_st may be null), then identities / zero over
+// the outputs (either may be null) when one of them failed
+void launch_dkg_generate_verdict(hipStream_t st, const uint8_t* accept, const uint8_t* point_bad, const uint8_t* share_st, size_t P, size_t degree,
+                                 uint8_t* part_status, uint8_t* out_commit, uint8_t* out_share);
 
 }  // namespace tc

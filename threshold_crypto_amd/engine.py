@@ -708,6 +708,93 @@ class Engine:
                    ctypes.byref(nfb))
         return ok, int(nfb.value)
 
+    # -- DKG finalisation: the accepted parts summed into the key set (src/poly.rs:870-876, 895-898) ----------
+    def _mask(self, mask, n, name):
+        if mask is not None:
+            self._arg(mask, (n,), "u8", name)
+        return _ptr(mask) if mask is not None else None
+
+    def g1_sum(self, pts, mask=None):
+        """Commitment::add_assign folded over n terms: pts (n, B, 96) -> out[j] = sum of the included pts[k, j]: (B, 96),
+        status (B,).  mask (n,) u8 (0 = excluded, never decoded) or None = all."""
+        dev = self._mode(pts, mask)
+        self._arg(pts, (None, None, G1_BYTES), "u8", "pts")
+        n, B = pts.shape[0], pts.shape[1]
+        return self._g1_sum(dev, pts, B * G1_BYTES, n, mask, B)
+
+    def g1_sum_strided(self, pts, B, mask=None):
+        """g1_sum over the first B of the S >= B points of every term: pts (n, S, 96), term stride S * 96 bytes"""
+        dev = self._mode(pts, mask)
+        self._arg(pts, (None, None, G1_BYTES), "u8", "pts")
+        n, S = pts.shape[0], pts.shape[1]
+        if not 0 <= int(B) <= S:
+            raise ValueError("B: at most the %d points a term holds" % S)
+        return self._g1_sum(dev, pts, S * G1_BYTES, n, mask, int(B))
+
+    def _g1_sum(self, dev, pts, stride, n, mask, B):
+        out = self._empty(dev, (B, G1_BYTES), ref=pts)
+        st = self._empty(dev, (B,), ref=pts)
+        self._call("tc_g1_sum_batch", _ptr(pts) if n else None, stride, n, self._mask(mask, n, "mask"), B, _ptr(out), _ptr(st))
+        return out, st
+
+    def bivar_row0_sum(self, commits, degree, mask=None):
+        """`sum_commit += bi_commit.row(0)` over the included parts: commits (P, S, 96) with S >= (degree+1)(degree+2)/2 points per
+        part -> (degree+1, 96), status (degree+1,)"""
+        dev = self._mode(commits, mask)
+        self._arg(commits, (None, None, G1_BYTES), "u8", "commits")
+        P, S = commits.shape[0], commits.shape[1]
+        if S < (degree + 1) * (degree + 2) // 2:
+            raise ValueError("commits: a commitment of degree %d holds %d points" % (degree, (degree + 1) * (degree + 2) // 2))
+        out = self._empty(dev, (degree + 1, G1_BYTES), ref=commits)
+        st = self._empty(dev, (degree + 1,), ref=commits)
+        if P == 0:                                   # the empty sum (the C entry treats P = 0 as a no-op)
+            out[:] = 0
+            out[:, 0] = 0x40
+            st[:] = 0
+            return out, st
+        self._call("tc_bivar_commitment_row0_sum_batch", _ptr(commits), S * G1_BYTES, int(degree), P, self._mask(mask, P, "mask"), _ptr(out),
+                   _ptr(st))
+        return out, st
+
+    def fr_sum(self, vals_fr, mask=None):
+        """Poly::add_assign per coefficient: vals_fr (n, B, 32) -> out[j] = sum of the included vals_fr[k, j] mod r: (B, 32), status (B,)"""
+        dev = self._mode(vals_fr, mask)
+        self._arg(vals_fr, (None, None, FR_BYTES), "u8", "vals_fr")
+        n, B = vals_fr.shape[0], vals_fr.shape[1]
+        out = self._empty(dev, (B, FR_BYTES), ref=vals_fr)
+        st = self._empty(dev, (B,), ref=vals_fr)
+        self._call("tc_fr_sum_batch", _ptr(vals_fr) if n else None, B * FR_BYTES, n, self._mask(mask, n, "mask"), B, _ptr(out), _ptr(st))
+        return out, st
+
+    def dkg_generate(self, commits, degree, accept=None, xs=None, vals_fr=None):
+        """The finalisation in one call: commits (P, S, 96), accept (P,) u8 or None = all, and for a node with a secret its samples
+        xs (P, n_v) u64 and vals_fr (P, n_v, 32) -> (the key set's commitment (degree+1, 96), the share (32,) or None, part_status
+        (P,)).  When an accepted part fails, the commitment is identities and the share zero."""
+        dev = self._mode(commits, accept, xs, vals_fr)
+        self._arg(commits, (None, None, G1_BYTES), "u8", "commits")
+        P, S = commits.shape[0], commits.shape[1]
+        if S < (degree + 1) * (degree + 2) // 2:
+            raise ValueError("commits: a commitment of degree %d holds %d points" % (degree, (degree + 1) * (degree + 2) // 2))
+        if (xs is None) != (vals_fr is None):
+            raise ValueError("xs and vals_fr come together")
+        n_v = 0
+        if xs is not None:
+            self._arg(xs, (P, None), "u64", "xs")
+            n_v = xs.shape[1]
+            self._arg(vals_fr, (P, n_v, FR_BYTES), "u8", "vals_fr")
+        out = self._empty(dev, (degree + 1, G1_BYTES), ref=commits)
+        share = self._empty(dev, (FR_BYTES,), ref=commits) if xs is not None else None
+        st = self._empty(dev, (P,), ref=commits)
+        if P == 0:
+            out[:] = 0
+            out[:, 0] = 0x40
+            if share is not None:
+                share[:] = 0
+            return out, share, st
+        self._call("tc_dkg_generate_batch", _ptr(commits), S * G1_BYTES, int(degree), P, self._mask(accept, P, "accept"),
+                   _ptr(xs) if n_v else None, _ptr(vals_fr) if n_v else None, n_v, _ptr(out), _ptr(share) if share is not None else None, _ptr(st))
+        return out, share, st
+
 
 class Group:
     """tc_group: several GPUs of one node driven from this process (one worker thread per GPU inside the library),

@@ -10,6 +10,10 @@ method names, group work on the MI355X behind the C ABI.
   BivarCommitment.verify_rows              tc_dkg_verify_rows_batch    (`row_poly.commitment() == bi_commit.row(m)`)
   Commitment.verify_values                 tc_dkg_verify_values_batch, or with a seed tc_dkg_verify_values_rlc_batch
                                            (`bi_commit.evaluate(m, s) == g1 * val`)
+  Commitment.__add__ / Commitment.sum      tc_g1_sum_batch             (Commitment::add_assign, src/poly.rs:462-471)
+  Poly.sum                                 tc_fr_sum_batch             (Poly::add_assign, src/poly.rs:68-80)
+  BivarCommitment.row0_sum                 tc_bivar_commitment_row0_sum_batch (`sum_commit += bi_commit.row(0)`)
+  dkg_generate                             tc_dkg_generate_batch       (the accepted parts -> commitment and share)
 
 Secret polynomials (Poly, BivarPoly) are Fr coefficient lists.  Poly.evaluate, BivarPoly.row and add/mul keep their
 host form (key generation outside the hot path in the reference; SecretKeySet does the same in api.py); the batch
@@ -28,6 +32,15 @@ def into_fr(x):
 
 def _fr_rows(vals):
     return _stack([into_fr(v).to_bytes(32, "little") for v in vals], 32)
+
+
+def _mask_bytes(mask, n):
+    if mask is None:
+        return None
+    mask = [1 if m else 0 for m in mask]
+    if len(mask) != n:
+        raise ValueError("one mask entry per term")
+    return np.array(mask, dtype=np.uint8)
 
 
 def coeff_pos(i, j):
@@ -99,6 +112,27 @@ class Commitment:
             if x == 0:
                 out[k] = self.coeff[0]
         return out
+
+    def __add__(self, other):
+        """Commitment::add_assign (src/poly.rs:462-471)."""
+        return Commitment.sum([self, other])
+
+    @staticmethod
+    def sum(commits, mask=None, engine=None):
+        """Commitment::add_assign folded over `commits` on the device: shorter ones are padded with the identity, trailing
+        identities are dropped like remove_zeros (src/poly.rs:466-470).  mask: one truthy / falsy entry per commitment (an
+        excluded one is not even decoded), None = all."""
+        e = engine or default_engine()
+        commits = list(commits)
+        width = max([len(c.coeff) for c in commits] + [0])
+        if width == 0:
+            return Commitment([], _trusted=True)
+        inf = bytes([0x40]) + bytes(95)
+        pts = np.stack([_stack(c.coeff + [inf] * (width - len(c.coeff)), 96) for c in commits])
+        out, st = e.g1_sum(pts, _mask_bytes(mask, len(commits)))
+        for s in st:
+            _raise_status(s)
+        return Commitment(Commitment([bytes(p) for p in out], _trusted=True)._trimmed(), _trusted=True)
 
     def verify_values(self, xs, vals, seed=None, engine=None):
         """`bi_commit.evaluate(m, s) == g1 * val` (src/poly.rs:846-848) with self = bi_commit.row(m): one bool per
@@ -173,6 +207,23 @@ class Poly:
         n = max(len(self.coeff), len(other.coeff))
         g = lambda p, k: p.coeff[k] if k < len(p.coeff) else 0
         return Poly([(g(self, k) + g(other, k)) % _R for k in range(n)])
+
+    @staticmethod
+    def sum(polys, mask=None, engine=None):
+        """Poly::add_assign (src/poly.rs:68-80) folded over `polys` on the device (the staged coefficients are wiped there)."""
+        e = engine or default_engine()
+        polys = list(polys)
+        width = max([len(p.coeff) for p in polys] + [0])
+        if width == 0:
+            return Poly([])
+        vals = np.zeros((len(polys), width, 32), dtype=np.uint8)
+        for k, p in enumerate(polys):
+            if p.coeff:
+                vals[k, :len(p.coeff)] = _fr_rows(p.coeff)
+        out, st = e.fr_sum(vals, _mask_bytes(mask, len(polys)))
+        for s in st:
+            _raise_status(s)
+        return Poly([int.from_bytes(bytes(c), "little") for c in out])
 
     def commitment(self, engine=None):
         """Poly::commitment (src/poly.rs:372-377)."""
@@ -306,6 +357,22 @@ class BivarCommitment:
         """BivarCommitment::evaluate (src/poly.rs:694-710) = row(x).evaluate(y)."""
         return self.row(x, engine).evaluate(y, engine)
 
+    @staticmethod
+    def row0_sum(commits, mask=None, engine=None):
+        """`sum_commit += bi_commit.row(0)` (src/poly.rs:895-898) over the included commitments of one degree: row(0)[i] is
+        coefficient (i, 0), so this is a plain sum of points."""
+        e = engine or default_engine()
+        commits = list(commits)
+        if not commits:
+            return Commitment([], _trusted=True)
+        d = commits[0].degree_
+        if any(c.degree_ != d for c in commits):
+            raise ValueError("all commitments of one batch must have the same degree")
+        out, st = e.bivar_row0_sum(np.stack([_stack(c.coeff, 96) for c in commits]), d, _mask_bytes(mask, len(commits)))
+        for s in st:
+            _raise_status(s)
+        return Commitment(Commitment([bytes(p) for p in out], _trusted=True)._trimmed(), _trusted=True)
+
     def verify_rows(self, xs, row_polys, engine=None):
         """`row_poly.commitment() == bi_commit.row(m)` (src/poly.rs:841-843) for several (m, row_poly) pairs under this
         commitment: (the row commitments, one bool per pair)"""
@@ -334,3 +401,44 @@ class BivarCommitment:
         out, ok = e.dkg_verify_rows(blob, d, np.array(xs, dtype=np.uint64), rows)
         rc = [Commitment([bytes(out[j, i]) for i in range(d + 1)], _trusted=True) for j in range(len(xs))]
         return rc, [bool(ok[j]) and ok_len[j] for j in range(len(xs))]
+
+
+def dkg_generate(bi_commits, accepted, samples=None, engine=None):
+    """The end of `distributed_key_generation` (src/poly.rs:870-876, 895-898) over the accepted parts: returns (the key set's
+    Commitment, this node's secret key share or None).  bi_commits: one BivarCommitment per dealer; accepted: one truthy /
+    falsy entry per dealer (None = all; a rejected dealer's commitment is never used); samples: per dealer the (u64 abscissa,
+    value) pairs this node received from that dealer's row -- a dict or a sequence, the same number for every dealer (a rejected
+    dealer's may be None) -- or None for an observer without a secret.  A failed accepted part raises."""
+    e = engine or default_engine()
+    bi_commits = list(bi_commits)
+    P = len(bi_commits)
+    if P == 0:
+        return Commitment([], _trusted=True), (0 if samples is not None else None)
+    d = bi_commits[0].degree_
+    if any(c.degree_ != d for c in bi_commits):
+        raise ValueError("all commitments of one batch must have the same degree")
+    acc = _mask_bytes(accepted, P)
+    xs = vals = None
+    if samples is not None:
+        if len(samples) != P:
+            raise ValueError("one set of samples per dealer")
+        taken = [acc is None or acc[p] for p in range(P)]
+        ordered = [(sorted(s.items()) if isinstance(s, dict) else list(s)) if t else None for s, t in zip(samples, taken)]
+        n_v = max([len(s) for s in ordered if s is not None] + [0])
+        if any(s is not None and len(s) != n_v for s in ordered):
+            raise ValueError("every accepted dealer needs the same number of samples")
+        if any(not 0 <= int(x) < 2 ** 64 for s in ordered if s is not None for x, _ in s):
+            raise ValueError("values are addressed by u64 abscissae")
+        xs = np.zeros((P, n_v), dtype=np.uint64)
+        vals = np.zeros((P, n_v, 32), dtype=np.uint8)
+        for p, s in enumerate(ordered):
+            if s is not None and n_v:
+                xs[p] = [int(x) for x, _ in s]
+                vals[p] = _fr_rows([y for _, y in s])
+    out, share, st = e.dkg_generate(np.stack([_stack(c.coeff, 96) for c in bi_commits]), d, acc, xs, vals)
+    for s in st:
+        if int(s) == 2:
+            raise ValueError("sample points must be distinct")   # the reference panics (src/poly.rs:404)
+        _raise_status(s)
+    commit = Commitment(Commitment([bytes(p) for p in out], _trusted=True)._trimmed(), _trusted=True)
+    return commit, (int.from_bytes(bytes(share), "little") if share is not None else None)
