@@ -294,6 +294,55 @@ int tc_encrypt_batch(tc_ctx* ctx, const uint8_t* pk_g1, size_t pk_stride, const 
 int tc_public_key_share_batch(tc_ctx* ctx, const uint8_t* commit, size_t t, const uint64_t* idx, size_t M, uint8_t* out,
                               uint8_t* status);
 
+/* ---- robust threshold combination: validate, select and combine in one call ---------------------- */
+/* What a node runs per message.  It holds up to N shares, slot i being node i's (abscissa i + 1, public key share
+ * Commitment::evaluate(i + 1)); some are absent, some may be forged; it must combine the first t+1 VALID ones and name the
+ * peers that sent bad ones.  Common to both entries:
+ *   commit    the PublicKeySet's (t+1) x 96 B commitment; commit[0] is the master key.  The N public key shares are computed
+ *             on the device once per call.  An undecodable commit -- in checked-input mode also a non-member one -- fails
+ *             EVERY job with TC_JOB_INVALID_ENCODING, the identity / zeros, used = bad = 0.
+ *   present   B x N bytes, NULL = every share is present.  An absent slot is never used, however malformed its bytes are
+ *             (the rule of `mask` in the DKG sums), in checked-input mode too.
+ *   used, bad B x N bytes each, optional, zero-initialised by the call.  status: B bytes.
+ *   limits    t + 1 <= N and B * N < 2^32; B = 0 is a no-op; a NULL context, or a NULL data pointer with a non-zero size,
+ *             answers TC_ERR_INVALID_ARG.  Both entries work in device-I/O mode.
+ * The flow is OPTIMISTIC, because a BLS signature (and a combined decryption share) is unique: if ANY t+1 shares combine to
+ * something that verifies under the master key, that something is the answer and none of those shares needs a check.
+ *  1. A job with fewer than t+1 present slots: TC_JOB_NOT_ENOUGH_SHARES, the identity's encoding, used = bad = 0.
+ *  2. Otherwise S0 = the first t+1 present slots in index order.  The job is CLEAN when all S0 shares decode, are group
+ *     members (checked-input mode) and their Lagrange combination verifies under commit[0].  Then status OK, out = the
+ *     combination, used marks S0, bad = 0.  A clean job makes NO CLAIM ABOUT INDIVIDUAL SHARES: two colluding wrong shares
+ *     whose errors cancel in the combination are not reported, and shares past S0 are never examined.
+ *  3. A job that is not clean is examined share by share: every present share gets its own check under pk_share(i) (and the
+ *     membership test in checked-input mode); bad[j*N + i] = 1 exactly for the present shares that fail it or do not decode.
+ *     Fewer than t+1 valid shares: TC_JOB_NOT_ENOUGH_SHARES and the identity (bad is still filled in).  Otherwise used marks
+ *     the first t+1 valid shares and out is their combination, which needs no further check.  *n_fallback (optional, host) =
+ *     the number of jobs that reached this step.
+ * With input checks off the caller vouches that the shares are group members, as for the other combined entries: a pairing
+ * cannot see a small-order component (it is killed by the final exponentiation), so a non-member share could pass its
+ * check and still spoil the combination. */
+/* Signatures: the loop of examples/threshold_sig.rs:115-131 over PublicKeyShare::verify (src/lib.rs:177-179) followed by
+ * PublicKeySet::combine_signatures (src/lib.rs:608-615).  sig_shares: B x N x 192.  Exactly one of `hashes` (B x 192 hash
+ * points) and `msgs` / `off` (hashed on the device) is given.  out_sig: B x 192.  The combinations of step 2 are verified
+ * under the one master key by random linear combination: `group`, `seed32` and the 2^-63 of a wrongly passing group are
+ * tc_verify_g2_rlc_batch's (seed32: 32 secret bytes in HOST memory in both I/O modes, wiped from the staging buffers), so
+ * the semantics above hold up to that probability. */
+int tc_combine_signatures_robust_batch(tc_ctx* ctx, const uint8_t* commit, size_t t, size_t N, const uint8_t* present,
+                                       const uint8_t* sig_shares, const uint8_t* hashes, const uint8_t* msgs, const uint64_t* off, size_t B,
+                                       size_t group, const uint8_t* seed32, uint8_t* out_sig, uint8_t* used, uint8_t* bad, uint8_t* status,
+                                       uint64_t* n_fallback);
+/* Decryption: the loop of examples/threshold_enc.rs over PublicKeyShare::verify_decryption_share (src/lib.rs:182-186)
+ * followed by PublicKeySet::decrypt (src/lib.rs:618-626).  shares_g1: B x N x 96; u / v / off / w: the ciphertexts;
+ * out_plain has the layout of v: xor_with_hash(g, v) of a job that ends OK, zeros otherwise.  The check of step 2 is
+ * verify_decryption_share of the combination under the master key, e(g, hash_g1_g2(u, v)) == e(commit[0], w), one per job;
+ * step 3 the same under pk_share(i).  u and w are tested for membership in checked-input mode, as in
+ * tc_verify_decryption_share_batch.  An INVALID CIPHERTEXT (Ciphertext::verify fails, or u / w undecodable or non-member)
+ * makes every honest share fail its check: the job ends as TC_JOB_NOT_ENOUGH_SHARES with all present shares marked bad --
+ * validate ciphertexts first (tc_ciphertext_verify_batch) when that blame would be acted on. */
+int tc_decrypt_robust_batch(tc_ctx* ctx, const uint8_t* commit, size_t t, size_t N, const uint8_t* present, const uint8_t* shares_g1,
+                            const uint8_t* u_g1, const uint8_t* v, const uint64_t* off, const uint8_t* w_g2, size_t B, uint8_t* out_plain,
+                            uint8_t* used, uint8_t* bad, uint8_t* status, uint64_t* n_fallback);
+
 /* ---- DKG algebra (src/poly.rs) ----------------------------------------------------------------- */
 /* out[i] = coeff_fr[i] * g1: Poly::commitment src/poly.rs:372-377 and BivarPoly::commitment :625-632 (every
  * coefficient times the G1 generator).  Fixed base: a signed 4-bit window table of g1, built once per context

@@ -530,7 +530,84 @@ class PublicKeySet {
     return decrypt_fr(ordered, ct, e);
   }
 
+  // What a node runs per message -- the loop of examples/threshold_sig.rs:115-131 followed by combine_signatures
+  // (src/lib.rs:608-615) -- as ONE device call (tc_combine_signatures_robust_batch).  jobs[j] maps node index (< n_nodes) to
+  // the share received from that node for message j: some nodes may be missing, some shares forged.  The first t+1 received
+  // shares are combined and the combination verified under the master key; only a message whose combination does not verify
+  // has its shares checked one by one.  A message that verified at once reports no bad index and makes no claim about its
+  // individual shares.  status: TC_JOB_OK or TC_JOB_NOT_ENOUGH_SHARES (TC_JOB_INVALID_ENCODING for every job: a bad key set).
+  struct RobustResult {
+    std::uint8_t status = 0;
+    std::vector<std::uint64_t> used, bad;  // node indices, ascending
+  };
+  std::vector<Signature> combine_signatures_robust_batch(const std::vector<std::map<std::uint64_t, SignatureShare>>& jobs, const Messages& msgs,
+                                                         std::size_t n_nodes, const std::array<std::uint8_t, 32>& seed,
+                                                         std::vector<RobustResult>& results, std::uint64_t* n_fallback = nullptr,
+                                                         Engine& e = Engine::instance()) const {
+    const std::size_t B = jobs.size(), N = n_nodes;
+    if (msgs.size() != B) throw std::invalid_argument("one message per share set");
+    std::vector<std::uint8_t> sh(B * N * 192 + 1), present(B * N + 1, 0), flat(B * 192 + 1), used(B * N + 1), bad(B * N + 1), st(B + 1);
+    for (std::size_t j = 0; j < B; j++)
+      for (const auto& kv : jobs[j]) {
+        if (kv.first >= N) throw std::invalid_argument("node index outside 0..n_nodes-1");
+        std::memcpy(&sh[(j * N + kv.first) * 192], kv.second.sig.g2.data(), 192);
+        present[j * N + kv.first] = 1;
+      }
+    std::vector<std::uint8_t> commit(commit_.size() * 96);
+    for (std::size_t k = 0; k < commit_.size(); k++) std::memcpy(&commit[k * 96], commit_[k].data(), 96);
+    if (B)
+      e.check(tc_combine_signatures_robust_batch(e.ctx(), commit.data(), threshold(), N, present.data(), sh.data(), nullptr, msgs.data(),
+                                                 msgs.off.data(), B, 0, seed.data(), flat.data(), used.data(), bad.data(), st.data(), n_fallback));
+    std::vector<Signature> out(B);
+    robust_results(B, N, st, used, bad, results);
+    for (std::size_t j = 0; j < B; j++) std::memcpy(out[j].g2.data(), &flat[j * 192], 192);
+    return out;
+  }
+  // The same for threshold decryption -- the loop of examples/threshold_enc.rs followed by PublicKeySet::decrypt
+  // (src/lib.rs:618-626) -- tc_decrypt_robust_batch.  Returns the plaintexts (empty for a ciphertext that did not end OK).  An
+  // invalid ciphertext makes every share fail: NotEnoughShares with every received share marked bad.
+  std::vector<Bytes> decrypt_robust_batch(const std::vector<std::map<std::uint64_t, DecryptionShare>>& jobs, const std::vector<Ciphertext>& cts,
+                                          std::size_t n_nodes, std::vector<RobustResult>& results, std::uint64_t* n_fallback = nullptr,
+                                          Engine& e = Engine::instance()) const {
+    const std::size_t B = jobs.size(), N = n_nodes;
+    if (cts.size() != B) throw std::invalid_argument("one ciphertext per share set");
+    std::vector<std::uint8_t> sh(B * N * 96 + 1), present(B * N + 1, 0), u(B * 96 + 1), w(B * 192 + 1), used(B * N + 1), bad(B * N + 1), st(B + 1);
+    Messages v;
+    for (std::size_t j = 0; j < B; j++) {
+      for (const auto& kv : jobs[j]) {
+        if (kv.first >= N) throw std::invalid_argument("node index outside 0..n_nodes-1");
+        std::memcpy(&sh[(j * N + kv.first) * 96], kv.second.g1.data(), 96);
+        present[j * N + kv.first] = 1;
+      }
+      std::memcpy(&u[j * 96], cts[j].u.data(), 96);
+      std::memcpy(&w[j * 192], cts[j].w.data(), 192);
+      v.push(cts[j].v);
+    }
+    std::vector<std::uint8_t> commit(commit_.size() * 96);
+    for (std::size_t k = 0; k < commit_.size(); k++) std::memcpy(&commit[k * 96], commit_[k].data(), 96);
+    Bytes plain(v.flat.size() + 1);
+    if (B)
+      e.check(tc_decrypt_robust_batch(e.ctx(), commit.data(), threshold(), N, present.data(), sh.data(), u.data(), v.data(), v.off.data(), w.data(), B,
+                                      plain.data(), used.data(), bad.data(), st.data(), n_fallback));
+    robust_results(B, N, st, used, bad, results);
+    std::vector<Bytes> out(B);
+    for (std::size_t j = 0; j < B; j++)
+      if (st[j] == TC_JOB_OK) out[j].assign(plain.begin() + v.off[j], plain.begin() + v.off[j + 1]);
+    return out;
+  }
+
  private:
+  static void robust_results(std::size_t B, std::size_t N, const std::vector<std::uint8_t>& st, const std::vector<std::uint8_t>& used,
+                             const std::vector<std::uint8_t>& bad, std::vector<RobustResult>& results) {
+    results.assign(B, RobustResult{});
+    for (std::size_t j = 0; j < B; j++) {
+      results[j].status = st[j];
+      for (std::size_t i = 0; i < N; i++) {
+        if (used[j * N + i]) results[j].used.push_back(i);
+        if (bad[j * N + i]) results[j].bad.push_back(i);
+      }
+    }
+  }
   Bytes decrypt_fr(const std::vector<std::pair<FrIndex, const DecryptionShare*>>& ordered, const Ciphertext& ct, Engine& e) const {
     const std::size_t n = ordered.size();
     std::vector<std::uint8_t> idx(n * 32 + 1), sh(n * 96 + 1);

@@ -532,6 +532,90 @@ impl PublicKeySet {
         })?;
         Ok(ok.chunks(n_nodes).map(|r| r.iter().map(|&b| b == 1).collect()).collect())
     }
+    /// What a node runs per message -- the loop of examples/threshold_sig.rs:115-131 followed by `combine_signatures`
+    /// (src/lib.rs:608-615) -- as ONE device call (tc_combine_signatures_robust_batch).  `jobs[j]` maps node index
+    /// (< n_nodes) to the share received from that node for `msgs[j]`; nodes may be missing, shares may be forged.  The first
+    /// t+1 received shares are combined and the combination verified under the master key; only a message whose combination
+    /// does not verify has its shares checked one by one.  Per message: the signature (or `NotEnoughShares`), the node
+    /// indices whose shares were used and the ones whose shares are bad.  A message that verified at once reports no bad
+    /// index and makes no claim about its individual shares.
+    pub fn combine_signatures_robust_batch<M: AsRef<[u8]>>(&self, gpu: &Gpu, n_nodes: usize, jobs: &[std::collections::BTreeMap<u64, SignatureShare>], msgs: &[M], seed: &[u8; 32]) -> GpuResult<Vec<RobustResult<Signature>>> {
+        if jobs.len() != msgs.len() {
+            return Err(shape_error("one message per share set"));
+        }
+        if jobs.is_empty() {
+            return Ok(Vec::new());
+        }
+        if n_nodes == 0 {
+            return Err(shape_error("n_nodes must be at least t + 1"));
+        }
+        let (mut shares, mut present) = (vec![0u8; jobs.len() * n_nodes * G2_BYTES], vec![0u8; jobs.len() * n_nodes]);
+        for (j, job) in jobs.iter().enumerate() {
+            for (&i, s) in job {
+                let slot = if (i as usize) < n_nodes { j * n_nodes + i as usize } else { return Err(shape_error("node index outside 0..n_nodes")) };
+                shares.get_mut(slot * G2_BYTES..(slot + 1) * G2_BYTES).ok_or_else(|| shape_error("node index outside 0..n_nodes"))?.copy_from_slice(&g2_bytes(&(s.0).0));
+                *present.get_mut(slot).ok_or_else(|| shape_error("node index outside 0..n_nodes"))? = 1;
+            }
+        }
+        let commit = self.commit_bytes();
+        let (flat, off) = pack_messages(msgs);
+        let (mut out, mut st) = (vec![0u8; jobs.len() * G2_BYTES], vec![0u8; jobs.len()]);
+        let (mut used, mut bad) = (vec![0u8; jobs.len() * n_nodes], vec![0u8; jobs.len() * n_nodes]);
+        let mut fallback = 0u64;
+        gpu.check(unsafe {
+            tc_combine_signatures_robust_batch(gpu.0, commit.as_ptr(), self.threshold(), n_nodes, present.as_ptr(), shares.as_ptr(), std::ptr::null(), flat.as_ptr(), off.as_ptr(), jobs.len(), 0, seed.as_ptr(), out.as_mut_ptr(), used.as_mut_ptr(), bad.as_mut_ptr(), st.as_mut_ptr(), &mut fallback)
+        })?;
+        st.iter()
+            .zip(out.chunks(G2_BYTES))
+            .zip(used.chunks(n_nodes).zip(bad.chunks(n_nodes)))
+            .map(|((&s, o), (u, b))| Ok(RobustResult { value: status_to_result(s, g2_from(o).map(Signature))?, used: marked(u), bad: marked(b) }))
+            .collect()
+    }
+    /// The same for threshold decryption -- the loop of examples/threshold_enc.rs followed by `decrypt` (src/lib.rs:618-626) --
+    /// tc_decrypt_robust_batch.  An invalid ciphertext makes every share fail: `NotEnoughShares` with every received share bad.
+    pub fn decrypt_robust_batch(&self, gpu: &Gpu, n_nodes: usize, jobs: &[std::collections::BTreeMap<u64, DecryptionShare>], cts: &[Ciphertext]) -> GpuResult<Vec<RobustResult<Vec<u8>>>> {
+        if jobs.len() != cts.len() {
+            return Err(shape_error("one ciphertext per share set"));
+        }
+        if jobs.is_empty() {
+            return Ok(Vec::new());
+        }
+        if n_nodes == 0 {
+            return Err(shape_error("n_nodes must be at least t + 1"));
+        }
+        let (mut shares, mut present) = (vec![0u8; jobs.len() * n_nodes * G1_BYTES], vec![0u8; jobs.len() * n_nodes]);
+        for (j, job) in jobs.iter().enumerate() {
+            for (&i, s) in job {
+                let slot = if (i as usize) < n_nodes { j * n_nodes + i as usize } else { return Err(shape_error("node index outside 0..n_nodes")) };
+                shares.get_mut(slot * G1_BYTES..(slot + 1) * G1_BYTES).ok_or_else(|| shape_error("node index outside 0..n_nodes"))?.copy_from_slice(&g1_bytes(&s.0));
+                *present.get_mut(slot).ok_or_else(|| shape_error("node index outside 0..n_nodes"))? = 1;
+            }
+        }
+        let commit = self.commit_bytes();
+        let (u, flat, off, w) = ciphertext_columns(cts);
+        let (mut out, mut st) = (vec![0u8; flat.len()], vec![0u8; jobs.len()]);
+        let (mut used, mut bad) = (vec![0u8; jobs.len() * n_nodes], vec![0u8; jobs.len() * n_nodes]);
+        let mut fallback = 0u64;
+        gpu.check(unsafe {
+            tc_decrypt_robust_batch(gpu.0, commit.as_ptr(), self.threshold(), n_nodes, present.as_ptr(), shares.as_ptr(), u.as_ptr(), flat.as_ptr(), off.as_ptr(), w.as_ptr(), jobs.len(), out.as_mut_ptr(), used.as_mut_ptr(), bad.as_mut_ptr(), st.as_mut_ptr(), &mut fallback)
+        })?;
+        Ok(st
+            .iter()
+            .zip(off.windows(2))
+            .zip(used.chunks(n_nodes).zip(bad.chunks(n_nodes)))
+            .map(|((&s, o), (u, b))| RobustResult { value: wire_status_to_result(s, out.get(o[0] as usize..o[1] as usize).map(|p| p.to_vec()).unwrap_or_default()), used: marked(u), bad: marked(b) })
+            .collect())
+    }
+}
+/// One message of the robust combiners: the value or the job's error, and the node indices used / found bad.
+#[derive(Debug, PartialEq)]
+pub struct RobustResult<T> {
+    pub value: JobResult<T>,
+    pub used: Vec<u64>,
+    pub bad: Vec<u64>,
+}
+fn marked(row: &[u8]) -> Vec<u64> {
+    row.iter().enumerate().filter(|(_, &b)| b != 0).map(|(i, _)| i as u64).collect()
 }
 
 // ---- A9: verification (src/lib.rs:108-117) ----------------------------------------------------------------------------

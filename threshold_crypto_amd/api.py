@@ -552,6 +552,61 @@ class PublicKeySet:
         res = [bytes(out[int(off[j]): int(off[j + 1])]) for j in range(len(jobs))]
         return res, st
 
+    def _robust_operands(self, jobs, n_nodes, width):
+        """jobs[j]: mapping node index -> share (a value of this module, or its raw uncompressed bytes as received: a forged
+        share need not be a group element).  Returns (N, shares (B, N, width), present (B, N))."""
+        N = int(n_nodes) if n_nodes is not None else max([int(i) + 1 for j in jobs for i in j] + [self.threshold() + 1])
+        sh = np.zeros((len(jobs), N, width), dtype=np.uint8)
+        present = np.zeros((len(jobs), N), dtype=np.uint8)
+        for j, job in enumerate(jobs):
+            for i, s in dict(job).items():
+                i = int(i)
+                if not 0 <= i < N:
+                    raise ValueError("node index %d outside 0..%d" % (i, N - 1))
+                raw = bytes(getattr(s, "raw", s))
+                if len(raw) != width:
+                    raise ValueError("share of node %d: expected %d bytes" % (i, width))
+                sh[j, i] = np.frombuffer(raw, dtype=np.uint8)
+                present[j, i] = 1
+        return N, sh, present
+
+    @staticmethod
+    def _robust_result(value, status, used_row, bad_row):
+        st = int(status)
+        res = value if st == 0 else _STATUS_EXC.get(st, Error)("job status %d" % st)
+        return res, [int(i) for i in np.nonzero(used_row)[0]], [int(i) for i in np.nonzero(bad_row)[0]]
+
+    def combine_signatures_robust_batch(self, jobs, msgs, n_nodes=None, engine=None, seed=None, group=0):
+        """What a node runs per message (the loop of examples/threshold_sig.rs:115-131 followed by combine_signatures,
+        src/lib.rs:608-615) as ONE device call, tc_combine_signatures_robust_batch: jobs[j] maps node index -> the share
+        received from that node for msgs[j]; some nodes may be missing, some shares forged.  The first t+1 received shares are
+        combined and the combination verified under the master key; only a message whose combination does not verify has
+        its shares checked one by one.  Returns one (Signature | NotEnoughShares, used node indices, bad node indices) per
+        message.  A message that verified at once reports no bad index and makes no claim about its individual shares."""
+        e = engine or default_engine()
+        if len(jobs) != len(msgs):
+            raise ValueError("one message per share set")
+        N, sh, present = self._robust_operands(jobs, n_nodes, 192)
+        flat, off = pack_messages([bytes(m) for m in msgs])
+        out, used, bad, st, _ = e.combine_signatures_robust(_stack(self.commit, 96), sh, msgs=flat, off=off, present=present, group=group,
+                                                            seed=seed)
+        return [self._robust_result(Signature(out[j], _trusted=True) if not int(st[j]) else None, st[j], used[j], bad[j])
+                for j in range(len(jobs))]
+
+    def decrypt_robust_batch(self, jobs, cts, n_nodes=None, engine=None):
+        """The same for threshold decryption (the loop of examples/threshold_enc.rs followed by PublicKeySet::decrypt,
+        src/lib.rs:618-626), tc_decrypt_robust_batch: jobs[j] maps node index -> the DecryptionShare received for cts[j].
+        Returns one (plaintext bytes | NotEnoughShares, used node indices, bad node indices) per ciphertext.  An invalid
+        ciphertext makes every share fail: NotEnoughShares with every received share marked bad."""
+        e = engine or default_engine()
+        if len(jobs) != len(cts):
+            raise ValueError("one ciphertext per share set")
+        N, sh, present = self._robust_operands(jobs, n_nodes, 96)
+        v, off = pack_messages([c.v for c in cts])
+        out, used, bad, st, _ = e.decrypt_robust(_stack(self.commit, 96), sh, _stack([c.u for c in cts], 96), v, off,
+                                                 _stack([c.w for c in cts], 192), present=present)
+        return [self._robust_result(bytes(out[int(off[j]): int(off[j + 1])]), st[j], used[j], bad[j]) for j in range(len(jobs))]
+
 
 class SecretKeySet:
     """struct SecretKeySet { poly: Poly } (src/lib.rs:631-635); poly = Fr coefficients."""

@@ -2,6 +2,7 @@
 // batch entry points.  Host code only; every computation is a gfx950 kernel launch (see
 // tc_launch.h).  There is no CPU compute path: without a HIP device tc_ctx_create fails.
 #include "tc_launch.h"
+#include "tc_robust.h"
 #include "../../include/tc_amd.h"
 
 #include <stdio.h>
@@ -1286,37 +1287,15 @@ int tc_verify_shares_rlc_batch(tc_ctx* ctx, const uint8_t* pk_shares, size_t N, 
   return on_exception((tc_ctx*)ctx);
 }
 
-// Signature batches under ONE key (BASELINE config 3's shape: 65 536 verifies under the master key) by random linear
-// combination, opt-in: the batch is cut into groups of `group` jobs, and a group passes with ONE check
-//     e(pk, sum_j r_j H_j) == e(g1, sum_j r_j sig_j)          (bilinearity; r_j secret, 2^63 values each)
-// instead of `group` checks of src/lib.rs:109; a group that fails (or holds an undecodable / non-member operand) is
-// re-checked job by job, so ok[] equals tc_verify_g2_batch's up to the 2^-63 of a wrongly passing group.  The two sums
-// are 16-column ladders over the psi-images (the two-stage kernels' short-scalar mode).  hash == nullptr: the hash points
-// are made on the device from msgs / off first (tc_verify_sig_batch's composition, hash constant folded into g1).
-static int verify_rlc(tc_ctx* ctx, const uint8_t* pk, const uint8_t* sig, const uint8_t* hash, const uint8_t* msgs, const uint64_t* off,
-                      size_t B, size_t group, const uint8_t* seed32, uint8_t* ok, uint64_t* n_fallback) {
-  TC_REQUIRE(ctx);
-  if (n_fallback) *n_fallback = 0;
-  if (B == 0) return TC_OK;
-  TC_REQUIRE(ctx && pk && sig && (hash || off) && seed32 && ok);
-  TC_REQUIRE(B < (1ull << 32));
-  if (group == 0) group = 64;
-  if (group > 1024) group = 1024;
-  if (group > B) group = B;
-  Call k(ctx);
-  uint64_t total = 0;
-  if (!hash) {
-    if (!total_bytes(k, off, B, &total)) return k.finish();
-    TC_REQUIRE(total == 0 || msgs);
-  }
-  const uint8_t* d_pk = k.in(pk, 96);
-  const uint8_t* d_sig = k.in(sig, B * 192);
-  const uint8_t* d_hash_in = hash ? k.in(hash, B * 192) : nullptr;
-  const uint8_t* d_msgs = hash ? nullptr : k.in(msgs, (size_t)total);
-  const uint64_t* d_off = hash ? nullptr : k.in(off, B + 1);
-  uint8_t* d_hash_own = hash ? nullptr : k.temp<uint8_t>(B * 192);
-  const uint8_t* d_hash = hash ? d_hash_in : d_hash_own;
-  const uint8_t* d_g1 = hash ? ctx->g1_gen : ctx->g1_gen_unfix;
+// The device temporaries of one pass of group checks over B jobs (seed32: HOST memory, copied here and wiped after the call).
+struct RlcWs {
+  size_t group, G, tail, NG;
+  uint8_t *d_seed, *d_r, *d_S, *d_H, *d_st, *d_okg;
+};
+static RlcWs rlc_workspace(Call& k, size_t B, size_t group, const uint8_t* seed32) {
+  tc_ctx* ctx = k.c;
+  RlcWs w{};
+  w.group = group;
   uint8_t* d_seed = k.temp<uint8_t>(32);
   if (d_seed) {
     k.check(hipMemcpyAsync(d_seed, seed32, 32, hipMemcpyHostToDevice, ctx->stream), "seed copy");
@@ -1326,18 +1305,32 @@ static int verify_rlc(tc_ctx* ctx, const uint8_t* pk, const uint8_t* sig, const 
   uint8_t* d_r = k.temp<uint8_t>(B * 32);
   if (d_r) k.wipe.emplace_back(d_r, B * 32);
   const size_t G = B / group, tail = B % group, NG = G + (tail ? 1 : 0);
-  uint8_t* d_S = k.temp<uint8_t>(NG * 192);
-  uint8_t* d_H = k.temp<uint8_t>(NG * 192);
-  uint8_t* d_st = k.temp<uint8_t>(2 * NG);
-  uint8_t* d_okg = k.temp<uint8_t>(NG);
-  uint8_t* d_ok = k.out(ok, B);
-  k.begin_timing();
-  k.check_points(false, d_pk, 0, 1, 1, B, 1);
-  k.check_points(true, d_sig, 192, 1, 1, B, 1);
-  if (hash) k.check_points(true, d_hash, 192, 1, 1, B, 1);
+  w.G = G;
+  w.tail = tail;
+  w.NG = NG;
+  w.d_seed = d_seed;
+  w.d_r = d_r;
+  w.d_S = k.temp<uint8_t>(NG * 192);
+  w.d_H = k.temp<uint8_t>(NG * 192);
+  w.d_st = k.temp<uint8_t>(2 * NG);
+  w.d_okg = k.temp<uint8_t>(NG);
+  return w;
+}
+// The group checks of verify_rlc over DEVICE operands, inside the caller's Call: d_ok[j] (B bytes) = e(pk, hash_j) ==
+// e(g1, sig_j) up to the 2^-63 of a wrongly passing group.  d_g1 is the generator that matches the hash points (g1_gen, or
+// g1_gen_unfix for hash points without their last constant multiplication).  The pending membership tests of the Call
+// (check_points: the key's first, then one verdict per job each) are consumed here and send their groups to the per-job
+// checks; member_checks: the per-job checks test sig (and the hash points when hash_is_operand) and the key for membership
+// again, as tc_verify_g2_batch would.  tc_combine_signatures_robust_batch runs this over the combinations it has just made,
+// with no pending test and member_checks off.  *n_fallback (optional) = jobs that went through the per-job checks.
+static void rlc_group_checks(Call& k, const RlcWs& w, const uint8_t* d_pk, const uint8_t* d_sig, const uint8_t* d_hash, const uint8_t* d_g1,
+                             size_t B, bool member_checks, bool hash_is_operand, uint8_t* d_ok, uint64_t* n_fallback) {
+  tc_ctx* ctx = k.c;
+  const size_t group = w.group, G = w.G, tail = w.tail, NG = w.NG;
+  uint8_t *d_seed = w.d_seed, *d_r = w.d_r, *d_S = w.d_S, *d_H = w.d_H, *d_st = w.d_st, *d_okg = w.d_okg;
+  const bool hash = hash_is_operand;
   std::vector<uint8_t> h_okg(NG), h_st(2 * NG), h_valid;
   if (!k.failed) {
-    if (!hash) tc::launch_hash_g2(ctx->tuning, ctx->stream, d_msgs, d_off, B, d_hash_own, /*fix=*/false);
     tc::launch_rlc_scalars(ctx->stream, d_seed, B, d_r);
     k.check(hipMemsetAsync(d_st, 0, 2 * NG, ctx->stream), "memset");
     const uint32_t* rr = reinterpret_cast<const uint32_t*>(d_r);
@@ -1394,7 +1387,7 @@ static int verify_rlc(tc_ctx* ctx, const uint8_t* pk, const uint8_t* sig, const 
         tc::launch_gather_rows(ctx->stream, d_sig, 192, d_map, R, c_sig);
         tc::launch_gather_rows(ctx->stream, d_hash, 192, d_map, R, c_hash);
         tc::launch_pairing_check(ctx->stream, d_pk, 0, c_hash, 192, d_g1, 0, c_sig, 192, R, c_ok, k.pairing_ws(R));
-        if (ctx->input_checks) {  // members only, as the per-job path would require
+        if (member_checks) {  // members only, as the per-job path would require
           uint8_t* v = k.temp<uint8_t>(R);
           tc::launch_subgroup_check_g2(ctx->stream, c_sig, 192, 1, 1, R, v);
           tc::launch_invalidate_jobs(ctx->stream, v, 1, 1, R, nullptr, nullptr, 0, c_ok);
@@ -1410,6 +1403,49 @@ static int verify_rlc(tc_ctx* ctx, const uint8_t* pk, const uint8_t* sig, const 
       }
       if (n_fallback) *n_fallback = R;
     }
+  }
+}
+
+// Signature batches under ONE key (BASELINE config 3's shape: 65 536 verifies under the master key) by random linear
+// combination, opt-in: the batch is cut into groups of `group` jobs, and a group passes with ONE check
+//     e(pk, sum_j r_j H_j) == e(g1, sum_j r_j sig_j)          (bilinearity; r_j secret, 2^63 values each)
+// instead of `group` checks of src/lib.rs:109; a group that fails (or holds an undecodable / non-member operand) is
+// re-checked job by job, so ok[] equals tc_verify_g2_batch's up to the 2^-63 of a wrongly passing group.  The two sums
+// are 16-column ladders over the psi-images (the two-stage kernels' short-scalar mode).  hash == nullptr: the hash points
+// are made on the device from msgs / off first (tc_verify_sig_batch's composition, hash constant folded into g1).
+static int verify_rlc(tc_ctx* ctx, const uint8_t* pk, const uint8_t* sig, const uint8_t* hash, const uint8_t* msgs, const uint64_t* off,
+                      size_t B, size_t group, const uint8_t* seed32, uint8_t* ok, uint64_t* n_fallback) {
+  TC_REQUIRE(ctx);
+  if (n_fallback) *n_fallback = 0;
+  if (B == 0) return TC_OK;
+  TC_REQUIRE(ctx && pk && sig && (hash || off) && seed32 && ok);
+  TC_REQUIRE(B < (1ull << 32));
+  if (group == 0) group = 64;
+  if (group > 1024) group = 1024;
+  if (group > B) group = B;
+  Call k(ctx);
+  uint64_t total = 0;
+  if (!hash) {
+    if (!total_bytes(k, off, B, &total)) return k.finish();
+    TC_REQUIRE(total == 0 || msgs);
+  }
+  const uint8_t* d_pk = k.in(pk, 96);
+  const uint8_t* d_sig = k.in(sig, B * 192);
+  const uint8_t* d_hash_in = hash ? k.in(hash, B * 192) : nullptr;
+  const uint8_t* d_msgs = hash ? nullptr : k.in(msgs, (size_t)total);
+  const uint64_t* d_off = hash ? nullptr : k.in(off, B + 1);
+  uint8_t* d_hash_own = hash ? nullptr : k.temp<uint8_t>(B * 192);
+  const uint8_t* d_hash = hash ? d_hash_in : d_hash_own;
+  const uint8_t* d_g1 = hash ? ctx->g1_gen : ctx->g1_gen_unfix;
+  const RlcWs ws = rlc_workspace(k, B, group, seed32);
+  uint8_t* d_ok = k.out(ok, B);
+  k.begin_timing();
+  k.check_points(false, d_pk, 0, 1, 1, B, 1);
+  k.check_points(true, d_sig, 192, 1, 1, B, 1);
+  if (hash) k.check_points(true, d_hash, 192, 1, 1, B, 1);
+  if (!k.failed) {
+    if (!hash) tc::launch_hash_g2(ctx->tuning, ctx->stream, d_msgs, d_off, B, d_hash_own, /*fix=*/false);
+    rlc_group_checks(k, ws, d_pk, d_sig, d_hash, d_g1, B, ctx->input_checks, hash != nullptr, d_ok, n_fallback);
   }
   k.end_timing();
   return k.finish();
@@ -1820,6 +1856,243 @@ int tc_verify_decryption_shares_rlc_batch(tc_ctx* ctx, const uint8_t* pk_shares,
   }
   k.end_timing();
   return k.finish();
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+// ---- robust combination ------------------------------------------------------------------------------
+// What a node runs per message: of up to N shares, some absent and some possibly forged, combine the first t+1 VALID ones and
+// name the senders of bad ones -- the loop of examples/threshold_sig.rs:115-131 followed by combine_signatures
+// (src/lib.rs:608-615), or the loop of examples/threshold_enc.rs followed by PublicKeySet::decrypt (src/lib.rs:618-626) --
+// optimistically.  Pass 1 combines the first t+1 PRESENT shares of every job and checks the combination under the master key
+// commit[0]; a BLS signature (a decryption share sum) is unique, so a combination that verifies is the answer and none of its
+// shares needs a check of its own.  Only the jobs whose combination does not stand go through pass 2: every present share
+// checked under its public key share, the first t+1 valid ones combined.  Selection, gather and re-selection run on the
+// device (k_robust.hip); the host sees B verdict bytes between the passes and builds the job maps of pass 2, as the other
+// combined entries do.  sig: G2 shares against hash points (hashes, or msgs / off hashed here); otherwise G1 decryption shares
+// against the ciphertexts (u, msgs = v, off, w) and the plaintexts as output.
+static int robust_combine(tc_ctx* ctx, bool sig, const uint8_t* commit, size_t t, size_t N, const uint8_t* present, const uint8_t* shares,
+                          const uint8_t* hashes, const uint8_t* msgs, const uint64_t* off, const uint8_t* u, const uint8_t* w, size_t B,
+                          size_t group, const uint8_t* seed32, uint8_t* out, bool out_unbacked, uint8_t* used, uint8_t* bad, uint8_t* status,
+                          uint64_t* n_fallback) {
+  TC_REQUIRE(ctx);
+  if (n_fallback) *n_fallback = 0;
+  if (B == 0) return TC_OK;
+  TC_REQUIRE(ctx && commit && shares && out && status);
+  TC_REQUIRE(t < (1u << 20));
+  TC_REQUIRE(t + 1 <= N);
+  TC_REQUIRE(N < (1ull << 32) && B < (1ull << 32) && B * N < (1ull << 32));
+  if (sig) TC_REQUIRE(seed32 && ((hashes != nullptr) != (off != nullptr)));
+  else TC_REQUIRE(u && off && w);
+  if (group == 0) group = 64;
+  if (group > 1024) group = 1024;
+  if (group > B) group = B;
+  const size_t PB = sig ? 192 : 96, need = t + 1;
+  Call k(ctx);
+  uint64_t total = 0;
+  if (off) {
+    if (!total_bytes(k, off, B, &total)) return k.finish();
+    TC_REQUIRE(total == 0 || msgs);
+    TC_REQUIRE(sig || total == 0 || !out_unbacked);
+  }
+  const uint8_t* d_commit = k.in(commit, need * 96);
+  const uint8_t* d_present = k.in(present, B * N);
+  const uint8_t* d_sh = k.in(shares, B * N * PB);
+  const uint8_t* d_hash_in = hashes ? k.in(hashes, B * 192) : nullptr;
+  const uint8_t* d_msgs = off ? k.in(msgs, (size_t)total) : nullptr;
+  const uint64_t* d_off = off ? k.in(off, B + 1) : nullptr;
+  const uint8_t* d_u = sig ? nullptr : k.in(u, B * 96);
+  const uint8_t* d_w = sig ? nullptr : k.in(w, B * 192);
+  uint8_t* d_status = k.out(status, B);
+  uint8_t* d_used = k.out(used, B * N, /*zero=*/true);
+  uint8_t* d_bad = k.out(bad, B * N, /*zero=*/true);
+  // the point result: the caller's signatures, or the G1 value the plaintext is masked with
+  uint8_t* d_res = sig ? k.out(out, B * 192) : k.temp<uint8_t>(B * 96);
+  uint8_t* d_plain = sig ? nullptr : k.out(out, (size_t)total, /*zero=*/true);  // failed jobs leave zeros
+  // the N public key shares, made once per call: Commitment::evaluate(i + 1), src/lib.rs:570-573
+  std::vector<uint64_t> h_slots(N);
+  for (size_t i = 0; i < N; i++) h_slots[i] = i;
+  uint64_t* d_pkidx = k.temp<uint64_t>(N);
+  uint8_t* d_pks = k.temp<uint8_t>(N * 96);
+  uint8_t* d_pkst = k.temp<uint8_t>(N, /*zero=*/true);
+  uint8_t* d_cval = k.temp<uint8_t>(need);
+  uint64_t* d_idx = k.temp<uint64_t>(B * need);
+  uint32_t* d_slot = k.temp<uint32_t>(B * need);
+  uint8_t* d_enough = k.temp<uint8_t>(B);
+  uint8_t* d_packed = k.temp<uint8_t>(B * need * PB);
+  uint8_t* d_comb = k.temp<uint8_t>(B * PB);
+  uint8_t* d_combc = sig ? nullptr : k.temp<uint8_t>(B * 96);
+  uint8_t* d_st1 = k.temp<uint8_t>(B, /*zero=*/true);
+  uint8_t* d_ok1 = k.temp<uint8_t>(B);
+  uint8_t* d_member = ctx->input_checks ? k.temp<uint8_t>(B * need) : nullptr;
+  uint8_t* d_verdict = k.temp<uint8_t>(B);
+  uint8_t* d_hash_own = hashes ? nullptr : k.temp<uint8_t>(B * 192);
+  const uint8_t* d_hash = hashes ? d_hash_in : d_hash_own;
+  // hash points made here lack their last constant multiplication: the generator side carries it (tc_verify_sig_batch)
+  const uint8_t* d_g1 = hashes ? ctx->g1_gen : ctx->g1_gen_unfix;
+  // what a job's own operands allow: 0 when its hash point / ciphertext is undecodable or, in checked-input mode, no group
+  // member -- every check of that job then fails, as tc_verify_g2_batch / tc_verify_decryption_share_batch answer ok = 0
+  uint8_t* d_jvalid = k.temp<uint8_t>(B);
+  uint8_t* d_jtmp = k.temp<uint8_t>(B);
+  RlcWs ws{};
+  if (sig) ws = rlc_workspace(k, B, group, seed32);
+  k.begin_timing();
+  std::vector<uint8_t> h_verdict(B), h_pkst(N), h_cval(need, 1);
+  std::vector<uint32_t> failed;
+  if (!k.failed) {
+    k.check(hipMemcpyAsync(d_pkidx, h_slots.data(), N * 8, hipMemcpyHostToDevice, ctx->stream), "index copy");
+    ctx->h2d_bytes += N * 8;
+    tc::launch_commitment_evaluate(ctx->stream, d_commit, t, d_pkidx, N, d_pks, d_pkst);
+    if (ctx->input_checks) tc::launch_subgroup_check_g1(ctx->stream, d_commit, 96, need, need, need, d_cval);
+    // pass 1: the first t+1 present shares, whatever they are
+    tc::launch_select_shares(ctx->stream, d_present, nullptr, N, need, B, nullptr, d_idx, d_slot, d_used, d_enough);
+    tc::launch_gather_selected(ctx->stream, d_sh, N, need, PB, d_slot, d_enough, B, d_packed);
+    combine_launch(k, sig, t, need, d_idx, nullptr, d_packed, B, d_comb, d_st1);
+    // membership of the selected shares goes into bytes of our own: a non-member share sends its job to pass 2 and ends as a
+    // bad bit there, never as a failed job
+    if (d_member) {
+      if (sig) tc::launch_subgroup_check_g2(ctx->stream, d_packed, PB, need, need, B * need, d_member);
+      else tc::launch_subgroup_check_g1(ctx->stream, d_packed, PB, need, need, B * need, d_member);
+    }
+    k.check(hipMemsetAsync(d_jvalid, 1, B, ctx->stream), "memset");
+    if (sig) {
+      if (hashes) {
+        if (ctx->input_checks) {
+          tc::launch_subgroup_check_g2(ctx->stream, d_hash, 192, 1, 1, B, d_jtmp);
+          tc::launch_invalidate_jobs(ctx->stream, d_jtmp, 1, 1, B, nullptr, nullptr, 0, d_jvalid);
+        }
+      } else {
+        tc::launch_hash_g2(ctx->tuning, ctx->stream, d_msgs, d_off, B, d_hash_own, /*fix=*/false);
+      }
+      // the combinations under the ONE master key, by random linear combination: about one pairing check per `group` jobs
+      rlc_group_checks(k, ws, d_commit, d_comb, d_hash, d_g1, B, /*member_checks=*/false, /*hash_is_operand=*/false, d_ok1, nullptr);
+    } else {
+      tc::launch_hash_g1_g2(ctx->tuning, ctx->stream, d_u, d_msgs, d_off, B, d_hash_own, d_jtmp, /*fix=*/false);
+      tc::launch_ok_and_status(ctx->stream, d_jtmp, B, d_jvalid);
+      if (ctx->input_checks) {
+        tc::launch_subgroup_check_g1(ctx->stream, d_u, 96, 1, 1, B, d_jtmp);
+        tc::launch_invalidate_jobs(ctx->stream, d_jtmp, 1, 1, B, nullptr, nullptr, 0, d_jvalid);
+        tc::launch_subgroup_check_g2(ctx->stream, d_w, 192, 1, 1, B, d_jtmp);
+        tc::launch_invalidate_jobs(ctx->stream, d_jtmp, 1, 1, B, nullptr, nullptr, 0, d_jvalid);
+      }
+      // verify_decryption_share of the COMBINATION under the master key: e(g, H) = e([c] g, Q') == e(commit[0], w)
+      tc::launch_g1_scale_cofactor_fix(ctx->stream, d_comb, 96, B, d_combc);
+      tc::launch_pairing_check(ctx->stream, d_combc, 96, d_hash, 192, d_commit, 0, d_w, 192, B, d_ok1, k.pairing_ws(B));
+    }
+    tc::launch_invalidate_jobs(ctx->stream, d_jvalid, 1, 1, B, nullptr, nullptr, 0, d_ok1);
+    tc::launch_robust_finish(ctx->stream, nullptr, N, need, PB, B, d_enough, d_st1, d_ok1, d_member, d_comb, d_res, d_status, d_used, d_verdict);
+    k.check(hipMemcpyAsync(h_verdict.data(), d_verdict, B, hipMemcpyDeviceToHost, ctx->stream), "verdict readback");
+    k.check(hipMemcpyAsync(h_pkst.data(), d_pkst, N, hipMemcpyDeviceToHost, ctx->stream), "status readback");
+    ctx->d2h_bytes += B + N;
+    if (ctx->input_checks) {
+      k.check(hipMemcpyAsync(h_cval.data(), d_cval, need, hipMemcpyDeviceToHost, ctx->stream), "valid readback");
+      ctx->d2h_bytes += need;
+    }
+    k.check(hipStreamSynchronize(ctx->stream), "stream sync");
+  }
+  bool commit_bad = false;
+  if (!k.failed) {
+    for (size_t i = 0; i < N; i++) commit_bad = commit_bad || h_pkst[i] != TC_JOB_OK;
+    for (size_t i = 0; i < need; i++) commit_bad = commit_bad || h_cval[i] == 0;
+  }
+  if (!k.failed && commit_bad) {
+    // no key set, no verdict on anything: every job fails with INVALID_ENCODING and the identity, used = bad = 0
+    k.check(hipMemsetAsync(d_status, TC_JOB_INVALID_ENCODING, B, ctx->stream), "memset");
+    k.check(hipMemsetAsync(d_jvalid, 0, 1, ctx->stream), "memset");
+    tc::launch_invalidate_jobs(ctx->stream, d_jvalid, 1, (size_t)-1, B, nullptr, d_res, PB, nullptr);
+    if (d_used) k.check(hipMemsetAsync(d_used, 0, B * N, ctx->stream), "memset");
+  } else if (!k.failed) {
+    for (size_t j = 0; j < B; j++)
+      if (h_verdict[j] == tc::kRobustRetry) failed.push_back((uint32_t)j);
+  }
+  if (!k.failed && !failed.empty()) {
+    // pass 2: every share of the jobs whose combination did not stand, checked under its public key share on compacted
+    // operands (PublicKeyShare::verify src/lib.rs:177-179 / verify_decryption_share :182-186); the verdict of an absent slot
+    // is dropped by k_robust_mark
+    const size_t F = failed.size(), R = F * N;
+    std::vector<uint32_t> m_rec(R), m_job(R), m_pk(R);
+    for (size_t f = 0; f < F; f++)
+      for (size_t i = 0; i < N; i++) {
+        m_rec[f * N + i] = (uint32_t)(failed[f] * N + i);
+        m_job[f * N + i] = failed[f];
+        m_pk[f * N + i] = (uint32_t)i;
+      }
+    uint32_t* d_maps = k.temp<uint32_t>(3 * R + F);
+    uint8_t* c_sh = k.temp<uint8_t>(R * PB);
+    uint8_t* c_shc = sig ? nullptr : k.temp<uint8_t>(R * 96);
+    uint8_t* c_hash = k.temp<uint8_t>(R * 192);
+    uint8_t* c_w = sig ? nullptr : k.temp<uint8_t>(R * 192);
+    uint8_t* c_pk = k.temp<uint8_t>(R * 96);
+    uint8_t* c_ok = k.temp<uint8_t>(R);
+    uint8_t* c_v = k.temp<uint8_t>(R);
+    uint8_t* c_present = k.temp<uint8_t>(R);
+    uint8_t* c_bad = k.temp<uint8_t>(R);
+    uint64_t* d_idx2 = k.temp<uint64_t>(F * need);
+    uint32_t* d_slot2 = k.temp<uint32_t>(F * need);
+    uint8_t* d_enough2 = k.temp<uint8_t>(F);
+    uint8_t* d_packed2 = k.temp<uint8_t>(F * need * PB);
+    uint8_t* d_comb2 = k.temp<uint8_t>(F * PB);
+    uint8_t* d_st2 = k.temp<uint8_t>(F, /*zero=*/true);
+    if (!k.failed) {
+      uint32_t* d_fmap = d_maps + 3 * R;
+      k.check(hipMemcpyAsync(d_maps, m_rec.data(), R * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
+      k.check(hipMemcpyAsync(d_maps + R, m_job.data(), R * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
+      k.check(hipMemcpyAsync(d_maps + 2 * R, m_pk.data(), R * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
+      k.check(hipMemcpyAsync(d_fmap, failed.data(), F * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
+      ctx->h2d_bytes += 12 * R + 4 * F;
+      tc::launch_gather_rows(ctx->stream, d_sh, PB, d_maps, R, c_sh);
+      tc::launch_gather_rows(ctx->stream, d_hash, 192, d_maps + R, R, c_hash);
+      tc::launch_gather_rows(ctx->stream, d_pks, 96, d_maps + 2 * R, R, c_pk);
+      if (sig) {
+        tc::launch_pairing_check(ctx->stream, c_pk, 96, c_hash, 192, d_g1, 0, c_sh, 192, R, c_ok, k.pairing_ws(R));
+      } else {
+        tc::launch_gather_rows(ctx->stream, d_w, 192, d_maps + R, R, c_w);
+        tc::launch_g1_scale_cofactor_fix(ctx->stream, c_sh, 96, R, c_shc);
+        tc::launch_pairing_check(ctx->stream, c_shc, 96, c_hash, 192, c_pk, 96, c_w, 192, R, c_ok, k.pairing_ws(R));
+      }
+      if (ctx->input_checks) {  // members only (the key shares are sums of the commitment's points, tested above)
+        if (sig) tc::launch_subgroup_check_g2(ctx->stream, c_sh, 192, 1, 1, R, c_v);
+        else tc::launch_subgroup_check_g1(ctx->stream, c_sh, 96, 1, 1, R, c_v);
+        tc::launch_invalidate_jobs(ctx->stream, c_v, 1, 1, R, nullptr, nullptr, 0, c_ok);
+      }
+      tc::launch_gather_bytes(ctx->stream, d_jvalid, d_maps + R, R, c_v);
+      tc::launch_invalidate_jobs(ctx->stream, c_v, 1, 1, R, nullptr, nullptr, 0, c_ok);
+      tc::launch_robust_mark(ctx->stream, d_present, d_maps, c_ok, R, c_present, c_bad, d_bad);
+      // the first t+1 VALID shares: their combination needs no further check
+      tc::launch_select_shares(ctx->stream, c_present, c_bad, N, need, F, d_fmap, d_idx2, d_slot2, d_used, d_enough2);
+      tc::launch_gather_selected(ctx->stream, c_sh, N, need, PB, d_slot2, d_enough2, F, d_packed2);
+      combine_launch(k, sig, t, need, d_idx2, nullptr, d_packed2, F, d_comb2, d_st2);
+      tc::launch_robust_finish(ctx->stream, d_fmap, N, need, PB, F, d_enough2, d_st2, nullptr, nullptr, d_comb2, d_res, d_status, d_used, nullptr);
+      k.check(hipStreamSynchronize(ctx->stream), "stream sync");  // the host maps go out of scope
+    }
+    if (n_fallback) *n_fallback = F;
+  }
+  // the plaintext of a job that ended OK: xor_with_hash(g, v), src/lib.rs:625
+  if (!k.failed && !sig) tc::launch_xor_with_hash(ctx->stream, d_res, d_msgs, d_off, B, d_plain, d_status);
+  k.end_timing();
+  return k.finish();
+}
+
+int tc_combine_signatures_robust_batch(tc_ctx* ctx, const uint8_t* commit, size_t t, size_t N, const uint8_t* present,
+                                       const uint8_t* sig_shares, const uint8_t* hashes, const uint8_t* msgs, const uint64_t* off, size_t B,
+                                       size_t group, const uint8_t* seed32, uint8_t* out_sig, uint8_t* used, uint8_t* bad, uint8_t* status,
+                                       uint64_t* n_fallback) try {
+  return robust_combine(ctx, true, commit, t, N, present, sig_shares, hashes, msgs, off, nullptr, nullptr, B, group, seed32, out_sig, false, used, bad,
+                        status, n_fallback);
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+int tc_decrypt_robust_batch(tc_ctx* ctx, const uint8_t* commit, size_t t, size_t N, const uint8_t* present, const uint8_t* shares_g1,
+                            const uint8_t* u_g1, const uint8_t* v, const uint64_t* off, const uint8_t* w_g2, size_t B, uint8_t* out_plain,
+                            uint8_t* used, uint8_t* bad, uint8_t* status, uint64_t* n_fallback) try {
+  TC_REQUIRE(ctx);
+  if (n_fallback) *n_fallback = 0;
+  if (B == 0) return TC_OK;  // (an empty batch is a no-op for every entry: a device-resident empty buffer has no address)
+  const bool unbacked = out_plain == nullptr;
+  if (unbacked) out_plain = &g_no_plaintext_bytes;
+  return robust_combine(ctx, false, commit, t, N, present, shares_g1, nullptr, v, off, u_g1, w_g2, B, 0, nullptr, out_plain, unbacked, used, bad, status,
+                        n_fallback);
 } catch (...) {
   return on_exception((tc_ctx*)ctx);
 }

@@ -264,4 +264,27 @@ void launch_bivar_column0(hipStream_t st, const uint8_t* commits, size_t stride,
 void launch_dkg_generate_verdict(hipStream_t st, const uint8_t* accept, const uint8_t* point_bad, const uint8_t* share_st, size_t P, size_t degree,
                                  uint8_t* part_status, uint8_t* out_commit, uint8_t* out_share);
 
+// The robust combiners (k_robust.hip; selection rule in tc_robust.h).  present / bad: jobs x N mask bytes, either may be null.
+//   launch_select_shares    idx / slot (jobs x need) = the first `need` eligible slots of every job; enough[j]; the used bytes of a
+//                           job that has enough, in row map[j] (null: j) of the caller's B x N array (used may be null)
+//   launch_gather_selected  dst (jobs x need x point_bytes) = the selected shares of shares (jobs x N x point_bytes); identities
+//                           for a job without enough
+//   launch_gather_bytes     dst[r] = src[map[r]]
+//   launch_robust_mark      record r = share rec[r] of the caller's arrays with check result ok[r]: the compacted masks
+//                           c_present / c_bad (rows bytes each) and the caller's bad[rec[r]] (may be null)
+//   launch_robust_finish    status / out / used of the jobs of one pass (job f of the pass = job map[f] of the call, null: f)
+//                           from enough, the combine status job_st, the check of the combination ok (null: none) and the
+//                           membership bytes of the selected shares (need per job, null: none); verdict[f] (may be null): a
+//                           RobustVerdict
+void launch_select_shares(hipStream_t st, const uint8_t* present, const uint8_t* bad, size_t N, size_t need, size_t jobs, const uint32_t* map,
+                          uint64_t* idx, uint32_t* slot, uint8_t* used, uint8_t* enough);
+void launch_gather_selected(hipStream_t st, const uint8_t* shares, size_t N, size_t need, size_t point_bytes, const uint32_t* slot,
+                            const uint8_t* enough, size_t jobs, uint8_t* dst);
+void launch_gather_bytes(hipStream_t st, const uint8_t* src, const uint32_t* map, size_t rows, uint8_t* dst);
+void launch_robust_mark(hipStream_t st, const uint8_t* present, const uint32_t* rec, const uint8_t* ok, size_t rows, uint8_t* c_present,
+                        uint8_t* c_bad, uint8_t* bad);
+void launch_robust_finish(hipStream_t st, const uint32_t* map, size_t N, size_t need, size_t point_bytes, size_t jobs, const uint8_t* enough,
+                          const uint8_t* job_st, const uint8_t* ok, const uint8_t* member, const uint8_t* comb, uint8_t* out, uint8_t* status,
+                          uint8_t* used, uint8_t* verdict);
+
 }  // namespace tc

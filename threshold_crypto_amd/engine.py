@@ -532,6 +532,68 @@ class Engine:
                    _ptr(ok), ctypes.byref(nfb))
         return ok, int(nfb.value)
 
+    # -- robust combination: validate, select and combine in one call -----------------------------------
+    def combine_signatures_robust(self, commit, sig_shares, hashes=None, msgs=None, off=None, present=None, group=0, seed=None):
+        """tc_combine_signatures_robust_batch (see tc_amd.h): commit (t+1, 96), sig_shares (B, N, 192) with slot i = node i's
+        share, either hashes (B, 192) or msgs / off, present (B, N) u8 or None = all.  The first t+1 present shares of every
+        message are combined and the combinations verified under the master key; only the messages whose combination does not
+        verify are examined share by share.  Returns (sig (B, 192), used (B, N), bad (B, N), status (B,), number of messages
+        examined share by share).  `seed`: 32 secret random bytes (os.urandom when omitted)."""
+        import os
+        if (hashes is None) == (off is None):
+            raise ValueError("exactly one of hashes and msgs / off")
+        dev = self._mode(commit, sig_shares, hashes, msgs, off, present)
+        self._arg(commit, (None, G1_BYTES), "u8", "commit")
+        t = commit.shape[0] - 1
+        self._arg(sig_shares, (None, None, G2_BYTES), "u8", "sig_shares")
+        B, N = sig_shares.shape[0], sig_shares.shape[1]
+        if t < 0 or t + 1 > N:
+            raise ValueError("commit holds t+1 = %d coefficients for N = %d shares per message" % (t + 1, N))
+        if hashes is not None:
+            self._arg(hashes, (B, G2_BYTES), "u8", "hashes")
+        else:
+            self._msgs(msgs, off, B)
+        if present is not None:
+            self._arg(present, (B, N), "u8", "present")
+        seed = bytes(seed) if seed is not None else os.urandom(32)
+        if len(seed) != 32:
+            raise ValueError("seed: 32 bytes")
+        out = self._empty(dev, (B, G2_BYTES), ref=sig_shares)
+        used = self._empty(dev, (B, N), ref=sig_shares)
+        bad = self._empty(dev, (B, N), ref=sig_shares)
+        st = self._empty(dev, (B,), ref=sig_shares)
+        nfb = ctypes.c_uint64(0)
+        self._call("tc_combine_signatures_robust_batch", _ptr(commit), t, N, _ptr(present), _ptr(sig_shares), _ptr(hashes),
+                   _ptr(msgs) if off is not None else None, _ptr(off), B, int(group), seed, _ptr(out), _ptr(used), _ptr(bad), _ptr(st),
+                   ctypes.byref(nfb))
+        return out, used, bad, st, int(nfb.value)
+
+    def decrypt_robust(self, commit, shares, u, v, off, w, present=None):
+        """tc_decrypt_robust_batch (see tc_amd.h): commit (t+1, 96), shares (B, N, 96) with slot i = node i's decryption share
+        of ciphertext (u, v, w)[j], present (B, N) u8 or None = all.  Returns (plaintext bytes laid out like v -- zeros for a
+        ciphertext that did not end OK --, used (B, N), bad (B, N), status (B,), number of ciphertexts examined share by
+        share)."""
+        dev = self._mode(commit, shares, u, v, off, w, present)
+        self._arg(commit, (None, G1_BYTES), "u8", "commit")
+        t = commit.shape[0] - 1
+        self._arg(shares, (None, None, G1_BYTES), "u8", "shares")
+        B, N = shares.shape[0], shares.shape[1]
+        if t < 0 or t + 1 > N:
+            raise ValueError("commit holds t+1 = %d coefficients for N = %d shares per ciphertext" % (t + 1, N))
+        self._arg(u, (B, G1_BYTES), "u8", "u")
+        self._arg(w, (B, G2_BYTES), "u8", "w")
+        self._msgs(v, off, B)
+        if present is not None:
+            self._arg(present, (B, N), "u8", "present")
+        out = self._empty(dev, tuple(v.shape), ref=v)
+        used = self._empty(dev, (B, N), ref=shares)
+        bad = self._empty(dev, (B, N), ref=shares)
+        st = self._empty(dev, (B,), ref=shares)
+        nfb = ctypes.c_uint64(0)
+        self._call("tc_decrypt_robust_batch", _ptr(commit), t, N, _ptr(present), _ptr(shares), _ptr(u), _ptr(v), _ptr(off), _ptr(w), B,
+                   _ptr(out), _ptr(used), _ptr(bad), _ptr(st), ctypes.byref(nfb))
+        return out, used, bad, st, int(nfb.value)
+
     # -- membership tests -----------------------------------------------------------------------------
     def g1_subgroup_check(self, pts):
         """ok[j] = pts[j] is a valid encoding of a point of G1 (on the curve, order r)"""
