@@ -1,0 +1,178 @@
+// Many-point conformance harness (test code only: never linked into libtc_amd.so, never run by bench.py).
+// Includes the product's kernel units k_msm.hip and k_comb.hip as they are (every unit of the product is self-contained:
+// -fno-gpu-rdc), so the __global__ kernels launched here are the product's own text, compiled with the product's flags.
+// Three entries; each allocates, copies in, launches, synchronises once, copies out, frees and returns the first HIP
+// error.  `parts` / `share` = 0 goes through the product's launcher (its own rule for the launch geometry); another value
+// launches the stage kernels directly with that value.  Tables, codes, outputs and written-only status bytes are filled
+// with 0x5A before the launch, so the caller sees what the kernels left in memory -- and what they did not touch.
+//   build: tests/manypoint_conformance.py (hipcc, keyed by a hash of the sources)
+#include <hip/hip_runtime.h>
+#include "../../threshold_crypto_amd/csrc/k_msm.hip"
+#include "../../threshold_crypto_amd/csrc/k_comb.hip"
+
+#include <vector>
+
+using namespace tc;
+
+constexpr int kMpSlotLeak = -2;  // a table slot was still marked in use after the run
+constexpr int kMpPoison = 0x5A;
+
+namespace {
+struct Dev {
+  std::vector<void*> owned;
+  hipError_t e = hipSuccess;
+  void* alloc(size_t bytes, int fill = -1) {
+    void* p = nullptr;
+    if (e == hipSuccess) e = hipMalloc(&p, bytes ? bytes : 1);
+    if (e == hipSuccess) owned.push_back(p);
+    if (e == hipSuccess && fill >= 0 && bytes) e = hipMemset(p, fill, bytes);
+    return e == hipSuccess ? p : nullptr;
+  }
+  void* upload(const void* src, size_t bytes) {
+    void* p = alloc(bytes);
+    if (e == hipSuccess && bytes) e = hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
+    return p;
+  }
+  void download(void* dst, const void* src, size_t bytes) {
+    if (e == hipSuccess && bytes) e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
+  }
+  void after_launch() {
+    if (e == hipSuccess) e = hipGetLastError();
+  }
+  void sync() {
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+  }
+  ~Dev() {
+    for (void* p : owned) hipFree(p);
+  }
+};
+bool legal_parts(size_t parts, size_t n, size_t most) {
+  return parts <= most && (parts & (parts - 1)) == 0 && (parts <= 1 || 4 * parts <= n);
+}
+size_t points_bytes(size_t n, size_t B, size_t stride, size_t point) { return (B - 1) * stride + n * point; }
+}  // namespace
+
+// G2: out (B x 192), status (B, copied in from status_in first), tbl (msm_table_bytes(n, B)), codes (msm_code_bytes(n, B)).
+// idx: null, or B x n_per_job indices for the MsmFilter with threshold t; need_value < 0: no `need` word, else its value.
+extern "C" int mp_msm_g2(size_t n, size_t B, size_t pts_stride, const uint8_t* points, const uint32_t* scalars, const uint8_t* status_in,
+                         int nbits, size_t parts, const uint64_t* idx, size_t n_per_job, size_t t, int need_value, uint8_t* out,
+                         uint8_t* status, int32_t* tbl, uint8_t* codes) {
+  if (!n || !B || nbits < 1 || nbits > 64 || !legal_parts(parts, n, 32)) return (int)hipErrorInvalidValue;
+  Dev d;
+  const size_t tb = msm_table_bytes(n, B), cb = msm_code_bytes(n, B);
+  const uint8_t* dpts = (const uint8_t*)d.upload(points, points_bytes(n, B, pts_stride, 192));
+  const uint32_t* dsc = (const uint32_t*)d.upload(scalars, B * n * 32);
+  uint8_t* dst = (uint8_t*)d.upload(status_in, B);
+  uint8_t* dout = (uint8_t*)d.alloc(B * 192, kMpPoison);
+  int32_t* dtbl = (int32_t*)d.alloc(tb, kMpPoison);
+  uint8_t* dcodes = (uint8_t*)d.alloc(cb, kMpPoison);
+  MsmFilter f;
+  if (idx) {
+    f.idx = (const uint64_t*)d.upload(idx, B * n_per_job * 8);
+    f.n_per_job = n_per_job;
+    f.t = t;
+  }
+  if (need_value >= 0) {
+    const uint32_t v = (uint32_t)need_value;
+    f.need = (const uint32_t*)d.upload(&v, 4);
+  }
+  if (d.e == hipSuccess) {
+    if (parts == 0) {
+      launch_msm_g2(0, n, pts_stride, dpts, dsc, B, dtbl, dcodes, dout, dst, nbits, f);
+    } else {
+      hipLaunchKernelGGL(k_msm_tables, dim3(grid_for(B * msm_chunks(n) * kG2Lanes)), dim3(kBlock), 0, 0, n, pts_stride, dpts, dsc, B, dtbl,
+                         dcodes, dst, nbits, f);
+      if (parts == 1)
+        hipLaunchKernelGGL(k_msm_ladder, dim3(grid_for(B * kG2Lanes)), dim3(kBlock), 0, 0, n, B, (const int32_t*)dtbl, (const uint8_t*)dcodes,
+                           dout, (const uint8_t*)dst, nbits, f);
+      else
+        hipLaunchKernelGGL(k_msm_ladder_split, dim3(grid_for(B * parts * kG2Lanes)), dim3(kBlock), 0, 0, n, B, (const int32_t*)dtbl,
+                           (const uint8_t*)dcodes, dout, (const uint8_t*)dst, nbits, f, parts);
+    }
+    d.after_launch();
+  }
+  d.sync();
+  d.download(out, dout, B * 192);
+  d.download(status, dst, B);
+  d.download(tbl, dtbl, tb);
+  d.download(codes, dcodes, cb);
+  return (int)d.e;
+}
+
+// G1: out (B x 96), status (B), tbl (msm_table_bytes_g1(n, B): B table sets in shared mode too), codes (msm_code_bytes).
+// pts_stride = 0 with nbits < 128: the shared table set.
+extern "C" int mp_msm_g1(size_t n, size_t B, size_t pts_stride, const uint8_t* points, const uint32_t* scalars, const uint8_t* status_in,
+                         int nbits, size_t parts, uint8_t* out, uint8_t* status, int32_t* tbl, uint8_t* codes) {
+  if (!n || !B || nbits < 2 || nbits > 128 || (nbits & 1) || !legal_parts(parts, n, 64)) return (int)hipErrorInvalidValue;
+  Dev d;
+  const size_t tb = msm_table_bytes_g1(n, B), cb = msm_code_bytes(n, B);
+  const uint8_t* dpts = (const uint8_t*)d.upload(points, points_bytes(n, B, pts_stride, 96));
+  const uint32_t* dsc = (const uint32_t*)d.upload(scalars, B * n * 32);
+  uint8_t* dst = (uint8_t*)d.upload(status_in, B);
+  uint8_t* dout = (uint8_t*)d.alloc(B * 96, kMpPoison);
+  int32_t* dtbl = (int32_t*)d.alloc(tb, kMpPoison);
+  uint8_t* dcodes = (uint8_t*)d.alloc(cb, kMpPoison);
+  if (d.e == hipSuccess) {
+    if (parts == 0) {
+      launch_msm_g1(0, n, pts_stride, dpts, dsc, B, dtbl, dcodes, dout, dst, nbits);
+    } else {
+      const int top = nbits / 2;
+      const int shared = msm_g1_shared_tables(pts_stride, nbits) ? 1 : 0;
+      hipLaunchKernelGGL(k_msm_tables_g1, dim3(grid_for(B * msm_chunks(n))), dim3(kBlock), 0, 0, n, pts_stride, dpts, dsc, B, dtbl, dcodes, dst,
+                         nbits);
+      if (parts == 1)
+        hipLaunchKernelGGL(k_msm_ladder_g1<false>, dim3(grid_for(B)), dim3(kBlock), 0, 0, n, B, (const int32_t*)dtbl, (const uint8_t*)dcodes, dout,
+                           (const uint8_t*)dst, parts, top, shared);
+      else
+        hipLaunchKernelGGL(k_msm_ladder_g1<true>, dim3(grid_for(B * parts)), dim3(kBlock), 0, 0, n, B, (const int32_t*)dtbl,
+                           (const uint8_t*)dcodes, dout, (const uint8_t*)dst, parts, top, shared);
+    }
+    d.after_launch();
+  }
+  d.sync();
+  d.download(out, dout, B * 96);
+  d.download(status, dst, B);
+  d.download(tbl, dtbl, tb);
+  d.download(codes, dcodes, cb);
+  return (int)d.e;
+}
+
+// Comb: sk (N x 32), idx (B x n), pts (B x 192); out (B x n x 192), status (B x n), ok (B), tbl (comb_table_bytes(B)).
+// Runs with a table arena of the product's geometry; every slot flag must be clear again afterwards (kMpSlotLeak).
+extern "C" int mp_comb(const uint8_t* sk, size_t N, const uint64_t* idx, const uint8_t* pts, size_t n, size_t B, size_t share, uint8_t* out,
+                       uint8_t* status, uint8_t* ok, int32_t* tbl) {
+  if (!n || !B || !N || share > (size_t)kCombShare) return (int)hipErrorInvalidValue;
+  Dev d;
+  const size_t tb = comb_table_bytes(B);
+  const uint8_t* dsk = (const uint8_t*)d.upload(sk, N * 32);
+  const uint64_t* didx = (const uint64_t*)d.upload(idx, B * n * 8);
+  const uint8_t* dpts = (const uint8_t*)d.upload(pts, B * 192);
+  uint8_t* dout = (uint8_t*)d.alloc(B * n * 192, kMpPoison);
+  uint8_t* dst = (uint8_t*)d.alloc(B * n, kMpPoison);
+  uint8_t* dok = (uint8_t*)d.alloc(B, kMpPoison);
+  int32_t* dtbl = (int32_t*)d.alloc(tb, kMpPoison);
+  TableArena ta;
+  ta.mem = (int32_t*)d.alloc(kTableArenaWords * 4, kMpPoison);
+  ta.flags = (uint32_t*)d.alloc(kTableArenaFlags * 4, 0);
+  if (d.e == hipSuccess) {
+    if (share == 0) {
+      launch_comb_sign(0, ta, dsk, N, didx, dpts, n, B, dtbl, dok, dout, dst);
+    } else {
+      hipLaunchKernelGGL(k_comb_tables, dim3(grid_for(B * kG2Lanes)), dim3(kBlock), 0, 0, dpts, B, dtbl, dok);
+      const size_t chunks = (n + share - 1) / share;
+      hipLaunchKernelGGL(k_comb_sign, dim3(grid_for(chunks * B * kG2Lanes)), dim3(kBlock), 0, 0, dsk, N, didx, (const int32_t*)dtbl,
+                         (const uint8_t*)dok, n, B, dout, dst, ta, share);
+    }
+    d.after_launch();
+  }
+  d.sync();
+  d.download(out, dout, B * n * 192);
+  d.download(status, dst, B * n);
+  d.download(ok, dok, B);
+  d.download(tbl, dtbl, tb);
+  std::vector<uint32_t> fl(kTableArenaFlags);
+  d.download(fl.data(), ta.flags, kTableArenaFlags * 4);
+  bool leak = false;
+  for (size_t i = 0; d.e == hipSuccess && i < fl.size(); i++) leak = leak || fl[i] != 0;
+  return d.e == hipSuccess && leak ? kMpSlotLeak : (int)d.e;
+}

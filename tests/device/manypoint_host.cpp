@@ -1,0 +1,187 @@
+// Host leg of the many-point conformance harness (tests/manypoint_conformance.py): the header routines the kernels of
+// k_msm.hip / k_comb.hip call -- job_msm_tables, job_msm_ladder_part<SPLIT>, their G1 twins, job_comb_tables, job_comb_sign --
+// run by g++ with -DTC_BOUND_CHECK over the same buffers, in the layout of tests/device/manypoint.hip: the jobs one after the
+// other, the parts of a job one after the other, then the kernel's xor tree of jac_add.  It proves the case tables, the
+// models and the checkers before any GPU time is spent.  What it cannot see is the kernels' own text (lane pairs, the
+// shuffle merge, the indexing): that is the GPU leg.  parts / share = 0 (the launcher's choice) exists on the device only.
+// With -DMP_MAIN it is a stand-alone program over a fixed short case list (for a g++ -fsanitize=address,undefined build).
+// Test code only: never linked into libtc_amd.so.
+#include "../../threshold_crypto_amd/csrc/tc_msm.h"
+#include "../../threshold_crypto_amd/csrc/tc_comb.h"
+
+#include <stdio.h>
+#include <string.h>
+#include <vector>
+
+using namespace tc;
+
+namespace {
+bool taken(const uint64_t* idx, size_t n_per_job, size_t t, size_t j) {
+  return !(idx && t >= 1 && t <= 3 && combine_small_applies(idx + j * n_per_job, (int)t));
+}
+template <class J>
+J merge(std::vector<J> r, size_t parts) {
+  for (size_t d = 1; d < parts; d <<= 1) {  // every lane (pair) adds its partner's value of the round before
+    std::vector<J> nr(parts);
+    for (size_t g = 0; g < parts; g++) nr[g] = jac_add(r[g], r[g ^ d]);
+    r = nr;
+  }
+  return r[0];
+}
+}  // namespace
+
+extern "C" {
+int mph_msm_g2(size_t n, size_t B, size_t pts_stride, const uint8_t* points, const uint32_t* scalars, const uint8_t* status_in, int nbits,
+               size_t parts, const uint64_t* idx, size_t n_per_job, size_t t, int need_value, uint8_t* out, uint8_t* status, int32_t* tbl,
+               uint8_t* codes) {
+  memcpy(status, status_in, B);
+  if (need_value == 0) return 0;
+  const size_t chunks = msm_chunks(n), shares4 = chunks * kMsmChunk;
+  for (size_t j = 0; j < B; j++) {
+    if (!taken(idx, n_per_job, t, j)) continue;
+    int32_t* jt = tbl + j * shares4 * 8 * kMsmEntryWords;
+    uint8_t* jc = codes + j * kMsmColumns * shares4;
+    for (size_t c = 0; c < chunks; c++) {
+      const bool ok = job_msm_tables(n, c, points + j * pts_stride, scalars + j * n * 8, jt, jc, true, nbits);
+      if (!ok && status[j] == TC_JOB_OK) status[j] = TC_JOB_INVALID_ENCODING;
+    }
+  }
+  for (size_t j = 0; j < B; j++) {
+    if (!taken(idx, n_per_job, t, j)) continue;
+    if (status[j] != TC_JOB_OK) {
+      g2_encode_uncompressed(G2Affine::infinity(), out + j * 192);
+      continue;
+    }
+    const int32_t* jt = tbl + j * shares4 * 8 * kMsmEntryWords;
+    const uint8_t* jc = codes + j * kMsmColumns * shares4;
+    std::vector<G2Jac> r(parts);
+    for (size_t g = 0; g < parts; g++)
+      r[g] = parts == 1 ? job_msm_ladder(n, jt, jc, nbits) : job_msm_ladder_part<true>(n, jt, jc, nbits, msm_part(n, g, parts));
+    g2_encode_uncompressed(jac_to_affine(merge(r, parts)), out + j * 192);
+  }
+  return 0;
+}
+
+int mph_msm_g1(size_t n, size_t B, size_t pts_stride, const uint8_t* points, const uint32_t* scalars, const uint8_t* status_in, int nbits,
+               size_t parts, uint8_t* out, uint8_t* status, int32_t* tbl, uint8_t* codes) {
+  memcpy(status, status_in, B);
+  const size_t chunks = msm_chunks(n), shares4 = chunks * kMsmChunk;
+  const bool shared = pts_stride == 0 && nbits < 128;
+  const int top = nbits / 2;
+  for (size_t j = 0; j < B; j++)
+    for (size_t c = 0; c < chunks; c++) {
+      const bool ok = job_msm_tables_g1(n, c, points + j * pts_stride, scalars + j * n * 8, tbl + (shared ? 0 : j * shares4 * 8 * kMsmEntryWordsG1),
+                                        codes + j * kMsmColumns * shares4, nbits, !shared || j == 0);
+      if (!ok && status[j] == TC_JOB_OK) status[j] = TC_JOB_INVALID_ENCODING;
+    }
+  for (size_t j = 0; j < B; j++) {
+    if (status[j] != TC_JOB_OK) {
+      g1_encode_uncompressed(G1Affine::infinity(), out + j * 96);
+      continue;
+    }
+    const int32_t* jt = tbl + (shared ? 0 : j * shares4 * 8 * kMsmEntryWordsG1);
+    const uint8_t* jc = codes + j * kMsmColumns * shares4;
+    std::vector<G1Jac> r(parts);
+    for (size_t g = 0; g < parts; g++)
+      r[g] = parts == 1 ? job_msm_ladder_g1_part<false>(n, jt, jc, msm_part(n), top) : job_msm_ladder_g1_part<true>(n, jt, jc, msm_part(n, g, parts), top);
+    g1_encode_uncompressed(jac_to_affine(merge(r, parts)), out + j * 96);
+  }
+  return 0;
+}
+
+int mph_comb(const uint8_t* sk, size_t N, const uint64_t* idx, const uint8_t* pts, size_t n, size_t B, size_t share, uint8_t* out, uint8_t* status,
+             uint8_t* ok, int32_t* tbl) {
+  for (size_t j = 0; j < B; j++) ok[j] = job_comb_tables(pts + j * 192, (tbl_word*)(tbl + j * (size_t)kCombTableWords)) ? 1 : 0;
+  const size_t chunks = (n + share - 1) / share;
+  for (size_t tid = 0; tid < chunks * B; tid++) {  // chunk-major, as k_comb_sign orders its lane pairs
+    const size_t c = tid / B, j = tid % B, s0 = c * share;
+    const int cnt = (int)((n - s0 < share) ? n - s0 : share);
+    const size_t o = j * n + s0;
+    job_comb_sign(sk, N, idx + o, cnt, (const tbl_word*)(tbl + j * (size_t)kCombTableWords), ok[j] != 0, out + o * 192, status + o, true);
+  }
+  return 0;
+}
+
+void mph_msm_part(size_t n, size_t g, size_t parts, size_t* out3) {
+  const MsmPart p = msm_part(n, g, parts);
+  out3[0] = p.s0;
+  out3[1] = p.s1;
+  out3[2] = p.trips;
+}
+void mph_sizes(size_t n, size_t B, size_t* out4) {
+  out4[0] = B * msm_chunks(n) * kMsmChunk * 8 * kMsmEntryWords * sizeof(int32_t);
+  out4[1] = B * kMsmColumns * msm_chunks(n) * kMsmChunk;
+  out4[2] = B * msm_chunks(n) * kMsmChunk * 8 * kMsmEntryWordsG1 * sizeof(int32_t);
+  out4[3] = B * (size_t)kCombTableWords * sizeof(int32_t);
+}
+}
+
+#if defined(MP_MAIN)
+#include "../../threshold_crypto_amd/csrc/tc_dkg.h"  // g1_mul_u64, for the inputs
+static void fr_words(uint64_t lo, uint32_t* w) {
+  memset(w, 0, 32);
+  w[0] = (uint32_t)lo;
+  w[1] = (uint32_t)(lo >> 32);
+}
+int main() {
+  int rc = 0;
+  const size_t n = 9, B = 2;
+  size_t sz[4];
+  mph_sizes(n, B, sz);
+  // G1: k g1 for k = 2 .. ; share 3 of job 0 the identity, shares 0 and 1 of job 1 equal with equal scalars
+  std::vector<uint8_t> p1(B * n * 96), st0(B, 0), st(B), out(B * 96), out1(B * 96), codes(sz[1]);
+  std::vector<uint32_t> sc(B * n * 8);
+  for (size_t i = 0; i < B * n; i++) {
+    g1_encode_uncompressed(jac_to_affine(g1_mul_u64(G1Jac::from_affine(g1_generator()), i == n + 1 ? n + 2 : i + 2)), p1.data() + i * 96);
+    fr_words(i == n + 1 ? 0x1234567 : 0x1234567 + 2 * i * i, sc.data() + i * 8);
+  }
+  memset(p1.data() + 3 * 96, 0, 96);
+  p1[3 * 96] = 0x40;
+  std::vector<int32_t> t1(sz[2] / 4);
+  for (size_t parts = 1; parts <= 2; parts *= 2) {
+    rc |= mph_msm_g1(n, B, n * 96, p1.data(), sc.data(), st0.data(), 128, parts, parts == 1 ? out1.data() : out.data(), st.data(), t1.data(), codes.data());
+    rc |= st[0] | st[1];
+    if (parts > 1) rc |= memcmp(out.data(), out1.data(), out.size()) ? 1 : 0;
+  }
+  // short scalars over the shared set: the same sum as over own points (job 0's)
+  for (size_t i = 0; i < B * n; i++) fr_words(2 * i + 1, sc.data() + i * 8);
+  rc |= mph_msm_g1(n, 1, n * 96, p1.data(), sc.data(), st0.data(), 32, 2, out1.data(), st.data(), t1.data(), codes.data());
+  rc |= mph_msm_g1(n, B, 0, p1.data(), sc.data(), st0.data(), 32, 1, out.data(), st.data(), t1.data(), codes.data());
+  rc |= st[0] | st[1] | (memcmp(out.data(), out1.data(), 96) ? 1 : 0);
+  // G2: the points come from the comb signer: sk[i] g2 for the keys 1 .. 9
+  std::vector<uint8_t> sk(n * 32, 0), h(192), shares(n * 192), sst(n), okb(1), o2(B * 192), o21(B * 192);
+  for (size_t i = 0; i < n; i++) sk[i * 32] = (uint8_t)(i + 1);  // little-endian Fr: keys 1 .. 9
+  g2_encode_uncompressed(G2Affine{Fq2::make(Fq::from_mont384(G2_GEN_X0), Fq::from_mont384(G2_GEN_X1)),
+                                  Fq2::make(Fq::from_mont384(G2_GEN_Y0), Fq::from_mont384(G2_GEN_Y1)), false},
+                         h.data());
+  std::vector<uint64_t> idx(n);
+  for (size_t i = 0; i < n; i++) idx[i] = i;
+  std::vector<int32_t> ct(sz[3] / 4 / B);
+  for (size_t share = 1; share <= 8; share += 3) {
+    rc |= mph_comb(sk.data(), n, idx.data(), h.data(), n, 1, share, shares.data(), sst.data(), okb.data(), ct.data());
+    for (size_t i = 0; i < n; i++) rc |= sst[i];
+    rc |= okb[0] == 1 ? 0 : 1;
+  }
+  rc |= memcmp(shares.data(), h.data(), 192) ? 1 : 0;  // key 1
+  std::vector<uint8_t> p2(B * n * 192);
+  for (size_t i = 0; i < B * n; i++) memcpy(p2.data() + i * 192, shares.data() + (i % n) * 192, 192);
+  memset(p2.data() + 4 * 192, 0, 192);
+  p2[4 * 192] = 0x40;
+  for (size_t i = 0; i < B * n; i++) fr_words(0xabcdef01 + 2 * i * i * i, sc.data() + i * 8);
+  std::vector<int32_t> t2(sz[0] / 4);
+  for (size_t parts = 1; parts <= 2; parts *= 2) {
+    rc |= mph_msm_g2(n, B, n * 192, p2.data(), sc.data(), st0.data(), 64, parts, nullptr, 0, 0, -1, parts == 1 ? o21.data() : o2.data(), st.data(), t2.data(),
+                     codes.data());
+    rc |= st[0] | st[1];
+    if (parts > 1) rc |= memcmp(o2.data(), o21.data(), o2.size()) ? 1 : 0;
+  }
+  for (size_t i = 0; i < B * n; i++) fr_words(2 * i + 1, sc.data() + i * 8);
+  rc |= mph_msm_g2(n, B, n * 192, p2.data(), sc.data(), st0.data(), 16, 2, nullptr, 0, 0, -1, o2.data(), st.data(), t2.data(), codes.data());
+  rc |= st[0] | st[1];
+  sc[0] = 2;  // an even short scalar fails its job
+  rc |= mph_msm_g2(n, B, n * 192, p2.data(), sc.data(), st0.data(), 16, 1, nullptr, 0, 0, -1, o2.data(), st.data(), t2.data(), codes.data());
+  rc |= (st[0] == TC_JOB_INVALID_ENCODING && st[1] == TC_JOB_OK && o2[0] == 0x40) ? 0 : 1;
+  printf("manypoint_host: %s\n", rc ? "FAILED" : "ok");
+  return rc ? 1 : 0;
+}
+#endif

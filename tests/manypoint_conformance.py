@@ -1,0 +1,994 @@
+"""Many-point conformance suite: the two-stage MSM kernels (k_msm.hip / tc_msm.h, G2 and G1) and the comb signer
+(k_comb.hip / tc_comb.h) against Python big integers, beside the device conformance suite (tests/device_conformance.py), whose
+oracle, psi, gls_bases, gls_digits, sac_model, limb helpers and NORM_LO / NORM_HI it reuses.
+
+Two legs run THE SAME case tables through the same checkers:
+
+  * tests/device/manypoint.hip (hipcc, the product's flags) launches the shipped kernels with launch parameters chosen by
+    the test -- `parts` / `share` given, or 0 for the product's launcher --: tests/test_gpu_manypoint.py;
+  * tests/device/manypoint_host.cpp (g++ -DTC_BOUND_CHECK) calls the header routines the kernels call, parts one after the
+    other, then the kernel's xor tree of jac_add: tests/test_manypoint_host.py.
+
+What is checked, all exact: output bytes (the oracle's uncompressed encoding of one multiplication by sum a_i s_i mod r --
+every point is a known multiple [a_i] G), status bytes, the table entries the kernels leave in HBM (decoded from the raw
+words of the tc_table.h / msm_store_entry_g1 layouts: the model's affine point, the infinity flag, every limb inside
+[NORM_LO, NORM_HI] 2^28, |value| <= 2.1 p -- the contract tbl_load_fq declares --, padding words), the digit codes (the
+model's for the columns in use, the 0x5A fill beyond the top column in short-scalar mode), that nothing else is written
+(jobs the MsmFilter leaves to the fast path, *need == 0, table sets 1 .. B-1 of the shared set), and that every legal
+`parts` / `share` and the launcher's own choice give the same bytes.
+
+Models.  Stage T: per share the flip decision, the eight entries (G2: B0 + subsets of the psi-bases; G1: {P, P - phi',
+P + 2 phi', P + phi', 3P, 3P + phi', 3P + 2 phi', 3P + 3 phi'}) from the oracle's affine group law, and the column codes.
+Stage L: because every point is [a] G with known a, psi is [x] on G2 and phi' is [x^2] on G1, every table entry and every
+accumulator value is a known multiple of G, and in a group of prime order r "P = +-Q" and "P = O" are statements about
+these multiples mod r; walk_part walks the part's columns on them and reports the sum and whether the branch-free pass meets
+a special case (an operand at infinity, P = +-Q).  walk_part_points is the same walk on the oracle's group law
+(device_conformance._walk_add); test_manypoint_host.py shows that the two agree.  merge_events does the same for the xor
+tree.  Every directed job carries a claim (which part meets a special case, which merge round doubles / cancels / meets the
+identity) that the model must confirm, and random filler jobs must be shown to meet none.
+
+Wave layout.  The kernels decide on the safe path once per wave (wave_any), so a batch opens with random jobs only (at the
+larger `parts` they fill whole waves that stay on the fast path) and continues with directed jobs, three of them side by
+side (whole waves on the safe path at the largest `parts`), then a random one (mixed waves).
+
+Findings.  (1) job_msm_ladder_safe restarted an accumulator that had come back to the identity from a lazily negated y, which
+the bound analysis rejects in the next addition ("merge opposite" in short-scalar mode at parts = 1: the whole job cancels);
+the selected y is carried now.  (2) job_msm_tables_g1 wrote identities into the SHARED table set when job 0's own scalar was
+bad (shared_case "job0 even" / "job0 >= r"); an entry depends on its point alone now.
+"""
+import ctypes
+import os
+import random
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import device_conformance as dc  # noqa: E402
+
+o = dc.o
+R, X, X2, P = dc.R, dc.X, dc.X2, dc.P
+OK, NOT_ENOUGH, INVALID = 0, 1, 3  # tc_codec.h TC_JOB_*
+POISON = 0x5A
+POISON_WORD = 0x5A5A5A5A
+SLOT_LEAK = -2  # manypoint.hip kMpSlotLeak
+COLS = 65       # tc_msm.h kMsmColumns / tc_comb.h kCombColumns
+ENTRY = {1: 32, 2: 64}  # words per table entry: kMsmEntryWordsG1 / kTblEntryWords
+PT_BYTES = {1: 96, 2: 192}
+MAX_PARTS = {1: 64, 2: 32}
+COMB_SHARE = 8  # tc_comb.h kCombShare
+E = {1: o.E1, 2: o.E2}
+GEN = {1: o.G1_GEN, 2: o.G2_GEN}
+BAD_POINT = {w: bytes([0x1f]) + b"\xff" * (PT_BYTES[w] - 1) for w in (1, 2)}  # x >= p: no decoder takes it
+DEV = dc.DEV
+
+
+def enc(w, pt):
+    return o.g1_uncompressed(pt) if w == 1 else o.g2_uncompressed(pt)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# builds
+# ---------------------------------------------------------------------------------------------------------------------
+def build_device():
+    """tests/device/manypoint.hip -> a gfx950 shared object, with the product's compiler flags (build.py FLAGS)."""
+    from threshold_crypto_amd import build as tcb
+    src = os.path.join(DEV, "manypoint.hip")
+    return dc._build("libtc_manypoint", lambda out: [dc.hipcc()] + tcb.FLAGS + ["-w", "-shared", src, "-o", out], {"manypoint.hip"})
+
+
+def build_host():
+    src = os.path.join(DEV, "manypoint_host.cpp")
+    return dc._build("libtc_manypoint_host_bc",
+                     lambda out: ["g++", "-O1", "-std=c++17", "-w", "-DTC_BOUND_CHECK", "-shared", "-fPIC", src, "-o", out],
+                     {"manypoint_host.cpp"})
+
+
+def build_host_main(extra=()):
+    """The stand-alone program of manypoint_host.cpp (its fixed short case list); extra: e.g. sanitizer flags."""
+    src = os.path.join(DEV, "manypoint_host.cpp")
+    return dc._build("manypoint_host_main",
+                     lambda out: ["g++", "-O1", "-std=c++17", "-w", "-DTC_BOUND_CHECK", "-DMP_MAIN"] + list(extra) + [src, "-o", out],
+                     {"manypoint_host.cpp"})
+
+
+_SZ, _VP, _INT = ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int
+
+
+def load(path, prefix):
+    """prefix "mp_": the device harness; "mph_": the host leg.  The three entries take the same arguments in both."""
+    lib = ctypes.CDLL(path)
+    g2 = getattr(lib, prefix + "msm_g2")
+    g2.argtypes = [_SZ, _SZ, _SZ, _VP, _VP, _VP, _INT, _SZ, _VP, _SZ, _SZ, _INT, _VP, _VP, _VP, _VP]
+    g1 = getattr(lib, prefix + "msm_g1")
+    g1.argtypes = [_SZ, _SZ, _SZ, _VP, _VP, _VP, _INT, _SZ, _VP, _VP, _VP, _VP]
+    comb = getattr(lib, prefix + "comb")
+    comb.argtypes = [_VP, _SZ, _VP, _VP, _SZ, _SZ, _SZ, _VP, _VP, _VP, _VP]
+    for f in (g2, g1, comb):
+        f.restype = _INT
+    return {"g2": g2, "g1": g1, "comb": comb, "lib": lib, "host": prefix == "mph_"}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# group elements as known multiples of the generator
+# ---------------------------------------------------------------------------------------------------------------------
+_POW2 = {}
+_PT = {1: {0: None}, 2: {0: None}}  # multiple mod r -> affine point
+
+
+def gmul(w, m):
+    """[m] G (cached): the sum of the 2^i G of m's bits on the oracle's group law."""
+    m %= R
+    if m not in _PT[w]:
+        if w not in _POW2:
+            pw = [GEN[w]]
+            for _ in range(254):
+                pw.append(E[w].dbl(pw[-1]))
+            _POW2[w] = pw
+        acc = dc._jac_of(E[w], None)
+        for i in range(255):
+            if (m >> i) & 1:
+                acc = E[w]._jadd_affine(acc, _POW2[w][i])
+        _PT[w][m] = E[w]._to_affine(acc)
+    return _PT[w][m]
+
+
+POOL_SIZE = {1: 272, 2: 136}
+_POOL = {}
+
+
+def pool(w):
+    """Distinct multiples a with their points: 24 random ones by multiplication, the rest by additions of those."""
+    if w not in _POOL:
+        rnd = random.Random("manypoint-pool-%d" % w)
+        base = [rnd.randrange(1, R) for _ in range(24)]
+        for a in base:
+            _PT[w][a] = E[w].mul(GEN[w], a)
+        mults = list(base)
+        a = base[0]
+        while len(mults) < POOL_SIZE[w]:
+            b = base[rnd.randrange(24)]
+            pt = E[w].add(_PT[w][a], _PT[w][b])
+            a = (a + b) % R
+            if a and a not in _PT[w]:
+                _PT[w][a] = pt
+                mults.append(a)
+        _POOL[w] = mults
+    return _POOL[w]
+
+
+def neg_mult(w, a):
+    """The multiple of -[a] G (its point goes into the cache without a multiplication)."""
+    a %= R
+    if a in _PT[w] and (R - a) % R not in _PT[w]:
+        _PT[w][(R - a) % R] = E[w].neg(_PT[w][a])
+    return (R - a) % R
+
+
+# entry m of a share's table as a multiple of the share's (possibly negated) point
+T2 = [1 + sum(X ** (j + 1) for j in range(3) if (m >> j) & 1) for m in range(8)]  # B0 + subsets of (|x|, |x|^2, |x|^3) B0
+T1 = [(1, 0), (1, -1), (1, 2), (1, 1), (3, 0), (3, 1), (3, 2), (3, 3)]             # A P + B phi', phi' = [x^2] P
+T1M = [A + B * X2 for A, B in T1]
+TM = {1: T1M, 2: T2}
+
+
+def entry_mults(w, a, flip):
+    return [(-a if flip else a) * t % R for t in TM[w]]
+
+
+def _phi_prime():
+    """phi' = -phi on G1: (x, y) -> (beta x, -y) for the cube root of unity beta that makes it [x^2]."""
+    want = o.E1.mul(o.G1_GEN, X2)
+    g = pow(2, (P - 1) // 3, P)
+    for beta in (g, g * g % P):
+        if beta != 1 and (beta * o.G1_X % P, P - o.G1_Y) == want:
+            return beta
+    raise AssertionError("no cube root of unity gives [x^2]")
+
+
+_BETA = []
+_TBL = {1: {}, 2: {}}
+
+
+def entry_points(w, a, flip=False):
+    """The eight entries of a share with point [a] G by the oracle's AFFINE group law (cached per point)."""
+    a %= R
+    if a == 0:
+        return [None] * 8
+    if a not in _TBL[w]:
+        Ec, p = E[w], gmul(w, a)
+        if w == 2:
+            tbl = dc.subset_table(o.E2, dc.gls_bases(p), True)
+        else:
+            if not _BETA:
+                _BETA.append(_phi_prime())
+            f1 = (_BETA[0] * p[0] % P, P - p[1])
+            p3 = Ec.add(Ec.dbl(p), p)
+            f2 = Ec.dbl(f1)
+            f3 = Ec.add(f2, f1)
+            tbl = [p, Ec.add(p, Ec.neg(f1)), Ec.add(p, f2), Ec.add(p, f1), p3, Ec.add(p3, f1), Ec.add(p3, f2), Ec.add(p3, f3)]
+        _TBL[w][a] = tbl
+    return [E[w].neg(e) for e in _TBL[w][a]] if flip else _TBL[w][a]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# stage T: the recodings
+# ---------------------------------------------------------------------------------------------------------------------
+def sac_cols(d, nbits=64):
+    """sac_recode4 over nbits columns: signs s_i (i < nbits; the leading +1 sits at column nbits), the bits u_j[i] and the
+    top bits.  nbits = 64 is device_conformance.sac_model."""
+    d0 = d[0] | 1
+    s = [1 if (d0 >> (i + 1)) & 1 else -1 for i in range(nbits)]
+    u, top = [], []
+    for j in (1, 2, 3):
+        k, uj = d[j], []
+        for i in range(nbits):
+            uj.append(k & 1)
+            k = (k - s[i] * (k & 1)) >> 1
+        u.append(uj)
+        top.append(k)
+    return s, u, top
+
+
+def g2_codes(k, nbits=64, padding=False):
+    """job_msm_tables' column codes of one share: (codes[0 .. nbits], flip, fits)."""
+    if nbits == 64:
+        flip, fits = k % 2 == 0, True
+        d = dc.gls_digits(R - k if flip else k)
+    else:
+        flip = False
+        d = dc.gls_digits(k)
+        fits = padding or (k % 2 == 1 and all(x >> nbits == 0 for x in d))
+        if padding or not fits:
+            d = [1, 0, 0, 0]
+    s, u, top = sac_cols(d, nbits)
+    codes = [u[0][i] | u[1][i] << 1 | u[2][i] << 2 | (8 if s[i] < 0 else 0) for i in range(nbits)]
+    return codes + [top[0] | top[1] << 1 | top[2] << 2], flip, fits
+
+
+def g1_codes(k, nbits=128, padding=False):
+    """msm_g1_recode's base-4 column codes of one share: (codes[0 .. nbits / 2], flip, fits)."""
+    if nbits == 128:
+        flip, fits = k % 2 == 0, True
+        kp = R - k if flip else k
+        k1, k2 = kp % X2, kp // X2
+    else:
+        flip = False
+        if padding:
+            k = 1
+        k1, k2 = k % X2, k // X2
+        fits = k1 % 2 == 1 and k1 >> nbits == 0 and k2 >> nbits == 0
+        if not fits:
+            k1, k2 = 1, 0
+    k1 |= 1
+    s = [1 if (k1 >> (i + 1)) & 1 else -1 for i in range(nbits)]
+    u = []
+    for i in range(nbits):
+        u.append(k2 & 1)
+        k2 = (k2 - s[i] * (k2 & 1)) >> 1
+    codes = [u[2 * c] | u[2 * c + 1] << 1 | (4 if s[2 * c] == s[2 * c + 1] else 0) | (8 if s[2 * c + 1] < 0 else 0) for c in range(nbits // 2)]
+    return codes + [3 if k2 else 0], flip, fits
+
+
+def codes_of(w, k, nbits, padding=False):
+    return g2_codes(k, nbits, padding) if w == 2 else g1_codes(k, nbits, padding)
+
+
+def codes_value(w, codes):
+    """The multiple of the share's (possibly negated) point that a column of codes stands for, in units of the point."""
+    top = len(codes) - 1
+    step = 2 if w == 2 else 4
+    acc = TM[w][codes[top] & 7]
+    for col in range(top - 1, -1, -1):
+        c = codes[col]
+        acc = acc * step + (-1 if c & 8 else 1) * TM[w][c & 7]
+    return acc
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# stage L: the walk, on multiples and on points
+# ---------------------------------------------------------------------------------------------------------------------
+def msm_part(n, g=0, parts=1):
+    """tc_msm.h msm_part: (s0, s1, trips)."""
+    return g * n // parts, (g + 1) * n // parts, -(-n // parts)
+
+
+def legal_parts(w, n):
+    """The values the launchers can produce: a power of two with at least four shares per part."""
+    return [p for p in (1, 2, 4, 8, 16, 32, 64) if p <= MAX_PARTS[w] and (p == 1 or 4 * p <= n)]
+
+
+def launcher_parts(w, n, B):
+    """launch_msm_g2 / launch_msm_g1: the parts they pick."""
+    parts, slots = 1, 65536 if w == 2 else 131072
+    while parts < MAX_PARTS[w] and B * parts * 2 <= slots and parts * 2 * 4 <= n:
+        parts *= 2
+    return parts
+
+
+def _rel(acc, e):
+    """What the branch-free mixed addition cannot do: an operand at infinity, P = +-Q."""
+    return e % R == 0 or acc % R == 0 or (acc - e) % R == 0 or (acc + e) % R == 0
+
+
+def walk_part(w, mults, codes, s0, s1):
+    """job_msm_ladder_part over the shares [s0, s1) on multiples of G: (the part's sum, a special case was met).
+    mults[s]: the 8 entry multiples of share s; codes[s]: its column codes.  Masked look-ups are not visited: the kernel
+    discards both their sum and their hit."""
+    top = len(codes[s0]) - 1
+    step = 2 if w == 2 else 4
+    acc, special = None, False
+    for col in range(top, -1, -1):
+        if col != top:
+            acc = acc * step % R
+        for s in range(s0, s1):
+            c = codes[s][col]
+            e = mults[s][c & 7]
+            if col != top and c & 8:
+                e = -e % R
+            if acc is None:
+                acc, special = e, e == 0
+            else:
+                special |= _rel(acc, e)
+                acc = (acc + e) % R
+    return acc, special
+
+
+def walk_part_points(w, points, codes, s0, s1):
+    """The same walk on the oracle's group law (device_conformance._walk_add): (affine sum, special)."""
+    Ec = E[w]
+    top = len(codes[s0]) - 1
+    acc, special = None, False
+    for col in range(top, -1, -1):
+        if col != top:
+            acc = Ec._jdbl(acc)
+            if w == 1:
+                acc = Ec._jdbl(acc)
+        for s in range(s0, s1):
+            c = codes[s][col]
+            e = points[s][c & 7]
+            if col != top and c & 8:
+                e = Ec.neg(e)
+            if acc is None:
+                acc, special = dc._jac_of(Ec, e), e is None
+            else:
+                acc, sp = dc._walk_add(Ec, acc, e)
+                special |= sp
+    return Ec._to_affine(acc), special
+
+
+def merge_events(sums):
+    """The xor tree of k_msm_ladder_split / k_msm_ladder_g1<true> over the parts' sums: (lane 0's result, the special
+    operand pairs jac_add meets as (round, lane, kind))."""
+    r, events, rnd_no, d = list(sums), [], 0, 1
+    while d < len(r):
+        nr = []
+        for g in range(len(r)):
+            a, b = r[g], r[g ^ d]
+            kind = "identity" if a == 0 or b == 0 else "equal" if a == b else "opposite" if (a + b) % R == 0 else None
+            if kind:
+                events.append((rnd_no, g, kind))
+            nr.append((a + b) % R)
+        r, d, rnd_no = nr, d * 2, rnd_no + 1
+    return r[0], events
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# MSM jobs and batches
+# ---------------------------------------------------------------------------------------------------------------------
+class Job:
+    """a[i]: the multiple of share i's point (0: the identity; None: an undecodable encoding), k[i]: its scalar.
+    claim: what the model must confirm -- "parts": p with "special": the parts (lane pairs) that meet a special case
+    (exactly those), "special_at_1": whether the unsplit ladder meets one, "merge": (round, kind) an event of the tree.
+    A random job claims that nothing special happens at any legal parts."""
+
+    def __init__(self, a, k, tag, status_in=OK, claim=None, directed=(), idx=None):
+        self.a, self.k, self.tag, self.status_in, self.claim, self.directed, self.idx = list(a), list(k), tag, status_in, claim, set(directed), idx
+        self.random = False
+
+
+class MsmCase:
+    def __init__(self, w, n, B, nbits, jobs, parts, shared=False, filter_t=None, need=-1, tag=""):
+        self.w, self.n, self.B, self.nbits, self.jobs, self.parts, self.shared = w, n, B, nbits, jobs, parts, shared
+        self.filter_t, self.need, self.tag = filter_t, need, tag or "G%d n=%d nbits=%d B=%d%s" % (w, n, nbits, B, " shared" if shared else "")
+        self.shares4 = 4 * ((n + 3) // 4)
+        self.full = nbits == (64 if w == 2 else 128)
+        self.top = nbits if w == 2 else nbits // 2
+        assert len(jobs) == B
+        self._ref = None
+
+    # ---- inputs ----
+    def points(self):
+        jobs = self.jobs[:1] if self.shared else self.jobs
+        return b"".join(BAD_POINT[self.w] if a is None else enc(self.w, gmul(self.w, a)) for j in jobs for a in j.a)
+
+    def scalars(self):
+        return np.array([dc.u32s(k) for j in self.jobs for k in j.k], dtype=np.uint32).reshape(-1)
+
+    def pts_stride(self):
+        return 0 if self.shared else self.n * PT_BYTES[self.w]
+
+    def taken(self, j):
+        """MsmFilter: the job belongs to the two-stage path."""
+        if self.need == 0:
+            return False
+        t = self.filter_t
+        return not (t is not None and 1 <= t <= 3 and dc.small_coeffs_model(self.jobs[j].idx[:t + 1]) is not None)
+
+    # ---- the model of one job ----
+    def share_codes(self, job):
+        """Column codes of all shares4 shares, the flips and whether every scalar is one the mode takes."""
+        out, flips, ok = [], [], True
+        for s in range(self.shares4):
+            pad = s >= self.n
+            k = 0 if pad else job.k[s]
+            if k >= R:
+                ok = False
+                k = 0
+            c, flip, fits = codes_of(self.w, k, self.nbits, pad)
+            ok &= fits
+            out.append(c)
+            flips.append(flip)
+        return out, flips, ok
+
+    def valid(self, job):
+        return all(a is not None for a in job.a) and self.share_codes(job)[2]
+
+    def job_model(self, job, parts):
+        """(sum, per part: special, merge events) of a valid job on multiples of G."""
+        codes, flips, _ = self.share_codes(job)
+        mults = [entry_mults(self.w, job.a[s], flips[s]) for s in range(self.n)]
+        sums, special = [], []
+        for g in range(parts):
+            s0, s1, _ = msm_part(self.n, g, parts)
+            acc, sp = walk_part(self.w, mults, codes, s0, s1)
+            sums.append(acc)
+            special.append(sp)
+        total, events = merge_events(sums)
+        return total, special, events
+
+    def ref(self):
+        """Expected status and output bytes per job, computed once."""
+        if self._ref is None:
+            w, st, out = self.w, [], []
+            for job in self.jobs:
+                if job.status_in != OK:
+                    st.append(job.status_in)
+                    out.append(enc(w, None))
+                elif not self.valid(job):
+                    st.append(INVALID)
+                    out.append(enc(w, None))
+                else:
+                    st.append(OK)
+                    out.append(enc(w, gmul(w, sum(a * k for a, k in zip(job.a, job.k)) % R)))
+            self._ref = (st, out)
+        return self._ref
+
+    def sample(self, job):
+        """Shares whose table entries are decoded and compared: all of them up to n = 13, else the first and last share of
+        every part of every legal parts, the padding shares and the job's directed shares."""
+        if self.n <= 13:
+            return list(range(self.shares4))
+        s = set(range(self.n, self.shares4)) | {x for x in job.directed if x < self.n}
+        for p in legal_parts(self.w, self.n):
+            for g in range(p):
+                s0, s1, _ = msm_part(self.n, g, p)
+                s |= {s0, s1 - 1}
+        return sorted(s)
+
+
+# ---- scalars ----
+def short_scalar(w, nbits, rnd):
+    if w == 2:
+        d = [rnd.getrandbits(nbits) | (1 if j == 0 else 0) for j in range(4)]
+        return sum(x * X ** j for j, x in enumerate(d))
+    return (rnd.getrandbits(nbits) | 1) + rnd.getrandbits(nbits) * X2
+
+
+def rand_scalar(case_full, w, nbits, rnd):
+    return rnd.randrange(1, R) if case_full else short_scalar(w, nbits, rnd)
+
+
+def edge_scalars(w):
+    ks = [0, 1, 2, R - 1, R - 2] + [X ** j + e for j in (1, 2, 3) for e in (0, 1, -1)] + [(1 << 64) - 1, 1 << 64, (1 << 64) + 1, (R - 1) // 2,
+                                                                                         (R + 1) // 2]
+    if w == 1:
+        ks += [k for k in dc._g1_edges(None) if k < R and k not in ks]
+        ks += [R - X2 * ((1 << 126) + 5) - 1]  # (k1 even: recoded as r - k)
+    return ks
+
+
+def _full(w, nbits):
+    return nbits == (64 if w == 2 else 128)
+
+
+def random_job(w, n, nbits, rnd, tag="random"):
+    a = rnd.sample(pool(w), n)
+    j = Job(a, [rand_scalar(_full(w, nbits), w, nbits, rnd) for _ in range(n)], tag)
+    j.random = True
+    return j
+
+
+def _solve(job, shares, t, target):
+    """Set the scalar of share t so that the shares' sum is `target` (multiples of G)."""
+    rest = sum(job.a[s] * job.k[s] for s in shares if s != t) % R
+    job.k[t] = (target - rest) * pow(job.a[t], -1, R) % R
+
+
+def directed_jobs(w, n, nbits, rnd):
+    """The directed jobs of one (group, n, nbits), each with the claim the model has to confirm (Job)."""
+    full = _full(w, nbits)
+    legal = legal_parts(w, n)
+    split = [p for p in legal if p > 1]
+    big = legal[-1]
+    jobs = []
+
+    def base(tag, **kw):
+        j = random_job(w, n, nbits, rnd, tag)
+        j.random = False
+        j.__dict__.update(kw)
+        jobs.append(j)
+        return j
+
+    def rng(p, g):
+        return msm_part(n, g, p)[:2]
+
+    # the identity
+    for p, g in sorted({(big, big - 1), (big, 0)}):
+        s0, _ = rng(p, g)
+        j = base("identity first of part %d/%d" % (g, p), claim={"parts": p, "special": {g}}, directed={s0})
+        j.a[s0] = 0
+    if n >= 3:
+        p = split[0] if split else 1
+        s0, s1 = rng(p, p - 1)
+        j = base("identity in the middle", claim={"parts": p, "special": {p - 1}}, directed={s0 + 1})
+        j.a[s0 + 1] = 0
+    if split:
+        p = big
+        g = 1
+        s0, s1 = rng(p, g)
+        j = base("identity: every share of part %d/%d" % (g, p), claim={"parts": p, "special": {g}, "merge": (0, "identity")}, directed=set(range(s0, s1)))
+        for s in range(s0, s1):
+            j.a[s] = 0
+    j = base("identity: every share", claim={"parts": big, "special": set(range(big))}, directed=set(range(n)))
+    j.a = [0] * n
+    # scalar edges (full-scalar mode), spread over the shares of as many jobs as it takes
+    if full:
+        ks = edge_scalars(w)
+        for i in range(0, len(ks), n):
+            chunk = ks[i:i + n]
+            j = base("scalar edges %d.." % i, directed=set(range(len(chunk))))
+            j.k[:len(chunk)] = chunk
+    # equal points with equal scalars, P and -P
+    # (the branch-free addition meets P = +-Q when the SUM SO FAR is +-the entry: the first two shares of a part)
+    p = split[-1] if split else 1
+    g = p - 1
+    s0, s1 = rng(p, g)
+    if n >= 2:
+        j = base("equal shares at the start of part %d/%d" % (g, p), claim={"parts": p, "special": {g}}, directed={s0, s0 + 1})
+        j.a[s0 + 1], j.k[s0 + 1] = j.a[s0], j.k[s0]
+        j = base("P and -P, equal scalars, at the start of part %d/%d" % (g, p), claim={"parts": p, "special": {g}}, directed={s0, s0 + 1})
+        j.a[s0 + 1], j.k[s0 + 1] = neg_mult(w, j.a[s0]), j.k[s0]
+        j = base("all shares equal", claim={"parts": big, "special": set(range(big))}, directed=set(range(n)))
+        j.a, j.k = [j.a[0]] * n, [j.k[0]] * n
+    if split:
+        p = split[0]
+        s0, s1 = rng(p, 0)
+        # the last share of part 0 and the first of part 1 equal: at parts = 1 the second one meets a sum, at `p` it starts part 1
+        j = base("equal shares across a part boundary", claim={"parts": p, "special": set()}, directed={s1 - 1, s1})
+        j.a[s1], j.k[s1] = j.a[s1 - 1], j.k[s1 - 1]
+        short = [(q, g) for q in split for g in range(q) if rng(q, g)[1] - rng(q, g)[0] < msm_part(n, g, q)[2] and rng(q, g)[1] < n]
+        if short:  # n not divisible by parts: the masked look-up of a shorter part, next to the share it must not take
+            q, g = short[-1]
+            t0, t1 = rng(q, g)
+            j = base("equal shares at the masked position of part %d/%d" % (g, q), claim={"parts": q, "special": set()}, directed={t0, t1 - 1, t1})
+            j.a[t1], j.k[t1] = j.a[t1 - 1], j.k[t1 - 1]
+            j.a[t0 + 1], j.k[t0 + 1] = neg_mult(w, j.a[t0 + 2]), j.k[t0 + 2]  # (... + Q - Q: sums that return to earlier values)
+    # the merge: partial sums of two partners equal, opposite, one of them the identity; first and a later round
+    for p, rd in ([(split[0], 0)] if split else []) + ([(big, big.bit_length() - 2)] if big >= 4 else []):
+        d = 1 << rd
+        sa = list(range(rng(p, 0)[0], rng(p, d - 1)[1]))
+        sb = list(range(rng(p, d)[0], rng(p, 2 * d - 1)[1]))
+        for kind in ("equal", "opposite", "identity"):
+            j = base("merge %s at round %d of parts %d" % (kind, rd, p), claim={"parts": p, "merge": (rd, kind)}, directed={sb[-1]})
+            if full:
+                suma = sum(j.a[s] * j.k[s] for s in sa) % R
+                _solve(j, sb, sb[-1], {"equal": suma, "opposite": -suma, "identity": 0}[kind])
+            elif kind == "identity":
+                for s in sb:
+                    j.a[s] = 0
+                j.directed |= set(sb)
+            elif len(sa) == len(sb):  # short scalars cannot be solved for: the partner's content, or its negative
+                for x, y in zip(sa, sb):
+                    j.a[y], j.k[y] = (j.a[x] if kind == "equal" else neg_mult(w, j.a[x])), j.k[x]
+                j.directed |= set(sb)
+            else:
+                jobs.pop()
+    # failures and kept statuses
+    base("status not OK on entry", status_in=NOT_ENOUGH)
+    j = base("undecodable point", directed={n - 1})
+    j.a[n - 1] = None
+    j = base("scalar = r", directed={0})
+    j.k[0] = R
+    j = base("scalar = 2^256 - 1", directed={n // 2})
+    j.k[n // 2] = (1 << 256) - 1
+    if not full:
+        top = (1 << nbits) - 1
+        j = base("largest short digits", directed={0, n - 1})
+        j.k[0] = j.k[n - 1] = sum(top * X ** i for i in range(4)) if w == 2 else top + top * X2
+        j = base("even short scalar", directed={0})
+        j.k[0] -= 1
+        j = base("digit with bit nbits set", directed={n - 1})
+        j.k[n - 1] = (1 + (1 << nbits) * X) if w == 2 else 1 + (1 << nbits) * X2
+        if w == 1:
+            j = base("k1 with bit nbits set", directed={0})
+            j.k[0] = (1 << nbits) + 1
+    return jobs
+
+
+def check_claims(case):
+    """The model confirms every directed job's claim, and shows the random jobs to meet no special case at all."""
+    bad = []
+    for ji, job in enumerate(case.jobs):
+        if not case.valid(job):
+            continue
+        if job.random:
+            for p in legal_parts(case.w, case.n):
+                _, special, events = case.job_model(job, p)
+                if any(special) or events:
+                    bad.append("job %d (%s): random, but special at parts %d: %s %s" % (ji, job.tag, p, special, events))
+        elif job.claim:
+            c = job.claim
+            _, special, events = case.job_model(job, c["parts"])
+            if "special" in c and {g for g, sp in enumerate(special) if sp} != c["special"]:
+                bad.append("job %d (%s): special parts %s, claimed %s" % (ji, job.tag, special, c["special"]))
+            if "special_at_1" in c and case.job_model(job, 1)[1][0] != c["special_at_1"]:
+                bad.append("job %d (%s): unsplit ladder special != %s" % (ji, job.tag, c["special_at_1"]))
+            if "merge" in c and not any((r, k) == c["merge"] for r, _, k in events):
+                bad.append("job %d (%s): merge events %s, claimed %s" % (ji, job.tag, events, c["merge"]))
+    return bad
+
+
+def lay_out(w, B, rnd_jobs, directed, head):
+    """`head` random jobs, then directed jobs three at a time with a random one after them; random ones to the end."""
+    jobs = [rnd_jobs() for _ in range(min(head, B))]
+    d = list(directed)
+    while len(jobs) < B:
+        for _ in range(3):
+            if d and len(jobs) < B:
+                jobs.append(d.pop(0))
+        if len(jobs) < B:
+            jobs.append(rnd_jobs())
+    return jobs, d
+
+
+_CASES = {}
+
+
+def msm_case(w, n, nbits, B, with_zero=True):
+    """The batch of one shape row: own points, every legal parts and the launcher's choice (0)."""
+    key = (w, n, nbits, B)
+    if key not in _CASES:
+        rnd = random.Random("manypoint-%d-%d-%d-%d" % key)
+
+        def rj():
+            for _ in range(50):
+                j = random_job(w, n, nbits, rnd)
+                one = MsmCase(w, n, 1, nbits, [j], [1])
+                models = [one.job_model(j, p) for p in legal_parts(w, n)]
+                if not any(any(sp) or ev for _, sp, ev in models):
+                    return j
+            raise AssertionError("no random job without a special case")
+        directed = directed_jobs(w, n, nbits, rnd)
+        head = {2: 8, 1: 32}[w] if B > 8 else 0
+        jobs, left = lay_out(w, B, rj, directed, head)
+        case = MsmCase(w, n, B, nbits, jobs, legal_parts(w, n) + [0])
+        case.left_out = [j.tag for j in left]
+        _CASES[key] = case
+    return _CASES[key]
+
+
+def top_case(w):
+    """parts = 32 (G2, n = 128) / 64 (G1, n = 256) with B = 3: a random job, an identity at the start of the last part and
+    merge partners that cancel at the last round."""
+    n = {2: 128, 1: 256}[w]
+    key = (w, n, "top")
+    if key not in _CASES:
+        nbits = 64 if w == 2 else 128
+        rnd = random.Random("manypoint-top-%d" % w)
+        d = directed_jobs(w, n, nbits, rnd)
+        big = MAX_PARTS[w]
+        pick = [j for j in d if j.tag.startswith("identity first of part %d/" % (big - 1)) or j.tag.startswith("merge opposite at round %d" % (big.bit_length() - 2))]
+        assert len(pick) == 2, [j.tag for j in d]
+        _CASES[key] = MsmCase(w, n, 3, nbits, [random_job(w, n, nbits, rnd)] + pick, [big, 0])
+    return _CASES[key]
+
+
+FILTER_IDS = [[0, 1, 2, 3], [70000, 1, 2, 3], [5, 2, 9, 7], [65535, 65536, 65537, 65538], [3, 4, 5, 6], [1 << 40, 2, 3, 4]]
+
+
+def filter_case(n, need=-1):
+    """The filter's shapes: one chunk with padding, t = n - 1, index lists the small-index fast path takes and leaves."""
+    key = (2, n, "filter", need)
+    if key not in _CASES:
+        rnd = random.Random("manypoint-filter-%d" % n)
+        B = 37
+        d = [j for j in directed_jobs(2, n, 64, rnd) if "part boundary" not in j.tag]
+        jobs, _ = lay_out(2, B, lambda: random_job(2, n, 64, rnd), d, 4)
+        for i, j in enumerate(jobs):
+            j.idx = FILTER_IDS[(i + i // 6) % len(FILTER_IDS)][:n]
+            j.claim = None
+            j.random = False
+        _CASES[key] = MsmCase(2, n, B, 64, jobs, [1, 0], filter_t=n - 1, need=need, tag="G2 filter n=%d need=%d" % (n, need))
+    return _CASES[key]
+
+
+def shared_case(n, variant):
+    """G1 short scalars over ONE point set (pts_stride = 0): every job's points are job 0's.  variant: "good" (failing jobs
+    other than 0 among good ones), "job0 even", "job0 >= r" (a failing job 0: the table set it builds for everybody must
+    not depend on its scalars)."""
+    key = (1, n, "shared", variant)
+    if key not in _CASES:
+        rnd = random.Random("manypoint-shared-%d" % n)
+        B, nbits = 70, 32
+        a = rnd.sample(pool(1), n)
+        jobs = []
+        for i in range(B):
+            j = Job(a, [short_scalar(1, nbits, rnd) for _ in range(n)], "shared %d" % i)
+            jobs.append(j)
+        top = (1 << nbits) - 1
+        jobs[3].k[0] = jobs[3].k[n - 1] = top + top * X2
+        jobs[3].tag = "largest short digits"
+        jobs[5].k[1] -= 1
+        jobs[5].tag = "even scalar in job 5"
+        jobs[40].k[n - 1] = R
+        jobs[40].tag = "scalar = r in job 40"
+        jobs[66].status_in = NOT_ENOUGH
+        jobs[67].k[2] = 1 + (1 << nbits) * X2
+        jobs[67].tag = "k2 with bit nbits set"
+        if variant == "job0 even":
+            jobs[0].k[0] -= 1
+        elif variant == "job0 >= r":
+            jobs[0].k[0] = R + 2
+        else:
+            assert variant == "good"
+        for j in jobs:
+            j.directed = {0, 1, 2, 3}
+        _CASES[key] = MsmCase(1, n, B, nbits, jobs, legal_parts(1, n) + [0], shared=True, tag="G1 shared n=%d %s" % (n, variant))
+    return _CASES[key]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# running and checking an MSM batch
+# ---------------------------------------------------------------------------------------------------------------------
+def _ptr(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+class HipError(AssertionError):
+    pass
+
+
+def run_msm(lib, case, parts):
+    """(out, status, tbl, codes) as the leg left them; tbl as int32 (B x shares4 x 8 x entry words), codes (B x 65 x shares4)."""
+    w, n, B = case.w, case.n, case.B
+    pts = np.frombuffer(case.points(), dtype=np.uint8).copy()
+    sc = case.scalars()
+    st_in = np.array([j.status_in for j in case.jobs], dtype=np.uint8)
+    out = np.full(B * PT_BYTES[w], POISON, dtype=np.uint8)
+    status = np.full(B, POISON, dtype=np.uint8)
+    tbl = np.full(B * case.shares4 * 8 * ENTRY[w], POISON_WORD, dtype=np.int32)
+    codes = np.full(B * COLS * case.shares4, POISON, dtype=np.uint8)
+    if w == 2:
+        idx = None
+        if case.filter_t is not None:
+            idx = np.array([j.idx for j in case.jobs], dtype=np.uint64).reshape(-1)
+        rc = lib["g2"](n, B, case.pts_stride(), _ptr(pts), _ptr(sc), _ptr(st_in), case.nbits, parts, _ptr(idx) if idx is not None else None,
+                       n if idx is not None else 0, case.filter_t or 0, case.need, _ptr(out), _ptr(status), _ptr(tbl), _ptr(codes))
+    else:
+        rc = lib["g1"](n, B, case.pts_stride(), _ptr(pts), _ptr(sc), _ptr(st_in), case.nbits, parts, _ptr(out), _ptr(status), _ptr(tbl), _ptr(codes))
+    if rc != 0:
+        raise HipError("%s parts=%d: the harness returned %d" % (case.tag, parts, rc))
+    return (out.reshape(B, -1), status, tbl.reshape(B, case.shares4, 8, ENTRY[w]), codes.reshape(B, COLS, case.shares4))
+
+
+_LIMB_LO, _LIMB_HI = dc.NORM_LO * (1 << dc.RB), dc.NORM_HI * (1 << dc.RB)
+_TOP_MAX = max(-_LIMB_LO, _LIMB_HI)
+TBL_VAL = 2.1  # tc_table.h tbl_load_fq: |value| <= 2.1 p
+
+
+def coord(words, what, bad):
+    """One stored coordinate (16 words): limbs inside the normalised interval, |value| <= 2.1 p; returns the residue."""
+    l = [int(x) for x in words[:14]]
+    if not (all(_LIMB_LO <= x <= _LIMB_HI for x in l[:13]) and abs(l[13]) <= _TOP_MAX):
+        bad.append("%s: limbs outside [%g, %g] 2^28: %s" % (what, dc.NORM_LO, dc.NORM_HI, l))
+    v = dc.value(l)
+    if abs(v) > TBL_VAL * P:
+        bad.append("%s: |value| = %.3f p > 2.1 p" % (what, abs(v) / P))
+    return v * dc.RINV % P
+
+
+def check_entry(w, e, want, what, bad):
+    """One table entry in the layout of tbl_store_g2 (x.c0, x.c1, y.c0, y.c1 rows of 16 words; word 15 of both x rows: the
+    infinity flag) or msm_store_entry_g1 (x, y rows; word 15 of x: the flag), against the model's affine point."""
+    e = [int(x) for x in e]
+    rows = 4 if w == 2 else 2
+    flag_rows = (0, 1) if w == 2 else (0,)
+    for r in range(rows):
+        if e[16 * r + 14] != 0 or e[16 * r + 15] != (int(want is None) if r in flag_rows else 0):
+            bad.append("%s: padding words of row %d: %s (infinity expected: %s)" % (what, r, e[16 * r + 14:16 * r + 16], want is None))
+    cs = [coord(e[16 * r:16 * r + 16], "%s row %d" % (what, r), bad) for r in range(rows)]
+    if want is not None:
+        got = ((cs[0], cs[1]), (cs[2], cs[3])) if w == 2 else (cs[0], cs[1])
+        if got != want:
+            bad.append("%s: wrong point" % what)
+
+
+def check_msm(case, parts, res, max_report=12):
+    """Every check of the suite on one run; returns the list of failures."""
+    out, status, tbl, codes = res
+    w, n, B = case.w, case.n, case.B
+    want_st, want_out = case.ref()
+    bad = []
+    poison_pt = bytes([POISON]) * PT_BYTES[w]
+    for ji, job in enumerate(case.jobs):
+        what = "%s parts=%d job %d (%s)" % (case.tag, parts, ji, job.tag)
+        if len(bad) > max_report:
+            break
+        if not case.taken(ji):  # left to the fast path / nothing to do: nothing is written
+            if bytes(out[ji]) != poison_pt or status[ji] != job.status_in:
+                bad.append("%s: not taken, but output or status written" % what)
+            if not (tbl[ji] == POISON_WORD).all() or not (codes[ji] == POISON).all():
+                bad.append("%s: not taken, but tables or codes written" % what)
+            continue
+        if status[ji] != want_st[ji]:
+            bad.append("%s: status %d, expected %d" % (what, status[ji], want_st[ji]))
+        if bytes(out[ji]) != want_out[ji]:
+            bad.append("%s: wrong output bytes" % what)
+        if not (codes[ji, case.top + 1:] == POISON).all():
+            bad.append("%s: codes written past column %d" % (what, case.top))
+        if case.shared and ji:
+            if not (tbl[ji] == POISON_WORD).all():
+                bad.append("%s: table set %d of the shared mode written" % (what, ji))
+        points_ok = all(a is not None for a in job.a)
+        if not case.valid(job) and not (case.shared and points_ok):
+            continue  # (a failed job's tables and codes are not read by anybody)
+        mcodes, flips, scal_ok = case.share_codes(job)
+        if scal_ok:
+            got = codes[ji, :case.top + 1, :].T.tolist()
+            if got != mcodes:
+                s = next(s for s in range(case.shares4) if got[s] != mcodes[s])
+                bad.append("%s: codes of share %d: %s, expected %s" % (what, s, got[s], mcodes[s]))
+        if case.shared and ji:
+            continue
+        for s in case.sample(job):
+            want = entry_points(w, job.a[s] if s < n else 0, flips[s] and s < n and scal_ok)
+            for m in range(8):
+                check_entry(w, tbl[ji, s, m], want[m], "%s share %d entry %d" % (what, s, m), bad)
+        # limb range of everything the job stored (the sampled entries also had their values checked)
+        limbs = tbl[ji].reshape(case.shares4, 8, -1, 16)[..., :13]
+        if limbs.min() < _LIMB_LO or limbs.max() > _LIMB_HI:
+            bad.append("%s: a stored limb outside [%g, %g] 2^28" % (what, dc.NORM_LO, dc.NORM_HI))
+    return bad
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the comb signer
+# ---------------------------------------------------------------------------------------------------------------------
+def comb_model(k):
+    """job_comb_sign for the key k < r over a point [a] G, in units of a: (flip, fix, special of the doubling-free pass when
+    a != 0, the multiple before the flip)."""
+    flip = k % 2 == 0
+    d = dc.gls_digits(R - k if flip else k)
+    s, u, top, fix = dc.sac_model(d)
+    acc = (T2[top[0] | top[1] << 1 | top[2] << 2] << 64) % R
+    special = False
+    for bit in range(63, -1, -1):
+        e = s[bit] * (T2[u[0][bit] | u[1][bit] << 1 | u[2][bit] << 2] << bit) % R
+        special |= _rel(acc, e)
+        acc = (acc + e) % R
+    if fix:
+        acc = (acc - 1) % R
+    return flip, fix, special, acc
+
+
+class CombCase:
+    """N keys, B messages (a multiple of G2's generator, 0 = the identity, None = undecodable), n signer indices each."""
+
+    def __init__(self, n, B, shares, tag=""):
+        rnd = random.Random("manypoint-comb-%d-%d" % (n, B))
+        self.n, self.B, self.N, self.shares = n, B, 40, shares
+        self.tag = tag or "comb n=%d B=%d" % (n, B)
+        ks = [0, 1, 2, R - 1, R, 3, (1 << 256) - 1, R - 2, X, X + 1, X ** 3 - 1, (R - 1) // 2]
+        self.keys = ks + [rnd.randrange(R) for _ in range(self.N - len(ks))]
+        msgs = [pool(2)[0], 0, pool(2)[1], None, pool(2)[2]]
+        self.msgs = [msgs[j % 5] for j in range(B)]
+        self.idx = []
+        for j in range(B):
+            row = [(j * 7 + 3 * s) % self.N for s in range(n)] if j % 2 else [(s + 3 * j) % 12 for s in range(n)]  # (the directed keys: the even rows)
+            if j % 3 == 0:
+                row[n // 2] = self.N          # the first index out of range
+            if j % 3 == 1:
+                row[n - 1] = 1 << 63
+            self.idx.append(row)
+        self._ref = None
+        self._tables = {}
+
+    def ref(self):
+        if self._ref is None:
+            st, out = [], []
+            for j in range(self.B):
+                a = self.msgs[j]
+                for i in self.idx[j]:
+                    good = a is not None and i < self.N and self.keys[i] < R
+                    st.append(OK if good else INVALID)
+                    out.append(enc(2, gmul(2, a * self.keys[i] % R) if good else None))
+            self._ref = (st, out)
+        return self._ref
+
+    def table(self, a):
+        """The 65 x 8 comb of a message: entry (c, m) = 2^c T[m], by doublings on the oracle's affine group law."""
+        if a not in self._tables:
+            col = entry_points(2, a or 0)
+            cols = [col]
+            for _ in range(COLS - 1):
+                col = [o.E2.dbl(e) for e in col]
+                cols.append(col)
+            self._tables[a] = cols
+        return self._tables[a]
+
+
+_COMB = {}
+
+
+def comb_case(n, B):
+    if (n, B) not in _COMB:
+        _COMB[(n, B)] = CombCase(n, B, list(range(1, COMB_SHARE + 1)) + [0] if B <= 8 else [3, 0])
+    return _COMB[(n, B)]
+
+
+def run_comb(lib, case, share):
+    n, B, N = case.n, case.B, case.N
+    sk = np.frombuffer(b"".join(k.to_bytes(32, "little") for k in case.keys), dtype=np.uint8).copy()
+    idx = np.array(case.idx, dtype=np.uint64).reshape(-1)
+    pts = np.frombuffer(b"".join(BAD_POINT[2] if a is None else enc(2, gmul(2, a)) for a in case.msgs), dtype=np.uint8).copy()
+    out = np.full(B * n * 192, POISON, dtype=np.uint8)
+    status = np.full(B * n, POISON, dtype=np.uint8)
+    ok = np.full(B, POISON, dtype=np.uint8)
+    tbl = np.full(B * COLS * 8 * 64, POISON_WORD, dtype=np.int32)
+    rc = lib["comb"](_ptr(sk), N, _ptr(idx), _ptr(pts), n, B, share, _ptr(out), _ptr(status), _ptr(ok), _ptr(tbl))
+    if rc != 0:
+        raise HipError("%s share=%d: the harness returned %d%s" % (case.tag, share, rc, " (a table slot stayed in use)" if rc == SLOT_LEAK else ""))
+    return out.reshape(B * n, 192), status, ok, tbl.reshape(B, COLS, 8, 64)
+
+
+def check_comb(case, share, res, max_report=12):
+    out, status, ok, tbl = res
+    want_st, want_out = case.ref()
+    bad = []
+    for i in range(case.B * case.n):
+        what = "%s share=%d message %d signer %d" % (case.tag, share, i // case.n, i % case.n)
+        if status[i] != want_st[i]:
+            bad.append("%s: status %d, expected %d" % (what, status[i], want_st[i]))
+        if bytes(out[i]) != want_out[i]:
+            bad.append("%s: wrong output bytes" % what)
+        if len(bad) > max_report:
+            return bad
+    first = {}
+    for j, a in enumerate(case.msgs):
+        what = "%s share=%d message %d" % (case.tag, share, j)
+        if ok[j] != int(a is not None):
+            bad.append("%s: ok byte %d" % (what, ok[j]))
+        if a in first:  # the same point: the same table, word for word (the first one is decoded)
+            if not (tbl[j] == tbl[first[a]]).all():
+                bad.append("%s: its comb differs from message %d's over the same point" % (what, first[a]))
+            continue
+        first[a] = j
+        want = case.table(a)
+        for c in range(COLS):
+            for m in range(8):
+                check_entry(2, tbl[j, c, m], want[c][m], "%s comb entry (%d, %d)" % (what, c, m), bad)
+            if len(bad) > max_report:
+                return bad
+    return bad

@@ -1,0 +1,256 @@
+"""CPU leg of the many-point conformance suite (tests/manypoint_conformance.py): the two-stage MSM (G2 and G1) and the comb
+signer.
+
+(a) tests/device/manypoint.hip -- the product's k_msm.hip and k_comb.hip plus the harness entries -- cross-compiles for
+    gfx950 with the product's flags.
+(b) The models are checked against the oracle: the recodings decode back to the scalar, the entry tables from the affine
+    group law are the multiples the walk uses, the walk on multiples agrees with the walk on the oracle's group law
+    (sum AND special-case verdict), msm_part tiles [0, n).
+(c) Every directed job's claim holds in the model ("this part meets a special case", "this merge round doubles / cancels /
+    meets the identity"), and every random filler job is shown to meet none, at every legal parts.
+(d) The host leg (tests/device/manypoint_host.cpp, g++ -DTC_BOUND_CHECK: the header routines the kernels call) runs the
+    full case tables of the GPU leg through the same checkers, so tables, models and checkers are proven before a GPU run.
+"""
+import ctypes
+import os
+import random
+import subprocess
+import sys
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import manypoint_conformance as mp  # noqa: E402
+
+dc, o, R, X, X2 = mp.dc, mp.o, mp.R, mp.X, mp.X2
+
+G2_FULL = [8, 9, 13, 68]
+G2_SHORT = [1, 5, 64]
+G1_FULL = [8, 9, 13, 68]
+G1_SHORT = [(1, 80), (10, 32), (70, 32)]
+SHARED = [(10, "good"), (10, "job0 even"), (10, "job0 >= r"), (70, "good"), (70, "job0 >= r")]
+COMB = [(3, 5), (8, 5), (9, 5), (24, 5), (30, 5), (30, 70)]
+
+
+def test_manypoint_kernels_cross_compile_for_gfx950():
+    assert os.path.getsize(mp.build_device()) > 0
+
+
+@pytest.fixture(scope="module")
+def host():
+    return mp.load(mp.build_host(), "mph_")
+
+
+def test_stand_alone_program_of_the_host_leg_passes():
+    r = subprocess.run([mp.build_host_main()], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
+
+
+# ---- (b) the models ---------------------------------------------------------------------------------------------------
+def test_msm_part_tiles_the_shares(host):
+    """For every tested (n, parts): the ranges tile [0, n), none is empty, trips = ceil(n / parts) covers the longest --
+    in the model and in tc_msm.h msm_part."""
+    out = (ctypes.c_size_t * 3)()
+    shapes = {(w, n) for w, ns in ((2, G2_FULL + G2_SHORT + [2, 3, 4, 128]), (1, G1_FULL + [1, 10, 70, 256])) for n in ns}
+    for w, n in sorted(shapes):
+        legal = mp.legal_parts(w, n)
+        assert legal[0] == 1 and all(p & (p - 1) == 0 and (p == 1 or 4 * p <= n) for p in legal)
+        for p in legal:
+            nxt = 0
+            for g in range(p):
+                s0, s1, trips = mp.msm_part(n, g, p)
+                host["lib"].mph_msm_part(ctypes.c_size_t(n), ctypes.c_size_t(g), ctypes.c_size_t(p), out)
+                assert (s0, s1, trips) == tuple(out), (n, g, p)
+                assert s0 == nxt and s1 > s0 and s1 - s0 in (trips, trips - 1) and trips == -(-n // p)
+                nxt = s1
+            assert nxt == n
+    assert mp.legal_parts(2, 128)[-1] == 32 and mp.legal_parts(1, 256)[-1] == 64 and mp.legal_parts(2, 127)[-1] == 16
+    # the launcher's own choice for the suite's shapes is one of the legal values
+    assert [mp.launcher_parts(2, n, 37) for n in (4, 8, 13, 68)] == [1, 2, 2, 16] and mp.launcher_parts(2, 128, 3) == 32
+    assert [mp.launcher_parts(1, n, 70) for n in (1, 10, 70)] == [1, 2, 16] and mp.launcher_parts(1, 256, 3) == 64
+
+
+def test_buffer_sizes_match_the_product(host):
+    out = (ctypes.c_size_t * 4)()
+    for n, B in ((1, 1), (9, 37), (68, 70)):
+        host["lib"].mph_sizes(ctypes.c_size_t(n), ctypes.c_size_t(B), out)
+        s4 = 4 * ((n + 3) // 4)
+        assert list(out) == [B * s4 * 8 * 64 * 4, B * 65 * s4, B * s4 * 8 * 32 * 4, B * 65 * 8 * 64 * 4]
+
+
+def test_recodings_decode_back_to_the_scalar():
+    rnd = random.Random(7)
+    assert mp.sac_cols([5, 7, 0, 1 << 63]) == dc.sac_model([5, 7, 0, 1 << 63])[:3]
+    for w in (1, 2):
+        ks = mp.edge_scalars(w) + [rnd.randrange(R) for _ in range(30)]
+        for k in ks:
+            codes, flip, fits = mp.codes_of(w, k, 64 if w == 2 else 128)
+            assert fits and flip == (k % 2 == 0) and len(codes) == 65
+            assert mp.codes_value(w, codes) == (R - k if flip else k), hex(k)
+        nb = 16 if w == 2 else 32
+        for _ in range(30):
+            k = mp.short_scalar(w, nb, rnd)
+            codes, flip, fits = mp.codes_of(w, k, nb)
+            assert fits and not flip and len(codes) == (nb if w == 2 else nb // 2) + 1 and mp.codes_value(w, codes) == k
+        assert mp.codes_of(w, 1, nb, padding=True) == mp.codes_of(w, 1, nb)
+        for k in (2, R - 1, (1 << nb) * (X if w == 2 else X2) + 1):
+            codes, flip, fits = mp.codes_of(w, k, nb)
+            assert not fits and mp.codes_value(w, codes) == 1
+    # the G1 edge list holds scalars with k1 even (flipped) and with the top column at entry 3
+    tops = [mp.g1_codes(k)[0][-1] for k in mp.edge_scalars(1)]
+    assert 3 in tops and 0 in tops and any(k % 2 == 0 for k in mp.edge_scalars(1))
+    assert 1 + (1 << 80) * X2 < R  # (the longest short scalars of the suite are scalars)
+
+
+def test_entry_tables_and_walks_agree_with_the_oracle():
+    """psi = [x] and phi' = [x^2]: the entries from the affine group law are the multiples the integer walk uses; the walk
+    on multiples and the walk on the oracle's group law give the same sum and the same special-case verdict, for generic
+    jobs and for jobs built on an exception."""
+    rnd = random.Random(13)
+    for w in (1, 2):
+        a = mp.pool(w)[5]
+        for flip in (False, True):
+            assert mp.entry_points(w, a, flip) == [mp.gmul(w, m) for m in mp.entry_mults(w, a, flip)]
+        assert mp.gmul(w, a) == mp.E[w].mul(mp.GEN[w], a) and mp.gmul(w, R - 1) == mp.E[w].neg(mp.GEN[w])
+        assert mp.entry_points(w, 0) == [None] * 8
+        n, nbits = 5, 64 if w == 2 else 128
+        jobs = [mp.random_job(w, n, nbits, rnd)] + [j for j in mp.directed_jobs(w, n, nbits, rnd) if j.claim]
+        verdicts = set()
+        for job in jobs:
+            case = mp.MsmCase(w, n, 1, nbits, [job], [1])
+            codes, flips, ok = case.share_codes(job)
+            assert ok
+            mults = [mp.entry_mults(w, job.a[s], flips[s]) for s in range(n)]
+            points = [mp.entry_points(w, job.a[s], flips[s]) for s in range(n)]
+            for s0, s1 in ((0, n), (1, 3)):
+                m, sp = mp.walk_part(w, mults, codes, s0, s1)
+                pt, sp2 = mp.walk_part_points(w, points, codes, s0, s1)
+                assert pt == mp.gmul(w, m) and sp == sp2, job.tag
+                assert m == sum(job.a[s] * job.k[s] for s in range(s0, s1)) % R
+                verdicts.add(sp)
+        assert verdicts == {False, True}
+    assert mp.merge_events([5, 5, 7, R - 7]) == (10, [(0, 0, "equal"), (0, 1, "equal"), (0, 2, "opposite"), (0, 3, "opposite"), (1, 0, "identity"),
+                                                      (1, 1, "identity"), (1, 2, "identity"), (1, 3, "identity")])
+    assert mp.merge_events([1, 2, 3, 4]) == (10, [])
+
+
+def test_comb_model():
+    """The doubling-free pass in units of the message point: it gives k for every key.  For a valid key the recoding never
+    sets fix (d0 = k' mod 2 is odd because |x| is even).  Of tiny keys, keys next to r and small digit vectors the model
+    finds exactly one that meets a special case over a point other than the identity: the key 0 (it runs as r, and the last
+    addition is P = -Q); the other way onto the safe ladder is a message at the identity."""
+    case = mp.comb_case(3, 5)
+    small = [c0 + c1 * X + c2 * X2 + c3 * X ** 3 for c0 in range(4) for c1 in range(3) for c2 in range(2) for c3 in range(2)]
+    for k in case.keys + list(range(64)) + [R - k for k in range(1, 64)] + small:
+        if k < R:
+            flip, fix, special, m = mp.comb_model(k)
+            assert (R - m if flip else m) % R == k and not fix and special == (k == 0), hex(k)
+    assert {0, 1, 2, R - 1} <= set(case.keys) and any(k >= R for k in case.keys)
+    for n, B in COMB:
+        c = mp.comb_case(n, B)
+        flat = [i for row in c.idx for i in row]
+        assert any(i >= c.N for i in flat) and {0, None} <= set(c.msgs) and (B > 8 or any(n % s for s in c.shares if s))
+        assert {c.keys[i] for i in flat if i < c.N} >= ({0, 1, 2, R - 1, R} if B == 5 and n >= 8 else {0, 1})
+
+
+# ---- (c) the claims ---------------------------------------------------------------------------------------------------
+def _all_msm_cases():
+    cases = [mp.msm_case(2, n, 64, 37) for n in G2_FULL] + [mp.msm_case(2, n, 16, 37) for n in G2_SHORT]
+    cases += [mp.msm_case(1, n, 128, 70) for n in G1_FULL] + [mp.msm_case(1, n, nb, 70) for n, nb in G1_SHORT]
+    cases += [mp.top_case(2), mp.top_case(1)]
+    return cases
+
+
+def test_directed_jobs_hit_what_they_claim_and_random_ones_hit_nothing():
+    seen = set()
+    for case in _all_msm_cases():
+        assert not mp.check_claims(case), case.tag
+        assert not getattr(case, "left_out", []), (case.tag, case.left_out)
+        tags = [j.tag for j in case.jobs]
+        seen |= {t.split(" of part")[0].split(" at round")[0].split(" at the start")[0] for t in tags}
+        assert sum(j.random for j in case.jobs) >= (3 if case.B > 3 else 1), case.tag
+        if case.B > 8:  # adversarial jobs share waves with ordinary ones; the head of the batch is ordinary
+            head = 8 if case.w == 2 else 32
+            assert all(j.random for j in case.jobs[:head]) and not all(j.random for j in case.jobs[head:])
+            assert case.B % (32 if case.w == 2 else 64) and case.B > (32 if case.w == 2 else 64)
+    assert seen >= {"identity first", "identity in the middle", "identity: every share", "equal shares", "P and -P, equal scalars,",
+                    "all shares equal", "equal shares across a part boundary", "equal shares at the masked position", "merge equal",
+                    "merge opposite", "merge identity", "status not OK on entry", "undecodable point", "scalar = r", "largest short digits",
+                    "even short scalar", "digit with bit nbits set", "random"}, seen
+    # a later round of the tree is reached where parts >= 4
+    big = [j.claim["merge"] for c in _all_msm_cases() for j in c.jobs if j.claim and "merge" in j.claim]
+    assert {r for r, _ in big} >= {0, 3, 4, 5} and {k for _, k in big} == {"equal", "opposite", "identity"}
+
+
+# ---- (d) the host leg over the full case tables -----------------------------------------------------------------------------
+def _run_case(host, case):
+    first = None
+    for parts in case.parts:
+        if parts == 0:
+            continue  # the launcher's own choice: the device leg
+        res = mp.run_msm(host, case, parts)
+        if first is None or not all((a == b).all() for a, b in zip(res, first)):  # (equal bytes need no second decoding)
+            bad = mp.check_msm(case, parts, res)
+            assert not bad, "\n".join(bad[:12])
+        if first is None:
+            first = res
+        assert all((a == b).all() for a, b in zip(res, first)), (case.tag, parts)
+
+
+@pytest.mark.parametrize("n", G2_FULL)
+def test_host_g2_msm_full_scalars(host, n):
+    _run_case(host, mp.msm_case(2, n, 64, 37))
+
+
+@pytest.mark.parametrize("n", G2_SHORT)
+def test_host_g2_msm_short_scalars(host, n):
+    _run_case(host, mp.msm_case(2, n, 16, 37))
+
+
+@pytest.mark.parametrize("n,need", [(2, -1), (3, -1), (4, -1), (3, 0), (3, 5)])
+def test_host_g2_msm_filter(host, n, need):
+    case = mp.filter_case(n, need)
+    taken = [case.taken(j) for j in range(case.B)]
+    assert (any(taken) and not all(taken)) if need else not any(taken)
+    _run_case(host, case)
+
+
+@pytest.mark.parametrize("w", [2, 1])
+def test_host_msm_largest_parts(host, w):
+    _run_case(host, mp.top_case(w))
+
+
+@pytest.mark.parametrize("n", G1_FULL)
+def test_host_g1_msm_full_scalars(host, n):
+    _run_case(host, mp.msm_case(1, n, 128, 70))
+
+
+@pytest.mark.parametrize("n,nbits", G1_SHORT)
+def test_host_g1_msm_short_scalars(host, n, nbits):
+    _run_case(host, mp.msm_case(1, n, nbits, 70))
+
+
+@pytest.mark.parametrize("n,variant", SHARED)
+def test_host_g1_msm_shared_set(host, n, variant):
+    """A failing job 0 must not change the table set it builds for everybody: jobs 1 .. B-1 still equal the oracle."""
+    case = mp.shared_case(n, variant)
+    st = case.ref()[0]
+    assert st.count(mp.OK) >= case.B - 6 and (st[0] == mp.OK) == (variant == "good") and st[5] == st[40] == st[67] == mp.INVALID
+    _run_case(host, case)
+
+
+@pytest.mark.parametrize("n,B", COMB)
+def test_host_comb(host, n, B):
+    case = mp.comb_case(n, B)
+    first = None
+    for share in case.shares:
+        if share == 0:
+            continue
+        res = mp.run_comb(host, case, share)
+        if first is None or not all((a == b).all() for a, b in zip(res, first)):
+            bad = mp.check_comb(case, share, res)
+            assert not bad, "\n".join(bad[:12])
+        if first is None:
+            first = res
+        assert all((a == b).all() for a, b in zip(res, first))

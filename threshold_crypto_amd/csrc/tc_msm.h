@@ -115,8 +115,10 @@ TC_HD_NOINLINE G2Jac job_msm_ladder_safe(size_t n, const int32_t* tbl, const uin
       const uint32_t code = cc[s];
       G2Affine e = msm_load_entry(tbl + (s * 8 + (code & 7)) * kMsmEntryWords);
       // (the top column adds every entry as it is: no sign select there, so that the accumulator starts from a
-      // carry-normalised y -- the lazy-limb budget of the first real addition depends on it)
-      if (col != nbits) e.y = Fq2::select((code >> 3) & 1, -e.y, e.y);
+      // carry-normalised y -- the lazy-limb budget of the first real addition depends on it; an accumulator that has
+      // come back to the identity -- the entries so far cancel -- restarts from the NEXT entry as it is, so the selected
+      // y is carried too: a negated y there exceeded the multiplier's operand bound in the addition after it)
+      if (col != nbits) e.y = Fq2::select((code >> 3) & 1, -e.y, e.y).norm();
       acc = G2Jac::select(take, jac_add_mixed(acc, e), acc);
     }
   }
@@ -275,11 +277,14 @@ TC_HD bool job_msm_tables_g1(size_t n, size_t c, const uint8_t* points, const ui
     G1Affine p = G1Affine::infinity();
     uint32_t sc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (s < n) {
-      ok &= g1_decode_uncompressed(points + s * 96, p);
+      // (an entry depends on its point alone -- never on a scalar, nor on the shares before it: the job that builds a SHARED
+      // table set builds it for every job, and a bad scalar of its own must only fail that job)
+      const bool decoded = g1_decode_uncompressed(points + s * 96, p);
+      if (!decoded) p = G1Affine::infinity();
+      ok &= decoded;
       for (int w = 0; w < 8; w++) sc[w] = scalars[s * 8 + w];
       ok &= limbs_lt_p<FrParams>(sc);
     }
-    if (!ok) p = G1Affine::infinity();
     if (s >= n && nbits < 128) sc[0] = 1;  // padding shares of the short-scalar mode: a valid short scalar (their point is the identity)
     bool fits = true;
     const bool flip = msm_g1_recode(sc, codes + s, shares4, nbits, &fits);
