@@ -342,8 +342,36 @@ int tc_combine_signatures_robust_batch(tc_ctx* ctx, const uint8_t* commit, size_
 int tc_decrypt_robust_batch(tc_ctx* ctx, const uint8_t* commit, size_t t, size_t N, const uint8_t* present, const uint8_t* shares_g1,
                             const uint8_t* u_g1, const uint8_t* v, const uint64_t* off, const uint8_t* w_g2, size_t B, uint8_t* out_plain,
                             uint8_t* used, uint8_t* bad, uint8_t* status, uint64_t* n_fallback);
+/* The two entries on WIRE BYTES, the form a node receives shares in: sig_shares96 is B x N x 96 (SignatureShare::to_bytes),
+ * shares48 is B x N x 48 (compressed G1 decryption shares).  No B x N uncompressed array is made: step 2 decodes only the
+ * t+1 shares of S0, straight from the caller's array.  Everything not named below -- commit, hashes, u and w (uncompressed,
+ * governed by tc_ctx_set_input_checks), present, used / bad / n_fallback, group / seed32, the limits, B = 0, NULL handling,
+ * device-I/O mode, rules 1 and 3, the all-jobs failure on a bad commit, the invalid-ciphertext behaviour -- is as above.
+ *   Shares are ALWAYS checked.  They are wire forms: from_bytes semantics (src/lib.rs:246-252, :140-146: on the curve AND in
+ *     the order-r subgroup) apply whatever the input-checks setting, as in tc_combine_signatures_wire_batch.
+ *   Rule 2, when a job is clean.  Step 2 decodes the S0 shares only as far as the CURVE (flags, range, square root, sign) and
+ *     defers membership to the combination C: the job is CLEAN when every share of S0 decodes to a curve point and C decodes
+ *     as a curve point, lies in the order-r subgroup and verifies under commit[0] -- one membership ladder per job instead of
+ *     t+1.  That acceptance is sound whatever the shares were: the pairing equation under commit[0] has exactly one solution
+ *     in G2 (in G1), so a subgroup point that satisfies it IS the master key's signature (IS sk u).  "No claim about
+ *     individual shares" now also covers membership: a non-member share inside S0 is reported only if its job reaches step 3,
+ *     which happens with overwhelming probability because the cofactor component of a random curve point has large order (its
+ *     multiple by a Lagrange coefficient does not vanish, so C is no subgroup point).  The invariant is
+ *         status OK  =>  out is the master key's signature / the true plaintext.
+ *   Step 3 gives every present share the full checked decode of from_bytes and its own pairing check, so a non-member share
+ *     ends as a bad bit there.  A share of S0 that fails even the curve-level decode sends its job to step 3; it is not a job
+ *     failure.
+ *   Output form.  out_sig96 is B x 96, Signature::to_bytes of the result; a job that does not end OK gets the identity's
+ *     compressed encoding (0xC0, then zeros).  out_plain is as above. */
+int tc_combine_signatures_robust_wire_batch(tc_ctx* ctx, const uint8_t* commit, size_t t, size_t N, const uint8_t* present,
+                                            const uint8_t* sig_shares96, const uint8_t* hashes, const uint8_t* msgs, const uint64_t* off, size_t B,
+                                            size_t group, const uint8_t* seed32, uint8_t* out_sig96, uint8_t* used, uint8_t* bad, uint8_t* status,
+                                            uint64_t* n_fallback);
+int tc_decrypt_robust_wire_batch(tc_ctx* ctx, const uint8_t* commit, size_t t, size_t N, const uint8_t* present, const uint8_t* shares48,
+                                 const uint8_t* u_g1, const uint8_t* v, const uint64_t* off, const uint8_t* w_g2, size_t B, uint8_t* out_plain,
+                                 uint8_t* used, uint8_t* bad, uint8_t* status, uint64_t* n_fallback);
 
-/* ---- DKG algebra (src/poly.rs) ----------------------------------------------------------------- */
+/* ---- DKG algebra (src/poly.rs)----------------------------------------------------------------- */
 /* out[i] = coeff_fr[i] * g1: Poly::commitment src/poly.rs:372-377 and BivarPoly::commitment :625-632 (every
  * coefficient times the G1 generator).  Fixed base: a signed 4-bit window table of g1, built once per context
  * and staged in LDS by every workgroup -- 64 mixed additions and no doubling per coefficient. */

@@ -34,6 +34,8 @@ using Bytes = std::vector<std::uint8_t>;
 using G1Bytes = std::array<std::uint8_t, 96>;
 using G2Bytes = std::array<std::uint8_t, 192>;
 using FrBytes = std::array<std::uint8_t, 32>;
+using G1Wire = std::array<std::uint8_t, 48>;  // the compressed (wire) forms: to_bytes of a G1 / G2 value
+using G2Wire = std::array<std::uint8_t, 96>;
 
 // An index type beyond u64 -- `T: IntoFr` of combine_signatures / decrypt (src/lib.rs:608-622) for T = Fr, i32, i64
 // (src/into_fr.rs:10-14, 28-56): the field element as 32 little-endian bytes, ordered by its canonical value like the derived
@@ -589,6 +591,66 @@ class PublicKeySet {
     if (B)
       e.check(tc_decrypt_robust_batch(e.ctx(), commit.data(), threshold(), N, present.data(), sh.data(), u.data(), v.data(), v.off.data(), w.data(), B,
                                       plain.data(), used.data(), bad.data(), st.data(), n_fallback));
+    robust_results(B, N, st, used, bad, results);
+    std::vector<Bytes> out(B);
+    for (std::size_t j = 0; j < B; j++)
+      if (st[j] == TC_JOB_OK) out[j].assign(plain.begin() + v.off[j], plain.begin() + v.off[j + 1]);
+    return out;
+  }
+
+  // The two robust combiners on WIRE BYTES (tc_combine_signatures_robust_wire_batch / tc_decrypt_robust_wire_batch): jobs[j] maps
+  // node index to the 96 bytes of SignatureShare::to_bytes (the 48 bytes of a compressed DecryptionShare) as received.  Only
+  // the t+1 shares that are combined get decoded, and group membership is tested on the combination; a message whose
+  // combination does not stand has every received share decoded as from_bytes decodes (curve AND subgroup, whatever the
+  // input-checks setting) and checked.  status OK means the result IS the master key's signature / the true plaintext.
+  // Signatures come back as Signature::to_bytes; a message that did not end OK gets the identity's encoding (0xC0, then zeros).
+  std::vector<G2Wire> combine_signatures_robust_wire_batch(const std::vector<std::map<std::uint64_t, G2Wire>>& jobs, const Messages& msgs,
+                                                           std::size_t n_nodes, const std::array<std::uint8_t, 32>& seed,
+                                                           std::vector<RobustResult>& results, std::uint64_t* n_fallback = nullptr,
+                                                           Engine& e = Engine::instance()) const {
+    const std::size_t B = jobs.size(), N = n_nodes;
+    if (msgs.size() != B) throw std::invalid_argument("one message per share set");
+    std::vector<std::uint8_t> sh(B * N * 96 + 1), present(B * N + 1, 0), flat(B * 96 + 1), used(B * N + 1), bad(B * N + 1), st(B + 1);
+    for (std::size_t j = 0; j < B; j++)
+      for (const auto& kv : jobs[j]) {
+        if (kv.first >= N) throw std::invalid_argument("node index outside 0..n_nodes-1");
+        std::memcpy(&sh[(j * N + kv.first) * 96], kv.second.data(), 96);
+        present[j * N + kv.first] = 1;
+      }
+    std::vector<std::uint8_t> commit(commit_.size() * 96);
+    for (std::size_t k = 0; k < commit_.size(); k++) std::memcpy(&commit[k * 96], commit_[k].data(), 96);
+    if (B)
+      e.check(tc_combine_signatures_robust_wire_batch(e.ctx(), commit.data(), threshold(), N, present.data(), sh.data(), nullptr, msgs.data(),
+                                                      msgs.off.data(), B, 0, seed.data(), flat.data(), used.data(), bad.data(), st.data(),
+                                                      n_fallback));
+    std::vector<G2Wire> out(B);
+    robust_results(B, N, st, used, bad, results);
+    for (std::size_t j = 0; j < B; j++) std::memcpy(out[j].data(), &flat[j * 96], 96);
+    return out;
+  }
+  std::vector<Bytes> decrypt_robust_wire_batch(const std::vector<std::map<std::uint64_t, G1Wire>>& jobs, const std::vector<Ciphertext>& cts,
+                                               std::size_t n_nodes, std::vector<RobustResult>& results, std::uint64_t* n_fallback = nullptr,
+                                               Engine& e = Engine::instance()) const {
+    const std::size_t B = jobs.size(), N = n_nodes;
+    if (cts.size() != B) throw std::invalid_argument("one ciphertext per share set");
+    std::vector<std::uint8_t> sh(B * N * 48 + 1), present(B * N + 1, 0), u(B * 96 + 1), w(B * 192 + 1), used(B * N + 1), bad(B * N + 1), st(B + 1);
+    Messages v;
+    for (std::size_t j = 0; j < B; j++) {
+      for (const auto& kv : jobs[j]) {
+        if (kv.first >= N) throw std::invalid_argument("node index outside 0..n_nodes-1");
+        std::memcpy(&sh[(j * N + kv.first) * 48], kv.second.data(), 48);
+        present[j * N + kv.first] = 1;
+      }
+      std::memcpy(&u[j * 96], cts[j].u.data(), 96);
+      std::memcpy(&w[j * 192], cts[j].w.data(), 192);
+      v.push(cts[j].v);
+    }
+    std::vector<std::uint8_t> commit(commit_.size() * 96);
+    for (std::size_t k = 0; k < commit_.size(); k++) std::memcpy(&commit[k * 96], commit_[k].data(), 96);
+    Bytes plain(v.flat.size() + 1);
+    if (B)
+      e.check(tc_decrypt_robust_wire_batch(e.ctx(), commit.data(), threshold(), N, present.data(), sh.data(), u.data(), v.data(), v.off.data(),
+                                           w.data(), B, plain.data(), used.data(), bad.data(), st.data(), n_fallback));
     robust_results(B, N, st, used, bad, results);
     std::vector<Bytes> out(B);
     for (std::size_t j = 0; j < B; j++)

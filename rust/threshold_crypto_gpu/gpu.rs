@@ -606,6 +606,83 @@ impl PublicKeySet {
             .map(|((&s, o), (u, b))| RobustResult { value: wire_status_to_result(s, out.get(o[0] as usize..o[1] as usize).map(|p| p.to_vec()).unwrap_or_default()), used: marked(u), bad: marked(b) })
             .collect())
     }
+    /// `combine_signatures_robust_batch` on WIRE BYTES (tc_combine_signatures_robust_wire_batch): `jobs[j]` maps node index to the
+    /// `SignatureShare::to_bytes` form received from that node.  Only the t+1 shares that are combined get decoded, and group
+    /// membership is tested on the combination; a message whose combination does not stand has every received share decoded
+    /// as `from_bytes` decodes (src/lib.rs:246-252: curve and subgroup) and checked.  The value of a message that ends OK is
+    /// `Signature::to_bytes` of the master key's signature.
+    pub fn combine_signatures_robust_wire_batch<M: AsRef<[u8]>>(&self, gpu: &Gpu, n_nodes: usize, jobs: &[std::collections::BTreeMap<u64, [u8; SIG_SIZE]>], msgs: &[M], seed: &[u8; 32]) -> GpuResult<Vec<RobustResult<[u8; SIG_SIZE]>>> {
+        if jobs.len() != msgs.len() {
+            return Err(shape_error("one message per share set"));
+        }
+        if jobs.is_empty() {
+            return Ok(Vec::new());
+        }
+        if n_nodes == 0 {
+            return Err(shape_error("n_nodes must be at least t + 1"));
+        }
+        let (mut shares, mut present) = (vec![0u8; jobs.len() * n_nodes * SIG_SIZE], vec![0u8; jobs.len() * n_nodes]);
+        for (j, job) in jobs.iter().enumerate() {
+            for (&i, s) in job {
+                let slot = if (i as usize) < n_nodes { j * n_nodes + i as usize } else { return Err(shape_error("node index outside 0..n_nodes")) };
+                shares.get_mut(slot * SIG_SIZE..(slot + 1) * SIG_SIZE).ok_or_else(|| shape_error("node index outside 0..n_nodes"))?.copy_from_slice(s);
+                *present.get_mut(slot).ok_or_else(|| shape_error("node index outside 0..n_nodes"))? = 1;
+            }
+        }
+        let commit = self.commit_bytes();
+        let (flat, off) = pack_messages(msgs);
+        let (mut out, mut st) = (vec![0u8; jobs.len() * SIG_SIZE], vec![0u8; jobs.len()]);
+        let (mut used, mut bad) = (vec![0u8; jobs.len() * n_nodes], vec![0u8; jobs.len() * n_nodes]);
+        let mut fallback = 0u64;
+        gpu.check(unsafe {
+            tc_combine_signatures_robust_wire_batch(gpu.0, commit.as_ptr(), self.threshold(), n_nodes, present.as_ptr(), shares.as_ptr(), std::ptr::null(), flat.as_ptr(), off.as_ptr(), jobs.len(), 0, seed.as_ptr(), out.as_mut_ptr(), used.as_mut_ptr(), bad.as_mut_ptr(), st.as_mut_ptr(), &mut fallback)
+        })?;
+        Ok(st
+            .iter()
+            .zip(out.chunks(SIG_SIZE))
+            .zip(used.chunks(n_nodes).zip(bad.chunks(n_nodes)))
+            .map(|((&s, o), (u, b))| {
+                let mut sig = [0u8; SIG_SIZE];
+                sig.copy_from_slice(o);
+                RobustResult { value: wire_status_to_result(s, sig), used: marked(u), bad: marked(b) }
+            })
+            .collect())
+    }
+    /// `decrypt_robust_batch` on WIRE BYTES (tc_decrypt_robust_wire_batch): `jobs[j]` maps node index to the 48 compressed
+    /// bytes of the `DecryptionShare` received for `cts[j]`.
+    pub fn decrypt_robust_wire_batch(&self, gpu: &Gpu, n_nodes: usize, jobs: &[std::collections::BTreeMap<u64, [u8; PK_SIZE]>], cts: &[Ciphertext]) -> GpuResult<Vec<RobustResult<Vec<u8>>>> {
+        if jobs.len() != cts.len() {
+            return Err(shape_error("one ciphertext per share set"));
+        }
+        if jobs.is_empty() {
+            return Ok(Vec::new());
+        }
+        if n_nodes == 0 {
+            return Err(shape_error("n_nodes must be at least t + 1"));
+        }
+        let (mut shares, mut present) = (vec![0u8; jobs.len() * n_nodes * PK_SIZE], vec![0u8; jobs.len() * n_nodes]);
+        for (j, job) in jobs.iter().enumerate() {
+            for (&i, s) in job {
+                let slot = if (i as usize) < n_nodes { j * n_nodes + i as usize } else { return Err(shape_error("node index outside 0..n_nodes")) };
+                shares.get_mut(slot * PK_SIZE..(slot + 1) * PK_SIZE).ok_or_else(|| shape_error("node index outside 0..n_nodes"))?.copy_from_slice(s);
+                *present.get_mut(slot).ok_or_else(|| shape_error("node index outside 0..n_nodes"))? = 1;
+            }
+        }
+        let commit = self.commit_bytes();
+        let (u, flat, off, w) = ciphertext_columns(cts);
+        let (mut out, mut st) = (vec![0u8; flat.len()], vec![0u8; jobs.len()]);
+        let (mut used, mut bad) = (vec![0u8; jobs.len() * n_nodes], vec![0u8; jobs.len() * n_nodes]);
+        let mut fallback = 0u64;
+        gpu.check(unsafe {
+            tc_decrypt_robust_wire_batch(gpu.0, commit.as_ptr(), self.threshold(), n_nodes, present.as_ptr(), shares.as_ptr(), u.as_ptr(), flat.as_ptr(), off.as_ptr(), w.as_ptr(), jobs.len(), out.as_mut_ptr(), used.as_mut_ptr(), bad.as_mut_ptr(), st.as_mut_ptr(), &mut fallback)
+        })?;
+        Ok(st
+            .iter()
+            .zip(off.windows(2))
+            .zip(used.chunks(n_nodes).zip(bad.chunks(n_nodes)))
+            .map(|((&s, o), (u, b))| RobustResult { value: wire_status_to_result(s, out.get(o[0] as usize..o[1] as usize).map(|p| p.to_vec()).unwrap_or_default()), used: marked(u), bad: marked(b) })
+            .collect())
+    }
 }
 /// One message of the robust combiners: the value or the job's error, and the node indices used / found bad.
 #[derive(Debug, PartialEq)]

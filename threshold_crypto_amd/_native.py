@@ -56,6 +56,10 @@ PROTOTYPES = {
                                            ctypes.POINTER(ctypes.c_uint64)],
     "tc_decrypt_robust_batch": [_u8p, _sz, _sz, _u8p, _u8p, _u8p, _u8p, _u64p, _u8p, _sz, _u8p, _u8p, _u8p, _u8p,
                                 ctypes.POINTER(ctypes.c_uint64)],
+    "tc_combine_signatures_robust_wire_batch": [_u8p, _sz, _sz, _u8p, _u8p, _u8p, _u8p, _u64p, _sz, _sz, ctypes.c_char_p, _u8p, _u8p, _u8p, _u8p,
+                                                ctypes.POINTER(ctypes.c_uint64)],
+    "tc_decrypt_robust_wire_batch": [_u8p, _sz, _sz, _u8p, _u8p, _u8p, _u8p, _u64p, _u8p, _sz, _u8p, _u8p, _u8p, _u8p,
+                                     ctypes.POINTER(ctypes.c_uint64)],
     "tc_ciphertext_verify_batch": [_u8p, _u8p, _u64p, _u8p, _sz, _u8p],
     "tc_pairing_product_check_batch": [_u8p, _u8p, _sz, _sz, _u8p],
     "tc_ciphertext_verify_rlc_batch": [_u8p, _u8p, _u64p, _u8p, _sz, _sz, ctypes.c_char_p, _u8p, ctypes.POINTER(ctypes.c_uint64)],

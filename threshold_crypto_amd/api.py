@@ -607,6 +607,40 @@ class PublicKeySet:
                                                  _stack([c.w for c in cts], 192), present=present)
         return [self._robust_result(bytes(out[int(off[j]): int(off[j + 1])]), st[j], used[j], bad[j]) for j in range(len(jobs))]
 
+    def combine_signatures_robust_wire_batch(self, jobs, msgs, n_nodes=None, engine=None, seed=None, group=0):
+        """combine_signatures_robust_batch on wire bytes, tc_combine_signatures_robust_wire_batch: jobs[j] maps node index -> the
+        96 bytes received from that node (SignatureShare::to_bytes).  Only the t+1 shares that are combined get decoded, and
+        group membership is tested on the combination; a message whose combination does not stand has every received share
+        decoded as from_bytes decodes (curve and subgroup) and checked.  Returns what combine_signatures_robust_batch returns;
+        a Signature that comes back IS the master key's signature of the message."""
+        e = engine or default_engine()
+        if len(jobs) != len(msgs):
+            raise ValueError("one message per share set")
+        N, sh, present = self._robust_operands(jobs, n_nodes, SIG_SIZE)
+        flat, off = pack_messages([bytes(m) for m in msgs])
+        out, used, bad, st, _ = e.combine_signatures_robust_wire(_stack(self.commit, 96), sh, msgs=flat, off=off, present=present, group=group,
+                                                                 seed=seed)
+        good = [j for j in range(len(jobs)) if not int(st[j])]
+        full = {}
+        if good:  # the values of this module hold the uncompressed form
+            pts, dst = e.g2_decompress(np.ascontiguousarray(out[good]))
+            for k, j in enumerate(good):
+                _raise_status(dst[k])
+                full[j] = Signature(pts[k], _trusted=True)
+        return [self._robust_result(full.get(j), st[j], used[j], bad[j]) for j in range(len(jobs))]
+
+    def decrypt_robust_wire_batch(self, jobs, cts, n_nodes=None, engine=None):
+        """decrypt_robust_batch on wire bytes, tc_decrypt_robust_wire_batch: jobs[j] maps node index -> the 48 bytes of the
+        compressed DecryptionShare received for cts[j]."""
+        e = engine or default_engine()
+        if len(jobs) != len(cts):
+            raise ValueError("one ciphertext per share set")
+        N, sh, present = self._robust_operands(jobs, n_nodes, 48)
+        v, off = pack_messages([c.v for c in cts])
+        out, used, bad, st, _ = e.decrypt_robust_wire(_stack(self.commit, 96), sh, _stack([c.u for c in cts], 96), v, off,
+                                                      _stack([c.w for c in cts], 192), present=present)
+        return [self._robust_result(bytes(out[int(off[j]): int(off[j + 1])]), st[j], used[j], bad[j]) for j in range(len(jobs))]
+
 
 class SecretKeySet:
     """struct SecretKeySet { poly: Poly } (src/lib.rs:631-635); poly = Fr coefficients."""

@@ -143,6 +143,40 @@ __global__ __launch_bounds__(kBlock, TC_WAVES_G2) void k_decompress_take_g2_x2(c
     if (has_b) valid[ib] = sb == TC_JOB_OK ? 1 : 0;
   }
 }
+// Wire ingest for the ROBUST combiners (tc_combine_signatures_robust_wire_batch / tc_decrypt_robust_wire_batch): record
+// i = j * need + k is the k-th share k_select_shares picked for job j, in[(j * N + slot[i]) * CBYTES ..], through the CURVE-LEVEL
+// decode (tc_sqrt.h MEMBER = false: the membership test is made once, on the combination), written compactly to out[i * BYTES ..]
+// with ok[i] = 1 iff it decoded.  A job without enough shares (enough[j] == 0, slots 0xffffffff) is not read: identities with
+// ok = 1, as k_gather_selected gives it.  One lane (G1) / one lane pair (G2) per record; every output byte has one writer.
+// Like their neighbours above these kernels hold no per-lane table: Call::guard_private (tc_api.hip) needs no new term.
+template <class F>
+__global__ __launch_bounds__(kBlock, (JobLanes<F>::N > 1 ? TC_WAVES_G2 : TC_WAVES_G1)) void k_decompress_selected(
+    const uint8_t* __restrict__ in, size_t N, size_t need, const uint32_t* __restrict__ slot, const uint8_t* __restrict__ enough, size_t n,
+    uint8_t* __restrict__ out, uint8_t* __restrict__ ok) {
+  constexpr int L = JobLanes<F>::N;
+  const size_t i = ((size_t)blockIdx.x * kBlock + threadIdx.x) / L;
+  if (i >= n) return;
+  const bool good = job_decompress_selected<F>(in, N, need, slot, enough, i, out + i * PointIO<F>::BYTES);
+  if (L == 1 || pair_leader()) ok[i] = good ? 1 : 0;
+}
+// G2: a lane pair takes records 2p and 2p + 1 (tc_duo.h), which may belong to two jobs; an odd count repeats the last pair's
+// first record in its second slot
+__global__ __launch_bounds__(kBlock, TC_WAVES_G2) void k_decompress_selected_g2_x2(const uint8_t* __restrict__ in, size_t N, size_t need,
+                                                                                const uint32_t* __restrict__ slot,
+                                                                                const uint8_t* __restrict__ enough, size_t n,
+                                                                                uint8_t* __restrict__ out, uint8_t* __restrict__ ok) {
+  const size_t p = ((size_t)blockIdx.x * kBlock + threadIdx.x) / kG2Lanes;
+  const size_t ia = 2 * p;
+  if (ia >= n) return;
+  const bool has_b = ia + 1 < n;
+  const size_t ib = has_b ? ia + 1 : ia;
+  bool oka, okb;
+  job_decompress_selected_g2_x2(in, N, need, slot, enough, ia, ib, out + ia * 192, has_b ? out + ib * 192 : nullptr, oka, okb);
+  if (pair_leader()) {
+    ok[ia] = oka ? 1 : 0;
+    if (has_b) ok[ib] = okb ? 1 : 0;
+  }
+}
 // the matching prefix of the index array: out[j * take + k] = idx[j * n_per_job + k]
 __global__ void k_take_u64(const uint64_t* __restrict__ in, size_t n_per_job, size_t take, size_t n, uint64_t* __restrict__ out) {
   const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
@@ -217,6 +251,14 @@ void launch_decompress_take(const Tuning& tn, hipStream_t st, bool g2, const uin
   if (g2 && duo_form(n, tn.duo_min_decode)) hipLaunchKernelGGL(k_decompress_take_g2_x2, dim3(grid_for((n + 1) / 2 * kG2Lanes)), dim3(kBlock), 0, st, in, n_per_job, take, n, out, valid);
   else if (g2) hipLaunchKernelGGL(k_decompress_take<Fq2>, dim3(grid_for(n * kG2Lanes)), dim3(kBlock), 0, st, in, n_per_job, take, n, out, valid);
   else hipLaunchKernelGGL(k_decompress_take<Fq>, dim3(grid_for(n)), dim3(kBlock), 0, st, in, n_per_job, take, n, out, valid);
+}
+void launch_decompress_selected(const Tuning& tn, hipStream_t st, bool g2, const uint8_t* in, size_t N, size_t need, const uint32_t* slot,
+                                const uint8_t* enough, size_t jobs, uint8_t* out, uint8_t* ok) {
+  const size_t n = jobs * need;
+  if (!n) return;
+  if (g2 && duo_form(n, tn.duo_min_decode)) hipLaunchKernelGGL(k_decompress_selected_g2_x2, dim3(grid_for((n + 1) / 2 * kG2Lanes)), dim3(kBlock), 0, st, in, N, need, slot, enough, n, out, ok);
+  else if (g2) hipLaunchKernelGGL(k_decompress_selected<Fq2>, dim3(grid_for(n * kG2Lanes)), dim3(kBlock), 0, st, in, N, need, slot, enough, n, out, ok);
+  else hipLaunchKernelGGL(k_decompress_selected<Fq>, dim3(grid_for(n)), dim3(kBlock), 0, st, in, N, need, slot, enough, n, out, ok);
 }
 void launch_take_u64(hipStream_t st, const uint64_t* in, size_t n_per_job, size_t take, size_t B, uint64_t* out) {
   if (B * take) hipLaunchKernelGGL(k_take_u64, dim3(grid_for(B * take)), dim3(kBlock), 0, st, in, n_per_job, take, B * take, out);

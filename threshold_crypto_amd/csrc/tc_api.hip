@@ -1871,7 +1871,14 @@ int tc_verify_decryption_shares_rlc_batch(tc_ctx* ctx, const uint8_t* pk_shares,
 // device (k_robust.hip); the host sees B verdict bytes between the passes and builds the job maps of pass 2, as the other
 // combined entries do.  sig: G2 shares against hash points (hashes, or msgs / off hashed here); otherwise G1 decryption shares
 // against the ciphertexts (u, msgs = v, off, w) and the plaintexts as output.
-static int robust_combine(tc_ctx* ctx, bool sig, const uint8_t* commit, size_t t, size_t N, const uint8_t* present, const uint8_t* shares,
+//
+// wire: the shares are the COMPRESSED wire forms (96 / 48 bytes, always checked: from_bytes src/lib.rs:246-252, 140-146) and a
+// signature leaves compressed.  Pass 1 decodes only the t+1 selected shares, straight out of the caller's array and only as far
+// as the curve (k_decompress_selected); membership is tested ONCE per job, on the combination: a point of the order-r subgroup
+// that satisfies the pairing equation under commit[0] is THE signature (THE sk u) whatever it was combined from.  A
+// combination that is off the curve, outside the subgroup or does not verify sends its job to pass 2, where every present
+// share goes through the full checked decode and its own pairing check.
+static int robust_combine(tc_ctx* ctx, bool sig, bool wire, const uint8_t* commit, size_t t, size_t N, const uint8_t* present, const uint8_t* shares,
                           const uint8_t* hashes, const uint8_t* msgs, const uint64_t* off, const uint8_t* u, const uint8_t* w, size_t B,
                           size_t group, const uint8_t* seed32, uint8_t* out, bool out_unbacked, uint8_t* used, uint8_t* bad, uint8_t* status,
                           uint64_t* n_fallback) {
@@ -1888,6 +1895,7 @@ static int robust_combine(tc_ctx* ctx, bool sig, const uint8_t* commit, size_t t
   if (group > 1024) group = 1024;
   if (group > B) group = B;
   const size_t PB = sig ? 192 : 96, need = t + 1;
+  const size_t SB = wire ? PB / 2 : PB;  // bytes per share in the caller's array
   Call k(ctx);
   uint64_t total = 0;
   if (off) {
@@ -1897,7 +1905,9 @@ static int robust_combine(tc_ctx* ctx, bool sig, const uint8_t* commit, size_t t
   }
   const uint8_t* d_commit = k.in(commit, need * 96);
   const uint8_t* d_present = k.in(present, B * N);
-  const uint8_t* d_sh = k.in(shares, B * N * PB);
+  const uint8_t* d_sh = k.in(shares, B * N * SB);
+  // (pass 2 expands the failed jobs' shares to the uncompressed form: guard_private sees the size the uncompressed entry has)
+  if (wire) k.operand_bytes += B * N * SB;
   const uint8_t* d_hash_in = hashes ? k.in(hashes, B * 192) : nullptr;
   const uint8_t* d_msgs = off ? k.in(msgs, (size_t)total) : nullptr;
   const uint64_t* d_off = off ? k.in(off, B + 1) : nullptr;
@@ -1907,7 +1917,9 @@ static int robust_combine(tc_ctx* ctx, bool sig, const uint8_t* commit, size_t t
   uint8_t* d_used = k.out(used, B * N, /*zero=*/true);
   uint8_t* d_bad = k.out(bad, B * N, /*zero=*/true);
   // the point result: the caller's signatures, or the G1 value the plaintext is masked with
-  uint8_t* d_res = sig ? k.out(out, B * 192) : k.temp<uint8_t>(B * 96);
+  // (wire signatures: compressed into the caller's B x 96 at the end)
+  uint8_t* d_res = sig && !wire ? k.out(out, B * 192) : k.temp<uint8_t>(B * PB);
+  uint8_t* d_out96 = sig && wire ? k.out(out, B * 96) : nullptr;
   uint8_t* d_plain = sig ? nullptr : k.out(out, (size_t)total, /*zero=*/true);  // failed jobs leave zeros
   // the N public key shares, made once per call: Commitment::evaluate(i + 1), src/lib.rs:570-573
   std::vector<uint64_t> h_slots(N);
@@ -1924,7 +1936,10 @@ static int robust_combine(tc_ctx* ctx, bool sig, const uint8_t* commit, size_t t
   uint8_t* d_combc = sig ? nullptr : k.temp<uint8_t>(B * 96);
   uint8_t* d_st1 = k.temp<uint8_t>(B, /*zero=*/true);
   uint8_t* d_ok1 = k.temp<uint8_t>(B);
-  uint8_t* d_member = ctx->input_checks ? k.temp<uint8_t>(B * need) : nullptr;
+  // what k_robust_finish requires of every selected share: membership (checked-input mode), or -- wire -- that it decoded
+  uint8_t* d_member = (wire || ctx->input_checks) ? k.temp<uint8_t>(B * need) : nullptr;
+  uint8_t* d_cmem = wire ? k.temp<uint8_t>(B) : nullptr;  // wire: the combination is on the curve and in the subgroup
+  uint8_t* d_hash_chk = wire && sig ? k.temp<uint8_t>(B * 192) : nullptr;
   uint8_t* d_verdict = k.temp<uint8_t>(B);
   uint8_t* d_hash_own = hashes ? nullptr : k.temp<uint8_t>(B * 192);
   const uint8_t* d_hash = hashes ? d_hash_in : d_hash_own;
@@ -1946,11 +1961,20 @@ static int robust_combine(tc_ctx* ctx, bool sig, const uint8_t* commit, size_t t
     if (ctx->input_checks) tc::launch_subgroup_check_g1(ctx->stream, d_commit, 96, need, need, need, d_cval);
     // pass 1: the first t+1 present shares, whatever they are
     tc::launch_select_shares(ctx->stream, d_present, nullptr, N, need, B, nullptr, d_idx, d_slot, d_used, d_enough);
-    tc::launch_gather_selected(ctx->stream, d_sh, N, need, PB, d_slot, d_enough, B, d_packed);
+    if (wire) tc::launch_decompress_selected(ctx->tuning, ctx->stream, sig, d_sh, N, need, d_slot, d_enough, B, d_packed, d_member);
+    else tc::launch_gather_selected(ctx->stream, d_sh, N, need, PB, d_slot, d_enough, B, d_packed);
     combine_launch(k, sig, t, need, d_idx, nullptr, d_packed, B, d_comb, d_st1);
     // membership of the selected shares goes into bytes of our own: a non-member share sends its job to pass 2 and ends as a
     // bad bit there, never as a failed job
-    if (d_member) {
+    if (wire) {
+      // ONE test per job, on the combination (decodes as a curve point, lies in the subgroup) instead of need per job.  A
+      // combination that fails becomes the identity -- and, for signatures, so does the job's hash point in the copy the group
+      // checks read: the job drops out of both sums of its group instead of sending the whole group to the per-job checks
+      if (sig) tc::launch_subgroup_check_g2(ctx->stream, d_comb, PB, 1, 1, B, d_cmem);
+      else tc::launch_subgroup_check_g1(ctx->stream, d_comb, PB, 1, 1, B, d_cmem);
+      tc::launch_invalidate_jobs(ctx->stream, d_member, need, 1, B, nullptr, nullptr, 0, d_cmem);  // (an undecodable share: pass 2 as well)
+      tc::launch_invalidate_jobs(ctx->stream, d_cmem, 1, 1, B, nullptr, d_comb, PB, nullptr);
+    } else if (d_member) {
       if (sig) tc::launch_subgroup_check_g2(ctx->stream, d_packed, PB, need, need, B * need, d_member);
       else tc::launch_subgroup_check_g1(ctx->stream, d_packed, PB, need, need, B * need, d_member);
     }
@@ -1965,7 +1989,13 @@ static int robust_combine(tc_ctx* ctx, bool sig, const uint8_t* commit, size_t t
         tc::launch_hash_g2(ctx->tuning, ctx->stream, d_msgs, d_off, B, d_hash_own, /*fix=*/false);
       }
       // the combinations under the ONE master key, by random linear combination: about one pairing check per `group` jobs
-      rlc_group_checks(k, ws, d_commit, d_comb, d_hash, d_g1, B, /*member_checks=*/false, /*hash_is_operand=*/false, d_ok1, nullptr);
+      const uint8_t* d_hash_rlc = d_hash;
+      if (wire) {
+        k.check(hipMemcpyAsync(d_hash_chk, d_hash, B * 192, hipMemcpyDeviceToDevice, ctx->stream), "hash copy");
+        tc::launch_invalidate_jobs(ctx->stream, d_cmem, 1, 1, B, nullptr, d_hash_chk, 192, nullptr);
+        d_hash_rlc = d_hash_chk;
+      }
+      rlc_group_checks(k, ws, d_commit, d_comb, d_hash_rlc, d_g1, B, /*member_checks=*/false, /*hash_is_operand=*/false, d_ok1, nullptr);
     } else {
       tc::launch_hash_g1_g2(ctx->tuning, ctx->stream, d_u, d_msgs, d_off, B, d_hash_own, d_jtmp, /*fix=*/false);
       tc::launch_ok_and_status(ctx->stream, d_jtmp, B, d_jvalid);
@@ -1980,6 +2010,7 @@ static int robust_combine(tc_ctx* ctx, bool sig, const uint8_t* commit, size_t t
       tc::launch_pairing_check(ctx->stream, d_combc, 96, d_hash, 192, d_commit, 0, d_w, 192, B, d_ok1, k.pairing_ws(B));
     }
     tc::launch_invalidate_jobs(ctx->stream, d_jvalid, 1, 1, B, nullptr, nullptr, 0, d_ok1);
+    if (wire) tc::launch_invalidate_jobs(ctx->stream, d_cmem, 1, 1, B, nullptr, nullptr, 0, d_ok1);
     tc::launch_robust_finish(ctx->stream, nullptr, N, need, PB, B, d_enough, d_st1, d_ok1, d_member, d_comb, d_res, d_status, d_used, d_verdict);
     k.check(hipMemcpyAsync(h_verdict.data(), d_verdict, B, hipMemcpyDeviceToHost, ctx->stream), "verdict readback");
     k.check(hipMemcpyAsync(h_pkst.data(), d_pkst, N, hipMemcpyDeviceToHost, ctx->stream), "status readback");
@@ -2019,6 +2050,8 @@ static int robust_combine(tc_ctx* ctx, bool sig, const uint8_t* commit, size_t t
       }
     uint32_t* d_maps = k.temp<uint32_t>(3 * R + F);
     uint8_t* c_sh = k.temp<uint8_t>(R * PB);
+    uint8_t* c_wire = wire ? k.temp<uint8_t>(R * SB) : nullptr;
+    uint8_t* c_dec = wire ? k.temp<uint8_t>(R) : nullptr;
     uint8_t* c_shc = sig ? nullptr : k.temp<uint8_t>(R * 96);
     uint8_t* c_hash = k.temp<uint8_t>(R * 192);
     uint8_t* c_w = sig ? nullptr : k.temp<uint8_t>(R * 192);
@@ -2040,7 +2073,15 @@ static int robust_combine(tc_ctx* ctx, bool sig, const uint8_t* commit, size_t t
       k.check(hipMemcpyAsync(d_maps + 2 * R, m_pk.data(), R * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
       k.check(hipMemcpyAsync(d_fmap, failed.data(), F * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
       ctx->h2d_bytes += 12 * R + 4 * F;
-      tc::launch_gather_rows(ctx->stream, d_sh, PB, d_maps, R, c_sh);
+      if (wire) {
+        // the full checked decode of from_bytes (curve AND subgroup); a failure leaves the identity -- decodable input for the
+        // pairing kernel -- and its verdict goes into c_ok below
+        tc::launch_gather_rows(ctx->stream, d_sh, SB, d_maps, R, c_wire);
+        if (sig) tc::launch_g2_decompress(ctx->tuning, ctx->stream, c_wire, R, c_sh, c_dec);
+        else tc::launch_g1_decompress(ctx->stream, c_wire, R, c_sh, c_dec);
+      } else {
+        tc::launch_gather_rows(ctx->stream, d_sh, PB, d_maps, R, c_sh);
+      }
       tc::launch_gather_rows(ctx->stream, d_hash, 192, d_maps + R, R, c_hash);
       tc::launch_gather_rows(ctx->stream, d_pks, 96, d_maps + 2 * R, R, c_pk);
       if (sig) {
@@ -2050,7 +2091,9 @@ static int robust_combine(tc_ctx* ctx, bool sig, const uint8_t* commit, size_t t
         tc::launch_g1_scale_cofactor_fix(ctx->stream, c_sh, 96, R, c_shc);
         tc::launch_pairing_check(ctx->stream, c_shc, 96, c_hash, 192, c_pk, 96, c_w, 192, R, c_ok, k.pairing_ws(R));
       }
-      if (ctx->input_checks) {  // members only (the key shares are sums of the commitment's points, tested above)
+      if (wire) {
+        tc::launch_ok_and_status(ctx->stream, c_dec, R, c_ok);  // (the checked decode has tested membership)
+      } else if (ctx->input_checks) {  // members only (the key shares are sums of the commitment's points, tested above)
         if (sig) tc::launch_subgroup_check_g2(ctx->stream, c_sh, 192, 1, 1, R, c_v);
         else tc::launch_subgroup_check_g1(ctx->stream, c_sh, 96, 1, 1, R, c_v);
         tc::launch_invalidate_jobs(ctx->stream, c_v, 1, 1, R, nullptr, nullptr, 0, c_ok);
@@ -2069,6 +2112,8 @@ static int robust_combine(tc_ctx* ctx, bool sig, const uint8_t* commit, size_t t
   }
   // the plaintext of a job that ended OK: xor_with_hash(g, v), src/lib.rs:625
   if (!k.failed && !sig) tc::launch_xor_with_hash(ctx->stream, d_res, d_msgs, d_off, B, d_plain, d_status);
+  // Signature::to_bytes of the results (the identity of a job that did not end OK: 0xC0, then zeros)
+  if (!k.failed && d_out96) tc::launch_g2_compress(ctx->stream, d_res, B, d_out96, nullptr);
   k.end_timing();
   return k.finish();
 }
@@ -2077,7 +2122,7 @@ int tc_combine_signatures_robust_batch(tc_ctx* ctx, const uint8_t* commit, size_
                                        const uint8_t* sig_shares, const uint8_t* hashes, const uint8_t* msgs, const uint64_t* off, size_t B,
                                        size_t group, const uint8_t* seed32, uint8_t* out_sig, uint8_t* used, uint8_t* bad, uint8_t* status,
                                        uint64_t* n_fallback) try {
-  return robust_combine(ctx, true, commit, t, N, present, sig_shares, hashes, msgs, off, nullptr, nullptr, B, group, seed32, out_sig, false, used, bad,
+  return robust_combine(ctx, true, false, commit, t, N, present, sig_shares, hashes, msgs, off, nullptr, nullptr, B, group, seed32, out_sig, false, used, bad,
                         status, n_fallback);
 } catch (...) {
   return on_exception((tc_ctx*)ctx);
@@ -2091,8 +2136,32 @@ int tc_decrypt_robust_batch(tc_ctx* ctx, const uint8_t* commit, size_t t, size_t
   if (B == 0) return TC_OK;  // (an empty batch is a no-op for every entry: a device-resident empty buffer has no address)
   const bool unbacked = out_plain == nullptr;
   if (unbacked) out_plain = &g_no_plaintext_bytes;
-  return robust_combine(ctx, false, commit, t, N, present, shares_g1, nullptr, v, off, u_g1, w_g2, B, 0, nullptr, out_plain, unbacked, used, bad, status,
-                        n_fallback);
+  return robust_combine(ctx, false, false, commit, t, N, present, shares_g1, nullptr, v, off, u_g1, w_g2, B, 0, nullptr, out_plain, unbacked, used, bad,
+                        status, n_fallback);
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+int tc_combine_signatures_robust_wire_batch(tc_ctx* ctx, const uint8_t* commit, size_t t, size_t N, const uint8_t* present,
+                                            const uint8_t* sig_shares96, const uint8_t* hashes, const uint8_t* msgs, const uint64_t* off, size_t B,
+                                            size_t group, const uint8_t* seed32, uint8_t* out_sig96, uint8_t* used, uint8_t* bad, uint8_t* status,
+                                            uint64_t* n_fallback) try {
+  return robust_combine(ctx, true, true, commit, t, N, present, sig_shares96, hashes, msgs, off, nullptr, nullptr, B, group, seed32, out_sig96, false,
+                        used, bad, status, n_fallback);
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+int tc_decrypt_robust_wire_batch(tc_ctx* ctx, const uint8_t* commit, size_t t, size_t N, const uint8_t* present, const uint8_t* shares48,
+                                 const uint8_t* u_g1, const uint8_t* v, const uint64_t* off, const uint8_t* w_g2, size_t B, uint8_t* out_plain,
+                                 uint8_t* used, uint8_t* bad, uint8_t* status, uint64_t* n_fallback) try {
+  TC_REQUIRE(ctx);
+  if (n_fallback) *n_fallback = 0;
+  if (B == 0) return TC_OK;
+  const bool unbacked = out_plain == nullptr;
+  if (unbacked) out_plain = &g_no_plaintext_bytes;
+  return robust_combine(ctx, false, true, commit, t, N, present, shares48, nullptr, v, off, u_g1, w_g2, B, 0, nullptr, out_plain, unbacked, used, bad,
+                        status, n_fallback);
 } catch (...) {
   return on_exception((tc_ctx*)ctx);
 }

@@ -6,6 +6,7 @@
 #include "tc_gls.h"
 #include "tc_hash.h"
 #include "tc_pairing.h"
+#include "tc_robust.h"
 #include "tc_threshold.h"
 
 namespace tc {
@@ -927,6 +928,62 @@ TC_HD void job_decompress_g2_x2(const uint8_t* in_a, const uint8_t* in_b, uint8_
   if (out_b) g2_encode_uncompressed(pb, out_b);
   st_a = oka ? TC_JOB_OK : TC_JOB_INVALID_ENCODING;
   st_b = okb ? TC_JOB_OK : TC_JOB_INVALID_ENCODING;
+}
+
+// ---- the selected decode of the wire-level robust combiners (k_mul.hip k_decompress_selected) -------------------------------
+// compressed -> uncompressed through the CURVE-LEVEL decode (tc_sqrt.h, MEMBER = false): flags, range, square root and sign,
+// no subgroup ladder.  A failure writes the identity.
+template <class F>
+TC_HD uint8_t job_decompress_curve(const uint8_t* in, uint8_t* out);
+template <>
+TC_HD uint8_t job_decompress_curve<Fq>(const uint8_t* in, uint8_t* out) {
+  G1Affine p;
+  bool ok = g1_decode_compressed<false>(in, p);
+  if (!ok) p = G1Affine::infinity();
+  g1_encode_uncompressed(p, out);
+  return ok ? TC_JOB_OK : TC_JOB_INVALID_ENCODING;
+}
+template <>
+TC_HD uint8_t job_decompress_curve<Fq2>(const uint8_t* in, uint8_t* out) {
+  G2Affine p;
+  bool ok = g2_decode_compressed<false>(in, p);
+  if (!ok) p = G2Affine::infinity();
+  g2_encode_uncompressed(p, out);
+  return ok ? TC_JOB_OK : TC_JOB_INVALID_ENCODING;
+}
+// Record i of the selected decode: the share at selected_source (tc_robust.h) of `in`, to out (this record's bytes).  A record
+// without a source -- its job lacks enough shares -- reads nothing and is the identity with ok = 1, what k_gather_selected
+// gives such a job.  Returns ok.
+template <class F>
+TC_HD bool job_decompress_selected(const uint8_t* in, size_t N, size_t need, const uint32_t* slot, const uint8_t* enough, size_t i, uint8_t* out) {
+  const size_t src = selected_source(i, N, need, slot, enough, PointIO<F>::CBYTES);
+  if (src == kNoSource) {
+    PointIO<F>::encode(Affine<F>::infinity(), out);
+    return true;
+  }
+  return job_decompress_curve<F>(in + src, out) == TC_JOB_OK;
+}
+// Records ia and ib (ib == ia: an odd record count, the second slot repeats the first and out_b is null) on one lane pair.  The
+// two may belong to different jobs; a record without a source borrows the other's bytes for the shared arithmetic and is
+// replaced by the identity before anything is written; two without a source decode nothing.
+TC_HD void job_decompress_selected_g2_x2(const uint8_t* in, size_t N, size_t need, const uint32_t* slot, const uint8_t* enough, size_t ia, size_t ib,
+                                         uint8_t* out_a, uint8_t* out_b, bool& oka, bool& okb) {
+  const size_t sa = selected_source(ia, N, need, slot, enough, 96), sb = selected_source(ib, N, need, slot, enough, 96);
+  G2Affine pa = G2Affine::infinity(), pb = G2Affine::infinity();
+  oka = okb = true;
+  if (sa != kNoSource || sb != kNoSource) {
+    g2_decode_compressed_x2<false>(in + (sa != kNoSource ? sa : sb), in + (sb != kNoSource ? sb : sa), pa, pb, oka, okb);
+    if (sa == kNoSource) {
+      pa = G2Affine::infinity();
+      oka = true;
+    }
+    if (sb == kNoSource) {
+      pb = G2Affine::infinity();
+      okb = true;
+    }
+  }
+  g2_encode_uncompressed(pa, out_a);
+  if (out_b) g2_encode_uncompressed(pb, out_b);
 }
 
 }  // namespace tc

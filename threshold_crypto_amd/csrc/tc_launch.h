@@ -280,6 +280,10 @@ void launch_select_shares(hipStream_t st, const uint8_t* present, const uint8_t*
                           uint64_t* idx, uint32_t* slot, uint8_t* used, uint8_t* enough);
 void launch_gather_selected(hipStream_t st, const uint8_t* shares, size_t N, size_t need, size_t point_bytes, const uint32_t* slot,
                             const uint8_t* enough, size_t jobs, uint8_t* dst);
+// the wire forms' replacement of launch_gather_selected (k_mul.hip): shares = jobs x N COMPRESSED encodings (96 / 48 bytes); dst as
+// above through the curve-level decode -- no membership test --, ok (jobs x need bytes) = 1 where the record decoded
+void launch_decompress_selected(const Tuning& tn, hipStream_t st, bool g2, const uint8_t* shares, size_t N, size_t need, const uint32_t* slot,
+                                const uint8_t* enough, size_t jobs, uint8_t* dst, uint8_t* ok);
 void launch_gather_bytes(hipStream_t st, const uint8_t* src, const uint32_t* map, size_t rows, uint8_t* dst);
 void launch_robust_mark(hipStream_t st, const uint8_t* present, const uint32_t* rec, const uint8_t* ok, size_t rows, uint8_t* c_present,
                         uint8_t* c_bad, uint8_t* bad);

@@ -57,6 +57,17 @@ TC_HD size_t select_first(const uint8_t* present_row, const uint8_t* bad_row, si
   return count;
 }
 
+// Where record i = j * need + k of the selected decode (k_decompress_selected, the wire forms of the robust combiners) finds
+// its compressed share in the caller's jobs x N array of `cbytes`-byte encodings: the byte offset (j * N + slot[i]) * cbytes.
+// A job without enough shares has no source -- its slots are 0xffffffff (k_select_shares) and are NOT read, no offset is
+// formed from them: kNoSource, and the record is the identity.
+constexpr size_t kNoSource = ~(size_t)0;
+TC_HD size_t selected_source(size_t i, size_t N, size_t need, const uint32_t* slot, const uint8_t* enough, size_t cbytes) {
+  const size_t j = i / need;
+  if (!enough[j]) return kNoSource;
+  return (j * N + (size_t)slot[i]) * cbytes;
+}
+
 // verdict of k_robust_finish for one job of a pass
 enum RobustVerdict : uint8_t {
   kRobustNotEnough = 0,  // fewer than t+1 eligible shares

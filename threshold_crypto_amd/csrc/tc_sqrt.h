@@ -167,6 +167,10 @@ TC_HD bool g2_in_subgroup(const G2Affine& p) {
 }
 
 // ---- checked decode of the compressed forms (EncodedPoint::into_affine) ------------------------
+// MEMBER = false is the CURVE-LEVEL form: flags, range, square root and sign as above, no subgroup ladder -- for callers that
+// settle membership on what they compute from the points (the wire forms of the robust combiners test the combination,
+// DESIGN.md 4.16).  The checked form is the default and compiles to the code it always was.
+template <bool MEMBER = true>
 TC_HD bool g1_decode_compressed(const uint8_t* b, G1Affine& p) {
   const uint8_t f = b[0];
   if (!(f & 0x80)) return false;
@@ -182,9 +186,11 @@ TC_HD bool g1_decode_compressed(const uint8_t* b, G1Affine& p) {
   const bool greatest = (f & 0x20) != 0;
   if (fq_lex_largest(y) != greatest) y = -y;
   p = G1Affine{x, y, false};
-  return g1_in_subgroup(p);
+  if constexpr (MEMBER) return g1_in_subgroup(p);
+  return true;
 }
 
+template <bool MEMBER = true>
 TC_HD bool g2_decode_compressed(const uint8_t* b, G2Affine& p) {
   const uint8_t f = b[0];
   if (!(f & 0x80)) return false;
@@ -200,7 +206,8 @@ TC_HD bool g2_decode_compressed(const uint8_t* b, G2Affine& p) {
   const bool greatest = (f & 0x20) != 0;
   if (fq2_lex_largest(y) != greatest) y = -y;
   p = G2Affine{x, y, false};
-  return g2_in_subgroup(p);
+  if constexpr (MEMBER) return g2_in_subgroup(p);
+  return true;
 }
 
 // ---- two jobs per lane pair (tc_duo.h) ----------------------------------------------------------
@@ -282,6 +289,7 @@ TC_HD int g2_parse_compressed(const uint8_t* b, Fq2& x, bool& greatest) {
   if (f & 0x40) return o == 0 ? 1 : 0;
   return in_range ? 2 : 0;
 }
+template <bool MEMBER = true>
 TC_HD void g2_decode_compressed_x2(const uint8_t* ba, const uint8_t* bb, G2Affine& pa, G2Affine& pb, bool& oka, bool& okb) {
   Fq2 xa, xb;
   bool ga, gb;
@@ -296,8 +304,11 @@ TC_HD void g2_decode_compressed_x2(const uint8_t* ba, const uint8_t* bb, G2Affin
   if (fq2_lex_largest(yb) != gb) yb = -yb;
   pa = G2Affine{xa, ya, false};
   pb = G2Affine{xb, yb, false};
-  const bool ina = g2_in_subgroup_call(pa);
-  const bool inb = g2_in_subgroup_call(pb);
+  bool ina = true, inb = true;  // (MEMBER = false: the curve-level form, as above)
+  if constexpr (MEMBER) {
+    ina = g2_in_subgroup_call(pa);
+    inb = g2_in_subgroup_call(pb);
+  }
   oka = ka == 2 ? (sqa && ina) : ka == 1;
   okb = kb == 2 ? (sqb && inb) : kb == 1;
   if (ka != 2 || !oka) pa = G2Affine::infinity();

@@ -533,7 +533,7 @@ class Engine:
         return ok, int(nfb.value)
 
     # -- robust combination: validate, select and combine in one call -----------------------------------
-    def combine_signatures_robust(self, commit, sig_shares, hashes=None, msgs=None, off=None, present=None, group=0, seed=None):
+    def combine_signatures_robust(self, commit, sig_shares, hashes=None, msgs=None, off=None, present=None, group=0, seed=None, _wire=False):
         """tc_combine_signatures_robust_batch (see tc_amd.h): commit (t+1, 96), sig_shares (B, N, 192) with slot i = node i's
         share, either hashes (B, 192) or msgs / off, present (B, N) u8 or None = all.  The first t+1 present shares of every
         message are combined and the combinations verified under the master key; only the messages whose combination does not
@@ -545,7 +545,8 @@ class Engine:
         dev = self._mode(commit, sig_shares, hashes, msgs, off, present)
         self._arg(commit, (None, G1_BYTES), "u8", "commit")
         t = commit.shape[0] - 1
-        self._arg(sig_shares, (None, None, G2_BYTES), "u8", "sig_shares")
+        width = G2_BYTES // 2 if _wire else G2_BYTES
+        self._arg(sig_shares, (None, None, width), "u8", "sig_shares")
         B, N = sig_shares.shape[0], sig_shares.shape[1]
         if t < 0 or t + 1 > N:
             raise ValueError("commit holds t+1 = %d coefficients for N = %d shares per message" % (t + 1, N))
@@ -558,17 +559,30 @@ class Engine:
         seed = bytes(seed) if seed is not None else os.urandom(32)
         if len(seed) != 32:
             raise ValueError("seed: 32 bytes")
-        out = self._empty(dev, (B, G2_BYTES), ref=sig_shares)
+        out = self._empty(dev, (B, width), ref=sig_shares)
         used = self._empty(dev, (B, N), ref=sig_shares)
         bad = self._empty(dev, (B, N), ref=sig_shares)
         st = self._empty(dev, (B,), ref=sig_shares)
         nfb = ctypes.c_uint64(0)
-        self._call("tc_combine_signatures_robust_batch", _ptr(commit), t, N, _ptr(present), _ptr(sig_shares), _ptr(hashes),
+        self._call("tc_combine_signatures_robust_wire_batch" if _wire else "tc_combine_signatures_robust_batch", _ptr(commit), t, N, _ptr(present), _ptr(sig_shares), _ptr(hashes),
                    _ptr(msgs) if off is not None else None, _ptr(off), B, int(group), seed, _ptr(out), _ptr(used), _ptr(bad), _ptr(st),
                    ctypes.byref(nfb))
         return out, used, bad, st, int(nfb.value)
 
-    def decrypt_robust(self, commit, shares, u, v, off, w, present=None):
+    def combine_signatures_robust_wire(self, commit, sig_shares96, hashes=None, msgs=None, off=None, present=None, group=0, seed=None):
+        """tc_combine_signatures_robust_wire_batch (see tc_amd.h): combine_signatures_robust on wire bytes -- sig_shares96 (B, N, 96)
+        holds SignatureShare::to_bytes forms, always through the checked decode -- of which only the t+1 selected shares of a
+        message are decoded; membership is tested on the combination.  Returns (sig (B, 96) = Signature::to_bytes, the identity's
+        0xC0 form for a message that did not end OK, used, bad, status, number of messages examined share by share)."""
+        return self.combine_signatures_robust(commit, sig_shares96, hashes=hashes, msgs=msgs, off=off, present=present, group=group, seed=seed,
+                                              _wire=True)
+
+    def decrypt_robust_wire(self, commit, shares48, u, v, off, w, present=None):
+        """tc_decrypt_robust_wire_batch (see tc_amd.h): decrypt_robust on wire bytes, shares48 (B, N, 48) compressed decryption
+        shares; everything else, and the result, as decrypt_robust."""
+        return self.decrypt_robust(commit, shares48, u, v, off, w, present=present, _wire=True)
+
+    def decrypt_robust(self, commit, shares, u, v, off, w, present=None, _wire=False):
         """tc_decrypt_robust_batch (see tc_amd.h): commit (t+1, 96), shares (B, N, 96) with slot i = node i's decryption share
         of ciphertext (u, v, w)[j], present (B, N) u8 or None = all.  Returns (plaintext bytes laid out like v -- zeros for a
         ciphertext that did not end OK --, used (B, N), bad (B, N), status (B,), number of ciphertexts examined share by
@@ -576,7 +590,7 @@ class Engine:
         dev = self._mode(commit, shares, u, v, off, w, present)
         self._arg(commit, (None, G1_BYTES), "u8", "commit")
         t = commit.shape[0] - 1
-        self._arg(shares, (None, None, G1_BYTES), "u8", "shares")
+        self._arg(shares, (None, None, G1_BYTES // 2 if _wire else G1_BYTES), "u8", "shares")
         B, N = shares.shape[0], shares.shape[1]
         if t < 0 or t + 1 > N:
             raise ValueError("commit holds t+1 = %d coefficients for N = %d shares per ciphertext" % (t + 1, N))
@@ -590,7 +604,7 @@ class Engine:
         bad = self._empty(dev, (B, N), ref=shares)
         st = self._empty(dev, (B,), ref=shares)
         nfb = ctypes.c_uint64(0)
-        self._call("tc_decrypt_robust_batch", _ptr(commit), t, N, _ptr(present), _ptr(shares), _ptr(u), _ptr(v), _ptr(off), _ptr(w), B,
+        self._call("tc_decrypt_robust_wire_batch" if _wire else "tc_decrypt_robust_batch", _ptr(commit), t, N, _ptr(present), _ptr(shares), _ptr(u), _ptr(v), _ptr(off), _ptr(w), B,
                    _ptr(out), _ptr(used), _ptr(bad), _ptr(st), ctypes.byref(nfb))
         return out, used, bad, st, int(nfb.value)
 
