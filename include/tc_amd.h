@@ -370,6 +370,31 @@ int tc_combine_signatures_robust_wire_batch(tc_ctx* ctx, const uint8_t* commit, 
 int tc_decrypt_robust_wire_batch(tc_ctx* ctx, const uint8_t* commit, size_t t, size_t N, const uint8_t* present, const uint8_t* shares48,
                                  const uint8_t* u_g1, const uint8_t* v, const uint64_t* off, const uint8_t* w_g2, size_t B, uint8_t* out_plain,
                                  uint8_t* used, uint8_t* bad, uint8_t* status, uint64_t* n_fallback);
+/* BLAME BY BISECTION: an opt-in form of step 3 for all four entries, off by default.  Step 3 as written costs a job N pairing
+ * checks however few of its shares are bad, so one forged share per message sets the cost of its honest receivers.  With the
+ * mode on, every examined share and its public key share are multiplied ONCE by a secret random 63-bit scalar r_i, RANGES of
+ * slots are tested with one pairing check each -- e(sum r_i pk_i, H) == e(g1, sum r_i sig_i), for decryption
+ * e(sum r_i share_i, H) == e(sum r_i pk_i, w) -- and only the ranges that fail are halved.  A job with k bad shares among N
+ * then costs at most min(1 + 2 k d, 2 N - 1) checks in at most 2 d + 1 rounds, d = ceil(log2 N) (17 instead of 200 checks at
+ * N = 200, k = 1); the rule is fixed in csrc/tc_blame.h.  The contract:
+ *   With the mode on, `out`, `used`, `bad`, `status` and *n_fallback are what the share-by-share step 3 produces, up to
+ *     2^-63 per range check (as for the random linear combinations of step 2).  A range that wrongly passes can leave a bad
+ *     share unmarked and, because the right half of a failing range whose left half passes is taken to be failing WITHOUT a
+ *     check of its own, mark an honest one.
+ *   Rules 1 and 2 and the clean-job path are untouched.
+ *   Only WHICH pairing checks step 3 runs changes: the checked decode of the wire entries, the per-share membership tests of
+ *     checked-input mode, the re-selection and the second combination stay as they are.  A present share that does not decode,
+ *     is no group member (where that is tested) or belongs to a job whose own operands are invalid is bad without any check.
+ * tc_ctx_set_blame_bisect: key32 == NULL = one pairing check per present share (default); key32 != NULL = blame by bisection.
+ * key32: 32 secret random bytes in HOST memory, copied into the context, wiped on destroy / when switched off.  Each robust
+ * call derives its own scalars from (key32, a per-context call counter) with ChaCha20 -- never from the caller's seed32, which
+ * stays step 2's -- so no scalar is shared between two calls or between the steps: the key must stay secret for the context's
+ * lifetime (whoever knows it can forge shares whose errors cancel in a range). */
+int tc_ctx_set_blame_bisect(tc_ctx* ctx, const uint8_t* key32);
+int tc_ctx_get_blame_bisect(const tc_ctx* ctx); /* 0 / 1; NULL ctx -> 0 */
+/* Step 3 of the LAST robust call on this context: pairing checks spent, rounds (host syncs) taken.  Share-by-share mode
+ * reports F * N and 1 for F jobs that reached step 3 (0 and 0 when none did).  Either pointer may be NULL. */
+int tc_ctx_last_blame_stats(const tc_ctx* ctx, uint64_t* pairing_checks, uint64_t* rounds);
 
 /* ---- DKG algebra (src/poly.rs)----------------------------------------------------------------- */
 /* out[i] = coeff_fr[i] * g1: Poly::commitment src/poly.rs:372-377 and BivarPoly::commitment :625-632 (every

@@ -733,6 +733,23 @@ inline bool is_member(const G2Bytes& p, Engine& e = Engine::instance()) {
   return ok != 0;
 }
 inline void set_input_checks(bool on, Engine& e = Engine::instance()) { e.check(tc_ctx_set_input_checks(e.ctx(), on ? 1 : 0)); }
+// How the robust combiners (PublicKeySet::*_robust*_batch) find the bad shares of a message whose first combination did not
+// verify (tc_ctx_set_blame_bisect): nullptr = one pairing check per received share (the default); a key of 32 secret random
+// bytes = blame by bisection -- the same results (up to 2^-63 per check), at most min(1 + 2 k d, 2 N - 1) pairing checks for k
+// bad shares among N, d = ceil(log2 N).  The key must stay secret for the engine's lifetime.
+inline void set_blame_bisect(const std::array<std::uint8_t, 32>* key, Engine& e = Engine::instance()) {
+  e.check(tc_ctx_set_blame_bisect(e.ctx(), key ? key->data() : nullptr));
+}
+inline bool blame_bisect(Engine& e = Engine::instance()) { return tc_ctx_get_blame_bisect(e.ctx()) != 0; }
+// what the share examination of the last robust call spent: pairing checks, rounds (host syncs)
+struct BlameStats {
+  std::uint64_t pairing_checks = 0, rounds = 0;
+};
+inline BlameStats last_blame_stats(Engine& e = Engine::instance()) {
+  BlameStats s;
+  e.check(tc_ctx_last_blame_stats(e.ctx(), &s.pairing_checks, &s.rounds));
+  return s;
+}
 
 // The share-validation loop of examples/threshold_sig.rs:115-131 -- ok[j][i] = pk_shares[i].verify(shares[j][i], msgs[j])
 // (src/lib.rs:177-179) -- through one random linear combination per message (tc_verify_shares_rlc_batch; per-share checks

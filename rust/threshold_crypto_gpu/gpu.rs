@@ -95,6 +95,26 @@ impl Gpu {
     pub fn trusted_operands(&self, trusted: bool) {
         unsafe { tc_ctx_set_input_checks(self.0, if trusted { 0 } else { 1 }) };
     }
+    /// How the robust combiners find the bad shares of a message whose first combination did not verify: `None` = one pairing
+    /// check per received share (the default); `Some(key)`, 32 secret random bytes = blame by bisection -- the same results (up
+    /// to 2^-63 per check), at most min(1 + 2 k d, 2 N - 1) pairing checks for k bad shares among N, d = ceil(log2 N).  The key
+    /// must stay secret for the context's lifetime; every call derives scalars of its own from it.
+    pub fn set_blame_bisect(&self, key: Option<&[u8; 32]>) -> GpuResult<()> {
+        let p = match key {
+            Some(k) => k.as_ptr(),
+            None => std::ptr::null(),
+        };
+        self.check(unsafe { tc_ctx_set_blame_bisect(self.0, p) })
+    }
+    pub fn blame_bisect(&self) -> GpuResult<bool> {
+        Ok(unsafe { tc_ctx_get_blame_bisect(self.0) } != 0)
+    }
+    /// (pairing checks, rounds) the share examination of the last robust call on this context spent
+    pub fn last_blame_stats(&self) -> GpuResult<(u64, u64)> {
+        let (mut checks, mut rounds) = (0u64, 0u64);
+        self.check(unsafe { tc_ctx_last_blame_stats(self.0, &mut checks, &mut rounds) })?;
+        Ok((checks, rounds))
+    }
     /// call-level return code -> `Err(GpuError)` with the library's message; never a panic
     fn check(&self, rc: c_int) -> GpuResult<()> {
         if rc == TC_OK {

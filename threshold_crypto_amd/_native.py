@@ -90,7 +90,8 @@ PROTOTYPES = {
 
 CONTEXT_SYMBOLS = ["tc_ctx_create", "tc_ctx_destroy", "tc_ctx_set_device_io", "tc_ctx_set_stream", "tc_sync",
                    "tc_last_error", "tc_ctx_set_timing", "tc_last_kernel_ms", "tc_version", "tc_ctx_set_input_checks",
-                   "tc_ctx_get_input_checks", "tc_ctx_transfer_bytes", "tc_ctx_trim", "tc_ctx_get_device_io", "tc_ctx_get_tuning"]
+                   "tc_ctx_get_input_checks", "tc_ctx_transfer_bytes", "tc_ctx_trim", "tc_ctx_get_device_io", "tc_ctx_get_tuning",
+                   "tc_ctx_set_blame_bisect", "tc_ctx_get_blame_bisect", "tc_ctx_last_blame_stats"]
 
 # the multi-GPU surface (tc_group_*): name -> (restype, argtypes); the group handle is an opaque pointer
 _grp = ctypes.c_void_p
@@ -160,6 +161,12 @@ def load():
     lib.tc_ctx_get_tuning.restype = ctypes.c_int
     lib.tc_ctx_transfer_bytes.argtypes = [_ctx, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     lib.tc_ctx_transfer_bytes.restype = ctypes.c_int
+    lib.tc_ctx_set_blame_bisect.argtypes = [_ctx, ctypes.c_char_p]
+    lib.tc_ctx_set_blame_bisect.restype = ctypes.c_int
+    lib.tc_ctx_get_blame_bisect.argtypes = [_ctx]
+    lib.tc_ctx_get_blame_bisect.restype = ctypes.c_int
+    lib.tc_ctx_last_blame_stats.argtypes = [_ctx, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+    lib.tc_ctx_last_blame_stats.restype = ctypes.c_int
     lib.tc_last_kernel_ms.argtypes = [_ctx]
     lib.tc_last_kernel_ms.restype = ctypes.c_double
     lib.tc_sync.argtypes = [_ctx]

@@ -60,6 +60,22 @@ def set_default_engine(engine):
     _default_engine = engine
 
 
+def set_blame_bisect(key=None, engine=None):
+    """How the robust combiners (PublicKeySet.*_robust_batch) find the bad shares of a message whose first combination did not
+    verify: None = one pairing check per received share (the default); 32 secret random bytes = blame by bisection
+    (Engine.set_blame_bisect) -- the same results, at most min(1 + 2 k d, 2 N - 1) pairing checks for k bad shares among N."""
+    (engine or default_engine()).set_blame_bisect(key)
+
+
+def blame_bisect(engine=None):
+    return (engine or default_engine()).blame_bisect()
+
+
+def last_blame_stats(engine=None):
+    """(pairing checks, rounds) the share examination of the last robust call spent (Engine.last_blame_stats)"""
+    return (engine or default_engine()).last_blame_stats()
+
+
 def _u8(b):
     return np.frombuffer(bytes(b), dtype=np.uint8).copy()
 

@@ -3,6 +3,7 @@
 // tc_launch.h).  There is no CPU compute path: without a HIP device tc_ctx_create fails.
 #include "tc_launch.h"
 #include "tc_robust.h"
+#include "tc_blame.h"
 #include "../../include/tc_amd.h"
 
 #include <stdio.h>
@@ -54,6 +55,12 @@ struct tc_ctx {
   int cus = 0;
   tc::Tuning tuning;  // form choices, fixed when the context is created (tc_launch.h)
   uint64_t h2d_bytes = 0, d2h_bytes = 0;  // bytes this context's staging copies moved over PCIe (tc_ctx_transfer_bytes)
+  // pass 2 of the robust combiners by bisection (tc_ctx_set_blame_bisect; tc_blame.h): the secret key the pass-2 scalars of
+  // every call derive from, the number of the next call under it, and what pass 2 of the last robust call spent
+  bool blame_bisect = false;
+  uint8_t blame_key[32] = {};
+  uint64_t blame_calls = 0;
+  uint64_t blame_checks = 0, blame_rounds = 0;
 };
 
 namespace {
@@ -445,6 +452,12 @@ tc::Tuning tuning_from_env() {
 }  // namespace
 
 // "never throws across the boundary" (include/tc_amd.h): every entry point below is a function-try-block that ends here.
+// zeroes secret host bytes in a way the optimiser may not drop
+static void wipe_host(uint8_t* p, size_t n) {
+  volatile uint8_t* v = p;
+  for (size_t i = 0; i < n; i++) v[i] = 0;
+}
+
 // The host code allocates (std::vector, std::string); under memory pressure that throws, and an exception that crossed the C ABI
 // into Rust or ctypes would be undefined behaviour.  The context stays usable: the arena flags are reset before the next use.
 static int on_exception(tc_ctx* ctx) noexcept {
@@ -528,6 +541,7 @@ void tc_ctx_destroy(tc_ctx* c) try {
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+  wipe_host(c->blame_key, 32);
   delete c;
 } catch (...) {
 }
@@ -551,6 +565,28 @@ int tc_ctx_set_stream(tc_ctx* ctx, void* hip_stream) try {
 int tc_ctx_set_input_checks(tc_ctx* ctx, int enabled) try {
   if (!ctx) return TC_ERR_INVALID_ARG;
   ctx->input_checks = enabled != 0;
+  return TC_OK;
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+int tc_ctx_set_blame_bisect(tc_ctx* ctx, const uint8_t* key32) try {
+  if (!ctx) return TC_ERR_INVALID_ARG;
+  wipe_host(ctx->blame_key, 32);
+  ctx->blame_bisect = key32 != nullptr;
+  // (the call counter is the context's and never goes back: setting the same key again cannot repeat a scalar)
+  if (key32) memcpy(ctx->blame_key, key32, 32);
+  return TC_OK;
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+int tc_ctx_get_blame_bisect(const tc_ctx* ctx) { return (ctx && ctx->blame_bisect) ? 1 : 0; }
+
+int tc_ctx_last_blame_stats(const tc_ctx* ctx, uint64_t* pairing_checks, uint64_t* rounds) try {
+  if (!ctx) return TC_ERR_INVALID_ARG;
+  if (pairing_checks) *pairing_checks = ctx->blame_checks;
+  if (rounds) *rounds = ctx->blame_rounds;
   return TC_OK;
 } catch (...) {
   return on_exception((tc_ctx*)ctx);
@@ -1860,6 +1896,127 @@ int tc_verify_decryption_shares_rlc_batch(tc_ctx* ctx, const uint8_t* pk_shares,
   return on_exception((tc_ctx*)ctx);
 }
 
+// Pass 2 of robust_combine by bisection (tc_ctx_set_blame_bisect; rule, bounds and the 2^-63 argument: tc_blame.h, DESIGN.md
+// 4.17): h_ok[f * N + i] = 0 exactly for the present shares of the failed jobs that per-share mode would answer ok = 0 for,
+// found with range checks over leaves [r] share / [r] pk_share (k_blame.hip).  c_sh: the failed jobs' shares, uncompressed
+// (F x N); c_dec: the status bytes of their checked decode (wire) or null; d_maps: the record / job maps of pass 2.  The host
+// drives the rounds -- one batched pairing-check launch and one readback of verdict bytes each -- and builds the worklists
+// (tc::BlameSearch, one per job).  The leaves of F x N slots take F N (576 B signatures / 384 B decryption): failed jobs
+// go through in chunks under the budget the two-stage tables have (msm_table_budget; TC_MSM_BUDGET).  The engine knows
+// nothing of the entry: the RLC fallbacks could drive it the same way.
+static void blame_pass(Call& k, bool sig, bool wire, size_t N, const std::vector<uint32_t>& failed, const uint32_t* d_maps, const uint8_t* c_sh,
+                       const uint8_t* c_dec, const uint8_t* d_present, const uint8_t* d_jvalid, const uint8_t* d_pks, const uint8_t* d_hash,
+                       const uint8_t* d_w, const uint8_t* d_g1, std::vector<uint8_t>& h_ok) {
+  tc_ctx* ctx = k.c;
+  const size_t F = failed.size(), R = F * N, PB = sig ? 192 : 96;
+  h_ok.assign(R, 1);
+  uint8_t* c_pres = k.temp<uint8_t>(R);
+  uint8_t* c_live = k.temp<uint8_t>(R);
+  uint8_t* c_v = k.temp<uint8_t>(R);
+  uint8_t* d_key = k.temp<uint8_t>(32);
+  uint8_t* d_seed = k.temp<uint8_t>(32);
+  if (d_key) k.wipe.emplace_back(d_key, 32);
+  if (d_seed) k.wipe.emplace_back(d_seed, 32);
+  const size_t leaf_s = tc::blame_leaf_bytes(sig), leaf_pk = tc::blame_leaf_bytes(false);
+  size_t Fc = msm_table_budget(k) / (N * (leaf_s + leaf_pk));
+  if (Fc < 1) Fc = 1;
+  if (Fc > F) Fc = F;
+  int32_t* d_leaf_s = k.temp<int32_t>(Fc * N * leaf_s / sizeof(int32_t));
+  int32_t* d_leaf_pk = k.temp<int32_t>(Fc * N * leaf_pk / sizeof(int32_t));
+  int32_t* d_sink = k.temp<int32_t>(tc::blame_sink_bytes() / sizeof(int32_t));
+  const tc::TableArena ta = k.tables();
+  if (k.failed) return;
+  // live = present, decoded, a group member where that is tested, and the job's own operands valid
+  if (d_present) tc::launch_gather_bytes(ctx->stream, d_present, d_maps, R, c_pres);
+  else k.check(hipMemsetAsync(c_pres, 1, R, ctx->stream), "memset");
+  k.check(hipMemcpyAsync(c_live, c_pres, R, hipMemcpyDeviceToDevice, ctx->stream), "live copy");
+  if (wire) {
+    tc::launch_ok_and_status(ctx->stream, c_dec, R, c_live);  // (the checked decode has tested membership)
+  } else if (ctx->input_checks) {
+    if (sig) tc::launch_subgroup_check_g2(ctx->stream, c_sh, 192, 1, 1, R, c_v);
+    else tc::launch_subgroup_check_g1(ctx->stream, c_sh, 96, 1, 1, R, c_v);
+    tc::launch_invalidate_jobs(ctx->stream, c_v, 1, 1, R, nullptr, nullptr, 0, c_live);
+  }
+  tc::launch_gather_bytes(ctx->stream, d_jvalid, d_maps + R, R, c_v);
+  tc::launch_invalidate_jobs(ctx->stream, c_v, 1, 1, R, nullptr, nullptr, 0, c_live);
+  // this call's scalars: ChaCha20 under a seed of its own, derived from the context's key and call counter
+  k.check(hipMemcpyAsync(d_key, ctx->blame_key, 32, hipMemcpyHostToDevice, ctx->stream), "key copy");
+  ctx->h2d_bytes += 32;
+  tc::launch_blame_seed(ctx->stream, d_key, ctx->blame_calls++, d_seed);
+  std::vector<uint8_t> h_pres, h_live, h_bad, h_verdict;
+  std::vector<tc::BlameSearch> search;
+  std::vector<tc::BlameRange> ranges;
+  std::vector<uint32_t> items, counts;
+  for (size_t f0 = 0; f0 < F && !k.failed; f0 += Fc) {
+    const size_t cnt = (F - f0 < Fc) ? F - f0 : Fc, rows = cnt * N;
+    // (the share leaves first: a share that does not decode clears its live byte, and its key share's leaf is the identity too)
+    tc::launch_blame_leaves(ctx->stream, ta, sig, d_seed, (uint64_t)(f0 * N), c_sh + f0 * N * PB, 0, c_live + f0 * N, rows, d_leaf_s, d_sink);
+    tc::launch_blame_leaves(ctx->stream, ta, false, d_seed, (uint64_t)(f0 * N), d_pks, N, c_live + f0 * N, rows, d_leaf_pk, d_sink);
+    h_pres.resize(rows);
+    h_live.resize(rows);
+    h_bad.assign(rows, 0);
+    k.check(hipMemcpyAsync(h_pres.data(), c_pres + f0 * N, rows, hipMemcpyDeviceToHost, ctx->stream), "present readback");
+    k.check(hipMemcpyAsync(h_live.data(), c_live + f0 * N, rows, hipMemcpyDeviceToHost, ctx->stream), "live readback");
+    ctx->d2h_bytes += 2 * rows;
+    if (!k.check(hipStreamSynchronize(ctx->stream), "stream sync")) break;
+    search.assign(cnt, tc::BlameSearch());
+    for (size_t f = 0; f < cnt; f++) search[f].start((uint32_t)N, h_pres.data() + f * N, h_live.data() + f * N, h_bad.data() + f * N);
+    while (!k.failed) {
+      // one round: the pending checks of every job of the chunk in ONE launch
+      ranges.clear();
+      counts.assign(cnt, 0);
+      for (size_t f = 0; f < cnt; f++) counts[f] = (uint32_t)search[f].plan(ranges);
+      const size_t n = ranges.size();
+      if (n == 0) break;
+      items.resize(4 * n);  // job of the chunk, lo, hi, job of the call
+      size_t longest = 1;
+      for (size_t f = 0, i = 0; f < cnt; f++)
+        for (uint32_t c = 0; c < counts[f]; c++, i++) {
+          items[i] = (uint32_t)f;
+          items[n + i] = ranges[i].lo;
+          items[2 * n + i] = ranges[i].hi;
+          items[3 * n + i] = failed[f0 + f];
+          if (ranges[i].hi - ranges[i].lo > longest) longest = ranges[i].hi - ranges[i].lo;
+        }
+      const size_t mark = ctx->next_slot;  // the round's buffers are the next round's: it ends with a sync
+      uint32_t* d_items = k.temp<uint32_t>(4 * n);
+      uint8_t* s_sh = k.temp<uint8_t>(n * PB);
+      uint8_t* s_shc = sig ? nullptr : k.temp<uint8_t>(n * 96);
+      uint8_t* s_pk = k.temp<uint8_t>(n * 96);
+      uint8_t* s_hash = k.temp<uint8_t>(n * 192);
+      uint8_t* s_w = sig ? nullptr : k.temp<uint8_t>(n * 192);
+      uint8_t* s_ok = k.temp<uint8_t>(n);
+      const tc::PairingWs pws = k.pairing_ws(n);
+      if (k.failed) break;
+      k.check(hipMemcpyAsync(d_items, items.data(), 16 * n, hipMemcpyHostToDevice, ctx->stream), "item copy");
+      ctx->h2d_bytes += 16 * n;
+      tc::launch_blame_range_sum(ctx->stream, sig, d_leaf_s, N, d_items, d_items + n, d_items + 2 * n, n, tc::blame_sum_parts(sig, n, longest, ctx->cus), s_sh);
+      tc::launch_blame_range_sum(ctx->stream, false, d_leaf_pk, N, d_items, d_items + n, d_items + 2 * n, n, tc::blame_sum_parts(false, n, longest, ctx->cus),
+                                 s_pk);
+      tc::launch_gather_rows(ctx->stream, d_hash, 192, d_items + 3 * n, n, s_hash);
+      if (sig) {
+        // e(sum r_i pk_i, H) == e(g1, sum r_i sig_i)
+        tc::launch_pairing_check(ctx->stream, s_pk, 96, s_hash, 192, d_g1, 0, s_sh, 192, n, s_ok, pws);
+      } else {
+        // e([c] sum r_i share_i, H') == e(sum r_i pk_i, w), the cofactor constant on the share side as in the per-share check
+        tc::launch_gather_rows(ctx->stream, d_w, 192, d_items + 3 * n, n, s_w);
+        tc::launch_g1_scale_cofactor_fix(ctx->stream, s_sh, 96, n, s_shc);
+        tc::launch_pairing_check(ctx->stream, s_shc, 96, s_hash, 192, s_pk, 96, s_w, 192, n, s_ok, pws);
+      }
+      h_verdict.resize(n);
+      k.check(hipMemcpyAsync(h_verdict.data(), s_ok, n, hipMemcpyDeviceToHost, ctx->stream), "verdict readback");
+      ctx->d2h_bytes += n;
+      k.check(hipStreamSynchronize(ctx->stream), "stream sync");
+      ctx->next_slot = mark;
+      if (k.failed) break;
+      for (size_t f = 0, i = 0; f < cnt; i += counts[f], f++) search[f].apply(h_verdict.data() + i);
+      ctx->blame_rounds++;
+    }
+    for (size_t f = 0; f < cnt; f++) ctx->blame_checks += search[f].checks;
+    for (size_t r = 0; r < rows; r++) h_ok[f0 * N + r] = h_bad[r] ? 0 : 1;
+  }
+}
+
 // ---- robust combination ------------------------------------------------------------------------------
 // What a node runs per message: of up to N shares, some absent and some possibly forged, combine the first t+1 VALID ones and
 // name the senders of bad ones -- the loop of examples/threshold_sig.rs:115-131 followed by combine_signatures
@@ -1883,6 +2040,7 @@ static int robust_combine(tc_ctx* ctx, bool sig, bool wire, const uint8_t* commi
                           size_t group, const uint8_t* seed32, uint8_t* out, bool out_unbacked, uint8_t* used, uint8_t* bad, uint8_t* status,
                           uint64_t* n_fallback) {
   TC_REQUIRE(ctx);
+  ctx->blame_checks = ctx->blame_rounds = 0;
   if (n_fallback) *n_fallback = 0;
   if (B == 0) return TC_OK;
   TC_REQUIRE(ctx && commit && shares && out && status);
@@ -1908,6 +2066,9 @@ static int robust_combine(tc_ctx* ctx, bool sig, bool wire, const uint8_t* commi
   const uint8_t* d_sh = k.in(shares, B * N * SB);
   // (pass 2 expands the failed jobs' shares to the uncompressed form: guard_private sees the size the uncompressed entry has)
   if (wire) k.operand_bytes += B * N * SB;
+  // (pass 2 by bisection multiplies the key share of every examined slot as well: lanes of its own, priced like an operand)
+  const bool bisect = ctx->blame_bisect;
+  if (bisect) k.operand_bytes += B * N * 96;
   const uint8_t* d_hash_in = hashes ? k.in(hashes, B * 192) : nullptr;
   const uint8_t* d_msgs = off ? k.in(msgs, (size_t)total) : nullptr;
   const uint64_t* d_off = off ? k.in(off, B + 1) : nullptr;
@@ -2052,12 +2213,14 @@ static int robust_combine(tc_ctx* ctx, bool sig, bool wire, const uint8_t* commi
     uint8_t* c_sh = k.temp<uint8_t>(R * PB);
     uint8_t* c_wire = wire ? k.temp<uint8_t>(R * SB) : nullptr;
     uint8_t* c_dec = wire ? k.temp<uint8_t>(R) : nullptr;
-    uint8_t* c_shc = sig ? nullptr : k.temp<uint8_t>(R * 96);
-    uint8_t* c_hash = k.temp<uint8_t>(R * 192);
-    uint8_t* c_w = sig ? nullptr : k.temp<uint8_t>(R * 192);
-    uint8_t* c_pk = k.temp<uint8_t>(R * 96);
+    uint8_t* c_shc = sig || bisect ? nullptr : k.temp<uint8_t>(R * 96);
+    // (the per-share checks read one hash point / w / key share per record; the range checks of the bisection gather theirs per round)
+    uint8_t* c_hash = bisect ? nullptr : k.temp<uint8_t>(R * 192);
+    uint8_t* c_w = sig || bisect ? nullptr : k.temp<uint8_t>(R * 192);
+    uint8_t* c_pk = bisect ? nullptr : k.temp<uint8_t>(R * 96);
     uint8_t* c_ok = k.temp<uint8_t>(R);
-    uint8_t* c_v = k.temp<uint8_t>(R);
+    uint8_t* c_v = bisect ? nullptr : k.temp<uint8_t>(R);
+    std::vector<uint8_t> h_ok;  // bisection: the verdicts come from the host's search
     uint8_t* c_present = k.temp<uint8_t>(R);
     uint8_t* c_bad = k.temp<uint8_t>(R);
     uint64_t* d_idx2 = k.temp<uint64_t>(F * need);
@@ -2082,24 +2245,35 @@ static int robust_combine(tc_ctx* ctx, bool sig, bool wire, const uint8_t* commi
       } else {
         tc::launch_gather_rows(ctx->stream, d_sh, PB, d_maps, R, c_sh);
       }
-      tc::launch_gather_rows(ctx->stream, d_hash, 192, d_maps + R, R, c_hash);
-      tc::launch_gather_rows(ctx->stream, d_pks, 96, d_maps + 2 * R, R, c_pk);
-      if (sig) {
-        tc::launch_pairing_check(ctx->stream, c_pk, 96, c_hash, 192, d_g1, 0, c_sh, 192, R, c_ok, k.pairing_ws(R));
+      if (bisect) {
+        // which checks run is the ONLY difference: ranges of slots, halved where they fail (blame_pass), instead of every slot
+        blame_pass(k, sig, wire, N, failed, d_maps, c_sh, c_dec, d_present, d_jvalid, d_pks, d_hash, d_w, d_g1, h_ok);
+        if (!k.failed) {
+          k.check(hipMemcpyAsync(c_ok, h_ok.data(), R, hipMemcpyHostToDevice, ctx->stream), "verdict copy");
+          ctx->h2d_bytes += R;
+        }
       } else {
-        tc::launch_gather_rows(ctx->stream, d_w, 192, d_maps + R, R, c_w);
-        tc::launch_g1_scale_cofactor_fix(ctx->stream, c_sh, 96, R, c_shc);
-        tc::launch_pairing_check(ctx->stream, c_shc, 96, c_hash, 192, c_pk, 96, c_w, 192, R, c_ok, k.pairing_ws(R));
-      }
-      if (wire) {
-        tc::launch_ok_and_status(ctx->stream, c_dec, R, c_ok);  // (the checked decode has tested membership)
-      } else if (ctx->input_checks) {  // members only (the key shares are sums of the commitment's points, tested above)
-        if (sig) tc::launch_subgroup_check_g2(ctx->stream, c_sh, 192, 1, 1, R, c_v);
-        else tc::launch_subgroup_check_g1(ctx->stream, c_sh, 96, 1, 1, R, c_v);
+        tc::launch_gather_rows(ctx->stream, d_hash, 192, d_maps + R, R, c_hash);
+        tc::launch_gather_rows(ctx->stream, d_pks, 96, d_maps + 2 * R, R, c_pk);
+        if (sig) {
+          tc::launch_pairing_check(ctx->stream, c_pk, 96, c_hash, 192, d_g1, 0, c_sh, 192, R, c_ok, k.pairing_ws(R));
+        } else {
+          tc::launch_gather_rows(ctx->stream, d_w, 192, d_maps + R, R, c_w);
+          tc::launch_g1_scale_cofactor_fix(ctx->stream, c_sh, 96, R, c_shc);
+          tc::launch_pairing_check(ctx->stream, c_shc, 96, c_hash, 192, c_pk, 96, c_w, 192, R, c_ok, k.pairing_ws(R));
+        }
+        if (wire) {
+          tc::launch_ok_and_status(ctx->stream, c_dec, R, c_ok);  // (the checked decode has tested membership)
+        } else if (ctx->input_checks) {  // members only (the key shares are sums of the commitment's points, tested above)
+          if (sig) tc::launch_subgroup_check_g2(ctx->stream, c_sh, 192, 1, 1, R, c_v);
+          else tc::launch_subgroup_check_g1(ctx->stream, c_sh, 96, 1, 1, R, c_v);
+          tc::launch_invalidate_jobs(ctx->stream, c_v, 1, 1, R, nullptr, nullptr, 0, c_ok);
+        }
+        tc::launch_gather_bytes(ctx->stream, d_jvalid, d_maps + R, R, c_v);
         tc::launch_invalidate_jobs(ctx->stream, c_v, 1, 1, R, nullptr, nullptr, 0, c_ok);
+        ctx->blame_checks = R;
+        ctx->blame_rounds = 1;
       }
-      tc::launch_gather_bytes(ctx->stream, d_jvalid, d_maps + R, R, c_v);
-      tc::launch_invalidate_jobs(ctx->stream, c_v, 1, 1, R, nullptr, nullptr, 0, c_ok);
       tc::launch_robust_mark(ctx->stream, d_present, d_maps, c_ok, R, c_present, c_bad, d_bad);
       // the first t+1 VALID shares: their combination needs no further check
       tc::launch_select_shares(ctx->stream, c_present, c_bad, N, need, F, d_fmap, d_idx2, d_slot2, d_used, d_enough2);

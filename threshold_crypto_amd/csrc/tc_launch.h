@@ -291,4 +291,21 @@ void launch_robust_finish(hipStream_t st, const uint32_t* map, size_t N, size_t 
                           const uint8_t* job_st, const uint8_t* ok, const uint8_t* member, const uint8_t* comb, uint8_t* out, uint8_t* status,
                           uint8_t* used, uint8_t* verdict);
 
+// Blame by bisection (k_blame.hip; rule and bounds in tc_blame.h).
+//   launch_blame_seed       seed_out (32 B) = the pass-2 seed of call number `call` under the context's 32-byte key
+//   launch_blame_leaves     leaves[i] = [r_(leaf0 + i)] pts[i % period] (period 0: pts[i]; affine encodings, 192 / 96 B) for i < n,
+//                           r the 63-bit scalar of launch_rlc_scalars drawn from seed32 at block leaf0 + i; blame_leaf_bytes(g2)
+//                           per leaf.  live: n bytes or null; 0 = the identity, and a point that does not decode clears its
+//                           byte.  sink: blame_sink_bytes() of scratch.
+//   launch_blame_range_sum  out[it] (192 / 96 B affine) = the sum of the leaves [lo[it], hi[it]) of job job[it] (N leaves per
+//                           job); `parts` lanes / lane pairs per item (blame_sum_parts)
+size_t blame_leaf_bytes(bool g2);
+size_t blame_sink_bytes();
+void launch_blame_seed(hipStream_t st, const uint8_t* key32, uint64_t call, uint8_t* seed_out);
+void launch_blame_leaves(hipStream_t st, TableArena ta, bool g2, const uint8_t* seed32, uint64_t leaf0, const uint8_t* pts, size_t period, uint8_t* live,
+                         size_t n, int32_t* leaves, int32_t* sink);
+size_t blame_sum_parts(bool g2, size_t n_items, size_t longest, int cus);
+void launch_blame_range_sum(hipStream_t st, bool g2, const int32_t* leaves, size_t N, const uint32_t* job, const uint32_t* lo, const uint32_t* hi,
+                            size_t n_items, size_t parts, uint8_t* out);
+
 }  // namespace tc

@@ -86,6 +86,31 @@ class Engine:
     def input_checks(self):
         return bool(self._lib.tc_ctx_get_input_checks(self._ctx))
 
+    def set_blame_bisect(self, key=None):
+        """Pass 2 of the four robust combiners (tc_ctx_set_blame_bisect): None = one pairing check per present share (the
+        default); 32 secret random bytes = blame by bisection -- range checks over shares multiplied by secret scalars, at most
+        min(1 + 2 k d, 2 N - 1) checks for a job with k bad shares among N (d = ceil(log2 N)), the same outputs up to 2^-63 per
+        check.  The key must stay secret for the context's lifetime; every call derives scalars of its own from it."""
+        if key is not None:
+            key = bytes(key)
+            if len(key) != 32:
+                raise ValueError("key: 32 bytes")
+        rc = self._lib.tc_ctx_set_blame_bisect(self._ctx, key)
+        if rc != 0:
+            raise TcError(rc, "tc_ctx_set_blame_bisect")
+
+    def blame_bisect(self):
+        return bool(self._lib.tc_ctx_get_blame_bisect(self._ctx))
+
+    def last_blame_stats(self):
+        """(pairing checks, rounds) pass 2 of the last robust call on this context spent: F * N and 1 share by share for F
+        messages examined, the search's totals by bisection, (0, 0) when no message reached pass 2"""
+        checks, rounds = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        rc = self._lib.tc_ctx_last_blame_stats(self._ctx, ctypes.byref(checks), ctypes.byref(rounds))
+        if rc != 0:
+            raise TcError(rc, "tc_ctx_last_blame_stats")
+        return int(checks.value), int(rounds.value)
+
     def trim(self):
         """give the context's staging / table buffers back to the device (tc_ctx_trim)"""
         self._lib.tc_ctx_trim(self._ctx)
