@@ -237,6 +237,33 @@ int tc_verify_g2_rlc_batch(tc_ctx* ctx, const uint8_t* pk, const uint8_t* sig, c
                            const uint8_t* seed32, uint8_t* ok, uint64_t* n_fallback);
 int tc_verify_sig_rlc_batch(tc_ctx* ctx, const uint8_t* pk, const uint8_t* sig, const uint8_t* msgs, const uint64_t* off, size_t B,
                             size_t group, const uint8_t* seed32, uint8_t* ok, uint64_t* n_fallback);
+/* Batch verification of RAGGED input (opt-in): M messages, message m owning the records rec_off[m] .. rec_off[m + 1], each
+ * record a signature sigs[r] and the index key_idx[r] of its key in a table of K keys -- votes of N validators under their own
+ * keys, the shares that have arrived so far, unrelated triples.  ok[r] = pks[key_idx[r]].verify_g2(sigs[r], hashes[m])
+ * (PublicKey::verify_g2 / verify, src/lib.rs:108-117; PublicKeyShare::verify, src/lib.rs:177-179; the loop of
+ * examples/threshold_sig.rs:115-131 when some shares are missing).  Messages are cut into groups of `group` consecutive
+ * messages (0 = 64; at most 1024); a group passes with ONE product check
+ *     prod_{m in g} e(P_m, H_m) == e(g1, S_g),   P_m = sum_{r in m} rho_r pks[key_idx[r]],   S_g = sum_{r in g} rho_r sigs[r]
+ * rho_r = the 63-bit scalar of ChaCha20(seed32, r): one Miller pair per MESSAGE, one final exponentiation per group and one
+ * hash_g2 per message instead of two pairs, one exponentiation and one hash per record.  A group that fails -- or holds an
+ * undecodable operand, an index >= K or, in checked-input mode, a non-member -- is re-checked record by record, so ok[] equals
+ * tc_verify_g2_batch's (pk_stride 96) on the expanded arrays up to 2^-63 per group; two records whose errors cancel in an
+ * unweighted sum are both rejected.  pks: K x 96 B; sigs: R x 192 B, R = rec_off[M] < 2^32; hashes: M x 192 B (msgs / off:
+ * one message per m, hashed on the device); rec_off: M + 1 values, 0 first, non-decreasing, in the memory of the other
+ * operands; key_idx: R values, or NULL for record r under pks[r] (K >= R); ok: R bytes; seed32: 32 secret random bytes in HOST
+ * memory; *n_fallback (optional) = records that went through the per-record checks.  Checked-input mode tests each key TABLE
+ * entry, each signature and each hash operand once.  The tables of the two sums take 3 KiB of device memory per record: a
+ * call whose tables exceed what tc_g2_lincomb_batch may spend fails with TC_ERR_HIP (split it).  Measured at about 65 536 records
+ * against tc_verify_g2_batch on the expanded arrays (profiles/verify_records_probe.txt): 1.17x at 200 keys x 328
+ * messages (8x faster than tc_verify_shares_rlc_batch there), SLOWER elsewhere -- 0.82x at 10 keys x 6 553 messages (1.09x behind
+ * tc_verify_shares_rlc_batch with hashing on both sides), 0.74x with 30 % of those records missing, 0.90x for 65 536 unrelated
+ * triples, 0.53x with a forged record in 1 % of the messages: at this size the launches of the combined form do not fill the GPU. */
+int tc_verify_g2_records_rlc_batch(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint64_t* key_idx, const uint8_t* sigs,
+                                   const uint64_t* rec_off, const uint8_t* hashes, size_t M, size_t group,
+                                   const uint8_t* seed32, uint8_t* ok, uint64_t* n_fallback);
+int tc_verify_sig_records_rlc_batch(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint64_t* key_idx, const uint8_t* sigs,
+                                    const uint64_t* rec_off, const uint8_t* msgs, const uint64_t* off, size_t M, size_t group,
+                                    const uint8_t* seed32, uint8_t* ok, uint64_t* n_fallback);
 /* Decryption-share validation by one random linear combination per ciphertext (opt-in): the loop of
  * examples/threshold_enc.rs over PublicKeyShare::verify_decryption_share (src/lib.rs:182-186) for B ciphertexts x N nodes.
  * pk_shares: N x 96 B (public_key_share(i), the same for every ciphertext); shares: B x N x 96 B; u / v / off / w: the

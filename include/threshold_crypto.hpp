@@ -223,6 +223,45 @@ struct PublicKey {
       e.check(tc_verify_sig_batch(e.ctx(), g1.data(), 0, flat.data(), msgs.data(), msgs.off.data(), sigs.size(), ok.data()));
     return std::vector<bool>(ok.begin(), ok.end());
   }
+  // MANY keys, any number of (key, signature) pairs per message -- votes under the validators' own keys, the shares that have
+  // arrived so far (a PublicKeyShare's key is its .pk, a SignatureShare's signature its .sig) -- through
+  // tc_verify_sig_records_rlc_batch (opt-in): one Miller pair and one hash per MESSAGE, one final exponentiation per group of
+  // `group` messages (0 = 64); groups that fail are re-checked pair by pair, so ok[m][k] = records[m][k].first.verify(
+  // records[m][k].second, msgs[m]) (src/lib.rs:115-117) up to 2^-63 per group.  Equal keys share one entry of the key table.
+  // seed: 32 bytes of fresh secret randomness, drawn after the signatures arrived.
+  static std::vector<std::vector<bool>> verify_records_batch(const std::vector<std::vector<std::pair<PublicKey, Signature>>>& records,
+                                                             const Messages& msgs, const std::array<std::uint8_t, 32>& seed,
+                                                             std::size_t group = 0, std::uint64_t* n_fallback = nullptr,
+                                                             Engine& e = Engine::instance()) {
+    const std::size_t M = records.size();
+    if (M != msgs.size()) throw std::invalid_argument("one list of (key, signature) pairs per message");
+    std::map<G1Bytes, std::uint64_t> slot;
+    std::vector<std::uint8_t> keys, sigs;
+    std::vector<std::uint64_t> key_idx, rec_off{0};
+    for (const auto& row : records) {
+      for (const auto& rec : row) {
+        auto it = slot.find(rec.first.g1);
+        if (it == slot.end()) {
+          it = slot.emplace(rec.first.g1, slot.size()).first;
+          keys.insert(keys.end(), rec.first.g1.begin(), rec.first.g1.end());
+        }
+        key_idx.push_back(it->second);
+        sigs.insert(sigs.end(), rec.second.g2.begin(), rec.second.g2.end());
+      }
+      rec_off.push_back(key_idx.size());
+    }
+    const std::size_t R = key_idx.size();
+    std::vector<std::uint8_t> ok(R + 1);
+    std::uint64_t nfb = 0;
+    if (R)
+      e.check(tc_verify_sig_records_rlc_batch(e.ctx(), keys.data(), slot.size(), key_idx.data(), sigs.data(), rec_off.data(), msgs.data(),
+                                              msgs.off.data(), M, group, seed.data(), ok.data(), &nfb));
+    if (n_fallback) *n_fallback = nfb;
+    std::vector<std::vector<bool>> out(M);
+    for (std::size_t m = 0; m < M; m++)
+      for (std::uint64_t r = rec_off[m]; r < rec_off[m + 1]; r++) out[m].push_back(ok[r] != 0);
+    return out;
+  }
   // PublicKey::to_bytes (src/lib.rs:149-153) / from_bytes (:140-146)
   std::array<std::uint8_t, PK_SIZE> to_bytes(Engine& e = Engine::instance()) const {
     std::array<std::uint8_t, PK_SIZE> out{};

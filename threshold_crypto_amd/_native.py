@@ -50,6 +50,9 @@ PROTOTYPES = {
     "tc_verify_shares_rlc_batch": [_u8p, _sz, _u8p, _u8p, _u64p, _sz, ctypes.c_char_p, _u8p, ctypes.POINTER(ctypes.c_uint64)],
     "tc_verify_g2_rlc_batch": [_u8p, _u8p, _u8p, _sz, _sz, ctypes.c_char_p, _u8p, ctypes.POINTER(ctypes.c_uint64)],
     "tc_verify_sig_rlc_batch": [_u8p, _u8p, _u8p, _u64p, _sz, _sz, ctypes.c_char_p, _u8p, ctypes.POINTER(ctypes.c_uint64)],
+    "tc_verify_g2_records_rlc_batch": [_u8p, _sz, _u64p, _u8p, _u64p, _u8p, _sz, _sz, ctypes.c_char_p, _u8p, ctypes.POINTER(ctypes.c_uint64)],
+    "tc_verify_sig_records_rlc_batch": [_u8p, _sz, _u64p, _u8p, _u64p, _u8p, _u64p, _sz, _sz, ctypes.c_char_p, _u8p,
+                                        ctypes.POINTER(ctypes.c_uint64)],
     "tc_verify_decryption_shares_rlc_batch": [_u8p, _sz, _u8p, _u8p, _u8p, _u64p, _u8p, _sz, ctypes.c_char_p, _u8p,
                                               ctypes.POINTER(ctypes.c_uint64)],
     "tc_combine_signatures_robust_batch": [_u8p, _sz, _sz, _u8p, _u8p, _u8p, _u8p, _u64p, _sz, _sz, ctypes.c_char_p, _u8p, _u8p, _u8p, _u8p,

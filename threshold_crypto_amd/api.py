@@ -297,6 +297,35 @@ class PublicKey(_G1Value):
             return e.verify_sig_rlc(_u8(self.raw), _stack([s.raw for s in sigs], 192), flat, off, seed=seed)[0].astype(bool)
         return e.verify_sig(_u8(self.raw), _stack([s.raw for s in sigs], 192), flat, off).astype(bool)
 
+    @staticmethod
+    def verify_records_batch(records, msgs, engine=None, seed=None, group=0):
+        """Batch verification under MANY keys (opt-in, tc_verify_sig_records_rlc_batch): records[m] is the list of
+        (PublicKey | PublicKeyShare, Signature | SignatureShare) pairs received for msgs[m] -- any number per message, none
+        included.  One Miller pair and one hash per message and one final exponentiation per group of `group` messages instead
+        of a full check per pair; groups that fail are re-checked pair by pair, so the booleans are PublicKey::verify's
+        (src/lib.rs:115-117) up to 2^-63 per group.  Equal keys share one entry of the key table.  `seed`: 32 secret random
+        bytes drawn after the signatures arrived.  Returns one list of booleans per message."""
+        e = engine or default_engine()
+        if len(records) != len(msgs):
+            raise ValueError("one list of (key, signature) pairs per message")
+        table, keys, key_idx, sigs, rec_off = {}, [], [], [], [0]
+        for row in records:
+            for pk, sig in row:
+                slot = table.get(pk.raw)
+                if slot is None:
+                    slot = table[pk.raw] = len(keys)
+                    keys.append(pk.raw)
+                key_idx.append(slot)
+                sigs.append(sig.raw)
+            rec_off.append(len(sigs))
+        if not sigs:
+            return [[] for _ in records]
+        flat, off = pack_messages([bytes(m) for m in msgs])
+        ok, _ = e.verify_sig_records_rlc(_stack(keys, 96), np.array(key_idx, dtype=np.uint64), _stack(sigs, 192), np.array(rec_off, dtype=np.uint64),
+                                         flat, off, group=group, seed=seed)
+        ok = ok.astype(bool)
+        return [[bool(x) for x in ok[rec_off[m]:rec_off[m + 1]]] for m in range(len(records))]
+
 
 class PublicKeyShare(PublicKey):
     """struct PublicKeyShare(PublicKey) (src/lib.rs:159)."""

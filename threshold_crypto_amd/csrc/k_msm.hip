@@ -1,6 +1,7 @@
 // gfx950 kernels: G2 linear combinations in two stages (tc_msm.h) -- the share combiner of the general path (every
 // job the small-index fast path does not take; BASELINE config "t=67, N=200") and tc_g2_lincomb_batch.
 #include "tc_msm.h"
+#include "tc_records.h"
 #include "tc_launch.h"
 
 namespace tc {
@@ -167,6 +168,154 @@ void launch_msm_g2(hipStream_t st, size_t n, size_t pts_stride, const uint8_t* p
   else
     hipLaunchKernelGGL(k_msm_ladder_split, dim3(grid_for(B * parts * kG2Lanes)), dim3(kBlock), 0, st, n, B, (const int32_t*)tbl,
                        (const uint8_t*)codes, out, (const uint8_t*)status, nbits, f, parts);
+}
+
+// ---- ragged sums (tc_records.h; tc_verify_g2_records_rlc_batch) -----------------------------------------------
+// The same two stages over SEGMENTS of one record array: segment j owns the records seg_first[j] .. seg_first[j + 1] and the
+// chunks first_chunk[j] .. first_chunk[j + 1] (both arrays J + 1 values, made by the host: rec_chunk_ranges).  Its tables and
+// codes have the layout of a job of the fixed-n kernels with n = its length, so stage T and stage L are job_msm_tables* /
+// job_msm_ladder*_part as they are; what is new is where a lane finds its work.
+static_assert(kRecChunk == kMsmChunk, "tc_records.h pads segments to the chunk of the two-stage kernels");
+
+// keys[r] = pks[key_idx[r]] (six lanes per record, 16 bytes each); an index outside the table leaves 96 bytes that no decoder
+// accepts (flag bit 7), so the record's segment fails in stage T and the record in the per-record pass
+__global__ __launch_bounds__(kBlock) void k_rec_gather_keys(const uint8_t* __restrict__ pks, size_t K, const uint64_t* __restrict__ key_idx, size_t R,
+                                                          uint8_t* __restrict__ keys) {
+  const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  const size_t r = tid / 6, w = tid % 6;
+  if (r >= R) return;
+  const uint64_t i = key_idx[r];
+  uint8_t* dst = keys + r * 96 + w * 16;
+  if (i < K) {
+    const uint8_t* src = pks + (size_t)i * 96 + w * 16;
+    for (int b = 0; b < 16; b++) dst[b] = src[b];
+  } else {
+    for (int b = 0; b < 16; b++) dst[b] = 0xff;
+  }
+}
+
+// the longest trip count among the lanes of the wave (every lane of the wave calls it)
+__device__ __forceinline__ uint32_t rec_wave_max(uint32_t v) {
+  TC_UNROLL for (int d = 32; d >= 1; d >>= 1) {
+    const uint32_t o = (uint32_t)__shfl_xor((int)v, d, 64);
+    v = o > v ? o : v;
+  }
+  return v;
+}
+
+// stage T: one lane pair per chunk of the launch, whichever segment it belongs to
+__global__ __launch_bounds__(kBlock, TC_WAVES_G2) void k_rec_tables_g2(const uint8_t* __restrict__ points, const uint32_t* __restrict__ scalars,
+                                                                     const uint64_t* __restrict__ seg_first, const uint64_t* __restrict__ first_chunk,
+                                                                     size_t J, int32_t* __restrict__ tbl, uint8_t* __restrict__ codes,
+                                                                     uint8_t* __restrict__ status, int nbits) {
+  const uint64_t c = ((size_t)blockIdx.x * kBlock + threadIdx.x) / kG2Lanes;
+  if (c >= first_chunk[J]) return;
+  const size_t j = rec_segment_of_chunk(first_chunk, J, c);
+  const uint64_t r0 = seg_first[j], len = seg_first[j + 1] - r0, p0 = first_chunk[j] * kMsmChunk;
+  const bool ok = job_msm_tables((size_t)len, (size_t)(c - first_chunk[j]), points + r0 * 192, scalars + r0 * 8, tbl + p0 * 8 * kMsmEntryWords,
+                                 codes + p0 * kMsmColumns, pair_leader(), nbits);
+  if (!ok && pair_leader() && status[j] == TC_JOB_OK) status[j] = TC_JOB_INVALID_ENCODING;
+}
+
+// stage L: `parts` lane pairs per segment (a power of two <= 32), each over rec_part's share of the segment's records.  The
+// segments of a wave differ in length: every lane runs the look-ups of the LONGEST part in the wave (one trip count per wave,
+// tc_common.h wave_any) and masks the ones past its own end.  A part without records -- an empty segment, a segment shorter
+// than `parts`, a segment that failed in stage T -- runs the loop over place 0 (of its segment, or of the launch), which exists
+// whenever the launch has a record, and its sum is replaced by the identity.  No lane of a live segment leaves before the last
+// exchange; the lanes behind the last segment leave as whole segments, after the wave's trip count is agreed.
+__global__ __launch_bounds__(kBlock, TC_WAVES_G2) void k_rec_ladder_g2(const uint64_t* __restrict__ seg_first, const uint64_t* __restrict__ first_chunk,
+                                                                     size_t J, const int32_t* __restrict__ tbl, const uint8_t* __restrict__ codes,
+                                                                     uint8_t* __restrict__ out, const uint8_t* __restrict__ status, int nbits,
+                                                                     size_t parts) {
+  const size_t lp = ((size_t)blockIdx.x * kBlock + threadIdx.x) / kG2Lanes;
+  const size_t j = lp / parts, g = lp % parts;
+  const bool live = j < J;
+  uint64_t len = 0, p0 = 0;
+  if (live && status[j] == TC_JOB_OK) {
+    len = seg_first[j + 1] - seg_first[j];
+    p0 = len ? first_chunk[j] * kMsmChunk : 0;
+  }
+  const uint32_t trips = rec_wave_max((uint32_t)rec_part_trips(len, parts));
+  if (!live) return;
+  const RecPart rp = rec_part(len, g, parts);
+  const bool none = rp.s0 >= rp.s1;
+  G2Jac r = job_msm_ladder_part<true>(len ? (size_t)len : 1, tbl + p0 * 8 * kMsmEntryWords, codes + p0 * kMsmColumns, nbits,
+                                      MsmPart{(size_t)rp.s0, (size_t)rp.s1, (size_t)trips});
+  r = G2Jac::select(none, G2Jac::infinity(), r);
+  TC_NOUNROLL for (size_t d = 1; d < parts; d <<= 1) {
+    const int lanes = (int)(d * kG2Lanes);
+    const G2Jac o{msm_from_partner(r.x, lanes), msm_from_partner(r.y, lanes), msm_from_partner(r.z, lanes)};
+    r = jac_add(r, o);
+  }
+  if (g == 0) g2_encode_uncompressed(jac_to_affine(r), out + j * 192);
+}
+
+// the same in G1: one lane per chunk, `parts` lanes per segment (a power of two <= 64)
+__global__ __launch_bounds__(kBlock, 2) void k_rec_tables_g1(const uint8_t* __restrict__ points, const uint32_t* __restrict__ scalars,
+                                                           const uint64_t* __restrict__ seg_first, const uint64_t* __restrict__ first_chunk, size_t J,
+                                                           int32_t* __restrict__ tbl, uint8_t* __restrict__ codes, uint8_t* __restrict__ status,
+                                                           int nbits) {
+  const uint64_t c = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (c >= first_chunk[J]) return;
+  const size_t j = rec_segment_of_chunk(first_chunk, J, c);
+  const uint64_t r0 = seg_first[j], len = seg_first[j + 1] - r0, p0 = first_chunk[j] * kMsmChunk;
+  const bool ok = job_msm_tables_g1((size_t)len, (size_t)(c - first_chunk[j]), points + r0 * 96, scalars + r0 * 8, tbl + p0 * 8 * kMsmEntryWordsG1,
+                                    codes + p0 * kMsmColumns, nbits, true);
+  if (!ok && status[j] == TC_JOB_OK) status[j] = TC_JOB_INVALID_ENCODING;
+}
+__global__ __launch_bounds__(kBlock, 2) void k_rec_ladder_g1(const uint64_t* __restrict__ seg_first, const uint64_t* __restrict__ first_chunk, size_t J,
+                                                           const int32_t* __restrict__ tbl, const uint8_t* __restrict__ codes, uint8_t* __restrict__ out,
+                                                           const uint8_t* __restrict__ status, int top, size_t parts) {
+  const size_t lp = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  const size_t j = lp / parts, g = lp % parts;
+  const bool live = j < J;
+  uint64_t len = 0, p0 = 0;
+  if (live && status[j] == TC_JOB_OK) {
+    len = seg_first[j + 1] - seg_first[j];
+    p0 = len ? first_chunk[j] * kMsmChunk : 0;
+  }
+  const uint32_t trips = rec_wave_max((uint32_t)rec_part_trips(len, parts));
+  if (!live) return;
+  const RecPart rp = rec_part(len, g, parts);
+  const bool none = rp.s0 >= rp.s1;
+  G1Jac r = job_msm_ladder_g1_part<true>(len ? (size_t)len : 1, tbl + p0 * 8 * kMsmEntryWordsG1, codes + p0 * kMsmColumns,
+                                         MsmPart{(size_t)rp.s0, (size_t)rp.s1, (size_t)trips}, top);
+  r = G1Jac::select(none, G1Jac::infinity(), r);
+  TC_NOUNROLL for (size_t d = 1; d < parts; d <<= 1) {
+    const G1Jac o{msm_from_lane(r.x, (int)d), msm_from_lane(r.y, (int)d), msm_from_lane(r.z, (int)d)};
+    r = jac_add(r, o);
+  }
+  if (g == 0) g1_encode_uncompressed(jac_to_affine(r), out + j * 96);
+}
+
+size_t rec_table_bytes(bool g2, uint64_t chunks) {
+  return (size_t)chunks * kMsmChunk * 8 * (g2 ? kMsmEntryWords : kMsmEntryWordsG1) * sizeof(int32_t);
+}
+size_t rec_code_bytes(uint64_t chunks) { return (size_t)chunks * kMsmChunk * kMsmColumns; }
+void launch_rec_gather_keys(hipStream_t st, const uint8_t* pks, size_t K, const uint64_t* key_idx, size_t R, uint8_t* keys) {
+  if (!R) return;
+  hipLaunchKernelGGL(k_rec_gather_keys, dim3(grid_for(R * 6)), dim3(kBlock), 0, st, pks, K, key_idx, R, keys);
+}
+// out[j] = sum_r scalars[r] points[r] over segment j's records, J segments with `chunks` = first_chunk[J] >= 1 chunks in all.
+// status: J bytes (TC_JOB_OK to run; a segment with an undecodable point or a scalar that is not short gets
+// TC_JOB_INVALID_ENCODING and the identity).  nbits: the short-scalar modes of launch_msm_g2 (< 64) / launch_msm_g1 (< 128, even).
+void launch_rec_sum_g2(hipStream_t st, const uint8_t* points, const uint32_t* scalars, const uint64_t* seg_first, const uint64_t* first_chunk, size_t J,
+                       uint64_t chunks, size_t parts, int32_t* tbl, uint8_t* codes, uint8_t* out, uint8_t* status, int nbits) {
+  if (!J || !chunks) return;
+  if (parts < 1 || parts > (size_t)kBlock / kG2Lanes || (parts & (parts - 1))) parts = 1;
+  hipLaunchKernelGGL(k_rec_tables_g2, dim3(grid_for((size_t)chunks * kG2Lanes)), dim3(kBlock), 0, st, points, scalars, seg_first, first_chunk, J, tbl,
+                     codes, status, nbits);
+  hipLaunchKernelGGL(k_rec_ladder_g2, dim3(grid_for(J * parts * kG2Lanes)), dim3(kBlock), 0, st, seg_first, first_chunk, J, (const int32_t*)tbl,
+                     (const uint8_t*)codes, out, (const uint8_t*)status, nbits, parts);
+}
+void launch_rec_sum_g1(hipStream_t st, const uint8_t* points, const uint32_t* scalars, const uint64_t* seg_first, const uint64_t* first_chunk, size_t J,
+                       uint64_t chunks, size_t parts, int32_t* tbl, uint8_t* codes, uint8_t* out, uint8_t* status, int nbits) {
+  if (!J || !chunks) return;
+  if (parts < 1 || parts > (size_t)kBlock || (parts & (parts - 1))) parts = 1;
+  hipLaunchKernelGGL(k_rec_tables_g1, dim3(grid_for((size_t)chunks)), dim3(kBlock), 0, st, points, scalars, seg_first, first_chunk, J, tbl, codes, status,
+                     nbits);
+  hipLaunchKernelGGL(k_rec_ladder_g1, dim3(grid_for(J * parts)), dim3(kBlock), 0, st, seg_first, first_chunk, J, (const int32_t*)tbl,
+                     (const uint8_t*)codes, out, (const uint8_t*)status, nbits / 2, parts);
 }
 
 }  // namespace tc

@@ -4,6 +4,7 @@
 #include "tc_launch.h"
 #include "tc_robust.h"
 #include "tc_blame.h"
+#include "tc_records.h"
 #include "../../include/tc_amd.h"
 
 #include <stdio.h>
@@ -436,6 +437,10 @@ tc::Tuning tuning_from_env() {
   if (const char* q = getenv("TC_SUM_PARTS")) {
     const size_t v = (size_t)strtoull(q, nullptr, 10);
     if (v >= 1 && v <= 64 && (v & (v - 1)) == 0) tn.sum_parts = v;  // a power of two within one wave; anything else: the default rule
+  }
+  if (const char* q = getenv("TC_RECORDS_PARTS")) {
+    const size_t v = (size_t)strtoull(q, nullptr, 10);
+    if (v >= 1 && v <= 64 && (v & (v - 1)) == 0) tn.records_parts = v;  // (G2 takes at most 32: a larger value means 32 there)
   }
   if (const char* o = getenv("TC_CHECKS_BESIDE")) tn.checks_beside = (o[0] >= '0' && o[0] <= '2') ? o[0] - '0' : 1;  // 0 one stream, 1 low priority, 2 normal
   return tn;
@@ -1505,6 +1510,286 @@ int tc_verify_sig_rlc_batch(tc_ctx* ctx, const uint8_t* pk, const uint8_t* sig, 
     return TC_ERR_INVALID_ARG;
   }
   return verify_rlc(ctx, pk, sig, nullptr, msgs, off, B, group, seed32, ok, n_fallback);
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+// Batch verification of ragged input: M messages, message m owning the records rec_off[m] .. rec_off[m + 1],
+// record r = (sigs[r], pks[key_idx[r]]).  Groups of `group` consecutive messages pass with ONE product check
+//     prod_{m in g} e(P_m, H_m) == e(g1, S_g),  P_m = sum_{r in m} rho_r pk_r (G1),  S_g = sum_{r in g} rho_r sig_r (G2)
+// -- the two ragged sums of k_msm.hip (k_rec_*) over the 63-bit scalars of k_rlc_scalars, then launch_pairing_product_check with
+// one pair per message; a group that fails, holds an operand that does not decode or (checked-input mode) is no member, is
+// re-checked record by record on compacted operands like the failed messages of tc_verify_shares_rlc_batch.  rec_off is brought
+// to the host in both I/O modes (8 (M + 1) bytes): the chunk ranges of the segments are host arithmetic (tc_records.h).
+static int verify_records(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint64_t* key_idx, const uint8_t* sigs, const uint64_t* rec_off,
+                          const uint8_t* hashes, const uint8_t* msgs, const uint64_t* off, size_t M, size_t group, const uint8_t* seed32,
+                          uint8_t* ok, uint64_t* n_fallback) {
+  TC_REQUIRE(ctx);
+  if (n_fallback) *n_fallback = 0;
+  if (M == 0) return TC_OK;
+  TC_REQUIRE(ctx && rec_off && (hashes || off) && seed32);
+  if (group == 0) group = 64;
+  if (group > 1024) group = 1024;
+  if (group > M) group = M;
+  Call k(ctx);
+  std::vector<uint64_t> h_rec;
+  if (ctx->device_io) {
+    h_rec.resize(M + 1);
+    if (!k.check(hipMemcpyAsync(h_rec.data(), rec_off, (M + 1) * 8, hipMemcpyDeviceToHost, ctx->stream), "offset readback") ||
+        !k.check(hipStreamSynchronize(ctx->stream), "stream sync"))
+      return k.finish();
+    ctx->d2h_bytes += (M + 1) * 8;
+  }
+  const uint64_t* hr = ctx->device_io ? h_rec.data() : rec_off;
+  bool good = hr[0] == 0;
+  for (size_t m = 0; m < M && good; m++) good = hr[m + 1] >= hr[m];
+  if (!good) {
+    k.fail("invalid argument: offsets must start at 0 and be non-decreasing");
+    k.arg_error = true;
+    return k.finish();
+  }
+  const uint64_t R64 = hr[M];
+  TC_REQUIRE(R64 < (1ull << 32));
+  const size_t R = (size_t)R64;
+  if (R == 0) return k.finish();
+  TC_REQUIRE(sigs && ok && (K == 0 || pks));
+  TC_REQUIRE(key_idx || K >= R);
+  uint64_t total = 0;
+  if (!hashes) {
+    if (!total_bytes(k, off, M, &total)) return k.finish();
+    TC_REQUIRE(total == 0 || msgs);
+  }
+  // the segments of the sums: messages (G1); in G2 the PIECES of the groups (tc_records.h: a group of many records would leave
+  // the GPU to a few waves), then, when a group has several, the groups as segments over the sums of their pieces.  One
+  // descriptor array: [rec_off | chunks of the messages | first records of the pieces | their chunks | first pieces of the
+  // groups | their chunks]
+  const size_t NG = tc::rec_groups(M, group);
+  const size_t simd_lanes = (size_t)(ctx->cus > 0 ? ctx->cus : 256) * 4 * tc::kBlock;  // one wave per SIMD
+  const size_t pairs_most = (size_t)tc::kBlock / tc::kG2Lanes;
+  std::vector<uint64_t> h_grp(NG + 1);
+  tc::rec_group_ranges(hr, M, group, h_grp.data());
+  const uint64_t piece = tc::rec_piece_size(R, simd_lanes / tc::kG2Lanes, pairs_most);
+  const size_t NP = (size_t)tc::rec_piece_total(h_grp.data(), NG, piece);
+  std::vector<uint64_t> desc(2 * (M + 1) + 2 * (NP + 1) + 2 * (NG + 1));
+  uint64_t *h_seg1 = desc.data(), *h_fc1 = h_seg1 + M + 1, *h_seg2 = h_fc1 + M + 1, *h_fc2 = h_seg2 + NP + 1, *h_seg3 = h_fc2 + NP + 1,
+           *h_fc3 = h_seg3 + NG + 1;
+  memcpy(h_seg1, hr, (M + 1) * 8);
+  const uint64_t C1 = tc::rec_chunk_ranges(h_seg1, M, h_fc1);
+  tc::rec_piece_ranges(h_grp.data(), NG, piece, h_seg2, h_seg3);
+  const uint64_t C2 = tc::rec_chunk_ranges(h_seg2, NP, h_fc2);
+  const uint64_t C3 = tc::rec_chunk_ranges(h_seg3, NG, h_fc3);
+  uint64_t longest1 = 0, longest2 = 0, longest3 = 0;
+  for (size_t m = 0; m < M; m++) longest1 = hr[m + 1] - hr[m] > longest1 ? hr[m + 1] - hr[m] : longest1;
+  for (size_t q = 0; q < NP; q++) longest2 = h_seg2[q + 1] - h_seg2[q] > longest2 ? h_seg2[q + 1] - h_seg2[q] : longest2;
+  for (size_t g = 0; g < NG; g++) longest3 = h_seg3[g + 1] - h_seg3[g] > longest3 ? h_seg3[g + 1] - h_seg3[g] : longest3;
+  bool direct = true;  // every group is exactly one piece: the sums of the pieces ARE the sums of the groups
+  for (size_t g = 0; g < NG; g++) direct = direct && h_seg3[g + 1] - h_seg3[g] == 1;
+  const size_t forced = ctx->tuning.records_parts, forced2 = forced > pairs_most ? pairs_most : forced;
+  const size_t parts1 = tc::rec_parts(M, longest1, simd_lanes, tc::kBlock, forced);
+  const size_t parts2 = tc::rec_parts(NP, longest2, simd_lanes / tc::kG2Lanes, pairs_most, forced2);
+  const size_t parts3 = tc::rec_parts(NG, longest3, simd_lanes / tc::kG2Lanes, pairs_most, forced2);
+  const size_t table_bytes = tc::rec_table_bytes(false, C1) + tc::rec_table_bytes(true, C2) + tc::rec_table_bytes(true, C3);
+  if (table_bytes > msm_table_budget(k)) {
+    k.fail("out of memory: the tables of " + std::to_string(R) + " records need " + std::to_string(table_bytes >> 20) + " MB; split the call");
+    return k.finish();
+  }
+  const uint8_t* d_pk = k.in(pks, K * 96);
+  const uint64_t* d_kidx = k.in(key_idx, key_idx ? R : 0);
+  const uint8_t* d_sig = k.in(sigs, R * 192);
+  const uint8_t* d_hash_in = hashes ? k.in(hashes, M * 192) : nullptr;
+  const uint8_t* d_msgs = hashes ? nullptr : k.in(msgs, (size_t)total);
+  const uint64_t* d_off = hashes ? nullptr : k.in(off, M + 1);
+  // the pairs of the product checks: `group` per group, the last group filled up with identity pairs (the factor 1), so that
+  // ONE launch checks every group (a launch of one job takes as long as a launch of a thousand)
+  const size_t MP = NG * group, pad = MP - M;
+  uint8_t* d_hash = k.temp<uint8_t>(MP * 192);
+  const uint8_t* d_g1 = hashes ? ctx->g1_gen : ctx->g1_gen_unfix;
+  uint64_t* d_desc = k.temp<uint64_t>(desc.size());
+  uint8_t* d_seed = k.temp<uint8_t>(32);
+  if (d_seed) {
+    k.check(hipMemcpyAsync(d_seed, seed32, 32, hipMemcpyHostToDevice, ctx->stream), "seed copy");
+    ctx->h2d_bytes += 32;
+    k.wipe.emplace_back(d_seed, 32);
+  }
+  uint8_t* d_r = k.temp<uint8_t>(R * 32);
+  if (d_r) k.wipe.emplace_back(d_r, R * 32);
+  uint8_t* d_keys_own = key_idx ? k.temp<uint8_t>(R * 96) : nullptr;
+  const uint8_t* d_keys = key_idx ? d_keys_own : d_pk;  // the key of record r
+  uint8_t* d_P = k.temp<uint8_t>(MP * 96);
+  uint8_t* d_S = k.temp<uint8_t>(NG * 192);
+  uint8_t* d_Sp = direct ? d_S : k.temp<uint8_t>(NP * 192);  // the sums of the pieces
+  uint8_t* d_ones = k.temp<uint8_t>(NP * 32);
+  uint8_t* d_st = k.temp<uint8_t>(M + NG + NP);  // messages | groups | pieces
+  uint8_t* d_okg = k.temp<uint8_t>(NG);
+  int32_t* d_tbl1 = k.temp<int32_t>(tc::rec_table_bytes(false, C1) / sizeof(int32_t));
+  int32_t* d_tbl2 = k.temp<int32_t>(tc::rec_table_bytes(true, C2) / sizeof(int32_t));
+  int32_t* d_tbl3 = k.temp<int32_t>(tc::rec_table_bytes(true, C3) / sizeof(int32_t));
+  uint8_t* d_codes1 = k.temp<uint8_t>(tc::rec_code_bytes(C1));
+  uint8_t* d_codes2 = k.temp<uint8_t>(tc::rec_code_bytes(C2));
+  uint8_t* d_codes3 = k.temp<uint8_t>(tc::rec_code_bytes(C3));
+  // the digit codes are a lossless recoding of the secret scalars: wiped like them
+  if (d_codes1) k.wipe.emplace_back(d_codes1, tc::rec_code_bytes(C1));
+  if (d_codes2) k.wipe.emplace_back(d_codes2, tc::rec_code_bytes(C2));
+  uint8_t* d_ok = k.out(ok, R);
+  int32_t* ws_groups = k.pairing_product_ws(group, NG, true);
+  k.begin_timing();
+  // checked-input mode: every key TABLE entry once (K tests, not R), every signature, every hash operand
+  const uint8_t *v_key = nullptr, *v_sig = nullptr, *v_hash = nullptr;
+  size_t before = k.checks.size();
+  k.check_points(false, d_pk, 96, K, K, 1, (size_t)-1);
+  if (k.checks.size() > before) v_key = k.checks.back().valid;
+  before = k.checks.size();
+  k.check_points(true, d_sig, 192, 1, 1, R, 1);
+  if (k.checks.size() > before) v_sig = k.checks.back().valid;
+  before = k.checks.size();
+  if (hashes) k.check_points(true, d_hash_in, 192, 1, 1, M, 1);
+  if (k.checks.size() > before) v_hash = k.checks.back().valid;
+  std::vector<uint8_t> h_okg(NG), h_st(M + NG + NP), h_vkey, h_vsig, h_vhash, h_pad(pad * (192 + 96), 0);
+  std::vector<uint64_t> h_kidx;
+  if (!k.failed) {
+    k.check(hipMemcpyAsync(d_desc, desc.data(), desc.size() * 8, hipMemcpyHostToDevice, ctx->stream), "descriptor copy");
+    ctx->h2d_bytes += desc.size() * 8;
+    k.check(hipMemsetAsync(d_st, 0, M + NG + NP, ctx->stream), "memset");
+    if (!hashes) tc::launch_hash_g2(ctx->tuning, ctx->stream, d_msgs, d_off, M, d_hash, /*fix=*/false);
+    else k.check(hipMemcpyAsync(d_hash, d_hash_in, M * 192, hipMemcpyDeviceToDevice, ctx->stream), "hash copy");
+    if (pad) {
+      for (size_t i = 0; i < pad; i++) h_pad[i * 192] = h_pad[pad * 192 + i * 96] = 0x40;  // the identity of G2 / of G1
+      k.check(hipMemcpyAsync(d_hash + M * 192, h_pad.data(), pad * 192, hipMemcpyHostToDevice, ctx->stream), "pad copy");
+      k.check(hipMemcpyAsync(d_P + M * 96, h_pad.data() + pad * 192, pad * 96, hipMemcpyHostToDevice, ctx->stream), "pad copy");
+      ctx->h2d_bytes += pad * 288;
+    }
+    tc::launch_rlc_scalars(ctx->stream, d_seed, R, d_r);
+    const uint32_t* rr = reinterpret_cast<const uint32_t*>(d_r);
+    if (key_idx) tc::launch_rec_gather_keys(ctx->stream, d_pk, K, d_kidx, R, d_keys_own);
+    const uint64_t *d_seg1 = d_desc, *d_fc1 = d_seg1 + M + 1, *d_seg2 = d_fc1 + M + 1, *d_fc2 = d_seg2 + NP + 1, *d_seg3 = d_fc2 + NP + 1,
+                   *d_fc3 = d_seg3 + NG + 1;
+    // (the short-scalar modes of the two-stage kernels: 40 two-half steps in G1, 16 columns in G2, as tc_ciphertext_verify_rlc_batch)
+    tc::launch_rec_sum_g1(ctx->stream, d_keys, rr, d_seg1, d_fc1, M, C1, parts1, d_tbl1, d_codes1, d_P, d_st, /*nbits=*/80);
+    tc::launch_rec_sum_g2(ctx->stream, d_sig, rr, d_seg2, d_fc2, NP, C2, parts2, d_tbl2, d_codes2, d_Sp, d_st + M + NG, /*nbits=*/16);
+    // S_g = the sum of the group's pieces: the same kernels over the piece sums with the scalar 1 (short and odd).  A group
+    // without records has no piece: its sum is the identity.
+    if (!direct) {
+      k.check(hipMemsetAsync(d_ones, 0, NP * 32, ctx->stream), "memset");
+      k.check(hipMemset2DAsync(d_ones, 32, 1, 1, NP, ctx->stream), "memset");
+      tc::launch_rec_sum_g2(ctx->stream, d_Sp, reinterpret_cast<const uint32_t*>(d_ones), d_seg3, d_fc3, NG, C3, parts3, d_tbl3, d_codes3, d_S,
+                            d_st + M, 16);
+    }
+    // one pair per message (an empty message: P_m = identity, the factor 1), one final exponentiation per group
+    tc::launch_pairing_product_check(ctx->stream, d_P, 96, d_hash, 192, group, NG, d_g1, 0, d_S, 192, d_okg, ws_groups);
+    k.check(hipMemsetAsync(d_ok, 1, R, ctx->stream), "memset");
+    k.check(hipMemcpyAsync(h_okg.data(), d_okg, NG, hipMemcpyDeviceToHost, ctx->stream), "ok readback");
+    k.check(hipMemcpyAsync(h_st.data(), d_st, M + NG + NP, hipMemcpyDeviceToHost, ctx->stream), "status readback");
+    ctx->d2h_bytes += M + 2 * NG + NP;
+    k.run_checks();  // (the membership tests ran beside the sums and the group checks; their verdicts are read back below)
+    k.checks.clear();
+    if (v_key) {
+      h_vkey.resize(K);
+      k.check(hipMemcpyAsync(h_vkey.data(), v_key, K, hipMemcpyDeviceToHost, ctx->stream), "valid readback");
+      ctx->d2h_bytes += K;
+    }
+    if (v_sig) {
+      h_vsig.resize(R);
+      k.check(hipMemcpyAsync(h_vsig.data(), v_sig, R, hipMemcpyDeviceToHost, ctx->stream), "valid readback");
+      ctx->d2h_bytes += R;
+    }
+    if (v_hash) {
+      h_vhash.resize(M);
+      k.check(hipMemcpyAsync(h_vhash.data(), v_hash, M, hipMemcpyDeviceToHost, ctx->stream), "valid readback");
+      ctx->d2h_bytes += M;
+    }
+    k.check(hipStreamSynchronize(ctx->stream), "stream sync");
+    // a bad key fails the groups of the records that NAME it: the indices are needed on the host only then
+    bool key_bad = false;
+    for (size_t i = 0; i < h_vkey.size() && !key_bad; i++) key_bad = h_vkey[i] == 0;
+    const uint64_t* hk = key_idx;
+    if (key_bad && key_idx && ctx->device_io && !k.failed) {
+      h_kidx.resize(R);
+      k.check(hipMemcpyAsync(h_kidx.data(), key_idx, R * 8, hipMemcpyDeviceToHost, ctx->stream), "index readback");
+      k.check(hipStreamSynchronize(ctx->stream), "stream sync");
+      ctx->d2h_bytes += R * 8;
+      hk = h_kidx.data();
+    }
+    std::vector<uint32_t> m_sig, m_hash;
+    if (!k.failed) {
+      for (size_t g = 0; g < NG; g++) {
+        const size_t mlo = g * group, mhi = (mlo + group < M) ? mlo + group : M;
+        const uint64_t rlo = hr[mlo], rhi = hr[mhi];
+        bool bad = !h_okg[g] || h_st[M + g] != TC_JOB_OK;
+        for (uint64_t q = h_seg3[g]; q < h_seg3[g + 1] && !bad; q++) bad = h_st[M + NG + q] != TC_JOB_OK;
+        for (size_t m = mlo; m < mhi && !bad; m++) bad = h_st[m] != TC_JOB_OK || (v_hash && h_vhash[m] == 0);
+        if (v_sig)
+          for (uint64_t r = rlo; r < rhi && !bad; r++) bad = h_vsig[r] == 0;
+        if (key_bad)
+          for (uint64_t r = rlo; r < rhi && !bad; r++) {
+            const uint64_t i = hk ? hk[r] : r;
+            bad = i < K && h_vkey[i] == 0;  // (an index >= K has failed its message in stage T already)
+          }
+        if (bad)
+          for (size_t m = mlo; m < mhi; m++)
+            for (uint64_t r = hr[m]; r < hr[m + 1]; r++) {
+              m_sig.push_back((uint32_t)r);
+              m_hash.push_back((uint32_t)m);
+            }
+      }
+    }
+    if (!k.failed && !m_sig.empty()) {
+      // the per-record check of tc_verify_g2_batch for every record of the failed groups, on compacted operands
+      const size_t F = m_sig.size();
+      uint32_t* d_maps = k.temp<uint32_t>(2 * F);
+      uint8_t* c_sig = k.temp<uint8_t>(F * 192);
+      uint8_t* c_hash = k.temp<uint8_t>(F * 192);
+      uint8_t* c_pk = k.temp<uint8_t>(F * 96);
+      uint8_t* c_ok = k.temp<uint8_t>(F);
+      uint8_t* vv = ctx->input_checks ? k.temp<uint8_t>(F) : nullptr;
+      const tc::PairingWs pws = k.pairing_ws(F);
+      if (!k.failed) {
+        k.check(hipMemcpyAsync(d_maps, m_sig.data(), F * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
+        k.check(hipMemcpyAsync(d_maps + F, m_hash.data(), F * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
+        ctx->h2d_bytes += 8 * F;
+        tc::launch_gather_rows(ctx->stream, d_sig, 192, d_maps, F, c_sig);
+        tc::launch_gather_rows(ctx->stream, d_hash, 192, d_maps + F, F, c_hash);
+        tc::launch_gather_rows(ctx->stream, d_keys, 96, d_maps, F, c_pk);
+        tc::launch_pairing_check(ctx->stream, c_pk, 96, c_hash, 192, d_g1, 0, c_sig, 192, F, c_ok, pws);  // src/lib.rs:109
+        if (ctx->input_checks) {  // members only, as the per-record path would require
+          tc::launch_subgroup_check_g1(ctx->stream, c_pk, 96, 1, 1, F, vv);
+          tc::launch_invalidate_jobs(ctx->stream, vv, 1, 1, F, nullptr, nullptr, 0, c_ok);
+          tc::launch_subgroup_check_g2(ctx->stream, c_sig, 192, 1, 1, F, vv);
+          tc::launch_invalidate_jobs(ctx->stream, vv, 1, 1, F, nullptr, nullptr, 0, c_ok);
+          if (hashes) {
+            tc::launch_subgroup_check_g2(ctx->stream, c_hash, 192, 1, 1, F, vv);
+            tc::launch_invalidate_jobs(ctx->stream, vv, 1, 1, F, nullptr, nullptr, 0, c_ok);
+          }
+        }
+        tc::launch_scatter_bytes(ctx->stream, c_ok, d_maps, F, d_ok);
+        k.check(hipStreamSynchronize(ctx->stream), "stream sync");  // the host maps go out of scope
+      }
+      if (n_fallback) *n_fallback = F;
+    }
+  }
+  k.end_timing();
+  return k.finish();
+}
+
+int tc_verify_g2_records_rlc_batch(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint64_t* key_idx, const uint8_t* sigs,
+                                   const uint64_t* rec_off, const uint8_t* hashes, size_t M, size_t group, const uint8_t* seed32, uint8_t* ok,
+                                   uint64_t* n_fallback) try {
+  if (ctx && M && !hashes) {
+    ctx->err = "invalid argument: hashes";
+    return TC_ERR_INVALID_ARG;
+  }
+  return verify_records(ctx, pks, K, key_idx, sigs, rec_off, hashes, nullptr, nullptr, M, group, seed32, ok, n_fallback);
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+int tc_verify_sig_records_rlc_batch(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint64_t* key_idx, const uint8_t* sigs,
+                                    const uint64_t* rec_off, const uint8_t* msgs, const uint64_t* off, size_t M, size_t group,
+                                    const uint8_t* seed32, uint8_t* ok, uint64_t* n_fallback) try {
+  if (ctx && M && !off) {
+    ctx->err = "invalid argument: off";
+    return TC_ERR_INVALID_ARG;
+  }
+  return verify_records(ctx, pks, K, key_idx, sigs, rec_off, nullptr, msgs, off, M, group, seed32, ok, n_fallback);
 } catch (...) {
   return on_exception((tc_ctx*)ctx);
 }

@@ -44,7 +44,7 @@ inline bool duo_form(size_t jobs, size_t min_jobs) { return jobs >= min_jobs; }
 // (TC_DUO_MIN=<jobs>, TC_PAIRING_FORM=quad|lines|pair|fused, TC_PAIRING_BUDGET=<bytes>, TC_CHECKS_BESIDE=0|1: tests and experiments) is read ONCE,
 // when the context is created (tc_api.hip tuning_from_env) -- no getenv on the launch path, nothing a concurrent setenv can race
 // with -- and tc_ctx_get_tuning reports what a context uses.
-constexpr size_t kMaxPrivateBytesPerLane = 12288;  // >= the largest private segment of any kernel (11 136 B: k_msm_tables_g1; tests/test_abi.py)
+constexpr size_t kMaxPrivateBytesPerLane = 12288;  // >= the largest private segment of any kernel (11 152 B: k_rec_tables_g1; tests/test_abi.py)
 struct Tuning {
   size_t duo_min_decode = kDuoMinDecode, duo_min_hash = kDuoMinHash;
   int pairing_form = 0;       // 0 = by batch size; 1 quad, 2 lines (prepared), 3 pair (one loop), 4 fused
@@ -56,6 +56,7 @@ struct Tuning {
   size_t msm_budget = 0;      // bytes the per-share tables of the two-stage kernels may take per call; 0 = a third of the free HBM, 1-24 GiB (TC_MSM_BUDGET: tests)
   int checks_beside = 1;  // checked-input mode: the membership tests on a second stream beside the call's main kernels (TC_CHECKS_BESIDE=0: before them, one stream)
   size_t sum_parts = 0;   // lanes per output of k_g1_sum (TC_SUM_PARTS=<1|2|4|...|64>: tests, tools/g1_sum_probe.py); 0 = by B, n and the CU count (g1_sum_parts)
+  size_t records_parts = 0;  // lanes / lane pairs per segment of the ragged sums (TC_RECORDS_PARTS=<1|2|...|64>: tests, tools/verify_records_probe.py); 0 = rec_parts
 };
 
 // The G1 ladder kernels keep their per-lane table in the HBM arena and fit 256 registers (two waves per SIMD) at
@@ -164,6 +165,17 @@ size_t msm_table_bytes_g1(size_t n, size_t B);
 size_t msm_table_jobs_g1(size_t pts_stride, int nbits, size_t B);  // 1 when every job shares ONE point set and the scalars are short
 void launch_msm_g1(hipStream_t st, size_t n, size_t pts_stride, const uint8_t* points, const uint32_t* scalars, size_t B, int32_t* tbl,
                    uint8_t* codes, uint8_t* out, uint8_t* status, int nbits = 128);
+// the two stages over ragged SEGMENTS of one record array (k_msm.hip k_rec_*, tc_records.h): seg_first / first_chunk are J + 1
+// device values each (rec_chunk_ranges), chunks = first_chunk[J]; tbl: rec_table_bytes, codes: rec_code_bytes; `parts` lanes
+// (G1) / lane pairs (G2) per segment (rec_parts); status: J bytes as for launch_msm_g2.  launch_rec_gather_keys: keys[r] =
+// pks[key_idx[r]], or an undecodable encoding for an index >= K.
+size_t rec_table_bytes(bool g2, uint64_t chunks);
+size_t rec_code_bytes(uint64_t chunks);
+void launch_rec_gather_keys(hipStream_t st, const uint8_t* pks, size_t K, const uint64_t* key_idx, size_t R, uint8_t* keys);
+void launch_rec_sum_g2(hipStream_t st, const uint8_t* points, const uint32_t* scalars, const uint64_t* seg_first, const uint64_t* first_chunk, size_t J,
+                       uint64_t chunks, size_t parts, int32_t* tbl, uint8_t* codes, uint8_t* out, uint8_t* status, int nbits);
+void launch_rec_sum_g1(hipStream_t st, const uint8_t* points, const uint32_t* scalars, const uint64_t* seg_first, const uint64_t* first_chunk, size_t J,
+                       uint64_t chunks, size_t parts, int32_t* tbl, uint8_t* codes, uint8_t* out, uint8_t* status, int nbits);
 // random scalars for the batch validation of G1 values: a + b x^2 with a (odd), b from 32-bit draws of ChaCha20(seed, i)
 void launch_rlc_scalars_g1(hipStream_t st, const uint8_t* seed32, size_t n, uint8_t* out_fr);
 

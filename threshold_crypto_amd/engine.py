@@ -452,6 +452,54 @@ class Engine:
         self._call("tc_verify_sig_rlc_batch", _ptr(pk), _ptr(sig), _ptr(msgs), _ptr(off), B, int(group), seed, _ptr(ok), ctypes.byref(nfb))
         return ok, int(nfb.value)
 
+    def _records(self, pks, key_idx, sigs, rec_off, M):
+        """the operands the two ragged entries share; returns (K, R)"""
+        self._arg(pks, (None, G1_BYTES), "u8", "pks")
+        self._arg(sigs, (None, G2_BYTES), "u8", "sigs")
+        self._arg(rec_off, (M + 1,), "u64", "rec_off")
+        K, R = pks.shape[0], sigs.shape[0]
+        if not _is_torch(rec_off) and int(rec_off[M]) != R:
+            raise ValueError("rec_off[M] = %d, sigs holds %d records" % (int(rec_off[M]), R))
+        if key_idx is not None:
+            self._arg(key_idx, (R,), "u64", "key_idx")
+        elif K < R:
+            raise ValueError("key_idx omitted: record r uses pks[r], %d keys for %d records" % (K, R))
+        return K, R
+
+    def verify_g2_records_rlc(self, pks, key_idx, sigs, rec_off, hashes, group=0, seed=None):
+        """Batch verification of ragged input (opt-in; see tc_amd.h): message m owns the records rec_off[m] .. rec_off[m + 1],
+        record r is the signature sigs[r] under pks[key_idx[r]] (key_idx None: pks[r]); one Miller pair per message, one final
+        exponentiation per group of `group` messages.  sigs must hold exactly rec_off[M] records.  Returns (ok (R,), number of
+        records that fell back to per-record checks).  `seed`: 32 secret random bytes (os.urandom when omitted)."""
+        import os
+        dev = self._mode(pks, key_idx, sigs, rec_off, hashes)
+        self._arg(hashes, (None, G2_BYTES), "u8", "hashes")
+        M = hashes.shape[0]
+        K, R = self._records(pks, key_idx, sigs, rec_off, M)
+        seed = bytes(seed) if seed is not None else os.urandom(32)
+        if len(seed) != 32:
+            raise ValueError("seed: 32 bytes")
+        ok = self._empty(dev, (R,), ref=sigs)
+        nfb = ctypes.c_uint64(0)
+        self._call("tc_verify_g2_records_rlc_batch", _ptr(pks), K, _ptr(key_idx), _ptr(sigs), _ptr(rec_off), _ptr(hashes), M, int(group), seed,
+                   _ptr(ok), ctypes.byref(nfb))
+        return ok, int(nfb.value)
+
+    def verify_sig_records_rlc(self, pks, key_idx, sigs, rec_off, msgs, off, group=0, seed=None):
+        """verify_g2_records_rlc with the messages hashed on the device (one hash per MESSAGE)"""
+        import os
+        dev = self._mode(pks, key_idx, sigs, rec_off, msgs, off)
+        M = self._msgs(msgs, off)
+        K, R = self._records(pks, key_idx, sigs, rec_off, M)
+        seed = bytes(seed) if seed is not None else os.urandom(32)
+        if len(seed) != 32:
+            raise ValueError("seed: 32 bytes")
+        ok = self._empty(dev, (R,), ref=sigs)
+        nfb = ctypes.c_uint64(0)
+        self._call("tc_verify_sig_records_rlc_batch", _ptr(pks), K, _ptr(key_idx), _ptr(sigs), _ptr(rec_off), _ptr(msgs), _ptr(off), M,
+                   int(group), seed, _ptr(ok), ctypes.byref(nfb))
+        return ok, int(nfb.value)
+
     def ciphertext_verify(self, u, v, off, w):
         dev = self._mode(u, v, off, w)
         self._arg(u, (None, G1_BYTES), "u8", "u")
