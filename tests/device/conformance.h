@@ -32,6 +32,11 @@
 // jac_to_affine of it (what every shipped job body does next) with the infinity bit in flag 0.  Ops whose routine keeps
 // a table in the arena of tc_table.h (conf_needs_table) run with a table slot held, as the product's kernels do.
 //
+// The wave-uniform forms of the G2 share combination (scalar ops 128 on, point ops 172 on, byte op 214) read K, the
+// coefficients, D or (q, T, E) from the wave's first active lane: their case tables give one such key to every aligned block
+// of 32 jobs, and an op hands back the routine's exception flag (flag 1) beside its result, so that a lane which met a
+// special case shows exactly there and its 31 wave-mates show untouched.
+//
 // The byte layer (ops 180 on: hash primitives and G1, one lane per job; ops 200 on: everything that holds Fq2 or calls
 // duo_each, a lane pair per job) applies the code on either side of the arithmetic: SHA3-256, the ChaCha20 word stream,
 // the rejection samplers and the hash onto G2 of tc_hash.h, the wire codecs of tc_codec.h / tc_sqrt.h and the job_*
@@ -79,20 +84,23 @@ enum Op {
   FR_SCALE_COFACTOR_FIX,
   DIV_BY_X_ABS = 110, GLS_DECOMPOSE, GLS_DECOMPOSE_ODD, SAC_RECODE4, GLV_DECOMPOSE, GLV_RECODE_SIGN_ALIGNED, MSM_G1_RECODE,
   LAGRANGE_COEFF = 120, LAGRANGE_COEFF_FR, LAGRANGE_ALL, LAGRANGE_SPLIT, LAGRANGE_SMALL_COEFFS, COMBINE_CLASS,
-  FR_INVERSE_OF_SMALL, GCD_U64,
+  FR_INVERSE_OF_SMALL, GCD_U64, WNAF_RECODE, COMBINE_QUOTIENT_DECOMPOSE, COMBINE_DIVIDE_CHOICE,
   // point multiplication on G1, one lane per job
   G1_ADD_AFFINE = 140, G1_COMMON_Z, G1_MUL_BY_X_ABS, G1_MUL_GLV, G1_MUL_GLV_JAC, G1_MUL_GLV_ARENA, G1_LINCOMB_CHUNK4,
   G1_STRAUS_SMALL, G1_STRAUS_SMALL_INLINE, G1_COMBINE_DIVIDE, G1_COMBINE_DIVIDE_ARENA, G1_MUL_U64,
   // point multiplication on G2 (lane pair)
   G2_ADD_AFFINE = 160, G2_COMMON_Z, G2_MUL_BY_X_ABS, G2_PSI_JAC, G2_GLS_BASES, G2_SAC_TABLE, G2_JOINT_MUL4, G2_MUL_GLS,
   G2_MUL_GLS_JAC, G2_CLEAR_COFACTOR, G2_STRAUS_SMALL, G2_COMBINE_DIVIDE,
+  // the wave-uniform forms of the G2 share combination (lane pair; the parameters named in each op are the WAVE's)
+  G2_STRAUS_SMALL_UNIFORM, G2_WNAF_TABLE, G2_COMBINE_DIVIDE_UNIFORM, G2_COMBINE_DIVIDE_QUOTIENT, G2_QUOTIENT_MUL,
+  G2_COMBINE_UNIFORM_WAVE,
   // the byte layer: hash primitives and G1, one lane per job
   SHA3_256 = 180, CHACHA_WORDS, FQ_RANDOM, XOR_WITH_HASH, FQ_FROM_BE48, FQ_TO_BE48, FQ_LEX_LARGEST, G1_DECODE_UNCOMPRESSED,
   G1_ENCODE_UNCOMPRESSED, G1_ENCODE_COMPRESSED, G1_DECODE_COMPRESSED,
   // the byte layer on Fq2 / two jobs per pair (lane pair)
   G2_RANDOM_FROM_SEED = 200, G2_RANDOM_FROM_SEED_X2, HASH_G2, HASH_G2_X2, HASH_G1_G2, HASH_G1_G2_X2, FQ2_FROM_BE96,
   FQ2_TO_BE96, FQ2_LEX_LARGEST, G2_DECODE_UNCOMPRESSED, G2_ENCODE_UNCOMPRESSED, G2_ENCODE_COMPRESSED, G2_DECODE_COMPRESSED,
-  G2_DECODE_COMPRESSED_X2,
+  G2_DECODE_COMPRESSED_X2, JOB_COMBINE_SMALL_G2,
 };
 
 // the quad ops (tc_quad.h): four lanes per job on the device, two threads per job on the host
@@ -108,7 +116,8 @@ TC_HD constexpr int conf_lanes(int op) {
 // ops whose routine keeps a table in the arena (tc_table.h): the kernel holds a table slot while the op runs
 TC_HD constexpr bool conf_needs_table(int op) {
   return op == G1_MUL_GLV_ARENA || op == G1_COMBINE_DIVIDE_ARENA || op == G2_SAC_TABLE || op == G2_JOINT_MUL4 ||
-         op == G2_MUL_GLS || op == G2_MUL_GLS_JAC || op == G2_COMBINE_DIVIDE;
+         op == G2_MUL_GLS || op == G2_MUL_GLS_JAC || op == G2_COMBINE_DIVIDE || (op >= G2_STRAUS_SMALL_UNIFORM && op < SHA3_256) ||
+         op == JOB_COMBINE_SMALL_G2;
 }
 // ops that take a row block (tc_pairing.h Fq2Rows): device, kConfLineWords words per lane in the row layout of
 // k_miller_lines; host, kMillerRowSlots Fq2 per job
@@ -465,6 +474,44 @@ TC_HD void conf_scalar(Ctx& c) {
     c.put_words(0, w, 8);
   } else if constexpr (OP == GCD_U64) {
     c.put_u64(0, 0, gcd_u64(c.u64(0), c.u64(1)));
+  } else if constexpr (OP == WNAF_RECODE) {
+    // the u64 of slot 0; out: the 65 digits of width 4 (words 0 .. 64), of width kQuotWidth (65 .. 129), then pos and neg of
+    // naf_recode (word pairs 65 and 66)
+    int8_t d4[kWnafCols], dq[kWnafCols];
+    wnaf_recode<4>(c.u64(0), d4);
+    wnaf_recode<kQuotWidth>(c.u64(0), dq);
+    uint32_t w[2 * kWnafCols];
+    TC_NOUNROLL for (int i = 0; i < kWnafCols; i++) {
+      w[i] = (uint32_t)(int32_t)d4[i];
+      w[kWnafCols + i] = (uint32_t)(int32_t)dq[i];
+    }
+    c.put_words(0, w, 2 * kWnafCols);
+    uint64_t pos = 0, neg = 0;
+    naf_recode(c.u64(0), &pos, &neg);
+    c.put_u64(0, kWnafCols, pos);
+    c.put_u64(0, kWnafCols + 1, neg);
+  } else if constexpr (OP == COMBINE_QUOTIENT_DECOMPOSE || OP == COMBINE_DIVIDE_CHOICE) {
+    // D = the u64 of slot 0.  DECOMPOSE: out q, T[4], E[4] (word pairs 0 .. 8), flag 0 = the verdict.  CHOICE: flag 0 =
+    // combine_divide_takes_quotient, flag 1 = the decomposition exists, and then both predictions (word pairs 0, 1)
+    const uint64_t D = c.u64(0);
+    uint64_t q = 0;
+    int64_t T[4] = {0, 0, 0, 0}, E[4] = {0, 0, 0, 0};
+    const bool ok = combine_quotient_decompose(D, &q, T, E);
+    if constexpr (OP == COMBINE_QUOTIENT_DECOMPOSE) {
+      c.put_u64(0, 0, q);
+      TC_UNROLL for (int j = 0; j < 4; j++) {
+        c.put_u64(0, 1 + j, (uint64_t)T[j]);
+        c.put_u64(0, 5 + j, (uint64_t)E[j]);
+      }
+      c.flag(0, ok);
+    } else {
+      c.flag(0, combine_divide_takes_quotient(D));
+      c.flag(1, ok);
+      if (ok) {
+        c.put_u64(0, 0, combine_divide_uniform_macs(D));
+        c.put_u64(0, 1, combine_divide_quotient_macs(q, T, E));
+      }
+    }
   }
 }
 
@@ -541,6 +588,27 @@ TC_HD void conf_straus(Ctx& c) {
   if (c.aux[0] == 3) r = conf_straus_k<F, 3, INLINE_SAFE>(c);
   if (c.aux[0] == 4) r = conf_straus_k<F, 4, INLINE_SAFE>(c);
   put_result(c, r);
+}
+
+// straus_small_uniform / combine_uniform_wave on K G2 points (slots 4 k) and the u64 words of slot 16
+template <int K>
+TC_HD void conf_straus_uniform(Ctx& c) {
+  G2Affine pts[K];
+  uint64_t cs[K];
+  affs_at<Fq2, K>(c, c.aux[1], pts);
+  TC_UNROLL for (int k = 0; k < K; k++) cs[k] = c.u64_at(16, k);
+  bool exc = false;
+  const G2Jac r = straus_small_uniform<Fq2, K>(pts, cs, exc);
+  put_result(c, r);
+  c.flag(1, exc);
+}
+template <int K>
+TC_HD void conf_uniform_wave(Ctx& c) {
+  G2Affine pts[K];
+  uint64_t cs[K];
+  affs_at<Fq2, K>(c, c.aux[1], pts);
+  TC_UNROLL for (int k = 0; k < K; k++) cs[k] = c.u64_at(16, k);
+  put_result(c, combine_uniform_wave<K>(pts, cs, c.u64_at(16, 4), c.aux[2] != 0));
 }
 
 template <int OP>
@@ -622,6 +690,48 @@ TC_HD void conf_mul(Ctx& c) {
     put_result(c, combine_divide(jac_at<Fq2>(c, 0), c.u64_at(6, 0), c.aux[0] != 0));
   } else if constexpr (OP == G1_MUL_U64) {
     put_result(c, g1_mul_u64(jac_at<Fq>(c, 0), c.u64_at(3, 0)));
+  // ---- the wave-uniform forms: K, the coefficients, D and (q, T, E) are read from the wave's first lane by the routines, so
+  // the case tables give one value to every job of a wave (tests/device_conformance.py uniform_table) ----
+  } else if constexpr (OP == G2_STRAUS_SMALL_UNIFORM) {  // operands as G2_STRAUS_SMALL; flag 1 = exc
+    if (c.aux[0] == 2) conf_straus_uniform<2>(c);
+    if (c.aux[0] == 3) conf_straus_uniform<3>(c);
+    if (c.aux[0] == 4) conf_straus_uniform<4>(c);
+  } else if constexpr (OP == G2_WNAF_TABLE) {
+    // a Jacobian point; out: entry m at 4 m, read back through entry(m), zn at 32; flag 0 = the entries' infinity bits, flag 1 = exc
+    G2WnafTable t;
+    bool exc = false;
+    g2_wnaf_table(jac_at<Fq2>(c, 0), t, exc);
+    int inf = 0;
+    TC_NOUNROLL for (int m = 0; m < 8; m++) {
+      const G2Affine e = t.entry(m);
+      put_aff(c, 4 * m, e);
+      inf |= (int)e.inf << m;
+    }
+    c.put(32, t.zn);
+    c.flag(0, inf);
+    c.flag(1, exc);
+  } else if constexpr (OP == G2_COMBINE_DIVIDE_UNIFORM || OP == G2_COMBINE_DIVIDE_QUOTIENT) {  // Q, D in the words of slot 6; flag 1 = exc
+    bool exc = false;
+    const G2Jac q = jac_at<Fq2>(c, 0);
+    const uint64_t D = c.u64_at(6, 0);
+    const G2Jac r = OP == G2_COMBINE_DIVIDE_UNIFORM ? combine_divide_uniform(q, D, exc) : combine_divide_quotient(q, D, exc);
+    put_result(c, r);
+    c.flag(1, exc);
+  } else if constexpr (OP == G2_QUOTIENT_MUL) {  // P; q, T[4], E[4] as nine u64 from slot 6 on; flag 1 = exc
+    int64_t T[4], E[4];
+    TC_UNROLL for (int j = 0; j < 4; j++) {
+      T[j] = (int64_t)c.u64_at(6, 1 + j);
+      E[j] = (int64_t)c.u64_at(6, 5 + j);
+    }
+    bool exc = false;
+    const G2Jac r = g2_quotient_mul(jac_at<Fq2>(c, 0), c.u64_at(6, 0), T, E, exc);
+    put_result(c, r);
+    c.flag(1, exc);
+  } else if constexpr (OP == G2_COMBINE_UNIFORM_WAVE) {
+    // aux[0] = K points (aux[1] their infinity bits), K u64 coefficients and D (the words of slot 16), aux[2] = d_neg
+    if (c.aux[0] == 2) conf_uniform_wave<2>(c);
+    if (c.aux[0] == 3) conf_uniform_wave<3>(c);
+    if (c.aux[0] == 4) conf_uniform_wave<4>(c);
   }
 }
 
@@ -640,6 +750,21 @@ TC_HD void put_decoded(Ctx& c, bool ok, const Affine<F>& p) {
   put_aff(c, 0, p);
   c.flag(0, ok);
   c.flag(1, p.inf);
+}
+
+constexpr int kConfIdx = 4 * 192;  // JOB_COMBINE_SMALL_G2: the index tuple behind four shares
+template <int K>
+TC_HD void conf_combine_small(Ctx& c) {
+  uint64_t idx[K];
+  TC_UNROLL for (int k = 0; k < K; k++) {
+    const uint32_t* w = (const uint32_t*)c.in_bytes(kConfIdx + 8 * k);
+    idx[k] = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
+  }
+  DirectIO io{c.in_bytes(0), (size_t)192, c.bytes(0)};
+  uint8_t status = 0xee;
+  const bool took = job_combine_small_io<Fq2, K, DirectIO>(idx, true, io, &status);
+  c.flag(0, status);
+  c.flag(1, took);
 }
 
 template <int OP>
@@ -789,6 +914,12 @@ TC_HD void conf_bytes(Ctx& c) {
                       (size_t)c.aux[1], c.bytes(0), (c.aux[2] & 2) ? nullptr : c.bytes(192), (c.aux[2] & 1) != 0, sa, sb);
     c.flag(0, sa);
     c.flag(1, sb);
+  } else if constexpr (OP == JOB_COMBINE_SMALL_G2) {
+    // aux[0] = K uncompressed shares at bytes 192 k, the K indices as u64 at byte kConfIdx; out: the 192 bytes of the
+    // combination (nothing where the fast path does not take the job); flag 0 = the status, flag 1 = the return value
+    if (c.aux[0] == 2) conf_combine_small<2>(c);
+    if (c.aux[0] == 3) conf_combine_small<3>(c);
+    if (c.aux[0] == 4) conf_combine_small<4>(c);
   }
 }
 
@@ -959,16 +1090,19 @@ TC_HD void conf_op(Ctx& c) {
   X(FR_ADD) X(FR_SUB) X(FR_MUL) X(FR_SQR) X(FR_INV) X(FR_FROM_CANONICAL) X(FR_TO_CANONICAL) X(FR_FROM_U64) X(FR_FROM_LE32)   \
   X(FR_SCALE_COFACTOR_FIX) X(DIV_BY_X_ABS) X(GLS_DECOMPOSE) X(GLS_DECOMPOSE_ODD) X(SAC_RECODE4) X(GLV_DECOMPOSE)              \
   X(GLV_RECODE_SIGN_ALIGNED) X(MSM_G1_RECODE) X(LAGRANGE_COEFF) X(LAGRANGE_COEFF_FR) X(LAGRANGE_ALL) X(LAGRANGE_SPLIT)      \
-  X(LAGRANGE_SMALL_COEFFS) X(COMBINE_CLASS) X(FR_INVERSE_OF_SMALL) X(GCD_U64)                                           \
+  X(LAGRANGE_SMALL_COEFFS) X(COMBINE_CLASS) X(FR_INVERSE_OF_SMALL) X(GCD_U64) X(WNAF_RECODE)                            \
+  X(COMBINE_QUOTIENT_DECOMPOSE) X(COMBINE_DIVIDE_CHOICE)                                                                \
   X(G1_ADD_AFFINE) X(G1_COMMON_Z) X(G1_MUL_BY_X_ABS) X(G1_MUL_GLV) X(G1_MUL_GLV_JAC) X(G1_MUL_GLV_ARENA)                \
   X(G1_LINCOMB_CHUNK4) X(G1_STRAUS_SMALL) X(G1_STRAUS_SMALL_INLINE) X(G1_COMBINE_DIVIDE) X(G1_COMBINE_DIVIDE_ARENA)     \
   X(G1_MUL_U64) X(G2_ADD_AFFINE) X(G2_COMMON_Z) X(G2_MUL_BY_X_ABS) X(G2_PSI_JAC) X(G2_GLS_BASES) X(G2_SAC_TABLE)        \
   X(G2_JOINT_MUL4) X(G2_MUL_GLS) X(G2_MUL_GLS_JAC) X(G2_CLEAR_COFACTOR) X(G2_STRAUS_SMALL) X(G2_COMBINE_DIVIDE)      \
+  X(G2_STRAUS_SMALL_UNIFORM) X(G2_WNAF_TABLE) X(G2_COMBINE_DIVIDE_UNIFORM) X(G2_COMBINE_DIVIDE_QUOTIENT) X(G2_QUOTIENT_MUL) \
+  X(G2_COMBINE_UNIFORM_WAVE)                                                                                            \
   X(SHA3_256) X(CHACHA_WORDS) X(FQ_RANDOM) X(XOR_WITH_HASH) X(FQ_FROM_BE48) X(FQ_TO_BE48) X(FQ_LEX_LARGEST)             \
   X(G1_DECODE_UNCOMPRESSED) X(G1_ENCODE_UNCOMPRESSED) X(G1_ENCODE_COMPRESSED) X(G1_DECODE_COMPRESSED)                   \
   X(G2_RANDOM_FROM_SEED) X(G2_RANDOM_FROM_SEED_X2) X(HASH_G2) X(HASH_G2_X2) X(HASH_G1_G2) X(HASH_G1_G2_X2)              \
   X(FQ2_FROM_BE96) X(FQ2_TO_BE96) X(FQ2_LEX_LARGEST) X(G2_DECODE_UNCOMPRESSED) X(G2_ENCODE_UNCOMPRESSED)                \
-  X(G2_ENCODE_COMPRESSED) X(G2_DECODE_COMPRESSED) X(G2_DECODE_COMPRESSED_X2)
+  X(G2_ENCODE_COMPRESSED) X(G2_DECODE_COMPRESSED) X(G2_DECODE_COMPRESSED_X2) X(JOB_COMBINE_SMALL_G2)
 
 }  // namespace conf
 }  // namespace tc

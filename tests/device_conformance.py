@@ -32,7 +32,12 @@ wrappers around them -- against hashlib, the oracle's ChaCha and samplers, and i
 words (raw_bytes), byte results are read back from the output row, which stays filled with the sentinel wherever the
 routine's documented length ends (check_row).  byte_cases() is the one shared table of encodings, each with the oracle's verdict.
 
-    python tests/device_conformance.py host OPNAME     (the host leg of one op; exit status 0 = every case passed)
+The wave-uniform forms of the G2 share combination (scalar ops 128 on, point ops 172 on, byte op 214) read their parameters
+from the wave's first active lane.  Their tables are aligned blocks of 32 jobs with one key and a ragged tail (uniform_table),
+the exceptional lanes first, last and in the middle of a block, and each routine's exception flag must equal what a Python
+walk of the same ladder says (straus_uniform_model, wnaf_ladder_model, quotient_mul_model), lane by lane.
+
+    python tests/device_conformance.py host OPNAME    (the host leg of one op; exit status 0 = every case passed)
 """
 import ctypes
 import hashlib
@@ -40,6 +45,7 @@ import itertools
 import math
 import os
 import random
+import re
 import shutil
 import subprocess
 import sys
@@ -91,18 +97,20 @@ OPS = dict(
     DIV_BY_X_ABS=110, GLS_DECOMPOSE=111, GLS_DECOMPOSE_ODD=112, SAC_RECODE4=113, GLV_DECOMPOSE=114,
     GLV_RECODE_SIGN_ALIGNED=115, MSM_G1_RECODE=116,
     LAGRANGE_COEFF=120, LAGRANGE_COEFF_FR=121, LAGRANGE_ALL=122, LAGRANGE_SPLIT=123, LAGRANGE_SMALL_COEFFS=124,
-    COMBINE_CLASS=125, FR_INVERSE_OF_SMALL=126, GCD_U64=127,
+    COMBINE_CLASS=125, FR_INVERSE_OF_SMALL=126, GCD_U64=127, WNAF_RECODE=128, COMBINE_QUOTIENT_DECOMPOSE=129,
+    COMBINE_DIVIDE_CHOICE=130,
     G1_ADD_AFFINE=140, G1_COMMON_Z=141, G1_MUL_BY_X_ABS=142, G1_MUL_GLV=143, G1_MUL_GLV_JAC=144, G1_MUL_GLV_ARENA=145,
     G1_LINCOMB_CHUNK4=146, G1_STRAUS_SMALL=147, G1_STRAUS_SMALL_INLINE=148, G1_COMBINE_DIVIDE=149,
     G1_COMBINE_DIVIDE_ARENA=150, G1_MUL_U64=151,
     G2_ADD_AFFINE=160, G2_COMMON_Z=161, G2_MUL_BY_X_ABS=162, G2_PSI_JAC=163, G2_GLS_BASES=164, G2_SAC_TABLE=165,
     G2_JOINT_MUL4=166, G2_MUL_GLS=167, G2_MUL_GLS_JAC=168, G2_CLEAR_COFACTOR=169, G2_STRAUS_SMALL=170,
-    G2_COMBINE_DIVIDE=171,
+    G2_COMBINE_DIVIDE=171, G2_STRAUS_SMALL_UNIFORM=172, G2_WNAF_TABLE=173, G2_COMBINE_DIVIDE_UNIFORM=174,
+    G2_COMBINE_DIVIDE_QUOTIENT=175, G2_QUOTIENT_MUL=176, G2_COMBINE_UNIFORM_WAVE=177,
     SHA3_256=180, CHACHA_WORDS=181, FQ_RANDOM=182, XOR_WITH_HASH=183, FQ_FROM_BE48=184, FQ_TO_BE48=185, FQ_LEX_LARGEST=186,
     G1_DECODE_UNCOMPRESSED=187, G1_ENCODE_UNCOMPRESSED=188, G1_ENCODE_COMPRESSED=189, G1_DECODE_COMPRESSED=190,
     G2_RANDOM_FROM_SEED=200, G2_RANDOM_FROM_SEED_X2=201, HASH_G2=202, HASH_G2_X2=203, HASH_G1_G2=204, HASH_G1_G2_X2=205,
     FQ2_FROM_BE96=206, FQ2_TO_BE96=207, FQ2_LEX_LARGEST=208, G2_DECODE_UNCOMPRESSED=209, G2_ENCODE_UNCOMPRESSED=210,
-    G2_ENCODE_COMPRESSED=211, G2_DECODE_COMPRESSED=212, G2_DECODE_COMPRESSED_X2=213)
+    G2_ENCODE_COMPRESSED=211, G2_DECODE_COMPRESSED=212, G2_DECODE_COMPRESSED_X2=213, JOB_COMBINE_SMALL_G2=214)
 
 
 def lanes(op):
@@ -113,7 +121,8 @@ def lanes(op):
 NEEDS_ROWS = {"MILLER_LINES"}  # conformance.h conf_needs_rows
 # conformance.h conf_needs_table: the device leg runs these with a slot of a table arena held (tc_table.h)
 NEEDS_TABLE = {"G1_MUL_GLV_ARENA", "G1_COMBINE_DIVIDE_ARENA", "G2_SAC_TABLE", "G2_JOINT_MUL4", "G2_MUL_GLS", "G2_MUL_GLS_JAC",
-               "G2_COMBINE_DIVIDE"}
+               "G2_COMBINE_DIVIDE", "G2_STRAUS_SMALL_UNIFORM", "G2_WNAF_TABLE", "G2_COMBINE_DIVIDE_UNIFORM", "G2_COMBINE_DIVIDE_QUOTIENT",
+               "G2_QUOTIENT_MUL", "G2_COMBINE_UNIFORM_WAVE", "JOB_COMBINE_SMALL_G2"}
 SLOT_LEAK = -2  # conformance.hip kConfSlotLeak: a table slot was still marked in use after the run
 
 
@@ -4367,6 +4376,840 @@ _encode_spec("G1_ENCODE_UNCOMPRESSED", 1, "unc")
 _encode_spec("G1_ENCODE_COMPRESSED", 1, "comp")
 _encode_spec("G2_ENCODE_UNCOMPRESSED", 2, "unc")
 _encode_spec("G2_ENCODE_COMPRESSED", 2, "comp")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the wave-uniform forms of the G2 share combination: scalar ops 128 .. 130, point ops 172 .. 177, byte op 214
+#
+# The routines read K, the coefficients, D or (q, T, E) from the wave's first active lane (wave_uniform), so a table of
+# these ops is a sequence of aligned blocks of 32 jobs that share that key (uniform_table), with a ragged last block: every
+# prefix sizes() launches keeps each wave uniform, because lanes past the end copy the last job.  Inside a block the
+# directed special lanes stand at lane-pair positions 0, 31 and in the middle (uniform_block), ordinary ones around them.
+# ---------------------------------------------------------------------------------------------------------------------
+def header_constant(header, name):
+    """An integer constant of a product header, read from its text (`name = 123`)."""
+    with open(os.path.join(CSRC, header)) as f:
+        return int(re.search(r"\b%s = (\d+)" % name, f.read()).group(1))
+
+
+QUOT_WIDTH = header_constant("tc_gls.h", "kQuotWidth")
+WNAF_COLS = header_constant("tc_gls.h", "kWnafCols")
+MACS = {n: header_constant("tc_jobs.h", n) for n in ("kMacsDbl", "kMacsAdd", "kMacsPsi2", "kMacsUniformFixed", "kMacsQuotientFixed")}
+WAVE_JOBS = 32  # lane pairs per wave
+
+
+def ten_signer_denominators(K):
+    """The generic denominators of the K-subsets of ten signers."""
+    ds = {small_coeffs_model(list(s))[2] for s in itertools.combinations(range(10), K)}
+    return sorted(d for d in ds if combine_class(d) == "generic")
+
+
+TEN_DS = sorted(set(ten_signer_denominators(2)) | set(ten_signer_denominators(3)) | set(ten_signer_denominators(4)))
+DIVIDE_UNIFORM_DS = TEN_DS + [286, 5720, 65521, (1 << 13) + 1, (1 << 16) + 1, (1 << 20) + 7, (1 << 32) + 15, (1 << 61) - 1, (1 << 62) - 57]
+QUOTIENT_DS = (list(range(8)) + TEN_DS + [286, 5720, 65521, (1 << 13) - 1, (1 << 13) + 1, (1 << 16) - 1, (1 << 16) + 1, (1 << 32) - 1,
+                                          (1 << 32) + 15, 3 ** 39, (1 << 61) - 1, (1 << 62) - 57, (1 << 62) - 1, 1 << 62, (1 << 62) + 1,
+                                          (1 << 63) + 1] + [1 << a for a in range(63)] + [X - 1, X, X + 1])
+
+
+def wnaf_model(d, W):
+    """tc_gls.h wnaf_recode<W>: the 65 digits."""
+    k, dig = d, []
+    for _ in range(WNAF_COLS):
+        m = 0
+        if k & 1:
+            m = k & ((1 << W) - 1)
+            if m > 1 << (W - 1):
+                m -= 1 << W
+            k -= m
+        dig.append(m)
+        k >>= 1
+    return dig
+
+
+def naf_model(c):
+    """tc_gls.h naf_recode: (pos, neg) as 64-bit masks (a digit in column 64 is dropped, as the routine drops it)."""
+    c3 = 3 * c
+    return ((c3 & ~c) >> 1) & M64, ((c & ~c3) >> 1) & M64
+
+
+def signed_naf(c):
+    p, m = naf_model(abs(c))
+    return (m, p) if c < 0 else (p, m)
+
+
+def quotient_decompose_model(D):
+    """tc_gls.h combine_quotient_decompose step by step: None where it refuses D, else (q, T, E, wide, negative) -- wide:
+    some division went through the bit-by-bit 128-bit path of udiv_u128_u64; negative: the rounding met n < 0."""
+    if D < 3 or D & (D - 1) == 0 or D >> 62:
+        return None
+    q, x0 = divmod(X, D)
+    wide = (x0 * x0) >> 64 != 0
+    x2 = x0 * x0 % D
+    wide |= (x2 * x2) >> 64 != 0
+    r1 = (x2 * x2 - x2 + 1) % D
+    if math.gcd(r1, D) != 1:
+        return None
+    k = D - pow(r1, -1, D)
+    dig = [k, 0, -k, 0, k + 1]
+    c, cs, es, negative = 0, [], [], False
+    for g in dig:
+        v = c * x0 + g
+        n = 2 * v + D
+        negative |= n < 0
+        wide |= (n if n >= 0 else -n + 2 * D - 1) >> 64 != 0
+        e = n // (2 * D)
+        cs.append(c)
+        es.append(e)
+        c = v - e * D
+    if c:
+        return None
+    T = [cs[4 - j] for j in range(4)]
+    E = [es[4 - j] for j in range(4)]
+    E[2] += es[0]
+    E[0] -= es[0]
+    for j in (1, 3):
+        T[j], E[j] = -T[j], -E[j]
+    return q, T, E, wide, negative
+
+
+def quotient_scalar(q, T, E):
+    """sum_j (T_j q + E_j) (-|x|)^j mod r: what [q] T(psi) P + E(psi) P multiplies a point of G2 by."""
+    return sum((T[j] * q + E[j]) * (-X) ** j for j in range(4)) % R
+
+
+def divide_macs_model(D):
+    """tc_jobs.h combine_divide_uniform_macs and combine_divide_quotient_macs from the digit counts: (uniform, quotient)."""
+    top = nz = nz2 = 0
+    for j, d in enumerate(gls_digits(pow(D, -1, R))):
+        for col, m in enumerate(wnaf_model(d, 4)):
+            if m:
+                nz += 1
+                nz2 += j >> 1
+                top = max(top, col)
+    uni = MACS["kMacsUniformFixed"] + top * MACS["kMacsDbl"] + (nz - 1) * MACS["kMacsAdd"] + nz2 * MACS["kMacsPsi2"]
+    q, T, E = quotient_decompose_model(D)[:3]
+    nt, ne = [signed_naf(t) for t in T], [signed_naf(e) for e in E]
+    any_t, any_e = 0, 0
+    for p, m in nt:
+        any_t |= p | m
+    for p, m in ne:
+        any_e |= p | m
+    top, nz, nz2 = (any_e.bit_length() - 1 if any_e else 0), 0, 0
+    for col, m in enumerate(wnaf_model(q, QUOT_WIDTH)):
+        if m:
+            nz += 1
+            top = max(top, col)
+    for j in range(4):
+        n = bin(nt[j][0] | nt[j][1]).count("1") + bin(ne[j][0] | ne[j][1]).count("1")
+        nz += n
+        nz2 += (j >> 1) * n
+    top += any_t.bit_length() - 1 if any_t else 0
+    quo = MACS["kMacsQuotientFixed"] + top * MACS["kMacsDbl"] + (nz - 2) * MACS["kMacsAdd"] + nz2 * MACS["kMacsPsi2"]
+    return uni & 0xffffffff, quo & 0xffffffff
+
+
+def takes_quotient_model(D):
+    if quotient_decompose_model(D) is None:
+        return False
+    uni, quo = divide_macs_model(D)
+    return quo < uni
+
+
+def _signed(w, bits=32):
+    return w - (1 << bits) if w >> (bits - 1) else w
+
+
+# ---- the scalar block: the recodings, the decomposition, the choice of the form ------------------------------------------
+def _u64_case(v, tag=""):
+    return scase(u32s(v, 2), tag="%s %d" % (tag, v), v=v)
+
+
+@spec("WNAF_RECODE", lambda rnd: _u64_case(rnd.getrandbits(rnd.choice([8, 31, 62, 63, 64])), "random"))
+def _(case=None, out=None, flags=None, rnd=None):
+    """sum dig[i] 2^i = d, every digit odd or zero and below 2^(W-1), nonzero digits at least W columns apart (W = 4 and
+    kQuotWidth); naf_recode: pos - neg = c (mod 2^64, and exactly for c < 2^63), disjoint, no two adjacent digits."""
+    if rnd is not None:
+        vals = [0, 1, 1 << 63, M64, 0xAAAAAAAAAAAAAAAA, 0x5555555555555555, X, X >> 16] + [7 << k for k in range(62)]
+        vals += [X // d for d in QUOTIENT_DS if d]
+        return [_u64_case(v, "edge") for v in vals]
+    v, ws = case.v, out_words(out)
+    for W, off in ((4, 0), (QUOT_WIDTH, WNAF_COLS)):
+        dig = [_signed(w) for w in ws[off:off + WNAF_COLS]]
+        expect(sum(d << i for i, d in enumerate(dig)) == v, case, "wnaf_recode<%d>: the digits do not sum to d: %s" % (W, dig))
+        expect(all(d == 0 or (d % 2 == 1 and abs(d) < 1 << (W - 1)) for d in dig), case, "wnaf_recode<%d>: digit out of range: %s" % (W, dig))
+        nz = [i for i, d in enumerate(dig) if d]
+        expect(all(b - a >= W for a, b in zip(nz, nz[1:])), case, "wnaf_recode<%d>: nonzero digits closer than W: %s" % (W, dig))
+    pos, neg = out_u64(out, WNAF_COLS), out_u64(out, WNAF_COLS + 1)
+    expect((pos - neg) % (1 << 64) == v and pos & neg == 0, case, "naf_recode: pos %x neg %x" % (pos, neg))
+    if v < 1 << 63:
+        expect(pos - neg == v and ((pos | neg) & ((pos | neg) >> 1)) == 0, case, "naf_recode: pos %x neg %x is no NAF of c" % (pos, neg))
+
+
+def _rand_quotient_d(rnd):
+    return rnd.getrandbits(rnd.choice([4, 8, 13, 16, 24, 33, 48, 62, 63]))
+
+
+@spec("COMBINE_QUOTIENT_DECOMPOSE", lambda rnd: _u64_case(_rand_quotient_d(rnd), "random D"), nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    """The routine's stated promise: true exactly for 3 <= D < 2^62 that is no power of two, and then q = floor(|x| / D) >= 3,
+    |T_j| <= D / 2, |E_j| <= D / 2 + 2 and D sum_j (T_j q + E_j) (-|x|)^j = 1 (mod r).  (D = |x| - 1, |x|, |x| + 1 would give
+    q = 1, 1, 0: they lie above 2^62 and are refused, so the promise q >= 3 holds.)"""
+    if rnd is not None:
+        return [_u64_case(d, "D") for d in QUOTIENT_DS]
+    D = case.v
+    want = 3 <= D < 1 << 62 and D & (D - 1) != 0
+    expect(flags[0] == int(want), case, "combine_quotient_decompose returned %d" % flags[0])
+    if not want:
+        return
+    q = out_u64(out, 0)
+    T = [_signed(out_u64(out, 1 + j), 64) for j in range(4)]
+    E = [_signed(out_u64(out, 5 + j), 64) for j in range(4)]
+    expect(q == X // D and q >= 3, case, "q = %d" % q)
+    expect(all(2 * abs(t) <= D for t in T), case, "|T_j| > D / 2: %s" % T)
+    expect(all(2 * abs(e) <= D + 4 for e in E), case, "|E_j| > D / 2 + 2: %s" % E)
+    expect(D * quotient_scalar(q, T, E) % R == 1, case, "D sum (T_j q + E_j) (-|x|)^j != 1 (mod r): q %d T %s E %s" % (q, T, E))
+    m = quotient_decompose_model(D)
+    expect(m is not None and (q, T, E) == m[:3], case, "q %d T %s E %s, the model's %s" % (q, T, E, m))
+
+
+@spec("COMBINE_DIVIDE_CHOICE", lambda rnd: _u64_case(_rand_quotient_d(rnd), "random D"), nflags=2)
+def _(case=None, out=None, flags=None, rnd=None):
+    """The two cost predictions restated from the digit counts and the kMacs* constants of tc_jobs.h, and the verdict
+    "quotient < uniform"; a D the decomposition refuses never takes the quotient form."""
+    if rnd is not None:
+        return [_u64_case(d, "D") for d in QUOTIENT_DS]
+    D = case.v
+    ok = quotient_decompose_model(D) is not None
+    expect(flags[1] == int(ok), case, "the decomposition exists: %d" % flags[1])
+    if not ok:
+        expect(flags[0] == 0, case, "takes the quotient form without a decomposition")
+        return
+    uni, quo = divide_macs_model(D)
+    expect((out_u64(out, 0), out_u64(out, 1)) == (uni, quo), case, "predictions %d %d, want %d %d" % (out_u64(out, 0), out_u64(out, 1), uni, quo))
+    expect(flags[0] == int(quo < uni), case, "combine_divide_takes_quotient = %d at %d against %d" % (flags[0], quo, uni))
+
+
+# ---- the ladder models: the wave-uniform ladders walked on the oracle's group law ----------------------------------------
+def straus_uniform_model(E, pts, cs):
+    """straus_small_uniform: (sum c_k P_k, special).  special: the first base taken is at infinity, or a later addition
+    meets acc = O, e = O or acc = +-e -- what the routine's exc must report, no more and no less."""
+    nafs = [naf_model(c) for c in cs]
+    anyb = 0
+    for p, m in nafs:
+        anyb |= p | m
+    acc, started, special = _jac_of(E, None), False, False
+    for bit in range(anyb.bit_length() - 1, -1, -1):
+        if started:
+            acc = E._jdbl(acc)
+        for k, (p, m) in enumerate(nafs):
+            s = ((p >> bit) & 1) - ((m >> bit) & 1)
+            if s:
+                acc, started, special = _uniform_take(E, acc, started, special, pts[k] if s > 0 else E.neg(pts[k]))
+    return E._to_affine(acc), special
+
+
+def _uniform_take(E, acc, started, special, e):
+    """One digit of a wave-uniform ladder: the first base starts the accumulator, later ones are generic additions."""
+    if started:
+        acc, sp = _walk_add(E, acc, e)
+        return acc, True, special or sp
+    return _jac_of(E, e), True, special or e is None
+
+
+def psi_power(p, j):
+    for _ in range(j):
+        p = psi(p)
+    return p
+
+
+def wnaf_ladder_model(p, D):
+    """combine_divide_uniform = g2_wnaf_table + g2_wnaf_ladder over the base-|x| digits of D^-1 mod r:
+    (sum_j d_j (-psi)^j P, special).  On G2 the point is [1 / D] P; elsewhere (psi != [x]) it is the reference itself."""
+    E = o.E2
+    if p is None or E.dbl(p) is None:
+        return None, True
+    odd = [E.mul(p, 2 * m + 1) for m in range(4)]
+    digs = [wnaf_model(d, 4) for d in gls_digits(pow(D, -1, R))]
+    acc, started, special = _jac_of(E, None), False, False
+    for col in range(WNAF_COLS - 1, -1, -1):
+        if started:
+            acc = E._jdbl(acc)
+        for j in range(4):
+            m = digs[j][col]
+            if m:
+                e = psi_power(odd[abs(m) >> 1], j)
+                if (m < 0) != (j % 2 == 1):  # the bases are P, -psi(P), psi^2(P), -psi^3(P)
+                    e = E.neg(e)
+                acc, started, special = _uniform_take(E, acc, started, special, e)
+    return E._to_affine(acc), special
+
+
+def quotient_mul_model(p, q, T, Ec):
+    """g2_quotient_mul: ([q] T(psi) P + E(psi) P, special) with T(psi) P = sum_j T_j psi^j(P)."""
+    E = o.E2
+    bases = [psi_power(p, j) for j in range(4)]
+
+    def add_bases(acc, started, special, nafs, bit):
+        for j, (pos, neg) in enumerate(nafs):
+            s = ((pos >> bit) & 1) - ((neg >> bit) & 1)
+            if s:
+                acc, started, special = _uniform_take(E, acc, started, special, bases[j] if s > 0 else E.neg(bases[j]))
+        return acc, started, special
+
+    nt, ne = [signed_naf(t) for t in T], [signed_naf(e) for e in Ec]
+    any_t = any_e = 0
+    for pos, neg in nt:
+        any_t |= pos | neg
+    for pos, neg in ne:
+        any_e |= pos | neg
+    acc, started, special = _jac_of(E, None), False, False
+    for bit in range(any_t.bit_length() - 1, -1, -1):
+        if started:
+            acc = E._jdbl(acc)
+        acc, started, special = add_bases(acc, started, special, nt, bit)
+    special |= not started
+    p1 = E._to_affine(acc)
+    tab = [p1, E.mul(p1, 3)]  # (kQuotWidth = 3: P1 and 3 P1)
+    assert QUOT_WIDTH == 3
+    special |= p1 is None or E.dbl(p1) is None or tab[1] is None
+    dig = wnaf_model(q, QUOT_WIDTH)
+    top = max([any_e.bit_length() - 1 if any_e else 0] + [col for col, m in enumerate(dig) if m])
+    acc, started = _jac_of(E, None), False
+    for col in range(top, -1, -1):
+        if started:
+            acc = E._jdbl(acc)
+        m = dig[col]
+        if m:
+            e = tab[abs(m) >> 1]
+            acc, started, special = _uniform_take(E, acc, started, special, e if m > 0 else E.neg(e))
+        if col < 64:
+            acc, started, special = add_bases(acc, started, special, ne, col)
+    special |= not started
+    return E._to_affine(acc), special
+
+
+# ---- the wave layout of the uniform ops --------------------------------------------------------------------------------------
+# where a block's directed cases stand, the special ones first (_special_first): both ends, then the middle; every third block
+# keeps an ordinary job in the first lane, every third in the last one
+SPECIAL_AT = ((0, 31, 13, 14, 7, 22, 1, 30, 16, 5, 26, 10), (31, 13, 14, 7, 22, 1, 30, 16, 5, 26, 10, 2), (0, 13, 14, 7, 22, 1, 30, 16, 5, 26, 10, 29))
+UNIFORM = {}  # op -> (key of a case, special of a case or None): what test_wave_layout_of_uniform_ops reads
+_POOL = {}
+
+
+def g2_pool():
+    """A handful of points of G2 that the uniform tables reuse (a reference costs a Python multiplication per distinct point)."""
+    if "g2" not in _POOL:
+        rnd = random.Random("uniform-pool")
+        _POOL["g2"] = [g2_point(rnd) for _ in range(8)]
+        _POOL["curve"] = [curve_point(G2F, rnd) for _ in range(2)]
+    return _POOL["g2"]
+
+
+def curve_pool():
+    g2_pool()
+    return _POOL["curve"]
+
+
+def uniform_block(directed, ordinary, n=WAVE_JOBS, variant=0):
+    """One block: makers of directed cases at SPECIAL_AT[variant % 3] (those that fit below n), ordinary(i) everywhere else."""
+    assert len(directed) <= len(SPECIAL_AT[0])
+    at = {p: make for p, make in zip(SPECIAL_AT[variant % 3], directed) if p < n}
+    return [at[i]() if i in at else ordinary(i) for i in range(n)]
+
+
+def uniform_table(op, blocks):
+    key_of = UNIFORM[op][0]
+    assert all(len(b) == WAVE_JOBS for b in blocks[:-1]) and 0 < len(blocks[-1]) < WAVE_JOBS
+    assert all(len({key_of(c) for c in b}) == 1 for b in blocks), op
+    return [c for b in blocks for c in b]
+
+
+def whole_table(op):
+    """A spec whose directed cases ARE the table (TABLES hook)."""
+    TABLES[op] = lambda edges, rnd: edges
+
+
+def _special_first(makers, special_of):
+    """Directed makers ordered so that the special ones come first (positions 0 and 31)."""
+    probe = [(m, special_of(m())) for m in makers]
+    return [m for m, s in probe if s] + [m for m, s in probe if not s]
+
+
+# ---- straus_small_uniform ------------------------------------------------------------------------------------------------------
+def ten_signer_tuples(K):
+    """(indices, c_abs, D) of the K-subsets of ten signers, the longest coefficients first: 9 bits for K = 4 (twelve subsets),
+    7 bits for K = 3, 4 bits for K = 2."""
+    out = [(list(s),) + tuple(small_coeffs_model(list(s))[i] for i in (0, 2)) for s in itertools.combinations(range(10), K)]
+    return sorted(out, key=lambda t: -max(t[1]))
+
+
+def _straus_uniform_ref(case):
+    def ref():
+        E = o.E2
+        want = None
+        for p, c in zip(case.pts, case.cs):
+            want = E.add(want, E.mul(p, c))
+        return want, straus_uniform_model(E, case.pts, case.cs)[1]
+    return cached("straus-uniform", (tuple(case.cs), tuple(case.pts)), ref)
+
+
+def related_point_sets(K, b):
+    """Points that meet the exception in mid-ladder, not at the start: with c = (3, 1) the accumulator reaches 3 P0 (the NAF
+    of 3 is 4 - 1) and then adds P1 = +-3 P0; with c = (2, 1) the doubling P1 = 2 P0 and the cancellation P1 = -2 P0 fire in
+    the LAST column, with c = (4, 2) in the first column after the start."""
+    E = o.E2
+    p3, p2 = E.mul(b[0], 3), E.dbl(b[0])
+    return [("P1 = 3 P0", [b[0], p3] + b[2:K]), ("P1 = -3 P0", [b[0], E.neg(p3)] + b[2:K]), ("P1 = 2 P0", [b[0], p2] + b[2:K]),
+            ("P1 = -2 P0", [b[0], E.neg(p2)] + b[2:K])]
+
+
+def _straus_uniform_keys(K):
+    big = (1 << 63) - 1
+    keys = [[3, 1] + [0] * (K - 2), [2, 1] + [0] * (K - 2), [4, 2] + [0] * (K - 2), [0] * K, [1] + [0] * (K - 1), [0] * (K - 1) + [1], [1] * K,
+            [1 << 62] + [1, 2, 3][:K - 1], [big] * K]
+    return keys + [c for _, c, _ in ten_signer_tuples(K)[:2]]
+
+
+def _uniform_point_sets(rnd, K):
+    pool = g2_pool()
+    ordinary = [[pool[(3 * i + k) % len(pool)] for k in range(K)] for i in range(3)]
+    return ordinary, _point_sets(G2F, rnd, K)[1:] + related_point_sets(K, ordinary[0])
+
+
+@spec("G2_STRAUS_SMALL_UNIFORM", None, nflags=2)
+def _(case=None, out=None, flags=None, rnd=None):
+    """exc equals the model's `special` on every job -- a spurious flag is a failure: maybe_zero56 errs with probability
+    2^-46 per addition --, and the point is sum c_k P_k wherever it is false (unspecified where it is true)."""
+    if rnd is not None:
+        blocks, specials = [], []
+        for K in (2, 3, 4):
+            ordinary, sets = _uniform_point_sets(rnd, K)
+            for cs in _straus_uniform_keys(K):
+                few = sets if max(cs) < 1 << 32 else sets[:2] + sets[-4:-2]  # (a long ladder: fewer distinct references)
+                def mk(pts, tag, cs=cs):
+                    return lambda: _small_mul_case(G2F, rnd, pts, cs, tag, rnd.random() < 0.3)
+                directed = _special_first([mk(pts, tag) for tag, pts in few], lambda c: _straus_uniform_ref(c)[1])
+                specials += [m for m in directed if K == 2 and cs == [1, 1] and _straus_uniform_ref(m())[1]]
+                blocks.append(uniform_block(directed, lambda i, cs=cs: mk(ordinary[i % 3], "ordinary", cs)(), variant=len(blocks)))
+        blocks.append([specials[i % len(specials)]() for i in range(WAVE_JOBS)])  # every job special
+        pool = g2_pool()
+        blocks.append(uniform_block([], lambda i: _small_mul_case(G2F, rnd, [pool[i % 3], pool[3 + i % 4]], [5, 9], "ordinary")))
+        blocks.append(blocks[0][:7])
+        return uniform_table("G2_STRAUS_SMALL_UNIFORM", blocks)
+    want, special = _straus_uniform_ref(case)
+    flags_agree(case, flags, 2)
+    expect(flags[1] == int(special), case, "straus_small_uniform: exc = %d, the model's special = %d" % (flags[1], special))
+    if not special:
+        check_result(G2F, case, out, flags, want, "straus_small_uniform")
+
+
+UNIFORM["G2_STRAUS_SMALL_UNIFORM"] = (lambda c: (len(c.cs), tuple(c.cs)), lambda c: _straus_uniform_ref(c)[1])
+whole_table("G2_STRAUS_SMALL_UNIFORM")
+
+
+# ---- g2_wnaf_table ---------------------------------------------------------------------------------------------------------------
+def order_two_point(rnd):
+    """(x, 0): of order two under the a = 0 group law, on the curve y^2 = x^3 - x^3 (the law never reads b)."""
+    return ((rnd.randrange(1, P), rnd.randrange(P)), (0, 0))
+
+
+def order_three_point(rnd):
+    """(0, y): 2 P = (0, -y) = -P under the a = 0 group law, so 3 P = O, 5 P = -P and 7 P = P."""
+    return ((0, 0), (rnd.randrange(1, P), rnd.randrange(P)))
+
+
+def j0_curve_orders():
+    """The orders of the six curves y^2 = x^3 + c over Fq2 (the sextic twists of one another), from the trace of E(Fq)."""
+    t1 = 1 - X
+    t2 = t1 * t1 - 2 * P
+    f = math.isqrt((4 * P * P - t2 * t2) // 3)
+    assert 3 * f * f == 4 * P * P - t2 * t2 and (P + 1 - t1) % R == 0
+    return [P * P + 1 - t for t in (t2, -t2, (t2 + 3 * f) // 2, (t2 - 3 * f) // 2, (-t2 + 3 * f) // 2, (-t2 - 3 * f) // 2)]
+
+
+def order_seven_point():
+    """A point of order seven of the one curve y^2 = x^3 + c over Fq2 whose order 7 divides (none has a point of order five,
+    so 5 P = O cannot be met by operands in Fq2; E' itself has none of order 3, 5 or 7).  7 P = O: entries 3 and 7."""
+    if "seven" not in _POOL:
+        E, F = o.E2, G2F.F
+        rnd = random.Random("order-seven")
+        assert H2 * R in j0_curve_orders() and not any(n % 5 == 0 for n in j0_curve_orders())
+        n, = [n for n in j0_curve_orders() if n % 7 == 0]
+        m = n
+        while m % 7 == 0:
+            m //= 7
+        while "seven" not in _POOL:
+            x, c = (rnd.randrange(P), rnd.randrange(P)), (rnd.randrange(P), rnd.randrange(P))
+            y = o.f2_sqrt(F.add(F.mul(F.sqr(x), x), c))
+            if y is None or E.mul((x, y), n) is not None:  # (not on a curve of that class)
+                continue
+            p7 = E.mul((x, y), m)
+            while p7 is not None and E.mul(p7, 7) is not None:
+                p7 = E.mul(p7, 7)
+            if p7 is not None:
+                _POOL["seven"] = p7
+    return _POOL["seven"]
+
+
+def _wnaf_table_special(p):
+    return p is None or o.E2.dbl(p) is None
+
+
+@spec("G2_WNAF_TABLE", None, nflags=2)
+def _(case=None, out=None, flags=None, rnd=None):
+    """Entry m < 4, taken back to the original curve as (x / zn^2, y / zn^3), is [2 m + 1] P, entry 4 + m is psi of entry m on
+    the scaled curve, and every stored coordinate is inside the table-entry contract.  exc is raised by the table for the
+    identity and for a point of order two (no table can be built); a point of small odd order only carries the infinity
+    bit of its entry (3 P = O: entries 1 and 5; 7 P = O: entries 3 and 7) into the ladder, which raises exc when it meets
+    that entry.  E'(Fq2) has no points of order 3, 5 or 7 (its cofactor is prime to 105), but the group law never reads b:
+    the operand of order three is (0, y), a point of y^2 = x^3 + y^2, the one of order seven lies on the one sextic twist
+    whose order 7 divides, and no curve y^2 = x^3 + c over Fq2 has a point of order five (order_seven_point)."""
+    if rnd is not None:
+        pool, small = g2_pool(), small_points(G2F)
+
+        def mk(p, tag):
+            return lambda: _jac_case(G2F, rnd, p, tag)
+        special = [mk(None, "P = O"), mk(None, "P = O"), mk(order_two_point(rnd), "order two"), mk(order_two_point(rnd), "order two")]
+        carried = [mk(order_three_point(rnd), "order three"), mk(order_seven_point(), "order seven"), mk(small[0], "order 13"), mk(small[1], "order 23"), mk(curve_pool()[0], "outside G2"),
+                   mk(order_three_point(rnd), "order three")]
+        blocks = [uniform_block(special + carried, lambda i: mk(pool[i % 4], "ordinary")()),
+                  [special[i % 4]() for i in range(WAVE_JOBS)],
+                  uniform_block([], lambda i: mk(pool[i % 8], "ordinary")()),
+                  uniform_block(carried + special, lambda i: mk(pool[4 + i % 4], "ordinary")()),
+                  uniform_block(special, lambda i: mk(pool[i % 4], "ordinary")(), variant=1),
+                  uniform_block(special, lambda i: mk(pool[i % 4], "ordinary")(), variant=2),
+                  uniform_block(special[:1], lambda i: mk(pool[i % 3], "ordinary")(), 9)]
+        return uniform_table("G2_WNAF_TABLE", blocks)
+    E, F = o.E2, G2F.F
+    special = _wnaf_table_special(case.p)
+    flags_agree(case, flags, 2)
+    expect(flags[1] == int(special), case, "g2_wnaf_table: exc = %d, want %d" % (flags[1], special))
+    if special:
+        return
+    want = cached("wnaf-table", case.p, lambda: [E.mul(case.p, 2 * m + 1) for m in range(4)])
+    inf = sum((1 << m | 1 << (4 + m)) for m, e in enumerate(want) if e is None)
+    expect(flags[0] == inf, case, "g2_wnaf_table: infinity bits %x, want %x" % (flags[0], inf))
+    zi = (pow(residue(out[32]), -1, P), 0)
+    zi2, zi3 = F.sqr(zi), F.mul(F.sqr(zi), zi)
+    for m, e in enumerate(want):
+        if e is None:
+            continue
+        raw = (G2F.res(out, 4 * m), G2F.res(out, 4 * m + 2))
+        expect((F.mul(raw[0], zi2), F.mul(raw[1], zi3)) == e, case, "g2_wnaf_table: entry %d is not [%d] P at Z = zn" % (m, 2 * m + 1))
+        expect((G2F.res(out, 16 + 4 * m), G2F.res(out, 18 + 4 * m)) == psi(raw), case, "g2_wnaf_table: entry %d is not psi of entry %d" % (4 + m, m))
+        check_bounded(case, out, 4 * m, 4, "g2_wnaf_table entry %d" % m, val_bound=2.1)
+        check_bounded(case, out, 16 + 4 * m, 4, "g2_wnaf_table entry %d" % (4 + m), val_bound=2.1)
+
+
+UNIFORM["G2_WNAF_TABLE"] = (lambda c: None, lambda c: _wnaf_table_special(c.p))
+whole_table("G2_WNAF_TABLE")
+
+
+# ---- combine_divide_uniform, combine_divide_quotient: both forms of [1 / D] for every D -------------------------------------------
+def _divide_uniform_ref(op, case):
+    def ref():
+        if op == "G2_COMBINE_DIVIDE_UNIFORM":
+            res, special = wnaf_ladder_model(case.p, case.d)
+        else:
+            m = quotient_decompose_model(case.d)
+            res, special = (None, True) if m is None else quotient_mul_model(case.p, m[0], m[1], m[2])
+        if case.sub and not special:
+            res = o.E2.mul(case.p, pow(case.d, -1, R))
+        return res, special
+    return cached(op, (case.d, case.p), ref)
+
+
+def _divide_uniform_spec(op, extra_ds):
+    def mk(rnd, p, d, tag, sub):
+        return lambda: _jac_case(G2F, rnd, p, "%s D=%d" % (tag, d), u32s(d, 2), d=d, sub=sub)
+
+    def fn(case=None, out=None, flags=None, rnd=None):
+        if rnd is not None:
+            pool, small, curve = g2_pool(), small_points(G2F), curve_pool()
+            blocks = []
+            for i, d in enumerate(DIVIDE_UNIFORM_DS + extra_ds):
+                directed = [mk(rnd, None, d, "Q = O", True), mk(rnd, None, d, "Q = O", True), mk(rnd, small[i % len(small)], d, "small order", False),
+                            mk(rnd, curve[i % 2], d, "outside G2", False)]
+                directed = _special_first(directed, lambda c: _divide_uniform_ref(op, c)[1])
+                ordinary = lambda k, d=d, i=i: mk(rnd, pool[(i + k % 3) % len(pool)], d, "ordinary", True)()
+                blocks.append(uniform_block(directed, ordinary, variant=i))
+                if i == 0:
+                    blocks.append([mk(rnd, None, d, "Q = O", True)() for _ in range(WAVE_JOBS)])  # every job special
+                    blocks.append(uniform_block([], ordinary))  # none
+            blocks.append(blocks[3][:11])
+            return uniform_table(op, blocks)
+        want, special = _divide_uniform_ref(op, case)
+        flags_agree(case, flags, 2)
+        expect(flags[1] == int(special), case, "%s: exc = %d, the model's special = %d" % (op, flags[1], special))
+        if not special:
+            check_result(G2F, case, out, flags, want, op.lower())
+    spec(op, None, nflags=2)(fn)
+    UNIFORM[op] = (lambda c: c.d, lambda c: _divide_uniform_ref(op, c)[1])
+    whole_table(op)
+
+
+_divide_uniform_spec("G2_COMBINE_DIVIDE_UNIFORM", [])
+_divide_uniform_spec("G2_COMBINE_DIVIDE_QUOTIENT", [1, 2, 4, 1 << 20])  # (refused by the decomposition: exc on every job)
+
+
+# ---- g2_quotient_mul with q, T, E given freely -------------------------------------------------------------------------------------
+def _quotient_keys():
+    """What no D reaches: T = 0, E = 0, T a single +-1, E longer than q, q = 3 and 2^63 + 1, a digit of q in column 64 beside
+    bits of E in column 63, negative T and E of 2^61 -- and a few real decompositions."""
+    keys = [quotient_decompose_model(d)[:3] for d in (7, 3, 189, 65521)]
+    q7, t7, e7 = keys[0]
+    keys += [(q7, [0, 0, 0, 0], e7), (q7, t7, [0, 0, 0, 0])]
+    keys += [(q7, [s if j == k else 0 for j in range(4)], [1, 0, -1, 2]) for k in range(4) for s in (1, -1)]
+    keys += [(3, [1, 0, 0, 0], [(1 << 20) + 1, 0, -5, 0]), (3, t7, e7), ((1 << 63) + 1, [1, -1, 0, 2], [0, 3, 0, -1]),
+             (M64, [1, 0, 0, 0], [(1 << 63) - 1, 0, -1, 0]), (X // 5, [-(1 << 61), 0, 1 << 61, 0], [1 << 61, -(1 << 61), 0, 0])]
+    return [(q, tuple(T), tuple(E)) for q, T, E in keys]
+
+
+def _quotient_mul_ref(case):
+    def ref():
+        q, T, E = case.key
+        res, special = quotient_mul_model(case.p, q, T, E)
+        if case.sub and not special:
+            res = o.E2.mul(case.p, quotient_scalar(q, T, E))
+        return res, special
+    return cached("quotient-mul", (case.key, case.p), ref)
+
+
+@spec("G2_QUOTIENT_MUL", None, nflags=2)
+def _(case=None, out=None, flags=None, rnd=None):
+    """[q] T(psi) P + E(psi) P by the model (on G2: the multiple by sum_j (T_j q + E_j) (-|x|)^j), exc = the model's special."""
+    if rnd is not None:
+        pool, small, curve = g2_pool(), small_points(G2F), curve_pool()
+
+        def mk(p, key, tag, sub):
+            q, T, E = key
+            ws = u64_words([q] + [t % (1 << 64) for t in T] + [e % (1 << 64) for e in E])
+            return lambda: _jac_case(G2F, rnd, p, "%s q=%x T=%s E=%s" % (tag, q, list(T), list(E)), ws, key=key, sub=sub)
+        blocks = []
+        for i, key in enumerate(_quotient_keys()):
+            directed = [mk(None, key, "P = O", True), mk(None, key, "P = O", True), mk(small[i % len(small)], key, "small order", False),
+                        mk(curve[i % 2], key, "outside G2", False)]
+            blocks.append(uniform_block(_special_first(directed, lambda c: _quotient_mul_ref(c)[1]),
+                                        lambda k, key=key, i=i: mk(pool[(i + k % 3) % len(pool)], key, "ordinary", True)(), variant=i))
+            if i == 0:
+                blocks.append(uniform_block([], lambda k: mk(pool[k % 3], key, "ordinary", True)()))
+        blocks.append(blocks[0][:5])
+        return uniform_table("G2_QUOTIENT_MUL", blocks)
+    want, special = _quotient_mul_ref(case)
+    flags_agree(case, flags, 2)
+    expect(flags[1] == int(special), case, "g2_quotient_mul: exc = %d, the model's special = %d" % (flags[1], special))
+    if not special:
+        check_result(G2F, case, out, flags, want, "g2_quotient_mul")
+
+
+UNIFORM["G2_QUOTIENT_MUL"] = (lambda c: c.key, lambda c: _quotient_mul_ref(c)[1])
+whole_table("G2_QUOTIENT_MUL")
+
+
+# ---- combine_uniform_wave: no flag -- the routine repairs its own exceptional lanes ------------------------------------------------
+def uniform_wave_tuples():
+    """Ten-signer index tuples of each class, with the real lagrange_small_coeffs outputs: D = 1, a power of two, a D that takes
+    the quotient form -- and (0, 10, 100, 1000), D = 81 000 000, which keeps the 4-dimensional ladder."""
+    out = []
+    for K in (2, 3, 4):
+        seen = set()
+        for s in itertools.combinations(range(10), K):
+            c, _, D = small_coeffs_model(list(s))
+            cls = combine_class(D)
+            if cls == "generic":
+                cls = "quotient" if takes_quotient_model(D) else "ladder"
+            if (cls, D > 20) not in seen and len([1 for k in seen if k[0] == cls]) < 2:
+                seen.add((cls, D > 20))
+                out.append((list(s), c, D, cls))
+    c, _, D = small_coeffs_model([0, 10, 100, 1000])
+    out.append(([0, 10, 100, 1000], c, D, "quotient" if takes_quotient_model(D) else "ladder"))
+    return out
+
+
+def _uniform_wave_case(rnd, pts, cs, d, neg, tag, sub=True):
+    K = len(pts)
+    slots = sum((aff_slots(G2F, rnd, p, rnd.random() < 0.3) for p in pts), []) + [encode(0)] * (4 * (4 - K))
+    return mcase(slots, u64_words(list(cs) + [0] * (4 - K) + [d]), [K, inf_mask(pts), int(neg)],
+                 "K=%d %s c=%s D=%s%d" % (K, tag, list(cs), "-" if neg else "", d), pts=pts, cs=list(cs), d=d, neg=neg, sub=sub)
+
+
+def _uniform_divide_model(a, d):
+    """The [1 / D] step of combine_uniform_wave for a generic D on ANY point: the fast form the prediction picks, and where
+    that raises its flag the 4-dimensional GLS multiplication of combine_divide.  (fast result or fallback, fast special)"""
+    if takes_quotient_model(d):
+        q, T, Ec = quotient_decompose_model(d)[:3]
+        res, special = quotient_mul_model(a, q, T, Ec)
+    else:
+        res, special = wnaf_ladder_model(a, d)
+    return (mul_gls_model(a, pow(d, -1, R))[0] if special and a is not None else res), special
+
+
+def _uniform_wave_ref(case):
+    def ref():
+        E = o.E2
+        s = None
+        for p, c in zip(case.pts, case.cs):
+            s = E.add(s, E.mul(p, c))
+        if case.sub:
+            return E.mul(s, pow(-case.d if case.neg else case.d, -1, R))
+        r = _uniform_divide_model(s, case.d)[0]
+        return E.neg(r) if case.neg else r
+    return cached("uniform-wave", (tuple(case.cs), case.d, case.neg, tuple(case.pts)), ref)
+
+
+def _uniform_wave_special(case):
+    """A lane that the fast forms cannot finish by themselves: the short ladder meets an exception, the sum is O, or the
+    [1 / D] ladder meets an exception on a sum of small order."""
+    E = o.E2
+    s, special = straus_uniform_model(E, case.pts, case.cs)
+    return special or s is None or (not case.sub and _uniform_divide_model(s, case.d)[1])
+
+
+def small_order_sum_points(K, cs, d):
+    """Multiples of ONE point of order 13 whose combination is not O: the only lanes of this op outside G2.  On G2 the [1 / D]
+    ladders meet no exception except on a sum at infinity, where even an unrepaired result has Z = 0; a sum of small order
+    makes them meet one with the accumulator anywhere, so these lanes are the ones that show whether the repair after the
+    [1 / D] step took place.  Their reference is the model's: the form that ran, on the oracle's group law."""
+    E = o.E2
+    s = small_points(G2F)[0]
+    for ms in itertools.product(range(1, 13), repeat=K):
+        pts = [E.mul(s, m) for m in ms]
+        a = None
+        for p, c in zip(pts, cs):
+            a = E.add(a, E.mul(p, c))
+        if a is not None and _uniform_divide_model(a, d)[1]:
+            return pts
+    raise AssertionError("no small-order sum that meets an exception for D = %d" % d)
+
+
+def zero_sum_points(pts, cs):
+    """The last point replaced so that sum c_k P_k = O: the [1 / D] step then starts from the identity."""
+    E = o.E2
+    s = None
+    for p, c in zip(pts[:-1], cs[:-1]):
+        s = E.add(s, E.mul(p, c))
+    return pts[:-1] + [E.mul(E.neg(s), pow(cs[-1], -1, R))]
+
+
+@spec("G2_COMBINE_UNIFORM_WAVE", None, nflags=1)
+def _(case=None, out=None, flags=None, rnd=None):
+    """[+-1 / D] sum c_k P_k on EVERY lane: combine_uniform_wave recomputes the lanes whose fast form raised its flag (the select
+    under wave_any), so no job may differ.  Operands are points of G2 and the identity only: the fast form and its fallback
+    use different decompositions of D^-1 mod r (digits of psi against the quotient of |x|), equal on G2 but not outside it.
+    The one exception is a lane per generic wave whose points are multiples of one point of order 13
+    (small_order_sum_points): its reference is the model of the form that ran."""
+    if rnd is not None:
+        blocks = []
+        for i, (ids, cs, d, cls) in enumerate(uniform_wave_tuples()):
+            K = len(cs)
+            ordinary, sets = _uniform_point_sets(rnd, K)
+            sets = sets[:6] + [("sum = O", zero_sum_points(ordinary[1], cs)), ("sum = O", zero_sum_points(ordinary[2], cs))]
+            for neg in (False, True):
+                def mk(pts, tag, cs=cs, d=d, neg=neg, sub=True):
+                    return lambda: _uniform_wave_case(rnd, pts, cs, d, neg, "%s %s" % (cls, tag), sub)
+                half = sets[::2] if neg else sets[1::2]
+                directed = [mk(pts, tag) for tag, pts in half]
+                if cls in ("quotient", "ladder"):  # (the other classes have no fast [1 / D] form to repair)
+                    directed.append(mk(small_order_sum_points(K, cs, d), "sum of order 13", sub=False))
+                directed = _special_first(directed, _uniform_wave_special)
+                blocks.append(uniform_block(directed, lambda k, mk=mk: mk(ordinary[k % 3], "ordinary")(), variant=len(blocks)))
+                if i == 0 and not neg:
+                    blocks.append([directed[k % 2]() for k in range(WAVE_JOBS)])  # every job exceptional
+                    blocks.append(uniform_block([], lambda k, mk=mk: mk(ordinary[k % 3], "ordinary")()))
+        blocks.append(blocks[-1][:13])
+        return uniform_table("G2_COMBINE_UNIFORM_WAVE", blocks)
+    check_result(G2F, case, out, flags, _uniform_wave_ref(case), "combine_uniform_wave")
+
+
+UNIFORM["G2_COMBINE_UNIFORM_WAVE"] = (lambda c: (len(c.cs), tuple(c.cs), c.d, c.neg), _uniform_wave_special)
+whole_table("G2_COMBINE_UNIFORM_WAVE")
+
+
+# ---- job_combine_small_io<Fq2>: the job body of the grouped G2 combination, on bytes ------------------------------------------------
+COMBINE_IDX_AT = 4 * 192  # conformance.h kConfIdx
+COMBINE_LEFT = 0xee  # the status a job that left the fast path leaves untouched (conformance.h)
+
+
+def _combine_case(ids, shares, wave, tag):
+    parts = [(192 * k, s) for k, s in enumerate(shares)] + [(COMBINE_IDX_AT, b"".join(int(i).to_bytes(8, "little") for i in ids))]
+    return bcase(parts, [len(ids)], "wave %s: %s %s" % (wave, tag, list(ids)), ids=list(ids), shares=[bytes(s) for s in shares], wave=wave, kind=tag)
+
+
+def _combine_ref(case):
+    """None: the fast path does not take the job (nothing is written); else (status, the 192 bytes): Oracle A's combination of
+    the shares, or the identity under status 3 where a share does not decode."""
+    def ref():
+        if small_coeffs_model(case.ids) is None:
+            return None
+        pts = []
+        for s in case.shares:
+            ok, p = byte_ref(2, "unc", s)
+            if not ok:
+                return 3, IDENTITY[(2, "unc")]
+            pts.append(p)
+        return 0, o.g2_uncompressed(o.combine_signatures(len(pts) - 1, zip(case.ids, pts)))
+    return cached("combine-small", (tuple(case.ids), tuple(case.shares)), ref)
+
+
+def combine_leaves_early(case):
+    """The job is gone before the uniformity ballot of its wave: not applicable, or a share that does not decode."""
+    r = _combine_ref(case)
+    return r is None or r[0] != 0
+
+
+@spec("JOB_COMBINE_SMALL_G2", None, nflags=2)
+def _(case=None, out=None, flags=None, rnd=None):
+    """Oracle A's combination of the share bytes on every job the fast path takes; return value false and the sentinel row
+    untouched where it does not.  The waves: (a) one tuple; (b) 32 different tuples (the mixed forms run); (c) one tuple
+    except one lane; (d) one tuple with jobs that leave before the uniformity ballot -- an index of 65 535, an undecodable
+    share, a duplicate index -- as job 0 (wave_uniform must read the first lane still there), as job 31 and as every other job;
+    (e) one tuple with a share at infinity and two equal shares on some lanes."""
+    if rnd is not None:
+        pool = g2_pool()
+        enc = [o.g2_uncompressed(p) for p in pool]
+        bad = [b for _, _, b in byte_cases(2, "unc") if not byte_ref(2, "unc", b)[0]]
+        tup = {4: [0, 1, 2, 7], 3: [0, 1, 7], 2: [0, 3]}
+
+        def shares(K, i):
+            return [enc[(3 * (i % 3) + k) % len(enc)] for k in range(K)]
+
+        def ordinary(wave, K=4):
+            return lambda i: _combine_case(tup[K], shares(K, i), wave, "ordinary")
+        leavers = [lambda w, i: _combine_case([0, 1, 2, 65535], shares(4, i), w, "index 65535"),
+                   lambda w, i: _combine_case(tup[4], shares(4, i)[:2] + [bad[i % 2]] + shares(4, i)[3:], w, "undecodable share"),
+                   lambda w, i: _combine_case([0, 1, 2, 2], shares(4, i), w, "duplicate index")]
+        blocks = [[ordinary("a%d" % K, K)(i) for i in range(WAVE_JOBS)] for K in (4, 3, 2)]
+        pairs = list(itertools.combinations(range(10), 2))[:WAVE_JOBS]
+        blocks.append([_combine_case(list(s), shares(2, 0), "b", "its own tuple") for s in pairs])
+        blocks.append([_combine_case([0, 1, 2, 5], shares(4, i), "c", "the other tuple") if i == 17 else ordinary("c")(i) for i in range(WAVE_JOBS)])
+        for k, leave in enumerate(leavers):
+            blocks.append([leave("d first %d" % k, i) if i == 0 else ordinary("d first %d" % k)(i) for i in range(WAVE_JOBS)])
+        blocks.append([leavers[i % 3]("d last", i) if i >= 30 else ordinary("d last")(i) for i in range(WAVE_JOBS)])
+        blocks.append([leavers[(i // 2) % 3]("d every other", i) if i % 2 == 0 else ordinary("d every other")(i) for i in range(WAVE_JOBS)])
+        ident = IDENTITY[(2, "unc")]
+
+        def special(i):
+            s = shares(4, i)
+            if i in (0, 31, 13):
+                return _combine_case(tup[4], [ident] + s[1:], "e", "share at infinity")
+            if i in (1, 14, 30):
+                return _combine_case(tup[4], [s[0], s[0]] + s[2:], "e", "two equal shares")
+            return ordinary("e")(i)
+        blocks.append([special(i) for i in range(WAVE_JOBS)])
+        blocks.append([ordinary("tail")(i) for i in range(5)])
+        assert all(len(b) == WAVE_JOBS for b in blocks[:-1])
+        return [c for b in blocks for c in b]
+    ref = _combine_ref(case)
+    flags_agree(case, flags, 2)
+    if ref is None:
+        expect((flags[0], flags[1]) == (COMBINE_LEFT, 0), case, "left the fast path: status %d, returned %d" % (flags[0], flags[1]))
+        check_row(case, out, [], [], "job_combine_small_io (not applicable)")
+    else:
+        expect((flags[0], flags[1]) == (ref[0], 1), case, "status %d, returned %d; want %d, 1" % (flags[0], flags[1], ref[0]))
+        check_row(case, out, [(0, ref[1])], [], "job_combine_small_io")
+
+
+whole_table("JOB_COMBINE_SMALL_G2")
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -306,7 +306,10 @@ TC_HD_NOINLINE G2Jac combine_divide_uniform(const G2Jac& q, uint64_t d_abs, bool
 TC_HD_NOINLINE G2Jac combine_divide_quotient(const G2Jac& q, uint64_t d_abs, bool& exc) {
   uint64_t qq = 0;
   int64_t T[4] = {0, 0, 0, 0}, E[4] = {0, 0, 0, 0};
-  exc = exc || q.is_inf() || !combine_quotient_decompose(d_abs, &qq, T, E);
+  // (decomposed on EVERY lane, before the lane's own flags are looked at: the wave takes q, T and E from its first lane, and a
+  // first lane with q at infinity that skipped the decomposition handed zeros to all 32 jobs, which then all raised exc)
+  const bool taken = combine_quotient_decompose(d_abs, &qq, T, E);
+  exc = exc || q.is_inf() || !taken;
   TC_UNROLL for (int j = 0; j < 4; j++) {
     T[j] = (int64_t)wave_uniform((uint64_t)T[j]);
     E[j] = (int64_t)wave_uniform((uint64_t)E[j]);
