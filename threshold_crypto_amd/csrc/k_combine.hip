@@ -7,16 +7,18 @@ namespace tc {
 
 // one lane per (job, sample position): lambda_i of job j.  Jobs the small-index fast path owns are
 // skipped; the others are counted in *need_general (one atomic per wave) so that k_combine_general can
-// leave at once when there is nothing for it to do.
+// leave at once when there is nothing for it to do.  counted: an earlier launch made that count already (the G2 grouping,
+// k_combine_group) -- nothing is counted here, and with a count of zero the kernel leaves before it looks at a job.
 __global__ __launch_bounds__(kBlock, TC_WAVES_G1) void k_lagrange(const uint64_t* __restrict__ idx, size_t n_per_job, size_t t,
                                                      size_t B, uint32_t* __restrict__ lam,
-                                                     uint8_t* __restrict__ status, uint32_t* __restrict__ need_general) {
+                                                     uint8_t* __restrict__ status, uint32_t* __restrict__ need_general, bool counted) {
+  if (counted && *need_general == 0) return;
   const size_t tid = (size_t)blockIdx.x * kBlock + threadIdx.x;
   const size_t k = t + 1;
   const bool live = tid < B * k;
   const size_t j = live ? tid / k : 0, i = live ? tid % k : 0;
   const bool general = live && !combine_small_applies(idx + j * n_per_job, (int)t);
-  const uint64_t m = __builtin_amdgcn_ballot_w64(general && i == 0);
+  const uint64_t m = counted ? 0 : __builtin_amdgcn_ballot_w64(general && i == 0);
   if (m && (threadIdx.x & 63) == (unsigned)__builtin_ctzll(m)) atomicAdd(need_general, (uint32_t)__builtin_popcountll(m));
   if (!general) return;  // the fast path owns the job (or the lane is past the end)
   uint8_t st = job_lagrange(idx + j * n_per_job, (int)t, (int)i, lam + tid * 8);
@@ -157,15 +159,19 @@ __global__ __launch_bounds__(kGroupBlock) void k_combine_scatter(const uint8_t* 
 
 // ---- grouping the G2 jobs by index tuple (tc_jobs.h combine_tuple_key) --------------------------------
 // Three kernels, no host decision in between (the mode is chosen on the device):
-//   k_combine_keys    per job: its key into the open-addressing table (64-bit atomicCAS, probing bounded by the table
-//                     size), its group = the table entry, its rank inside the group (one atomic per distinct key and
-//                     wave); and, for the fallback, its denominator class and its rank inside the class
+//   k_combine_group   per job: its key, counted per workgroup in an LDS table first (tc_jobs.h combine_wg_insert); then one
+//                     lane per distinct key of the workgroup finds the key's entry in the call's table (64-bit atomicCAS,
+//                     probing bounded by the table size) and adds the workgroup's count to the entry's with ONE atomic, so a
+//                     workgroup waits for one round trip to the memory side, not for one per key; group = the entry, rank =
+//                     what that atomic returned + the rank inside the workgroup.  For the fallback, the job's denominator
+//                     class and its rank inside the class.  On the side: perm filled with the padding marker, and the jobs
+//                     the fast path leaves counted in ws[kGwsNeed]
 //   k_combine_plan    one workgroup: subset mode or class mode (tc_jobs.h combine_subset_mode), the first slot of every group
+//                     by a prefix sum per order (tc_jobs.h combine_scan_step)
 //   k_combine_place   perm[start[group] + rank] = job
-// Workspace words (ws): keys, counts, starts of the table entries, then kGwsMisc; zeroed by the launcher for every call.
-constexpr uint32_t kGwsCount = 2 * kSubsetSlots, kGwsStart = 3 * kSubsetSlots, kGwsMisc = 4 * kSubsetSlots;
-constexpr uint32_t kGwsClassCount = kGwsMisc, kGwsClassStart = kGwsMisc + 4, kGwsGroups = kGwsMisc + 8, kGwsOverflow = kGwsMisc + 9,
-                   kGwsMode = kGwsMisc + 10, kGwsZeroWords = kGwsMisc + 16;
+// No workgroup waits for another; what crosses workgroups inside a launch does so as the result of an atomic.
+// Workspace words (ws): tc_jobs.h kGws*; zeroed by the launcher for every call.
+static_assert(kGroupBlock == (int)kGroupWgJobs, "one lane per job of the workgroup");
 struct GroupWs {
   uint32_t* ws;     // kGwsZeroWords words, zeroed
   uint32_t* rank;   // B: rank inside the tuple's group
@@ -182,14 +188,24 @@ TC_D GroupWs group_ws(uint32_t* ws, size_t B) {
   g.cls = reinterpret_cast<uint8_t*>(g.crank + B + (B + 1) / 2);
   return g;
 }
-__global__ __launch_bounds__(kGroupBlock) void k_combine_keys(const uint64_t* __restrict__ idx, size_t n_per_job, size_t t, size_t B,
-                                                          uint32_t* __restrict__ ws_words) {
+__global__ __launch_bounds__(kGroupBlock) void k_combine_group(const uint64_t* __restrict__ idx, size_t n_per_job, size_t t, size_t B,
+                                                           uint32_t* __restrict__ ws_words, size_t slots, uint32_t* __restrict__ perm) {
   __shared__ uint32_t wave_count[kGroupBlock / 64][kCombineClasses];
   __shared__ uint32_t wg_base[kCombineClasses];
+  __shared__ uint64_t wkey[kGroupWgSlots];
+  __shared__ uint32_t wcount[kGroupWgSlots];
+  __shared__ uint32_t wbase[kGroupWgSlots];
+  __shared__ uint16_t wentry[kGroupWgSlots];
   const GroupWs g = group_ws(ws_words, B);
   const size_t j = (size_t)blockIdx.x * kGroupBlock + threadIdx.x;
   const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool live = j < B;
+  for (uint32_t s = threadIdx.x; s < kGroupWgSlots; s += kGroupBlock) {
+    wkey[s] = 0;
+    wcount[s] = 0;
+  }
+  // every slot of perm is padding until k_combine_place (a later launch on the stream) puts a job there
+  for (size_t i = j; i < slots; i += (size_t)gridDim.x * kGroupBlock) perm[i] = 0xffffffffu;
   int c = -1;
   const uint64_t key = live ? combine_tuple_key(idx + j * n_per_job, (int)t, &c) : 0;
   if (!live) c = -1;
@@ -206,50 +222,22 @@ __global__ __launch_bounds__(kGroupBlock) void k_combine_keys(const uint64_t* __
     for (int w = 0; w < kGroupBlock / 64; w++) total += wave_count[w][threadIdx.x];
     wg_base[threadIdx.x] = total ? atomicAdd(&g.ws[kGwsClassCount + threadIdx.x], total) : 0;
   }
+  // the key: counted in the workgroup's table, then one lane per distinct key goes to the call's table
+  uint32_t s = 0, local_rank = 0;
+  bool made = false;
+  if (live) s = combine_wg_insert(wkey, wcount, key, &local_rank, &made);
+  __syncthreads();
+  if (made) combine_wg_publish(s, wkey, wcount, wentry, wbase, g.ws);
   __syncthreads();
   if (live) {
     uint32_t pos = wg_base[c];
     for (unsigned w = 0; w < wave; w++) pos += wave_count[w][c];
     g.cls[j] = (uint8_t)c;
     g.crank[j] = pos + (uint32_t)__builtin_popcountll(mine & ((1ull << lane) - 1ull));
-  }
-  // the key's table entry
-  unsigned long long* keys = reinterpret_cast<unsigned long long*>(g.ws);
-  uint32_t h = 0;
-  bool found = false;
-  if (live && __hip_atomic_load(&g.ws[kGwsOverflow], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-    h = combine_key_hash(key) & (kSubsetSlots - 1);
-    for (uint32_t probe = 0; probe < kSubsetSlots && !found; probe++) {
-      unsigned long long cur = __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (cur == 0) {
-        cur = atomicCAS(&keys[h], 0ull, (unsigned long long)key);
-        if (cur == 0) {  // a new group
-          cur = key;
-          if (atomicAdd(&g.ws[kGwsGroups], 1u) >= kSubsetMaxGroups) atomicExch(&g.ws[kGwsOverflow], 1u);
-        }
-      }
-      if (cur == key) found = true;
-      else h = (h + 1) & (kSubsetSlots - 1);
+    if (wentry[s] < kSubsetSlots) {
+      g.grp[j] = wentry[s];
+      g.rank[j] = wbase[s] + local_rank;
     }
-    if (!found) atomicExch(&g.ws[kGwsOverflow], 1u);  // the table is full
-  }
-  // rank inside the group: the lanes of the wave that hold one key share one atomic
-  uint32_t rank = 0;
-  uint64_t todo = __builtin_amdgcn_ballot_w64(found);
-  while (todo) {
-    const int leader = __builtin_ctzll(todo);
-    const uint32_t hl = (uint32_t)__builtin_amdgcn_readlane((int)h, leader);
-    const bool same = found && h == hl;
-    const uint64_t m = __builtin_amdgcn_ballot_w64(same);
-    uint32_t base = 0;
-    if ((int)lane == leader) base = atomicAdd(&g.ws[kGwsCount + hl], (uint32_t)__builtin_popcountll(m));
-    base = (uint32_t)__builtin_amdgcn_readlane((int)base, leader);
-    if (same) rank = base + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
-    todo &= ~m;
-  }
-  if (found) {
-    g.grp[j] = (uint16_t)h;
-    g.rank[j] = rank;
   }
 }
 __global__ __launch_bounds__(kSubsetSlots) void k_combine_plan(size_t t, size_t B, uint32_t* __restrict__ ws_words) {
@@ -257,6 +245,7 @@ __global__ __launch_bounds__(kSubsetSlots) void k_combine_plan(size_t t, size_t 
   __shared__ uint8_t order[kSubsetSlots];
   __shared__ uint32_t ccount[kCombineClasses];
   __shared__ uint8_t corder[kCombineClasses];
+  __shared__ __attribute__((aligned(16))) uint32_t scan[2 * kSubsetSlots * kGroupOrders];
   const uint32_t s = threadIdx.x;
   const unsigned long long key = reinterpret_cast<const unsigned long long*>(ws_words)[s];
   count[s] = ws_words[kGwsCount + s];
@@ -267,7 +256,11 @@ __global__ __launch_bounds__(kSubsetSlots) void k_combine_plan(size_t t, size_t 
   }
   __syncthreads();
   const bool subset = combine_subset_mode(ws_words[kGwsOverflow] != 0, ws_words[kGwsGroups], B);
-  ws_words[kGwsStart + s] = subset ? combine_group_start(count, order, kSubsetSlots, s, kSubsetPad) : 0;
+  for (int step = 0; step < combine_scan_steps(kSubsetSlots); step++) {
+    combine_scan_step(step, s, kSubsetSlots, count, order, kSubsetPad, scan);
+    __syncthreads();
+  }
+  ws_words[kGwsStart + s] = subset ? combine_scan_start(s, kSubsetSlots, count, order, kSubsetPad, scan) : 0;
   if (s < kCombineClasses) ws_words[kGwsClassStart + s] = combine_group_start(ccount, corder, kCombineClasses, s, kClassPad);
   if (s == 0) ws_words[kGwsMode] = subset ? 1u : 0u;
 }
@@ -396,9 +389,9 @@ void launch_lincomb_g1(hipStream_t st, size_t n, const uint8_t* scalars, const u
 }
 
 void launch_lagrange(hipStream_t st, const uint64_t* idx, size_t n_per_job, size_t t, size_t B, uint32_t* lam,
-                     uint8_t* status, uint32_t* need_general) {
+                     uint8_t* status, uint32_t* need_general, bool counted) {
   const size_t n = B * (t + 1);
-  if (n) hipLaunchKernelGGL(k_lagrange, dim3(grid_for(n)), dim3(kBlock), 0, st, idx, n_per_job, t, B, lam, status, need_general);
+  if (n) hipLaunchKernelGGL(k_lagrange, dim3(grid_for(n)), dim3(kBlock), 0, st, idx, n_per_job, t, B, lam, status, need_general, counted);
 }
 void launch_fr_idx_narrow(hipStream_t st, const uint32_t* idx_fr, size_t n_per_job, size_t take, size_t B, uint64_t* idx64, uint32_t* wide,
                           uint8_t* valid) {
@@ -457,10 +450,12 @@ size_t combine_group_slots(size_t B) { return B + (size_t)kCombineClasses * kCom
 // G2: every group padded to a whole wave -- at most kSubsetMaxGroups of them in subset mode, the classes otherwise
 size_t combine_group_slots_g2(size_t B) { return B + (size_t)kSubsetMaxGroups * (kSubsetPad - 1); }
 size_t combine_group_ws_words(size_t B) { return (size_t)kGwsZeroWords + 2 * B + (B + 1) / 2 + (B + 3) / 4; }
+uint32_t* combine_group_need(uint32_t* gws) { return gws ? gws + kGwsNeed : nullptr; }
 // gws: combine_group_ws_words(B) words, perm: combine_group_slots_g2(B) words (scratch of the caller, 8-byte aligned); pass
-// perm = nullptr to run the jobs in their own order
+// perm = nullptr to run the jobs in their own order.  With both, the grouping counts the jobs the fast path leaves in
+// combine_group_need(gws) and the Lagrange stage of the call is launched HERE, behind that count (the caller launches none)
 void launch_combine_g2(hipStream_t st, TableArena ta, size_t t, size_t n_per_job, const uint64_t* idx, const uint8_t* shares,
-                       const uint32_t* lam, size_t B, uint8_t* out, uint8_t* status, uint32_t* gws,
+                       uint32_t* lam, size_t B, uint8_t* out, uint8_t* status, uint32_t* gws,
                        uint32_t* perm, const uint32_t* need_general, hipEvent_t before_main) {
   if (!B || !ta.mem || !ta.flags) return;
   if (t >= 1 && t <= 3) {
@@ -468,11 +463,11 @@ void launch_combine_g2(hipStream_t st, TableArena ta, size_t t, size_t n_per_job
     if (perm && gws) {
       slots = combine_group_slots_g2(B);
       (void)hipMemsetAsync(gws, 0, kGwsZeroWords * sizeof(uint32_t), st);
-      (void)hipMemsetAsync(perm, 0xff, slots * sizeof(uint32_t), st);
       const unsigned gb = (unsigned)((B + kGroupBlock - 1) / kGroupBlock);
-      hipLaunchKernelGGL(k_combine_keys, dim3(gb), dim3(kGroupBlock), 0, st, idx, n_per_job, t, B, gws);
+      hipLaunchKernelGGL(k_combine_group, dim3(gb), dim3(kGroupBlock), 0, st, idx, n_per_job, t, B, gws, slots, perm);
       hipLaunchKernelGGL(k_combine_plan, dim3(1), dim3(kSubsetSlots), 0, st, t, B, gws);
       hipLaunchKernelGGL(k_combine_place, dim3(gb), dim3(kGroupBlock), 0, st, B, gws, slots, perm);
+      launch_lagrange(st, idx, n_per_job, t, B, lam, status, combine_group_need(gws), /*counted=*/true);
     } else {
       perm = nullptr;
     }

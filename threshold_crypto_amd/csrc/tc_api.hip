@@ -824,12 +824,15 @@ static void combine_launch(Call& k, bool g2, size_t t, size_t n, const uint64_t*
   // the cheap forms of the final division (tc_jobs.h combine_divide); not worth three launches for a
   // batch that fills a fraction of the machine anyway
   const bool group = !d_idx_fr && t >= 1 && t <= 3 && (g2 ? B >= 4096 : B >= tc::kG1GroupMinJobs);
-  // (G2 groups by index tuple, or by class where the tuples are too many: k_combine.hip k_combine_keys)
+  // (G2 groups by index tuple, or by class where the tuples are too many: k_combine.hip k_combine_group)
   uint8_t* d_cls = group && !g2 ? k.temp<uint8_t>(B) : nullptr;
   uint32_t* d_counters = group && !g2 ? k.temp<uint32_t>(8) : nullptr;
   uint32_t* d_gws = group && g2 ? k.temp<uint32_t>(tc::combine_group_ws_words(B)) : nullptr;
   uint32_t* d_perm = group ? k.temp<uint32_t>(g2 ? tc::combine_group_slots_g2(B) : tc::combine_group_slots(B)) : nullptr;
-  uint32_t* d_need = (t > 0 && !d_idx_fr) ? k.temp<uint32_t>(1, /*zero=*/true) : nullptr;
+  // the count of the jobs the fast path leaves: a word of the grouping's workspace where G2 groups (k_combine_group counts
+  // them, and launch_combine_g2 runs the Lagrange stage behind it), a zeroed word the Lagrange stage counts in otherwise
+  const bool counted = group && g2;
+  uint32_t* d_need = counted ? tc::combine_group_need(d_gws) : (t > 0 && !d_idx_fr) ? k.temp<uint32_t>(1, /*zero=*/true) : nullptr;
   if (k.failed) return;
   if (d_idx_fr) {
     // `T: IntoFr` abscissae beyond u64 (src/into_fr.rs:10-14, 28-56): no small-index fast path, no integer differences
@@ -843,7 +846,7 @@ static void combine_launch(Call& k, bool g2, size_t t, size_t n, const uint64_t*
   if (t + 1 >= tc::kMsmMinPoints) {
     uint32_t* d_ws = k.temp<uint32_t>(tc::lagrange_all_ws_words(t, B));
     if (!k.failed) tc::launch_lagrange_all(ctx->stream, d_idx, n, t, B, d_lam, d_ws, d_st);
-  } else if (t > 0) {
+  } else if (t > 0 && !counted) {
     tc::launch_lagrange(ctx->stream, d_idx, n, t, B, d_lam, d_st, d_need);
   }
   if (g2 && t + 1 >= tc::kMsmMinPoints) {

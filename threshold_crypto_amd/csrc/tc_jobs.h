@@ -559,6 +559,126 @@ TC_HD uint32_t combine_group_start(const uint32_t* count, const uint8_t* order, 
   return start;
 }
 
+// ---- the pieces of the grouping kernels (k_combine.hip k_combine_group / k_combine_plan) ------------------------------
+// Written over arrays so that g++ runs them too (tests/group): on the device the arrays are LDS and the call's workspace and
+// the accesses below are atomics; on the host one thread runs the jobs one after the other and they are plain accesses.
+#if defined(__HIP_DEVICE_COMPILE__)
+TC_HD uint64_t group_cas64(uint64_t* p, uint64_t expect, uint64_t val) {
+  return (uint64_t)atomicCAS(reinterpret_cast<unsigned long long*>(p), (unsigned long long)expect, (unsigned long long)val);
+}
+TC_HD uint32_t group_add32(uint32_t* p, uint32_t v) { return atomicAdd(p, v); }
+TC_HD void group_set32(uint32_t* p, uint32_t v) { atomicExch(p, v); }
+TC_HD uint32_t group_load32(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+TC_HD uint64_t group_load64(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+#else
+TC_HD uint64_t group_cas64(uint64_t* p, uint64_t expect, uint64_t val) {
+  const uint64_t cur = *p;
+  if (cur == expect) *p = val;
+  return cur;
+}
+TC_HD uint32_t group_add32(uint32_t* p, uint32_t v) {
+  const uint32_t cur = *p;
+  *p = cur + v;
+  return cur;
+}
+TC_HD void group_set32(uint32_t* p, uint32_t v) { *p = v; }
+TC_HD uint32_t group_load32(const uint32_t* p) { return *p; }
+TC_HD uint64_t group_load64(const uint64_t* p) { return *p; }
+#endif
+// The call's workspace, in words (zeroed by the launcher for every call): the table's keys (64 bits each), the jobs per entry,
+// the first slot per entry, then single words.  kGwsNeed: the jobs the fast path leaves (key "none"), for the Lagrange stage
+// and the two-stage kernels behind it.
+constexpr uint32_t kGwsCount = 2 * kSubsetSlots, kGwsStart = 3 * kSubsetSlots, kGwsMisc = 4 * kSubsetSlots;
+constexpr uint32_t kGwsClassCount = kGwsMisc, kGwsClassStart = kGwsMisc + 4, kGwsGroups = kGwsMisc + 8, kGwsOverflow = kGwsMisc + 9,
+                   kGwsMode = kGwsMisc + 10, kGwsNeed = kGwsMisc + 11, kGwsZeroWords = kGwsMisc + 16;
+// A workgroup takes kGroupWgJobs jobs and first counts them per key in a table of its own (twice as many entries as jobs, so a
+// probe always meets the key or an empty entry); then ONE lane per distinct key does the key's work on the call's table.
+constexpr uint32_t kGroupWgJobs = 256;
+constexpr uint32_t kGroupWgSlots = 2 * kGroupWgJobs;
+// (bits of the hash the call's table does not use: keys that meet there are spread here)
+TC_HD uint32_t combine_wg_hash(uint64_t key) { return (combine_key_hash(key) >> 9) & (kGroupWgSlots - 1); }
+// One job's step (wkey / wcount: kGroupWgSlots zeroed entries): the entry of its key, its rank among the workgroup's jobs of
+// that key, and whether this job made the entry -- the job that did is the key's lane in combine_wg_publish.
+TC_HD uint32_t combine_wg_insert(uint64_t* wkey, uint32_t* wcount, uint64_t key, uint32_t* local_rank, bool* made) {
+  uint32_t s = combine_wg_hash(key);
+  *made = false;
+  for (uint32_t probe = 0; probe < kGroupWgSlots; probe++) {
+    const uint64_t cur = group_cas64(&wkey[s], 0ull, key);
+    if (cur == 0) *made = true;
+    if (cur == 0 || cur == key) break;
+    s = (s + 1) & (kGroupWgSlots - 1);
+  }
+  *local_rank = group_add32(&wcount[s], 1u);
+  return s;
+}
+// The probe of the call's table starts at the low bits of the hash and advances by an odd step taken from its top bits (every
+// entry is visited once in kSubsetSlots steps).  The keys are small indices in 16-bit fields and the low bits of their hashes
+// cluster: the 210 four-subsets of ten signers start at 123 entries, and one entry further per step left the last key 41
+// steps from home -- every step a dependent round trip to memory, and with every workgroup of a launch inserting into the
+// empty table at once a run grows one key per round trip.  With a step of its own per key the longest probe of that batch
+// is 6 steps; k_combine_group took 0.084 ms with the one and 0.041 ms with the other (profiles/combine_group_ab.txt).
+TC_HD uint32_t combine_probe_step(uint64_t key) { return ((combine_key_hash(key) >> 15) & (kSubsetSlots - 1)) | 1u; }
+// The key's entry in the call's table: open addressing, the probing bounded by the table's size.  kSubsetSlots when there is
+// none (the table is full, or an earlier key closed it); more than kSubsetMaxGroups keys, or a full table, raise the overflow
+// flag -- the plan then orders the jobs by class and no entry is used.
+TC_HD uint32_t combine_table_entry(uint32_t* ws, uint64_t key) {
+  uint64_t* keys = reinterpret_cast<uint64_t*>(ws);
+  if (group_load32(&ws[kGwsOverflow]) != 0) return kSubsetSlots;
+  uint32_t h = combine_key_hash(key) & (kSubsetSlots - 1);
+  const uint32_t step = combine_probe_step(key);
+  for (uint32_t probe = 0; probe < kSubsetSlots; probe++) {
+    uint64_t cur = group_load64(&keys[h]);
+    if (cur == 0) {
+      cur = group_cas64(&keys[h], 0ull, key);
+      if (cur == 0) {  // a new group
+        cur = key;
+        if (group_add32(&ws[kGwsGroups], 1u) >= kSubsetMaxGroups) group_set32(&ws[kGwsOverflow], 1u);
+      }
+    }
+    if (cur == key) return h;
+    h = (h + step) & (kSubsetSlots - 1);
+  }
+  group_set32(&ws[kGwsOverflow], 1u);  // the table is full
+  return kSubsetSlots;
+}
+// The lane that made entry s of the workgroup's table, once every job of the workgroup is counted: the key's entry in the
+// call's table and, with ONE addition of the workgroup's count, the rank of the workgroup's first job of the key.
+TC_HD void combine_wg_publish(uint32_t s, const uint64_t* wkey, const uint32_t* wcount, uint16_t* wentry, uint32_t* wbase, uint32_t* ws) {
+  const uint64_t key = wkey[s];
+  if (key == kTupleKeyNone) group_add32(&ws[kGwsNeed], wcount[s]);
+  const uint32_t h = combine_table_entry(ws, key);
+  wentry[s] = (uint16_t)h;
+  wbase[s] = h < kSubsetSlots ? group_add32(&ws[kGwsCount + h], wcount[s]) : 0;
+}
+
+// combine_group_start for every group at once, as a prefix sum per order instead of n walks over n counts.  These are the
+// steps of n threads with a barrier after each (the host runs step after step, thread after thread); buf: 2 n rows of
+// kGroupOrders words.
+//   step 0                     row s = the padded size of group s in the column of its order, zero in the others
+//   step k = 1 .. L, 2^L >= n  row s of this step = row s + row s - 2^(k-1) of the step before (the two halves of buf alternate)
+//   combine_scan_start         the totals of the orders before the group's own + what its own column holds in front of it
+TC_HD int combine_scan_steps(uint32_t n) {
+  int L = 0;
+  while ((1u << L) < n) L++;
+  return L + 1;
+}
+TC_HD void combine_scan_step(int step, uint32_t s, uint32_t n, const uint32_t* count, const uint8_t* order, uint32_t pad, uint32_t* buf) {
+  if (step == 0) {
+    for (int o = 0; o < kGroupOrders; o++) buf[s * kGroupOrders + o] = (int)order[s] == o ? (count[s] + pad - 1) / pad * pad : 0;
+    return;
+  }
+  const uint32_t d = 1u << (step - 1);
+  const uint32_t* src = buf + (size_t)((step - 1) & 1) * n * kGroupOrders;
+  uint32_t* dst = buf + (size_t)(step & 1) * n * kGroupOrders;
+  for (int o = 0; o < kGroupOrders; o++) dst[s * kGroupOrders + o] = src[s * kGroupOrders + o] + (s >= d ? src[(s - d) * kGroupOrders + o] : 0);
+}
+TC_HD uint32_t combine_scan_start(uint32_t s, uint32_t n, const uint32_t* count, const uint8_t* order, uint32_t pad, const uint32_t* buf) {
+  const uint32_t* sum = buf + (size_t)((combine_scan_steps(n) - 1) & 1) * n * kGroupOrders;  // inclusive sums, where the last step left them
+  uint32_t start = sum[s * kGroupOrders + order[s]] - (count[s] + pad - 1) / pad * pad;
+  for (int o = 0; o < (int)order[s]; o++) start += sum[(n - 1) * kGroupOrders + o];
+  return start;
+}
+
 // out = sum_{i <= t} lambda_i * share_i over the FIRST t+1 samples of the job
 // (interpolate, src/lib.rs:719-767).  lam: (t+1) x 8 canonical words from job_lagrange.
 // t == 0: the first sample is returned unchanged (src/lib.rs:735-737) -- decoded and encoded again, so a bad encoding fails

@@ -101,9 +101,10 @@ void launch_decompress_take(const Tuning& tn, hipStream_t st, bool g2, const uin
 void launch_take_u64(hipStream_t st, const uint64_t* in, size_t n_per_job, size_t take, size_t B, uint64_t* out);
 
 // need_general: one zeroed device word; the Lagrange stage counts the jobs the small-index fast path
-// does not take, the general combine kernel leaves at once when it stays zero (k_combine.hip)
+// does not take, the general combine kernel leaves at once when it stays zero (k_combine.hip).  counted: the word holds
+// that count already (launch_combine_g2's grouping made it): nothing is added, and zero ends the kernel at once
 void launch_lagrange(hipStream_t st, const uint64_t* idx, size_t n_per_job, size_t t, size_t B, uint32_t* lam,
-                     uint8_t* status, uint32_t* need_general);
+                     uint8_t* status, uint32_t* need_general, bool counted = false);
 // every coefficient of a job from ONE lane with one inversion (large thresholds); ws: lagrange_all_ws_words
 size_t lagrange_all_ws_words(size_t t, size_t B);
 void launch_lagrange_all(hipStream_t st, const uint64_t* idx, size_t n_per_job, size_t t, size_t B, uint32_t* lam, uint32_t* ws,
@@ -128,11 +129,14 @@ void launch_fr_idx_narrow(hipStream_t st, const uint32_t* idx_fr, size_t n_per_j
 void launch_lagrange_fr(hipStream_t st, const uint32_t* idx_fr, size_t n_per_job, size_t t, size_t B, uint32_t* lam, uint8_t* status);
 size_t combine_group_slots(size_t B);
 // G2 groups its fast-path jobs by index tuple (k_combine.hip): gws = combine_group_ws_words(B) words and perm =
-// combine_group_slots_g2(B) words of the caller's scratch, both or neither
+// combine_group_slots_g2(B) words of the caller's scratch, both or neither.  With both the launch also counts the jobs the
+// fast path leaves, in the word combine_group_need(gws) of the workspace, and launches the call's Lagrange stage itself
+// (launch_lagrange, counted) -- the caller launches none and hands that word to what runs behind (MsmFilter::need)
 size_t combine_group_slots_g2(size_t B);
 size_t combine_group_ws_words(size_t B);
+uint32_t* combine_group_need(uint32_t* gws);
 void launch_combine_g2(hipStream_t st, TableArena ta, size_t t, size_t n_per_job, const uint64_t* idx, const uint8_t* shares,
-                       const uint32_t* lam, size_t B, uint8_t* out, uint8_t* status, uint32_t* gws,
+                       uint32_t* lam, size_t B, uint8_t* out, uint8_t* status, uint32_t* gws,
                        uint32_t* perm, const uint32_t* need_general, hipEvent_t before_main = nullptr);
 // shared_points: every job combines the SAME n points (points holds n of them) with its own n scalars
 void launch_lincomb_g1(hipStream_t st, size_t n, const uint8_t* scalars, const uint8_t* points, size_t B, uint8_t* out,
