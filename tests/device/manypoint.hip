@@ -1,7 +1,7 @@
 // Many-point conformance harness (test code only: never linked into libtc_amd.so, never run by bench.py).
 // Includes the product's kernel units k_msm.hip and k_comb.hip as they are (every unit of the product is self-contained:
 // -fno-gpu-rdc), so the __global__ kernels launched here are the product's own text, compiled with the product's flags.
-// Three entries; each allocates, copies in, launches, synchronises once, copies out, frees and returns the first HIP
+// Five entries; each allocates, copies in, launches, synchronises once, copies out, frees and returns the first HIP
 // error.  `parts` / `share` = 0 goes through the product's launcher (its own rule for the launch geometry); another value
 // launches the stage kernels directly with that value.  Tables, codes, outputs and written-only status bytes are filled
 // with 0x5A before the launch, so the caller sees what the kernels left in memory -- and what they did not touch.
@@ -10,6 +10,7 @@
 #include "../../threshold_crypto_amd/csrc/k_msm.hip"
 #include "../../threshold_crypto_amd/csrc/k_comb.hip"
 
+#include <string.h>
 #include <vector>
 
 using namespace tc;
@@ -175,4 +176,56 @@ extern "C" int mp_comb(const uint8_t* sk, size_t N, const uint64_t* idx, const u
   bool leak = false;
   for (size_t i = 0; d.e == hipSuccess && i < fl.size(); i++) leak = leak || fl[i] != 0;
   return d.e == hipSuccess && leak ? kMpSlotLeak : (int)d.e;
+}
+
+// The ragged sums (k_rec_tables_g2 / k_rec_ladder_g2, w = 2; k_rec_tables_g1 / k_rec_ladder_g1, w = 1) through their launchers, the
+// only route to these kernels: `parts` goes in by value, legal or not.  J segments of one record array (seg_first: J + 1
+// values); first_chunk_out (J + 1) is rec_chunk_ranges' answer.  out: (J + 1) rows, status: J bytes, tbl: rec_table_bytes and
+// codes: rec_code_bytes of the launch's chunks AND ONE MORE (the guard rows / chunk behind them come back as they were filled).
+extern "C" int mp_rec_sum(int w, size_t J, const uint64_t* seg_first, const uint8_t* points, const uint32_t* scalars, const uint8_t* status_in,
+                          int nbits, size_t parts, uint8_t* out, uint8_t* status, int32_t* tbl, uint8_t* codes, uint64_t* first_chunk_out) {
+  const bool g2 = w == 2;
+  if ((w != 1 && w != 2) || nbits < 2 || nbits > (g2 ? 64 : 128) || (!g2 && (nbits & 1))) return (int)hipErrorInvalidValue;
+  for (size_t j = 0; j < J; j++)
+    if (seg_first[j + 1] < seg_first[j]) return (int)hipErrorInvalidValue;
+  std::vector<uint64_t> fc(J + 1);
+  const uint64_t chunks = rec_chunk_ranges(seg_first, J, fc.data());
+  memcpy(first_chunk_out, fc.data(), (J + 1) * 8);
+  const size_t R = (size_t)seg_first[J], pt = g2 ? 192 : 96;
+  const size_t tb = rec_table_bytes(g2, chunks + 1), cb = rec_code_bytes(chunks + 1), ob = (J + 1) * pt;
+  Dev d;
+  const uint8_t* dpts = (const uint8_t*)d.upload(points, R * pt);
+  const uint32_t* dsc = (const uint32_t*)d.upload(scalars, R * 32);
+  const uint64_t* dseg = (const uint64_t*)d.upload(seg_first, (J + 1) * 8);
+  const uint64_t* dfc = (const uint64_t*)d.upload(fc.data(), (J + 1) * 8);
+  uint8_t* dst = (uint8_t*)d.upload(status_in, J);
+  uint8_t* dout = (uint8_t*)d.alloc(ob, kMpPoison);
+  int32_t* dtbl = (int32_t*)d.alloc(tb, kMpPoison);
+  uint8_t* dcodes = (uint8_t*)d.alloc(cb, kMpPoison);
+  if (d.e == hipSuccess) {
+    if (g2) launch_rec_sum_g2(0, dpts, dsc, dseg, dfc, J, chunks, parts, dtbl, dcodes, dout, dst, nbits);
+    else launch_rec_sum_g1(0, dpts, dsc, dseg, dfc, J, chunks, parts, dtbl, dcodes, dout, dst, nbits);
+    d.after_launch();
+  }
+  d.sync();
+  d.download(out, dout, ob);
+  d.download(status, dst, J);
+  d.download(tbl, dtbl, tb);
+  d.download(codes, dcodes, cb);
+  return (int)d.e;
+}
+
+// k_rec_gather_keys through its launcher: pks (K x 96), key_idx (R), keys (R x 96 and 96 guard bytes behind them)
+extern "C" int mp_rec_gather_keys(const uint8_t* pks, size_t K, const uint64_t* key_idx, size_t R, uint8_t* keys) {
+  Dev d;
+  const uint8_t* dpk = (const uint8_t*)d.upload(pks, K * 96);
+  const uint64_t* didx = (const uint64_t*)d.upload(key_idx, R * 8);
+  uint8_t* dkeys = (uint8_t*)d.alloc(R * 96 + 96, kMpPoison);
+  if (d.e == hipSuccess) {
+    launch_rec_gather_keys(0, dpk, K, didx, R, dkeys);
+    d.after_launch();
+  }
+  d.sync();
+  d.download(keys, dkeys, R * 96 + 96);
+  return (int)d.e;
 }

@@ -8,6 +8,7 @@
 // Test code only: never linked into libtc_amd.so.
 #include "../../threshold_crypto_amd/csrc/tc_msm.h"
 #include "../../threshold_crypto_amd/csrc/tc_comb.h"
+#include "../../threshold_crypto_amd/csrc/tc_records.h"
 
 #include <stdio.h>
 #include <string.h>
@@ -27,6 +28,68 @@ J merge(std::vector<J> r, size_t parts) {
     r = nr;
   }
   return r[0];
+}
+// what differs between the two groups in the ragged sums (k_rec_*_g2 / k_rec_*_g1)
+struct RecG2 {
+  using Jac = G2Jac;
+  static constexpr size_t kPoint = 192, kEntry = kMsmEntryWords, kMost = 32;
+  static bool tables(size_t n, size_t c, const uint8_t* p, const uint32_t* k, int32_t* t, uint8_t* cd, int nbits) {
+    return job_msm_tables(n, c, p, k, t, cd, true, nbits);
+  }
+  static Jac ladder(size_t n, const int32_t* t, const uint8_t* cd, int nbits, MsmPart part) { return job_msm_ladder_part<true>(n, t, cd, nbits, part); }
+  static void encode(const Jac& r, uint8_t* o) { g2_encode_uncompressed(jac_to_affine(r), o); }
+};
+struct RecG1 {
+  using Jac = G1Jac;
+  static constexpr size_t kPoint = 96, kEntry = kMsmEntryWordsG1, kMost = 64;
+  static bool tables(size_t n, size_t c, const uint8_t* p, const uint32_t* k, int32_t* t, uint8_t* cd, int nbits) {
+    return job_msm_tables_g1(n, c, p, k, t, cd, nbits, true);
+  }
+  static Jac ladder(size_t n, const int32_t* t, const uint8_t* cd, int nbits, MsmPart part) {
+    return job_msm_ladder_g1_part<true>(n, t, cd, part, nbits / 2);
+  }
+  static void encode(const Jac& r, uint8_t* o) { g1_encode_uncompressed(jac_to_affine(r), o); }
+};
+// launch_rec_sum_g2 / _g1 as the kernels run it: stage T chunk by chunk, stage L wave by wave (kMost / parts segments per wave,
+// one trip count per wave), the parts of a segment one after the other, the `none` select, the xor tree.
+template <class G>
+void rec_sum(size_t J, const uint64_t* seg_first, const uint8_t* points, const uint32_t* scalars, int nbits, size_t parts, uint8_t* out,
+             uint8_t* status, int32_t* tbl, uint8_t* codes, const uint64_t* first_chunk) {
+  const uint64_t chunks = first_chunk[J];
+  if (!J || !chunks) return;
+  if (parts < 1 || parts > G::kMost || (parts & (parts - 1))) parts = 1;
+  for (uint64_t c = 0; c < chunks; c++) {
+    const size_t j = rec_segment_of_chunk(first_chunk, J, c);
+    const uint64_t r0 = seg_first[j], len = seg_first[j + 1] - r0, p0 = first_chunk[j] * kMsmChunk;
+    const bool ok = G::tables((size_t)len, (size_t)(c - first_chunk[j]), points + r0 * G::kPoint, scalars + r0 * 8, tbl + p0 * 8 * G::kEntry,
+                              codes + p0 * kMsmColumns, nbits);
+    if (!ok && status[j] == TC_JOB_OK) status[j] = TC_JOB_INVALID_ENCODING;
+  }
+  const size_t per_wave = G::kMost / parts;
+  for (size_t j0 = 0; j0 < J; j0 += per_wave) {
+    const size_t j1 = j0 + per_wave < J ? j0 + per_wave : J;
+    std::vector<uint64_t> len(j1 - j0, 0), p0(j1 - j0, 0);
+    uint64_t trips = 0;  // (the lanes behind the last segment bring len = 0)
+    for (size_t j = j0; j < j1; j++) {
+      if (status[j] == TC_JOB_OK) {
+        len[j - j0] = seg_first[j + 1] - seg_first[j];
+        p0[j - j0] = len[j - j0] ? first_chunk[j] * kMsmChunk : 0;
+      }
+      const uint64_t t = rec_part_trips(len[j - j0], parts);
+      trips = t > trips ? t : trips;
+    }
+    for (size_t j = j0; j < j1; j++) {
+      const uint64_t l = len[j - j0], p = p0[j - j0];
+      std::vector<typename G::Jac> r(parts);
+      for (size_t g = 0; g < parts; g++) {
+        const RecPart rp = rec_part(l, g, parts);
+        const bool none = rp.s0 >= rp.s1;
+        r[g] = G::ladder(l ? (size_t)l : 1, tbl + p * 8 * G::kEntry, codes + p * kMsmColumns, nbits, MsmPart{(size_t)rp.s0, (size_t)rp.s1, (size_t)trips});
+        r[g] = G::Jac::select(none, G::Jac::infinity(), r[g]);
+      }
+      G::encode(merge(r, parts), out + j * G::kPoint);
+    }
+  }
 }
 }  // namespace
 
@@ -102,6 +165,36 @@ int mph_comb(const uint8_t* sk, size_t N, const uint64_t* idx, const uint8_t* pt
   return 0;
 }
 
+// The ragged sums: J segments of one record array (seg_first: J + 1 values), out (J x 96 / 192 and whatever the caller keeps behind
+// them), status (J), tbl / codes (the launch's chunks and whatever the caller keeps behind them), first_chunk (J + 1, written).
+int mph_rec_sum(int w, size_t J, const uint64_t* seg_first, const uint8_t* points, const uint32_t* scalars, const uint8_t* status_in, int nbits,
+                size_t parts, uint8_t* out, uint8_t* status, int32_t* tbl, uint8_t* codes, uint64_t* first_chunk) {
+  memcpy(status, status_in, J);
+  rec_chunk_ranges(seg_first, J, first_chunk);
+  if (w == 2) rec_sum<RecG2>(J, seg_first, points, scalars, nbits, parts, out, status, tbl, codes, first_chunk);
+  else rec_sum<RecG1>(J, seg_first, points, scalars, nbits, parts, out, status, tbl, codes, first_chunk);
+  return 0;
+}
+// k_rec_gather_keys: keys (R x 96 and whatever the caller keeps behind them)
+int mph_rec_gather_keys(const uint8_t* pks, size_t K, const uint64_t* key_idx, size_t R, uint8_t* keys) {
+  for (size_t r = 0; r < R; r++) {
+    if (key_idx[r] < K) memcpy(keys + r * 96, pks + (size_t)key_idx[r] * 96, 96);
+    else memset(keys + r * 96, 0xff, 96);
+  }
+  return 0;
+}
+void mph_rec_part(uint64_t len, size_t g, size_t parts, uint64_t* out3) {
+  const RecPart p = rec_part(len, g, parts);
+  out3[0] = p.s0;
+  out3[1] = p.s1;
+  out3[2] = rec_part_trips(len, parts);
+}
+// out3: table bytes in G2, in G1, code bytes of a launch of `chunks` chunks (k_msm.hip rec_table_bytes / rec_code_bytes)
+void mph_rec_sizes(uint64_t chunks, size_t* out3) {
+  out3[0] = (size_t)chunks * kMsmChunk * 8 * kMsmEntryWords * sizeof(int32_t);
+  out3[1] = (size_t)chunks * kMsmChunk * 8 * kMsmEntryWordsG1 * sizeof(int32_t);
+  out3[2] = (size_t)chunks * kMsmChunk * kMsmColumns;
+}
 void mph_msm_part(size_t n, size_t g, size_t parts, size_t* out3) {
   const MsmPart p = msm_part(n, g, parts);
   out3[0] = p.s0;
@@ -181,6 +274,42 @@ int main() {
   sc[0] = 2;  // an even short scalar fails its job
   rc |= mph_msm_g2(n, B, n * 192, p2.data(), sc.data(), st0.data(), 16, 1, nullptr, 0, 0, -1, o2.data(), st.data(), t2.data(), codes.data());
   rc |= (st[0] == TC_JOB_INVALID_ENCODING && st[1] == TC_JOB_OK && o2[0] == 0x40) ? 0 : 1;
+  // ragged sums, one case per group: segments of 0, 1, 5, 0, 2 and 3 records over the points and (short, odd) scalars above;
+  // every split gives the bytes of parts = 1, empty segments give the identity, [1] P = P
+  {
+    const uint64_t seg[7] = {0, 0, 1, 6, 6, 8, 11};
+    const size_t J = 6;
+    std::vector<uint64_t> fc(J + 1);
+    std::vector<uint8_t> st6(J), z6(J, 0);
+    for (size_t i = 0; i < B * n; i++) fr_words(2 * i + 1, sc.data() + i * 8);
+    for (int w = 1; w <= 2; w++) {
+      const size_t pt = w == 2 ? 192 : 96;
+      const uint64_t C = 5;  // 0 + 1 + 2 + 0 + 1 + 1 chunks, and one more behind them that must stay as it is
+      size_t rs[3];
+      mph_rec_sizes(C + 1, rs);
+      std::vector<int32_t> tb(rs[w == 2 ? 0 : 1] / 4);
+      std::vector<uint8_t> cd(rs[2]), ro(J * pt), ro1(J * pt);
+      const uint8_t* pp = w == 2 ? p2.data() : p1.data();
+      for (size_t parts : {(size_t)1, (size_t)2, (size_t)8, (size_t)32, (size_t)3}) {
+        std::fill(tb.begin(), tb.end(), 0x5A5A5A5A);
+        std::fill(cd.begin(), cd.end(), (uint8_t)0x5A);
+        rc |= mph_rec_sum(w, J, seg, pp, sc.data(), z6.data(), w == 2 ? 16 : 32, parts, parts == 1 ? ro1.data() : ro.data(), st6.data(), tb.data(),
+                          cd.data(), fc.data());
+        for (size_t j = 0; j < J; j++) rc |= st6[j];
+        rc |= fc[J] == C ? 0 : 1;
+        if (parts != 1) rc |= memcmp(ro.data(), ro1.data(), ro.size()) ? 1 : 0;
+        for (size_t i = tb.size() / (C + 1) * C; i < tb.size(); i++) rc |= tb[i] == 0x5A5A5A5A ? 0 : 1;
+        for (size_t i = cd.size() / (C + 1) * C; i < cd.size(); i++) rc |= cd[i] == 0x5A ? 0 : 1;
+      }
+      rc |= (ro1[0] == 0x40 && ro1[3 * pt] == 0x40) ? 0 : 1;
+      rc |= memcmp(ro1.data() + pt, pp, pt) ? 1 : 0;  // (record 0 has the scalar 1)
+    }
+    uint8_t keys[3 * 96 + 96];
+    memset(keys, 0x5A, sizeof keys);
+    const uint64_t ki[3] = {1, 2, ~0ull};
+    rc |= mph_rec_gather_keys(p1.data(), 2, ki, 3, keys);
+    rc |= (memcmp(keys, p1.data() + 96, 96) == 0 && keys[96] == 0xff && keys[3 * 96 - 1] == 0xff && keys[3 * 96] == 0x5A) ? 0 : 1;
+  }
   printf("manypoint_host: %s\n", rc ? "FAILED" : "ok");
   return rc ? 1 : 0;
 }

@@ -35,6 +35,11 @@ Findings.  (1) job_msm_ladder_safe restarted an accumulator that had come back t
 the bound analysis rejects in the next addition ("merge opposite" in short-scalar mode at parts = 1: the whole job cancels);
 the selected y is carried now.  (2) job_msm_tables_g1 wrote identities into the SHARED table set when job 0's own scalar was
 bad (shared_case "job0 even" / "job0 >= r"); an entry depends on its point alone now.
+
+The ragged sums of the records verifier (k_rec_tables_* / k_rec_ladder_* / k_rec_gather_keys, tc_records.h) run through the same
+two legs, checkers and pool: RecCase and rec_case at the end of this file.  A launch is J segments of one record array; what is
+new against the fixed-n kernels is where a lane finds its work (first_chunk[j], the segment's own column stride), one trip
+count per WAVE, and parts without records.  Nothing was found there.
 """
 import ctypes
 import os
@@ -97,7 +102,7 @@ _SZ, _VP, _INT = ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int
 
 
 def load(path, prefix):
-    """prefix "mp_": the device harness; "mph_": the host leg.  The three entries take the same arguments in both."""
+    """prefix "mp_": the device harness; "mph_": the host leg.  The five entries take the same arguments in both."""
     lib = ctypes.CDLL(path)
     g2 = getattr(lib, prefix + "msm_g2")
     g2.argtypes = [_SZ, _SZ, _SZ, _VP, _VP, _VP, _INT, _SZ, _VP, _SZ, _SZ, _INT, _VP, _VP, _VP, _VP]
@@ -105,9 +110,13 @@ def load(path, prefix):
     g1.argtypes = [_SZ, _SZ, _SZ, _VP, _VP, _VP, _INT, _SZ, _VP, _VP, _VP, _VP]
     comb = getattr(lib, prefix + "comb")
     comb.argtypes = [_VP, _SZ, _VP, _VP, _SZ, _SZ, _SZ, _VP, _VP, _VP, _VP]
-    for f in (g2, g1, comb):
+    rec = getattr(lib, prefix + "rec_sum")
+    rec.argtypes = [_INT, _SZ, _VP, _VP, _VP, _VP, _INT, _SZ, _VP, _VP, _VP, _VP, _VP]
+    gather = getattr(lib, prefix + "rec_gather_keys")
+    gather.argtypes = [_VP, _SZ, _VP, _SZ, _VP]
+    for f in (g2, g1, comb, rec, gather):
         f.restype = _INT
-    return {"g2": g2, "g1": g1, "comb": comb, "lib": lib, "host": prefix == "mph_"}
+    return {"g2": g2, "g1": g1, "comb": comb, "rec": rec, "gather": gather, "lib": lib, "host": prefix == "mph_"}
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -992,3 +1001,318 @@ def check_comb(case, share, res, max_report=12):
             if len(bad) > max_report:
                 return bad
     return bad
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the ragged sums (k_rec_tables_* / k_rec_ladder_* / k_rec_gather_keys; tc_records.h)
+# ---------------------------------------------------------------------------------------------------------------------
+# A launch is J SEGMENTS of one record array.  Segment j of len records keeps the tables and codes of a fixed-n job with n = len,
+# at first_chunk[j] (the column stride of its codes is its OWN shares4); stage L gives it `parts` lanes / lane pairs, rec_part's
+# ranges, of which some are EMPTY when len < parts, and every lane of a wave runs the trip count of the longest part in the wave.
+# A segment is a Job (a[i], k[i], status_in); its claim is a LIST of claims, one per `parts` it speaks about.
+REC_PARTS = {w: [p for p in (1, 2, 4, 8, 16, 32, 64) if p <= MAX_PARTS[w]] for w in (1, 2)}
+REC_ILLEGAL = {w: [3, 2 * MAX_PARTS[w]] for w in (1, 2)}  # the launchers run them as parts = 1
+REC_NBITS = {1: 80, 2: 16}                                # the modes tc_verify_*_records_rlc_batch ships
+REC_FULL = {1: 128, 2: 64}
+REC_J = 70
+REC_HEAD = [0, 0, 130, 1, 65, 2, 64, 3, 33, 4, 5, 7, 8, 9, 1, 2]  # random segments: long and short ones side by side
+
+
+def rec_part(length, g, parts):
+    """tc_records.h rec_part and rec_part_trips: (s0, s1, trips); s0 == s1: the part is empty."""
+    return g * length // parts, (g + 1) * length // parts, -(-length // parts)
+
+
+class RecCase:
+    def __init__(self, w, nbits, segs, tag, parts=None):
+        self.w, self.nbits, self.segs, self.tag, self.J = w, nbits, segs, tag, len(segs)
+        self.parts = list(parts) if parts else REC_PARTS[w] + REC_ILLEGAL[w]
+        self.top = nbits if w == 2 else nbits // 2
+        self.lens = [len(s.a) for s in segs]
+        self.seg_first, self.first_chunk = [0], [0]
+        for n in self.lens:
+            self.seg_first.append(self.seg_first[-1] + n)
+            self.first_chunk.append(self.first_chunk[-1] + (n + 3) // 4)
+        self.records, self.chunks = self.seg_first[-1], self.first_chunk[-1]
+        self.one = [MsmCase(w, len(s.a), 1, nbits, [s], [1]) for s in segs]  # the fixed-n model of a segment's stage T
+        self._ref = None
+
+    def valid(self, j):
+        return self.one[j].valid(self.segs[j])
+
+    def seg_model(self, j, parts):
+        """(sum, per part: special, merge events) of a valid segment on multiples of G.  An empty part has the sum 0; what its
+        lane computes before the kernel replaces it cannot be observed and is not described."""
+        seg, n = self.segs[j], self.lens[j]
+        codes, flips, _ = self.one[j].share_codes(seg)
+        mults = [entry_mults(self.w, seg.a[s], flips[s]) for s in range(n)]
+        sums, special = [], []
+        for g in range(parts):
+            s0, s1, _ = rec_part(n, g, parts)
+            acc, sp = walk_part(self.w, mults, codes, s0, s1) if s0 < s1 else (0, False)
+            sums.append(acc)
+            special.append(sp)
+        total, events = merge_events(sums)
+        return total, special, events
+
+    def ref(self):
+        """Expected status and output bytes per segment, once.  A launch without a record returns before it writes anything."""
+        if self._ref is None:
+            w, st, out = self.w, [], []
+            for j, seg in enumerate(self.segs):
+                good = seg.status_in == OK and self.valid(j)
+                st.append(seg.status_in if seg.status_in != OK else OK if good else INVALID)
+                if self.chunks == 0:
+                    out.append(bytes([POISON]) * PT_BYTES[w])
+                else:
+                    out.append(enc(w, gmul(w, sum(a * k for a, k in zip(seg.a, seg.k)) % R) if good else None))
+            if self.chunks == 0:
+                st = [seg.status_in for seg in self.segs]
+            self._ref = (st, out)
+        return self._ref
+
+
+def check_rec_claims(case):
+    """The model confirms every claim of every directed segment; a random segment meets no special case in any part at any
+    parts, and its tree meets nothing but the identities that its EMPTY parts bring (parts > len)."""
+    bad = []
+    for j, seg in enumerate(case.segs):
+        if not case.valid(j):
+            continue
+        what = "%s segment %d (%s, len %d)" % (case.tag, j, seg.tag, case.lens[j])
+        if seg.random:
+            for p in REC_PARTS[case.w]:
+                _, special, events = case.seg_model(j, p)
+                if any(special) or any(p <= case.lens[j] or k != "identity" for _, _, k in events):
+                    bad.append("%s: random, but special at parts %d: %s %s" % (what, p, special, events))
+            continue
+        claims = seg.claim if isinstance(seg.claim, list) else [seg.claim] if seg.claim else []
+        for c in claims:
+            _, special, events = case.seg_model(j, c["parts"])
+            if "special" in c and {g for g, sp in enumerate(special) if sp} != c["special"]:
+                bad.append("%s: special parts %s at parts %d, claimed %s" % (what, special, c["parts"], c["special"]))
+            if "merge" in c and not any((r, k) == c["merge"] for r, _, k in events):
+                bad.append("%s: merge events %s at parts %d, claimed %s" % (what, events, c["parts"], c["merge"]))
+    return bad
+
+
+def _rec_scalar(w, nbits, rnd, unit):
+    return 1 if unit else rand_scalar(_full(w, nbits), w, nbits, rnd)
+
+
+def rec_random_seg(w, n, nbits, rnd, unit=False, tag="random"):
+    """A random segment that the model shows to meet nothing (check_rec_claims' rule)."""
+    for _ in range(50):
+        seg = Job(rnd.sample(pool(w), n), [_rec_scalar(w, nbits, rnd, unit) for _ in range(n)], tag)
+        seg.random = True
+        if not check_rec_claims(RecCase(w, nbits, [seg], "probe")):
+            return seg
+    raise AssertionError("no random segment without a special case")
+
+
+def rec_directed(w, nbits, rnd, unit=False):
+    """The directed segments of the ragged forms: short ones, where parts > len leaves empty parts beside the special case."""
+    full, most = _full(w, nbits), MAX_PARTS[w]
+    last = most.bit_length() - 2  # the last round of the tree at the largest split
+    segs = []
+
+    def base(n, tag, claim=None, **kw):
+        s = rec_random_seg(w, n, nbits, rnd, unit, tag)
+        s.random, s.claim = False, claim
+        s.__dict__.update(kw)
+        segs.append(s)
+        return s
+
+    # two adjacent records with the same point and scalar: P = Q at the top column in one part, `equal` in the tree in two
+    s = base(2, "equal neighbours", [{"parts": 1, "special": {0}}, {"parts": 2, "special": set(), "merge": (0, "equal")},
+                                     {"parts": most, "special": set(), "merge": (last, "equal")}])
+    s.a[1], s.k[1] = s.a[0], s.k[0]
+    s = base(5, "equal neighbours at the start of 5", [{"parts": 1, "special": {0}}, {"parts": 2, "special": {0}}, {"parts": 8, "merge": (0, "identity")}])
+    s.a[1], s.k[1] = s.a[0], s.k[0]
+    # a record and its negative: the whole segment is the identity / the accumulator comes back to the identity in mid-ladder
+    s = base(2, "P and -P", [{"parts": 1, "special": {0}}, {"parts": 2, "special": set(), "merge": (0, "opposite")},
+                             {"parts": 4, "special": set(), "merge": (1, "opposite")}, {"parts": most, "special": set(), "merge": (last, "opposite")}])
+    s.a[1], s.k[1] = neg_mult(w, s.a[0]), s.k[0]
+    s = base(3, "P, -P, Q", [{"parts": 1, "special": {0}}, {"parts": 2, "special": set()}])
+    s.a[1], s.k[1] = neg_mult(w, s.a[0]), s.k[0]
+    # the identity as a record: alone, first of a part, in mid-part
+    s = base(1, "identity alone", [{"parts": 1, "special": {0}}, {"parts": most, "special": {most - 1}, "merge": (0, "identity")}])
+    s.a[0] = 0
+    s = base(9, "identity first, and first of part 2/4", [{"parts": 1, "special": {0}}, {"parts": 4, "special": {0, 2}}])
+    s.a[0] = s.a[4] = 0
+    s = base(5, "identity in mid-part", [{"parts": 1, "special": {0}}, {"parts": 2, "special": {0}}, {"parts": 16, "special": {6}}])
+    s.a[1] = 0
+    # halves that cancel: the last round of the tree meets `opposite` at 2, 4 and 8 parts
+    s = base(8, "opposite halves", [{"parts": p, "merge": (p.bit_length() - 2, "opposite")} for p in (2, 4, 8)])
+    for i in range(4):
+        s.a[4 + i], s.k[4 + i] = neg_mult(w, s.a[i]), s.k[i]
+    # failures: the neighbours must stay exact
+    s = base(5, "undecodable first record")
+    s.a[0] = None
+    s = base(5, "undecodable last record")
+    s.a[4] = None
+    base(3, "status not OK on entry", status_in=NOT_ENOUGH)
+    if not unit:
+        s = base(3, "scalar = r")
+        s.k[1] = R
+        if not full:
+            s = base(3, "even scalar")
+            s.k[2] -= 1
+            s = base(2, "scalar that is not short")
+            s.k[0] = (1 + (1 << nbits) * X) if w == 2 else 1 + (1 << nbits) * X2
+    return segs
+
+
+def rec_lay_out(w, nbits, rnd, head, directed, J, unit=False):
+    """lay_out for segments: random ones of the lengths `head`, then three directed ones and a short random one, to J."""
+    segs = [rec_random_seg(w, n, nbits, rnd, unit, "random len %d" % n) for n in head]
+    # a failing segment goes between two that are OK: both neighbours must stay exact
+    fails = [s for s in directed if s.status_in != OK or not MsmCase(w, len(s.a), 1, nbits, [s], [1]).valid(s)]
+    good = [s for s in directed if not any(s is f for f in fails)]
+    d, fill = [], 0
+    while good or fails:
+        d += good[:1] + fails[:1]
+        good, fails = good[1:], fails[1:]
+    while len(segs) < J:
+        for _ in range(3):
+            if d and len(segs) < J:
+                segs.append(d.pop(0))
+        if len(segs) < J:
+            fill += 1
+            segs.append(rec_random_seg(w, 1 + (fill % 3 == 0), nbits, rnd, unit, "random filler"))
+    return segs, d
+
+
+_REC = {}
+REC_TABLES = [(1, "short"), (2, "short"), (2, "unit"), (1, "full"), (2, "full"), (1, "fail first"), (2, "fail first"), (1, "no segment"),
+              (2, "no segment"), (1, "all empty"), (2, "all empty"), (1, "one record"), (2, "one record")]
+
+
+def rec_case(w, kind):
+    """short: the shipped mode, J = 70 (more than one wave of segments at parts = 1, a ragged last wave), the directed jobs of
+    the fixed-n suite at n = 8 (their claims hold as they are: rec_part cuts as msm_part does) and rec_directed.  unit: every
+    scalar 1 (the second-level launch over piece sums).  full: a small table at full width.  fail first: the first segment with
+    records fails in stage T, between empty ones -- place 0 of the launch, on which empty parts fall back, is a failed segment's."""
+    key = (w, kind)
+    if key in _REC:
+        return _REC[key]
+    rnd = random.Random("manypoint-rec-%d-%s" % key)
+    nbits = REC_FULL[w] if kind == "full" else REC_NBITS[w]
+    tag = "rec G%d %s nbits=%d" % (w, kind, nbits)
+    left = []
+    if kind == "short":
+        keep = ("merge", "equal shares", "identity in the middle", "largest short digits", "digit with bit", "k1 with bit")
+        fixed = [j for j in directed_jobs(w, 8, nbits, rnd) if j.tag.startswith(keep)]  # (the rest has a shorter twin in rec_directed)
+        segs, left = rec_lay_out(w, nbits, rnd, REC_HEAD, rec_directed(w, nbits, rnd) + fixed, REC_J)
+    elif kind == "unit":
+        segs, left = rec_lay_out(w, nbits, rnd, REC_HEAD, rec_directed(w, nbits, rnd, True), REC_J, True)
+    elif kind == "full":
+        segs, left = rec_lay_out(w, nbits, rnd, [0, 1, 33, 2, 9, 5, 3, 8], rec_directed(w, nbits, rnd), 27)
+    elif kind == "fail first":
+        bad = rec_random_seg(w, 3, nbits, rnd, tag="undecodable first record of the launch")
+        bad.random, bad.a[0] = False, None
+        kept = rec_random_seg(w, 2, nbits, rnd, tag="status not OK on entry")
+        kept.random, kept.status_in = False, NOT_ENOUGH
+        segs = [rec_random_seg(w, n, nbits, rnd) if n is not None else s for n, s in
+                ((0, None), (None, bad), (0, None), (5, None), (0, None), (2, None), (None, kept), (1, None), (0, None))]
+    elif kind == "no segment":
+        segs = []
+    elif kind == "all empty":
+        segs = [rec_random_seg(w, 0, nbits, rnd) for _ in range(5)]
+    else:
+        assert kind == "one record"
+        segs = [rec_random_seg(w, 1, nbits, rnd)]
+    case = RecCase(w, nbits, segs, tag)
+    case.left_out = [s.tag for s in left]
+    _REC[key] = case
+    return case
+
+
+def run_rec(lib, case, parts):
+    """(out (J + 1 rows), status, tbl, codes (both with one guard chunk), first_chunk) as the leg left them."""
+    w, J = case.w, case.J
+    pts = np.frombuffer(b"".join(BAD_POINT[w] if a is None else enc(w, gmul(w, a)) for s in case.segs for a in s.a) + b"\0", dtype=np.uint8).copy()
+    sc = np.array([dc.u32s(k) for s in case.segs for k in s.k] + [[0] * 8], dtype=np.uint32).reshape(-1)
+    st_in = np.array([s.status_in for s in case.segs] + [0], dtype=np.uint8)
+    seg_first = np.array(case.seg_first, dtype=np.uint64)
+    out = np.full((J + 1) * PT_BYTES[w], POISON, dtype=np.uint8)
+    status = np.full(J + 1, POISON, dtype=np.uint8)
+    tbl = np.full((case.chunks + 1) * 4 * 8 * ENTRY[w], POISON_WORD, dtype=np.int32)
+    codes = np.full((case.chunks + 1) * 4 * COLS, POISON, dtype=np.uint8)
+    fc = np.full(J + 1, 0x5A5A5A5A5A5A5A5A, dtype=np.uint64)
+    rc = lib["rec"](w, J, _ptr(seg_first), _ptr(pts), _ptr(sc), _ptr(st_in), case.nbits, parts, _ptr(out), _ptr(status), _ptr(tbl), _ptr(codes), _ptr(fc))
+    if rc != 0:
+        raise HipError("%s parts=%d: the harness returned %d" % (case.tag, parts, rc))
+    return out.reshape(J + 1, -1), status, tbl, codes, fc
+
+
+def check_rec(case, parts, res, max_report=12):
+    """Every check of the ragged sums on one run; returns the list of failures."""
+    out, status, tbl, codes, fc = res
+    w, J, ew = case.w, case.J, ENTRY[case.w]
+    want_st, want_out = case.ref()
+    what0 = "%s parts=%d" % (case.tag, parts)
+    bad = []
+    if fc.tolist() != case.first_chunk:
+        bad.append("%s: first_chunk %s, expected %s" % (what0, fc.tolist(), case.first_chunk))
+    if bytes(out[J]) != bytes([POISON]) * PT_BYTES[w] or status[J] != POISON:
+        bad.append("%s: output or status written behind the last segment" % what0)
+    used_t, used_c = case.chunks * 4 * 8 * ew, case.chunks * 4 * COLS
+    if not (tbl[used_t:] == POISON_WORD).all() or not (codes[used_c:] == POISON).all():
+        bad.append("%s: the guard chunk behind the tables or the codes written" % what0)
+    if case.chunks == 0 and (not (tbl == POISON_WORD).all() or not (codes == POISON).all()):
+        bad.append("%s: a launch without records wrote tables or codes" % what0)
+    for j, seg in enumerate(case.segs):
+        if len(bad) > max_report:
+            break
+        n = case.lens[j]
+        what = "%s segment %d (%s, len %d)" % (what0, j, seg.tag, n)
+        if status[j] != want_st[j]:
+            bad.append("%s: status %d, expected %d" % (what, status[j], want_st[j]))
+        if bytes(out[j]) != want_out[j]:
+            bad.append("%s: wrong output bytes" % what)
+        if not n:
+            continue
+        p0, s4 = case.first_chunk[j] * 4, 4 * ((n + 3) // 4)
+        assert s4 == case.one[j].shares4
+        t = tbl[p0 * 8 * ew:(p0 + s4) * 8 * ew].reshape(s4, 8, ew)
+        c = codes[p0 * COLS:(p0 + s4) * COLS].reshape(COLS, s4)  # (the column stride is this segment's)
+        if not (c[case.top + 1:] == POISON).all():
+            bad.append("%s: codes written past column %d" % (what, case.top))
+        if not case.valid(j):
+            continue  # (a failed segment's tables and codes are read by nobody: only where it wrote matters, and the
+            #            neighbours' exact contents and the fill above show that)
+        mcodes, flips, _ = case.one[j].share_codes(seg)
+        got = c[:case.top + 1, :].T.tolist()
+        if got != mcodes:
+            s = next(s for s in range(s4) if got[s] != mcodes[s])
+            bad.append("%s: codes of place %d: %s, expected %s" % (what, s, got[s], mcodes[s]))
+        for s in range(s4):
+            want = entry_points(w, seg.a[s] if s < n else 0, flips[s] and s < n)
+            for m in range(8):
+                check_entry(w, t[s, m], want[m], "%s place %d entry %d" % (what, s, m), bad)
+    return bad
+
+
+# ---- k_rec_gather_keys ----
+GATHER_K, GATHER_R = 5, 71  # 6 lanes per record: 426 lanes, no multiple of a workgroup
+
+
+def gather_case():
+    idx = [0, GATHER_K - 1, GATHER_K, 1 << 32, (1 << 64) - 1, 1, 2, 3]
+    idx = [idx[(r + r // 8) % len(idx)] for r in range(GATHER_R)]
+    pks = [enc(1, gmul(1, a)) for a in pool(1)[:GATHER_K]]
+    want = b"".join(pks[i] if i < GATHER_K else b"\xff" * 96 for i in idx) + bytes([POISON]) * 96
+    return pks, idx, want
+
+
+def run_gather(lib):
+    """The bytes the leg left in keys (R rows and the guard row), and the expected ones."""
+    pks, idx, want = gather_case()
+    pk = np.frombuffer(b"".join(pks), dtype=np.uint8).copy()
+    ix = np.array(idx, dtype=np.uint64)
+    keys = np.full(GATHER_R * 96 + 96, POISON, dtype=np.uint8)
+    rc = lib["gather"](_ptr(pk), GATHER_K, _ptr(ix), GATHER_R, _ptr(keys))
+    if rc != 0:
+        raise HipError("gather keys: the harness returned %d" % rc)
+    return bytes(keys), want

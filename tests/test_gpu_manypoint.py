@@ -8,7 +8,8 @@ against the models (affine point, infinity flag, limb range, |value| <= 2.1 p, p
 column), nothing written for jobs the filter leaves alone / with *need == 0 / in table sets 1 .. B-1 of the shared set, and
 the same bytes for every parts / share.  Covered geometry: parts 1 .. 32 (G2) and 1 .. 64 (G1) including the unsplit ladder
 kernel, short-scalar mode with nbits = 16 (G2), 32 and 80 (G1), the shared table set, the filter's shapes n = 2, 3, 4,
-share = 1 .. 8 of the comb and several workgroups with a ragged tail.  Invalid encodings are ordinary data; after a HIP
+share = 1 .. 8 of the comb and several workgroups with a ragged tail; the ragged sums of the records verifier (k_rec_*) over
+70 segments of 0 .. 130 records at every power of two of parts up to a wave's worth, and k_rec_gather_keys.  Invalid encodings are ordinary data; after a HIP
 error nothing more is launched."""
 import os
 import sys
@@ -103,3 +104,28 @@ def test_comb_signer(lib, n, B):
         if first is None:
             first = res
         assert all((a == b).all() for a, b in zip(res, first)), "%s: share = %d and share = %d leave different bytes" % (case.tag, share, case.shares[0])
+
+
+def _run_rec(lib, case):
+    first = None
+    for parts in case.parts:
+        res = _launch(mp.run_rec, lib, case, parts)
+        if first is None or not all((a == b).all() for a, b in zip(res, first)):  # (equal bytes need no second decoding)
+            bad = mp.check_rec(case, parts, res)
+            assert not bad, "\n".join(bad[:12])
+        if first is None:
+            first = res
+        assert all((a == b).all() for a, b in zip(res, first)), "%s: parts = %d and parts = %d leave different bytes" % (case.tag, parts, case.parts[0])
+
+
+@pytest.mark.parametrize("w,kind", mp.REC_TABLES)
+def test_rec_sum(lib, w, kind):
+    """The ragged sums (k_rec_tables_* / k_rec_ladder_*) through launch_rec_sum_g1 / _g2: every power of two of parts up to a
+    wave's worth, then 3 and twice the maximum (run as parts = 1), all with the same bytes -- outputs, statuses, tables, codes
+    and the untouched guards behind them."""
+    _run_rec(lib, mp.rec_case(w, kind))
+
+
+def test_rec_gather_keys(lib):
+    got, want = _launch(mp.run_gather, lib)
+    assert got == want

@@ -10,6 +10,8 @@ signer.
     meets the identity"), and every random filler job is shown to meet none, at every legal parts.
 (d) The host leg (tests/device/manypoint_host.cpp, g++ -DTC_BOUND_CHECK: the header routines the kernels call) runs the
     full case tables of the GPU leg through the same checkers, so tables, models and checkers are proven before a GPU run.
+(e) The ragged sums of the records verifier (k_rec_*): the model's rec_part is the library's, the tables have the shapes the
+    ragged forms need, every directed segment hits what it claims, and the host leg runs every table at every parts.
 """
 import ctypes
 import os
@@ -34,7 +36,13 @@ COMB = [(3, 5), (8, 5), (9, 5), (24, 5), (30, 5), (30, 70)]
 
 
 def test_manypoint_kernels_cross_compile_for_gfx950():
-    assert os.path.getsize(mp.build_device()) > 0
+    lib = mp.build_device()
+    assert os.path.getsize(lib) > 0
+    with open(lib, "rb") as f:
+        text = f.read()
+    for name in (b"mp_msm_g2", b"mp_msm_g1", b"mp_comb", b"mp_rec_sum", b"mp_rec_gather_keys",
+                 b"k_rec_tables_g2", b"k_rec_ladder_g2", b"k_rec_tables_g1", b"k_rec_ladder_g1", b"k_rec_gather_keys"):
+        assert name in text, name  # the entries of the harness and the ragged kernels they reach
 
 
 @pytest.fixture(scope="module")
@@ -254,3 +262,89 @@ def test_host_comb(host, n, B):
         if first is None:
             first = res
         assert all((a == b).all() for a, b in zip(res, first))
+
+
+# ---- the ragged sums (k_rec_*; tc_records.h) --------------------------------------------------------------------------------
+def test_rec_part_of_the_model_tiles_a_segment_as_the_library_does(host):
+    """For every length of the tables and every parts: the model's rec_part is tc_records.h's, the ranges tile [0, len) in
+    order, a part holds trips or trips - 1 records (EMPTY ones where len < parts), and trips = ceil(len / parts)."""
+    out = (ctypes.c_uint64 * 3)()
+    lens = sorted({n for w, kind in mp.REC_TABLES for n in mp.rec_case(w, kind).lens} | {0, 1, 2, 3, 4, 5, 7, 8, 9, 33, 64, 65, 130})
+    for n in lens:
+        for p in mp.REC_PARTS[1]:
+            nxt, empty = 0, 0
+            for g in range(p):
+                s0, s1, trips = mp.rec_part(n, g, p)
+                host["lib"].mph_rec_part(ctypes.c_uint64(n), ctypes.c_size_t(g), ctypes.c_size_t(p), out)
+                assert (s0, s1, trips) == tuple(out), (n, g, p)
+                assert s0 == nxt and s1 >= s0 and trips == -(-n // p) and (s1 - s0 in (trips, trips - 1) or s1 == s0)
+                nxt, empty = s1, empty + (s1 == s0)
+            assert nxt == n and empty == max(p - n, 0), (n, p)
+    sz = (ctypes.c_size_t * 3)()
+    host["lib"].mph_rec_sizes(ctypes.c_uint64(7), sz)
+    assert list(sz) == [7 * 4 * 8 * 64 * 4, 7 * 4 * 8 * 32 * 4, 7 * 4 * 65]
+
+
+def test_rec_tables_have_the_shapes_the_ragged_forms_need():
+    for w in (1, 2):
+        case = mp.rec_case(w, "short")
+        most = mp.MAX_PARTS[w]
+        assert case.J == mp.REC_J > most and case.J % most and case.records < 512 and case.lens[:2] == [0, 0]
+        assert set(case.lens) >= {0, 1, 2, 3, 4, 5, 7, 8, 9, 33, 64, 65, 130}
+        assert case.parts == [p for p in (1, 2, 4, 8, 16, 32, 64) if p <= most] + [3, 2 * most]
+        assert all(s.random for s in case.segs[:16]) and case.lens[2:4] == [130, 1]  # whole waves of random segments first
+        directed = sum(not s.random for s in case.segs)
+        assert directed >= 20
+        for i in range(16, 16 + 4 * (directed // 3), 4):  # then three directed segments and a random one
+            assert [s.random for s in case.segs[i:i + 4]] == [False, False, False, True], i
+        assert case.nbits == mp.REC_NBITS[w] and mp.rec_case(w, "full").nbits == mp.REC_FULL[w]
+        st = mp.rec_case(w, "fail first").ref()[0]
+        assert mp.rec_case(w, "fail first").lens[:3] == [0, 3, 0] and st[:3] == [mp.OK, mp.INVALID, mp.OK] and mp.NOT_ENOUGH in st
+        assert mp.rec_case(w, "no segment").J == 0 and mp.rec_case(w, "all empty").chunks == 0 and mp.rec_case(w, "one record").lens == [1]
+    assert all(k == 1 for s in mp.rec_case(2, "unit").segs for k in s.k)
+    pks, idx, want = mp.gather_case()
+    assert {0, mp.GATHER_K - 1, mp.GATHER_K, 1 << 32, (1 << 64) - 1} <= set(idx) and len(idx) == 71 and (71 * 6) % 64 and len(want) == 72 * 96
+
+
+def test_directed_segments_hit_what_they_claim_and_random_ones_hit_nothing():
+    seen, merges = set(), set()
+    for w, kind in mp.REC_TABLES:
+        case = mp.rec_case(w, kind)
+        assert not mp.check_rec_claims(case), case.tag
+        assert not case.left_out, (case.tag, case.left_out)
+        if kind in ("short", "unit", "full"):
+            tags = {s.tag for s in case.segs}
+            seen |= tags
+            assert tags >= {"equal neighbours", "P and -P", "P, -P, Q", "identity alone", "identity first, and first of part 2/4", "identity in mid-part",
+                            "opposite halves", "undecodable first record", "undecodable last record", "status not OK on entry"}, case.tag
+            claims = [c for s in case.segs if isinstance(s.claim, list) for c in s.claim]
+            merges |= {(w, c["parts"]) + c["merge"] for c in claims if "merge" in c}
+            st = case.ref()[0]
+            for j, s in enumerate(case.segs):  # a failing segment sits between segments that are OK
+                if st[j] != mp.OK:
+                    assert st[j - 1] == mp.OK and (j + 1 == case.J or st[j + 1] == mp.OK or not case.segs[j + 1].random), (case.tag, j)
+    assert seen >= {"even scalar", "scalar that is not short", "scalar = r", "digit with bit nbits set", "merge opposite at round 0 of parts 2"}, seen
+    assert merges >= {(2, 32, 4, "opposite"), (1, 64, 5, "opposite"), (2, 32, 4, "equal"), (2, 2, 0, "equal"), (2, 8, 2, "opposite"), (1, 64, 0, "identity")}
+
+
+def _run_rec(host, case):
+    first = None
+    for parts in case.parts:
+        res = mp.run_rec(host, case, parts)
+        if first is None or not all((a == b).all() for a, b in zip(res, first)):  # (equal bytes need no second decoding)
+            bad = mp.check_rec(case, parts, res)
+            assert not bad, "\n".join(bad[:12])
+        if first is None:
+            first = res
+        assert all((a == b).all() for a, b in zip(res, first)), "%s: parts = %d and parts = %d leave different bytes" % (case.tag, parts, case.parts[0])
+
+
+@pytest.mark.parametrize("w,kind", mp.REC_TABLES)
+def test_host_rec_sum(host, w, kind):
+    """Every legal parts gives the bytes of parts = 1 -- outputs, statuses, tables, codes, guards --, an illegal one too."""
+    _run_rec(host, mp.rec_case(w, kind))
+
+
+def test_host_rec_gather_keys(host):
+    got, want = mp.run_gather(host)
+    assert got == want
