@@ -5,10 +5,12 @@
 #include "tc_robust.h"
 #include "tc_blame.h"
 #include "tc_records.h"
+#include "tc_fallback.h"
 #include "../../include/tc_amd.h"
 
 #include <stdio.h>
 #include <string.h>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -165,8 +167,7 @@ struct Call {
     size_t n = count * sizeof(T);
     void* d = scratch(n);
     if (!d) return nullptr;
-    if (n && !check(hipMemcpyAsync(d, p, n, hipMemcpyHostToDevice, c->stream), "H2D copy")) return nullptr;
-    c->h2d_bytes += n;
+    if (n && !upload(d, p, n, "H2D copy")) return nullptr;
     if (secret) wipe.emplace_back(d, n);
     return (const T*)d;
   }
@@ -197,6 +198,38 @@ struct Call {
     if (d && zero && n) check(hipMemsetAsync(d, 0, n, c->stream), "memset");
     return d;
   }
+  // the staging copies of a call, on its stream: the ONLY places that count the bytes moved over PCIe (tc_ctx_transfer_bytes)
+  bool upload(void* dst, const void* host_src, size_t bytes, const char* what) {
+    if (!check(hipMemcpyAsync(dst, host_src, bytes, hipMemcpyHostToDevice, c->stream), what)) return false;
+    c->h2d_bytes += bytes;
+    return true;
+  }
+  bool readback(void* host_dst, const void* dev_src, size_t bytes, const char* what) {
+    if (!check(hipMemcpyAsync(host_dst, dev_src, bytes, hipMemcpyDeviceToHost, c->stream), what)) return false;
+    c->d2h_bytes += bytes;
+    return true;
+  }
+  // a temporary that holds secret scalars (or a lossless recoding of them): zeroed when the call ends
+  template <class T>
+  T* secret_temp(size_t count) {
+    T* d = temp<T>(count);
+    if (d) wipe.emplace_back(d, count * sizeof(T));
+    return d;
+  }
+  // the seed of a combined entry on the device: host memory in both I/O modes (32 bytes; secret until the call returns)
+  uint8_t* secret_seed(const uint8_t* seed32) {
+    uint8_t* d = secret_temp<uint8_t>(32);
+    if (d) upload(d, seed32, 32, "seed copy");
+    return d;
+  }
+  // members only: ok[j] &= (row j of pts is a point of the order-r subgroup) for R rows of `stride` bytes -- stride 0: ONE point,
+  // shared by every row.  v: R bytes of scratch.
+  void require_members(bool g2, const uint8_t* pts, size_t stride, size_t R, uint8_t* v, uint8_t* ok) {
+    const size_t n = stride ? R : 1;
+    if (g2) tc::launch_subgroup_check_g2(c->stream, pts, stride, 1, 1, n, v);
+    else tc::launch_subgroup_check_g1(c->stream, pts, stride, 1, 1, n, v);
+    tc::launch_invalidate_jobs(c->stream, v, 1, stride ? 1 : (size_t)-1, R, nullptr, nullptr, 0, ok);
+  }
   // the Miller values between the two kernels of a pairing check (k_pairing.hip)
   // (+ the line buffer of the prepared form, one tile of checks sized to the memory this call may spend: msm_table_budget)
   tc::PairingWs pairing_ws(size_t B);
@@ -205,9 +238,10 @@ struct Call {
   // Checked-input mode (tc_ctx_set_input_checks): validate the first `take` points of `records` records of
   // n_per_job points each (stride 0 = ONE point shared by every job); job j owns record j / group.
   // always: the test runs whatever the context's switch says (entries that multiply a SECRET by the operand)
-  void check_points(bool g2, const uint8_t* d_pts, size_t stride, size_t n_per_job, size_t take, size_t records, size_t group,
-                    bool always = false) {
-    if (!(c->input_checks || always) || failed || !d_pts || !records || !take) return;
+  // Returns the handle of the verdict bytes (Call::take_verdicts), nullptr when nothing was registered.
+  const uint8_t* check_points(bool g2, const uint8_t* d_pts, size_t stride, size_t n_per_job, size_t take, size_t records, size_t group,
+                              bool always = false) {
+    if (!(c->input_checks || always) || failed || !d_pts || !records || !take) return nullptr;
     const size_t PB = g2 ? 192 : 96;
     if (stride == 0) {
       stride = PB;
@@ -218,16 +252,17 @@ struct Call {
     const size_t n = records * take;
     const size_t bytes = records * n_per_job * stride;
     uint8_t* v = temp<uint8_t>(n);
-    if (!v) return;
+    if (!v) return nullptr;
     // The tests are NOT launched here.  They read operands only and nothing reads their verdict before apply_checks, so they
     // run on the context's second stream BESIDE the main kernels of the call, submitted after them (apply_checks): a launch
     // that ends with idle SIMDs -- the 65 536-job combination's last third, DESIGN.md 5.2 -- gets its tail filled (default-mode
     // combine_signatures 10.2 -> 9.3 ms per call, profiles/r06_checks_beside_ab.txt), and a small batch runs both at once.
     // ev_fork marks where the operands are ready in the main stream (every check_points call precedes the main kernels).
     const bool beside = c->tuning.checks_beside && !overlaps_output(d_pts, bytes) && side_stream_ready();
-    if (beside && !check(hipEventRecord(c->ev_fork, c->stream), "event record")) return;
+    if (beside && !check(hipEventRecord(c->ev_fork, c->stream), "event record")) return nullptr;
     checks.push_back({v, take, group, g2, d_pts, stride, n_per_job, take, n, bytes});
     if (!beside) launch_pending(checks.back(), c->stream);
+    return v;
   }
   // the context's second stream, made on first use: non-blocking and of the LOWEST priority the device offers, so that its
   // kernels take the wave slots the main kernels leave idle instead of competing with them for the dispatcher, and so that it
@@ -275,6 +310,19 @@ struct Call {
       for (auto& p : checks) tc::launch_invalidate_jobs(c->stream, p.valid, p.per_job, p.group, B, status, out, out_bytes, ok);
     checks.clear();
   }
+  // For the entries whose HOST decides what falls back: the deferred tests run, and the verdict bytes behind each handle
+  // (check_points' return value; a null handle -- nothing registered -- leaves its vector empty) are read back, as many as were
+  // registered.  The pending list ends empty; with nothing pending and no handle this does nothing.
+  void take_verdicts(std::initializer_list<std::pair<const uint8_t*, std::vector<uint8_t>*>> want) {
+    run_checks();
+    for (auto& w : want)
+      for (auto& p : checks)
+        if (w.first && p.valid == w.first) {
+          w.second->resize(p.n);
+          readback(w.second->data(), p.valid, p.n, "valid readback");
+        }
+    checks.clear();
+  }
   // Every entry calls begin_timing() after its allocations and before its first launch: the place to refuse a call the RUNTIME
   // could not survive.  The kernels' private segments (spilled registers, ladder tables: up to 11 KB per lane) are allocated by
   // the ROCm runtime when a dispatch needs them, per queue, for as many waves as the dispatch has (at most 32 per CU); when that
@@ -310,10 +358,7 @@ struct Call {
     for (auto& w : wipe) (void)hipMemsetAsync(w.first, 0, w.second, c->stream);  // zero secret scalars
     if (!failed)
       for (auto& o : outs)
-        if (o.n) {
-          check(hipMemcpyAsync(o.host, o.dev, o.n, hipMemcpyDeviceToHost, c->stream), "D2H copy");
-          c->d2h_bytes += o.n;
-        }
+        if (o.n) readback(o.host, o.dev, o.n, "D2H copy");
     for (auto& w : wipe_after_copy) (void)hipMemsetAsync(w.first, 0, w.second, c->stream);  // stream-ordered after the copies
     if (!c->device_io || c->timing || failed) {
       hipError_t e = hipStreamSynchronize(c->stream);
@@ -344,8 +389,7 @@ bool total_bytes(Call& k, const uint64_t* off, size_t B, uint64_t* total) {
     *total = off[B];
     return true;
   }
-  if (!k.check(hipMemcpyAsync(total, off + B, 8, hipMemcpyDeviceToHost, k.c->stream), "offset readback")) return false;
-  k.c->d2h_bytes += 8;
+  if (!k.readback(total, off + B, 8, "offset readback")) return false;
   return k.check(hipStreamSynchronize(k.c->stream), "stream sync");
 }
 
@@ -425,6 +469,55 @@ void msm_g1(Call& k, size_t n, size_t pts_stride, const uint8_t* d_pts, const ui
                       nbits);
   }
 }
+
+// The compacted operands of a fallback (the combined entries re-check what their one check per group rejected, item by item):
+// row r of a gathered operand is row map[r] of the call's array, through one to four index maps the host has built; one verdict
+// byte per row in c_ok, scattered through one of the maps into the call's ok[] at the end.  Which operands are gathered, which
+// pairing equation runs over them and which of them are tested for membership is the entry's business, at its call site.
+struct Compacted {
+  Call& k;
+  size_t R;  // rows of c_ok
+  std::vector<size_t> first;  // map i = d_maps[first[i] .. first[i + 1])
+  uint32_t* d_maps;
+  uint8_t* c_ok;
+  uint8_t* c_v = nullptr;
+  Compacted(Call& call, size_t rows, std::initializer_list<const std::vector<uint32_t>*> maps) : k(call), R(rows), first(1, 0) {
+    for (auto* m : maps) first.push_back(first.back() + m->size());
+    d_maps = k.temp<uint32_t>(first.back());
+    c_ok = k.temp<uint8_t>(R);
+    size_t i = 0;
+    for (auto* m : maps) {
+      if (!k.failed) k.upload(d_maps + first[i], m->data(), m->size() * 4, "map copy");
+      i++;
+    }
+  }
+  const uint32_t* map(size_t which) const { return d_maps + first[which]; }
+  // the rows of src (stride bytes each) that map `which` names
+  uint8_t* gather(const void* src, size_t stride, size_t which) {
+    const size_t n = first[which + 1] - first[which];
+    uint8_t* d = k.temp<uint8_t>(n * stride);
+    if (!k.failed) tc::launch_gather_rows(k.c->stream, (const uint8_t*)src, stride, map(which), n, d);
+    return d;
+  }
+  uint8_t* scratch() {  // R bytes
+    if (!c_v) c_v = k.temp<uint8_t>(R);
+    return c_v;
+  }
+  // c_ok[r] &= (row r of pts is a group member); stride 0: one point for every row (Call::require_members)
+  void members(bool g2, const uint8_t* pts, size_t stride) {
+    uint8_t* v = scratch();
+    if (!k.failed) k.require_members(g2, pts, stride, R, v, c_ok);
+  }
+  // the host maps may go out of scope after this
+  void sync() {
+    const hipError_t e = hipStreamSynchronize(k.c->stream);
+    if (!k.failed) k.check(e, "stream sync");
+  }
+  void finish(uint8_t* d_ok, size_t which) {
+    if (!k.failed) tc::launch_scatter_bytes(k.c->stream, c_ok, map(which), R, d_ok);
+    sync();
+  }
+};
 
 // TC_DUO_MIN / TC_PAIRING_FORM / TC_PAIRING_BUDGET / TC_SUM_PARTS (tests, experiments): read here, once per context, never on the launch path
 tc::Tuning tuning_from_env() {
@@ -927,8 +1020,7 @@ static int combine(tc_ctx* ctx, bool g2, size_t t, size_t n, const uint64_t* idx
       k.check(hipMemsetAsync(d_canon, 1, B, ctx->stream), "memset");
       tc::launch_fr_idx_narrow(ctx->stream, d_idx_fr, n, t + 1, B, d_idx64, d_wide, d_canon);
       uint32_t wide = 0;
-      k.check(hipMemcpyAsync(&wide, d_wide, 4, hipMemcpyDeviceToHost, ctx->stream), "readback");
-      ctx->d2h_bytes += 4;
+      k.readback(&wide, d_wide, 4, "readback");
       k.check(hipStreamSynchronize(ctx->stream), "stream sync");
       k.checks.push_back({d_canon, 1, 1});  // a job that owns a non-canonical abscissa (>= r) fails like an undecodable operand
       if (wide == 0) {
@@ -1247,15 +1339,8 @@ int tc_verify_shares_rlc_batch(tc_ctx* ctx, const uint8_t* pk_shares, size_t N, 
   const uint8_t* d_sig = k.in(sig_shares, B * N * 192);
   const uint8_t* d_msgs = k.in(msgs, (size_t)total);
   const uint64_t* d_off = k.in(off, B + 1);
-  // the seed is host memory in both I/O modes (32 bytes; it must stay secret until the call returns)
-  uint8_t* d_seed = k.temp<uint8_t>(32);
-  if (d_seed) {
-    k.check(hipMemcpyAsync(d_seed, seed32, 32, hipMemcpyHostToDevice, ctx->stream), "seed copy");
-    ctx->h2d_bytes += 32;
-    k.wipe.emplace_back(d_seed, 32);
-  }
-  uint8_t* d_r = k.temp<uint8_t>(B * N * 32);
-  if (d_r) k.wipe.emplace_back(d_r, B * N * 32);
+  uint8_t* d_seed = k.secret_seed(seed32);
+  uint8_t* d_r = k.secret_temp<uint8_t>(B * N * 32);
   uint8_t* d_hash = k.temp<uint8_t>(B * 192);
   uint8_t* d_S = k.temp<uint8_t>(B * 192);
   uint8_t* d_P = k.temp<uint8_t>(B * 96);
@@ -1279,10 +1364,9 @@ int tc_verify_shares_rlc_batch(tc_ctx* ctx, const uint8_t* pk_shares, size_t N, 
     // message to the per-share fallback
     k.apply_checks(B, nullptr, nullptr, 0, d_okmsg);
     k.check(hipMemsetAsync(d_ok, 1, B * N, ctx->stream), "memset");
-    k.check(hipMemcpyAsync(h_okmsg.data(), d_okmsg, B, hipMemcpyDeviceToHost, ctx->stream), "ok readback");
+    k.readback(h_okmsg.data(), d_okmsg, B, "ok readback");
     std::vector<uint8_t> h_stS(B);
-    k.check(hipMemcpyAsync(h_stS.data(), d_stS, B, hipMemcpyDeviceToHost, ctx->stream), "status readback");
-    ctx->d2h_bytes += 2 * B;
+    k.readback(h_stS.data(), d_stS, B, "status readback");
     k.check(hipStreamSynchronize(ctx->stream), "stream sync");
     std::vector<uint32_t> failed;
     if (!k.failed)
@@ -1291,37 +1375,18 @@ int tc_verify_shares_rlc_batch(tc_ctx* ctx, const uint8_t* pk_shares, size_t N, 
     if (!k.failed && !failed.empty()) {
       // per-share pairing checks for every share of the failed messages, on compacted operands
       const size_t F = failed.size(), R = F * N;
-      std::vector<uint32_t> m_sig(R), m_hash(R), m_pk(R);
-      for (size_t f = 0; f < F; f++)
-        for (size_t i = 0; i < N; i++) {
-          m_sig[f * N + i] = (uint32_t)(failed[f] * N + i);
-          m_hash[f * N + i] = failed[f];
-          m_pk[f * N + i] = (uint32_t)i;
-        }
-      uint32_t* d_maps = k.temp<uint32_t>(3 * R);
-      uint8_t* c_sig = k.temp<uint8_t>(R * 192);
-      uint8_t* c_hash = k.temp<uint8_t>(R * 192);
-      uint8_t* c_pk = k.temp<uint8_t>(R * 96);
-      uint8_t* c_ok = k.temp<uint8_t>(R);
-      if (!k.failed) {
-        k.check(hipMemcpyAsync(d_maps, m_sig.data(), R * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
-        k.check(hipMemcpyAsync(d_maps + R, m_hash.data(), R * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
-        k.check(hipMemcpyAsync(d_maps + 2 * R, m_pk.data(), R * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
-        ctx->h2d_bytes += 12 * R;
-        tc::launch_gather_rows(ctx->stream, d_sig, 192, d_maps, R, c_sig);
-        tc::launch_gather_rows(ctx->stream, d_hash, 192, d_maps + R, R, c_hash);
-        tc::launch_gather_rows(ctx->stream, d_pk, 96, d_maps + 2 * R, R, c_pk);
-        tc::launch_pairing_check(ctx->stream, c_pk, 96, c_hash, 192, ctx->g1_gen_unfix, 0, c_sig, 192, R, c_ok, k.pairing_ws(R));
-        if (ctx->input_checks) {  // members only, as the per-share path would require
-          uint8_t* v = k.temp<uint8_t>(R);
-          tc::launch_subgroup_check_g2(ctx->stream, c_sig, 192, 1, 1, R, v);
-          tc::launch_invalidate_jobs(ctx->stream, v, 1, 1, R, nullptr, nullptr, 0, c_ok);
-          tc::launch_subgroup_check_g1(ctx->stream, c_pk, 96, 1, 1, R, v);
-          tc::launch_invalidate_jobs(ctx->stream, v, 1, 1, R, nullptr, nullptr, 0, c_ok);
-        }
-        tc::launch_scatter_bytes(ctx->stream, c_ok, d_maps, R, d_ok);
-        k.check(hipStreamSynchronize(ctx->stream), "stream sync");  // the host maps go out of scope
+      const tc::SlotMaps m = tc::slot_maps(failed.data(), F, N);
+      Compacted c(k, R, {&m.record, &m.job, &m.slot});
+      const uint8_t* c_sig = c.gather(d_sig, 192, 0);
+      const uint8_t* c_hash = c.gather(d_hash, 192, 1);
+      const uint8_t* c_pk = c.gather(d_pk, 96, 2);
+      const tc::PairingWs pws = k.pairing_ws(R);
+      if (!k.failed) tc::launch_pairing_check(ctx->stream, c_pk, 96, c_hash, 192, ctx->g1_gen_unfix, 0, c_sig, 192, R, c.c_ok, pws);
+      if (ctx->input_checks) {  // members only, as the per-share path would require
+        c.members(true, c_sig, 192);
+        c.members(false, c_pk, 96);
       }
+      c.finish(d_ok, 0);
       if (n_fallback) *n_fallback = F;
     }
   }
@@ -1331,123 +1396,85 @@ int tc_verify_shares_rlc_batch(tc_ctx* ctx, const uint8_t* pk_shares, size_t N, 
   return on_exception((tc_ctx*)ctx);
 }
 
-// The device temporaries of one pass of group checks over B jobs (seed32: HOST memory, copied here and wiped after the call).
+// The device temporaries of one pass of group checks over B jobs (seed32: HOST memory, copied here and wiped after the call);
+// `group` is the caller's, cut: what it means for B jobs (tc_fallback.h).
 struct RlcWs {
-  size_t group, G, tail, NG;
+  tc::GroupCut cut;
   uint8_t *d_seed, *d_r, *d_S, *d_H, *d_st, *d_okg;
 };
 static RlcWs rlc_workspace(Call& k, size_t B, size_t group, const uint8_t* seed32) {
-  tc_ctx* ctx = k.c;
   RlcWs w{};
-  w.group = group;
-  uint8_t* d_seed = k.temp<uint8_t>(32);
-  if (d_seed) {
-    k.check(hipMemcpyAsync(d_seed, seed32, 32, hipMemcpyHostToDevice, ctx->stream), "seed copy");
-    ctx->h2d_bytes += 32;
-    k.wipe.emplace_back(d_seed, 32);
-  }
-  uint8_t* d_r = k.temp<uint8_t>(B * 32);
-  if (d_r) k.wipe.emplace_back(d_r, B * 32);
-  const size_t G = B / group, tail = B % group, NG = G + (tail ? 1 : 0);
-  w.G = G;
-  w.tail = tail;
-  w.NG = NG;
-  w.d_seed = d_seed;
-  w.d_r = d_r;
-  w.d_S = k.temp<uint8_t>(NG * 192);
-  w.d_H = k.temp<uint8_t>(NG * 192);
-  w.d_st = k.temp<uint8_t>(2 * NG);
-  w.d_okg = k.temp<uint8_t>(NG);
+  w.cut = tc::group_cut(B, group);
+  w.d_seed = k.secret_seed(seed32);
+  w.d_r = k.secret_temp<uint8_t>(B * 32);
+  w.d_S = k.temp<uint8_t>(w.cut.NG * 192);
+  w.d_H = k.temp<uint8_t>(w.cut.NG * 192);
+  w.d_st = k.temp<uint8_t>(2 * w.cut.NG);
+  w.d_okg = k.temp<uint8_t>(w.cut.NG);
   return w;
 }
 // The group checks of verify_rlc over DEVICE operands, inside the caller's Call: d_ok[j] (B bytes) = e(pk, hash_j) ==
 // e(g1, sig_j) up to the 2^-63 of a wrongly passing group.  d_g1 is the generator that matches the hash points (g1_gen, or
-// g1_gen_unfix for hash points without their last constant multiplication).  The pending membership tests of the Call
-// (check_points: the key's first, then one verdict per job each) are consumed here and send their groups to the per-job
-// checks; member_checks: the per-job checks test sig (and the hash points when hash_is_operand) and the key for membership
-// again, as tc_verify_g2_batch would.  tc_combine_signatures_robust_batch runs this over the combinations it has just made,
-// with no pending test and member_checks off.  *n_fallback (optional) = jobs that went through the per-job checks.
+// g1_gen_unfix for hash points without their last constant multiplication).  v_key / v_sig / v_hash: the handles of the
+// caller's pending membership tests (Call::check_points; null: not registered) -- one byte for the key, one per job for the
+// others; they are consumed here and send their groups to the per-job checks.  member_checks: the per-job checks test sig
+// (and the hash points when hash_is_operand) and the key for membership again, as tc_verify_g2_batch would.
+// tc_combine_signatures_robust_batch runs this over the combinations it has just made, with no pending test and
+// member_checks off.  *n_fallback (optional) = jobs that went through the per-job checks.
 static void rlc_group_checks(Call& k, const RlcWs& w, const uint8_t* d_pk, const uint8_t* d_sig, const uint8_t* d_hash, const uint8_t* d_g1,
-                             size_t B, bool member_checks, bool hash_is_operand, uint8_t* d_ok, uint64_t* n_fallback) {
+                             size_t B, const uint8_t* v_key, const uint8_t* v_sig, const uint8_t* v_hash, bool member_checks,
+                             bool hash_is_operand, uint8_t* d_ok, uint64_t* n_fallback) {
   tc_ctx* ctx = k.c;
-  const size_t group = w.group, G = w.G, tail = w.tail, NG = w.NG;
+  const size_t group = w.cut.group, G = w.cut.G, tail = w.cut.tail, NG = w.cut.NG;
   uint8_t *d_seed = w.d_seed, *d_r = w.d_r, *d_S = w.d_S, *d_H = w.d_H, *d_st = w.d_st, *d_okg = w.d_okg;
-  const bool hash = hash_is_operand;
-  std::vector<uint8_t> h_okg(NG), h_st(2 * NG), h_valid;
-  if (!k.failed) {
-    tc::launch_rlc_scalars(ctx->stream, d_seed, B, d_r);
-    k.check(hipMemsetAsync(d_st, 0, 2 * NG, ctx->stream), "memset");
-    const uint32_t* rr = reinterpret_cast<const uint32_t*>(d_r);
-    if (G) {
-      msm_g2(k, group, group * 192, d_sig, rr, G, d_S, d_st, /*nbits=*/16, tc::MsmFilter(), /*secret_scalars=*/true);
-      msm_g2(k, group, group * 192, d_hash, rr, G, d_H, d_st + NG, 16, tc::MsmFilter(), true);
-    }
-    if (tail) {
-      msm_g2(k, tail, tail * 192, d_sig + G * group * 192, rr + G * group * 8, 1, d_S + G * 192, d_st + G, 16, tc::MsmFilter(), true);
-      msm_g2(k, tail, tail * 192, d_hash + G * group * 192, rr + G * group * 8, 1, d_H + G * 192, d_st + NG + G, 16, tc::MsmFilter(), true);
-    }
-    tc::launch_pairing_check(ctx->stream, d_pk, 0, d_H, 192, d_g1, 0, d_S, 192, NG, d_okg, k.pairing_ws(NG));
-    k.check(hipMemsetAsync(d_ok, 1, B, ctx->stream), "memset");
-    k.check(hipMemcpyAsync(h_okg.data(), d_okg, NG, hipMemcpyDeviceToHost, ctx->stream), "ok readback");
-    k.check(hipMemcpyAsync(h_st.data(), d_st, 2 * NG, hipMemcpyDeviceToHost, ctx->stream), "status readback");
-    ctx->d2h_bytes += 3 * NG;
-    // checked-input mode: a group that owns a non-member operand goes to the per-job path as well
-    std::vector<const uint8_t*> valid_ptrs;
-    k.run_checks();  // (the membership tests ran beside the two sums and the group checks; their verdicts are read back below)
-    for (auto& p : k.checks) valid_ptrs.push_back(p.valid);
-    const size_t n_checks = k.checks.size();
-    k.checks.clear();
-    if (n_checks) {
-      h_valid.resize(n_checks * B);
-      for (size_t q = 0; q < n_checks; q++) {
-        const bool shared = (q == 0);  // the first pending check is the key's (one byte for the whole batch)
-        k.check(hipMemcpyAsync(h_valid.data() + q * B, valid_ptrs[q], shared ? 1 : B, hipMemcpyDeviceToHost, ctx->stream), "valid readback");
-        ctx->d2h_bytes += shared ? 1 : B;
-      }
-    }
-    k.check(hipStreamSynchronize(ctx->stream), "stream sync");
-    std::vector<uint32_t> failed;
-    if (!k.failed) {
-      const bool key_bad = n_checks && h_valid[0] == 0;
-      for (size_t g = 0; g < NG; g++) {
-        bool bad = key_bad || !h_okg[g] || h_st[g] != TC_JOB_OK || h_st[NG + g] != TC_JOB_OK;
-        const size_t lo = g * group, hi = (lo + group < B) ? lo + group : B;
-        for (size_t q = 1; q < n_checks && !bad; q++)
-          for (size_t j = lo; j < hi && !bad; j++) bad = h_valid[q * B + j] == 0;
-        if (bad)
-          for (size_t j = lo; j < hi; j++) failed.push_back((uint32_t)j);
-      }
-    }
-    if (!k.failed && !failed.empty()) {
-      // per-job pairing checks for every job of the failed groups, on compacted operands
-      const size_t R = failed.size();
-      uint32_t* d_map = k.temp<uint32_t>(R);
-      uint8_t* c_sig = k.temp<uint8_t>(R * 192);
-      uint8_t* c_hash = k.temp<uint8_t>(R * 192);
-      uint8_t* c_ok = k.temp<uint8_t>(R);
-      if (!k.failed) {
-        k.check(hipMemcpyAsync(d_map, failed.data(), R * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
-        ctx->h2d_bytes += 4 * R;
-        tc::launch_gather_rows(ctx->stream, d_sig, 192, d_map, R, c_sig);
-        tc::launch_gather_rows(ctx->stream, d_hash, 192, d_map, R, c_hash);
-        tc::launch_pairing_check(ctx->stream, d_pk, 0, c_hash, 192, d_g1, 0, c_sig, 192, R, c_ok, k.pairing_ws(R));
-        if (member_checks) {  // members only, as the per-job path would require
-          uint8_t* v = k.temp<uint8_t>(R);
-          tc::launch_subgroup_check_g2(ctx->stream, c_sig, 192, 1, 1, R, v);
-          tc::launch_invalidate_jobs(ctx->stream, v, 1, 1, R, nullptr, nullptr, 0, c_ok);
-          if (hash) {
-            tc::launch_subgroup_check_g2(ctx->stream, c_hash, 192, 1, 1, R, v);
-            tc::launch_invalidate_jobs(ctx->stream, v, 1, 1, R, nullptr, nullptr, 0, c_ok);
-          }
-          tc::launch_subgroup_check_g1(ctx->stream, d_pk, 0, 1, 1, 1, v);
-          tc::launch_invalidate_jobs(ctx->stream, v, 1, (size_t)-1, R, nullptr, nullptr, 0, c_ok);
-        }
-        tc::launch_scatter_bytes(ctx->stream, c_ok, d_map, R, d_ok);
-        k.check(hipStreamSynchronize(ctx->stream), "stream sync");  // the host map goes out of scope
-      }
-      if (n_fallback) *n_fallback = R;
-    }
+  std::vector<uint8_t> h_okg(NG), h_st(2 * NG), h_vkey, h_vsig, h_vhash;
+  if (k.failed) return;
+  tc::launch_rlc_scalars(ctx->stream, d_seed, B, d_r);
+  k.check(hipMemsetAsync(d_st, 0, 2 * NG, ctx->stream), "memset");
+  const uint32_t* rr = reinterpret_cast<const uint32_t*>(d_r);
+  if (G) {
+    msm_g2(k, group, group * 192, d_sig, rr, G, d_S, d_st, /*nbits=*/16, tc::MsmFilter(), /*secret_scalars=*/true);
+    msm_g2(k, group, group * 192, d_hash, rr, G, d_H, d_st + NG, 16, tc::MsmFilter(), true);
   }
+  if (tail) {
+    msm_g2(k, tail, tail * 192, d_sig + G * group * 192, rr + G * group * 8, 1, d_S + G * 192, d_st + G, 16, tc::MsmFilter(), true);
+    msm_g2(k, tail, tail * 192, d_hash + G * group * 192, rr + G * group * 8, 1, d_H + G * 192, d_st + NG + G, 16, tc::MsmFilter(), true);
+  }
+  tc::launch_pairing_check(ctx->stream, d_pk, 0, d_H, 192, d_g1, 0, d_S, 192, NG, d_okg, k.pairing_ws(NG));
+  k.check(hipMemsetAsync(d_ok, 1, B, ctx->stream), "memset");
+  k.readback(h_okg.data(), d_okg, NG, "ok readback");
+  k.readback(h_st.data(), d_st, 2 * NG, "status readback");
+  // checked-input mode: a group that owns a non-member operand goes to the per-job path as well
+  // (the membership tests ran beside the two sums and the group checks)
+  k.take_verdicts({{v_key, &h_vkey}, {v_sig, &h_vsig}, {v_hash, &h_vhash}});
+  k.check(hipStreamSynchronize(ctx->stream), "stream sync");
+  if (k.failed) return;
+  const bool key_bad = !h_vkey.empty() && h_vkey[0] == 0;
+  std::vector<uint8_t> bad(NG);
+  for (size_t g = 0; g < NG; g++) {
+    bool b = key_bad || !h_okg[g] || h_st[g] != TC_JOB_OK || h_st[NG + g] != TC_JOB_OK;
+    const size_t lo = g * group, hi = (lo + group < B) ? lo + group : B;
+    for (const std::vector<uint8_t>* hv : {&h_vsig, &h_vhash})
+      for (size_t j = lo; j < hi && !b && !hv->empty(); j++) b = (*hv)[j] == 0;
+    bad[g] = b;
+  }
+  std::vector<uint32_t> failed;
+  tc::failed_jobs_of_groups(bad.data(), w.cut, B, failed);
+  if (failed.empty()) return;
+  // per-job pairing checks for every job of the failed groups, on compacted operands
+  const size_t R = failed.size();
+  Compacted c(k, R, {&failed});
+  const uint8_t* c_sig = c.gather(d_sig, 192, 0);
+  const uint8_t* c_hash = c.gather(d_hash, 192, 0);
+  const tc::PairingWs pws = k.pairing_ws(R);
+  if (!k.failed) tc::launch_pairing_check(ctx->stream, d_pk, 0, c_hash, 192, d_g1, 0, c_sig, 192, R, c.c_ok, pws);
+  if (member_checks) {  // members only, as the per-job path would require
+    c.members(true, c_sig, 192);
+    if (hash_is_operand) c.members(true, c_hash, 192);
+    c.members(false, d_pk, 0);  // the one key
+  }
+  c.finish(d_ok, 0);
+  if (n_fallback) *n_fallback = R;
 }
 
 // Signature batches under ONE key (BASELINE config 3's shape: 65 536 verifies under the master key) by random linear
@@ -1464,9 +1491,6 @@ static int verify_rlc(tc_ctx* ctx, const uint8_t* pk, const uint8_t* sig, const 
   if (B == 0) return TC_OK;
   TC_REQUIRE(ctx && pk && sig && (hash || off) && seed32 && ok);
   TC_REQUIRE(B < (1ull << 32));
-  if (group == 0) group = 64;
-  if (group > 1024) group = 1024;
-  if (group > B) group = B;
   Call k(ctx);
   uint64_t total = 0;
   if (!hash) {
@@ -1484,12 +1508,12 @@ static int verify_rlc(tc_ctx* ctx, const uint8_t* pk, const uint8_t* sig, const 
   const RlcWs ws = rlc_workspace(k, B, group, seed32);
   uint8_t* d_ok = k.out(ok, B);
   k.begin_timing();
-  k.check_points(false, d_pk, 0, 1, 1, B, 1);
-  k.check_points(true, d_sig, 192, 1, 1, B, 1);
-  if (hash) k.check_points(true, d_hash, 192, 1, 1, B, 1);
+  const uint8_t* v_key = k.check_points(false, d_pk, 0, 1, 1, B, 1);
+  const uint8_t* v_sig = k.check_points(true, d_sig, 192, 1, 1, B, 1);
+  const uint8_t* v_hash = hash ? k.check_points(true, d_hash, 192, 1, 1, B, 1) : nullptr;
   if (!k.failed) {
     if (!hash) tc::launch_hash_g2(ctx->tuning, ctx->stream, d_msgs, d_off, B, d_hash_own, /*fix=*/false);
-    rlc_group_checks(k, ws, d_pk, d_sig, d_hash, d_g1, B, ctx->input_checks, hash != nullptr, d_ok, n_fallback);
+    rlc_group_checks(k, ws, d_pk, d_sig, d_hash, d_g1, B, v_key, v_sig, v_hash, ctx->input_checks, hash != nullptr, d_ok, n_fallback);
   }
   k.end_timing();
   return k.finish();
@@ -1531,17 +1555,14 @@ static int verify_records(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint6
   if (n_fallback) *n_fallback = 0;
   if (M == 0) return TC_OK;
   TC_REQUIRE(ctx && rec_off && (hashes || off) && seed32);
-  if (group == 0) group = 64;
-  if (group > 1024) group = 1024;
-  if (group > M) group = M;
+  const tc::GroupCut cut = tc::group_cut(M, group);  // groups of MESSAGES
+  group = cut.group;
   Call k(ctx);
   std::vector<uint64_t> h_rec;
   if (ctx->device_io) {
     h_rec.resize(M + 1);
-    if (!k.check(hipMemcpyAsync(h_rec.data(), rec_off, (M + 1) * 8, hipMemcpyDeviceToHost, ctx->stream), "offset readback") ||
-        !k.check(hipStreamSynchronize(ctx->stream), "stream sync"))
+    if (!k.readback(h_rec.data(), rec_off, (M + 1) * 8, "offset readback") || !k.check(hipStreamSynchronize(ctx->stream), "stream sync"))
       return k.finish();
-    ctx->d2h_bytes += (M + 1) * 8;
   }
   const uint64_t* hr = ctx->device_io ? h_rec.data() : rec_off;
   bool good = hr[0] == 0;
@@ -1566,7 +1587,7 @@ static int verify_records(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint6
   // the GPU to a few waves), then, when a group has several, the groups as segments over the sums of their pieces.  One
   // descriptor array: [rec_off | chunks of the messages | first records of the pieces | their chunks | first pieces of the
   // groups | their chunks]
-  const size_t NG = tc::rec_groups(M, group);
+  const size_t NG = cut.NG;  // = tc::rec_groups(M, group)
   const size_t simd_lanes = (size_t)(ctx->cus > 0 ? ctx->cus : 256) * 4 * tc::kBlock;  // one wave per SIMD
   const size_t pairs_most = (size_t)tc::kBlock / tc::kG2Lanes;
   std::vector<uint64_t> h_grp(NG + 1);
@@ -1608,14 +1629,8 @@ static int verify_records(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint6
   uint8_t* d_hash = k.temp<uint8_t>(MP * 192);
   const uint8_t* d_g1 = hashes ? ctx->g1_gen : ctx->g1_gen_unfix;
   uint64_t* d_desc = k.temp<uint64_t>(desc.size());
-  uint8_t* d_seed = k.temp<uint8_t>(32);
-  if (d_seed) {
-    k.check(hipMemcpyAsync(d_seed, seed32, 32, hipMemcpyHostToDevice, ctx->stream), "seed copy");
-    ctx->h2d_bytes += 32;
-    k.wipe.emplace_back(d_seed, 32);
-  }
-  uint8_t* d_r = k.temp<uint8_t>(R * 32);
-  if (d_r) k.wipe.emplace_back(d_r, R * 32);
+  uint8_t* d_seed = k.secret_seed(seed32);
+  uint8_t* d_r = k.secret_temp<uint8_t>(R * 32);
   uint8_t* d_keys_own = key_idx ? k.temp<uint8_t>(R * 96) : nullptr;
   const uint8_t* d_keys = key_idx ? d_keys_own : d_pk;  // the key of record r
   uint8_t* d_P = k.temp<uint8_t>(MP * 96);
@@ -1627,39 +1642,28 @@ static int verify_records(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint6
   int32_t* d_tbl1 = k.temp<int32_t>(tc::rec_table_bytes(false, C1) / sizeof(int32_t));
   int32_t* d_tbl2 = k.temp<int32_t>(tc::rec_table_bytes(true, C2) / sizeof(int32_t));
   int32_t* d_tbl3 = k.temp<int32_t>(tc::rec_table_bytes(true, C3) / sizeof(int32_t));
-  uint8_t* d_codes1 = k.temp<uint8_t>(tc::rec_code_bytes(C1));
-  uint8_t* d_codes2 = k.temp<uint8_t>(tc::rec_code_bytes(C2));
+  // (the digit codes are a lossless recoding of the secret scalars: wiped like them; the third sum's scalars are all 1)
+  uint8_t* d_codes1 = k.secret_temp<uint8_t>(tc::rec_code_bytes(C1));
+  uint8_t* d_codes2 = k.secret_temp<uint8_t>(tc::rec_code_bytes(C2));
   uint8_t* d_codes3 = k.temp<uint8_t>(tc::rec_code_bytes(C3));
-  // the digit codes are a lossless recoding of the secret scalars: wiped like them
-  if (d_codes1) k.wipe.emplace_back(d_codes1, tc::rec_code_bytes(C1));
-  if (d_codes2) k.wipe.emplace_back(d_codes2, tc::rec_code_bytes(C2));
   uint8_t* d_ok = k.out(ok, R);
   int32_t* ws_groups = k.pairing_product_ws(group, NG, true);
   k.begin_timing();
   // checked-input mode: every key TABLE entry once (K tests, not R), every signature, every hash operand
-  const uint8_t *v_key = nullptr, *v_sig = nullptr, *v_hash = nullptr;
-  size_t before = k.checks.size();
-  k.check_points(false, d_pk, 96, K, K, 1, (size_t)-1);
-  if (k.checks.size() > before) v_key = k.checks.back().valid;
-  before = k.checks.size();
-  k.check_points(true, d_sig, 192, 1, 1, R, 1);
-  if (k.checks.size() > before) v_sig = k.checks.back().valid;
-  before = k.checks.size();
-  if (hashes) k.check_points(true, d_hash_in, 192, 1, 1, M, 1);
-  if (k.checks.size() > before) v_hash = k.checks.back().valid;
+  const uint8_t* v_key = k.check_points(false, d_pk, 96, K, K, 1, (size_t)-1);
+  const uint8_t* v_sig = k.check_points(true, d_sig, 192, 1, 1, R, 1);
+  const uint8_t* v_hash = hashes ? k.check_points(true, d_hash_in, 192, 1, 1, M, 1) : nullptr;
   std::vector<uint8_t> h_okg(NG), h_st(M + NG + NP), h_vkey, h_vsig, h_vhash, h_pad(pad * (192 + 96), 0);
   std::vector<uint64_t> h_kidx;
   if (!k.failed) {
-    k.check(hipMemcpyAsync(d_desc, desc.data(), desc.size() * 8, hipMemcpyHostToDevice, ctx->stream), "descriptor copy");
-    ctx->h2d_bytes += desc.size() * 8;
+    k.upload(d_desc, desc.data(), desc.size() * 8, "descriptor copy");
     k.check(hipMemsetAsync(d_st, 0, M + NG + NP, ctx->stream), "memset");
     if (!hashes) tc::launch_hash_g2(ctx->tuning, ctx->stream, d_msgs, d_off, M, d_hash, /*fix=*/false);
     else k.check(hipMemcpyAsync(d_hash, d_hash_in, M * 192, hipMemcpyDeviceToDevice, ctx->stream), "hash copy");
     if (pad) {
       for (size_t i = 0; i < pad; i++) h_pad[i * 192] = h_pad[pad * 192 + i * 96] = 0x40;  // the identity of G2 / of G1
-      k.check(hipMemcpyAsync(d_hash + M * 192, h_pad.data(), pad * 192, hipMemcpyHostToDevice, ctx->stream), "pad copy");
-      k.check(hipMemcpyAsync(d_P + M * 96, h_pad.data() + pad * 192, pad * 96, hipMemcpyHostToDevice, ctx->stream), "pad copy");
-      ctx->h2d_bytes += pad * 288;
+      k.upload(d_hash + M * 192, h_pad.data(), pad * 192, "pad copy");
+      k.upload(d_P + M * 96, h_pad.data() + pad * 192, pad * 96, "pad copy");
     }
     tc::launch_rlc_scalars(ctx->stream, d_seed, R, d_r);
     const uint32_t* rr = reinterpret_cast<const uint32_t*>(d_r);
@@ -1680,26 +1684,10 @@ static int verify_records(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint6
     // one pair per message (an empty message: P_m = identity, the factor 1), one final exponentiation per group
     tc::launch_pairing_product_check(ctx->stream, d_P, 96, d_hash, 192, group, NG, d_g1, 0, d_S, 192, d_okg, ws_groups);
     k.check(hipMemsetAsync(d_ok, 1, R, ctx->stream), "memset");
-    k.check(hipMemcpyAsync(h_okg.data(), d_okg, NG, hipMemcpyDeviceToHost, ctx->stream), "ok readback");
-    k.check(hipMemcpyAsync(h_st.data(), d_st, M + NG + NP, hipMemcpyDeviceToHost, ctx->stream), "status readback");
-    ctx->d2h_bytes += M + 2 * NG + NP;
-    k.run_checks();  // (the membership tests ran beside the sums and the group checks; their verdicts are read back below)
-    k.checks.clear();
-    if (v_key) {
-      h_vkey.resize(K);
-      k.check(hipMemcpyAsync(h_vkey.data(), v_key, K, hipMemcpyDeviceToHost, ctx->stream), "valid readback");
-      ctx->d2h_bytes += K;
-    }
-    if (v_sig) {
-      h_vsig.resize(R);
-      k.check(hipMemcpyAsync(h_vsig.data(), v_sig, R, hipMemcpyDeviceToHost, ctx->stream), "valid readback");
-      ctx->d2h_bytes += R;
-    }
-    if (v_hash) {
-      h_vhash.resize(M);
-      k.check(hipMemcpyAsync(h_vhash.data(), v_hash, M, hipMemcpyDeviceToHost, ctx->stream), "valid readback");
-      ctx->d2h_bytes += M;
-    }
+    k.readback(h_okg.data(), d_okg, NG, "ok readback");
+    k.readback(h_st.data(), d_st, M + NG + NP, "status readback");
+    // (the membership tests ran beside the sums and the group checks)
+    k.take_verdicts({{v_key, &h_vkey}, {v_sig, &h_vsig}, {v_hash, &h_vhash}});
     k.check(hipStreamSynchronize(ctx->stream), "stream sync");
     // a bad key fails the groups of the records that NAME it: the indices are needed on the host only then
     bool key_bad = false;
@@ -1707,65 +1695,51 @@ static int verify_records(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint6
     const uint64_t* hk = key_idx;
     if (key_bad && key_idx && ctx->device_io && !k.failed) {
       h_kidx.resize(R);
-      k.check(hipMemcpyAsync(h_kidx.data(), key_idx, R * 8, hipMemcpyDeviceToHost, ctx->stream), "index readback");
+      k.readback(h_kidx.data(), key_idx, R * 8, "index readback");
       k.check(hipStreamSynchronize(ctx->stream), "stream sync");
-      ctx->d2h_bytes += R * 8;
       hk = h_kidx.data();
     }
     std::vector<uint32_t> m_sig, m_hash;
     if (!k.failed) {
+      std::vector<uint8_t> bad_group(NG);
       for (size_t g = 0; g < NG; g++) {
         const size_t mlo = g * group, mhi = (mlo + group < M) ? mlo + group : M;
         const uint64_t rlo = hr[mlo], rhi = hr[mhi];
         bool bad = !h_okg[g] || h_st[M + g] != TC_JOB_OK;
         for (uint64_t q = h_seg3[g]; q < h_seg3[g + 1] && !bad; q++) bad = h_st[M + NG + q] != TC_JOB_OK;
-        for (size_t m = mlo; m < mhi && !bad; m++) bad = h_st[m] != TC_JOB_OK || (v_hash && h_vhash[m] == 0);
-        if (v_sig)
-          for (uint64_t r = rlo; r < rhi && !bad; r++) bad = h_vsig[r] == 0;
+        for (size_t m = mlo; m < mhi && !bad; m++) bad = h_st[m] != TC_JOB_OK || (!h_vhash.empty() && h_vhash[m] == 0);
+        for (uint64_t r = rlo; r < rhi && !bad && !h_vsig.empty(); r++) bad = h_vsig[r] == 0;
         if (key_bad)
           for (uint64_t r = rlo; r < rhi && !bad; r++) {
             const uint64_t i = hk ? hk[r] : r;
             bad = i < K && h_vkey[i] == 0;  // (an index >= K has failed its message in stage T already)
           }
-        if (bad)
-          for (size_t m = mlo; m < mhi; m++)
-            for (uint64_t r = hr[m]; r < hr[m + 1]; r++) {
-              m_sig.push_back((uint32_t)r);
-              m_hash.push_back((uint32_t)m);
-            }
+        bad_group[g] = bad;
       }
+      // every record of the messages of the bad groups
+      std::vector<uint32_t> bad_msgs;
+      tc::failed_jobs_of_groups(bad_group.data(), cut, M, bad_msgs);
+      for (uint32_t m : bad_msgs)
+        for (uint64_t r = hr[m]; r < hr[m + 1]; r++) {
+          m_sig.push_back((uint32_t)r);
+          m_hash.push_back(m);
+        }
     }
     if (!k.failed && !m_sig.empty()) {
       // the per-record check of tc_verify_g2_batch for every record of the failed groups, on compacted operands
       const size_t F = m_sig.size();
-      uint32_t* d_maps = k.temp<uint32_t>(2 * F);
-      uint8_t* c_sig = k.temp<uint8_t>(F * 192);
-      uint8_t* c_hash = k.temp<uint8_t>(F * 192);
-      uint8_t* c_pk = k.temp<uint8_t>(F * 96);
-      uint8_t* c_ok = k.temp<uint8_t>(F);
-      uint8_t* vv = ctx->input_checks ? k.temp<uint8_t>(F) : nullptr;
+      Compacted c(k, F, {&m_sig, &m_hash});
+      const uint8_t* c_sig = c.gather(d_sig, 192, 0);
+      const uint8_t* c_hash = c.gather(d_hash, 192, 1);
+      const uint8_t* c_pk = c.gather(d_keys, 96, 0);
       const tc::PairingWs pws = k.pairing_ws(F);
-      if (!k.failed) {
-        k.check(hipMemcpyAsync(d_maps, m_sig.data(), F * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
-        k.check(hipMemcpyAsync(d_maps + F, m_hash.data(), F * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
-        ctx->h2d_bytes += 8 * F;
-        tc::launch_gather_rows(ctx->stream, d_sig, 192, d_maps, F, c_sig);
-        tc::launch_gather_rows(ctx->stream, d_hash, 192, d_maps + F, F, c_hash);
-        tc::launch_gather_rows(ctx->stream, d_keys, 96, d_maps, F, c_pk);
-        tc::launch_pairing_check(ctx->stream, c_pk, 96, c_hash, 192, d_g1, 0, c_sig, 192, F, c_ok, pws);  // src/lib.rs:109
-        if (ctx->input_checks) {  // members only, as the per-record path would require
-          tc::launch_subgroup_check_g1(ctx->stream, c_pk, 96, 1, 1, F, vv);
-          tc::launch_invalidate_jobs(ctx->stream, vv, 1, 1, F, nullptr, nullptr, 0, c_ok);
-          tc::launch_subgroup_check_g2(ctx->stream, c_sig, 192, 1, 1, F, vv);
-          tc::launch_invalidate_jobs(ctx->stream, vv, 1, 1, F, nullptr, nullptr, 0, c_ok);
-          if (hashes) {
-            tc::launch_subgroup_check_g2(ctx->stream, c_hash, 192, 1, 1, F, vv);
-            tc::launch_invalidate_jobs(ctx->stream, vv, 1, 1, F, nullptr, nullptr, 0, c_ok);
-          }
-        }
-        tc::launch_scatter_bytes(ctx->stream, c_ok, d_maps, F, d_ok);
-        k.check(hipStreamSynchronize(ctx->stream), "stream sync");  // the host maps go out of scope
+      if (!k.failed) tc::launch_pairing_check(ctx->stream, c_pk, 96, c_hash, 192, d_g1, 0, c_sig, 192, F, c.c_ok, pws);  // src/lib.rs:109
+      if (ctx->input_checks) {  // members only, as the per-record path would require
+        c.members(false, c_pk, 96);
+        c.members(true, c_sig, 192);
+        if (hashes) c.members(true, c_hash, 192);
       }
+      c.finish(d_ok, 0);
       if (n_fallback) *n_fallback = F;
     }
   }
@@ -1850,9 +1824,9 @@ int tc_ciphertext_verify_rlc_batch(tc_ctx* ctx, const uint8_t* u, const uint8_t*
   if (B == 0) return TC_OK;
   TC_REQUIRE(ctx && u && off && w && seed32 && ok);
   TC_REQUIRE(B < (1ull << 32));
-  if (group == 0) group = 64;
-  if (group > 1024) group = 1024;
-  if (group > B) group = B;
+  const tc::GroupCut cut = tc::group_cut(B, group);
+  group = cut.group;
+  const size_t G = cut.G, tail = cut.tail, NG = cut.NG;
   Call k(ctx);
   uint64_t total = 0;
   if (!total_bytes(k, off, B, &total)) return k.finish();
@@ -1861,15 +1835,8 @@ int tc_ciphertext_verify_rlc_batch(tc_ctx* ctx, const uint8_t* u, const uint8_t*
   const uint8_t* d_v = k.in(v, (size_t)total);
   const uint64_t* d_off = k.in(off, B + 1);
   const uint8_t* d_w = k.in(w, B * 192);
-  uint8_t* d_seed = k.temp<uint8_t>(32);
-  if (d_seed) {
-    k.check(hipMemcpyAsync(d_seed, seed32, 32, hipMemcpyHostToDevice, ctx->stream), "seed copy");
-    ctx->h2d_bytes += 32;
-    k.wipe.emplace_back(d_seed, 32);
-  }
-  uint8_t* d_r = k.temp<uint8_t>(B * 32);
-  if (d_r) k.wipe.emplace_back(d_r, B * 32);
-  const size_t G = B / group, tail = B % group, NG = G + (tail ? 1 : 0);
+  uint8_t* d_seed = k.secret_seed(seed32);
+  uint8_t* d_r = k.secret_temp<uint8_t>(B * 32);
   uint8_t* d_hash = k.temp<uint8_t>(B * 192);
   uint8_t* d_ru = k.temp<uint8_t>(B * 96);     // r_j u_j
   uint8_t* d_W = k.temp<uint8_t>(NG * 192);    // sum_j r_j w_j per group
@@ -1879,9 +1846,9 @@ int tc_ciphertext_verify_rlc_batch(tc_ctx* ctx, const uint8_t* u, const uint8_t*
   int32_t* ws_groups = G ? k.pairing_product_ws(group, G, true) : nullptr;
   int32_t* ws_tail = tail ? k.pairing_product_ws(tail, 1, true) : nullptr;
   k.begin_timing();
-  k.check_points(false, d_u, 96, 1, 1, B, 1);
-  k.check_points(true, d_w, 192, 1, 1, B, 1);
-  std::vector<uint8_t> h_okg(NG), h_st(2 * B + NG), h_valid;
+  const uint8_t* v_u = k.check_points(false, d_u, 96, 1, 1, B, 1);
+  const uint8_t* v_w = k.check_points(true, d_w, 192, 1, 1, B, 1);
+  std::vector<uint8_t> h_okg(NG), h_st(2 * B + NG), h_vu, h_vw;
   if (!k.failed) {
     k.check(hipMemsetAsync(d_st, 0, 2 * B + NG, ctx->stream), "memset");
     // an undecodable u leaves a hash that does not decode either (and a status): its group falls back
@@ -1898,60 +1865,39 @@ int tc_ciphertext_verify_rlc_batch(tc_ctx* ctx, const uint8_t* u, const uint8_t*
       tc::launch_pairing_product_check(ctx->stream, d_ru + G * group * 96, 96, d_hash + G * group * 192, 192, tail, 1, ctx->g1_gen_unfix, 0,
                                        d_W + G * 192, 192, d_okg + G, ws_tail);
     k.check(hipMemsetAsync(d_ok, 1, B, ctx->stream), "memset");
-    k.check(hipMemcpyAsync(h_okg.data(), d_okg, NG, hipMemcpyDeviceToHost, ctx->stream), "ok readback");
-    k.check(hipMemcpyAsync(h_st.data(), d_st, 2 * B + NG, hipMemcpyDeviceToHost, ctx->stream), "status readback");
-    ctx->d2h_bytes += 2 * NG + 2 * B;
+    k.readback(h_okg.data(), d_okg, NG, "ok readback");
+    k.readback(h_st.data(), d_st, 2 * B + NG, "status readback");
     // checked-input mode: a group that owns a non-member operand goes to the per-ciphertext path as well
-    std::vector<const uint8_t*> valid_ptrs;
-    k.run_checks();  // (the membership tests ran beside the sums and the group checks; their verdicts are read back below)
-    for (auto& p : k.checks) valid_ptrs.push_back(p.valid);
-    const size_t n_checks = k.checks.size();
-    k.checks.clear();
-    if (n_checks) {
-      h_valid.resize(n_checks * B);
-      for (size_t q = 0; q < n_checks; q++)
-        k.check(hipMemcpyAsync(h_valid.data() + q * B, valid_ptrs[q], B, hipMemcpyDeviceToHost, ctx->stream), "valid readback");
-      ctx->d2h_bytes += n_checks * B;
-    }
+    // (the membership tests ran beside the sums and the group checks)
+    k.take_verdicts({{v_u, &h_vu}, {v_w, &h_vw}});
     k.check(hipStreamSynchronize(ctx->stream), "stream sync");
     std::vector<uint32_t> failed;
     if (!k.failed) {
+      std::vector<uint8_t> bad_group(NG);
       for (size_t g = 0; g < NG; g++) {
         bool bad = !h_okg[g] || h_st[2 * B + g] != TC_JOB_OK;
         const size_t lo = g * group, hi = (lo + group < B) ? lo + group : B;
         for (size_t j = lo; j < hi && !bad; j++) bad = h_st[j] != TC_JOB_OK || h_st[B + j] != TC_JOB_OK;
-        for (size_t q = 0; q < n_checks && !bad; q++)
-          for (size_t j = lo; j < hi && !bad; j++) bad = h_valid[q * B + j] == 0;
-        if (bad)
-          for (size_t j = lo; j < hi; j++) failed.push_back((uint32_t)j);
+        for (const std::vector<uint8_t>* hv : {&h_vu, &h_vw})
+          for (size_t j = lo; j < hi && !bad && !hv->empty(); j++) bad = (*hv)[j] == 0;
+        bad_group[g] = bad;
       }
+      tc::failed_jobs_of_groups(bad_group.data(), cut, B, failed);
     }
     if (!k.failed && !failed.empty()) {
       // the per-ciphertext check of tc_ciphertext_verify_batch for every ciphertext of the failed groups, on compacted operands
       const size_t R = failed.size();
-      uint32_t* d_map = k.temp<uint32_t>(R);
-      uint8_t* c_u = k.temp<uint8_t>(R * 96);
-      uint8_t* c_hash = k.temp<uint8_t>(R * 192);
-      uint8_t* c_w = k.temp<uint8_t>(R * 192);
-      uint8_t* c_ok = k.temp<uint8_t>(R);
-      uint8_t* vv = ctx->input_checks ? k.temp<uint8_t>(R) : nullptr;
+      Compacted c(k, R, {&failed});
+      const uint8_t* c_u = c.gather(d_u, 96, 0);
+      const uint8_t* c_hash = c.gather(d_hash, 192, 0);
+      const uint8_t* c_w = c.gather(d_w, 192, 0);
       const tc::PairingWs pws = k.pairing_ws(R);
-      if (!k.failed) {
-        k.check(hipMemcpyAsync(d_map, failed.data(), R * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
-        ctx->h2d_bytes += 4 * R;
-        tc::launch_gather_rows(ctx->stream, d_u, 96, d_map, R, c_u);
-        tc::launch_gather_rows(ctx->stream, d_hash, 192, d_map, R, c_hash);
-        tc::launch_gather_rows(ctx->stream, d_w, 192, d_map, R, c_w);
-        tc::launch_pairing_check(ctx->stream, ctx->g1_gen_unfix, 0, c_w, 192, c_u, 96, c_hash, 192, R, c_ok, pws);  // src/lib.rs:511
-        if (ctx->input_checks) {  // members only, as the per-ciphertext path would require
-          tc::launch_subgroup_check_g1(ctx->stream, c_u, 96, 1, 1, R, vv);
-          tc::launch_invalidate_jobs(ctx->stream, vv, 1, 1, R, nullptr, nullptr, 0, c_ok);
-          tc::launch_subgroup_check_g2(ctx->stream, c_w, 192, 1, 1, R, vv);
-          tc::launch_invalidate_jobs(ctx->stream, vv, 1, 1, R, nullptr, nullptr, 0, c_ok);
-        }
-        tc::launch_scatter_bytes(ctx->stream, c_ok, d_map, R, d_ok);
-        k.check(hipStreamSynchronize(ctx->stream), "stream sync");  // the host map goes out of scope
+      if (!k.failed) tc::launch_pairing_check(ctx->stream, ctx->g1_gen_unfix, 0, c_w, 192, c_u, 96, c_hash, 192, R, c.c_ok, pws);  // src/lib.rs:511
+      if (ctx->input_checks) {  // members only, as the per-ciphertext path would require
+        c.members(false, c_u, 96);
+        c.members(true, c_w, 192);
       }
+      c.finish(d_ok, 0);
       if (n_fallback) *n_fallback = R;
     }
   }
@@ -2086,14 +2032,8 @@ int tc_verify_decryption_shares_rlc_batch(tc_ctx* ctx, const uint8_t* pk_shares,
   const uint8_t* d_v = k.in(v, (size_t)total);
   const uint64_t* d_off = k.in(off, B + 1);
   const uint8_t* d_w = k.in(w, B * 192);
-  uint8_t* d_seed = k.temp<uint8_t>(32);
-  if (d_seed) {
-    k.check(hipMemcpyAsync(d_seed, seed32, 32, hipMemcpyHostToDevice, ctx->stream), "seed copy");
-    ctx->h2d_bytes += 32;
-    k.wipe.emplace_back(d_seed, 32);
-  }
-  uint8_t* d_r = k.temp<uint8_t>(B * N * 32);
-  if (d_r) k.wipe.emplace_back(d_r, B * N * 32);
+  uint8_t* d_seed = k.secret_seed(seed32);
+  uint8_t* d_r = k.secret_temp<uint8_t>(B * N * 32);
   uint8_t* d_hash = k.temp<uint8_t>(B * 192);
   uint8_t* d_D = k.temp<uint8_t>(B * 96);
   uint8_t* d_Dc = k.temp<uint8_t>(B * 96);
@@ -2119,9 +2059,8 @@ int tc_verify_decryption_shares_rlc_batch(tc_ctx* ctx, const uint8_t* pk_shares,
     tc::launch_pairing_check(ctx->stream, d_Dc, 96, d_hash, 192, d_P, 96, d_w, 192, B, d_okct, k.pairing_ws(B));
     k.apply_checks(B, nullptr, nullptr, 0, d_okct);  // checked-input mode: a ciphertext owning a non-member operand falls back
     k.check(hipMemsetAsync(d_ok, 1, B * N, ctx->stream), "memset");
-    k.check(hipMemcpyAsync(h_okct.data(), d_okct, B, hipMemcpyDeviceToHost, ctx->stream), "ok readback");
-    k.check(hipMemcpyAsync(h_st.data(), d_st, 3 * B, hipMemcpyDeviceToHost, ctx->stream), "status readback");
-    ctx->d2h_bytes += 4 * B;
+    k.readback(h_okct.data(), d_okct, B, "ok readback");
+    k.readback(h_st.data(), d_st, 3 * B, "status readback");
     k.check(hipStreamSynchronize(ctx->stream), "stream sync");
     std::vector<uint32_t> failed;
     if (!k.failed)
@@ -2130,51 +2069,28 @@ int tc_verify_decryption_shares_rlc_batch(tc_ctx* ctx, const uint8_t* pk_shares,
     if (!k.failed && !failed.empty()) {
       // per-share pairing checks for every share of the failed ciphertexts, on compacted operands
       const size_t F = failed.size(), R = F * N;
-      std::vector<uint32_t> m_sh(R), m_ct(R), m_pk(R);
-      for (size_t f = 0; f < F; f++)
-        for (size_t i = 0; i < N; i++) {
-          m_sh[f * N + i] = (uint32_t)(failed[f] * N + i);
-          m_ct[f * N + i] = failed[f];
-          m_pk[f * N + i] = (uint32_t)i;
-        }
-      uint32_t* d_maps = k.temp<uint32_t>(3 * R);
-      uint8_t* c_sh = k.temp<uint8_t>(R * 96);
+      const tc::SlotMaps m = tc::slot_maps(failed.data(), F, N);
+      Compacted c(k, R, {&m.record, &m.job, &m.slot});
+      const uint8_t* c_sh = c.gather(d_sh, 96, 0);
+      const uint8_t* c_hash = c.gather(d_hash, 192, 1);
+      const uint8_t* c_w = c.gather(d_w, 192, 1);
+      const uint8_t* c_pk = c.gather(d_pk, 96, 2);
       uint8_t* c_shc = k.temp<uint8_t>(R * 96);
-      uint8_t* c_hash = k.temp<uint8_t>(R * 192);
-      uint8_t* c_w = k.temp<uint8_t>(R * 192);
-      uint8_t* c_pk = k.temp<uint8_t>(R * 96);
-      uint8_t* c_ok = k.temp<uint8_t>(R);
+      const tc::PairingWs pws = k.pairing_ws(R);
       if (!k.failed) {
-        k.check(hipMemcpyAsync(d_maps, m_sh.data(), R * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
-        k.check(hipMemcpyAsync(d_maps + R, m_ct.data(), R * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
-        k.check(hipMemcpyAsync(d_maps + 2 * R, m_pk.data(), R * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
-        ctx->h2d_bytes += 12 * R;
-        tc::launch_gather_rows(ctx->stream, d_sh, 96, d_maps, R, c_sh);
-        tc::launch_gather_rows(ctx->stream, d_hash, 192, d_maps + R, R, c_hash);
-        tc::launch_gather_rows(ctx->stream, d_w, 192, d_maps + R, R, c_w);
-        tc::launch_gather_rows(ctx->stream, d_pk, 96, d_maps + 2 * R, R, c_pk);
+        // e([c] share, Q') == e(pk, w), the cofactor constant on the share side as in the combined check above
         tc::launch_g1_scale_cofactor_fix(ctx->stream, c_sh, 96, R, c_shc);
-        tc::launch_pairing_check(ctx->stream, c_shc, 96, c_hash, 192, c_pk, 96, c_w, 192, R, c_ok, k.pairing_ws(R));
-        if (ctx->input_checks) {  // members only, as the per-share path would require
-          uint8_t* vv = k.temp<uint8_t>(R);
-          tc::launch_subgroup_check_g1(ctx->stream, c_sh, 96, 1, 1, R, vv);
-          tc::launch_invalidate_jobs(ctx->stream, vv, 1, 1, R, nullptr, nullptr, 0, c_ok);
-          tc::launch_subgroup_check_g1(ctx->stream, c_pk, 96, 1, 1, R, vv);
-          tc::launch_invalidate_jobs(ctx->stream, vv, 1, 1, R, nullptr, nullptr, 0, c_ok);
-          tc::launch_subgroup_check_g2(ctx->stream, c_w, 192, 1, 1, R, vv);
-          tc::launch_invalidate_jobs(ctx->stream, vv, 1, 1, R, nullptr, nullptr, 0, c_ok);
-          // ... and u, which tc_verify_decryption_share_batch checks too (an on-curve u outside G1 used to
-          // reach the bare pairing result here)
-          uint8_t* c_u = k.temp<uint8_t>(R * 96);
-          if (c_u) {
-            tc::launch_gather_rows(ctx->stream, d_u, 96, d_maps + R, R, c_u);
-            tc::launch_subgroup_check_g1(ctx->stream, c_u, 96, 1, 1, R, vv);
-            tc::launch_invalidate_jobs(ctx->stream, vv, 1, 1, R, nullptr, nullptr, 0, c_ok);
-          }
-        }
-        tc::launch_scatter_bytes(ctx->stream, c_ok, d_maps, R, d_ok);
-        k.check(hipStreamSynchronize(ctx->stream), "stream sync");  // the host maps go out of scope
+        tc::launch_pairing_check(ctx->stream, c_shc, 96, c_hash, 192, c_pk, 96, c_w, 192, R, c.c_ok, pws);
       }
+      if (ctx->input_checks) {  // members only, as the per-share path would require
+        c.members(false, c_sh, 96);
+        c.members(false, c_pk, 96);
+        c.members(true, c_w, 192);
+        // ... and u, which tc_verify_decryption_share_batch checks too (an on-curve u outside G1 used to
+        // reach the bare pairing result here)
+        c.members(false, c.gather(d_u, 96, 1), 96);
+      }
+      c.finish(d_ok, 0);
       if (n_fallback) *n_fallback = F;
     }
   }
@@ -2201,10 +2117,8 @@ static void blame_pass(Call& k, bool sig, bool wire, size_t N, const std::vector
   uint8_t* c_pres = k.temp<uint8_t>(R);
   uint8_t* c_live = k.temp<uint8_t>(R);
   uint8_t* c_v = k.temp<uint8_t>(R);
-  uint8_t* d_key = k.temp<uint8_t>(32);
-  uint8_t* d_seed = k.temp<uint8_t>(32);
-  if (d_key) k.wipe.emplace_back(d_key, 32);
-  if (d_seed) k.wipe.emplace_back(d_seed, 32);
+  uint8_t* d_key = k.secret_temp<uint8_t>(32);
+  uint8_t* d_seed = k.secret_temp<uint8_t>(32);
   const size_t leaf_s = tc::blame_leaf_bytes(sig), leaf_pk = tc::blame_leaf_bytes(false);
   size_t Fc = msm_table_budget(k) / (N * (leaf_s + leaf_pk));
   if (Fc < 1) Fc = 1;
@@ -2221,15 +2135,12 @@ static void blame_pass(Call& k, bool sig, bool wire, size_t N, const std::vector
   if (wire) {
     tc::launch_ok_and_status(ctx->stream, c_dec, R, c_live);  // (the checked decode has tested membership)
   } else if (ctx->input_checks) {
-    if (sig) tc::launch_subgroup_check_g2(ctx->stream, c_sh, 192, 1, 1, R, c_v);
-    else tc::launch_subgroup_check_g1(ctx->stream, c_sh, 96, 1, 1, R, c_v);
-    tc::launch_invalidate_jobs(ctx->stream, c_v, 1, 1, R, nullptr, nullptr, 0, c_live);
+    k.require_members(sig, c_sh, PB, R, c_v, c_live);
   }
   tc::launch_gather_bytes(ctx->stream, d_jvalid, d_maps + R, R, c_v);
   tc::launch_invalidate_jobs(ctx->stream, c_v, 1, 1, R, nullptr, nullptr, 0, c_live);
   // this call's scalars: ChaCha20 under a seed of its own, derived from the context's key and call counter
-  k.check(hipMemcpyAsync(d_key, ctx->blame_key, 32, hipMemcpyHostToDevice, ctx->stream), "key copy");
-  ctx->h2d_bytes += 32;
+  k.upload(d_key, ctx->blame_key, 32, "key copy");
   tc::launch_blame_seed(ctx->stream, d_key, ctx->blame_calls++, d_seed);
   std::vector<uint8_t> h_pres, h_live, h_bad, h_verdict;
   std::vector<tc::BlameSearch> search;
@@ -2243,9 +2154,8 @@ static void blame_pass(Call& k, bool sig, bool wire, size_t N, const std::vector
     h_pres.resize(rows);
     h_live.resize(rows);
     h_bad.assign(rows, 0);
-    k.check(hipMemcpyAsync(h_pres.data(), c_pres + f0 * N, rows, hipMemcpyDeviceToHost, ctx->stream), "present readback");
-    k.check(hipMemcpyAsync(h_live.data(), c_live + f0 * N, rows, hipMemcpyDeviceToHost, ctx->stream), "live readback");
-    ctx->d2h_bytes += 2 * rows;
+    k.readback(h_pres.data(), c_pres + f0 * N, rows, "present readback");
+    k.readback(h_live.data(), c_live + f0 * N, rows, "live readback");
     if (!k.check(hipStreamSynchronize(ctx->stream), "stream sync")) break;
     search.assign(cnt, tc::BlameSearch());
     for (size_t f = 0; f < cnt; f++) search[f].start((uint32_t)N, h_pres.data() + f * N, h_live.data() + f * N, h_bad.data() + f * N);
@@ -2276,8 +2186,7 @@ static void blame_pass(Call& k, bool sig, bool wire, size_t N, const std::vector
       uint8_t* s_ok = k.temp<uint8_t>(n);
       const tc::PairingWs pws = k.pairing_ws(n);
       if (k.failed) break;
-      k.check(hipMemcpyAsync(d_items, items.data(), 16 * n, hipMemcpyHostToDevice, ctx->stream), "item copy");
-      ctx->h2d_bytes += 16 * n;
+      k.upload(d_items, items.data(), 16 * n, "item copy");
       tc::launch_blame_range_sum(ctx->stream, sig, d_leaf_s, N, d_items, d_items + n, d_items + 2 * n, n, tc::blame_sum_parts(sig, n, longest, ctx->cus), s_sh);
       tc::launch_blame_range_sum(ctx->stream, false, d_leaf_pk, N, d_items, d_items + n, d_items + 2 * n, n, tc::blame_sum_parts(false, n, longest, ctx->cus),
                                  s_pk);
@@ -2292,8 +2201,7 @@ static void blame_pass(Call& k, bool sig, bool wire, size_t N, const std::vector
         tc::launch_pairing_check(ctx->stream, s_shc, 96, s_hash, 192, s_pk, 96, s_w, 192, n, s_ok, pws);
       }
       h_verdict.resize(n);
-      k.check(hipMemcpyAsync(h_verdict.data(), s_ok, n, hipMemcpyDeviceToHost, ctx->stream), "verdict readback");
-      ctx->d2h_bytes += n;
+      k.readback(h_verdict.data(), s_ok, n, "verdict readback");
       k.check(hipStreamSynchronize(ctx->stream), "stream sync");
       ctx->next_slot = mark;
       if (k.failed) break;
@@ -2337,9 +2245,6 @@ static int robust_combine(tc_ctx* ctx, bool sig, bool wire, const uint8_t* commi
   TC_REQUIRE(N < (1ull << 32) && B < (1ull << 32) && B * N < (1ull << 32));
   if (sig) TC_REQUIRE(seed32 && ((hashes != nullptr) != (off != nullptr)));
   else TC_REQUIRE(u && off && w);
-  if (group == 0) group = 64;
-  if (group > 1024) group = 1024;
-  if (group > B) group = B;
   const size_t PB = sig ? 192 : 96, need = t + 1;
   const size_t SB = wire ? PB / 2 : PB;  // bytes per share in the caller's array
   Call k(ctx);
@@ -2404,8 +2309,7 @@ static int robust_combine(tc_ctx* ctx, bool sig, bool wire, const uint8_t* commi
   std::vector<uint8_t> h_verdict(B), h_pkst(N), h_cval(need, 1);
   std::vector<uint32_t> failed;
   if (!k.failed) {
-    k.check(hipMemcpyAsync(d_pkidx, h_slots.data(), N * 8, hipMemcpyHostToDevice, ctx->stream), "index copy");
-    ctx->h2d_bytes += N * 8;
+    k.upload(d_pkidx, h_slots.data(), N * 8, "index copy");
     tc::launch_commitment_evaluate(ctx->stream, d_commit, t, d_pkidx, N, d_pks, d_pkst);
     if (ctx->input_checks) tc::launch_subgroup_check_g1(ctx->stream, d_commit, 96, need, need, need, d_cval);
     // pass 1: the first t+1 present shares, whatever they are
@@ -2430,10 +2334,7 @@ static int robust_combine(tc_ctx* ctx, bool sig, bool wire, const uint8_t* commi
     k.check(hipMemsetAsync(d_jvalid, 1, B, ctx->stream), "memset");
     if (sig) {
       if (hashes) {
-        if (ctx->input_checks) {
-          tc::launch_subgroup_check_g2(ctx->stream, d_hash, 192, 1, 1, B, d_jtmp);
-          tc::launch_invalidate_jobs(ctx->stream, d_jtmp, 1, 1, B, nullptr, nullptr, 0, d_jvalid);
-        }
+        if (ctx->input_checks) k.require_members(true, d_hash, 192, B, d_jtmp, d_jvalid);
       } else {
         tc::launch_hash_g2(ctx->tuning, ctx->stream, d_msgs, d_off, B, d_hash_own, /*fix=*/false);
       }
@@ -2444,15 +2345,14 @@ static int robust_combine(tc_ctx* ctx, bool sig, bool wire, const uint8_t* commi
         tc::launch_invalidate_jobs(ctx->stream, d_cmem, 1, 1, B, nullptr, d_hash_chk, 192, nullptr);
         d_hash_rlc = d_hash_chk;
       }
-      rlc_group_checks(k, ws, d_commit, d_comb, d_hash_rlc, d_g1, B, /*member_checks=*/false, /*hash_is_operand=*/false, d_ok1, nullptr);
+      rlc_group_checks(k, ws, d_commit, d_comb, d_hash_rlc, d_g1, B, nullptr, nullptr, nullptr, /*member_checks=*/false, /*hash_is_operand=*/false,
+                       d_ok1, nullptr);
     } else {
       tc::launch_hash_g1_g2(ctx->tuning, ctx->stream, d_u, d_msgs, d_off, B, d_hash_own, d_jtmp, /*fix=*/false);
       tc::launch_ok_and_status(ctx->stream, d_jtmp, B, d_jvalid);
       if (ctx->input_checks) {
-        tc::launch_subgroup_check_g1(ctx->stream, d_u, 96, 1, 1, B, d_jtmp);
-        tc::launch_invalidate_jobs(ctx->stream, d_jtmp, 1, 1, B, nullptr, nullptr, 0, d_jvalid);
-        tc::launch_subgroup_check_g2(ctx->stream, d_w, 192, 1, 1, B, d_jtmp);
-        tc::launch_invalidate_jobs(ctx->stream, d_jtmp, 1, 1, B, nullptr, nullptr, 0, d_jvalid);
+        k.require_members(false, d_u, 96, B, d_jtmp, d_jvalid);
+        k.require_members(true, d_w, 192, B, d_jtmp, d_jvalid);
       }
       // verify_decryption_share of the COMBINATION under the master key: e(g, H) = e([c] g, Q') == e(commit[0], w)
       tc::launch_g1_scale_cofactor_fix(ctx->stream, d_comb, 96, B, d_combc);
@@ -2461,13 +2361,9 @@ static int robust_combine(tc_ctx* ctx, bool sig, bool wire, const uint8_t* commi
     tc::launch_invalidate_jobs(ctx->stream, d_jvalid, 1, 1, B, nullptr, nullptr, 0, d_ok1);
     if (wire) tc::launch_invalidate_jobs(ctx->stream, d_cmem, 1, 1, B, nullptr, nullptr, 0, d_ok1);
     tc::launch_robust_finish(ctx->stream, nullptr, N, need, PB, B, d_enough, d_st1, d_ok1, d_member, d_comb, d_res, d_status, d_used, d_verdict);
-    k.check(hipMemcpyAsync(h_verdict.data(), d_verdict, B, hipMemcpyDeviceToHost, ctx->stream), "verdict readback");
-    k.check(hipMemcpyAsync(h_pkst.data(), d_pkst, N, hipMemcpyDeviceToHost, ctx->stream), "status readback");
-    ctx->d2h_bytes += B + N;
-    if (ctx->input_checks) {
-      k.check(hipMemcpyAsync(h_cval.data(), d_cval, need, hipMemcpyDeviceToHost, ctx->stream), "valid readback");
-      ctx->d2h_bytes += need;
-    }
+    k.readback(h_verdict.data(), d_verdict, B, "verdict readback");
+    k.readback(h_pkst.data(), d_pkst, N, "status readback");
+    if (ctx->input_checks) k.readback(h_cval.data(), d_cval, need, "valid readback");
     k.check(hipStreamSynchronize(ctx->stream), "stream sync");
   }
   bool commit_bad = false;
@@ -2490,24 +2386,15 @@ static int robust_combine(tc_ctx* ctx, bool sig, bool wire, const uint8_t* commi
     // operands (PublicKeyShare::verify src/lib.rs:177-179 / verify_decryption_share :182-186); the verdict of an absent slot
     // is dropped by k_robust_mark
     const size_t F = failed.size(), R = F * N;
-    std::vector<uint32_t> m_rec(R), m_job(R), m_pk(R);
-    for (size_t f = 0; f < F; f++)
-      for (size_t i = 0; i < N; i++) {
-        m_rec[f * N + i] = (uint32_t)(failed[f] * N + i);
-        m_job[f * N + i] = failed[f];
-        m_pk[f * N + i] = (uint32_t)i;
-      }
-    uint32_t* d_maps = k.temp<uint32_t>(3 * R + F);
-    uint8_t* c_sh = k.temp<uint8_t>(R * PB);
-    uint8_t* c_wire = wire ? k.temp<uint8_t>(R * SB) : nullptr;
+    const tc::SlotMaps m = tc::slot_maps(failed.data(), F, N);
+    Compacted c(k, R, {&m.record, &m.job, &m.slot, &failed});
+    const uint32_t *d_maps = c.map(0), *d_fmap = c.map(3);  // (record | job | slot maps, R entries each, then the F failed jobs)
+    uint8_t* c_ok = c.c_ok;
+    // wire: the full checked decode of from_bytes (curve AND subgroup); a failure leaves the identity -- decodable input for the
+    // pairing kernel -- and its verdict goes into c_ok below
+    const uint8_t* c_wire = wire ? c.gather(d_sh, SB, 0) : nullptr;
     uint8_t* c_dec = wire ? k.temp<uint8_t>(R) : nullptr;
-    uint8_t* c_shc = sig || bisect ? nullptr : k.temp<uint8_t>(R * 96);
-    // (the per-share checks read one hash point / w / key share per record; the range checks of the bisection gather theirs per round)
-    uint8_t* c_hash = bisect ? nullptr : k.temp<uint8_t>(R * 192);
-    uint8_t* c_w = sig || bisect ? nullptr : k.temp<uint8_t>(R * 192);
-    uint8_t* c_pk = bisect ? nullptr : k.temp<uint8_t>(R * 96);
-    uint8_t* c_ok = k.temp<uint8_t>(R);
-    uint8_t* c_v = bisect ? nullptr : k.temp<uint8_t>(R);
+    uint8_t* c_sh = wire ? k.temp<uint8_t>(R * PB) : c.gather(d_sh, PB, 0);
     std::vector<uint8_t> h_ok;  // bisection: the verdicts come from the host's search
     uint8_t* c_present = k.temp<uint8_t>(R);
     uint8_t* c_bad = k.temp<uint8_t>(R);
@@ -2517,59 +2404,51 @@ static int robust_combine(tc_ctx* ctx, bool sig, bool wire, const uint8_t* commi
     uint8_t* d_packed2 = k.temp<uint8_t>(F * need * PB);
     uint8_t* d_comb2 = k.temp<uint8_t>(F * PB);
     uint8_t* d_st2 = k.temp<uint8_t>(F, /*zero=*/true);
-    if (!k.failed) {
-      uint32_t* d_fmap = d_maps + 3 * R;
-      k.check(hipMemcpyAsync(d_maps, m_rec.data(), R * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
-      k.check(hipMemcpyAsync(d_maps + R, m_job.data(), R * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
-      k.check(hipMemcpyAsync(d_maps + 2 * R, m_pk.data(), R * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
-      k.check(hipMemcpyAsync(d_fmap, failed.data(), F * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
-      ctx->h2d_bytes += 12 * R + 4 * F;
-      if (wire) {
-        // the full checked decode of from_bytes (curve AND subgroup); a failure leaves the identity -- decodable input for the
-        // pairing kernel -- and its verdict goes into c_ok below
-        tc::launch_gather_rows(ctx->stream, d_sh, SB, d_maps, R, c_wire);
-        if (sig) tc::launch_g2_decompress(ctx->tuning, ctx->stream, c_wire, R, c_sh, c_dec);
-        else tc::launch_g1_decompress(ctx->stream, c_wire, R, c_sh, c_dec);
-      } else {
-        tc::launch_gather_rows(ctx->stream, d_sh, PB, d_maps, R, c_sh);
-      }
-      if (bisect) {
-        // which checks run is the ONLY difference: ranges of slots, halved where they fail (blame_pass), instead of every slot
-        blame_pass(k, sig, wire, N, failed, d_maps, c_sh, c_dec, d_present, d_jvalid, d_pks, d_hash, d_w, d_g1, h_ok);
-        if (!k.failed) {
-          k.check(hipMemcpyAsync(c_ok, h_ok.data(), R, hipMemcpyHostToDevice, ctx->stream), "verdict copy");
-          ctx->h2d_bytes += R;
-        }
-      } else {
-        tc::launch_gather_rows(ctx->stream, d_hash, 192, d_maps + R, R, c_hash);
-        tc::launch_gather_rows(ctx->stream, d_pks, 96, d_maps + 2 * R, R, c_pk);
+    if (wire && !k.failed) {
+      if (sig) tc::launch_g2_decompress(ctx->tuning, ctx->stream, c_wire, R, c_sh, c_dec);
+      else tc::launch_g1_decompress(ctx->stream, c_wire, R, c_sh, c_dec);
+    }
+    if (bisect) {
+      // which checks run is the ONLY difference: ranges of slots, halved where they fail (blame_pass), instead of every slot
+      if (!k.failed) blame_pass(k, sig, wire, N, failed, d_maps, c_sh, c_dec, d_present, d_jvalid, d_pks, d_hash, d_w, d_g1, h_ok);
+      if (!k.failed) k.upload(c_ok, h_ok.data(), R, "verdict copy");
+    } else {
+      // (the per-share checks read one hash point / w / key share per record; the range checks of the bisection gather theirs per round)
+      const uint8_t* c_hash = c.gather(d_hash, 192, 1);
+      const uint8_t* c_pk = c.gather(d_pks, 96, 2);
+      const uint8_t* c_w = sig ? nullptr : c.gather(d_w, 192, 1);
+      uint8_t* c_shc = sig ? nullptr : k.temp<uint8_t>(R * 96);
+      const tc::PairingWs pws = k.pairing_ws(R);
+      if (!k.failed) {
         if (sig) {
-          tc::launch_pairing_check(ctx->stream, c_pk, 96, c_hash, 192, d_g1, 0, c_sh, 192, R, c_ok, k.pairing_ws(R));
+          tc::launch_pairing_check(ctx->stream, c_pk, 96, c_hash, 192, d_g1, 0, c_sh, 192, R, c_ok, pws);
         } else {
-          tc::launch_gather_rows(ctx->stream, d_w, 192, d_maps + R, R, c_w);
           tc::launch_g1_scale_cofactor_fix(ctx->stream, c_sh, 96, R, c_shc);
-          tc::launch_pairing_check(ctx->stream, c_shc, 96, c_hash, 192, c_pk, 96, c_w, 192, R, c_ok, k.pairing_ws(R));
+          tc::launch_pairing_check(ctx->stream, c_shc, 96, c_hash, 192, c_pk, 96, c_w, 192, R, c_ok, pws);
         }
-        if (wire) {
-          tc::launch_ok_and_status(ctx->stream, c_dec, R, c_ok);  // (the checked decode has tested membership)
-        } else if (ctx->input_checks) {  // members only (the key shares are sums of the commitment's points, tested above)
-          if (sig) tc::launch_subgroup_check_g2(ctx->stream, c_sh, 192, 1, 1, R, c_v);
-          else tc::launch_subgroup_check_g1(ctx->stream, c_sh, 96, 1, 1, R, c_v);
-          tc::launch_invalidate_jobs(ctx->stream, c_v, 1, 1, R, nullptr, nullptr, 0, c_ok);
-        }
-        tc::launch_gather_bytes(ctx->stream, d_jvalid, d_maps + R, R, c_v);
+      }
+      if (wire) {
+        if (!k.failed) tc::launch_ok_and_status(ctx->stream, c_dec, R, c_ok);  // (the checked decode has tested membership)
+      } else if (ctx->input_checks) {  // members only (the key shares are sums of the commitment's points, tested above)
+        c.members(sig, c_sh, PB);
+      }
+      uint8_t* c_v = c.scratch();
+      if (!k.failed) {
+        tc::launch_gather_bytes(ctx->stream, d_jvalid, c.map(1), R, c_v);
         tc::launch_invalidate_jobs(ctx->stream, c_v, 1, 1, R, nullptr, nullptr, 0, c_ok);
         ctx->blame_checks = R;
         ctx->blame_rounds = 1;
       }
+    }
+    if (!k.failed) {
       tc::launch_robust_mark(ctx->stream, d_present, d_maps, c_ok, R, c_present, c_bad, d_bad);
       // the first t+1 VALID shares: their combination needs no further check
       tc::launch_select_shares(ctx->stream, c_present, c_bad, N, need, F, d_fmap, d_idx2, d_slot2, d_used, d_enough2);
       tc::launch_gather_selected(ctx->stream, c_sh, N, need, PB, d_slot2, d_enough2, F, d_packed2);
       combine_launch(k, sig, t, need, d_idx2, nullptr, d_packed2, F, d_comb2, d_st2);
       tc::launch_robust_finish(ctx->stream, d_fmap, N, need, PB, F, d_enough2, d_st2, nullptr, nullptr, d_comb2, d_res, d_status, d_used, nullptr);
-      k.check(hipStreamSynchronize(ctx->stream), "stream sync");  // the host maps go out of scope
     }
+    c.sync();
     if (n_fallback) *n_fallback = F;
   }
   // the plaintext of a job that ended OK: xor_with_hash(g, v), src/lib.rs:625
@@ -2855,15 +2734,8 @@ int tc_dkg_verify_values_rlc_batch(tc_ctx* ctx, const uint8_t* rows, size_t degr
   const uint8_t* d_rows = k.in(rows, B * row_bytes);
   const uint64_t* d_x = k.in(xs, B * n);
   const uint8_t* d_vals = k.in(vals_fr, B * n * 32, /*secret=*/true);
-  // the seed is host memory in both I/O modes (32 bytes; it must stay secret until the call returns)
-  uint8_t* d_seed = k.temp<uint8_t>(32);
-  if (d_seed) {
-    k.check(hipMemcpyAsync(d_seed, seed32, 32, hipMemcpyHostToDevice, ctx->stream), "seed copy");
-    ctx->h2d_bytes += 32;
-    k.wipe.emplace_back(d_seed, 32);
-  }
-  uint32_t* d_sc = k.temp<uint32_t>(B * np * 8);
-  if (d_sc) k.wipe.emplace_back(d_sc, B * np * 8 * sizeof(uint32_t));
+  uint8_t* d_seed = k.secret_seed(seed32);
+  uint32_t* d_sc = k.secret_temp<uint32_t>(B * np * 8);
   uint8_t* d_pts = k.temp<uint8_t>(B * np * 96);
   uint8_t* d_sum = k.temp<uint8_t>(B * 96);
   uint8_t* d_st = k.temp<uint8_t>(B);
@@ -2883,36 +2755,24 @@ int tc_dkg_verify_values_rlc_batch(tc_ctx* ctx, const uint8_t* rows, size_t degr
     // checked-input mode: a job owning a non-member row point falls back (and fails there)
     k.apply_checks(B, nullptr, nullptr, 0, d_okjob);
     k.check(hipMemsetAsync(d_ok, 1, B * n, ctx->stream), "memset");
-    k.check(hipMemcpyAsync(h_okjob.data(), d_okjob, B, hipMemcpyDeviceToHost, ctx->stream), "ok readback");
-    ctx->d2h_bytes += B;
+    k.readback(h_okjob.data(), d_okjob, B, "ok readback");
     k.check(hipStreamSynchronize(ctx->stream), "stream sync");
     std::vector<uint32_t> failed;
     if (!k.failed)
       for (size_t j = 0; j < B; j++)
         if (!h_okjob[j]) failed.push_back((uint32_t)j);
     if (!k.failed && !failed.empty()) {
-      // the exact kernels for every value of the failed jobs, on compacted operands
+      // the exact kernels for every value of the failed jobs, on compacted operands: whole rows gathered by job, the verdicts
+      // scattered by value
       const size_t F = failed.size(), R = F * n;
-      std::vector<uint32_t> m_val(R);
-      for (size_t f = 0; f < F; f++)
-        for (size_t i = 0; i < n; i++) m_val[f * n + i] = (uint32_t)(failed[f] * n + i);
-      uint32_t* d_maps = k.temp<uint32_t>(F + R);
-      uint8_t* c_rows = k.temp<uint8_t>(F * row_bytes);
-      uint64_t* c_x = k.temp<uint64_t>(R);
-      uint8_t* c_vals = k.temp<uint8_t>(R * 32);
-      if (c_vals) k.wipe.emplace_back(c_vals, R * 32);
-      uint8_t* c_ok = k.temp<uint8_t>(R);
-      if (!k.failed) {
-        k.check(hipMemcpyAsync(d_maps, failed.data(), F * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
-        k.check(hipMemcpyAsync(d_maps + F, m_val.data(), R * 4, hipMemcpyHostToDevice, ctx->stream), "map copy");
-        ctx->h2d_bytes += 4 * (F + R);
-        tc::launch_gather_rows(ctx->stream, d_rows, row_bytes, d_maps, F, c_rows);
-        tc::launch_gather_rows(ctx->stream, reinterpret_cast<const uint8_t*>(d_x), n * 8, d_maps, F, reinterpret_cast<uint8_t*>(c_x));
-        tc::launch_gather_rows(ctx->stream, d_vals, n * 32, d_maps, F, c_vals);
-        dkg_values_exact(k, c_rows, degree, c_x, c_vals, n, F, c_ok, /*checked=*/ctx->input_checks);
-        if (!k.failed) tc::launch_scatter_bytes(ctx->stream, c_ok, d_maps + F, R, d_ok);
-        k.check(hipStreamSynchronize(ctx->stream), "stream sync");  // the host maps go out of scope
-      }
+      const tc::SlotMaps m = tc::slot_maps(failed.data(), F, n);
+      Compacted c(k, R, {&failed, &m.record});
+      const uint8_t* c_rows = c.gather(d_rows, row_bytes, 0);
+      const uint64_t* c_x = reinterpret_cast<const uint64_t*>(c.gather(d_x, n * 8, 0));
+      const uint8_t* c_vals = c.gather(d_vals, n * 32, 0);
+      if (c_vals) k.wipe.emplace_back(const_cast<uint8_t*>(c_vals), R * 32);
+      if (!k.failed) dkg_values_exact(k, c_rows, degree, c_x, c_vals, n, F, c.c_ok, /*checked=*/ctx->input_checks);
+      c.finish(d_ok, 1);
       if (n_fallback) *n_fallback = F;
     }
   }
