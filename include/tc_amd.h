@@ -274,6 +274,40 @@ int tc_verify_sig_records_rlc_batch(tc_ctx* ctx, const uint8_t* pks, size_t K, c
 int tc_verify_decryption_shares_rlc_batch(tc_ctx* ctx, const uint8_t* pk_shares, size_t N, const uint8_t* shares, const uint8_t* u,
                                           const uint8_t* v, const uint64_t* off, const uint8_t* w, size_t B, const uint8_t* seed32,
                                           uint8_t* ok, uint64_t* n_fallback);
+/* Decryption-share validation of RAGGED input (opt-in; the decryption form of tc_verify_g2_records_rlc_batch): M ciphertexts,
+ * ciphertext c owning the records rec_off[c] .. rec_off[c + 1], each record a decryption share shares[r] and the index
+ * key_idx[r] of its key in a table of K keys -- the shares a node has received so far for every ciphertext of an epoch, in any
+ * number and order.  ok[r] = pks[key_idx[r]].verify_decryption_share(&shares[r], &ct[c]) (PublicKeyShare::verify_decryption_share,
+ * src/lib.rs:182-186; the loop of examples/threshold_enc.rs when some shares are missing).  Ciphertexts are cut into groups of
+ * `group` consecutive ciphertexts (0 = 64; at most 1024); a group passes with ONE product check
+ *     prod_{c in g} e(A_c, H_c) e(-B_c, w_c) == 1,   A_c = sum_{r in c} rho_r shares[r],   B_c = sum_{r in c} rho_r pks[key_idx[r]]
+ * H_c = hash_g1_g2(u_c, v_c), rho_r = the 63-bit scalar a + b x^2 of ChaCha20(seed32, r): two Miller pairs per CIPHERTEXT (one
+ * lane pair) and one final exponentiation per group instead of two pairs and one exponentiation per record.  A group that
+ * fails -- or holds an undecodable operand, an index >= K or, in checked-input mode, a non-member -- is re-checked record by
+ * record, so ok[] equals tc_verify_decryption_share_batch's (pk_stride 96) on the expanded arrays up to 2^-63 per group; two
+ * records whose errors cancel in an unweighted sum are both rejected.  The result does not depend on Ciphertext::verify (the
+ * reference's verify_decryption_share does not call it): an invalid ciphertext makes its honest shares fail.  pks: K x 96 B;
+ * shares: R x 96 B, R = rec_off[M] < 2^32; u: M x 96 B, v / off: the M byte strings, w: M x 192 B (the pre-hashed form takes
+ * hashes: M x 192 B = hash_g1_g2(u, v), tc_hash_g1_g2_batch, instead of u / v / off); rec_off: M + 1 values, 0 first,
+ * non-decreasing, in the memory of the other operands; key_idx: R values, or NULL for record r under pks[r] (K >= R); ok: R
+ * bytes; seed32: 32 secret random bytes in HOST memory, drawn after the shares were received; *n_fallback (optional) = records
+ * that went through the per-record checks.  Checked-input mode tests each key TABLE entry, each share, each u (each hash in the
+ * pre-hashed form) and each w once.  The tables of the two sums take 2 KiB of device memory per record: a call whose tables
+ * exceed what tc_g2_lincomb_batch may spend fails with TC_ERR_HIP (split it).  Measured at about 65 536 records against
+ * tc_verify_decryption_share_batch on the expanded arrays, hashing on both sides, input checks on / off
+ * (profiles/dshare_records_probe.txt): 1.41x / 1.60x at 10 keys x 6 553 ciphertexts, 1.28x / 1.53x with 30 % of
+ * those records missing, 1.91x / 2.40x at 200 keys x 328 ciphertexts; SLOWER with a forged record in 1 % of the ciphertexts
+ * (0.80x / 0.92x: 48 % of the records go through the second pass at group 64) and level for 65 536 unrelated triples (0.95x /
+ * 1.00x).  On DENSE input tc_verify_decryption_shares_rlc_batch stays ahead: the ragged entry runs at 0.79x / 0.95x of it at 10
+ * keys, 0.80x / 0.96x at 200 keys, 0.78x / 0.83x with the forged records. */
+int tc_verify_decryption_share_records_rlc_batch(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint64_t* key_idx,
+                                                 const uint8_t* shares, const uint64_t* rec_off, const uint8_t* u, const uint8_t* v,
+                                                 const uint64_t* off, const uint8_t* w, size_t M, size_t group, const uint8_t* seed32,
+                                                 uint8_t* ok, uint64_t* n_fallback);
+int tc_verify_decryption_share_records_prehashed_rlc_batch(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint64_t* key_idx,
+                                                           const uint8_t* shares, const uint64_t* rec_off, const uint8_t* hashes,
+                                                           const uint8_t* w, size_t M, size_t group, const uint8_t* seed32, uint8_t* ok,
+                                                           uint64_t* n_fallback);
 /* ok[j] = Ciphertext(u[j], v[j], w[j]).verify() = e(g1, w) == e(u, hash_g1_g2(u, v))   src/lib.rs:508-512 */
 int tc_ciphertext_verify_batch(tc_ctx* ctx, const uint8_t* u_g1, const uint8_t* v, const uint64_t* off,
                                const uint8_t* w_g2, size_t B, uint8_t* ok);

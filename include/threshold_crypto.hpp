@@ -295,6 +295,48 @@ struct PublicKeyShare {
                                              ct.v.empty() ? &dummy : ct.v.data(), off, ct.w.data(), 1, &ok));
     return ok != 0;
   }
+  // MANY key shares, any number of (key share, decryption share) pairs per ciphertext -- the shares a node has received so far
+  // for every ciphertext of an epoch -- through tc_verify_decryption_share_records_rlc_batch (opt-in): two Miller pairs and one
+  // hash per CIPHERTEXT, one final exponentiation per group of `group` ciphertexts (0 = 64); groups that fail are re-checked
+  // pair by pair, so ok[c][k] = records[c][k].first.verify_decryption_share(records[c][k].second, cts[c]) (src/lib.rs:182-186,
+  // the loop of examples/threshold_enc.rs) up to 2^-63 per group.  Equal keys share one entry of the key table.
+  // seed: 32 bytes of fresh secret randomness, drawn after the shares arrived.
+  static std::vector<std::vector<bool>> verify_decryption_share_records_batch(
+      const std::vector<std::vector<std::pair<PublicKeyShare, DecryptionShare>>>& records, const std::vector<Ciphertext>& cts,
+      const std::array<std::uint8_t, 32>& seed, std::size_t group = 0, std::uint64_t* n_fallback = nullptr, Engine& e = Engine::instance()) {
+    const std::size_t M = records.size();
+    if (M != cts.size()) throw std::invalid_argument("one list of (key share, decryption share) pairs per ciphertext");
+    std::map<G1Bytes, std::uint64_t> slot;
+    std::vector<std::uint8_t> keys, shares, u, w;
+    std::vector<std::uint64_t> key_idx, rec_off{0};
+    Messages v;
+    for (std::size_t c = 0; c < M; c++) {
+      for (const auto& rec : records[c]) {
+        auto it = slot.find(rec.first.pk.g1);
+        if (it == slot.end()) {
+          it = slot.emplace(rec.first.pk.g1, slot.size()).first;
+          keys.insert(keys.end(), rec.first.pk.g1.begin(), rec.first.pk.g1.end());
+        }
+        key_idx.push_back(it->second);
+        shares.insert(shares.end(), rec.second.g1.begin(), rec.second.g1.end());
+      }
+      rec_off.push_back(key_idx.size());
+      u.insert(u.end(), cts[c].u.begin(), cts[c].u.end());
+      w.insert(w.end(), cts[c].w.begin(), cts[c].w.end());
+      v.push(cts[c].v);
+    }
+    const std::size_t R = key_idx.size();
+    std::vector<std::uint8_t> ok(R + 1);
+    std::uint64_t nfb = 0;
+    if (R)
+      e.check(tc_verify_decryption_share_records_rlc_batch(e.ctx(), keys.data(), slot.size(), key_idx.data(), shares.data(), rec_off.data(),
+                                                           u.data(), v.data(), v.off.data(), w.data(), M, group, seed.data(), ok.data(), &nfb));
+    if (n_fallback) *n_fallback = nfb;
+    std::vector<std::vector<bool>> out(M);
+    for (std::size_t c = 0; c < M; c++)
+      for (std::uint64_t r = rec_off[c]; r < rec_off[c + 1]; r++) out[c].push_back(ok[r] != 0);
+    return out;
+  }
 };
 
 inline const G1Bytes& g1_generator() {

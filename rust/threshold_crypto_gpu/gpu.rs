@@ -864,6 +864,46 @@ impl PublicKeyShare {
         })?;
         Ok(ok.into_iter().map(|b| b == 1).collect())
     }
+    /// `verify_decryption_share` (src/lib.rs:182-186) under MANY key shares for ragged input (opt-in,
+    /// tc_verify_decryption_share_records_rlc_batch): `records[c]` holds the (key share, decryption share) pairs received for
+    /// `cts[c]` -- the loop of examples/threshold_enc.rs when shares are missing.  Two Miller pairs per ciphertext and one final
+    /// exponentiation per group of `group` ciphertexts (0 = 64); groups that fail are re-checked pair by pair.  Equal keys share
+    /// one entry of the key table.  One vector of booleans per ciphertext.
+    pub fn verify_decryption_share_records_batch(gpu: &Gpu, records: &[Vec<(PublicKeyShare, DecryptionShare)>], cts: &[Ciphertext], group: usize, seed: &[u8; 32]) -> GpuResult<Vec<Vec<bool>>> {
+        if records.len() != cts.len() {
+            return Err(shape_error("one list of (key share, decryption share) pairs per ciphertext"));
+        }
+        let mut slots: std::collections::BTreeMap<Vec<u8>, u64> = std::collections::BTreeMap::new();
+        let (mut keys, mut key_idx, mut s, mut rec_off) = (Vec::new(), Vec::new(), Vec::new(), vec![0u64]);
+        let (mut u, mut w) = (Vec::new(), Vec::new());
+        for (row, ct) in records.iter().zip(cts) {
+            for (pk, sh) in row {
+                let raw = g1_bytes(&(pk.0).0).to_vec();
+                let next = slots.len() as u64;
+                let slot = *slots.entry(raw.clone()).or_insert(next);
+                if slot == next {
+                    keys.extend_from_slice(&raw);
+                }
+                key_idx.push(slot);
+                s.extend_from_slice(&g1_bytes(&sh.0));
+            }
+            rec_off.push(key_idx.len() as u64);
+            u.extend_from_slice(&g1_bytes(&ct.0));
+            w.extend_from_slice(&g2_bytes(&ct.2));
+        }
+        if key_idx.is_empty() {
+            return Ok(vec![Vec::new(); cts.len()]);
+        }
+        let vs: Vec<&[u8]> = cts.iter().map(|c| c.1.as_slice()).collect();
+        let (flat, off) = pack_messages(&vs);
+        let mut ok = vec![0u8; key_idx.len()];
+        let mut fallback = 0u64;
+        gpu.check(unsafe {
+            tc_verify_decryption_share_records_rlc_batch(gpu.0, keys.as_ptr(), slots.len(), key_idx.as_ptr(), s.as_ptr(), rec_off.as_ptr(), u.as_ptr(), flat.as_ptr(), off.as_ptr(), w.as_ptr(), cts.len(), group, seed.as_ptr(), ok.as_mut_ptr(), &mut fallback)
+        })?;
+        let mut bits = ok.into_iter().map(|b| b == 1);
+        Ok(records.iter().map(|row| bits.by_ref().take(row.len()).collect()).collect())
+    }
 }
 
 // ---- A13: wire formats (src/lib.rs:140-153, 246-259) ------------------------------------------------------------------

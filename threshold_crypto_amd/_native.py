@@ -55,6 +55,10 @@ PROTOTYPES = {
                                         ctypes.POINTER(ctypes.c_uint64)],
     "tc_verify_decryption_shares_rlc_batch": [_u8p, _sz, _u8p, _u8p, _u8p, _u64p, _u8p, _sz, ctypes.c_char_p, _u8p,
                                               ctypes.POINTER(ctypes.c_uint64)],
+    "tc_verify_decryption_share_records_rlc_batch": [_u8p, _sz, _u64p, _u8p, _u64p, _u8p, _u8p, _u64p, _u8p, _sz, _sz, ctypes.c_char_p, _u8p,
+                                                     ctypes.POINTER(ctypes.c_uint64)],
+    "tc_verify_decryption_share_records_prehashed_rlc_batch": [_u8p, _sz, _u64p, _u8p, _u64p, _u8p, _u8p, _sz, _sz, ctypes.c_char_p, _u8p,
+                                                               ctypes.POINTER(ctypes.c_uint64)],
     "tc_combine_signatures_robust_batch": [_u8p, _sz, _sz, _u8p, _u8p, _u8p, _u8p, _u64p, _sz, _sz, ctypes.c_char_p, _u8p, _u8p, _u8p, _u8p,
                                            ctypes.POINTER(ctypes.c_uint64)],
     "tc_decrypt_robust_batch": [_u8p, _sz, _sz, _u8p, _u8p, _u8p, _u8p, _u64p, _u8p, _sz, _u8p, _u8p, _u8p, _u8p,

@@ -360,6 +360,36 @@ class PublicKeyShare(PublicKey):
         return ok.astype(bool)
 
     @staticmethod
+    def verify_decryption_share_records_batch(records, cts, engine=None, seed=None, group=0):
+        """verify_decryption_share under MANY key shares for ragged input (opt-in, tc_verify_decryption_share_records_rlc_batch):
+        records[c] is the list of (PublicKeyShare, DecryptionShare) pairs received for cts[c] -- any number per ciphertext, none
+        included.  Two Miller pairs and one hash per ciphertext and one final exponentiation per group of `group` ciphertexts
+        instead of a full check per pair; groups that fail are re-checked pair by pair, so the booleans are
+        PublicKeyShare::verify_decryption_share's (src/lib.rs:182-186) up to 2^-63 per group.  Equal keys share one entry of the
+        key table.  `seed`: 32 secret random bytes drawn after the shares arrived.  Returns one list of booleans per ciphertext."""
+        e = engine or default_engine()
+        if len(records) != len(cts):
+            raise ValueError("one list of (key share, decryption share) pairs per ciphertext")
+        table, keys, key_idx, shares, rec_off = {}, [], [], [], [0]
+        for row in records:
+            for pk, share in row:
+                slot = table.get(pk.raw)
+                if slot is None:
+                    slot = table[pk.raw] = len(keys)
+                    keys.append(pk.raw)
+                key_idx.append(slot)
+                shares.append(share.raw)
+            rec_off.append(len(shares))
+        if not shares:
+            return [[] for _ in records]
+        v, off = pack_messages([c.v for c in cts])
+        ok, _ = e.verify_decryption_share_records_rlc(_stack(keys, 96), np.array(key_idx, dtype=np.uint64), _stack(shares, 96),
+                                                      np.array(rec_off, dtype=np.uint64), _stack([c.u for c in cts], 96), v, off,
+                                                      _stack([c.w for c in cts], 192), group=group, seed=seed)
+        ok = ok.astype(bool)
+        return [[bool(x) for x in ok[rec_off[c]:rec_off[c + 1]]] for c in range(len(records))]
+
+    @staticmethod
     def verify_batch_shares(pk_shares, sig_shares, msgs, engine=None):
         """PublicKeyShare::verify (src/lib.rs:177-179) for many (share key, share, msg) triples."""
         e = engine or default_engine()

@@ -288,6 +288,54 @@ __global__ __launch_bounds__(kBlock, 2) void k_rec_ladder_g1(const uint64_t* __r
   if (g == 0) g1_encode_uncompressed(jac_to_affine(r), out + j * 96);
 }
 
+// The PAIRED form (tc_verify_decryption_share_records_rlc_batch): segment j is summed over points_a AND over
+// points_b with the same scalars, both in one launch per stage (tc_records.h rec_pair_*: where a lane finds its work).  Half 1
+// keeps tables and digit codes of its own behind half 0's; the bodies are job_msm_tables_g1 / job_msm_ladder_g1_part as they are.
+// status[j] is set when either half fails.
+__global__ __launch_bounds__(kBlock, 2) void k_rec_tables_g1_pair(const uint8_t* __restrict__ points_a, const uint8_t* __restrict__ points_b,
+                                                                const uint32_t* __restrict__ scalars, const uint64_t* __restrict__ seg_first,
+                                                                const uint64_t* __restrict__ first_chunk, size_t J, int32_t* __restrict__ tbl,
+                                                                uint8_t* __restrict__ codes, uint8_t* __restrict__ status, int nbits) {
+  const uint64_t t = (size_t)blockIdx.x * kBlock + threadIdx.x, chunks = first_chunk[J];
+  if (t >= rec_pair_tables_lanes(chunks)) return;
+  const RecPairChunk h = rec_pair_chunk(t, chunks);
+  const size_t j = rec_segment_of_chunk(first_chunk, J, h.c);
+  const uint64_t r0 = seg_first[j], len = seg_first[j + 1] - r0, p0 = rec_pair_place(h.half, first_chunk[j], chunks);
+  const bool ok = job_msm_tables_g1((size_t)len, (size_t)(h.c - first_chunk[j]), (h.half ? points_b : points_a) + r0 * 96, scalars + r0 * 8,
+                                    tbl + p0 * 8 * kMsmEntryWordsG1, codes + p0 * kMsmColumns, nbits, true);
+  if (!ok && status[j] == TC_JOB_OK) status[j] = TC_JOB_INVALID_ENCODING;
+}
+// stage L: the rules of k_rec_ladder_g1 (one trip count per wave, masked look-ups, the identity for a part without records, no
+// lane of a live sum leaving before the last exchange) over 2 J sums; the leader lane of a sum writes A_j, or -B_j, into the
+// interleaved operand array of the product check (the identity stays the identity: its encoding has no y)
+__global__ __launch_bounds__(kBlock, 2) void k_rec_ladder_g1_pair(const uint64_t* __restrict__ seg_first, const uint64_t* __restrict__ first_chunk,
+                                                                size_t J, const int32_t* __restrict__ tbl, const uint8_t* __restrict__ codes,
+                                                                uint8_t* __restrict__ out, const uint8_t* __restrict__ status, int top, size_t parts) {
+  const RecPairLane w = rec_pair_lane((size_t)blockIdx.x * kBlock + threadIdx.x, parts);
+  const bool live = w.j < J;
+  uint64_t len = 0, p0 = 0;
+  if (live && status[w.j] == TC_JOB_OK) {
+    len = seg_first[w.j + 1] - seg_first[w.j];
+    p0 = len ? rec_pair_place(w.half, first_chunk[w.j], first_chunk[J]) : 0;
+  }
+  const uint32_t trips = rec_wave_max((uint32_t)rec_part_trips(len, parts));
+  if (!live) return;
+  const RecPart rp = rec_part(len, w.g, parts);
+  const bool none = rp.s0 >= rp.s1;
+  G1Jac r = job_msm_ladder_g1_part<true>(len ? (size_t)len : 1, tbl + p0 * 8 * kMsmEntryWordsG1, codes + p0 * kMsmColumns,
+                                         MsmPart{(size_t)rp.s0, (size_t)rp.s1, (size_t)trips}, top);
+  r = G1Jac::select(none, G1Jac::infinity(), r);
+  TC_NOUNROLL for (size_t d = 1; d < parts; d <<= 1) {
+    const G1Jac o{msm_from_lane(r.x, (int)d), msm_from_lane(r.y, (int)d), msm_from_lane(r.z, (int)d)};
+    r = jac_add(r, o);
+  }
+  if (w.g == 0) {
+    G1Affine a = jac_to_affine(r);
+    a.y = Fq::select(w.half != 0, -a.y, a.y).norm();
+    g1_encode_uncompressed(a, out + rec_pair_out(w.j, w.half));
+  }
+}
+
 size_t rec_table_bytes(bool g2, uint64_t chunks) {
   return (size_t)chunks * kMsmChunk * 8 * (g2 ? kMsmEntryWords : kMsmEntryWordsG1) * sizeof(int32_t);
 }
@@ -316,6 +364,19 @@ void launch_rec_sum_g1(hipStream_t st, const uint8_t* points, const uint32_t* sc
                      nbits);
   hipLaunchKernelGGL(k_rec_ladder_g1, dim3(grid_for(J * parts)), dim3(kBlock), 0, st, seg_first, first_chunk, J, (const int32_t*)tbl,
                      (const uint8_t*)codes, out, (const uint8_t*)status, nbits / 2, parts);
+}
+// out[2 j] = sum_r scalars[r] points_a[r], out[2 j + 1] = -sum_r scalars[r] points_b[r] over segment j's records (J x 2 x 96
+// bytes: the a operands of launch_pairing_product_check with two pairs per segment), ONE launch per stage for both sums.
+// tbl: rec_table_bytes(false, 2 chunks), codes: rec_code_bytes(2 chunks); status: J bytes, set when either half fails.
+void launch_rec_sum_g1_pair(hipStream_t st, const uint8_t* points_a, const uint8_t* points_b, const uint32_t* scalars, const uint64_t* seg_first,
+                            const uint64_t* first_chunk, size_t J, uint64_t chunks, size_t parts, int32_t* tbl, uint8_t* codes, uint8_t* out,
+                            uint8_t* status, int nbits) {
+  if (!J || !chunks) return;
+  if (parts < 1 || parts > (size_t)kBlock || (parts & (parts - 1))) parts = 1;
+  hipLaunchKernelGGL(k_rec_tables_g1_pair, dim3(grid_for((size_t)rec_pair_tables_lanes(chunks))), dim3(kBlock), 0, st, points_a, points_b, scalars,
+                     seg_first, first_chunk, J, tbl, codes, status, nbits);
+  hipLaunchKernelGGL(k_rec_ladder_g1_pair, dim3(grid_for(rec_pair_ladder_lanes(J, parts))), dim3(kBlock), 0, st, seg_first, first_chunk, J,
+                     (const int32_t*)tbl, (const uint8_t*)codes, out, (const uint8_t*)status, nbits / 2, parts);
 }
 
 }  // namespace tc

@@ -2100,6 +2100,220 @@ int tc_verify_decryption_shares_rlc_batch(tc_ctx* ctx, const uint8_t* pk_shares,
   return on_exception((tc_ctx*)ctx);
 }
 
+// Batch verification of ragged decryption shares: M ciphertexts, ciphertext c owning the records rec_off[c] ..
+// rec_off[c + 1], record r = (shares[r], pks[key_idx[r]]).  Groups of `group` consecutive ciphertexts pass with ONE product check
+//     prod_{c in g} e(A_c, H_c) e(-B_c, w_c) == 1,  A_c = sum_{r in c} rho_r share_r,  B_c = sum_{r in c} rho_r pk_r  (both G1)
+// -- both ragged sums from ONE launch per stage (k_msm.hip k_rec_*_g1_pair) over the 63-bit scalars of k_rlc_scalars_g1, written
+// straight into the interleaved operands [A_c, -B_c] of launch_pairing_product_check, two pairs per ciphertext, against [H_c, w_c].
+// H_c is the FIXED hash (fix = true), so the hashing and the pre-hashed entry share every step behind it and no cofactor scaling
+// stands between the sums and the check.  A group that fails, holds an operand that does not decode or (checked-input mode) is
+// no member, is re-checked record by record on compacted operands like the failed ciphertexts of
+// tc_verify_decryption_shares_rlc_batch.  rec_off is brought to the host in both I/O modes, as in verify_records.
+static int verify_dshare_records(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint64_t* key_idx, const uint8_t* shares, const uint64_t* rec_off,
+                                 const uint8_t* hashes, const uint8_t* u, const uint8_t* v, const uint64_t* off, const uint8_t* w, size_t M,
+                                 size_t group, const uint8_t* seed32, uint8_t* ok, uint64_t* n_fallback) {
+  TC_REQUIRE(ctx);
+  if (n_fallback) *n_fallback = 0;
+  if (M == 0) return TC_OK;
+  TC_REQUIRE(ctx && rec_off && (hashes || (u && off)) && w && seed32);
+  const tc::GroupCut cut = tc::group_cut(M, group);  // groups of CIPHERTEXTS
+  group = cut.group;
+  Call k(ctx);
+  std::vector<uint64_t> h_rec;
+  if (ctx->device_io) {
+    h_rec.resize(M + 1);
+    if (!k.readback(h_rec.data(), rec_off, (M + 1) * 8, "offset readback") || !k.check(hipStreamSynchronize(ctx->stream), "stream sync"))
+      return k.finish();
+  }
+  const uint64_t* hr = ctx->device_io ? h_rec.data() : rec_off;
+  bool good = hr[0] == 0;
+  for (size_t m = 0; m < M && good; m++) good = hr[m + 1] >= hr[m];
+  if (!good) {
+    k.fail("invalid argument: offsets must start at 0 and be non-decreasing");
+    k.arg_error = true;
+    return k.finish();
+  }
+  const uint64_t R64 = hr[M];
+  TC_REQUIRE(R64 < (1ull << 32));
+  const size_t R = (size_t)R64;
+  if (R == 0) return k.finish();
+  TC_REQUIRE(shares && ok && (K == 0 || pks));
+  TC_REQUIRE(key_idx || K >= R);
+  uint64_t total = 0;
+  if (!hashes) {
+    if (!total_bytes(k, off, M, &total)) return k.finish();
+    TC_REQUIRE(total == 0 || v);
+  }
+  // the segments of both sums: the ciphertexts.  One descriptor array: [rec_off | chunks of the ciphertexts]
+  const size_t NG = cut.NG;
+  const size_t simd_lanes = (size_t)(ctx->cus > 0 ? ctx->cus : 256) * 4 * tc::kBlock;  // one wave per SIMD
+  std::vector<uint64_t> desc(2 * (M + 1));
+  uint64_t *h_seg = desc.data(), *h_fc = h_seg + M + 1;
+  memcpy(h_seg, hr, (M + 1) * 8);
+  const uint64_t C = tc::rec_chunk_ranges(h_seg, M, h_fc);
+  uint64_t longest = 0;
+  for (size_t m = 0; m < M; m++) longest = hr[m + 1] - hr[m] > longest ? hr[m + 1] - hr[m] : longest;
+  const size_t parts = tc::rec_parts(2 * M, longest, simd_lanes, tc::kBlock, ctx->tuning.records_parts);  // lanes per SUM, two sums per ciphertext
+  const size_t table_bytes = tc::rec_table_bytes(false, 2 * C);
+  if (table_bytes > msm_table_budget(k)) {
+    k.fail("out of memory: the tables of " + std::to_string(R) + " records need " + std::to_string(table_bytes >> 20) + " MB; split the call");
+    return k.finish();
+  }
+  const uint8_t* d_pk = k.in(pks, K * 96);
+  const uint64_t* d_kidx = k.in(key_idx, key_idx ? R : 0);
+  const uint8_t* d_sh = k.in(shares, R * 96);
+  const uint8_t* d_hash_in = hashes ? k.in(hashes, M * 192) : nullptr;
+  const uint8_t* d_u = hashes ? nullptr : k.in(u, M * 96);
+  const uint8_t* d_v = hashes ? nullptr : k.in(v, (size_t)total);
+  const uint64_t* d_off = hashes ? nullptr : k.in(off, M + 1);
+  const uint8_t* d_w = k.in(w, M * 192);
+  // the pairs of the product checks: 2 * group per group, the last group filled up with identity pairs (the factor 1), so that
+  // ONE launch checks every group
+  const size_t MP = NG * group, pad = MP - M;
+  uint8_t* d_hash_own = hashes ? nullptr : k.temp<uint8_t>(M * 192);
+  const uint8_t* d_hash = hashes ? d_hash_in : d_hash_own;
+  uint8_t* d_ab = k.temp<uint8_t>(MP * 2 * 96);   // [A_c, -B_c]
+  uint8_t* d_hw = k.temp<uint8_t>(MP * 2 * 192);  // [H_c, w_c]
+  uint64_t* d_desc = k.temp<uint64_t>(desc.size());
+  uint8_t* d_seed = k.secret_seed(seed32);
+  uint8_t* d_r = k.secret_temp<uint8_t>(R * 32);
+  uint8_t* d_keys_own = key_idx ? k.temp<uint8_t>(R * 96) : nullptr;
+  const uint8_t* d_keys = key_idx ? d_keys_own : d_pk;  // the key of record r
+  uint8_t* d_st = k.temp<uint8_t>(2 * M);  // the sums of the ciphertexts | their hashes
+  uint8_t* d_okg = k.temp<uint8_t>(NG);
+  int32_t* d_tbl = k.temp<int32_t>(table_bytes / sizeof(int32_t));
+  // (the digit codes are a lossless recoding of the secret scalars: wiped like them)
+  uint8_t* d_codes = k.secret_temp<uint8_t>(tc::rec_code_bytes(2 * C));
+  uint8_t* d_ok = k.out(ok, R);
+  int32_t* ws_groups = k.pairing_product_ws(2 * group, NG, false);
+  k.begin_timing();
+  // checked-input mode: every key TABLE entry once (K tests, not R), every share, every u (or hash) and every w
+  const uint8_t* v_key = k.check_points(false, d_pk, 96, K, K, 1, (size_t)-1);
+  const uint8_t* v_sh = k.check_points(false, d_sh, 96, 1, 1, R, 1);
+  const uint8_t* v_u = hashes ? k.check_points(true, d_hash_in, 192, 1, 1, M, 1) : k.check_points(false, d_u, 96, 1, 1, M, 1);
+  const uint8_t* v_w = k.check_points(true, d_w, 192, 1, 1, M, 1);
+  std::vector<uint8_t> h_okg(NG), h_st(2 * M), h_vkey, h_vsh, h_vu, h_vw, h_pad(pad * 2 * (192 + 96), 0);
+  std::vector<uint64_t> h_kidx;
+  if (!k.failed) {
+    k.upload(d_desc, desc.data(), desc.size() * 8, "descriptor copy");
+    k.check(hipMemsetAsync(d_st, 0, 2 * M, ctx->stream), "memset");
+    if (!hashes) tc::launch_hash_g1_g2(ctx->tuning, ctx->stream, d_u, d_v, d_off, M, d_hash_own, d_st + M, /*fix=*/true);
+    k.check(hipMemcpy2DAsync(d_hw, 384, d_hash, 192, 192, M, hipMemcpyDeviceToDevice, ctx->stream), "hash copy");
+    k.check(hipMemcpy2DAsync(d_hw + 192, 384, d_w, 192, 192, M, hipMemcpyDeviceToDevice, ctx->stream), "w copy");
+    if (pad) {
+      for (size_t i = 0; i < 2 * pad; i++) h_pad[i * 192] = h_pad[2 * pad * 192 + i * 96] = 0x40;  // the identity of G2 / of G1
+      k.upload(d_hw + M * 384, h_pad.data(), 2 * pad * 192, "pad copy");
+      k.upload(d_ab + M * 192, h_pad.data() + 2 * pad * 192, 2 * pad * 96, "pad copy");
+    }
+    tc::launch_rlc_scalars_g1(ctx->stream, d_seed, R, d_r);
+    if (key_idx) tc::launch_rec_gather_keys(ctx->stream, d_pk, K, d_kidx, R, d_keys_own);
+    const uint64_t *d_seg = d_desc, *d_fc = d_seg + M + 1;
+    // (the short-scalar mode of the G1 two-stage kernels: 16 two-half steps, as tc_verify_decryption_shares_rlc_batch)
+    tc::launch_rec_sum_g1_pair(ctx->stream, d_sh, d_keys, reinterpret_cast<const uint32_t*>(d_r), d_seg, d_fc, M, C, parts, d_tbl, d_codes, d_ab,
+                               d_st, /*nbits=*/32);
+    // two pairs per ciphertext (one lane pair of the Miller stage; an empty ciphertext: both sums the identity, the factor 1),
+    // one final exponentiation per group                                                          (src/lib.rs:185)
+    tc::launch_pairing_product_check(ctx->stream, d_ab, 96, d_hw, 192, 2 * group, NG, nullptr, 0, nullptr, 0, d_okg, ws_groups);
+    k.check(hipMemsetAsync(d_ok, 1, R, ctx->stream), "memset");
+    k.readback(h_okg.data(), d_okg, NG, "ok readback");
+    k.readback(h_st.data(), d_st, 2 * M, "status readback");
+    // (the membership tests ran beside the sums and the group checks)
+    k.take_verdicts({{v_key, &h_vkey}, {v_sh, &h_vsh}, {v_u, &h_vu}, {v_w, &h_vw}});
+    k.check(hipStreamSynchronize(ctx->stream), "stream sync");
+    // a bad key fails the groups of the records that NAME it: the indices are needed on the host only then
+    bool key_bad = false;
+    for (size_t i = 0; i < h_vkey.size() && !key_bad; i++) key_bad = h_vkey[i] == 0;
+    const uint64_t* hk = key_idx;
+    if (key_bad && key_idx && ctx->device_io && !k.failed) {
+      h_kidx.resize(R);
+      k.readback(h_kidx.data(), key_idx, R * 8, "index readback");
+      k.check(hipStreamSynchronize(ctx->stream), "stream sync");
+      hk = h_kidx.data();
+    }
+    std::vector<uint32_t> m_rec, m_ct;
+    if (!k.failed) {
+      std::vector<uint8_t> bad_group(NG);
+      for (size_t g = 0; g < NG; g++) {
+        const size_t mlo = g * group, mhi = (mlo + group < M) ? mlo + group : M;
+        const uint64_t rlo = hr[mlo], rhi = hr[mhi];
+        bool bad = !h_okg[g];
+        for (size_t m = mlo; m < mhi && !bad; m++)
+          bad = h_st[m] != TC_JOB_OK || h_st[M + m] != TC_JOB_OK || (!h_vu.empty() && h_vu[m] == 0) || (!h_vw.empty() && h_vw[m] == 0);
+        for (uint64_t r = rlo; r < rhi && !bad && !h_vsh.empty(); r++) bad = h_vsh[r] == 0;
+        if (key_bad)
+          for (uint64_t r = rlo; r < rhi && !bad; r++) {
+            const uint64_t i = hk ? hk[r] : r;
+            bad = i < K && h_vkey[i] == 0;  // (an index >= K has failed its ciphertext in stage T already)
+          }
+        bad_group[g] = bad;
+      }
+      // every record of the ciphertexts of the bad groups
+      std::vector<uint32_t> bad_cts;
+      tc::failed_jobs_of_groups(bad_group.data(), cut, M, bad_cts);
+      for (uint32_t m : bad_cts)
+        for (uint64_t r = hr[m]; r < hr[m + 1]; r++) {
+          m_rec.push_back((uint32_t)r);
+          m_ct.push_back(m);
+        }
+    }
+    if (!k.failed && !m_rec.empty()) {
+      // the per-record check of tc_verify_decryption_share_batch for every record of the failed groups, on compacted operands
+      const size_t F = m_rec.size();
+      // (the fixed hash of an undecodable u is the identity, which a pairing check would SKIP: the per-record path sees an
+      // encoding that does not decode there and answers 0 -- so do these records)
+      for (size_t m = 0; m < M && !hashes && !k.failed; m++)
+        if (h_st[M + m] != TC_JOB_OK) k.check(hipMemsetAsync(d_hash_own + m * 192, 0xff, 192, ctx->stream), "memset");
+      Compacted c(k, F, {&m_rec, &m_ct});
+      const uint8_t* c_sh = c.gather(d_sh, 96, 0);
+      const uint8_t* c_pk = c.gather(d_keys, 96, 0);
+      const uint8_t* c_hash = c.gather(d_hash, 192, 1);
+      const uint8_t* c_w = c.gather(d_w, 192, 1);
+      const tc::PairingWs pws = k.pairing_ws(F);
+      // e(share, H) == e(pk, w)                                                                     (src/lib.rs:185)
+      if (!k.failed) tc::launch_pairing_check(ctx->stream, c_sh, 96, c_hash, 192, c_pk, 96, c_w, 192, F, c.c_ok, pws);
+      if (ctx->input_checks) {  // members only, as the per-record path would require
+        c.members(false, c_sh, 96);
+        c.members(false, c_pk, 96);
+        c.members(true, c_w, 192);
+        if (hashes) c.members(true, c_hash, 192);
+        else c.members(false, c.gather(d_u, 96, 1), 96);
+      }
+      c.finish(d_ok, 0);
+      if (n_fallback) *n_fallback = F;
+    }
+  }
+  k.end_timing();
+  return k.finish();
+}
+
+// PublicKeyShare::verify_decryption_share (src/lib.rs:182-186) over ragged records, the loop of examples/threshold_enc.rs:
+// ok[r] for every received (key, share) record of every ciphertext, one final exponentiation per group of ciphertexts
+int tc_verify_decryption_share_records_rlc_batch(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint64_t* key_idx, const uint8_t* shares,
+                                                 const uint64_t* rec_off, const uint8_t* u, const uint8_t* v, const uint64_t* off, const uint8_t* w,
+                                                 size_t M, size_t group, const uint8_t* seed32, uint8_t* ok, uint64_t* n_fallback) try {
+  if (ctx && M && !(u && off)) {
+    ctx->err = "invalid argument: u, off";
+    return TC_ERR_INVALID_ARG;
+  }
+  return verify_dshare_records(ctx, pks, K, key_idx, shares, rec_off, nullptr, u, v, off, w, M, group, seed32, ok, n_fallback);
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+// the same with hashes[c] = hash_g1_g2(u_c, v_c) made by the caller (tc_hash_g1_g2_batch): src/lib.rs:182-186 with its hash at
+// hand, the loop of examples/threshold_enc.rs
+int tc_verify_decryption_share_records_prehashed_rlc_batch(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint64_t* key_idx,
+                                                           const uint8_t* shares, const uint64_t* rec_off, const uint8_t* hashes, const uint8_t* w,
+                                                           size_t M, size_t group, const uint8_t* seed32, uint8_t* ok, uint64_t* n_fallback) try {
+  if (ctx && M && !hashes) {
+    ctx->err = "invalid argument: hashes";
+    return TC_ERR_INVALID_ARG;
+  }
+  return verify_dshare_records(ctx, pks, K, key_idx, shares, rec_off, hashes, nullptr, nullptr, nullptr, w, M, group, seed32, ok, n_fallback);
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
 // Pass 2 of robust_combine by bisection (tc_ctx_set_blame_bisect; rule, bounds and the 2^-63 argument: tc_blame.h, DESIGN.md
 // 4.17): h_ok[f * N + i] = 0 exactly for the present shares of the failed jobs that per-share mode would answer ok = 0 for,
 // found with range checks over leaves [r] share / [r] pk_share (k_blame.hip).  c_sh: the failed jobs' shares, uncompressed

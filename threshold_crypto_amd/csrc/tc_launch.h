@@ -180,6 +180,12 @@ void launch_rec_sum_g2(hipStream_t st, const uint8_t* points, const uint32_t* sc
                        uint64_t chunks, size_t parts, int32_t* tbl, uint8_t* codes, uint8_t* out, uint8_t* status, int nbits);
 void launch_rec_sum_g1(hipStream_t st, const uint8_t* points, const uint32_t* scalars, const uint64_t* seg_first, const uint64_t* first_chunk, size_t J,
                        uint64_t chunks, size_t parts, int32_t* tbl, uint8_t* codes, uint8_t* out, uint8_t* status, int nbits);
+// the PAIRED G1 form (k_rec_*_g1_pair): both sums of every segment, over points_a and over points_b with the same scalars, in one
+// stage-T and one stage-L launch; out[2 j] = A_j, out[2 j + 1] = -B_j (J x 2 x 96 bytes); tbl: rec_table_bytes(false, 2 chunks),
+// codes: rec_code_bytes(2 chunks); `parts` lanes per SUM; status[j] is set when either half fails
+void launch_rec_sum_g1_pair(hipStream_t st, const uint8_t* points_a, const uint8_t* points_b, const uint32_t* scalars, const uint64_t* seg_first,
+                            const uint64_t* first_chunk, size_t J, uint64_t chunks, size_t parts, int32_t* tbl, uint8_t* codes, uint8_t* out,
+                            uint8_t* status, int nbits);
 // random scalars for the batch validation of G1 values: a + b x^2 with a (odd), b from 32-bit draws of ChaCha20(seed, i)
 void launch_rlc_scalars_g1(hipStream_t st, const uint8_t* seed32, size_t n, uint8_t* out_fr);
 

@@ -96,4 +96,33 @@ TC_HD RecPart rec_part(uint64_t len, size_t g, size_t parts) { return RecPart{g 
 // look-ups per column that the longest part of the segment makes: what every lane of a wave runs (the shorter parts mask)
 TC_HD uint64_t rec_part_trips(uint64_t len, size_t parts) { return (len + parts - 1) / parts; }
 
+// The PAIRED G1 sums of tc_verify_decryption_share_records_rlc_batch (k_msm.hip k_rec_*_g1_pair): every segment
+// is summed twice with the same scalars -- half 0 over points_a, half 1 over points_b -- in one stage-T and one stage-L launch
+// of 2 J logical segments.  The tables and digit codes of half 1 lie behind ALL of half 0's, at chunk offset `chunks` =
+// first_chunk[J], so a half has the layout of a launch_rec_sum_g1 call and no two lanes share a byte.
+constexpr size_t kRecPairPoint = 96;  // bytes of an encoded G1 result
+// stage T: lane t < 2 chunks works on chunk t of half 0, or on chunk t - chunks of half 1
+struct RecPairChunk {
+  size_t half;
+  uint64_t c;
+};
+TC_HD uint64_t rec_pair_tables_lanes(uint64_t chunks) { return 2 * chunks; }
+TC_HD RecPairChunk rec_pair_chunk(uint64_t t, uint64_t chunks) { return t < chunks ? RecPairChunk{0, t} : RecPairChunk{1, t - chunks}; }
+// the first table / code PLACE of a segment that starts at chunk `first` in its half
+TC_HD uint64_t rec_pair_place(size_t half, uint64_t first, uint64_t chunks) { return (half * chunks + first) * kRecChunk; }
+// stage L: `parts` lanes per sum (a power of two of at most 64), the two sums of a segment next to each other -- they have the
+// same length, so the same trip count: lanes [2 j parts, (2 j + 1) parts) are half 0 of segment j, the next `parts` lanes half 1.
+// A sum never spans two waves (parts divides 64 and its lanes start at a multiple of parts); with parts = 64 the halves of a
+// segment are two whole waves.
+struct RecPairLane {
+  size_t j, half, g;
+};
+TC_HD size_t rec_pair_ladder_lanes(size_t J, size_t parts) { return 2 * J * parts; }
+TC_HD RecPairLane rec_pair_lane(size_t lane, size_t parts) {
+  const size_t q = lane / parts;
+  return RecPairLane{q / 2, q % 2, lane % parts};
+}
+// where the leader lane of (segment j, half) writes: the operand array of the product check interleaves A_j and -B_j
+TC_HD size_t rec_pair_out(size_t j, size_t half) { return (2 * j + half) * kRecPairPoint; }
+
 }  // namespace tc

@@ -605,6 +605,59 @@ class Engine:
                    _ptr(ok), ctypes.byref(nfb))
         return ok, int(nfb.value)
 
+    def _dshare_records(self, pks, key_idx, shares, rec_off, M):
+        """the operands the two ragged decryption-share entries share; returns (K, R)"""
+        self._arg(pks, (None, G1_BYTES), "u8", "pks")
+        self._arg(shares, (None, G1_BYTES), "u8", "shares")
+        self._arg(rec_off, (M + 1,), "u64", "rec_off")
+        K, R = pks.shape[0], shares.shape[0]
+        if not _is_torch(rec_off) and int(rec_off[M]) != R:
+            raise ValueError("rec_off[M] = %d, shares holds %d records" % (int(rec_off[M]), R))
+        if key_idx is not None:
+            self._arg(key_idx, (R,), "u64", "key_idx")
+        elif K < R:
+            raise ValueError("key_idx omitted: record r uses pks[r], %d keys for %d records" % (K, R))
+        return K, R
+
+    def verify_decryption_share_records_rlc(self, pks, key_idx, shares, rec_off, u, v, off, w, group=0, seed=None):
+        """Decryption-share validation of ragged input (opt-in; see tc_amd.h): ciphertext c owns the records rec_off[c] ..
+        rec_off[c + 1], record r is the share shares[r] under pks[key_idx[r]] (key_idx None: pks[r]); two Miller pairs per
+        ciphertext, one final exponentiation per group of `group` ciphertexts.  shares must hold exactly rec_off[M] records.
+        Returns (ok (R,), number of records that fell back to per-record checks).  `seed`: 32 secret random bytes (os.urandom
+        when omitted)."""
+        import os
+        dev = self._mode(pks, key_idx, shares, rec_off, u, v, off, w)
+        self._arg(u, (None, G1_BYTES), "u8", "u")
+        M = u.shape[0]
+        self._msgs(v, off, M)
+        self._arg(w, (M, G2_BYTES), "u8", "w")
+        K, R = self._dshare_records(pks, key_idx, shares, rec_off, M)
+        seed = bytes(seed) if seed is not None else os.urandom(32)
+        if len(seed) != 32:
+            raise ValueError("seed: 32 bytes")
+        ok = self._empty(dev, (R,), ref=shares)
+        nfb = ctypes.c_uint64(0)
+        self._call("tc_verify_decryption_share_records_rlc_batch", _ptr(pks), K, _ptr(key_idx), _ptr(shares), _ptr(rec_off), _ptr(u), _ptr(v),
+                   _ptr(off), _ptr(w), M, int(group), seed, _ptr(ok), ctypes.byref(nfb))
+        return ok, int(nfb.value)
+
+    def verify_decryption_share_records_prehashed_rlc(self, pks, key_idx, shares, rec_off, hashes, w, group=0, seed=None):
+        """verify_decryption_share_records_rlc with hashes[c] = hash_g1_g2(u_c, v_c) made by the caller (hash_g1_g2)"""
+        import os
+        dev = self._mode(pks, key_idx, shares, rec_off, hashes, w)
+        self._arg(hashes, (None, G2_BYTES), "u8", "hashes")
+        M = hashes.shape[0]
+        self._arg(w, (M, G2_BYTES), "u8", "w")
+        K, R = self._dshare_records(pks, key_idx, shares, rec_off, M)
+        seed = bytes(seed) if seed is not None else os.urandom(32)
+        if len(seed) != 32:
+            raise ValueError("seed: 32 bytes")
+        ok = self._empty(dev, (R,), ref=shares)
+        nfb = ctypes.c_uint64(0)
+        self._call("tc_verify_decryption_share_records_prehashed_rlc_batch", _ptr(pks), K, _ptr(key_idx), _ptr(shares), _ptr(rec_off),
+                   _ptr(hashes), _ptr(w), M, int(group), seed, _ptr(ok), ctypes.byref(nfb))
+        return ok, int(nfb.value)
+
     # -- robust combination: validate, select and combine in one call -----------------------------------
     def combine_signatures_robust(self, commit, sig_shares, hashes=None, msgs=None, off=None, present=None, group=0, seed=None, _wire=False):
         """tc_combine_signatures_robust_batch (see tc_amd.h): commit (t+1, 96), sig_shares (B, N, 192) with slot i = node i's
