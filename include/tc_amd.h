@@ -70,6 +70,7 @@ extern "C" {
 #define TC_JOB_NOT_ENOUGH_SHARES 1 /* Error::NotEnoughShares   src/error.rs:9  */
 #define TC_JOB_DUPLICATE_ENTRY 2   /* Error::DuplicateEntry    src/error.rs:12 */
 #define TC_JOB_INVALID_ENCODING 3  /* FromBytesError::Invalid  src/error.rs:39 */
+#define TC_JOB_SHARE_MISMATCH 4    /* tc_dkg_reshare_batch: a dealer's constant term is not the public key share it holds (no reference error) */
 
 #define TC_G1_BYTES 96
 #define TC_G2_BYTES 192
@@ -558,6 +559,46 @@ int tc_fr_sum_batch(tc_ctx* ctx, const uint8_t* vals_fr, size_t term_stride, siz
 int tc_dkg_generate_batch(tc_ctx* ctx, const uint8_t* commits, size_t commit_stride, size_t degree, size_t P,
                           const uint8_t* accept, const uint64_t* xs, const uint8_t* vals_fr, size_t n_v, uint8_t* out_commit,
                           uint8_t* out_share_fr, uint8_t* part_status);
+
+/* ---- DKG resharing: a new validator set, the SAME master key ----
+ * The old holders of shares deal; the messages are the DKG's and are checked by tc_dkg_verify_rows_batch /
+ * tc_dkg_verify_values_batch as they are.  The finalisation weights dealer p by the Lagrange coefficient at zero of its
+ * abscissa (the coefficients of src/lib.rs:719-767) instead of 1, so `Poly * Fr` (src/poly.rs:210-254) and
+ * Commitment::add_assign (src/poly.rs:462-471) take the places of the plain sums of src/poly.rs:870-876 and :895-898.
+ * The rules of the finalisation entries above (strides, mask, checked-input mode on INCLUDED terms only, identity and empty
+ * cases, secrets, device-I/O) carry over.  weights_fr: n x 32 B little-endian canonical, PUBLIC, shared by all outputs; an
+ * included term whose weight is not canonical (>= r) fails EVERY output; the weight of an excluded term is not looked at. */
+/* out[j] = sum_{k<n, included} weights[k] * pts[k*term_stride + j*96].  Each product is tc_g1_mul_batch's ladder; the products
+ * are added with the complete formulas, so weights[a]*pts[a] == +-weights[b]*pts[b] is an ordinary input. */
+int tc_g1_weighted_sum_batch(tc_ctx* ctx, const uint8_t* pts, size_t term_stride, size_t n, const uint8_t* weights_fr,
+                             const uint8_t* mask, size_t B, uint8_t* out, uint8_t* status);
+/* out[j] = sum_{k<n, included} weights[k] * vals[k*term_stride + j*32] mod r.  vals and out are SECRETS, as in tc_fr_sum_batch. */
+int tc_fr_weighted_sum_batch(tc_ctx* ctx, const uint8_t* vals_fr, size_t term_stride, size_t n, const uint8_t* weights_fr,
+                             const uint8_t* mask, size_t B, uint8_t* out_fr, uint8_t* status);
+/* The finalisation of a resharing in one call.  old_commit ((t_old+1) x 96): the commitment of the key set being handed over;
+ * old node i holds f(i+1) and its public key share is old_commit.evaluate(i+1) (src/poly.rs:497-508).  Part p is dealt by old
+ * node dealer_idx[p] (P x u64): a symmetric bivariate polynomial of the NEW degree whose constant term is that node's share.
+ * commits, commit_stride, accept, xs, vals_fr, n_v, out_commit, out_share_fr (NULL: an observer) and part_status are
+ * tc_dkg_generate_batch's.  S = the first t_old+1 accepted parts in part order (the `take(t + 1)` of src/lib.rs:719-767),
+ * lambda_p = the Lagrange coefficient at zero of abscissa dealer_idx[p]+1 within S:
+ *     out_commit[i] = sum_{p in S} lambda_p * commits[p][coeff_pos(i,0)]     out_share = sum_{p in S} lambda_p * F_p(m, 0)
+ * so out_commit[0] == old_commit[0].  used (P bytes, optional) marks S; status: ONE byte (optional).  In this order:
+ *  1. old_commit does not decode (checked-input mode: or holds a non-member): status = TC_JOB_INVALID_ENCODING, every
+ *     part_status OK, used = 0, the outputs guarded.
+ *  2. A rejected part is never read and stays OK.
+ *  3. EVERY accepted part is examined, not only S -- the blame is complete and equal at all nodes.  First match:
+ *     TC_JOB_INVALID_ENCODING  a first-column point that does not decode (checked mode: or is no member), a non-canonical value
+ *     TC_JOB_DUPLICATE_ENTRY   dealer_idx[p] repeats that of an earlier accepted part; an abscissa repeats in its samples
+ *     TC_JOB_SHARE_MISMATCH    commits[p][coeff_pos(0,0)] != old_commit.evaluate(dealer_idx[p]+1), as group elements
+ *  4. Any accepted part not OK: status = the code of the first such part, used = 0, the outputs guarded.
+ *  5. Otherwise fewer than t_old+1 accepted parts: status = TC_JOB_NOT_ENOUGH_SHARES, the outputs guarded.
+ *  6. Otherwise used marks S, the outputs are as above, status = TC_JOB_OK.
+ * Guarded: degree+1 identity encodings and a zero share, never a partial key.  The call returns TC_OK in all these cases.
+ * Only the first columns are read.  P = 0 is a no-op; t_old, degree < 4096, P < 65536. */
+int tc_dkg_reshare_batch(tc_ctx* ctx, const uint8_t* old_commit, size_t t_old, const uint64_t* dealer_idx, const uint8_t* commits,
+                         size_t commit_stride, size_t degree, size_t P, const uint8_t* accept, const uint64_t* xs,
+                         const uint8_t* vals_fr, size_t n_v, uint8_t* out_commit, uint8_t* out_share_fr, uint8_t* used,
+                         uint8_t* part_status, uint8_t* status);
 
 /* ---- membership tests ------------------------------------------------------------------------ */
 /* ok[j] = 1 iff pts[j] decodes (range, flags, curve equation) and lies in the order-r subgroup: the

@@ -92,6 +92,10 @@ struct FromBytesError : std::runtime_error {
 struct GpuError : std::runtime_error {
   using std::runtime_error::runtime_error;
 };
+// TC_JOB_SHARE_MISMATCH (dkg_reshare): a dealer's constant term is not the public key share it holds; no reference error
+struct ShareMismatch : std::runtime_error {
+  ShareMismatch() : std::runtime_error("A resharing dealer's constant term is not its public key share.") {}
+};
 
 // One libtc_amd context = one MI355X + one HIP stream.
 class Engine {
@@ -119,6 +123,7 @@ inline void raise_status(std::uint8_t st) {
   if (st == TC_JOB_NOT_ENOUGH_SHARES) throw ErrorException(Error::NotEnoughShares);
   if (st == TC_JOB_DUPLICATE_ENTRY) throw ErrorException(Error::DuplicateEntry);
   if (st == TC_JOB_INVALID_ENCODING) throw FromBytesError();
+  if (st == TC_JOB_SHARE_MISMATCH) throw ShareMismatch();
 }
 
 struct Messages {  // packed variable-length byte strings
@@ -1126,6 +1131,55 @@ inline std::vector<G1Bytes> dkg_generate(const std::vector<std::vector<G1Bytes>>
                                   share_out ? share_out->data() : nullptr, st.data()));
   { volatile std::uint8_t* z = v.data(); for (std::size_t i = 0; i < v.size(); i++) z[i] = 0; }  // the staged values are secrets
   for (std::size_t p = 0; p < P; p++) raise_status(st[p]);
+  std::vector<G1Bytes> res(n);
+  for (std::size_t i = 0; i < n; i++) std::memcpy(res[i].data(), &out[i * 96], 96);
+  return res;
+}
+
+// Resharing (tc_dkg_reshare_batch): old node dealer_idx[p] dealt bi_commits[p], a symmetric polynomial of the NEW degree whose
+// constant term is its share of old_commit's key; the first old_commit.size() accepted parts are combined with their Lagrange
+// coefficients at zero (src/lib.rs:719-767; `Poly * Fr` src/poly.rs:210-254, Commitment::add_assign :462-471), so the result's
+// coefficient 0 is old_commit's.  The other arguments are dkg_generate's; used_out (optional) marks the parts that were combined.
+// A failed accepted part throws, a wrong constant term ShareMismatch, too few accepted parts Error::NotEnoughShares.
+inline std::vector<G1Bytes> dkg_reshare(const std::vector<G1Bytes>& old_commit, const std::vector<std::uint64_t>& dealer_idx,
+                                        const std::vector<std::vector<G1Bytes>>& bi_commits, std::size_t degree, const std::vector<bool>& accepted = {},
+                                        const std::vector<std::vector<std::uint64_t>>* xs = nullptr,
+                                        const std::vector<std::vector<FrBytes>>* vals = nullptr, FrBytes* share_out = nullptr,
+                                        std::vector<bool>* used_out = nullptr, Engine& e = Engine::instance()) {
+  const std::size_t P = bi_commits.size(), n = degree + 1, nco = n * (n + 1) / 2;
+  if (old_commit.empty()) throw std::invalid_argument("old_commit: the commitment of the key set being handed over");
+  if (dealer_idx.size() != P) throw std::invalid_argument("one dealer index per part");
+  if (!accepted.empty() && accepted.size() != P) throw std::invalid_argument("one accepted entry per dealer");
+  if (share_out && (!xs || !vals || xs->size() != P || vals->size() != P)) throw std::invalid_argument("a share needs the samples of every dealer");
+  const std::size_t nv = (share_out && P) ? (*xs)[0].size() : 0;
+  std::vector<std::uint8_t> oc(old_commit.size() * 96), c(P * nco * 96 + 1), a(P + 1, 1), v(P * nv * 32 + 1), out(n * 96 + 1), st(P + 1), used(P + 1);
+  std::vector<std::uint64_t> x(P * nv + 1);
+  for (std::size_t i = 0; i < old_commit.size(); i++) std::memcpy(&oc[i * 96], old_commit[i].data(), 96);
+  for (std::size_t p = 0; p < P; p++) {
+    if (bi_commits[p].size() != nco) throw std::invalid_argument("bivariate commitment size");
+    if (!accepted.empty()) a[p] = accepted[p] ? 1 : 0;
+    for (std::size_t i = 0; i < nco; i++) std::memcpy(&c[(p * nco + i) * 96], bi_commits[p][i].data(), 96);
+    if (share_out && a[p]) {
+      if ((*xs)[p].size() != nv || (*vals)[p].size() != nv) throw std::invalid_argument("every accepted dealer needs the same number of samples");
+      for (std::size_t k = 0; k < nv; k++) {
+        x[p * nv + k] = (*xs)[p][k];
+        std::memcpy(&v[(p * nv + k) * 32], (*vals)[p][k].data(), 32);
+      }
+    }
+  }
+  if (share_out) share_out->fill(0);
+  std::uint8_t status = TC_JOB_NOT_ENOUGH_SHARES;  // P = 0: nobody dealt
+  if (P)
+    e.check(tc_dkg_reshare_batch(e.ctx(), oc.data(), old_commit.size() - 1, dealer_idx.data(), c.data(), nco * 96, degree, P,
+                                 accepted.empty() ? nullptr : a.data(), x.data(), v.data(), nv, out.data(), share_out ? share_out->data() : nullptr,
+                                 used.data(), st.data(), &status));
+  { volatile std::uint8_t* z = v.data(); for (std::size_t i = 0; i < v.size(); i++) z[i] = 0; }  // the staged values are secrets
+  for (std::size_t p = 0; p < P; p++) raise_status(st[p]);
+  raise_status(status);
+  if (used_out) {
+    used_out->assign(P, false);
+    for (std::size_t p = 0; p < P; p++) (*used_out)[p] = used[p] != 0;
+  }
   std::vector<G1Bytes> res(n);
   for (std::size_t i = 0; i < n; i++) std::memcpy(res[i].data(), &out[i * 96], 96);
   return res;

@@ -996,6 +996,55 @@ pub fn interpolate_batch(gpu: &Gpu, samples: &[Vec<(Fr, Fr)>]) -> GpuResult<Vec<
         .collect()
 }
 
+/// What `dkg_reshare_batch` decided: `status` and `part_status` are TC_JOB_* codes (TC_JOB_SHARE_MISMATCH: a dealer's constant
+/// term is not the public key share it holds); unless `status` is TC_JOB_OK the commitment is identities, the share zero and
+/// nothing is marked used.
+pub struct Reshared {
+    pub status: u8,
+    pub part_status: Vec<u8>,
+    pub used: Vec<bool>,
+    pub commitment: Commitment,
+    pub share: Option<Fr>,
+}
+/// Hands the SAME master key to a new validator set: old node `dealer_idx[p]` dealt `parts[p]`, a symmetric polynomial of the new
+/// degree whose constant term is its share under `old_commit`; the first `old_commit.degree() + 1` accepted parts are combined with
+/// their Lagrange coefficients at zero (the coefficients of src/lib.rs:719-767 in place of the plain sums of src/poly.rs:870-876,
+/// 895-898).  `samples`: per part the (abscissa, value) pairs this node holds of that dealer's row, the same number for every
+/// part; None for an observer.
+pub fn dkg_reshare_batch(gpu: &Gpu, old_commit: &Commitment, dealer_idx: &[u64], parts: &[&BivarCommitment], accept: &[bool], samples: Option<&[Vec<(u64, Fr)>]>) -> GpuResult<Reshared> {
+    let p = parts.len();
+    let d = parts.first().map(|c| c.degree()).unwrap_or(0);
+    if old_commit.coeff.is_empty() || p == 0 || dealer_idx.len() != p || accept.len() != p || parts.iter().any(|c| c.degree() != d) {
+        return Err(shape_error("one dealer index and one accept entry per part, all parts of one degree, a non-empty old commitment"));
+    }
+    let n_v = samples.and_then(|s| s.first()).map(|s| s.len()).unwrap_or(0);
+    if samples.map(|s| s.len() != p || s.iter().any(|row| row.len() != n_v)).unwrap_or(false) {
+        return Err(shape_error("every part needs the same number of samples"));
+    }
+    let old: Vec<u8> = old_commit.coeff.iter().flat_map(|q| g1_bytes(q).to_vec()).collect();
+    let commits: Vec<u8> = parts.iter().flat_map(|c| c.coeff.iter().flat_map(|q| g1_bytes(q).to_vec())).collect();
+    let acc: Vec<u8> = accept.iter().map(|&a| a as u8).collect();
+    let (mut xs, mut vals) = (Vec::new(), Vec::new());
+    for row in samples.unwrap_or(&[]) {
+        for (x, y) in row {
+            xs.push(*x);
+            vals.extend_from_slice(&fr_bytes(y));
+        }
+    }
+    let stride = (d + 1) * (d + 2) / 2 * G1_BYTES;
+    let (mut out, mut share, mut used, mut st) = (vec![0u8; (d + 1) * G1_BYTES], [0u8; FR_BYTES], vec![0u8; p], vec![0u8; p]);
+    let mut status = 0u8;
+    let share_ptr = if samples.is_some() { share.as_mut_ptr() } else { std::ptr::null_mut() };
+    let rc = unsafe {
+        tc_dkg_reshare_batch(gpu.0, old.as_ptr(), old_commit.coeff.len() - 1, dealer_idx.as_ptr(), commits.as_ptr(), stride, d, p, acc.as_ptr(), xs.as_ptr(), vals.as_ptr(), n_v, out.as_mut_ptr(), share_ptr, used.as_mut_ptr(), st.as_mut_ptr(), &mut status)
+    };
+    vals.iter_mut().for_each(|b| *b = 0);
+    gpu.check(rc)?;
+    let new_share = if samples.is_some() { Some(fr_from(&share)?) } else { None };
+    share.iter_mut().for_each(|b| *b = 0);
+    Ok(Reshared { status, part_status: st, used: used.into_iter().map(|u| u == 1).collect(), commitment: Commitment { coeff: g1_vec(&out)? }, share: new_share })
+}
+
 // ---- (e): several GPUs of one node from one process ---------------------------------------------------------------------
 /// One worker thread + one context per GPU inside the library; batches are sharded contiguously, the key set travels
 /// by ONE RCCL broadcast over xGMI, valid counts by one all-reduce.

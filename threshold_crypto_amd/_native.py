@@ -19,6 +19,7 @@ JOB_OK = 0
 JOB_NOT_ENOUGH_SHARES = 1
 JOB_DUPLICATE_ENTRY = 2
 JOB_INVALID_ENCODING = 3
+JOB_SHARE_MISMATCH = 4
 
 _u8p = ctypes.c_void_p      # data pointers are passed as raw addresses (host or device)
 _u64p = ctypes.c_void_p
@@ -87,6 +88,9 @@ PROTOTYPES = {
     "tc_bivar_commitment_row0_sum_batch": [_u8p, _sz, _sz, _sz, _u8p, _u8p, _u8p],
     "tc_fr_sum_batch": [_u8p, _sz, _sz, _u8p, _sz, _u8p, _u8p],
     "tc_dkg_generate_batch": [_u8p, _sz, _sz, _sz, _u8p, _u64p, _u8p, _sz, _u8p, _u8p, _u8p],
+    "tc_g1_weighted_sum_batch": [_u8p, _sz, _sz, _u8p, _u8p, _sz, _u8p, _u8p],
+    "tc_fr_weighted_sum_batch": [_u8p, _sz, _sz, _u8p, _u8p, _sz, _u8p, _u8p],
+    "tc_dkg_reshare_batch": [_u8p, _sz, _u64p, _u8p, _sz, _sz, _sz, _u8p, _u64p, _u8p, _sz, _u8p, _u8p, _u8p, _u8p, _u8p],
     "tc_g1_subgroup_check_batch": [_u8p, _sz, _u8p],
     "tc_g2_subgroup_check_batch": [_u8p, _sz, _u8p],
     "tc_g1_compress_batch": [_u8p, _sz, _u8p, _u8p],

@@ -1,7 +1,8 @@
 // gfx950 kernels: DKG algebra (tc_dkg.h) -- fixed-base commitments from an LDS-resident window table of the
 // G1 generator, rows of bivariate commitments, Fr interpolation, and the DKG verification kernels: Fr rows and values, the
 // per-job forms of the two G1 Horner kernels, the comparisons and the scalars of the combined values check, and the DKG
-// finalisation: sums of G1 points split over the lanes of a wave, sums of Fr values, interpolation at zero.
+// finalisation: sums of G1 points split over the lanes of a wave, sums of Fr values, interpolation at zero; and the resharing:
+// the same sums with one public weight per term, the dealers' constant check, the selection and the verdict.
 #include "tc_dkg.h"
 #include "tc_launch.h"
 
@@ -355,6 +356,213 @@ void launch_dkg_generate_verdict(hipStream_t st, const uint8_t* accept, const ui
   hipLaunchKernelGGL(k_dkg_part_status, dim3(grid_for(P)), dim3(kBlock), 0, st, accept, point_bad, share_st, P, part_status);
   hipLaunchKernelGGL(k_dkg_generate_guard, dim3(grid_for(degree + 2)), dim3(kBlock), 0, st, (const uint8_t*)part_status, P, degree, out_commit,
                      out_share);
+}
+
+// ---- DKG resharing (tc_dkg.h): the same sums with one public weight per term ------------------------------------------------------
+// rec[k] = the validated, recoded form of weight k: once per term, whatever the number of outputs
+__global__ __launch_bounds__(kBlock) void k_wsum_recode(const uint8_t* __restrict__ w, size_t n, uint32_t* __restrict__ rec) {
+  const size_t k = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (k < n) wsum_recode_weight(w + k * 32, rec + k * kWsumWeightWords);
+}
+// out[j] = sum_{k < n, included} w_k pts[k * term_stride + off(j)]: k_g1_sum's lanes, every term through a GLV ladder first.  Same
+// lane rules -- `parts` adjacent lanes per group, parts | 64, log2(parts) rounds of __shfl_xor + the complete addition, no lane of
+// a live group leaves before the last round, the lanes of groups past the end leave as whole groups, the validity flags travel with
+// the sums.  A term costs a ladder, and one wave per output leaves most of the GPU idle at the DKG shapes (68 outputs): so the
+// terms of an output may be cut into `slices` ranges (wsum_slice_part), group q = s * B + j summing slice s of output j into
+// out[q] with its validity byte in part_ok[q] -- what k_g1_sum then adds up as `slices` terms per output.  slices = 1: group j
+// is output j, out and status are the call's.  sel: job_g1_wsum_part's term list (n = its length) or null.  Built for one wave per
+// SIMD: a launch is a few hundred waves of ladders whose 8-entry table wants the registers.
+template <class OFF>
+__global__ __launch_bounds__(kBlock, TC_WAVES_G1) void k_g1_wsum(const uint8_t* __restrict__ pts, size_t term_stride, size_t n,
+                                                                 const uint32_t* __restrict__ rec, const uint8_t* __restrict__ mask,
+                                                                 const uint8_t* __restrict__ member, size_t B, size_t parts, size_t slices,
+                                                                 uint8_t* __restrict__ out, uint8_t* __restrict__ status,
+                                                                 uint8_t* __restrict__ part_ok, const uint32_t* __restrict__ sel) {
+  const size_t lp = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  const size_t q = lp / parts, g = lp % parts;
+  if (q >= B * slices) return;
+  const size_t s = q / B, j = q % B;
+  bool ok;
+  G1Jac r = job_g1_wsum_part(pts + OFF()(j), term_stride, rec, mask, member ? member + j : nullptr, B, wsum_slice_part(n, s, slices, g, parts), ok,
+                             nullptr, sel);
+  int good = ok ? 1 : 0;
+  TC_NOUNROLL for (size_t d = 1; d < parts; d <<= 1) {
+    G1Jac o = r;
+    TC_UNROLL for (int i = 0; i < FQ_LIMBS; i++) {
+      o.x.l[i] = __shfl_xor(r.x.l[i], (int)d, 64);
+      o.y.l[i] = __shfl_xor(r.y.l[i], (int)d, 64);
+      o.z.l[i] = __shfl_xor(r.z.l[i], (int)d, 64);
+    }
+    good &= __shfl_xor(good, (int)d, 64);
+    r = jac_add(r, o);
+  }
+  if (g != 0) return;
+  g1_encode_uncompressed(good ? jac_to_affine(r) : G1Affine::infinity(), out + q * 96);
+  if (part_ok) part_ok[q] = good ? 1 : 0;
+  else if (status) status[q] = good ? TC_JOB_OK : TC_JOB_INVALID_ENCODING;
+}
+__global__ __launch_bounds__(kBlock) void k_fr_wsum(const uint8_t* __restrict__ vals, size_t term_stride, size_t n, const uint8_t* __restrict__ w,
+                                                    const uint8_t* __restrict__ mask, size_t B, uint8_t* __restrict__ out,
+                                                    uint8_t* __restrict__ status) {
+  const size_t j = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (j >= B) return;
+  const uint8_t st = job_fr_wsum(vals + j * 32, term_stride, n, w, mask, out + j * 32);
+  if (status) status[j] = st;
+}
+// tc_dkg_reshare_batch, what EVERY accepted part is examined for.  Lane p < P: dup[p] (its dealer index repeats an earlier accepted
+// part's), point_bad[p] (a first-column point does not decode or, member given -- P x (degree+1) verdicts of the membership test --
+// is no member) and const_st[p], the constant check against old_commit.evaluate(dealer_idx[p] + 1); a rejected part is not read.
+// Lane P: old_bad[0] = old_commit does not decode (old_member, t_old + 1 verdicts or null: or holds a non-member).
+__global__ __launch_bounds__(kBlock, TC_WAVES_G1_AUX) void k_reshare_check(const uint8_t* __restrict__ old_commit, const uint8_t* __restrict__ old_member,
+                                                                          size_t t_old, const uint64_t* __restrict__ dealer_idx,
+                                                                          const uint8_t* __restrict__ commits, size_t stride, size_t degree,
+                                                                          const uint8_t* __restrict__ accept, const uint8_t* __restrict__ member, size_t P,
+                                                                          uint8_t* __restrict__ const_st, uint8_t* __restrict__ point_bad,
+                                                                          uint8_t* __restrict__ dup, uint8_t* __restrict__ old_bad) {
+  const size_t p = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (p > P) return;
+  if (p == P) {
+    bool bad = false;
+    for (size_t k = 0; k <= t_old; k++) {
+      G1Affine c;
+      bad = bad || !g1_decode_uncompressed(old_commit + k * 96, c) || (old_member && old_member[k] == 0);
+    }
+    old_bad[0] = bad ? 1 : 0;
+    return;
+  }
+  uint8_t cs = TC_JOB_OK, pb = 0, du = 0;
+  if (reshare_accepted(accept, p)) {
+    du = reshare_is_duplicate(accept, dealer_idx, p) ? 1 : 0;
+    for (size_t i = 0; i <= degree; i++) {
+      G1Affine c;
+      if (!g1_decode_uncompressed(commits + p * stride + bivar_coeff_pos(i, 0) * 96, c) || (member && member[p * (degree + 1) + i] == 0)) pb = 1;
+    }
+    cs = job_reshare_constant_check(old_commit, t_old, dealer_idx[p], commits + p * stride);
+  }
+  const_st[p] = cs;
+  point_bad[p] = pb;
+  dup[p] = du;
+}
+// part_status[p], the first matching code: INVALID_ENCODING (a bad first-column point, a non-canonical value), DUPLICATE_ENTRY (a
+// repeated dealer index, a repeated abscissa), SHARE_MISMATCH; a rejected part, and every part under a bad old_commit, is OK
+__global__ __launch_bounds__(kBlock) void k_reshare_part_status(const uint8_t* __restrict__ accept, const uint8_t* __restrict__ const_st,
+                                                                const uint8_t* __restrict__ point_bad, const uint8_t* __restrict__ dup,
+                                                                const uint8_t* __restrict__ share_st, const uint8_t* __restrict__ old_bad, size_t P,
+                                                                uint8_t* __restrict__ part_status) {
+  const size_t p = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (p >= P) return;
+  uint8_t st = TC_JOB_OK;
+  if (old_bad[0] == 0 && reshare_accepted(accept, p)) {
+    const uint8_t ss = share_st ? share_st[p] : (uint8_t)TC_JOB_OK;
+    if (point_bad[p] || const_st[p] == TC_JOB_INVALID_ENCODING || ss == TC_JOB_INVALID_ENCODING) st = TC_JOB_INVALID_ENCODING;
+    else if (dup[p] || ss == TC_JOB_DUPLICATE_ENTRY) st = TC_JOB_DUPLICATE_ENTRY;
+    else if (const_st[p] == TC_JOB_SHARE_MISMATCH) st = TC_JOB_SHARE_MISMATCH;
+  }
+  part_status[p] = st;
+}
+// the verdict and the plan, ONE lane: status[0]; used[p] (zero unless the verdict is OK); the dealers of S and their Lagrange
+// coefficients at zero (lagrange_all_at_zero over distinct abscissae: duplicates were turned away above), written as weight p of
+// `weights` (P x 32 B, zeroed by the caller) for the parts of S.  sel_idx / sel_part: t_old + 1 entries, lam: (t_old + 1) x 8 words,
+// ws: 4 (t_old + 1) x 8 words.
+__global__ __launch_bounds__(kBlock) void k_reshare_plan(const uint8_t* __restrict__ accept, const uint64_t* __restrict__ dealer_idx, size_t t_old, size_t P,
+                                                         const uint8_t* __restrict__ part_status, const uint8_t* __restrict__ old_bad,
+                                                         uint8_t* __restrict__ used, uint32_t* __restrict__ sel_part, uint64_t* __restrict__ sel_idx,
+                                                         uint32_t* __restrict__ lam, uint32_t* __restrict__ ws, uint8_t* __restrict__ weights,
+                                                         uint8_t* __restrict__ status) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  uint8_t st = old_bad[0] ? (uint8_t)TC_JOB_INVALID_ENCODING : (uint8_t)TC_JOB_OK;
+  for (size_t p = 0; p < P && st == TC_JOB_OK; p++) st = part_status[p];
+  bool selected = false;
+  if (st == TC_JOB_OK) {
+    selected = reshare_select(accept, dealer_idx, t_old, P, used, sel_part, sel_idx, nullptr);
+    if (!selected) st = TC_JOB_NOT_ENOUGH_SHARES;
+  }
+  if (selected) {
+    st = lagrange_all_at_zero(sel_idx, (int)t_old, lam, ws);
+    if (st == TC_JOB_OK) {
+      for (size_t i = 0; i <= t_old; i++)
+        for (int b = 0; b < 32; b++) weights[(size_t)sel_part[i] * 32 + b] = (uint8_t)(lam[i * 8 + (b >> 2)] >> (8 * (b & 3)));
+    }
+  }
+  if (st != TC_JOB_OK)
+    for (size_t p = 0; p < P; p++) used[p] = 0;
+  status[0] = st;
+}
+// ... and never a partial key: unless the verdict is OK, lane i <= degree writes the identity over out_commit[i] and lane degree + 1
+// zero over the share (either may be null)
+__global__ __launch_bounds__(kBlock) void k_reshare_guard(const uint8_t* __restrict__ status, size_t degree, uint8_t* __restrict__ out_commit,
+                                                          uint8_t* __restrict__ out_share) {
+  const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i > degree + 1 || status[0] == TC_JOB_OK) return;
+  if (i <= degree) {
+    if (out_commit) g1_encode_uncompressed(G1Affine::infinity(), out_commit + i * 96);
+  } else if (out_share) {
+    for (int b = 0; b < 32; b++) out_share[b] = 0;
+  }
+}
+
+// lanes per output of k_g1_wsum: TC_SUM_PARTS when set (forced), else g1_sum_parts' rule with the cap at n instead of n / 2 -- a
+// term costs a ladder here, so a lane with ONE term is still work worth a lane
+size_t g1_wsum_parts(size_t B, size_t n, int cus, size_t forced) {
+  if (forced) return forced;
+  const size_t want = (size_t)(cus > 0 ? cus : 256) * 4 * kBlock;
+  size_t parts = 1;
+  while (parts < 64 && B * parts < want && parts * 2 <= n) parts *= 2;
+  return parts;
+}
+// slices per output: TC_WSUM_SLICES when set (forced), else, once an output has a whole wave and still more than one term per
+// lane, as many as bring it to one term per lane -- while the launch stays within one wave per SIMD (4 per CU)
+size_t g1_wsum_slices(size_t B, size_t n, size_t parts, int cus, size_t forced) {
+  size_t slices = forced;
+  if (!slices) {
+    if (parts < 64 || n <= 64) return 1;
+    const size_t room = (size_t)(cus > 0 ? cus : 256) * 4 / (B ? B : 1);
+    slices = (n + 63) / 64;
+    if (slices > room) slices = room;
+  }
+  if (slices > n) slices = n;
+  return slices < 1 ? 1 : slices;
+}
+size_t wsum_rec_words() { return kWsumWeightWords; }
+void launch_wsum_recode(hipStream_t st, const uint8_t* weights_fr, size_t n, uint32_t* rec) {
+  if (n) hipLaunchKernelGGL(k_wsum_recode, dim3(grid_for(n)), dim3(kBlock), 0, st, weights_fr, n, rec);
+}
+void launch_g1_wsum(hipStream_t st, bool column0, const uint8_t* pts, size_t term_stride, size_t n, const uint32_t* rec, const uint8_t* mask,
+                    const uint8_t* member, size_t B, size_t parts, size_t slices, uint8_t* out, uint8_t* status, uint8_t* part_ok,
+                    const uint32_t* sel) {
+  if (!B) return;
+  if (parts < 1 || parts > 64 || (parts & (parts - 1))) parts = 1;
+  if (slices < 1 || !part_ok) slices = 1;
+  if (slices == 1) part_ok = nullptr;
+  const dim3 grid(grid_for(B * slices * parts));
+  if (column0)
+    hipLaunchKernelGGL(k_g1_wsum<SumOffColumn0>, grid, dim3(kBlock), 0, st, pts, term_stride, n, rec, mask, member, B, parts, slices, out, status,
+                       part_ok, sel);
+  else
+    hipLaunchKernelGGL(k_g1_wsum<SumOffPlain>, grid, dim3(kBlock), 0, st, pts, term_stride, n, rec, mask, member, B, parts, slices, out, status,
+                       part_ok, sel);
+}
+void launch_fr_wsum(hipStream_t st, const uint8_t* vals_fr, size_t term_stride, size_t n, const uint8_t* weights_fr, const uint8_t* mask, size_t B,
+                    uint8_t* out_fr, uint8_t* status) {
+  if (B) hipLaunchKernelGGL(k_fr_wsum, dim3(grid_for(B)), dim3(kBlock), 0, st, vals_fr, term_stride, n, weights_fr, mask, B, out_fr, status);
+}
+void launch_reshare_check(hipStream_t st, const uint8_t* old_commit, const uint8_t* old_member, size_t t_old, const uint64_t* dealer_idx,
+                          const uint8_t* commits, size_t stride, size_t degree, const uint8_t* accept, const uint8_t* member, size_t P,
+                          uint8_t* const_st, uint8_t* point_bad, uint8_t* dup, uint8_t* old_bad) {
+  hipLaunchKernelGGL(k_reshare_check, dim3(grid_for(P + 1)), dim3(kBlock), 0, st, old_commit, old_member, t_old, dealer_idx, commits, stride, degree,
+                     accept, member, P, const_st, point_bad, dup, old_bad);
+}
+size_t reshare_plan_ws_words(size_t t_old) { return 5 * (t_old + 1) * 8; }  // lam, then lagrange_all_at_zero's scratch
+void launch_reshare_verdict(hipStream_t st, const uint8_t* accept, const uint64_t* dealer_idx, size_t t_old, size_t P, const uint8_t* const_st,
+                            const uint8_t* point_bad, const uint8_t* dup, const uint8_t* share_st, const uint8_t* old_bad, uint8_t* part_status,
+                            uint8_t* used, uint32_t* sel_part, uint64_t* sel_idx, uint32_t* ws, uint8_t* weights, uint8_t* status) {
+  if (!P) return;
+  hipLaunchKernelGGL(k_reshare_part_status, dim3(grid_for(P)), dim3(kBlock), 0, st, accept, const_st, point_bad, dup, share_st, old_bad, P, part_status);
+  hipLaunchKernelGGL(k_reshare_plan, dim3(1), dim3(kBlock), 0, st, accept, dealer_idx, t_old, P, (const uint8_t*)part_status, old_bad, used, sel_part,
+                     sel_idx, ws, ws + (t_old + 1) * 8, weights, status);
+}
+void launch_reshare_guard(hipStream_t st, const uint8_t* status, size_t degree, uint8_t* out_commit, uint8_t* out_share) {
+  hipLaunchKernelGGL(k_reshare_guard, dim3(grid_for(degree + 2)), dim3(kBlock), 0, st, status, degree, out_commit, out_share);
 }
 
 }  // namespace tc

@@ -531,6 +531,10 @@ tc::Tuning tuning_from_env() {
     const size_t v = (size_t)strtoull(q, nullptr, 10);
     if (v >= 1 && v <= 64 && (v & (v - 1)) == 0) tn.sum_parts = v;  // a power of two within one wave; anything else: the default rule
   }
+  if (const char* q = getenv("TC_WSUM_SLICES")) {
+    const size_t v = (size_t)strtoull(q, nullptr, 10);
+    if (v >= 1 && v <= 64) tn.wsum_slices = v;  // (the launch takes at most as many as there are terms); anything else: the default rule
+  }
   if (const char* q = getenv("TC_RECORDS_PARTS")) {
     const size_t v = (size_t)strtoull(q, nullptr, 10);
     if (v >= 1 && v <= 64 && (v & (v - 1)) == 0) tn.records_parts = v;  // (G2 takes at most 32: a larger value means 32 there)
@@ -3001,26 +3005,52 @@ int tc_dkg_verify_values_rlc_batch(tc_ctx* ctx, const uint8_t* rows, size_t degr
 // marks by record and cannot express the mask, so the membership test runs here and the sum kernel reads its verdicts for the
 // INCLUDED terms only (as dkg_values_exact(checked = true) does for its compacted operands).  column0: the terms are bivariate
 // commitments and output j is coefficient (j, 0); the test then reads a compact copy of the first columns.
+// (the membership half, shared with the weighted sums: the verdict bytes, n x B, or null with the checks off; a column0 operand
+// is replaced by the compact copy of its first columns)
+static const uint8_t* g1_sum_members(Call& k, bool& column0, const uint8_t*& d_pts, size_t& term_stride, size_t n, size_t B) {
+  tc_ctx* ctx = k.c;
+  if (!ctx->input_checks || !n) return nullptr;
+  uint8_t* d_valid = k.temp<uint8_t>(n * B);
+  uint8_t* d_col = column0 ? k.temp<uint8_t>(n * B * 96) : nullptr;
+  if (k.failed) return nullptr;
+  if (column0) {
+    tc::launch_bivar_column0(ctx->stream, d_pts, term_stride, B - 1, n, d_col);
+    d_pts = d_col;
+    term_stride = B * 96;
+    column0 = false;
+  }
+  tc::launch_subgroup_check_g1(ctx->stream, d_pts, 96, term_stride / 96, B, n * B, d_valid);
+  return d_valid;
+}
 static void g1_sum(Call& k, bool column0, const uint8_t* d_pts, size_t term_stride, size_t n, const uint8_t* d_mask, size_t B, uint8_t* d_out,
                    uint8_t* d_st, uint8_t* d_term_bad) {
   tc_ctx* ctx = k.c;
-  const uint8_t* d_member = nullptr;
-  if (ctx->input_checks && n) {
-    uint8_t* d_valid = k.temp<uint8_t>(n * B);
-    uint8_t* d_col = column0 ? k.temp<uint8_t>(n * B * 96) : nullptr;
-    if (k.failed) return;
-    if (column0) {
-      tc::launch_bivar_column0(ctx->stream, d_pts, term_stride, B - 1, n, d_col);
-      d_pts = d_col;
-      term_stride = B * 96;
-      column0 = false;
-    }
-    tc::launch_subgroup_check_g1(ctx->stream, d_pts, 96, term_stride / 96, B, n * B, d_valid);
-    d_member = d_valid;
-  }
+  const uint8_t* d_member = g1_sum_members(k, column0, d_pts, term_stride, n, B);
   if (k.failed) return;
   tc::launch_g1_sum(ctx->stream, column0, d_pts, term_stride, n, d_mask, d_member, B, tc::g1_sum_parts(B, n, ctx->cus, ctx->tuning.sum_parts), d_out,
                     d_st, d_term_bad);
+}
+// the weighted form: d_w = n x 32 B weights, recoded once per term; d_member as g1_sum_members left it.  d_sel (may be null):
+// n_sel term numbers, the only terms the sum visits
+static void g1_wsum(Call& k, bool column0, const uint8_t* d_pts, size_t term_stride, size_t n, const uint8_t* d_w, const uint8_t* d_mask,
+                    const uint8_t* d_member, size_t B, uint8_t* d_out, uint8_t* d_st, const uint32_t* d_sel = nullptr, size_t n_sel = 0) {
+  tc_ctx* ctx = k.c;
+  uint32_t* d_rec = k.temp<uint32_t>(n * tc::wsum_rec_words());
+  if (k.failed) return;
+  tc::launch_wsum_recode(ctx->stream, d_w, n, d_rec);
+  const size_t visited = d_sel ? n_sel : n;
+  const size_t parts = tc::g1_wsum_parts(B, visited, ctx->cus, ctx->tuning.sum_parts);
+  const size_t slices = tc::g1_wsum_slices(B, visited, parts, ctx->cus, ctx->tuning.wsum_slices);
+  if (slices <= 1) {
+    tc::launch_g1_wsum(ctx->stream, column0, d_pts, term_stride, visited, d_rec, d_mask, d_member, B, parts, 1, d_out, d_st, nullptr, d_sel);
+    return;
+  }
+  // a long sum: `slices` partial sums per output, each by its own lanes, then the plain sum of those
+  uint8_t* d_partial = k.temp<uint8_t>(B * slices * 96);
+  uint8_t* d_pok = k.temp<uint8_t>(B * slices);
+  if (k.failed) return;
+  tc::launch_g1_wsum(ctx->stream, column0, d_pts, term_stride, visited, d_rec, d_mask, d_member, B, parts, slices, d_partial, nullptr, d_pok, d_sel);
+  tc::launch_g1_sum(ctx->stream, false, d_partial, B * 96, slices, nullptr, d_pok, B, tc::g1_sum_parts(B, slices, ctx->cus, 0), d_out, d_st, nullptr);
 }
 
 int tc_g1_sum_batch(tc_ctx* ctx, const uint8_t* pts, size_t term_stride, size_t n, const uint8_t* mask, size_t B, uint8_t* out,
@@ -3120,6 +3150,116 @@ int tc_dkg_generate_batch(tc_ctx* ctx, const uint8_t* commits, size_t commit_str
     tc::launch_fr_sum(ctx->stream, d_part, 32, P, d_acc, 1, d_os, nullptr);
   }
   if (!k.failed) tc::launch_dkg_generate_verdict(ctx->stream, d_acc, d_bad, d_sst, P, degree, d_ps, d_oc, d_os);
+  k.end_timing();
+  return k.finish();
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+// ---- DKG resharing: the accepted parts summed with Lagrange weights, the master key unchanged ---------------------------------
+// (`Poly * Fr` src/poly.rs:210-254, Commitment::add_assign :462-471, the finalisation :870-876 and :895-898, the coefficients of
+// src/lib.rs:719-767)
+int tc_g1_weighted_sum_batch(tc_ctx* ctx, const uint8_t* pts, size_t term_stride, size_t n, const uint8_t* weights_fr, const uint8_t* mask, size_t B,
+                             uint8_t* out, uint8_t* status) try {
+  TC_REQUIRE(ctx);
+  if (B == 0) return TC_OK;
+  TC_REQUIRE(ctx && out && (n == 0 || (pts && weights_fr)));
+  TC_REQUIRE(n == 0 || (term_stride % 96 == 0 && term_stride / 96 >= B));
+  TC_REQUIRE(B < (1ull << 26) && n < (1ull << 32) && B * n < (1ull << 40));
+  Call k(ctx);
+  const uint8_t* d_pts = k.in(pts, n ? (n - 1) * term_stride + B * 96 : 0);
+  const uint8_t* d_w = k.in(weights_fr, n * 32);
+  const uint8_t* d_mask = k.in(mask, n);
+  uint8_t* d_out = k.out(out, B * 96);
+  uint8_t* d_st = k.out(status, B);
+  k.begin_timing();
+  bool column0 = false;
+  const uint8_t* d_member = g1_sum_members(k, column0, d_pts, term_stride, n, B);
+  g1_wsum(k, false, d_pts, term_stride, n, d_w, d_mask, d_member, B, d_out, d_st);
+  k.end_timing();
+  return k.finish();
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+int tc_fr_weighted_sum_batch(tc_ctx* ctx, const uint8_t* vals_fr, size_t term_stride, size_t n, const uint8_t* weights_fr, const uint8_t* mask, size_t B,
+                             uint8_t* out_fr, uint8_t* status) try {
+  TC_REQUIRE(ctx);
+  if (B == 0) return TC_OK;
+  TC_REQUIRE(ctx && out_fr && (n == 0 || (vals_fr && weights_fr)));
+  TC_REQUIRE(n == 0 || (term_stride % 32 == 0 && term_stride / 32 >= B));
+  TC_REQUIRE(B < (1ull << 32) && n < (1ull << 32));
+  Call k(ctx);
+  const uint8_t* d_v = k.in(vals_fr, n ? (n - 1) * term_stride + B * 32 : 0, /*secret=*/true);
+  const uint8_t* d_w = k.in(weights_fr, n * 32);
+  const uint8_t* d_mask = k.in(mask, n);
+  uint8_t* d_out = k.out(out_fr, B * 32);
+  if (d_out && !ctx->device_io) k.wipe_after_copy.emplace_back(d_out, B * 32);
+  uint8_t* d_st = k.out(status, B);
+  k.begin_timing();
+  if (!k.failed) tc::launch_fr_wsum(ctx->stream, d_v, term_stride, n, d_w, d_mask, B, d_out, d_st);
+  k.end_timing();
+  return k.finish();
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+// Every accepted part is examined (k_reshare_check, the interpolations at zero), the verdict kernels pick S and its Lagrange
+// weights, and the two weighted sums run with `used` as their mask -- the G1 sum over the t_old + 1 part numbers of S only, so its
+// ladders spread evenly over the lanes wherever S sits among the P parts.  A failed verdict leaves used all zero (and the part
+// numbers at their zero fill: part 0, masked out), so the sums are the identity and zero already; the guard writes them once more.
+// Nothing of the selection passes through the host.
+int tc_dkg_reshare_batch(tc_ctx* ctx, const uint8_t* old_commit, size_t t_old, const uint64_t* dealer_idx, const uint8_t* commits, size_t commit_stride,
+                         size_t degree, size_t P, const uint8_t* accept, const uint64_t* xs, const uint8_t* vals_fr, size_t n_v, uint8_t* out_commit,
+                         uint8_t* out_share_fr, uint8_t* used, uint8_t* part_status, uint8_t* status) try {
+  TC_REQUIRE(ctx);
+  if (P == 0) return TC_OK;
+  TC_REQUIRE(ctx && old_commit && dealer_idx && commits);
+  TC_REQUIRE(degree < (1u << 12) && t_old < (1u << 12) && P < (1ull << 16) && n_v < (1u << 16));
+  const size_t n = degree + 1, ncoeff = n * (n + 1) / 2;
+  TC_REQUIRE(commit_stride % 96 == 0 && commit_stride >= ncoeff * 96);
+  const bool share = out_share_fr != nullptr;
+  TC_REQUIRE(!share || n_v == 0 || (xs && vals_fr));
+  Call k(ctx);
+  const uint8_t* d_old = k.in(old_commit, (t_old + 1) * 96);
+  const uint64_t* d_di = k.in(dealer_idx, P);
+  const uint8_t* d_c = k.in(commits, (P - 1) * commit_stride + ncoeff * 96);
+  const uint8_t* d_acc = k.in(accept, P);
+  const uint64_t* d_x = share ? k.in(xs, P * n_v) : nullptr;
+  const uint8_t* d_v = share ? k.in(vals_fr, P * n_v * 32, /*secret=*/true) : nullptr;
+  uint8_t* d_oc = out_commit ? k.out(out_commit, n * 96) : k.temp<uint8_t>(n * 96);
+  uint8_t* d_os = k.out(out_share_fr, 32);
+  if (d_os && !ctx->device_io) k.wipe_after_copy.emplace_back(d_os, 32);
+  uint8_t* d_used = used ? k.out(used, P) : k.temp<uint8_t>(P);
+  uint8_t* d_ps = part_status ? k.out(part_status, P) : k.temp<uint8_t>(P);
+  uint8_t* d_status = status ? k.out(status, 1) : k.temp<uint8_t>(1);
+  uint8_t* d_flags = k.temp<uint8_t>(3 * P + 1);  // const_st, point_bad, dup, old_bad
+  uint8_t* d_part = share ? k.temp<uint8_t>(P * 32) : nullptr;  // the parts' contributions to the share: secret
+  if (d_part) k.wipe.emplace_back(d_part, P * 32);
+  uint8_t* d_sst = share ? k.temp<uint8_t>(P) : nullptr;
+  uint8_t* d_w = k.temp<uint8_t>(P * 32, /*zero=*/true);  // lambda_p on S: public
+  uint32_t* d_sel = k.temp<uint32_t>(t_old + 1, /*zero=*/true);  // (read by the sum whatever the verdict: never uninitialised)
+  uint64_t* d_sidx = k.temp<uint64_t>(t_old + 1);
+  uint32_t* d_ws = k.temp<uint32_t>(tc::reshare_plan_ws_words(t_old));
+  uint8_t* d_oldv = ctx->input_checks ? k.temp<uint8_t>(t_old + 1) : nullptr;
+  k.begin_timing();
+  if (!k.failed) {
+    bool column0 = true;
+    const uint8_t* d_pts = d_c;
+    size_t term_stride = commit_stride;
+    const uint8_t* d_member = g1_sum_members(k, column0, d_pts, term_stride, P, n);
+    if (d_oldv && !k.failed) tc::launch_subgroup_check_g1(ctx->stream, d_old, 96, 1, 1, t_old + 1, d_oldv);
+    if (!k.failed) {
+      tc::launch_reshare_check(ctx->stream, d_old, d_oldv, t_old, d_di, d_c, commit_stride, degree, d_acc, d_member, P, d_flags, d_flags + P,
+                               d_flags + 2 * P, d_flags + 3 * P);
+      if (share) tc::launch_fr_interpolate_at_zero(ctx->stream, n_v, d_x, d_v, d_acc, P, d_part, d_sst);
+      tc::launch_reshare_verdict(ctx->stream, d_acc, d_di, t_old, P, d_flags, d_flags + P, d_flags + 2 * P, d_sst, d_flags + 3 * P, d_ps, d_used, d_sel,
+                                 d_sidx, d_ws, d_w, d_status);
+      g1_wsum(k, column0, d_pts, term_stride, P, d_w, d_used, d_member, n, d_oc, nullptr, d_sel, t_old + 1);
+      if (share && !k.failed) tc::launch_fr_wsum(ctx->stream, d_part, 32, P, d_w, d_used, 1, d_os, nullptr);
+      if (!k.failed) tc::launch_reshare_guard(ctx->stream, d_status, degree, d_oc, d_os);
+    }
+  }
   k.end_timing();
   return k.finish();
 } catch (...) {

@@ -16,6 +16,7 @@ enum : uint8_t {
   TC_JOB_NOT_ENOUGH_SHARES = 1,  // Error::NotEnoughShares  (/root/reference/src/error.rs:9)
   TC_JOB_DUPLICATE_ENTRY = 2,    // Error::DuplicateEntry   (/root/reference/src/error.rs:12)
   TC_JOB_INVALID_ENCODING = 3,   // FromBytesError::Invalid (/root/reference/src/error.rs:39)
+  TC_JOB_SHARE_MISMATCH = 4,     // a resharing dealer's constant term is not its public key share (no reference error)
 };
 
 TC_HD uint32_t load_be32(const uint8_t* p) {

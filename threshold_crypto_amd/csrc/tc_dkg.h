@@ -368,4 +368,157 @@ TC_HD uint8_t job_fr_interpolate_at_zero(size_t n, const uint64_t* xs, const uin
   return !ok ? TC_JOB_INVALID_ENCODING : dup ? TC_JOB_DUPLICATE_ENTRY : TC_JOB_OK;
 }
 
+// ---- DKG resharing: the accepted parts summed with Lagrange weights (`Poly * Fr` src/poly.rs:210-254, Commitment::add_assign
+// :462-471, the tail of distributed_key_generation :870-876, 895-898, the coefficients of src/lib.rs:719-767) ---------------------
+// A weight is shared by every output of a sum, so it is validated and recoded ONCE per term (k_dkg.hip k_wsum_recode) into
+// kWsumWeightWords words: neg (4), u (4) of glv_recode_sign_aligned and the flags below.
+constexpr int kWsumWeightWords = 9;
+constexpr uint32_t kWsumTop = 1u, kWsumFlip = 2u, kWsumZero = 4u, kWsumValid = 8u;
+TC_HD void wsum_recode_weight(const uint8_t* w_le32, uint32_t* rec) {
+  uint32_t k[8];
+  const bool ok = fr_from_le32(w_le32, k);
+  bool zero = true;
+  TC_UNROLL for (int i = 0; i < 8; i++) zero = zero && k[i] == 0;
+  tc_u128 neg = 0, u = 0;
+  bool top = false, flip = false;
+  if (ok && !zero) flip = glv_recode_sign_aligned(k, &neg, &u, &top);
+  TC_UNROLL for (int i = 0; i < 4; i++) {
+    rec[i] = (uint32_t)(neg >> (32 * i));
+    rec[4 + i] = (uint32_t)(u >> (32 * i));
+  }
+  rec[8] = (top ? kWsumTop : 0u) | (flip ? kWsumFlip : 0u) | (zero ? kWsumZero : 0u) | (ok ? kWsumValid : 0u);
+}
+
+// the weighted twin of job_g1_sum_part: one lane's partial sum  sum_{k in part, included} w_k pts[k * term_stride], weights as
+// wsum_recode_weight left them (rec: term 0's).  Mask, member and term_bad as there: an excluded term is neither decoded nor
+// multiplied, and its weight is not looked at.  An included term with a non-canonical weight clears ok -- in the lane that owns
+// the term of EVERY output, so every output fails.  Each product is the GLV ladder of tc_g1_mul_batch's routine (g1_mul_glv,
+// here from the recoded scalar); a zero weight or an identity term contributes nothing and runs no ladder.  The products are
+// folded with the COMPLETE addition: the weights are public, so a dealer can choose its commitment such that w_a P_a = +-w_b P_b.
+// A long sum is cut into `slices` consecutive ranges of positions, each with its own group of `parts` lanes (k_g1_wsum): lane g of
+// slice s owns sum_part of the slice's range -- every position in exactly one (slice, lane).
+TC_HD SumPart wsum_slice_part(size_t n, size_t s, size_t slices, size_t g, size_t parts) {
+  const SumPart sl = sum_part(n, s, slices);
+  const SumPart in = sum_part(sl.k1 - sl.k0, g, parts);
+  return SumPart{sl.k0 + in.k0, sl.k0 + in.k1};
+}
+// sel (may be null): the sum runs over the terms sel[0 .. n) instead of 0 .. n -- part is then a range of POSITIONS in sel, and
+// pts, rec, mask, member and term_bad are still addressed by term (tc_dkg_reshare_batch: the t_old + 1 dealers of S out of P
+// parts, spread evenly over the lanes of an output wherever they sit among the parts).
+TC_HD G1Jac job_g1_wsum_part(const uint8_t* pts, size_t term_stride, const uint32_t* rec, const uint8_t* mask, const uint8_t* member,
+                             size_t member_stride, SumPart part, bool& ok, uint8_t* term_bad = nullptr, const uint32_t* sel = nullptr) {
+  G1Jac acc = G1Jac::infinity();
+  ok = true;
+  TC_NOUNROLL for (size_t pos = part.k0; pos < part.k1; pos++) {
+    const size_t k = sel ? (size_t)sel[pos] : pos;
+    if (mask && mask[k] == 0) continue;
+    G1Affine c;
+    bool good = g1_decode_uncompressed(pts + k * term_stride, c);
+    if (member) good = good && member[k * member_stride] != 0;
+    if (!good && term_bad) term_bad[k] = 1;
+    const uint32_t* r = rec + k * kWsumWeightWords;
+    const uint32_t flags = r[8];
+    good = good && (flags & kWsumValid) != 0;
+    ok = ok && good;
+    if (!good || (flags & kWsumZero) || c.inf) continue;
+    GlvRecoded w;
+    w.neg = w.u = 0;
+    TC_UNROLL for (int i = 0; i < 4; i++) {
+      w.neg |= (tc_u128)r[i] << (32 * i);
+      w.u |= (tc_u128)r[4 + i] << (32 * i);
+    }
+    w.top = (flags & kWsumTop) != 0;
+    w.flip = (flags & kWsumFlip) != 0;
+    acc = jac_add(acc, g1_mul_glv_recoded(c, w));
+  }
+  return acc;
+}
+
+// out = sum_{k < n, included} w_k vals[k * term_stride] mod r  (`Poly * Fr` src/poly.rs:210-254 per coefficient, then :876).  w: n x 32 B
+// LE canonical, shared by all outputs.  An included non-canonical value or weight: zero output, TC_JOB_INVALID_ENCODING.
+TC_HD uint8_t job_fr_wsum(const uint8_t* vals, size_t term_stride, size_t n, const uint8_t* w_le32, const uint8_t* mask, uint8_t* out32) {
+  Fr acc = Fr::zero();
+  bool ok = true;
+  TC_NOUNROLL for (size_t k = 0; k < n; k++) {
+    if (mask && mask[k] == 0) continue;
+    uint32_t v[8], w[8];
+    const bool good = fr_from_le32(vals + k * term_stride, v) & fr_from_le32(w_le32 + k * 32, w);
+    ok = ok && good;
+    if (good) acc = acc + Fr::from_canonical(v) * Fr::from_canonical(w);
+  }
+  if (!ok) acc = Fr::zero();
+  fr_store_le32(acc, out32);
+  return ok ? TC_JOB_OK : TC_JOB_INVALID_ENCODING;
+}
+
+// Who deals into a resharing.  Plain integer code (host and device).  Part p is accepted when accept is null or accept[p] != 0
+// and claims to be old node dealer_idx[p].  dup[p] = 1 for an accepted part whose index repeats that of an EARLIER accepted part
+// (the first claim of an index is not marked).  S = the first t_old + 1 accepted parts in part order, the `take(t + 1)` of
+// src/lib.rs:719-767: used[p] = 1 on S, sel_part / sel_idx (t_old + 1 entries each) = its part numbers and dealer indices in that
+// order -- the abscissae of lagrange_all_at_zero are sel_idx + 1.  Returns false, with used all zero and nothing selected,
+// when fewer than t_old + 1 parts are accepted; dup is filled in either way.  Any of used, sel_part, sel_idx, dup may be null.
+TC_HD bool reshare_accepted(const uint8_t* accept, size_t p) { return !accept || accept[p] != 0; }
+TC_HD bool reshare_is_duplicate(const uint8_t* accept, const uint64_t* dealer_idx, size_t p) {
+  if (!reshare_accepted(accept, p)) return false;
+  TC_NOUNROLL for (size_t q = 0; q < p; q++)
+    if (reshare_accepted(accept, q) && dealer_idx[q] == dealer_idx[p]) return true;
+  return false;
+}
+TC_HD bool reshare_select(const uint8_t* accept, const uint64_t* dealer_idx, size_t t_old, size_t P, uint8_t* used, uint32_t* sel_part,
+                          uint64_t* sel_idx, uint8_t* dup) {
+  size_t accepted = 0;
+  TC_NOUNROLL for (size_t p = 0; p < P; p++) {
+    if (dup) dup[p] = reshare_is_duplicate(accept, dealer_idx, p) ? 1 : 0;
+    if (reshare_accepted(accept, p)) accepted++;
+  }
+  const bool enough = accepted > t_old;
+  size_t taken = 0;
+  TC_NOUNROLL for (size_t p = 0; p < P; p++) {
+    const bool take = enough && taken <= t_old && reshare_accepted(accept, p);
+    if (used) used[p] = take ? 1 : 0;
+    if (take) {
+      if (sel_part) sel_part[taken] = (uint32_t)p;
+      if (sel_idx) sel_idx[taken] = dealer_idx[p];
+      taken++;
+    }
+  }
+  return enough;
+}
+
+// old_commit.evaluate(idx + 1) (src/poly.rs:497-508), the public key share old node idx is known to hold -- job_commitment_evaluate_at
+// with the abscissa idx + 1 taken in Fr, so idx = 2^64 - 1 (abscissa 2^64: 64 doublings per Horner step) is an index like any other
+TC_HD uint8_t job_commitment_evaluate_idx(const uint8_t* commit, size_t degree, uint64_t idx, G1Jac& res) {
+  const uint64_t x = idx + 1;
+  G1Affine c;
+  bool ok = g1_decode_uncompressed(commit + degree * 96, c);
+  res = G1Jac::from_affine(c);
+  TC_NOUNROLL for (size_t kk = degree; kk-- > 0;) {
+    G1Jac scaled;
+    if (x != 0) {
+      scaled = g1_mul_u64(res, x);
+    } else {
+      scaled = res;
+      TC_NOUNROLL for (int b = 0; b < 64; b++) scaled = jac_dbl(scaled);
+    }
+    ok &= g1_decode_uncompressed(commit + kk * 96, c);
+    res = jac_add_mixed(scaled, c);
+  }
+  return ok ? TC_JOB_OK : TC_JOB_INVALID_ENCODING;
+}
+// the constant check of one dealer: its C[pos(0, 0)] (c0: 96 B) against old_commit.evaluate(idx + 1), as GROUP ELEMENTS (both
+// sides re-encoded canonically).  OK / TC_JOB_SHARE_MISMATCH; INVALID_ENCODING when c0 does not decode.  An old_commit that does
+// not decode is the caller's to notice (the answer is then meaningless).
+TC_HD uint8_t job_reshare_constant_check(const uint8_t* old_commit, size_t t_old, uint64_t idx, const uint8_t* c0) {
+  G1Jac want;
+  (void)job_commitment_evaluate_idx(old_commit, t_old, idx, want);
+  G1Affine got;
+  if (!g1_decode_uncompressed(c0, got)) return TC_JOB_INVALID_ENCODING;
+  uint8_t a[96], b[96];
+  g1_encode_uncompressed(jac_to_affine(want), a);
+  g1_encode_uncompressed(got, b);
+  bool same = true;
+  TC_NOUNROLL for (int i = 0; i < 96; i++) same = same && a[i] == b[i];
+  return same ? TC_JOB_OK : TC_JOB_SHARE_MISMATCH;
+}
+
 }  // namespace tc

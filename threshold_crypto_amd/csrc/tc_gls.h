@@ -618,12 +618,10 @@ TC_HD bool glv_recode_sign_aligned(const uint32_t* k, tc_u128* neg_out, tc_u128*
 // ARENA: the table goes to this lane's 1 KB of the wave's arena slot (tc_table.h lane_table: full-line entries) instead of staying in
 // 224 registers -- the form of the kernels built for TWO waves per SIMD (256 registers), which batches above one wave per SIMD
 // take; the caller's kernel must hold a slot (table_slot_acquire).
+// (the ladder proper takes the recoded scalar, so that a caller who multiplies MANY points by one scalar recodes it once:
+// g1_mul_glv_recoded below)
 template <bool ARENA>
-TC_HD G1Jac g1_mul_glv_impl(const G1Affine& p, const uint32_t* k) {
-  if (!ARENA && p.inf) return G1Jac::infinity();
-  tc_u128 neg, u;
-  bool top;
-  const bool flip = glv_recode_sign_aligned(k, &neg, &u, &top);
+TC_HD G1Jac g1_mul_glv_ladder(const G1Affine& p, tc_u128 neg, tc_u128 u, bool top, bool flip) {
   G1Affine b = p;
   b.y = Fq::select(flip, -p.y, p.y).norm();
   const G1Jac p2 = jac_dbl(G1Jac::from_affine(b));
@@ -667,8 +665,25 @@ TC_HD G1Jac g1_mul_glv_impl(const G1Affine& p, const uint32_t* k) {
   if (ARENA && p.inf) acc = G1Jac::infinity();  // (uniform control flow up to here: the slot's stores and loads are the wave's)
   return acc;
 }
+template <bool ARENA>
+TC_HD G1Jac g1_mul_glv_impl(const G1Affine& p, const uint32_t* k) {
+  if (!ARENA && p.inf) return G1Jac::infinity();
+  tc_u128 neg, u;
+  bool top;
+  const bool flip = glv_recode_sign_aligned(k, &neg, &u, &top);
+  return g1_mul_glv_ladder<ARENA>(p, neg, u, top, flip);
+}
 TC_HD_NOINLINE G1Jac g1_mul_glv(const G1Affine& p, const uint32_t* k) { return g1_mul_glv_impl<false>(p, k); }
 TC_HD_NOINLINE G1Jac g1_mul_glv_arena(const G1Affine& p, const uint32_t* k) { return g1_mul_glv_impl<true>(p, k); }
+// [k] P from glv_recode_sign_aligned's output for k (one scalar over many points: the weighted sums of tc_dkg.h)
+struct GlvRecoded {
+  tc_u128 neg, u;
+  bool top, flip;
+};
+TC_HD_NOINLINE G1Jac g1_mul_glv_recoded(const G1Affine& p, const GlvRecoded& w) {
+  if (p.inf) return G1Jac::infinity();
+  return g1_mul_glv_ladder<false>(p, w.neg, w.u, w.top, w.flip);
+}
 // the same for a Jacobian P (the share combiner's final [D^-1] step)
 // (no inversion: (X, Y) is an affine point of the isomorphic curve y^2 = x^3 + b Z^6, phi acts on
 // it the same way, and the a = 0 group law never reads b; the result's Z is multiplied by Z)

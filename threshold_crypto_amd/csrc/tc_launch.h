@@ -56,6 +56,7 @@ struct Tuning {
   size_t msm_budget = 0;      // bytes the per-share tables of the two-stage kernels may take per call; 0 = a third of the free HBM, 1-24 GiB (TC_MSM_BUDGET: tests)
   int checks_beside = 1;  // checked-input mode: the membership tests on a second stream beside the call's main kernels (TC_CHECKS_BESIDE=0: before them, one stream)
   size_t sum_parts = 0;   // lanes per output of k_g1_sum (TC_SUM_PARTS=<1|2|4|...|64>: tests, tools/g1_sum_probe.py); 0 = by B, n and the CU count (g1_sum_parts)
+  size_t wsum_slices = 0; // slices per output of k_g1_wsum (TC_WSUM_SLICES=<n>: tests, tools/dkg_reshare_probe.py); 0 = by B, n and the CU count (g1_wsum_slices)
   size_t records_parts = 0;  // lanes / lane pairs per segment of the ragged sums (TC_RECORDS_PARTS=<1|2|...|64>: tests, tools/verify_records_probe.py); 0 = rec_parts
 };
 
@@ -285,6 +286,34 @@ void launch_bivar_column0(hipStream_t st, const uint8_t* commits, size_t stride,
 // the outputs (either may be null) when one of them failed
 void launch_dkg_generate_verdict(hipStream_t st, const uint8_t* accept, const uint8_t* point_bad, const uint8_t* share_st, size_t P, size_t degree,
                                  uint8_t* part_status, uint8_t* out_commit, uint8_t* out_share);
+// DKG resharing (k_dkg.hip): the sums above with one public weight per term.  weights_fr: n x 32 B LE canonical; rec: n x
+// wsum_rec_words() words, the weights validated and recoded once per term (launch_wsum_recode) for launch_g1_wsum, which takes
+// its lanes per output from g1_wsum_parts.  A non-canonical weight of an included term fails every output.  sel (may be null): n
+// term numbers, the sum runs over those terms only (everything else is still addressed by term).
+size_t wsum_rec_words();
+size_t g1_wsum_parts(size_t B, size_t n, int cus, size_t forced);
+void launch_wsum_recode(hipStream_t st, const uint8_t* weights_fr, size_t n, uint32_t* rec);
+// slices > 1 (g1_wsum_slices): out = B x slices partial sums, slice-major, with one validity byte each in part_ok -- the caller adds
+// them up with launch_g1_sum (term_stride B * 96, n = slices, member = part_ok); slices = 1: out / status are the final ones
+size_t g1_wsum_slices(size_t B, size_t n, size_t parts, int cus, size_t forced);
+void launch_g1_wsum(hipStream_t st, bool column0, const uint8_t* pts, size_t term_stride, size_t n, const uint32_t* rec, const uint8_t* mask,
+                    const uint8_t* member, size_t B, size_t parts, size_t slices, uint8_t* out, uint8_t* status, uint8_t* part_ok,
+                    const uint32_t* sel = nullptr);
+void launch_fr_wsum(hipStream_t st, const uint8_t* vals_fr, size_t term_stride, size_t n, const uint8_t* weights_fr, const uint8_t* mask, size_t B,
+                    uint8_t* out_fr, uint8_t* status);
+// tc_dkg_reshare_batch.  launch_reshare_check: per part const_st / point_bad / dup (P bytes each) and old_bad (1 byte); member:
+// P x (degree+1) verdicts of the first columns' membership test or null, old_member: t_old + 1 or null.  launch_reshare_verdict:
+// part_status, then the call's status byte, used (P bytes), the dealers of S (sel_part / sel_idx: t_old + 1 entries) and their
+// Lagrange coefficients as weights (P x 32 B, zeroed by the caller); ws: reshare_plan_ws_words(t_old).  launch_reshare_guard:
+// identities / zero over the outputs (either may be null) unless the status byte is OK.
+void launch_reshare_check(hipStream_t st, const uint8_t* old_commit, const uint8_t* old_member, size_t t_old, const uint64_t* dealer_idx,
+                          const uint8_t* commits, size_t stride, size_t degree, const uint8_t* accept, const uint8_t* member, size_t P,
+                          uint8_t* const_st, uint8_t* point_bad, uint8_t* dup, uint8_t* old_bad);
+size_t reshare_plan_ws_words(size_t t_old);
+void launch_reshare_verdict(hipStream_t st, const uint8_t* accept, const uint64_t* dealer_idx, size_t t_old, size_t P, const uint8_t* const_st,
+                            const uint8_t* point_bad, const uint8_t* dup, const uint8_t* share_st, const uint8_t* old_bad, uint8_t* part_status,
+                            uint8_t* used, uint32_t* sel_part, uint64_t* sel_idx, uint32_t* ws, uint8_t* weights, uint8_t* status);
+void launch_reshare_guard(hipStream_t st, const uint8_t* status, size_t degree, uint8_t* out_commit, uint8_t* out_share);
 
 // The robust combiners (k_robust.hip; selection rule in tc_robust.h).  present / bad: jobs x N mask bytes, either may be null.
 //   launch_select_shares    idx / slot (jobs x need) = the first `need` eligible slots of every job; enough[j]; the used bytes of a

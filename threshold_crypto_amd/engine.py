@@ -997,6 +997,70 @@ class Engine:
                    _ptr(xs) if n_v else None, _ptr(vals_fr) if n_v else None, n_v, _ptr(out), _ptr(share) if share is not None else None, _ptr(st))
         return out, share, st
 
+    # -- DKG resharing: the same sums with Lagrange weights (src/poly.rs:210-254, 462-471; src/lib.rs:719-767) ----------
+    def g1_weighted_sum(self, pts, weights_fr, mask=None):
+        """pts (n, B, 96), weights_fr (n, 32) canonical LE, public -> out[j] = sum of the included weights[k] * pts[k, j]: (B, 96),
+        status (B,).  An included term with a non-canonical weight fails every output."""
+        dev = self._mode(pts, weights_fr, mask)
+        self._arg(pts, (None, None, G1_BYTES), "u8", "pts")
+        n, B = pts.shape[0], pts.shape[1]
+        self._arg(weights_fr, (n, FR_BYTES), "u8", "weights_fr")
+        out = self._empty(dev, (B, G1_BYTES), ref=pts)
+        st = self._empty(dev, (B,), ref=pts)
+        self._call("tc_g1_weighted_sum_batch", _ptr(pts) if n else None, B * G1_BYTES, n, _ptr(weights_fr) if n else None, self._mask(mask, n, "mask"),
+                   B, _ptr(out), _ptr(st))
+        return out, st
+
+    def fr_weighted_sum(self, vals_fr, weights_fr, mask=None):
+        """vals_fr (n, B, 32) secret, weights_fr (n, 32) public -> out[j] = sum of the included weights[k] * vals_fr[k, j] mod r:
+        (B, 32), status (B,)"""
+        dev = self._mode(vals_fr, weights_fr, mask)
+        self._arg(vals_fr, (None, None, FR_BYTES), "u8", "vals_fr")
+        n, B = vals_fr.shape[0], vals_fr.shape[1]
+        self._arg(weights_fr, (n, FR_BYTES), "u8", "weights_fr")
+        out = self._empty(dev, (B, FR_BYTES), ref=vals_fr)
+        st = self._empty(dev, (B,), ref=vals_fr)
+        self._call("tc_fr_weighted_sum_batch", _ptr(vals_fr) if n else None, B * FR_BYTES, n, _ptr(weights_fr) if n else None,
+                   self._mask(mask, n, "mask"), B, _ptr(out), _ptr(st))
+        return out, st
+
+    def dkg_reshare(self, old_commit, dealer_idx, commits, degree, accept=None, xs=None, vals_fr=None):
+        """The finalisation of a resharing: old_commit (t_old+1, 96), dealer_idx (P,) u64 (part p is dealt by old node dealer_idx[p]),
+        commits / accept / xs / vals_fr as in dkg_generate -> (the new commitment (degree+1, 96), the share (32,) or None, used (P,),
+        part_status (P,), status (1,)).  Unless status is 0 the commitment is identities, the share zero and used all zero."""
+        dev = self._mode(old_commit, dealer_idx, commits, accept, xs, vals_fr)
+        self._arg(old_commit, (None, G1_BYTES), "u8", "old_commit")
+        self._arg(commits, (None, None, G1_BYTES), "u8", "commits")
+        P, S = commits.shape[0], commits.shape[1]
+        self._arg(dealer_idx, (P,), "u64", "dealer_idx")
+        if old_commit.shape[0] < 1:
+            raise ValueError("old_commit: at least one coefficient")
+        if S < (degree + 1) * (degree + 2) // 2:
+            raise ValueError("commits: a commitment of degree %d holds %d points" % (degree, (degree + 1) * (degree + 2) // 2))
+        if (xs is None) != (vals_fr is None):
+            raise ValueError("xs and vals_fr come together")
+        n_v = 0
+        if xs is not None:
+            self._arg(xs, (P, None), "u64", "xs")
+            n_v = xs.shape[1]
+            self._arg(vals_fr, (P, n_v, FR_BYTES), "u8", "vals_fr")
+        out = self._empty(dev, (degree + 1, G1_BYTES), ref=commits)
+        share = self._empty(dev, (FR_BYTES,), ref=commits) if xs is not None else None
+        used = self._empty(dev, (P,), ref=commits)
+        st = self._empty(dev, (P,), ref=commits)
+        status = self._empty(dev, (1,), ref=commits)
+        if P == 0:                                   # nobody dealt (the C entry treats P = 0 as a no-op)
+            out[:] = 0
+            out[:, 0] = 0x40
+            if share is not None:
+                share[:] = 0
+            status[:] = _native.JOB_NOT_ENOUGH_SHARES
+            return out, share, used, st, status
+        self._call("tc_dkg_reshare_batch", _ptr(old_commit), old_commit.shape[0] - 1, _ptr(dealer_idx), _ptr(commits), S * G1_BYTES, int(degree), P,
+                   self._mask(accept, P, "accept"), _ptr(xs) if n_v else None, _ptr(vals_fr) if n_v else None, n_v, _ptr(out),
+                   _ptr(share) if share is not None else None, _ptr(used), _ptr(st), _ptr(status))
+        return out, share, used, st, status
+
 
 class Group:
     """tc_group: several GPUs of one node driven from this process (one worker thread per GPU inside the library),

@@ -14,6 +14,9 @@ method names, group work on the MI355X behind the C ABI.
   Poly.sum                                 tc_fr_sum_batch             (Poly::add_assign, src/poly.rs:68-80)
   BivarCommitment.row0_sum                 tc_bivar_commitment_row0_sum_batch (`sum_commit += bi_commit.row(0)`)
   dkg_generate                             tc_dkg_generate_batch       (the accepted parts -> commitment and share)
+  Commitment.weighted_sum                  tc_g1_weighted_sum_batch    (`Poly * Fr` src/poly.rs:210-254 in the exponent, then :462-471)
+  Poly.weighted_sum                        tc_fr_weighted_sum_batch    (`Poly * Fr`, then Poly::add_assign)
+  dkg_reshare                              tc_dkg_reshare_batch        (old holders deal, the master key stays)
 
 Secret polynomials (Poly, BivarPoly) are Fr coefficient lists.  Poly.evaluate, BivarPoly.row and add/mul keep their
 host form (key generation outside the hot path in the reference; SecretKeySet does the same in api.py); the batch
@@ -22,7 +25,7 @@ imports the oracle; there is no CPU fallback for the group operations.
 """
 import numpy as np
 
-from .api import _R, _stack, _raise_status, _require_members, default_engine
+from .api import _R, _stack, _raise_status, _require_members, default_engine, Error
 
 
 def into_fr(x):
@@ -134,6 +137,24 @@ class Commitment:
             _raise_status(s)
         return Commitment(Commitment([bytes(p) for p in out], _trusted=True)._trimmed(), _trusted=True)
 
+    @staticmethod
+    def weighted_sum(commits, weights, mask=None, engine=None):
+        """sum_k weights[k] * commits[k] on the device (`Poly * Fr` src/poly.rs:210-254 in the exponent, folded by
+        Commitment::add_assign :462-471).  weights: IntoFr values, public; mask as in Commitment.sum."""
+        e = engine or default_engine()
+        commits = list(commits)
+        if len(weights) != len(commits):
+            raise ValueError("one weight per commitment")
+        width = max([len(c.coeff) for c in commits] + [0])
+        if width == 0:
+            return Commitment([], _trusted=True)
+        inf = bytes([0x40]) + bytes(95)
+        pts = np.stack([_stack(c.coeff + [inf] * (width - len(c.coeff)), 96) for c in commits])
+        out, st = e.g1_weighted_sum(pts, _fr_rows(weights), _mask_bytes(mask, len(commits)))
+        for s in st:
+            _raise_status(s)
+        return Commitment(Commitment([bytes(p) for p in out], _trusted=True)._trimmed(), _trusted=True)
+
     def verify_values(self, xs, vals, seed=None, engine=None):
         """`bi_commit.evaluate(m, s) == g1 * val` (src/poly.rs:846-848) with self = bi_commit.row(m): one bool per
         (u64 abscissa, value) pair.  With a 32-byte secret `seed` the values are checked by one random linear
@@ -225,6 +246,26 @@ class Poly:
             _raise_status(s)
         return Poly([int.from_bytes(bytes(c), "little") for c in out])
 
+    @staticmethod
+    def weighted_sum(polys, weights, mask=None, engine=None):
+        """sum_k weights[k] * polys[k] on the device (`Poly * Fr` src/poly.rs:210-254, then Poly::add_assign :68-80); the staged
+        coefficients are wiped there.  weights: IntoFr values, public."""
+        e = engine or default_engine()
+        polys = list(polys)
+        if len(weights) != len(polys):
+            raise ValueError("one weight per polynomial")
+        width = max([len(p.coeff) for p in polys] + [0])
+        if width == 0:
+            return Poly([])
+        vals = np.zeros((len(polys), width, 32), dtype=np.uint8)
+        for k, p in enumerate(polys):
+            if p.coeff:
+                vals[k, :len(p.coeff)] = _fr_rows(p.coeff)
+        out, st = e.fr_weighted_sum(vals, _fr_rows(weights), _mask_bytes(mask, len(polys)))
+        for s in st:
+            _raise_status(s)
+        return Poly([int.from_bytes(bytes(c), "little") for c in out])
+
     def commitment(self, engine=None):
         """Poly::commitment (src/poly.rs:372-377)."""
         return Poly.commitment_batch([self], engine)[0]
@@ -281,6 +322,13 @@ class BivarPoly:
 
     def degree(self):
         return self.degree_
+
+    @staticmethod
+    def random_with_constant(degree, secret, rng):
+        """The dealer's side of a resharing: a random symmetric polynomial of `degree` with F(0, 0) = secret (BivarPoly::random,
+        src/poly.rs:562-585, with coefficient (0, 0) replaced).  rng: anything with randrange, e.g. secrets.SystemRandom()."""
+        n = (int(degree) + 1) * (int(degree) + 2) // 2
+        return BivarPoly(degree, [into_fr(secret)] + [rng.randrange(_R) for _ in range(n - 1)])
 
     def _powers(self, x):
         out, p, x = [], 1, into_fr(x)
@@ -403,6 +451,29 @@ class BivarCommitment:
         return rc, [bool(ok[j]) and ok_len[j] for j in range(len(xs))]
 
 
+def _stage_samples(samples, acc, P):
+    """the (u64 abscissa, value) pairs a node received, one set per dealer, as the (P, n_v) / (P, n_v, 32) arrays of the
+    finalisation entries; (None, None) for an observer"""
+    if samples is None:
+        return None, None
+    if len(samples) != P:
+        raise ValueError("one set of samples per dealer")
+    taken = [acc is None or acc[p] for p in range(P)]
+    ordered = [(sorted(s.items()) if isinstance(s, dict) else list(s)) if t else None for s, t in zip(samples, taken)]
+    n_v = max([len(s) for s in ordered if s is not None] + [0])
+    if any(s is not None and len(s) != n_v for s in ordered):
+        raise ValueError("every accepted dealer needs the same number of samples")
+    if any(not 0 <= int(x) < 2 ** 64 for s in ordered if s is not None for x, _ in s):
+        raise ValueError("values are addressed by u64 abscissae")
+    xs = np.zeros((P, n_v), dtype=np.uint64)
+    vals = np.zeros((P, n_v, 32), dtype=np.uint8)
+    for p, s in enumerate(ordered):
+        if s is not None and n_v:
+            xs[p] = [int(x) for x, _ in s]
+            vals[p] = _fr_rows([y for _, y in s])
+    return xs, vals
+
+
 def dkg_generate(bi_commits, accepted, samples=None, engine=None):
     """The end of `distributed_key_generation` (src/poly.rs:870-876, 895-898) over the accepted parts: returns (the key set's
     Commitment, this node's secret key share or None).  bi_commits: one BivarCommitment per dealer; accepted: one truthy /
@@ -418,23 +489,7 @@ def dkg_generate(bi_commits, accepted, samples=None, engine=None):
     if any(c.degree_ != d for c in bi_commits):
         raise ValueError("all commitments of one batch must have the same degree")
     acc = _mask_bytes(accepted, P)
-    xs = vals = None
-    if samples is not None:
-        if len(samples) != P:
-            raise ValueError("one set of samples per dealer")
-        taken = [acc is None or acc[p] for p in range(P)]
-        ordered = [(sorted(s.items()) if isinstance(s, dict) else list(s)) if t else None for s, t in zip(samples, taken)]
-        n_v = max([len(s) for s in ordered if s is not None] + [0])
-        if any(s is not None and len(s) != n_v for s in ordered):
-            raise ValueError("every accepted dealer needs the same number of samples")
-        if any(not 0 <= int(x) < 2 ** 64 for s in ordered if s is not None for x, _ in s):
-            raise ValueError("values are addressed by u64 abscissae")
-        xs = np.zeros((P, n_v), dtype=np.uint64)
-        vals = np.zeros((P, n_v, 32), dtype=np.uint8)
-        for p, s in enumerate(ordered):
-            if s is not None and n_v:
-                xs[p] = [int(x) for x, _ in s]
-                vals[p] = _fr_rows([y for _, y in s])
+    xs, vals = _stage_samples(samples, acc, P)
     out, share, st = e.dkg_generate(np.stack([_stack(c.coeff, 96) for c in bi_commits]), d, acc, xs, vals)
     for s in st:
         if int(s) == 2:
@@ -442,3 +497,40 @@ def dkg_generate(bi_commits, accepted, samples=None, engine=None):
         _raise_status(s)
     commit = Commitment(Commitment([bytes(p) for p in out], _trusted=True)._trimmed(), _trusted=True)
     return commit, (int.from_bytes(bytes(share), "little") if share is not None else None)
+
+
+class ShareMismatch(Error):
+    """a resharing dealer's constant term is not the public key share of the old node it claims to be (TC_JOB_SHARE_MISMATCH)"""
+
+
+def dkg_reshare(old_commit, dealer_idx, bi_commits, accepted, samples=None, engine=None):
+    """Hands the SAME master key to a new validator set (tc_dkg_reshare_batch): old node dealer_idx[p] dealt bi_commits[p], a
+    symmetric polynomial of the new degree whose constant term is its share of old_commit's key.  The first
+    old_commit.degree() + 1 accepted parts are combined with their Lagrange coefficients at zero.  accepted and samples as
+    in dkg_generate.  Returns (the new key set's Commitment -- its coefficient 0 is old_commit's --, this node's new secret key
+    share or None, used: one bool per dealer).  A failed accepted part raises, as in dkg_generate; a dealer whose constant
+    term is not its public key share raises ShareMismatch, too few accepted parts NotEnoughShares."""
+    e = engine or default_engine()
+    bi_commits = list(bi_commits)
+    P = len(bi_commits)
+    if len(dealer_idx) != P:
+        raise ValueError("one dealer index per part")
+    if any(not 0 <= int(i) < 2 ** 64 for i in dealer_idx):
+        raise ValueError("dealers are addressed by u64 indices")
+    if not old_commit.coeff:
+        raise ValueError("old_commit: the commitment of the key set being handed over")
+    if P == 0:
+        _raise_status(1)
+    d = bi_commits[0].degree_
+    if any(c.degree_ != d for c in bi_commits):
+        raise ValueError("all commitments of one batch must have the same degree")
+    acc = _mask_bytes(accepted, P)
+    xs, vals = _stage_samples(samples, acc, P)
+    out, share, used, st, status = e.dkg_reshare(_stack(old_commit.coeff, 96), np.array([int(i) for i in dealer_idx], dtype=np.uint64),
+                                                 np.stack([_stack(c.coeff, 96) for c in bi_commits]), d, acc, xs, vals)
+    for s in list(st) + [status[0]]:
+        if int(s) == 4:
+            raise ShareMismatch("a dealer's constant term is not its public key share")
+        _raise_status(s)
+    commit = Commitment(Commitment([bytes(p) for p in out], _trusted=True)._trimmed(), _trusted=True)
+    return commit, (int.from_bytes(bytes(share), "little") if share is not None else None), [bool(u) for u in used]
