@@ -146,6 +146,14 @@ int tc_sign_shares_g2_batch(tc_ctx* ctx, const uint8_t* sk_table, size_t N, cons
 /* SecretKeyShare::decrypt_share_no_verify src/lib.rs:460-462, SecretKey::public_key :367-369 */
 int tc_g1_mul_batch(tc_ctx* ctx, const uint8_t* fr, const uint8_t* pts, size_t S, size_t B, uint8_t* out,
                     uint8_t* status);
+/* out[j*n + k] = sk_table[idx[j*n + k]] * u[j]: SecretKeyShare::decrypt_share_no_verify (src/lib.rs:460-462) for
+ * the n selected holders of ciphertext j.  status[j*n + k].  u is tested for membership in checked-input mode.
+ * The G1 counterpart of tc_sign_shares_g2_batch: an index >= N or a scalar >= r fails its own output
+ * (TC_JOB_INVALID_ENCODING, the identity's encoding), an undecodable u the n outputs of its ciphertext.  From enough holders
+ * and ciphertexts on (TC_COMB_G1_MIN="<holders>,<batch>" at tc_ctx_create overrides the built-in thresholds) the doublings are
+ * done once per ciphertext, on a comb of u (profiles/decrypt_shares_probe.txt). */
+int tc_decrypt_shares_g1_batch(tc_ctx* ctx, const uint8_t* sk_table, size_t N, const uint64_t* idx, const uint8_t* u_g1,
+                               size_t n, size_t B, uint8_t* out, uint8_t* status);
 /* out[j*S + s] = fr[s] * hash_g2(msg[j])   SecretKey::sign :379-381, SecretKeyShare::sign :447-449 */
 int tc_sign_batch(tc_ctx* ctx, const uint8_t* fr, const uint8_t* msgs, const uint64_t* off, size_t S, size_t B,
                   uint8_t* out_g2, uint8_t* status);
@@ -333,6 +341,13 @@ int tc_ciphertext_verify_rlc_batch(tc_ctx* ctx, const uint8_t* u_g1, const uint8
  * Ciphertext only exists after the checked decode, src/lib.rs:140-146).  A non-canonical sk_fr (>= r) gives ok[j] = 0. */
 int tc_decrypt_share_batch(tc_ctx* ctx, const uint8_t* sk_fr, const uint8_t* u_g1, const uint8_t* v, const uint64_t* off,
                            const uint8_t* w_g2, size_t B, uint8_t* out_g1, uint8_t* ok);
+/* SecretKeyShare::decrypt_share (src/lib.rs:452-457) for the same holders: Ciphertext::verify ONCE per ciphertext,
+ * then the n shares.  ok[j] = 0 -> the n outputs are the identity's encoding.  u and w are tested for membership
+ * ALWAYS, as in tc_decrypt_share_batch.  out: B x n x 96 B; status[j*n + k] (may be NULL): a holder's own failure (index >= N,
+ * scalar >= r) fails that output only and leaves ok[j] alone. */
+int tc_decrypt_shares_batch(tc_ctx* ctx, const uint8_t* sk_table, size_t N, const uint64_t* idx, const uint8_t* u_g1,
+                            const uint8_t* v, const uint64_t* off, const uint8_t* w_g2, size_t n, size_t B,
+                            uint8_t* out, uint8_t* ok, uint8_t* status);
 /* SecretKey::decrypt src/lib.rs:384-391: Ciphertext::verify, g = [sk] u, xor_with_hash(g, v).  out bytes[off[j]..off[j+1]] =
  * the plaintext when ok[j] = 1, zeros when the ciphertext is invalid (None). */
 int tc_secret_key_decrypt_batch(tc_ctx* ctx, const uint8_t* sk_fr, const uint8_t* u_g1, const uint8_t* v, const uint64_t* off,

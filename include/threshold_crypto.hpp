@@ -454,6 +454,43 @@ inline std::vector<std::vector<SignatureShare>> sign_shares_batch(const std::vec
   return out;
 }
 
+// S key holders x B ciphertexts in one call (tc_decrypt_shares_batch: Ciphertext::verify once per ciphertext, then the S
+// multiplications): out[j][s] = shares[s].decrypt_share(cts[j]) (src/lib.rs:452-457); out[j] is empty where Ciphertext::verify fails
+inline std::vector<std::optional<std::vector<DecryptionShare>>> decrypt_shares_batch(const std::vector<const SecretKeyShare*>& shares,
+                                                                                    const std::vector<Ciphertext>& cts,
+                                                                                    Engine& e = Engine::instance()) {
+  const std::size_t S = shares.size(), B = cts.size();
+  std::vector<std::optional<std::vector<DecryptionShare>>> out(B);
+  if (!S || !B) return out;
+  std::vector<std::uint8_t> fr(S * 32), u(B * 96), w(B * 192), flat(S * B * 96), st(S * B), ok(B);
+  std::vector<std::uint64_t> idx(S * B), off(B + 1, 0);
+  Bytes v;
+  for (std::size_t s = 0; s < S; s++) std::memcpy(&fr[s * 32], shares[s]->key().fr().data(), 32);
+  for (std::size_t j = 0; j < B; j++) {
+    std::memcpy(&u[j * 96], cts[j].u.data(), 96);
+    std::memcpy(&w[j * 192], cts[j].w.data(), 192);
+    v.insert(v.end(), cts[j].v.begin(), cts[j].v.end());
+    off[j + 1] = v.size();
+    for (std::size_t s = 0; s < S; s++) idx[j * S + s] = s;
+  }
+  std::uint8_t dummy = 0;
+  const int rc = tc_decrypt_shares_batch(e.ctx(), fr.data(), S, idx.data(), u.data(), v.empty() ? &dummy : v.data(), off.data(), w.data(), S, B,
+                                         flat.data(), ok.data(), st.data());
+  volatile std::uint8_t* z = fr.data();
+  for (std::size_t i = 0; i < fr.size(); i++) z[i] = 0;
+  e.check(rc);
+  for (std::size_t j = 0; j < B; j++) {
+    if (!ok[j]) continue;
+    std::vector<DecryptionShare> row(S);
+    for (std::size_t s = 0; s < S; s++) {
+      raise_status(st[j * S + s]);
+      std::memcpy(row[s].g1.data(), &flat[(j * S + s) * 96], 96);
+    }
+    out[j] = std::move(row);
+  }
+  return out;
+}
+
 // struct PublicKeySet { commit: Commitment } (src/lib.rs:539-543): commit = G1 coefficients
 class PublicKeySet {
  public:

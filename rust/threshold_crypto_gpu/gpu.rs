@@ -348,6 +348,44 @@ impl SecretKeyShare {
         out.chunks(G1_BYTES).zip(ok).map(|(c, good)| if good == 1 { g1_from(c).map(|p| Some(DecryptionShare(p))) } else { Ok(None) }).collect()
     }
 }
+impl SecretKeySet {
+    /// The decryption shares of B ciphertexts by per-ciphertext holder subsets, generated on the device from the key set
+    /// (tc_decrypt_shares_batch): `holders[j]` lists the n share indices of ciphertext j; out[j] = `None` where the ciphertext
+    /// does not verify (Ciphertext::verify runs ONCE per ciphertext), else out[j][k] = share(holders[j][k]).decrypt_share(cts[j]).
+    pub fn decrypt_shares_batch(&self, gpu: &Gpu, n_nodes: usize, holders: &[Vec<u64>], cts: &[Ciphertext]) -> GpuResult<Vec<Option<Vec<DecryptionShare>>>> {
+        let b = cts.len();
+        let n = holders.first().map(|s| s.len()).unwrap_or(0);
+        if holders.len() != b || holders.iter().any(|s| s.len() != n) {
+            return Err(shape_error("one holder list of the same length per ciphertext"));
+        }
+        if b == 0 || n == 0 {
+            return Ok((0..b).map(|_| None).collect());
+        }
+        let mut table = Vec::with_capacity(n_nodes * FR_BYTES);
+        for i in 0..n_nodes {
+            table.extend_from_slice(&fr_bytes(&(self.secret_key_share(i).0).0));
+        }
+        let idx: Vec<u64> = holders.iter().flatten().cloned().collect();
+        let (u, flat, off, w) = ciphertext_columns(cts);
+        let (mut out, mut ok, mut st) = (vec![0u8; b * n * G1_BYTES], vec![0u8; b], vec![0u8; b * n]);
+        let rc = unsafe {
+            tc_decrypt_shares_batch(gpu.0, table.as_ptr(), n_nodes, idx.as_ptr(), u.as_ptr(), flat.as_ptr(), off.as_ptr(), w.as_ptr(), n, b, out.as_mut_ptr(), ok.as_mut_ptr(), st.as_mut_ptr())
+        };
+        table.iter_mut().for_each(|x| *x = 0);
+        gpu.check(rc)?;
+        out.chunks(n * G1_BYTES)
+            .zip(ok)
+            .zip(st.chunks(n))
+            .map(|((job, good), job_st)| -> GpuResult<Option<Vec<DecryptionShare>>> {
+                if good != 1 {
+                    return Ok(None);
+                }
+                all_ok(job_st)?;
+                Ok(Some(g1_vec(job)?.into_iter().map(DecryptionShare).collect()))
+            })
+            .collect()
+    }
+}
 impl SecretKey {
     /// `decrypt` for B ciphertexts (src/lib.rs:384-391): `None` where the ciphertext does not verify; verify, [sk] u and
     /// xor_with_hash in one call (tc_secret_key_decrypt_batch).

@@ -33,6 +33,7 @@ PROTOTYPES = {
     "tc_g2_mul_batch": [_u8p, _u8p, _sz, _sz, _u8p, _u8p],
     "tc_g1_mul_batch": [_u8p, _u8p, _sz, _sz, _u8p, _u8p],
     "tc_sign_shares_g2_batch": [_u8p, _sz, _u64p, _u8p, _sz, _sz, _u8p, _u8p],
+    "tc_decrypt_shares_g1_batch": [_u8p, _sz, _u64p, _u8p, _sz, _sz, _u8p, _u8p],
     "tc_sign_batch": [_u8p, _u8p, _u64p, _sz, _sz, _u8p, _u8p],
     "tc_combine_g2_batch": [_sz, _sz, _u64p, _u8p, _sz, _u8p, _u8p],
     "tc_combine_g1_batch": [_sz, _sz, _u64p, _u8p, _sz, _u8p, _u8p],
@@ -72,6 +73,7 @@ PROTOTYPES = {
     "tc_pairing_product_check_batch": [_u8p, _u8p, _sz, _sz, _u8p],
     "tc_ciphertext_verify_rlc_batch": [_u8p, _u8p, _u64p, _u8p, _sz, _sz, ctypes.c_char_p, _u8p, ctypes.POINTER(ctypes.c_uint64)],
     "tc_decrypt_share_batch": [_u8p, _u8p, _u8p, _u64p, _u8p, _sz, _u8p, _u8p],
+    "tc_decrypt_shares_batch": [_u8p, _sz, _u64p, _u8p, _u8p, _u64p, _u8p, _sz, _sz, _u8p, _u8p, _u8p],
     "tc_secret_key_decrypt_batch": [_u8p, _u8p, _u8p, _u64p, _u8p, _sz, _u8p, _u8p],
     "tc_verify_decryption_share_batch": [_u8p, _sz, _u8p, _u8p, _u8p, _u64p, _u8p, _sz, _u8p],
     "tc_encrypt_batch": [_u8p, _sz, _u8p, _u8p, _u64p, _sz, _u8p, _u8p, _u8p, _u8p],

@@ -501,6 +501,28 @@ def sign_shares_batch(secret_key_shares, msgs, engine=None):
     return [[SignatureShare(out[j, s], _trusted=True) for s in range(len(secret_key_shares))] for j in range(len(msgs))]
 
 
+def decrypt_shares_batch(secret_key_shares, cts, engine=None):
+    """S key holders x B ciphertexts in one call (tc_decrypt_shares_batch: Ciphertext::verify once per ciphertext, then the S
+    multiplications): result[j][s] = shares[s].decrypt_share(cts[j]), result[j] = None where Ciphertext::verify fails."""
+    e = engine or default_engine()
+    S, B = len(secret_key_shares), len(cts)
+    if S == 0 or B == 0:
+        return [[] for _ in range(B)]
+    v, off = pack_messages([ct.v for ct in cts])
+    table = _stack([s._bytes() for s in secret_key_shares], 32)
+    idx = np.ascontiguousarray(np.tile(np.arange(S, dtype=np.uint64), (B, 1)))
+    out, ok, st = e.decrypt_shares(table, idx, _stack([ct.u for ct in cts], 96), v, off, _stack([ct.w for ct in cts], 192))
+    rows = []
+    for j in range(B):
+        if not ok[j]:
+            rows.append(None)
+            continue
+        for s_ in st[j]:
+            _raise_status(s_)
+        rows.append([DecryptionShare(out[j, s], _trusted=True) for s in range(S)])
+    return rows
+
+
 def _ordered(shares):
     """The reference iterates a BTreeMap / any IntoIterator of (index, share): dicts are taken in
     ascending index order (BTreeMap), sequences of pairs in the order given."""

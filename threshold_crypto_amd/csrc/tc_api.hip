@@ -539,6 +539,18 @@ tc::Tuning tuning_from_env() {
     const size_t v = (size_t)strtoull(q, nullptr, 10);
     if (v >= 1 && v <= 64 && (v & (v - 1)) == 0) tn.records_parts = v;  // (G2 takes at most 32: a larger value means 32 there)
   }
+  if (const char* g = getenv("TC_COMB_G1_MIN")) {  // "<holders>,<batch>": both or neither
+    char* end = nullptr;
+    const unsigned long long h = strtoull(g, &end, 10);
+    if (end && end != g && *end == ',') {
+      const char* b = end + 1;
+      const unsigned long long m = strtoull(b, &end, 10);
+      if (end && end != b) {
+        tn.comb_g1_min_holders = (size_t)h;
+        tn.comb_g1_min_batch = (size_t)m;
+      }
+    }
+  }
   if (const char* o = getenv("TC_CHECKS_BESIDE")) tn.checks_beside = (o[0] >= '0' && o[0] <= '2') ? o[0] - '0' : 1;  // 0 one stream, 1 low priority, 2 normal
   return tn;
 }
@@ -872,6 +884,51 @@ int tc_sign_shares_g2_batch(tc_ctx* ctx, const uint8_t* sk_table, size_t N, cons
     tc::launch_g2_mul_gather(ctx->stream, k.tables(), d_sk, N, d_idx, d_h, n, B, d_out, d_st);
   }
   k.apply_checks(B * n, d_st, d_out, 192, nullptr);
+  k.end_timing();
+  return k.finish();
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+// out[j*n + k] = sk[idx[j*n + k]] * u[j] in G1 (the multiplication stage of both tc_decrypt_shares_* entries): the per-ciphertext
+// comb (k_comb.hip, tc_comb_g1.h) from the context's thresholds on, one arena ladder per share below them.  The combs (66 KB per
+// ciphertext) live in one HBM buffer, ciphertexts run through it in tiles.
+static void decrypt_shares_mul(Call& k, const uint8_t* d_sk, size_t N, const uint64_t* d_idx, const uint8_t* d_u, size_t n, size_t B,
+                               uint8_t* d_out, uint8_t* d_st) {
+  if (k.failed) return;
+  tc_ctx* ctx = k.c;
+  if (n >= ctx->tuning.comb_g1_min_holders && B >= ctx->tuning.comb_g1_min_batch) {
+    const size_t per_ct = tc::comb_table_bytes_g1(1);
+    size_t tile = msm_table_budget(k) / per_ct;
+    if (tile < 1) tile = 1;
+    if (tile > B) tile = B;
+    int32_t* d_tbl = k.temp<int32_t>(tc::comb_table_bytes_g1(tile) / sizeof(int32_t));
+    uint8_t* d_tok = k.temp<uint8_t>(tile);
+    for (size_t lo = 0; lo < B && !k.failed; lo += tile) {
+      const size_t cnt = (B - lo < tile) ? B - lo : tile;
+      tc::launch_comb_decrypt(ctx->stream, d_sk, N, d_idx + lo * n, d_u + lo * 96, n, cnt, d_tbl, d_tok, d_out + lo * n * 96,
+                              d_st ? d_st + lo * n : nullptr);
+    }
+  } else {
+    tc::launch_g1_mul_gather(ctx->stream, k.tables(), d_sk, N, d_idx, d_u, n, B, d_out, d_st);
+  }
+}
+
+int tc_decrypt_shares_g1_batch(tc_ctx* ctx, const uint8_t* sk_table, size_t N, const uint64_t* idx, const uint8_t* u_g1, size_t n, size_t B,
+                               uint8_t* out, uint8_t* status) try {
+  TC_REQUIRE(ctx);
+  if (n == 0 || B == 0) return TC_OK;
+  TC_REQUIRE(ctx && sk_table && idx && u_g1 && out && N > 0);
+  Call k(ctx);
+  const uint8_t* d_sk = k.in(sk_table, N * 32, /*secret=*/true);
+  const uint64_t* d_idx = k.in(idx, B * n);
+  const uint8_t* d_u = k.in(u_g1, B * 96);
+  uint8_t* d_out = k.out(out, B * n * 96);
+  uint8_t* d_st = k.out(status, B * n);
+  k.begin_timing();
+  k.check_points(false, d_u, 96, 1, 1, B, n);
+  decrypt_shares_mul(k, d_sk, N, d_idx, d_u, n, B, d_out, d_st);
+  k.apply_checks(B * n, d_st, d_out, 96, nullptr);
   k.end_timing();
   return k.finish();
 } catch (...) {
@@ -1959,6 +2016,46 @@ int tc_decrypt_share_batch(tc_ctx* ctx, const uint8_t* sk_fr, const uint8_t* u, 
                            size_t B, uint8_t* out_g1, uint8_t* ok) try {
   TC_REQUIRE(ctx && (B == 0 || out_g1));
   return verified_decrypt(ctx, sk_fr, u, v, off, w, B, out_g1, nullptr, ok);
+} catch (...) {
+  return on_exception((tc_ctx*)ctx);
+}
+
+// The same for n selected holders per ciphertext: Ciphertext::verify (the hash + pairing check of verified_decrypt) ONCE per
+// ciphertext, then the n shares by decrypt_shares_mul.  ok[j] is the verdict on ciphertext j; a holder's own failure (index >= N,
+// scalar >= r) is reported in its status byte and leaves ok[j] alone.
+int tc_decrypt_shares_batch(tc_ctx* ctx, const uint8_t* sk_table, size_t N, const uint64_t* idx, const uint8_t* u, const uint8_t* v,
+                            const uint64_t* off, const uint8_t* w, size_t n, size_t B, uint8_t* out, uint8_t* ok, uint8_t* status) try {
+  TC_REQUIRE(ctx);
+  if (n == 0 || B == 0) return TC_OK;
+  TC_REQUIRE(ctx && sk_table && idx && u && off && w && out && ok && N > 0);
+  Call k(ctx);
+  uint64_t total = 0;
+  if (!total_bytes(k, off, B, &total)) return k.finish();
+  TC_REQUIRE(total == 0 || v);
+  const uint8_t* d_sk = k.in(sk_table, N * 32, /*secret=*/true);
+  const uint64_t* d_idx = k.in(idx, B * n);
+  const uint8_t* d_u = k.in(u, B * 96);
+  const uint8_t* d_v = k.in(v, (size_t)total);
+  const uint64_t* d_off = k.in(off, B + 1);
+  const uint8_t* d_w = k.in(w, B * 192);
+  uint8_t* d_hash = k.temp<uint8_t>(B * 192);
+  uint8_t* d_ok = k.out(ok, B);
+  uint8_t* d_out = k.out(out, B * n * 96);
+  uint8_t* d_st = status ? k.out(status, B * n) : k.temp<uint8_t>(B * n);
+  k.begin_timing();
+  // ALWAYS, as in verified_decrypt: [sk] u for a u with a small-order component would leak sk modulo the cofactor's factors
+  k.check_points(false, d_u, 96, 1, 1, B, 1, /*always=*/true);
+  k.check_points(true, d_w, 192, 1, 1, B, 1, /*always=*/true);
+  if (!k.failed) {
+    tc::launch_hash_g1_g2(ctx->tuning, ctx->stream, d_u, d_v, d_off, B, d_hash, nullptr, /*fix=*/false);
+    tc::launch_pairing_check(ctx->stream, ctx->g1_gen_unfix, 0, d_w, 192, d_u, 96, d_hash, 192, B, d_ok, k.pairing_ws(B));  // src/lib.rs:511
+    k.apply_checks(B, nullptr, nullptr, 0, d_ok);
+    decrypt_shares_mul(k, d_sk, N, d_idx, d_u, n, B, d_out, d_st);
+    // `if !ct.verify() { return None; }` (src/lib.rs:453): a ciphertext that fails the check gets n identities, never [sk] u
+    if (!k.failed) tc::launch_invalidate_jobs(ctx->stream, d_ok, 1, n, B * n, d_st, d_out, 96, nullptr);
+  }
+  k.end_timing();
+  return k.finish();
 } catch (...) {
   return on_exception((tc_ctx*)ctx);
 }

@@ -40,6 +40,16 @@ constexpr size_t kDuoMinDecode = 32768 + 1;
 constexpr size_t kDuoMinHash = 131072;
 inline bool duo_form(size_t jobs, size_t min_jobs) { return jobs >= min_jobs; }
 
+// Decryption shares of many holders per ciphertext (tc_decrypt_shares_g1_batch): the per-ciphertext G1 comb (k_comb.hip) from this
+// many holders and this many ciphertexts on, one arena ladder per share below.  Measured (profiles/decrypt_shares_probe.txt, one
+// MI355X, ms comb / ladders): a comb is built by ONE lane per ciphertext in 128 dependent doubling steps, ~17 ms whatever the batch,
+// and a share then costs 0.4-0.5 of a ladder --
+//   n = 68:      B = 1 024: 17.7 / 3.8    4 096: 20.9 / 9.9    16 384: 31.8 / 30.9    65 536: 74.8 / 117.5    131 072: 125.4 / 234.0
+//   B = 65 536:  n = 4: 23.4 / 7.6    8: 26.1 / 14.7    16: 32.4 / 28.7    32: 51.0 / 56.0;      B = 131 072, n = 16: 53.7 / 56.1
+// -- so it pays from about 1.3 million shares per call on.  The two thresholds keep every call they admit above that.
+constexpr size_t kCombG1MinHolders = 24;
+constexpr size_t kCombG1MinBatch = 65536;
+
 // The form choices of a context.  The defaults are the measured thresholds above / in k_pairing.hip; the environment
 // (TC_DUO_MIN=<jobs>, TC_PAIRING_FORM=quad|lines|pair|fused, TC_PAIRING_BUDGET=<bytes>, TC_CHECKS_BESIDE=0|1: tests and experiments) is read ONCE,
 // when the context is created (tc_api.hip tuning_from_env) -- no getenv on the launch path, nothing a concurrent setenv can race
@@ -58,6 +68,9 @@ struct Tuning {
   size_t sum_parts = 0;   // lanes per output of k_g1_sum (TC_SUM_PARTS=<1|2|4|...|64>: tests, tools/g1_sum_probe.py); 0 = by B, n and the CU count (g1_sum_parts)
   size_t wsum_slices = 0; // slices per output of k_g1_wsum (TC_WSUM_SLICES=<n>: tests, tools/dkg_reshare_probe.py); 0 = by B, n and the CU count (g1_wsum_slices)
   size_t records_parts = 0;  // lanes / lane pairs per segment of the ragged sums (TC_RECORDS_PARTS=<1|2|...|64>: tests, tools/verify_records_probe.py); 0 = rec_parts
+  // tc_decrypt_shares_*: the G1 comb from this many holders AND this many ciphertexts on (TC_COMB_G1_MIN="<holders>,<batch>": tests,
+  // tools/decrypt_shares_probe.py)
+  size_t comb_g1_min_holders = kCombG1MinHolders, comb_g1_min_batch = kCombG1MinBatch;
 };
 
 // The G1 ladder kernels keep their per-lane table in the HBM arena and fit 256 registers (two waves per SIMD) at
@@ -92,6 +105,23 @@ inline size_t signers_per_lane_pair(size_t n, size_t B, size_t most) {
 size_t comb_table_bytes(size_t B);
 void launch_comb_sign(hipStream_t st, TableArena ta, const uint8_t* sk, size_t N, const uint64_t* idx, const uint8_t* pts, size_t n, size_t B,
                       int32_t* tbl, uint8_t* ok, uint8_t* out, uint8_t* status);
+// The same for decryption shares (k_comb.hip, tc_comb_g1.h): out[j*n + k] = sk[idx[j*n + k]] * pts[j] in G1, the shares of
+// ciphertext j by its n selected key holders out of N.  launch_comb_decrypt: a per-ciphertext comb in HBM (tbl:
+// comb_table_bytes_g1(B), ok: B bytes), then doubling-free multiplications; launch_g1_mul_gather: one arena ladder per share.
+// The comb runs from kCombG1MinHolders holders and kCombG1MinBatch ciphertexts on (TC_COMB_G1_MIN="<holders>,<batch>" at
+// context creation overrides both: Tuning::comb_g1_min_*, above).
+// holders a lane of k_comb_decrypt takes: the G1 twin of signers_per_lane_pair -- one lane per job, so ONE round of the 2048
+// wave slots is 131 072 lanes
+inline size_t holders_per_lane(size_t n, size_t B, size_t most) {
+  for (size_t share = 1; share < most; share++)
+    if (((n + share - 1) / share) * B <= 131072) return share;
+  return most;
+}
+size_t comb_table_bytes_g1(size_t B);
+void launch_comb_decrypt(hipStream_t st, const uint8_t* sk, size_t N, const uint64_t* idx, const uint8_t* pts, size_t n, size_t B, int32_t* tbl,
+                         uint8_t* ok, uint8_t* out, uint8_t* status);
+void launch_g1_mul_gather(hipStream_t st, TableArena ta, const uint8_t* sk, size_t N, const uint64_t* idx, const uint8_t* pts, size_t n, size_t B,
+                          uint8_t* out, uint8_t* status);
 void launch_g1_compress(hipStream_t st, const uint8_t* in, size_t B, uint8_t* out, uint8_t* status);
 void launch_g2_compress(hipStream_t st, const uint8_t* in, size_t B, uint8_t* out, uint8_t* status);
 void launch_g1_decompress(hipStream_t st, const uint8_t* in, size_t B, uint8_t* out, uint8_t* status);

@@ -254,6 +254,19 @@ class Engine:
         self._call("tc_sign_shares_g2_batch", _ptr(sk_table), sk_table.shape[0], _ptr(idx), _ptr(hashes), n, B, _ptr(out), _ptr(st))
         return out, st
 
+    def decrypt_shares_g1(self, sk_table, idx, u):
+        """out[j, k] = sk_table[idx[j, k]] * u[j]: SecretKeyShare::decrypt_share_no_verify (src/lib.rs:460-462) for the selected
+        holders of each ciphertext -> (shares (B, n, 96), status (B, n))"""
+        dev = self._mode(sk_table, idx, u)
+        self._arg(sk_table, (None, FR_BYTES), "u8", "sk_table")
+        self._arg(idx, (None, None), "u64", "idx")
+        B, n = idx.shape
+        self._arg(u, (B, G1_BYTES), "u8", "u")
+        out = self._empty(dev, (B, n, G1_BYTES), ref=u)
+        st = self._empty(dev, (B, n), ref=u)
+        self._call("tc_decrypt_shares_g1_batch", _ptr(sk_table), sk_table.shape[0], _ptr(idx), _ptr(u), n, B, _ptr(out), _ptr(st))
+        return out, st
+
     def sign(self, fr, msgs, off):
         dev = self._mode(fr, msgs, off)
         self._arg(fr, (None, FR_BYTES), "u8", "fr")
@@ -557,6 +570,24 @@ class Engine:
         ok = self._empty(dev, (B,), ref=u)
         self._call("tc_decrypt_share_batch", _ptr(fr), _ptr(u), _ptr(v), _ptr(off), _ptr(w), B, _ptr(out), _ptr(ok))
         return out, ok
+
+    def decrypt_shares(self, sk_table, idx, u, v, off, w):
+        """SecretKeyShare::decrypt_share (src/lib.rs:452-457) for the n selected holders idx[j] of each of B ciphertexts, out of a
+        table of N key shares -> (shares (B, n, 96), ok (B,), status (B, n)): Ciphertext::verify once per ciphertext; the shares
+        of a ciphertext that fails it are identities (the reference returns None)."""
+        dev = self._mode(sk_table, idx, u, v, off, w)
+        self._arg(sk_table, (None, FR_BYTES), "u8", "sk_table")
+        self._arg(idx, (None, None), "u64", "idx")
+        B, n = idx.shape
+        self._arg(u, (B, G1_BYTES), "u8", "u")
+        self._msgs(v, off, B)
+        self._arg(w, (B, G2_BYTES), "u8", "w")
+        out = self._empty(dev, (B, n, G1_BYTES), ref=u)
+        ok = self._empty(dev, (B,), ref=u)
+        st = self._empty(dev, (B, n), ref=u)
+        self._call("tc_decrypt_shares_batch", _ptr(sk_table), sk_table.shape[0], _ptr(idx), _ptr(u), _ptr(v), _ptr(off), _ptr(w), n, B,
+                   _ptr(out), _ptr(ok), _ptr(st))
+        return out, ok, st
 
     def secret_key_decrypt(self, fr, u, v, off, w):
         """SecretKey::decrypt (src/lib.rs:384-391) for B ciphertexts -> (plaintext bytes laid out like v, ok (B,)); the bytes
