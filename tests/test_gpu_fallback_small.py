@@ -9,13 +9,18 @@ and the bytes the call moved over PCIe (tc_ctx_transfer_bytes), with input check
     fault in job 4 (only the tail falls back), in job 0, then everywhere (a wrong key; a ciphertext names no key: one fault in
     every group instead);
   * records: M = 3 messages of 2, 0 and 1 records, K = 2 keys through key_idx, group = 2; the bad record in the last message,
-    in the first, and (checked mode) a key table entry outside G1 that only message 0 names;
+    in the first, and (checked mode) a key table entry outside G1 that only message 0 names; the same for the decryption shares
+    of M = 3 ciphertexts (verify_decryption_share_records_rlc and its pre-hashed form); and that last case once more per entry
+    with every operand in device memory -- the only path through the read-back of key_idx, which the host needs only when a key
+    table entry is bad;
   * DKG values: degree 1, n = 2, B = 3, one wrong value in job 2.
 
 The expected verdicts come from the matching per-item entry on the same (expanded) arrays, one item per case also from the
 oracle; the robust expectations from the model of tests/test_gpu_robust.py; n_fallback from the model of
 tests/test_gpu_pairing_product.py (_fallback; per message: group = 1).  The transfer bytes are what the entries moved before the
-staging helpers existed: TRANSFERS below was printed by this file, its assertion replaced by the print, on commit 5eb9372."""
+staging helpers existed: TRANSFERS below was printed by this file, its assertion replaced by the print, on commit 5eb9372.  The
+pairs of the decryption records and of the device-I/O cases (the last block of TRANSFERS) were printed the same way on commit
+735d348, the parent of the change that folded the bad-group rule and the front end of the two records entries into one copy."""
 import random
 
 import numpy as np
@@ -116,6 +121,25 @@ TRANSFERS = {
     'robust_dec_wire per_share unchecked bad': (1627, 61),
     'robust_dec_wire bisect unchecked clean': (1587, 61),
     'robust_dec_wire bisect unchecked bad': (1726, 71),
+    # recorded on commit 735d348 (the device_io cases: every operand in device memory)
+    'verify_g2_records_rlc checked key_outside_g1 device_io': (496, 73),
+    'verify_sig_records_rlc checked key_outside_g1 device_io': (496, 78),
+    'verify_decryption_share_records_rlc checked clean': (2106, 22),
+    'verify_decryption_share_records_rlc checked bad_last': (2114, 22),
+    'verify_decryption_share_records_rlc checked bad_first': (2122, 22),
+    'verify_decryption_share_records_rlc checked key_outside_g1': (2122, 22),
+    'verify_decryption_share_records_prehashed_rlc checked clean': (2328, 22),
+    'verify_decryption_share_records_prehashed_rlc checked bad_last': (2336, 22),
+    'verify_decryption_share_records_prehashed_rlc checked bad_first': (2344, 22),
+    'verify_decryption_share_records_prehashed_rlc checked key_outside_g1': (2344, 22),
+    'verify_decryption_share_records_rlc unchecked clean': (2106, 11),
+    'verify_decryption_share_records_rlc unchecked bad_last': (2114, 11),
+    'verify_decryption_share_records_rlc unchecked bad_first': (2122, 11),
+    'verify_decryption_share_records_prehashed_rlc unchecked clean': (2328, 11),
+    'verify_decryption_share_records_prehashed_rlc unchecked bad_last': (2336, 11),
+    'verify_decryption_share_records_prehashed_rlc unchecked bad_first': (2344, 11),
+    'verify_decryption_share_records_rlc checked key_outside_g1 device_io': (688, 83),
+    'verify_decryption_share_records_prehashed_rlc checked key_outside_g1 device_io': (688, 75),
 }
 
 
@@ -224,18 +248,32 @@ def test_ciphertext_verify_rlc(engine, small, checked):
 
 
 # ---- records: ragged messages, keys named through a table -----------------------------------------------------------------------
+REC_KEY_IDX = np.array([0, 1, 0], dtype=np.uint64)
+REC_OFF = np.array([0, 2, 2, 3], dtype=np.uint64)
+REC_JOB = [0, 0, 2]                                                        # the message / ciphertext of record r
+REC_CASES = [("clean", None, False, []), ("bad_last", 2, False, [2]), ("bad_first", 0, False, [0])]
+KEY_OUTSIDE_G1 = ("key_outside_g1", None, True, [1])                       # checked mode only
+
+
+def records_fallback(faults):
+    """n_fallback: every record of the groups that hold a fault"""
+    groups = {REC_JOB[r] // GROUP for r in faults}
+    return sum(1 for r in range(3) if REC_JOB[r] // GROUP in groups)
+
+
+def on_device(*arrays):
+    import torch
+    dev = torch.device("cuda:0")
+    return [torch.from_numpy(np.ascontiguousarray(a).view(np.int64) if a.dtype == np.uint64 else np.ascontiguousarray(a)).to(dev) for a in arrays]
+
+
 @pytest.mark.parametrize("entry", ["verify_g2_records_rlc", "verify_sig_records_rlc"])
 def test_records(engine, small, checked, entry):
     w = small.sig
-    key_idx = np.array([0, 1, 0], dtype=np.uint64)
-    rec_off = np.array([0, 2, 2, 3], dtype=np.uint64)
-    msg_of = [0, 0, 2]
+    key_idx, rec_off, msg_of = REC_KEY_IDX, REC_OFF, REC_JOB
     hashes = np.ascontiguousarray(w.hashes[:3])
     flat, off = pack_messages(w.msgs[:3])
-    cases = [("clean", None, False, []), ("bad_last", 2, False, [2]), ("bad_first", 0, False, [0])]
-    if checked:
-        cases.append(("key_outside_g1", None, True, [1]))
-    for case, bad, outside, faults in cases:
+    for case, bad, outside, faults in REC_CASES + ([KEY_OUTSIDE_G1] if checked else []):
         pks = np.ascontiguousarray(small.pk_sig[:2]).copy()
         sigs = np.stack([w.shares[0, 0], w.shares[0, 1], w.shares[2, 0]])
         if bad is not None:
@@ -253,8 +291,105 @@ def test_records(engine, small, checked, entry):
             run = lambda: engine.verify_sig_records_rlc(pks, key_idx, sigs, rec_off, flat, off, group=GROUP, seed=SEED)
         ok, nfb = measured(engine, "%s %s %s" % (entry, tag(checked), case), run)
         assert ok.tolist() == want.tolist()
-        groups = {msg_of[r] // GROUP for r in faults}
-        assert nfb == sum(1 for r in range(3) if msg_of[r] // GROUP in groups)
+        assert nfb == records_fallback(faults)
+
+
+@pytest.mark.parametrize("entry", ["verify_g2_records_rlc", "verify_sig_records_rlc"])
+def test_records_device_io(engine, small, entry):
+    """the key table entry outside G1 with every operand in device memory: key_idx comes back to the host for the bad-group rule"""
+    w = small.sig
+    hashes = np.ascontiguousarray(w.hashes[:3])
+    flat, off = pack_messages(w.msgs[:3])
+    pks = np.ascontiguousarray(small.pk_sig[:2]).copy()
+    pks[1] = u8(o.g1_uncompressed(non_member_g1(random.Random(11))))
+    sigs = np.stack([w.shares[0, 0], w.shares[0, 1], w.shares[2, 0]])
+    if entry == "verify_g2_records_rlc":
+        call, rest = engine.verify_g2_records_rlc, (hashes,)
+    else:
+        call, rest = engine.verify_sig_records_rlc, (flat, off)
+    want, want_nfb = call(pks, REC_KEY_IDX, sigs, REC_OFF, *rest, group=GROUP, seed=SEED)
+    assert np.flatnonzero(np.asarray(want) == 0).tolist() == [1] and want_nfb == 2
+    dev = on_device(pks, REC_KEY_IDX, sigs, REC_OFF, *rest)
+    try:
+        ok, nfb = measured(engine, "%s checked key_outside_g1 device_io" % entry, lambda: call(*dev, group=GROUP, seed=SEED))
+        engine.sync()
+        assert ok.cpu().numpy().tolist() == np.asarray(want).tolist() and nfb == want_nfb
+    finally:
+        engine.sync()
+
+
+def dshare_records_inputs(small, bad, outside):
+    """(pks, shares) of the three records: key 0 and key 1 for ciphertext 0, key 0 for ciphertext 2"""
+    e = small.enc
+    pks = np.ascontiguousarray(small.pk_enc[:2]).copy()
+    shares = np.stack([e.shares[0, 0], e.shares[0, 1], e.shares[2, 0]])
+    if bad is not None:
+        shares[bad] = e.shares[2 - REC_JOB[bad], 0]                        # key 0's share of the OTHER ciphertext
+    if outside:
+        pks[1] = u8(o.g1_uncompressed(non_member_g1(random.Random(11))))
+    return pks, shares
+
+
+class DshareRecords:
+    """the three ciphertexts of the decryption records cases, and their expansion to one ciphertext per record"""
+    def __init__(self, engine, small):
+        e = small.enc
+        self.u, self.w = np.ascontiguousarray(e.u[:3]), np.ascontiguousarray(e.w[:3])
+        self.v, self.off = np.ascontiguousarray(e.v[:int(e.off[3])]), np.ascontiguousarray(e.off[:4])
+        self.vs = [bytes(e.v[int(e.off[j]):int(e.off[j + 1])]) for j in range(3)]
+        hashes, st = engine.hash_g1_g2(self.u, self.v, self.off)
+        assert not np.asarray(st).any()
+        self.hashes = np.ascontiguousarray(hashes)
+        self.u_x, self.w_x = np.ascontiguousarray(self.u[REC_JOB]), np.ascontiguousarray(self.w[REC_JOB])
+        self.v_x, self.off_x = pack_messages([self.vs[j] for j in REC_JOB])
+
+    def entry(self, engine, name):
+        """(the entry, its operands behind rec_off)"""
+        if name == "verify_decryption_share_records_rlc":
+            return engine.verify_decryption_share_records_rlc, (self.u, self.v, self.off, self.w)
+        return engine.verify_decryption_share_records_prehashed_rlc, (self.hashes, self.w)
+
+
+DSHARE_ENTRIES = ["verify_decryption_share_records_rlc", "verify_decryption_share_records_prehashed_rlc"]
+
+
+@pytest.fixture(scope="module")
+def dshare(engine, small):
+    return DshareRecords(engine, small)
+
+
+@pytest.mark.parametrize("entry", DSHARE_ENTRIES)
+def test_dshare_records(engine, small, dshare, checked, entry):
+    d = dshare
+    call, rest = d.entry(engine, entry)
+    for case, bad, outside, faults in REC_CASES + ([KEY_OUTSIDE_G1] if checked else []):
+        pks, shares = dshare_records_inputs(small, bad, outside)
+        pk_x = np.ascontiguousarray(pks[REC_KEY_IDX.astype(np.int64)])
+        want = engine.verify_decryption_share(pk_x, shares, d.u_x, d.v_x, d.off_x, d.w_x)
+        assert np.flatnonzero(want == 0).tolist() == faults
+        if not outside:                                                    # (the oracle's check tests no membership)
+            assert bool(c.verify_decryption_share(bytes(pk_x[2]), bytes(shares[2]), bytes(d.u[2]), d.vs[2], bytes(d.w[2]))) == bool(want[2])
+        ok, nfb = measured(engine, "%s %s %s" % (entry, tag(checked), case),
+                           lambda: call(pks, REC_KEY_IDX, shares, REC_OFF, *rest, group=GROUP, seed=SEED))
+        assert ok.tolist() == want.tolist()
+        assert nfb == records_fallback(faults) == {"clean": 0, "bad_last": 1, "bad_first": 2, "key_outside_g1": 2}[case]
+
+
+@pytest.mark.parametrize("entry", DSHARE_ENTRIES)
+def test_dshare_records_device_io(engine, small, dshare, entry):
+    """the key table entry outside G1 with every operand in device memory (test_records_device_io for the decryption shares)"""
+    d = dshare
+    call, rest = d.entry(engine, entry)
+    pks, shares = dshare_records_inputs(small, None, True)
+    want, want_nfb = call(pks, REC_KEY_IDX, shares, REC_OFF, *rest, group=GROUP, seed=SEED)
+    assert np.flatnonzero(np.asarray(want) == 0).tolist() == [1] and want_nfb == 2
+    dev = on_device(pks, REC_KEY_IDX, shares, REC_OFF, *rest)
+    try:
+        ok, nfb = measured(engine, "%s checked key_outside_g1 device_io" % entry, lambda: call(*dev, group=GROUP, seed=SEED))
+        engine.sync()
+        assert ok.cpu().numpy().tolist() == np.asarray(want).tolist() and nfb == want_nfb
+    finally:
+        engine.sync()
 
 
 # ---- per ciphertext: the decryption shares of B ciphertexts under N key shares ------------------------------------------------

@@ -203,7 +203,7 @@ def test_cancelling_pair_is_rejected(world):
 # ---- 4 ---------------------------------------------------------------------------------------------------------------------------
 # (a point outside G1 is only told apart in checked-input mode: no case with the checks off)
 MALFORMED = [(kind, checked) for kind in ("share_undecodable", "key_undecodable", "index_K", "index_max", "u_undecodable", "w_undecodable",
-                                          "share_non_member", "u_non_member") for checked in (True, False)
+                                          "share_non_member", "key_non_member", "u_non_member") for checked in (True, False)
              if checked or not kind.endswith("non_member")]
 
 
@@ -217,8 +217,11 @@ def test_one_malformed_operand(world, kind, checked):
     elif kind == "share_non_member":
         bad = [case.rec(2, 0)]
         case.shares[bad[0]] = non_member_g1(random.Random(5))
-    elif kind == "key_undecodable":
-        case.pks[3, 50] ^= 1                                     # every record that names key 3, and only those
+    elif kind in ("key_undecodable", "key_non_member"):          # every record that names key 3, and only those
+        if kind == "key_undecodable":
+            case.pks[3, 50] ^= 1
+        else:
+            case.pks[3] = non_member_g1(random.Random(7))
         bad = [r for r in range(case.R) if int(case.key_idx[r]) == 3]
         assert len(bad) >= 2 and len({case.ct_of[r] for r in bad}) >= 2
     elif kind in ("index_K", "index_max"):

@@ -1510,17 +1510,13 @@ static void rlc_group_checks(Call& k, const RlcWs& w, const uint8_t* d_pk, const
   k.take_verdicts({{v_key, &h_vkey}, {v_sig, &h_vsig}, {v_hash, &h_vhash}});
   k.check(hipStreamSynchronize(ctx->stream), "stream sync");
   if (k.failed) return;
-  const bool key_bad = !h_vkey.empty() && h_vkey[0] == 0;
-  std::vector<uint8_t> bad(NG);
-  for (size_t g = 0; g < NG; g++) {
-    bool b = key_bad || !h_okg[g] || h_st[g] != TC_JOB_OK || h_st[NG + g] != TC_JOB_OK;
-    const size_t lo = g * group, hi = (lo + group < B) ? lo + group : B;
-    for (const std::vector<uint8_t>* hv : {&h_vsig, &h_vhash})
-      for (size_t j = lo; j < hi && !b && !hv->empty(); j++) b = (*hv)[j] == 0;
-    bad[g] = b;
-  }
-  std::vector<uint32_t> failed;
-  tc::failed_jobs_of_groups(bad.data(), w.cut, B, failed);
+  tc::BadGroups bad(w.cut, B);
+  bad.per_group(h_okg.data(), true);
+  bad.per_group(h_st.data(), false);       // the sums of the signatures
+  bad.per_group(h_st.data() + NG, false);  // and of the hash points
+  if (!h_vkey.empty() && h_vkey[0] == 0) bad.all();
+  bad.jobs({tc::bytes_or_null(h_vsig), tc::bytes_or_null(h_vhash)}, true);
+  const std::vector<uint32_t> failed = bad.failed_jobs();
   if (failed.empty()) return;
   // per-job pairing checks for every job of the failed groups, on compacted operands
   const size_t R = failed.size();
@@ -1602,13 +1598,82 @@ int tc_verify_sig_rlc_batch(tc_ctx* ctx, const uint8_t* pk, const uint8_t* sig, 
   return on_exception((tc_ctx*)ctx);
 }
 
+// What the two ragged entries (verify_records, verify_dshare_records) share around their sums and their fallback: rec_off on the
+// host, the inputs of the plan, the key of record r, the identity pairs that fill up the last group, and key_idx on the host.
+struct Records {
+  Call& k;
+  const uint8_t* pks;
+  const uint64_t* key_idx;  // the caller's, in the memory of the other operands; null: record r under pks[r]
+  size_t K, M, R = 0, simd_lanes = 0;
+  tc::GroupCut cut;              // groups of jobs (messages / ciphertexts)
+  uint64_t longest = 0;          // the most records of one job
+  const uint64_t *hr = nullptr, *d_kidx = nullptr;  // rec_off on the host; key_idx as an operand
+  std::vector<uint64_t> h_rec, h_grp, h_kidx;  // h_grp: NG + 1 values, the first record of every group
+  std::vector<uint8_t> h_pad;
+  const uint8_t *d_pk = nullptr, *d_keys = nullptr;  // the key table; the key of record r
+  Records(Call& call, const uint8_t* pks_, size_t K_, const uint64_t* key_idx_, size_t M_, size_t group)
+      : k(call), pks(pks_), key_idx(key_idx_), K(K_), M(M_), cut(tc::group_cut(M_, group)), h_grp(cut.NG + 1) {}
+  bool require(bool cond, const char* what) {
+    if (!cond) k.fail(std::string("invalid argument: ") + what);
+    k.arg_error = k.arg_error || !cond;
+    return cond;
+  }
+  // rec_off comes to the host in both I/O modes (device I/O: 8 (M + 1) bytes and one sync: the chunk ranges of the segments are host
+  // arithmetic, tc_records.h) and is validated.  records / ok: the caller's per-record operand and output.  false: the call is
+  // over -- an error, or no record at all -- and the entry returns k.finish()
+  bool offsets(const uint64_t* rec_off, const void* records, const void* ok) {
+    if (k.c->device_io) {
+      h_rec.resize(M + 1);
+      if (!k.readback(h_rec.data(), rec_off, (M + 1) * 8, "offset readback") || !k.check(hipStreamSynchronize(k.c->stream), "stream sync")) return false;
+    }
+    hr = k.c->device_io ? h_rec.data() : rec_off;
+    bool good = hr[0] == 0;
+    for (size_t m = 0; m < M && good; m++) good = hr[m + 1] >= hr[m];
+    if (!require(good, "offsets must start at 0 and be non-decreasing") || !require(hr[M] < (1ull << 32), "R < 2^32")) return false;
+    R = (size_t)hr[M];
+    if (R == 0 || !require(records && ok && (K == 0 || pks), "records && ok && (K == 0 || pks)") || !require(key_idx || K >= R, "key_idx || K >= R"))
+      return false;
+    simd_lanes = (size_t)(k.c->cus > 0 ? k.c->cus : 256) * 4 * tc::kBlock;  // one wave per SIMD
+    for (size_t m = 0; m < M; m++) longest = hr[m + 1] - hr[m] > longest ? hr[m + 1] - hr[m] : longest;
+    tc::rec_group_ranges(hr, M, cut.group, h_grp.data());
+    return true;
+  }
+  bool tables_fit(size_t table_bytes) {  // false: the sums need more table memory than a call may spend; the entry returns k.finish()
+    const bool fit = table_bytes <= msm_table_budget(k);
+    if (!fit) k.fail("out of memory: the tables of " + std::to_string(R) + " records need " + std::to_string(table_bytes >> 20) + " MB; split the call");
+    return fit;
+  }
+  void stage_keys() {  // the key table and the indices as operands; d_keys: the table itself, or the room that gather_keys() fills
+    d_pk = k.in(pks, K * 96);
+    d_kidx = k.in(key_idx, key_idx ? R : 0);
+    d_keys = key_idx ? k.temp<uint8_t>(R * 96) : d_pk;
+  }
+  void gather_keys() { if (key_idx) tc::launch_rec_gather_keys(k.c->stream, d_pk, K, d_kidx, R, const_cast<uint8_t*>(d_keys)); }
+  // the pairs that fill up the last group, so that ONE launch checks every group: `count` identities of G2 at g2_tail, of G1 at g1_tail
+  void pad_identities(uint8_t* g2_tail, uint8_t* g1_tail, size_t count) {
+    if (count == 0) return;
+    h_pad.assign(count * (192 + 96), 0);
+    for (size_t i = 0; i < count; i++) h_pad[i * 192] = h_pad[count * 192 + i * 96] = 0x40;  // the identity of G2 / of G1
+    k.upload(g2_tail, h_pad.data(), count * 192, "pad copy");
+    k.upload(g1_tail, h_pad.data() + count * 192, count * 96, "pad copy");
+  }
+  // key_idx for BadGroups::named_keys: a bad key fails the groups of the records that NAME it, so the indices are needed on the
+  // host only then, and only then does device I/O read them back (8 R bytes and one sync)
+  const uint64_t* host_key_idx(const std::vector<uint8_t>& h_vkey) {
+    if (!key_idx || !k.c->device_io || !tc::has_zero(h_vkey.data(), h_vkey.size())) return key_idx;
+    h_kidx.resize(R);
+    k.readback(h_kidx.data(), key_idx, R * 8, "index readback");
+    k.check(hipStreamSynchronize(k.c->stream), "stream sync");
+    return h_kidx.data();
+  }
+};
+
 // Batch verification of ragged input: M messages, message m owning the records rec_off[m] .. rec_off[m + 1],
 // record r = (sigs[r], pks[key_idx[r]]).  Groups of `group` consecutive messages pass with ONE product check
 //     prod_{m in g} e(P_m, H_m) == e(g1, S_g),  P_m = sum_{r in m} rho_r pk_r (G1),  S_g = sum_{r in g} rho_r sig_r (G2)
 // -- the two ragged sums of k_msm.hip (k_rec_*) over the 63-bit scalars of k_rlc_scalars, then launch_pairing_product_check with
 // one pair per message; a group that fails, holds an operand that does not decode or (checked-input mode) is no member, is
-// re-checked record by record on compacted operands like the failed messages of tc_verify_shares_rlc_batch.  rec_off is brought
-// to the host in both I/O modes (8 (M + 1) bytes): the chunk ranges of the segments are host arithmetic (tc_records.h).
+// re-checked record by record on compacted operands like the failed messages of tc_verify_shares_rlc_batch.
 static int verify_records(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint64_t* key_idx, const uint8_t* sigs, const uint64_t* rec_off,
                           const uint8_t* hashes, const uint8_t* msgs, const uint64_t* off, size_t M, size_t group, const uint8_t* seed32,
                           uint8_t* ok, uint64_t* n_fallback) {
@@ -1616,29 +1681,11 @@ static int verify_records(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint6
   if (n_fallback) *n_fallback = 0;
   if (M == 0) return TC_OK;
   TC_REQUIRE(ctx && rec_off && (hashes || off) && seed32);
-  const tc::GroupCut cut = tc::group_cut(M, group);  // groups of MESSAGES
-  group = cut.group;
   Call k(ctx);
-  std::vector<uint64_t> h_rec;
-  if (ctx->device_io) {
-    h_rec.resize(M + 1);
-    if (!k.readback(h_rec.data(), rec_off, (M + 1) * 8, "offset readback") || !k.check(hipStreamSynchronize(ctx->stream), "stream sync"))
-      return k.finish();
-  }
-  const uint64_t* hr = ctx->device_io ? h_rec.data() : rec_off;
-  bool good = hr[0] == 0;
-  for (size_t m = 0; m < M && good; m++) good = hr[m + 1] >= hr[m];
-  if (!good) {
-    k.fail("invalid argument: offsets must start at 0 and be non-decreasing");
-    k.arg_error = true;
-    return k.finish();
-  }
-  const uint64_t R64 = hr[M];
-  TC_REQUIRE(R64 < (1ull << 32));
-  const size_t R = (size_t)R64;
-  if (R == 0) return k.finish();
-  TC_REQUIRE(sigs && ok && (K == 0 || pks));
-  TC_REQUIRE(key_idx || K >= R);
+  Records f(k, pks, K, key_idx, M, group);  // groups of MESSAGES
+  if (!f.offsets(rec_off, sigs, ok)) return k.finish();
+  group = f.cut.group;
+  const size_t R = f.R, NG = f.cut.NG, simd_lanes = f.simd_lanes;  // NG = tc::rec_groups(M, group)
   uint64_t total = 0;
   if (!hashes) {
     if (!total_bytes(k, off, M, &total)) return k.finish();
@@ -1648,52 +1695,40 @@ static int verify_records(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint6
   // the GPU to a few waves), then, when a group has several, the groups as segments over the sums of their pieces.  One
   // descriptor array: [rec_off | chunks of the messages | first records of the pieces | their chunks | first pieces of the
   // groups | their chunks]
-  const size_t NG = cut.NG;  // = tc::rec_groups(M, group)
-  const size_t simd_lanes = (size_t)(ctx->cus > 0 ? ctx->cus : 256) * 4 * tc::kBlock;  // one wave per SIMD
   const size_t pairs_most = (size_t)tc::kBlock / tc::kG2Lanes;
-  std::vector<uint64_t> h_grp(NG + 1);
-  tc::rec_group_ranges(hr, M, group, h_grp.data());
   const uint64_t piece = tc::rec_piece_size(R, simd_lanes / tc::kG2Lanes, pairs_most);
-  const size_t NP = (size_t)tc::rec_piece_total(h_grp.data(), NG, piece);
+  const size_t NP = (size_t)tc::rec_piece_total(f.h_grp.data(), NG, piece);
   std::vector<uint64_t> desc(2 * (M + 1) + 2 * (NP + 1) + 2 * (NG + 1));
   uint64_t *h_seg1 = desc.data(), *h_fc1 = h_seg1 + M + 1, *h_seg2 = h_fc1 + M + 1, *h_fc2 = h_seg2 + NP + 1, *h_seg3 = h_fc2 + NP + 1,
            *h_fc3 = h_seg3 + NG + 1;
-  memcpy(h_seg1, hr, (M + 1) * 8);
+  memcpy(h_seg1, f.hr, (M + 1) * 8);
   const uint64_t C1 = tc::rec_chunk_ranges(h_seg1, M, h_fc1);
-  tc::rec_piece_ranges(h_grp.data(), NG, piece, h_seg2, h_seg3);
+  tc::rec_piece_ranges(f.h_grp.data(), NG, piece, h_seg2, h_seg3);
   const uint64_t C2 = tc::rec_chunk_ranges(h_seg2, NP, h_fc2);
   const uint64_t C3 = tc::rec_chunk_ranges(h_seg3, NG, h_fc3);
-  uint64_t longest1 = 0, longest2 = 0, longest3 = 0;
-  for (size_t m = 0; m < M; m++) longest1 = hr[m + 1] - hr[m] > longest1 ? hr[m + 1] - hr[m] : longest1;
+  uint64_t longest2 = 0, longest3 = 0;
   for (size_t q = 0; q < NP; q++) longest2 = h_seg2[q + 1] - h_seg2[q] > longest2 ? h_seg2[q + 1] - h_seg2[q] : longest2;
   for (size_t g = 0; g < NG; g++) longest3 = h_seg3[g + 1] - h_seg3[g] > longest3 ? h_seg3[g + 1] - h_seg3[g] : longest3;
   bool direct = true;  // every group is exactly one piece: the sums of the pieces ARE the sums of the groups
   for (size_t g = 0; g < NG; g++) direct = direct && h_seg3[g + 1] - h_seg3[g] == 1;
   const size_t forced = ctx->tuning.records_parts, forced2 = forced > pairs_most ? pairs_most : forced;
-  const size_t parts1 = tc::rec_parts(M, longest1, simd_lanes, tc::kBlock, forced);
+  const size_t parts1 = tc::rec_parts(M, f.longest, simd_lanes, tc::kBlock, forced);
   const size_t parts2 = tc::rec_parts(NP, longest2, simd_lanes / tc::kG2Lanes, pairs_most, forced2);
   const size_t parts3 = tc::rec_parts(NG, longest3, simd_lanes / tc::kG2Lanes, pairs_most, forced2);
-  const size_t table_bytes = tc::rec_table_bytes(false, C1) + tc::rec_table_bytes(true, C2) + tc::rec_table_bytes(true, C3);
-  if (table_bytes > msm_table_budget(k)) {
-    k.fail("out of memory: the tables of " + std::to_string(R) + " records need " + std::to_string(table_bytes >> 20) + " MB; split the call");
-    return k.finish();
-  }
-  const uint8_t* d_pk = k.in(pks, K * 96);
-  const uint64_t* d_kidx = k.in(key_idx, key_idx ? R : 0);
+  if (!f.tables_fit(tc::rec_table_bytes(false, C1) + tc::rec_table_bytes(true, C2) + tc::rec_table_bytes(true, C3))) return k.finish();
+  f.stage_keys();
   const uint8_t* d_sig = k.in(sigs, R * 192);
   const uint8_t* d_hash_in = hashes ? k.in(hashes, M * 192) : nullptr;
   const uint8_t* d_msgs = hashes ? nullptr : k.in(msgs, (size_t)total);
   const uint64_t* d_off = hashes ? nullptr : k.in(off, M + 1);
   // the pairs of the product checks: `group` per group, the last group filled up with identity pairs (the factor 1), so that
   // ONE launch checks every group (a launch of one job takes as long as a launch of a thousand)
-  const size_t MP = NG * group, pad = MP - M;
+  const size_t MP = NG * group;
   uint8_t* d_hash = k.temp<uint8_t>(MP * 192);
   const uint8_t* d_g1 = hashes ? ctx->g1_gen : ctx->g1_gen_unfix;
   uint64_t* d_desc = k.temp<uint64_t>(desc.size());
   uint8_t* d_seed = k.secret_seed(seed32);
   uint8_t* d_r = k.secret_temp<uint8_t>(R * 32);
-  uint8_t* d_keys_own = key_idx ? k.temp<uint8_t>(R * 96) : nullptr;
-  const uint8_t* d_keys = key_idx ? d_keys_own : d_pk;  // the key of record r
   uint8_t* d_P = k.temp<uint8_t>(MP * 96);
   uint8_t* d_S = k.temp<uint8_t>(NG * 192);
   uint8_t* d_Sp = direct ? d_S : k.temp<uint8_t>(NP * 192);  // the sums of the pieces
@@ -1711,28 +1746,23 @@ static int verify_records(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint6
   int32_t* ws_groups = k.pairing_product_ws(group, NG, true);
   k.begin_timing();
   // checked-input mode: every key TABLE entry once (K tests, not R), every signature, every hash operand
-  const uint8_t* v_key = k.check_points(false, d_pk, 96, K, K, 1, (size_t)-1);
+  const uint8_t* v_key = k.check_points(false, f.d_pk, 96, K, K, 1, (size_t)-1);
   const uint8_t* v_sig = k.check_points(true, d_sig, 192, 1, 1, R, 1);
   const uint8_t* v_hash = hashes ? k.check_points(true, d_hash_in, 192, 1, 1, M, 1) : nullptr;
-  std::vector<uint8_t> h_okg(NG), h_st(M + NG + NP), h_vkey, h_vsig, h_vhash, h_pad(pad * (192 + 96), 0);
-  std::vector<uint64_t> h_kidx;
+  std::vector<uint8_t> h_okg(NG), h_st(M + NG + NP), h_vkey, h_vsig, h_vhash;
   if (!k.failed) {
     k.upload(d_desc, desc.data(), desc.size() * 8, "descriptor copy");
     k.check(hipMemsetAsync(d_st, 0, M + NG + NP, ctx->stream), "memset");
     if (!hashes) tc::launch_hash_g2(ctx->tuning, ctx->stream, d_msgs, d_off, M, d_hash, /*fix=*/false);
     else k.check(hipMemcpyAsync(d_hash, d_hash_in, M * 192, hipMemcpyDeviceToDevice, ctx->stream), "hash copy");
-    if (pad) {
-      for (size_t i = 0; i < pad; i++) h_pad[i * 192] = h_pad[pad * 192 + i * 96] = 0x40;  // the identity of G2 / of G1
-      k.upload(d_hash + M * 192, h_pad.data(), pad * 192, "pad copy");
-      k.upload(d_P + M * 96, h_pad.data() + pad * 192, pad * 96, "pad copy");
-    }
+    f.pad_identities(d_hash + M * 192, d_P + M * 96, MP - M);
     tc::launch_rlc_scalars(ctx->stream, d_seed, R, d_r);
     const uint32_t* rr = reinterpret_cast<const uint32_t*>(d_r);
-    if (key_idx) tc::launch_rec_gather_keys(ctx->stream, d_pk, K, d_kidx, R, d_keys_own);
+    f.gather_keys();
     const uint64_t *d_seg1 = d_desc, *d_fc1 = d_seg1 + M + 1, *d_seg2 = d_fc1 + M + 1, *d_fc2 = d_seg2 + NP + 1, *d_seg3 = d_fc2 + NP + 1,
                    *d_fc3 = d_seg3 + NG + 1;
     // (the short-scalar modes of the two-stage kernels: 40 two-half steps in G1, 16 columns in G2, as tc_ciphertext_verify_rlc_batch)
-    tc::launch_rec_sum_g1(ctx->stream, d_keys, rr, d_seg1, d_fc1, M, C1, parts1, d_tbl1, d_codes1, d_P, d_st, /*nbits=*/80);
+    tc::launch_rec_sum_g1(ctx->stream, f.d_keys, rr, d_seg1, d_fc1, M, C1, parts1, d_tbl1, d_codes1, d_P, d_st, /*nbits=*/80);
     tc::launch_rec_sum_g2(ctx->stream, d_sig, rr, d_seg2, d_fc2, NP, C2, parts2, d_tbl2, d_codes2, d_Sp, d_st + M + NG, /*nbits=*/16);
     // S_g = the sum of the group's pieces: the same kernels over the piece sums with the scalar 1 (short and odd).  A group
     // without records has no piece: its sum is the identity.
@@ -1750,49 +1780,25 @@ static int verify_records(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint6
     // (the membership tests ran beside the sums and the group checks)
     k.take_verdicts({{v_key, &h_vkey}, {v_sig, &h_vsig}, {v_hash, &h_vhash}});
     k.check(hipStreamSynchronize(ctx->stream), "stream sync");
-    // a bad key fails the groups of the records that NAME it: the indices are needed on the host only then
-    bool key_bad = false;
-    for (size_t i = 0; i < h_vkey.size() && !key_bad; i++) key_bad = h_vkey[i] == 0;
-    const uint64_t* hk = key_idx;
-    if (key_bad && key_idx && ctx->device_io && !k.failed) {
-      h_kidx.resize(R);
-      k.readback(h_kidx.data(), key_idx, R * 8, "index readback");
-      k.check(hipStreamSynchronize(ctx->stream), "stream sync");
-      hk = h_kidx.data();
-    }
-    std::vector<uint32_t> m_sig, m_hash;
+    tc::SlotMaps maps;  // every record of the messages of the bad groups
     if (!k.failed) {
-      std::vector<uint8_t> bad_group(NG);
-      for (size_t g = 0; g < NG; g++) {
-        const size_t mlo = g * group, mhi = (mlo + group < M) ? mlo + group : M;
-        const uint64_t rlo = hr[mlo], rhi = hr[mhi];
-        bool bad = !h_okg[g] || h_st[M + g] != TC_JOB_OK;
-        for (uint64_t q = h_seg3[g]; q < h_seg3[g + 1] && !bad; q++) bad = h_st[M + NG + q] != TC_JOB_OK;
-        for (size_t m = mlo; m < mhi && !bad; m++) bad = h_st[m] != TC_JOB_OK || (!h_vhash.empty() && h_vhash[m] == 0);
-        for (uint64_t r = rlo; r < rhi && !bad && !h_vsig.empty(); r++) bad = h_vsig[r] == 0;
-        if (key_bad)
-          for (uint64_t r = rlo; r < rhi && !bad; r++) {
-            const uint64_t i = hk ? hk[r] : r;
-            bad = i < K && h_vkey[i] == 0;  // (an index >= K has failed its message in stage T already)
-          }
-        bad_group[g] = bad;
-      }
-      // every record of the messages of the bad groups
-      std::vector<uint32_t> bad_msgs;
-      tc::failed_jobs_of_groups(bad_group.data(), cut, M, bad_msgs);
-      for (uint32_t m : bad_msgs)
-        for (uint64_t r = hr[m]; r < hr[m + 1]; r++) {
-          m_sig.push_back((uint32_t)r);
-          m_hash.push_back(m);
-        }
+      tc::BadGroups bad(f.cut, M);
+      bad.per_group(h_okg.data(), true);
+      bad.per_group(h_st.data() + M, false);                  // the sums of the groups,
+      bad.spans(h_seg3, h_st.data() + M + NG, false);         // of their pieces
+      bad.jobs({h_st.data()}, false);                         // and of their messages
+      bad.jobs({tc::bytes_or_null(h_vhash)}, true);
+      bad.spans(f.h_grp.data(), tc::bytes_or_null(h_vsig), true);
+      bad.named_keys(f.h_grp.data(), f.host_key_idx(h_vkey), K, tc::bytes_or_null(h_vkey));
+      maps = tc::records_of_jobs(f.hr, bad.failed_jobs());
     }
-    if (!k.failed && !m_sig.empty()) {
+    if (!k.failed && !maps.record.empty()) {
       // the per-record check of tc_verify_g2_batch for every record of the failed groups, on compacted operands
-      const size_t F = m_sig.size();
-      Compacted c(k, F, {&m_sig, &m_hash});
+      const size_t F = maps.record.size();
+      Compacted c(k, F, {&maps.record, &maps.job});
       const uint8_t* c_sig = c.gather(d_sig, 192, 0);
       const uint8_t* c_hash = c.gather(d_hash, 192, 1);
-      const uint8_t* c_pk = c.gather(d_keys, 96, 0);
+      const uint8_t* c_pk = c.gather(f.d_keys, 96, 0);
       const tc::PairingWs pws = k.pairing_ws(F);
       if (!k.failed) tc::launch_pairing_check(ctx->stream, c_pk, 96, c_hash, 192, d_g1, 0, c_sig, 192, F, c.c_ok, pws);  // src/lib.rs:109
       if (ctx->input_checks) {  // members only, as the per-record path would require
@@ -1934,16 +1940,12 @@ int tc_ciphertext_verify_rlc_batch(tc_ctx* ctx, const uint8_t* u, const uint8_t*
     k.check(hipStreamSynchronize(ctx->stream), "stream sync");
     std::vector<uint32_t> failed;
     if (!k.failed) {
-      std::vector<uint8_t> bad_group(NG);
-      for (size_t g = 0; g < NG; g++) {
-        bool bad = !h_okg[g] || h_st[2 * B + g] != TC_JOB_OK;
-        const size_t lo = g * group, hi = (lo + group < B) ? lo + group : B;
-        for (size_t j = lo; j < hi && !bad; j++) bad = h_st[j] != TC_JOB_OK || h_st[B + j] != TC_JOB_OK;
-        for (const std::vector<uint8_t>* hv : {&h_vu, &h_vw})
-          for (size_t j = lo; j < hi && !bad && !hv->empty(); j++) bad = (*hv)[j] == 0;
-        bad_group[g] = bad;
-      }
-      tc::failed_jobs_of_groups(bad_group.data(), cut, B, failed);
+      tc::BadGroups bad(cut, B);
+      bad.per_group(h_okg.data(), true);
+      bad.per_group(h_st.data() + 2 * B, false);                 // the sums of the groups
+      bad.jobs({h_st.data(), h_st.data() + B}, false);           // the hashes and r_j u_j
+      bad.jobs({tc::bytes_or_null(h_vu), tc::bytes_or_null(h_vw)}, true);
+      failed = bad.failed_jobs();
     }
     if (!k.failed && !failed.empty()) {
       // the per-ciphertext check of tc_ciphertext_verify_batch for every ciphertext of the failed groups, on compacted operands
@@ -2209,7 +2211,7 @@ int tc_verify_decryption_shares_rlc_batch(tc_ctx* ctx, const uint8_t* pk_shares,
 // H_c is the FIXED hash (fix = true), so the hashing and the pre-hashed entry share every step behind it and no cofactor scaling
 // stands between the sums and the check.  A group that fails, holds an operand that does not decode or (checked-input mode) is
 // no member, is re-checked record by record on compacted operands like the failed ciphertexts of
-// tc_verify_decryption_shares_rlc_batch.  rec_off is brought to the host in both I/O modes, as in verify_records.
+// tc_verify_decryption_shares_rlc_batch.
 static int verify_dshare_records(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint64_t* key_idx, const uint8_t* shares, const uint64_t* rec_off,
                                  const uint8_t* hashes, const uint8_t* u, const uint8_t* v, const uint64_t* off, const uint8_t* w, size_t M,
                                  size_t group, const uint8_t* seed32, uint8_t* ok, uint64_t* n_fallback) {
@@ -2217,51 +2219,25 @@ static int verify_dshare_records(tc_ctx* ctx, const uint8_t* pks, size_t K, cons
   if (n_fallback) *n_fallback = 0;
   if (M == 0) return TC_OK;
   TC_REQUIRE(ctx && rec_off && (hashes || (u && off)) && w && seed32);
-  const tc::GroupCut cut = tc::group_cut(M, group);  // groups of CIPHERTEXTS
-  group = cut.group;
   Call k(ctx);
-  std::vector<uint64_t> h_rec;
-  if (ctx->device_io) {
-    h_rec.resize(M + 1);
-    if (!k.readback(h_rec.data(), rec_off, (M + 1) * 8, "offset readback") || !k.check(hipStreamSynchronize(ctx->stream), "stream sync"))
-      return k.finish();
-  }
-  const uint64_t* hr = ctx->device_io ? h_rec.data() : rec_off;
-  bool good = hr[0] == 0;
-  for (size_t m = 0; m < M && good; m++) good = hr[m + 1] >= hr[m];
-  if (!good) {
-    k.fail("invalid argument: offsets must start at 0 and be non-decreasing");
-    k.arg_error = true;
-    return k.finish();
-  }
-  const uint64_t R64 = hr[M];
-  TC_REQUIRE(R64 < (1ull << 32));
-  const size_t R = (size_t)R64;
-  if (R == 0) return k.finish();
-  TC_REQUIRE(shares && ok && (K == 0 || pks));
-  TC_REQUIRE(key_idx || K >= R);
+  Records f(k, pks, K, key_idx, M, group);  // groups of CIPHERTEXTS
+  if (!f.offsets(rec_off, shares, ok)) return k.finish();
+  group = f.cut.group;
+  const size_t R = f.R, NG = f.cut.NG;
   uint64_t total = 0;
   if (!hashes) {
     if (!total_bytes(k, off, M, &total)) return k.finish();
     TC_REQUIRE(total == 0 || v);
   }
   // the segments of both sums: the ciphertexts.  One descriptor array: [rec_off | chunks of the ciphertexts]
-  const size_t NG = cut.NG;
-  const size_t simd_lanes = (size_t)(ctx->cus > 0 ? ctx->cus : 256) * 4 * tc::kBlock;  // one wave per SIMD
   std::vector<uint64_t> desc(2 * (M + 1));
   uint64_t *h_seg = desc.data(), *h_fc = h_seg + M + 1;
-  memcpy(h_seg, hr, (M + 1) * 8);
+  memcpy(h_seg, f.hr, (M + 1) * 8);
   const uint64_t C = tc::rec_chunk_ranges(h_seg, M, h_fc);
-  uint64_t longest = 0;
-  for (size_t m = 0; m < M; m++) longest = hr[m + 1] - hr[m] > longest ? hr[m + 1] - hr[m] : longest;
-  const size_t parts = tc::rec_parts(2 * M, longest, simd_lanes, tc::kBlock, ctx->tuning.records_parts);  // lanes per SUM, two sums per ciphertext
+  const size_t parts = tc::rec_parts(2 * M, f.longest, f.simd_lanes, tc::kBlock, ctx->tuning.records_parts);  // lanes per SUM, two sums per ciphertext
   const size_t table_bytes = tc::rec_table_bytes(false, 2 * C);
-  if (table_bytes > msm_table_budget(k)) {
-    k.fail("out of memory: the tables of " + std::to_string(R) + " records need " + std::to_string(table_bytes >> 20) + " MB; split the call");
-    return k.finish();
-  }
-  const uint8_t* d_pk = k.in(pks, K * 96);
-  const uint64_t* d_kidx = k.in(key_idx, key_idx ? R : 0);
+  if (!f.tables_fit(table_bytes)) return k.finish();
+  f.stage_keys();
   const uint8_t* d_sh = k.in(shares, R * 96);
   const uint8_t* d_hash_in = hashes ? k.in(hashes, M * 192) : nullptr;
   const uint8_t* d_u = hashes ? nullptr : k.in(u, M * 96);
@@ -2270,7 +2246,7 @@ static int verify_dshare_records(tc_ctx* ctx, const uint8_t* pks, size_t K, cons
   const uint8_t* d_w = k.in(w, M * 192);
   // the pairs of the product checks: 2 * group per group, the last group filled up with identity pairs (the factor 1), so that
   // ONE launch checks every group
-  const size_t MP = NG * group, pad = MP - M;
+  const size_t MP = NG * group;
   uint8_t* d_hash_own = hashes ? nullptr : k.temp<uint8_t>(M * 192);
   const uint8_t* d_hash = hashes ? d_hash_in : d_hash_own;
   uint8_t* d_ab = k.temp<uint8_t>(MP * 2 * 96);   // [A_c, -B_c]
@@ -2278,8 +2254,6 @@ static int verify_dshare_records(tc_ctx* ctx, const uint8_t* pks, size_t K, cons
   uint64_t* d_desc = k.temp<uint64_t>(desc.size());
   uint8_t* d_seed = k.secret_seed(seed32);
   uint8_t* d_r = k.secret_temp<uint8_t>(R * 32);
-  uint8_t* d_keys_own = key_idx ? k.temp<uint8_t>(R * 96) : nullptr;
-  const uint8_t* d_keys = key_idx ? d_keys_own : d_pk;  // the key of record r
   uint8_t* d_st = k.temp<uint8_t>(2 * M);  // the sums of the ciphertexts | their hashes
   uint8_t* d_okg = k.temp<uint8_t>(NG);
   int32_t* d_tbl = k.temp<int32_t>(table_bytes / sizeof(int32_t));
@@ -2289,28 +2263,23 @@ static int verify_dshare_records(tc_ctx* ctx, const uint8_t* pks, size_t K, cons
   int32_t* ws_groups = k.pairing_product_ws(2 * group, NG, false);
   k.begin_timing();
   // checked-input mode: every key TABLE entry once (K tests, not R), every share, every u (or hash) and every w
-  const uint8_t* v_key = k.check_points(false, d_pk, 96, K, K, 1, (size_t)-1);
+  const uint8_t* v_key = k.check_points(false, f.d_pk, 96, K, K, 1, (size_t)-1);
   const uint8_t* v_sh = k.check_points(false, d_sh, 96, 1, 1, R, 1);
   const uint8_t* v_u = hashes ? k.check_points(true, d_hash_in, 192, 1, 1, M, 1) : k.check_points(false, d_u, 96, 1, 1, M, 1);
   const uint8_t* v_w = k.check_points(true, d_w, 192, 1, 1, M, 1);
-  std::vector<uint8_t> h_okg(NG), h_st(2 * M), h_vkey, h_vsh, h_vu, h_vw, h_pad(pad * 2 * (192 + 96), 0);
-  std::vector<uint64_t> h_kidx;
+  std::vector<uint8_t> h_okg(NG), h_st(2 * M), h_vkey, h_vsh, h_vu, h_vw;
   if (!k.failed) {
     k.upload(d_desc, desc.data(), desc.size() * 8, "descriptor copy");
     k.check(hipMemsetAsync(d_st, 0, 2 * M, ctx->stream), "memset");
     if (!hashes) tc::launch_hash_g1_g2(ctx->tuning, ctx->stream, d_u, d_v, d_off, M, d_hash_own, d_st + M, /*fix=*/true);
     k.check(hipMemcpy2DAsync(d_hw, 384, d_hash, 192, 192, M, hipMemcpyDeviceToDevice, ctx->stream), "hash copy");
     k.check(hipMemcpy2DAsync(d_hw + 192, 384, d_w, 192, 192, M, hipMemcpyDeviceToDevice, ctx->stream), "w copy");
-    if (pad) {
-      for (size_t i = 0; i < 2 * pad; i++) h_pad[i * 192] = h_pad[2 * pad * 192 + i * 96] = 0x40;  // the identity of G2 / of G1
-      k.upload(d_hw + M * 384, h_pad.data(), 2 * pad * 192, "pad copy");
-      k.upload(d_ab + M * 192, h_pad.data() + 2 * pad * 192, 2 * pad * 96, "pad copy");
-    }
+    f.pad_identities(d_hw + M * 384, d_ab + M * 192, 2 * (MP - M));
     tc::launch_rlc_scalars_g1(ctx->stream, d_seed, R, d_r);
-    if (key_idx) tc::launch_rec_gather_keys(ctx->stream, d_pk, K, d_kidx, R, d_keys_own);
+    f.gather_keys();
     const uint64_t *d_seg = d_desc, *d_fc = d_seg + M + 1;
     // (the short-scalar mode of the G1 two-stage kernels: 16 two-half steps, as tc_verify_decryption_shares_rlc_batch)
-    tc::launch_rec_sum_g1_pair(ctx->stream, d_sh, d_keys, reinterpret_cast<const uint32_t*>(d_r), d_seg, d_fc, M, C, parts, d_tbl, d_codes, d_ab,
+    tc::launch_rec_sum_g1_pair(ctx->stream, d_sh, f.d_keys, reinterpret_cast<const uint32_t*>(d_r), d_seg, d_fc, M, C, parts, d_tbl, d_codes, d_ab,
                                d_st, /*nbits=*/32);
     // two pairs per ciphertext (one lane pair of the Miller stage; an empty ciphertext: both sums the identity, the factor 1),
     // one final exponentiation per group                                                          (src/lib.rs:185)
@@ -2321,52 +2290,26 @@ static int verify_dshare_records(tc_ctx* ctx, const uint8_t* pks, size_t K, cons
     // (the membership tests ran beside the sums and the group checks)
     k.take_verdicts({{v_key, &h_vkey}, {v_sh, &h_vsh}, {v_u, &h_vu}, {v_w, &h_vw}});
     k.check(hipStreamSynchronize(ctx->stream), "stream sync");
-    // a bad key fails the groups of the records that NAME it: the indices are needed on the host only then
-    bool key_bad = false;
-    for (size_t i = 0; i < h_vkey.size() && !key_bad; i++) key_bad = h_vkey[i] == 0;
-    const uint64_t* hk = key_idx;
-    if (key_bad && key_idx && ctx->device_io && !k.failed) {
-      h_kidx.resize(R);
-      k.readback(h_kidx.data(), key_idx, R * 8, "index readback");
-      k.check(hipStreamSynchronize(ctx->stream), "stream sync");
-      hk = h_kidx.data();
-    }
-    std::vector<uint32_t> m_rec, m_ct;
+    tc::SlotMaps maps;  // every record of the ciphertexts of the bad groups
     if (!k.failed) {
-      std::vector<uint8_t> bad_group(NG);
-      for (size_t g = 0; g < NG; g++) {
-        const size_t mlo = g * group, mhi = (mlo + group < M) ? mlo + group : M;
-        const uint64_t rlo = hr[mlo], rhi = hr[mhi];
-        bool bad = !h_okg[g];
-        for (size_t m = mlo; m < mhi && !bad; m++)
-          bad = h_st[m] != TC_JOB_OK || h_st[M + m] != TC_JOB_OK || (!h_vu.empty() && h_vu[m] == 0) || (!h_vw.empty() && h_vw[m] == 0);
-        for (uint64_t r = rlo; r < rhi && !bad && !h_vsh.empty(); r++) bad = h_vsh[r] == 0;
-        if (key_bad)
-          for (uint64_t r = rlo; r < rhi && !bad; r++) {
-            const uint64_t i = hk ? hk[r] : r;
-            bad = i < K && h_vkey[i] == 0;  // (an index >= K has failed its ciphertext in stage T already)
-          }
-        bad_group[g] = bad;
-      }
-      // every record of the ciphertexts of the bad groups
-      std::vector<uint32_t> bad_cts;
-      tc::failed_jobs_of_groups(bad_group.data(), cut, M, bad_cts);
-      for (uint32_t m : bad_cts)
-        for (uint64_t r = hr[m]; r < hr[m + 1]; r++) {
-          m_rec.push_back((uint32_t)r);
-          m_ct.push_back(m);
-        }
+      tc::BadGroups bad(f.cut, M);
+      bad.per_group(h_okg.data(), true);
+      bad.jobs({h_st.data(), h_st.data() + M}, false);  // the sums of the ciphertexts and their hashes
+      bad.jobs({tc::bytes_or_null(h_vu), tc::bytes_or_null(h_vw)}, true);
+      bad.spans(f.h_grp.data(), tc::bytes_or_null(h_vsh), true);
+      bad.named_keys(f.h_grp.data(), f.host_key_idx(h_vkey), K, tc::bytes_or_null(h_vkey));
+      maps = tc::records_of_jobs(f.hr, bad.failed_jobs());
     }
-    if (!k.failed && !m_rec.empty()) {
+    if (!k.failed && !maps.record.empty()) {
       // the per-record check of tc_verify_decryption_share_batch for every record of the failed groups, on compacted operands
-      const size_t F = m_rec.size();
+      const size_t F = maps.record.size();
       // (the fixed hash of an undecodable u is the identity, which a pairing check would SKIP: the per-record path sees an
       // encoding that does not decode there and answers 0 -- so do these records)
       for (size_t m = 0; m < M && !hashes && !k.failed; m++)
         if (h_st[M + m] != TC_JOB_OK) k.check(hipMemsetAsync(d_hash_own + m * 192, 0xff, 192, ctx->stream), "memset");
-      Compacted c(k, F, {&m_rec, &m_ct});
+      Compacted c(k, F, {&maps.record, &maps.job});
       const uint8_t* c_sh = c.gather(d_sh, 96, 0);
-      const uint8_t* c_pk = c.gather(d_keys, 96, 0);
+      const uint8_t* c_pk = c.gather(f.d_keys, 96, 0);
       const uint8_t* c_hash = c.gather(d_hash, 192, 1);
       const uint8_t* c_w = c.gather(d_w, 192, 1);
       const tc::PairingWs pws = k.pairing_ws(F);
