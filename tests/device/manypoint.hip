@@ -1,7 +1,8 @@
 // Many-point conformance harness (test code only: never linked into libtc_amd.so, never run by bench.py).
 // Includes the product's kernel units k_msm.hip and k_comb.hip as they are (every unit of the product is self-contained:
 // -fno-gpu-rdc), so the __global__ kernels launched here are the product's own text, compiled with the product's flags.
-// Five entries; each allocates, copies in, launches, synchronises once, copies out, frees and returns the first HIP
+// Eight entries (the two-stage sums in G2 and G1, the comb signer, the ragged sums and their key gather, the paired ragged sums,
+// the G1 comb of the decryption shares and the arena ladders beside it); each allocates, copies in, launches, synchronises once, copies out, frees and returns the first HIP
 // error.  `parts` / `share` = 0 goes through the product's launcher (its own rule for the launch geometry); another value
 // launches the stage kernels directly with that value.  Tables, codes, outputs and written-only status bytes are filled
 // with 0x5A before the launch, so the caller sees what the kernels left in memory -- and what they did not touch.
@@ -51,6 +52,21 @@ bool legal_parts(size_t parts, size_t n, size_t most) {
   return parts <= most && (parts & (parts - 1)) == 0 && (parts <= 1 || 4 * parts <= n);
 }
 size_t points_bytes(size_t n, size_t B, size_t stride, size_t point) { return (B - 1) * stride + n * point; }
+// a table arena of the product's geometry, every slot free
+TableArena arena(Dev& d) {
+  TableArena ta;
+  ta.mem = (int32_t*)d.alloc(kTableArenaWords * 4, kMpPoison);
+  ta.flags = (uint32_t*)d.alloc(kTableArenaFlags * 4, 0);
+  return ta;
+}
+// the entry's return value after a run with an arena: the first HIP error, else kMpSlotLeak when a slot flag is still set
+int arena_result(Dev& d, const TableArena& ta) {
+  std::vector<uint32_t> fl(kTableArenaFlags);
+  d.download(fl.data(), ta.flags, kTableArenaFlags * 4);
+  bool leak = false;
+  for (size_t i = 0; d.e == hipSuccess && i < fl.size(); i++) leak = leak || fl[i] != 0;
+  return d.e == hipSuccess && leak ? kMpSlotLeak : (int)d.e;
+}
 }  // namespace
 
 // G2: out (B x 192), status (B, copied in from status_in first), tbl (msm_table_bytes(n, B)), codes (msm_code_bytes(n, B)).
@@ -152,9 +168,7 @@ extern "C" int mp_comb(const uint8_t* sk, size_t N, const uint64_t* idx, const u
   uint8_t* dst = (uint8_t*)d.alloc(B * n, kMpPoison);
   uint8_t* dok = (uint8_t*)d.alloc(B, kMpPoison);
   int32_t* dtbl = (int32_t*)d.alloc(tb, kMpPoison);
-  TableArena ta;
-  ta.mem = (int32_t*)d.alloc(kTableArenaWords * 4, kMpPoison);
-  ta.flags = (uint32_t*)d.alloc(kTableArenaFlags * 4, 0);
+  TableArena ta = arena(d);
   if (d.e == hipSuccess) {
     if (share == 0) {
       launch_comb_sign(0, ta, dsk, N, didx, dpts, n, B, dtbl, dok, dout, dst);
@@ -171,11 +185,7 @@ extern "C" int mp_comb(const uint8_t* sk, size_t N, const uint64_t* idx, const u
   d.download(status, dst, B * n);
   d.download(ok, dok, B);
   d.download(tbl, dtbl, tb);
-  std::vector<uint32_t> fl(kTableArenaFlags);
-  d.download(fl.data(), ta.flags, kTableArenaFlags * 4);
-  bool leak = false;
-  for (size_t i = 0; d.e == hipSuccess && i < fl.size(); i++) leak = leak || fl[i] != 0;
-  return d.e == hipSuccess && leak ? kMpSlotLeak : (int)d.e;
+  return arena_result(d, ta);
 }
 
 // The ragged sums (k_rec_tables_g2 / k_rec_ladder_g2, w = 2; k_rec_tables_g1 / k_rec_ladder_g1, w = 1) through their launchers, the
@@ -213,6 +223,98 @@ extern "C" int mp_rec_sum(int w, size_t J, const uint64_t* seg_first, const uint
   d.download(tbl, dtbl, tb);
   d.download(codes, dcodes, cb);
   return (int)d.e;
+}
+
+// The PAIRED ragged sums (k_rec_tables_g1_pair / k_rec_ladder_g1_pair) through launch_rec_sum_g1_pair, the only route: segment j
+// over points_a and over points_b with the same scalars.  out: 2 J + 2 rows (A_j, -B_j interleaved, two guard rows), status: J bytes,
+// tbl / codes: 2 x the launch's chunks AND ONE MORE (the guard chunk behind half 1).
+extern "C" int mp_rec_sum_pair(size_t J, const uint64_t* seg_first, const uint8_t* points_a, const uint8_t* points_b, const uint32_t* scalars,
+                               const uint8_t* status_in, int nbits, size_t parts, uint8_t* out, uint8_t* status, int32_t* tbl, uint8_t* codes,
+                               uint64_t* first_chunk_out) {
+  if (nbits < 2 || nbits > 128 || (nbits & 1)) return (int)hipErrorInvalidValue;
+  for (size_t j = 0; j < J; j++)
+    if (seg_first[j + 1] < seg_first[j]) return (int)hipErrorInvalidValue;
+  std::vector<uint64_t> fc(J + 1);
+  const uint64_t chunks = rec_chunk_ranges(seg_first, J, fc.data());
+  memcpy(first_chunk_out, fc.data(), (J + 1) * 8);
+  const size_t R = (size_t)seg_first[J];
+  const size_t tb = rec_table_bytes(false, 2 * chunks + 1), cb = rec_code_bytes(2 * chunks + 1), ob = (2 * J + 2) * 96;
+  Dev d;
+  const uint8_t* dpa = (const uint8_t*)d.upload(points_a, R * 96);
+  const uint8_t* dpb = (const uint8_t*)d.upload(points_b, R * 96);
+  const uint32_t* dsc = (const uint32_t*)d.upload(scalars, R * 32);
+  const uint64_t* dseg = (const uint64_t*)d.upload(seg_first, (J + 1) * 8);
+  const uint64_t* dfc = (const uint64_t*)d.upload(fc.data(), (J + 1) * 8);
+  uint8_t* dst = (uint8_t*)d.upload(status_in, J);
+  uint8_t* dout = (uint8_t*)d.alloc(ob, kMpPoison);
+  int32_t* dtbl = (int32_t*)d.alloc(tb, kMpPoison);
+  uint8_t* dcodes = (uint8_t*)d.alloc(cb, kMpPoison);
+  if (d.e == hipSuccess) {
+    launch_rec_sum_g1_pair(0, dpa, dpb, dsc, dseg, dfc, J, chunks, parts, dtbl, dcodes, dout, dst, nbits);
+    d.after_launch();
+  }
+  d.sync();
+  d.download(out, dout, ob);
+  d.download(status, dst, J);
+  d.download(tbl, dtbl, tb);
+  d.download(codes, dcodes, cb);
+  return (int)d.e;
+}
+
+// G1 comb: sk (N x 32), idx (B x n), pts (B x 96); out (B n + 1 rows of 96), status (B n + 1), ok (B + 1), tbl (comb_table_bytes_g1(B)
+// and one entry of 128 bytes): the last row / byte / entry of each is a guard.  share = 0: launch_comb_decrypt.
+extern "C" int mp_comb_g1(const uint8_t* sk, size_t N, const uint64_t* idx, const uint8_t* pts, size_t n, size_t B, size_t share, uint8_t* out,
+                          uint8_t* status, uint8_t* ok, int32_t* tbl) {
+  if (!n || !B || !N || share > (size_t)kCombG1Share) return (int)hipErrorInvalidValue;
+  Dev d;
+  const size_t tb = comb_table_bytes_g1(B) + kMsmEntryWordsG1 * sizeof(int32_t), rows = B * n + 1;
+  const uint8_t* dsk = (const uint8_t*)d.upload(sk, N * 32);
+  const uint64_t* didx = (const uint64_t*)d.upload(idx, B * n * 8);
+  const uint8_t* dpts = (const uint8_t*)d.upload(pts, B * 96);
+  uint8_t* dout = (uint8_t*)d.alloc(rows * 96, kMpPoison);
+  uint8_t* dst = (uint8_t*)d.alloc(rows, kMpPoison);
+  uint8_t* dok = (uint8_t*)d.alloc(B + 1, kMpPoison);
+  int32_t* dtbl = (int32_t*)d.alloc(tb, kMpPoison);
+  if (d.e == hipSuccess) {
+    if (share == 0) {
+      launch_comb_decrypt(0, dsk, N, didx, dpts, n, B, dtbl, dok, dout, dst);
+    } else {
+      hipLaunchKernelGGL(k_comb_tables_g1, dim3(grid_for(B)), dim3(kBlock), 0, 0, dpts, B, dtbl, dok);
+      const size_t chunks = (n + share - 1) / share;
+      hipLaunchKernelGGL(k_comb_decrypt, dim3(grid_for(chunks * B)), dim3(kBlock), 0, 0, dsk, N, didx, (const int32_t*)dtbl, (const uint8_t*)dok, n, B,
+                         dout, dst, share);
+    }
+    d.after_launch();
+  }
+  d.sync();
+  d.download(out, dout, rows * 96);
+  d.download(status, dst, rows);
+  d.download(ok, dok, B + 1);
+  d.download(tbl, dtbl, tb);
+  return (int)d.e;
+}
+
+// k_g1_mul_gather through its launcher, with a table arena of the product's geometry: out (B n + 1 rows), status (B n + 1), the
+// last of each a guard; every slot flag must be clear again afterwards (kMpSlotLeak)
+extern "C" int mp_g1_mul_gather(const uint8_t* sk, size_t N, const uint64_t* idx, const uint8_t* pts, size_t n, size_t B, uint8_t* out,
+                                uint8_t* status) {
+  if (!n || !B || !N) return (int)hipErrorInvalidValue;
+  Dev d;
+  const size_t rows = B * n + 1;
+  const uint8_t* dsk = (const uint8_t*)d.upload(sk, N * 32);
+  const uint64_t* didx = (const uint64_t*)d.upload(idx, B * n * 8);
+  const uint8_t* dpts = (const uint8_t*)d.upload(pts, B * 96);
+  uint8_t* dout = (uint8_t*)d.alloc(rows * 96, kMpPoison);
+  uint8_t* dst = (uint8_t*)d.alloc(rows, kMpPoison);
+  TableArena ta = arena(d);
+  if (d.e == hipSuccess) {
+    launch_g1_mul_gather(0, ta, dsk, N, didx, dpts, n, B, dout, dst);
+    d.after_launch();
+  }
+  d.sync();
+  d.download(out, dout, rows * 96);
+  d.download(status, dst, rows);
+  return arena_result(d, ta);
 }
 
 // k_rec_gather_keys through its launcher: pks (K x 96), key_idx (R), keys (R x 96 and 96 guard bytes behind them)

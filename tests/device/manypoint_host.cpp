@@ -1,5 +1,6 @@
 // Host leg of the many-point conformance harness (tests/manypoint_conformance.py): the header routines the kernels of
-// k_msm.hip / k_comb.hip call -- job_msm_tables, job_msm_ladder_part<SPLIT>, their G1 twins, job_comb_tables, job_comb_sign --
+// k_msm.hip / k_comb.hip call -- job_msm_tables, job_msm_ladder_part<SPLIT>, their G1 twins, job_comb_tables, job_comb_sign,
+// job_comb_tables_g1, job_comb_decrypt, and the lane arithmetic of the ragged and the paired ragged sums (tc_records.h) --
 // run by g++ with -DTC_BOUND_CHECK over the same buffers, in the layout of tests/device/manypoint.hip: the jobs one after the
 // other, the parts of a job one after the other, then the kernel's xor tree of jac_add.  It proves the case tables, the
 // models and the checkers before any GPU time is spent.  What it cannot see is the kernels' own text (lane pairs, the
@@ -8,6 +9,7 @@
 // Test code only: never linked into libtc_amd.so.
 #include "../../threshold_crypto_amd/csrc/tc_msm.h"
 #include "../../threshold_crypto_amd/csrc/tc_comb.h"
+#include "../../threshold_crypto_amd/csrc/tc_comb_g1.h"
 #include "../../threshold_crypto_amd/csrc/tc_records.h"
 
 #include <stdio.h>
@@ -37,7 +39,7 @@ struct RecG2 {
     return job_msm_tables(n, c, p, k, t, cd, true, nbits);
   }
   static Jac ladder(size_t n, const int32_t* t, const uint8_t* cd, int nbits, MsmPart part) { return job_msm_ladder_part<true>(n, t, cd, nbits, part); }
-  static void encode(const Jac& r, uint8_t* o) { g2_encode_uncompressed(jac_to_affine(r), o); }
+  static void encode(const Jac& r, uint8_t* o, bool) { g2_encode_uncompressed(jac_to_affine(r), o); }  // (no paired form in G2)
 };
 struct RecG1 {
   using Jac = G1Jac;
@@ -48,38 +50,50 @@ struct RecG1 {
   static Jac ladder(size_t n, const int32_t* t, const uint8_t* cd, int nbits, MsmPart part) {
     return job_msm_ladder_g1_part<true>(n, t, cd, part, nbits / 2);
   }
-  static void encode(const Jac& r, uint8_t* o) { g1_encode_uncompressed(jac_to_affine(r), o); }
+  static void encode(const Jac& r, uint8_t* o, bool negate) {  // (the identity stays the identity: its encoding has no y)
+    G1Affine a = jac_to_affine(r);
+    a.y = Fq::select(negate, -a.y, a.y).norm();
+    g1_encode_uncompressed(a, o);
+  }
 };
-// launch_rec_sum_g2 / _g1 as the kernels run it: stage T chunk by chunk, stage L wave by wave (kMost / parts segments per wave,
-// one trip count per wave), the parts of a segment one after the other, the `none` select, the xor tree.
+// launch_rec_sum_g2 / _g1 as the kernels run it: stage T chunk by chunk, stage L wave by wave (kMost / parts sums per wave,
+// one trip count per wave), the parts of a sum one after the other, the `none` select, the xor tree.  points_b != null: the
+// PAIRED form of launch_rec_sum_g1_pair -- 2 chunks lanes in stage T (rec_pair_chunk, rec_pair_place), the two sums of a segment
+// next to each other in stage L (rec_pair_lane), A_j and -B_j interleaved in out (rec_pair_out).
 template <class G>
-void rec_sum(size_t J, const uint64_t* seg_first, const uint8_t* points, const uint32_t* scalars, int nbits, size_t parts, uint8_t* out,
-             uint8_t* status, int32_t* tbl, uint8_t* codes, const uint64_t* first_chunk) {
+void rec_sum(size_t J, const uint64_t* seg_first, const uint8_t* points, const uint8_t* points_b, const uint32_t* scalars, int nbits, size_t parts,
+             uint8_t* out, uint8_t* status, int32_t* tbl, uint8_t* codes, const uint64_t* first_chunk) {
   const uint64_t chunks = first_chunk[J];
   if (!J || !chunks) return;
   if (parts < 1 || parts > G::kMost || (parts & (parts - 1))) parts = 1;
-  for (uint64_t c = 0; c < chunks; c++) {
-    const size_t j = rec_segment_of_chunk(first_chunk, J, c);
-    const uint64_t r0 = seg_first[j], len = seg_first[j + 1] - r0, p0 = first_chunk[j] * kMsmChunk;
-    const bool ok = G::tables((size_t)len, (size_t)(c - first_chunk[j]), points + r0 * G::kPoint, scalars + r0 * 8, tbl + p0 * 8 * G::kEntry,
-                              codes + p0 * kMsmColumns, nbits);
+  const bool pair = points_b != nullptr;
+  for (uint64_t t = 0; t < (pair ? rec_pair_tables_lanes(chunks) : chunks); t++) {
+    const RecPairChunk h = pair ? rec_pair_chunk(t, chunks) : RecPairChunk{0, t};
+    const size_t j = rec_segment_of_chunk(first_chunk, J, h.c);
+    const uint64_t r0 = seg_first[j], len = seg_first[j + 1] - r0;
+    const uint64_t p0 = pair ? rec_pair_place(h.half, first_chunk[j], chunks) : first_chunk[j] * kMsmChunk;
+    const bool ok = G::tables((size_t)len, (size_t)(h.c - first_chunk[j]), (h.half ? points_b : points) + r0 * G::kPoint, scalars + r0 * 8,
+                              tbl + p0 * 8 * G::kEntry, codes + p0 * kMsmColumns, nbits);
     if (!ok && status[j] == TC_JOB_OK) status[j] = TC_JOB_INVALID_ENCODING;
   }
-  const size_t per_wave = G::kMost / parts;
-  for (size_t j0 = 0; j0 < J; j0 += per_wave) {
-    const size_t j1 = j0 + per_wave < J ? j0 + per_wave : J;
-    std::vector<uint64_t> len(j1 - j0, 0), p0(j1 - j0, 0);
-    uint64_t trips = 0;  // (the lanes behind the last segment bring len = 0)
-    for (size_t j = j0; j < j1; j++) {
-      if (status[j] == TC_JOB_OK) {
-        len[j - j0] = seg_first[j + 1] - seg_first[j];
-        p0[j - j0] = len[j - j0] ? first_chunk[j] * kMsmChunk : 0;
+  const size_t per_wave = G::kMost / parts, sums = pair ? rec_pair_ladder_lanes(J, parts) / parts : J;
+  for (size_t q0 = 0; q0 < sums; q0 += per_wave) {
+    const size_t q1 = q0 + per_wave < sums ? q0 + per_wave : sums;
+    std::vector<uint64_t> len(q1 - q0, 0), p0(q1 - q0, 0);
+    std::vector<RecPairLane> who(q1 - q0);
+    uint64_t trips = 0;  // (the lanes behind the last sum bring len = 0)
+    for (size_t q = q0; q < q1; q++) {
+      const RecPairLane w = who[q - q0] = pair ? rec_pair_lane(q * parts, parts) : RecPairLane{q, 0, 0};
+      if (status[w.j] == TC_JOB_OK) {
+        len[q - q0] = seg_first[w.j + 1] - seg_first[w.j];
+        p0[q - q0] = !len[q - q0] ? 0 : pair ? rec_pair_place(w.half, first_chunk[w.j], chunks) : first_chunk[w.j] * kMsmChunk;
       }
-      const uint64_t t = rec_part_trips(len[j - j0], parts);
+      const uint64_t t = rec_part_trips(len[q - q0], parts);
       trips = t > trips ? t : trips;
     }
-    for (size_t j = j0; j < j1; j++) {
-      const uint64_t l = len[j - j0], p = p0[j - j0];
+    for (size_t q = q0; q < q1; q++) {
+      const uint64_t l = len[q - q0], p = p0[q - q0];
+      const RecPairLane w = who[q - q0];
       std::vector<typename G::Jac> r(parts);
       for (size_t g = 0; g < parts; g++) {
         const RecPart rp = rec_part(l, g, parts);
@@ -87,7 +101,7 @@ void rec_sum(size_t J, const uint64_t* seg_first, const uint8_t* points, const u
         r[g] = G::ladder(l ? (size_t)l : 1, tbl + p * 8 * G::kEntry, codes + p * kMsmColumns, nbits, MsmPart{(size_t)rp.s0, (size_t)rp.s1, (size_t)trips});
         r[g] = G::Jac::select(none, G::Jac::infinity(), r[g]);
       }
-      G::encode(merge(r, parts), out + j * G::kPoint);
+      G::encode(merge(r, parts), pair ? out + rec_pair_out(w.j, w.half) : out + w.j * G::kPoint, w.half != 0);
     }
   }
 }
@@ -165,14 +179,38 @@ int mph_comb(const uint8_t* sk, size_t N, const uint64_t* idx, const uint8_t* pt
   return 0;
 }
 
+// The G1 comb: stage T per ciphertext, stage S chunk by chunk in the lane order of k_comb_decrypt (on the host a lane's holder
+// loop is its own: what the WAVE's loop adds is the device leg's to show)
+int mph_comb_g1(const uint8_t* sk, size_t N, const uint64_t* idx, const uint8_t* pts, size_t n, size_t B, size_t share, uint8_t* out, uint8_t* status,
+                uint8_t* ok, int32_t* tbl) {
+  if (share < 1 || share > (size_t)kCombG1Share) return 1;
+  for (size_t j = 0; j < B; j++) ok[j] = job_comb_tables_g1(pts + j * 96, tbl + j * (size_t)kCombG1TableWords) ? 1 : 0;
+  const size_t chunks = (n + share - 1) / share;
+  for (size_t tid = 0; tid < chunks * B; tid++) {
+    const size_t c = tid / B, j = tid % B, s0 = c * share;
+    const int cnt = (int)((n - s0 < share) ? n - s0 : share);
+    const size_t o = j * n + s0;
+    job_comb_decrypt(sk, N, idx + o, cnt, tbl + j * (size_t)kCombG1TableWords, ok[j] != 0, out + o * 96, status + o);
+  }
+  return 0;
+}
+
 // The ragged sums: J segments of one record array (seg_first: J + 1 values), out (J x 96 / 192 and whatever the caller keeps behind
 // them), status (J), tbl / codes (the launch's chunks and whatever the caller keeps behind them), first_chunk (J + 1, written).
 int mph_rec_sum(int w, size_t J, const uint64_t* seg_first, const uint8_t* points, const uint32_t* scalars, const uint8_t* status_in, int nbits,
                 size_t parts, uint8_t* out, uint8_t* status, int32_t* tbl, uint8_t* codes, uint64_t* first_chunk) {
   memcpy(status, status_in, J);
   rec_chunk_ranges(seg_first, J, first_chunk);
-  if (w == 2) rec_sum<RecG2>(J, seg_first, points, scalars, nbits, parts, out, status, tbl, codes, first_chunk);
-  else rec_sum<RecG1>(J, seg_first, points, scalars, nbits, parts, out, status, tbl, codes, first_chunk);
+  if (w == 2) rec_sum<RecG2>(J, seg_first, points, nullptr, scalars, nbits, parts, out, status, tbl, codes, first_chunk);
+  else rec_sum<RecG1>(J, seg_first, points, nullptr, scalars, nbits, parts, out, status, tbl, codes, first_chunk);
+  return 0;
+}
+// The paired sums: out (2 J x 96), tbl / codes (2 x the launch's chunks), each with whatever the caller keeps behind them
+int mph_rec_sum_pair(size_t J, const uint64_t* seg_first, const uint8_t* points_a, const uint8_t* points_b, const uint32_t* scalars,
+                     const uint8_t* status_in, int nbits, size_t parts, uint8_t* out, uint8_t* status, int32_t* tbl, uint8_t* codes, uint64_t* first_chunk) {
+  memcpy(status, status_in, J);
+  rec_chunk_ranges(seg_first, J, first_chunk);
+  rec_sum<RecG1>(J, seg_first, points_a, points_b, scalars, nbits, parts, out, status, tbl, codes, first_chunk);
   return 0;
 }
 // k_rec_gather_keys: keys (R x 96 and whatever the caller keeps behind them)
@@ -303,6 +341,54 @@ int main() {
       }
       rc |= (ro1[0] == 0x40 && ro1[3 * pt] == 0x40) ? 0 : 1;
       rc |= memcmp(ro1.data() + pt, pp, pt) ? 1 : 0;  // (record 0 has the scalar 1)
+    }
+    // the paired sums over the same segments: a = the G1 points, b = the same array from record 3 on (b's first record is the
+    // identity); half 0 is the unpaired sum over a, half 1 has the x of the unpaired sum over b, every split gives the same bytes
+    {
+      const uint64_t C = 5;
+      size_t rs[3];
+      mph_rec_sizes(2 * C + 1, rs);
+      std::vector<int32_t> tb(rs[1] / 4);
+      std::vector<uint8_t> cd(rs[2]), ua(J * 96), ub(J * 96), po(2 * J * 96), po1(2 * J * 96);
+      const uint8_t* pb = p1.data() + 3 * 96;
+      rc |= mph_rec_sum(1, J, seg, p1.data(), sc.data(), z6.data(), 32, 1, ua.data(), st6.data(), tb.data(), cd.data(), fc.data());
+      rc |= mph_rec_sum(1, J, seg, pb, sc.data(), z6.data(), 32, 1, ub.data(), st6.data(), tb.data(), cd.data(), fc.data());
+      for (size_t parts : {(size_t)1, (size_t)2, (size_t)16, (size_t)64, (size_t)3}) {
+        std::fill(tb.begin(), tb.end(), 0x5A5A5A5A);
+        std::fill(cd.begin(), cd.end(), (uint8_t)0x5A);
+        rc |= mph_rec_sum_pair(J, seg, p1.data(), pb, sc.data(), z6.data(), 32, parts, parts == 1 ? po1.data() : po.data(), st6.data(), tb.data(),
+                               cd.data(), fc.data());
+        for (size_t j = 0; j < J; j++) rc |= st6[j];
+        if (parts != 1) rc |= memcmp(po.data(), po1.data(), po.size()) ? 1 : 0;
+        for (size_t i = tb.size() / (2 * C + 1) * 2 * C; i < tb.size(); i++) rc |= tb[i] == 0x5A5A5A5A ? 0 : 1;
+        for (size_t i = cd.size() / (2 * C + 1) * 2 * C; i < cd.size(); i++) rc |= cd[i] == 0x5A ? 0 : 1;
+        rc |= memcmp(cd.data(), cd.data() + C * kMsmChunk * kMsmColumns, C * kMsmChunk * kMsmColumns) ? 1 : 0;  // the same scalars
+      }
+      for (size_t j = 0; j < J; j++) {
+        rc |= memcmp(po1.data() + 2 * j * 96, ua.data() + j * 96, 96) ? 1 : 0;
+        rc |= memcmp(po1.data() + (2 * j + 1) * 96, ub.data() + j * 96, 48) ? 1 : 0;
+        const bool inf = ub[j * 96] == 0x40;  // -B_j: the identity as it is, else another y
+        rc |= (memcmp(po1.data() + (2 * j + 1) * 96 + 48, ub.data() + j * 96 + 48, 48) == 0) == inf ? 0 : 1;
+      }
+    }
+    // the G1 comb: the keys 1 .. 9 over u = 2 g1 and over the identity, at 1, 4 and 8 holders per lane
+    {
+      const size_t Bc = 2;
+      std::vector<uint8_t> u(Bc * 96), co(Bc * n * 96), co1(Bc * n * 96), cs(Bc * n), cok(Bc);
+      memcpy(u.data(), p1.data(), 96);
+      memcpy(u.data() + 96, p1.data() + 3 * 96, 96);
+      std::vector<uint64_t> ci(Bc * n);
+      for (size_t i = 0; i < Bc * n; i++) ci[i] = i % n;
+      std::vector<int32_t> ct1(Bc * (size_t)kCombG1TableWords);
+      for (size_t share : {(size_t)1, (size_t)4, (size_t)8}) {
+        rc |= mph_comb_g1(sk.data(), n, ci.data(), u.data(), n, Bc, share, share == 1 ? co1.data() : co.data(), cs.data(), cok.data(), ct1.data());
+        for (size_t i = 0; i < Bc * n; i++) rc |= cs[i];
+        rc |= (cok[0] == 1 && cok[1] == 1) ? 0 : 1;
+        if (share != 1) rc |= memcmp(co.data(), co1.data(), co.size()) ? 1 : 0;
+      }
+      rc |= memcmp(co1.data(), u.data(), 96) ? 1 : 0;             // key 1
+      rc |= memcmp(co1.data() + 96, p1.data() + 2 * 96, 96) ? 1 : 0;  // key 2 over 2 g1: record 2 is 4 g1
+      for (size_t i = 0; i < n; i++) rc |= co1[(n + i) * 96] == 0x40 ? 0 : 1;
     }
     uint8_t keys[3 * 96 + 96];
     memset(keys, 0x5A, sizeof keys);

@@ -40,6 +40,18 @@ The ragged sums of the records verifier (k_rec_tables_* / k_rec_ladder_* / k_rec
 two legs, checkers and pool: RecCase and rec_case at the end of this file.  A launch is J segments of one record array; what is
 new against the fixed-n kernels is where a lane finds its work (first_chunk[j], the segment's own column stride), one trip
 count per WAVE, and parts without records.  Nothing was found there.
+
+The PAIRED ragged sums of the decryption-share verifier (k_rec_tables_g1_pair / k_rec_ladder_g1_pair, tc_records.h rec_pair_*):
+PairCase at the end of this file.  Their results never leave the device, and an error common to both halves -- a record dropped
+from both, a wrong digit in both -- cancels in the product check that consumes them; here out[2 j] = A_j and out[2 j + 1] = -B_j are
+compared byte for byte.  A launch is two RecCases, one per half, over the same scalars: the models, the claims and the table
+checker are the unpaired ones, applied to half h at chunk offset h * chunks.  The halves of every segment are different samples of
+the pool, and a directed segment has its special case in ONE half.
+
+The G1 comb of the decryption shares (k_comb_tables_g1 / k_comb_decrypt, tc_comb_g1.h) and the arena ladders beside it
+(k_g1_mul_gather): Comb1Case.  The launcher takes one holder per lane up to 131 072 (ciphertext, holder) pairs, so the suite
+forces share = 1 .. 8: the wave's holder loop, lanes with fewer holders than their wave's longest, lanes past the end.  The 514
+table entries per ciphertext are the model's, column by column (two doublings of the oracle's affine law per column).
 """
 import ctypes
 import os
@@ -102,7 +114,7 @@ _SZ, _VP, _INT = ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int
 
 
 def load(path, prefix):
-    """prefix "mp_": the device harness; "mph_": the host leg.  The five entries take the same arguments in both."""
+    """prefix "mp_": the device harness; "mph_": the host leg.  The entries that both have take the same arguments in both."""
     lib = ctypes.CDLL(path)
     g2 = getattr(lib, prefix + "msm_g2")
     g2.argtypes = [_SZ, _SZ, _SZ, _VP, _VP, _VP, _INT, _SZ, _VP, _SZ, _SZ, _INT, _VP, _VP, _VP, _VP]
@@ -114,9 +126,17 @@ def load(path, prefix):
     rec.argtypes = [_INT, _SZ, _VP, _VP, _VP, _VP, _INT, _SZ, _VP, _VP, _VP, _VP, _VP]
     gather = getattr(lib, prefix + "rec_gather_keys")
     gather.argtypes = [_VP, _SZ, _VP, _SZ, _VP]
-    for f in (g2, g1, comb, rec, gather):
+    pair = getattr(lib, prefix + "rec_sum_pair")
+    pair.argtypes = [_SZ, _VP, _VP, _VP, _VP, _VP, _INT, _SZ, _VP, _VP, _VP, _VP, _VP]
+    comb1 = getattr(lib, prefix + "comb_g1")
+    comb1.argtypes = [_VP, _SZ, _VP, _VP, _SZ, _SZ, _SZ, _VP, _VP, _VP, _VP]
+    entries = {"g2": g2, "g1": g1, "comb": comb, "rec": rec, "gather": gather, "rec_pair": pair, "comb_g1": comb1}
+    if prefix == "mp_":  # (the arena ladders of k_g1_mul_gather: the device leg only)
+        entries["g1_mul_gather"] = lib.mp_g1_mul_gather
+        entries["g1_mul_gather"].argtypes = [_VP, _SZ, _VP, _VP, _SZ, _SZ, _VP, _VP]
+    for f in entries.values():
         f.restype = _INT
-    return {"g2": g2, "g1": g1, "comb": comb, "rec": rec, "gather": gather, "lib": lib, "host": prefix == "mph_"}
+    return dict(entries, lib=lib, host=prefix == "mph_")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -882,6 +902,22 @@ def check_msm(case, parts, res, max_report=12):
     return bad
 
 
+def sweep(lib, case, run, check, values, name, launch=None):
+    """One run of `case` per value of the launch parameter `name`.  The first run, and every run whose bytes differ from it, goes
+    through `check`; then all runs must have left the first run's bytes.  launch(run, lib, case, value): the caller's wrapper of a
+    run (the GPU leg launches nothing after a HIP error).  Returns the first run's buffers."""
+    first = v0 = None
+    for v in values:
+        res = launch(run, lib, case, v) if launch else run(lib, case, v)
+        if first is None or not all((a == b).all() for a, b in zip(res, first)):  # (equal bytes need no second decoding)
+            bad = check(case, v, res)
+            assert not bad, "\n".join(bad[:12])
+        if first is None:
+            first, v0 = res, v
+        assert all((a == b).all() for a, b in zip(res, first)), "%s: %s = %d and %s = %d leave different bytes" % (case.tag, name, v, name, v0)
+    return first
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the comb signer
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1000,6 +1036,214 @@ def check_comb(case, share, res, max_report=12):
                 check_entry(2, tbl[j, c, m], want[c][m], "%s comb entry (%d, %d)" % (what, c, m), bad)
             if len(bad) > max_report:
                 return bad
+    return bad
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the G1 comb of the decryption shares (k_comb_tables_g1 / k_comb_decrypt / k_g1_mul_gather; tc_comb_g1.h)
+# ---------------------------------------------------------------------------------------------------------------------
+# Stage S gives a lane one ciphertext and up to `share` of its n holders, chunk-major (lane = chunk * B + ciphertext), and the
+# holder loop is the WAVE's: a lane with fewer holders than the longest of its wave repeats its first one and drops the result,
+# a lane past the end has none.  The launcher takes share = 1 up to 131 072 (ciphertext, holder) pairs, so the suite forces it.
+COMB1_COLS = 64                   # tc_comb_g1.h kCombG1Columns
+COMB1_ENTRIES = COMB1_COLS * 8 + 2
+COMB1_N = 16
+COMB1_SHAPES = [(1, 5), (7, 5), (8, 5), (9, 5), (17, 5), (9, 70)]
+COMB1_CHECKED = {5: [0, 1, 2, 3, 4], 70: [0, 63, 64, 69]}  # the ciphertexts whose 514 entries are decoded
+K_ZERO, K_R, K_BIG = 0, 10, 11   # places in the key table: the scalar 0, r and 2^256 - 1
+# what a case has to contain, per share, as comb1_events finds it
+COMB1_CLAIMS = {
+    (1, 5): {1: {"index out of range first of chunk"}},
+    (7, 5): {2: {"zero first of short last chunk in a mixed wave"}, 7: {"zero in the middle of a full chunk"}},
+    (8, 5): {8: {"zero in the middle of a full chunk", "index out of range first of chunk", "invalid scalar last of chunk"}},
+    (9, 5): {8: {"zero first of short last chunk in a mixed wave", "zero in the middle of a full chunk", "index out of range first of chunk",
+                 "index out of range last of chunk", "invalid scalar last of chunk"},
+             4: {"zero first of short last chunk in a mixed wave", "invalid scalar first of chunk"}},
+    (17, 5): {8: {"zero first of short last chunk in a mixed wave"}},
+    (9, 70): {s: {"zero first of short last chunk in a mixed wave", "zero in the middle of a full chunk", "identity u in a mixed wave",
+                  "undecodable u in a mixed wave", "invalid scalar first of chunk", "invalid scalar last of chunk",
+                  "index out of range first of chunk", "index out of range last of chunk", "lanes past the end beside live ones"} for s in (4, 8)},
+}
+
+
+def comb1_model(k):
+    """job_comb_decrypt for the scalar k < r over a point other than the identity, in units of the point: (the multiple, the
+    doubling-free pass meets a special case).  The recoding is the ladder's (g1_codes); the comb is built over P, the result
+    negated for an even k."""
+    codes, flip, _ = g1_codes(k)
+    acc = (T1M[codes[COMB1_COLS] & 7] << 128) % R
+    special = False
+    for c in range(COMB1_COLS - 1, -1, -1):
+        e = (-1 if codes[c] & 8 else 1) * (T1M[codes[c] & 7] << (2 * c)) % R
+        special |= _rel(acc, e)
+        acc = (acc + e) % R
+    return (R - acc if flip else acc) % R, special
+
+
+class Comb1Case:
+    """N keys, B ciphertexts (u a multiple of G1's generator, 0 = the identity, None = undecodable), n holder indices each."""
+
+    def __init__(self, n, B):
+        rnd = random.Random("manypoint-comb1-%d-%d" % (n, B))
+        self.n, self.B, self.N, self.tag = n, B, COMB1_N, "comb G1 n=%d B=%d" % (n, B)
+        self.shares = list(range(COMB_SHARE + 1))
+        self.keys = [0, 1, 2, 3, 4, 5, X2, X2 - 1, X2 + 1, R - 1, R, (1 << 256) - 1] + [rnd.randrange(1, R) for _ in range(4)]
+        good = [i for i, k in enumerate(self.keys) if 0 < k < R]
+        N, last = self.N, n - 1
+        self.u = [pool(1)[j % 3] for j in range(B)]
+        if B == 5:
+            self.u[3], self.u[4] = 0, None
+            rows = {1: "descending", 2: "repeated"}
+            put = {(0, last): K_ZERO, (0, 1): K_ZERO, (2, 7): (1 << 64) - 1, (2, 4): K_BIG, (2, last): K_R, (2, 0): N, (3, 0): 1 << 32}
+        else:
+            self.u[64], self.u[69] = 0, None
+            rows = {60: "descending", 61: "repeated"}
+            put = {(3, 8): K_ZERO, (66, 8): K_ZERO, (5, 2): K_ZERO, (7, 0): N, (7, 7): K_R, (9, 0): K_BIG, (9, 7): (1 << 64) - 1, (11, 4): 1 << 32,
+                   (11, 3): K_R, (63, 5): N}
+        self.idx = []
+        for j in range(B):
+            how = rows.get(j)
+            self.idx.append([good[-1 - s % len(good)] if how == "descending" else 7 if how == "repeated" else good[(5 * j + 3 * s) % len(good)]
+                             for s in range(n)])
+        for (j, s), i in put.items():  # (a later entry wins where two fall on one place of a short row)
+            if s < n and not (i == K_ZERO and s == 1 and n < 3):
+                self.idx[j][s] = i
+        self.checked = COMB1_CHECKED[B]
+        self._ref = None
+        self._tables = {}
+
+    def ref(self):
+        if self._ref is None:
+            st, out = [], []
+            for j in range(self.B):
+                a = self.u[j]
+                for i in self.idx[j]:
+                    good = a is not None and i < self.N and self.keys[i] < R
+                    st.append(OK if good else INVALID)
+                    out.append(enc(1, gmul(1, a * self.keys[i] % R) if good else None))
+            self._ref = (st, out)
+        return self._ref
+
+    def table(self, a):
+        """The 514 entries over u = [a] G: entry c * 8 + m = 4^c T[m] column by column, two doublings of the oracle's affine
+        group law per column; then the start entries 4^64 T[0] and 4^64 T[3]."""
+        if a not in self._tables:
+            col = entry_points(1, a or 0)
+            ents = []
+            for _ in range(COMB1_COLS):
+                ents += col
+                col = [o.E1.dbl(o.E1.dbl(e)) for e in col]
+            self._tables[a] = ents + [col[0], col[3]]
+        return self._tables[a]
+
+
+def comb1_events(case, share):
+    """What the lanes of k_comb_decrypt meet at `share` holders per lane, by the kernel's lane order: the kinds COMB1_CLAIMS names."""
+    n, B, N = case.n, case.B, case.N
+    chunks = -(-n // share)
+    lanes = chunks * B
+    cnt_of = lambda tid: min(share, n - tid // B * share) if tid < lanes else 0  # noqa: E731
+    waves = [{cnt_of(t) for t in range(w0, w0 + 64)} for w0 in range(0, lanes, 64)]
+    mixed = [share in cs and any(0 < c < share for c in cs) for cs in waves]
+    found = set()
+    if lanes % 64:
+        found.add("lanes past the end beside live ones")
+    for tid in range(lanes):
+        c, j = tid // B, tid % B
+        s0, cnt, u = c * share, cnt_of(tid), case.u[j]
+        if mixed[tid // 64] and u in (0, None):
+            found.add("identity u in a mixed wave" if u == 0 else "undecodable u in a mixed wave")
+        for s in range(s0, s0 + cnt):
+            i = case.idx[j][s]
+            where = [w for w, hit in (("first", s == s0), ("last", s == s0 + cnt - 1)) if hit]
+            if i >= N or case.keys[i] >= R:
+                found |= {"%s %s of chunk" % ("index out of range" if i >= N else "invalid scalar", w) for w in where}
+            elif u not in (0, None) and comb1_model(case.keys[i])[1]:  # (the scalar 0, test_manypoint_host.py shows)
+                if s == s0 and cnt < share and c == chunks - 1 and mixed[tid // 64]:
+                    found.add("zero first of short last chunk in a mixed wave")
+                if cnt == share and not where:
+                    found.add("zero in the middle of a full chunk")
+    return found
+
+
+_COMB1 = {}
+
+
+def comb1_case(n, B):
+    if (n, B) not in _COMB1:
+        _COMB1[(n, B)] = Comb1Case(n, B)
+    return _COMB1[(n, B)]
+
+
+def _comb1_in(case):
+    sk = np.frombuffer(b"".join(k.to_bytes(32, "little") for k in case.keys), dtype=np.uint8).copy()
+    idx = np.array(case.idx, dtype=np.uint64).reshape(-1)
+    pts = np.frombuffer(b"".join(BAD_POINT[1] if a is None else enc(1, gmul(1, a)) for a in case.u), dtype=np.uint8).copy()
+    out = np.full((case.B * case.n + 1) * 96, POISON, dtype=np.uint8)
+    status = np.full(case.B * case.n + 1, POISON, dtype=np.uint8)
+    return sk, idx, pts, out, status
+
+
+def run_comb1(lib, case, share):
+    """(out (B n + 1 rows), status (B n + 1), ok (B + 1), tbl (B x 514 entries and a guard entry)) as the leg left them."""
+    sk, idx, pts, out, status = _comb1_in(case)
+    ok = np.full(case.B + 1, POISON, dtype=np.uint8)
+    tbl = np.full((case.B * COMB1_ENTRIES + 1) * ENTRY[1], POISON_WORD, dtype=np.int32)
+    rc = lib["comb_g1"](_ptr(sk), case.N, _ptr(idx), _ptr(pts), case.n, case.B, share, _ptr(out), _ptr(status), _ptr(ok), _ptr(tbl))
+    if rc != 0:
+        raise HipError("%s share=%d: the harness returned %d" % (case.tag, share, rc))
+    return out.reshape(-1, 96), status, ok, tbl.reshape(-1, ENTRY[1])
+
+
+def run_g1_mul_gather(lib, case):
+    """k_g1_mul_gather over the comb's case: (out (B n + 1 rows), status (B n + 1))."""
+    sk, idx, pts, out, status = _comb1_in(case)
+    rc = lib["g1_mul_gather"](_ptr(sk), case.N, _ptr(idx), _ptr(pts), case.n, case.B, _ptr(out), _ptr(status))
+    if rc != 0:
+        raise HipError("%s gather: the harness returned %d%s" % (case.tag, rc, " (a table slot stayed in use)" if rc == SLOT_LEAK else ""))
+    return out.reshape(-1, 96), status
+
+
+def check_comb1_out(case, what0, out, status, max_report=12):
+    """Outputs and statuses of a run over a Comb1Case (the comb's or the gather ladders'), and the guards behind them."""
+    want_st, want_out = case.ref()
+    bad, rows = [], case.B * case.n
+    if bytes(out[rows]) != bytes([POISON]) * 96 or status[rows] != POISON:
+        bad.append("%s: output or status written behind the last share" % what0)
+    for i in range(rows):
+        what = "%s ciphertext %d holder %d" % (what0, i // case.n, i % case.n)
+        if status[i] != want_st[i]:
+            bad.append("%s: status %d, expected %d" % (what, status[i], want_st[i]))
+        if bytes(out[i]) != want_out[i]:
+            bad.append("%s: wrong output bytes" % what)
+        if len(bad) > max_report:
+            break
+    return bad
+
+
+def check_comb1(case, share, res, max_report=12):
+    out, status, ok, tbl = res
+    what0 = "%s share=%d" % (case.tag, share)
+    bad = check_comb1_out(case, what0, out, status, max_report)
+    if ok[case.B] != POISON or not (tbl[case.B * COMB1_ENTRIES] == POISON_WORD).all():
+        bad.append("%s: the ok byte or the table entry behind the last ciphertext written" % what0)
+    limbs = tbl[:case.B * COMB1_ENTRIES].reshape(-1, 2, 16)[..., :13]
+    if limbs.min() < _LIMB_LO or limbs.max() > _LIMB_HI:
+        bad.append("%s: a stored limb outside [%g, %g] 2^28" % (what0, dc.NORM_LO, dc.NORM_HI))
+    first = {}
+    for j, a in enumerate(case.u):
+        what = "%s ciphertext %d" % (what0, j)
+        t = tbl[j * COMB1_ENTRIES:(j + 1) * COMB1_ENTRIES]
+        if ok[j] != int(a is not None):
+            bad.append("%s: ok byte %d" % (what, ok[j]))
+        if a in first and not (t == tbl[first[a] * COMB1_ENTRIES:(first[a] + 1) * COMB1_ENTRIES]).all():
+            bad.append("%s: its comb differs from ciphertext %d's over the same point" % (what, first[a]))
+        first.setdefault(a, j)
+        if j not in case.checked or len(bad) > max_report:
+            continue
+        want = case.table(a)  # (None, an undecodable u: the identity's table)
+        for e in range(COMB1_ENTRIES):
+            check_entry(1, t[e], want[e], "%s comb entry %d (column %d)" % (what, e, e // 8), bad)
     return bad
 
 
@@ -1163,11 +1407,14 @@ def rec_directed(w, nbits, rnd, unit=False):
     return segs
 
 
-def rec_lay_out(w, nbits, rnd, head, directed, J, unit=False):
-    """lay_out for segments: random ones of the lengths `head`, then three directed ones and a short random one, to J."""
-    segs = [rec_random_seg(w, n, nbits, rnd, unit, "random len %d" % n) for n in head]
+def rec_lay_out(w, nbits, rnd, head, directed, J, unit=False, make=None, failing=None):
+    """lay_out for segments: random ones of the lengths `head`, then three directed ones and a short random one, to J.
+    make(n, tag): a random segment, failing(s): a directed segment fails -- the paired form brings its own."""
+    make = make or (lambda n, tag: rec_random_seg(w, n, nbits, rnd, unit, tag))
+    failing = failing or (lambda s: s.status_in != OK or not MsmCase(w, len(s.a), 1, nbits, [s], [1]).valid(s))
+    segs = [make(n, "random len %d" % n) for n in head]
     # a failing segment goes between two that are OK: both neighbours must stay exact
-    fails = [s for s in directed if s.status_in != OK or not MsmCase(w, len(s.a), 1, nbits, [s], [1]).valid(s)]
+    fails = [s for s in directed if failing(s)]
     good = [s for s in directed if not any(s is f for f in fails)]
     d, fill = [], 0
     while good or fails:
@@ -1179,8 +1426,25 @@ def rec_lay_out(w, nbits, rnd, head, directed, J, unit=False):
                 segs.append(d.pop(0))
         if len(segs) < J:
             fill += 1
-            segs.append(rec_random_seg(w, 1 + (fill % 3 == 0), nbits, rnd, unit, "random filler"))
+            segs.append(make(1 + (fill % 3 == 0), "random filler"))
     return segs, d
+
+
+def rec_small_segs(w, kind, nbits, rnd):
+    """The segments of the small kinds (rec_case): fail first, no segment, all empty, one record."""
+    if kind == "fail first":
+        bad = rec_random_seg(w, 3, nbits, rnd, tag="undecodable first record of the launch")
+        bad.random, bad.a[0] = False, None
+        kept = rec_random_seg(w, 2, nbits, rnd, tag="status not OK on entry")
+        kept.random, kept.status_in = False, NOT_ENOUGH
+        return [rec_random_seg(w, n, nbits, rnd) if n is not None else s for n, s in
+                ((0, None), (None, bad), (0, None), (5, None), (0, None), (2, None), (None, kept), (1, None), (0, None))]
+    if kind == "no segment":
+        return []
+    if kind == "all empty":
+        return [rec_random_seg(w, 0, nbits, rnd) for _ in range(5)]
+    assert kind == "one record"
+    return [rec_random_seg(w, 1, nbits, rnd)]
 
 
 _REC = {}
@@ -1208,20 +1472,8 @@ def rec_case(w, kind):
         segs, left = rec_lay_out(w, nbits, rnd, REC_HEAD, rec_directed(w, nbits, rnd, True), REC_J, True)
     elif kind == "full":
         segs, left = rec_lay_out(w, nbits, rnd, [0, 1, 33, 2, 9, 5, 3, 8], rec_directed(w, nbits, rnd), 27)
-    elif kind == "fail first":
-        bad = rec_random_seg(w, 3, nbits, rnd, tag="undecodable first record of the launch")
-        bad.random, bad.a[0] = False, None
-        kept = rec_random_seg(w, 2, nbits, rnd, tag="status not OK on entry")
-        kept.random, kept.status_in = False, NOT_ENOUGH
-        segs = [rec_random_seg(w, n, nbits, rnd) if n is not None else s for n, s in
-                ((0, None), (None, bad), (0, None), (5, None), (0, None), (2, None), (None, kept), (1, None), (0, None))]
-    elif kind == "no segment":
-        segs = []
-    elif kind == "all empty":
-        segs = [rec_random_seg(w, 0, nbits, rnd) for _ in range(5)]
     else:
-        assert kind == "one record"
-        segs = [rec_random_seg(w, 1, nbits, rnd)]
+        segs = rec_small_segs(w, kind, nbits, rnd)
     case = RecCase(w, nbits, segs, tag)
     case.left_out = [s.tag for s in left]
     _REC[key] = case
@@ -1265,12 +1517,24 @@ def check_rec(case, parts, res, max_report=12):
     for j, seg in enumerate(case.segs):
         if len(bad) > max_report:
             break
-        n = case.lens[j]
-        what = "%s segment %d (%s, len %d)" % (what0, j, seg.tag, n)
+        what = "%s segment %d (%s, len %d)" % (what0, j, seg.tag, case.lens[j])
         if status[j] != want_st[j]:
             bad.append("%s: status %d, expected %d" % (what, status[j], want_st[j]))
         if bytes(out[j]) != want_out[j]:
             bad.append("%s: wrong output bytes" % what)
+    check_rec_places(case, what0, tbl, codes, bad, max_report)
+    return bad
+
+
+def check_rec_places(case, what0, tbl, codes, bad, max_report=12):
+    """The tables and digit codes of every segment of `case` in tbl / codes, which start at the segments' chunk 0 (the paired
+    form hands in one half at a time)."""
+    w, ew = case.w, ENTRY[case.w]
+    for j, seg in enumerate(case.segs):
+        if len(bad) > max_report:
+            break
+        n = case.lens[j]
+        what = "%s segment %d (%s, len %d)" % (what0, j, seg.tag, n)
         if not n:
             continue
         p0, s4 = case.first_chunk[j] * 4, 4 * ((n + 3) // 4)
@@ -1291,6 +1555,164 @@ def check_rec(case, parts, res, max_report=12):
             want = entry_points(w, seg.a[s] if s < n else 0, flips[s] and s < n)
             for m in range(8):
                 check_entry(w, t[s, m], want[m], "%s place %d entry %d" % (what, s, m), bad)
+
+
+# ---- the PAIRED ragged sums (k_rec_tables_g1_pair / k_rec_ladder_g1_pair; tc_records.h rec_pair_*) ----
+# Segment j is summed over points_a and over points_b with the SAME scalars; out[2 j] = A_j, out[2 j + 1] = -B_j.  A pair is two
+# segments (Jobs) that share k and status_in: half 0 over a, half 1 over b.  Each half of a launch is a RecCase of its own --
+# the models, the claims and the table checker are the unpaired ones, run once per half.
+PAIR_NBITS = 32  # tc_verify_decryption_share_records_rlc_batch ships G1 short scalars of 32 bits
+PAIR_TABLES = ["short", "full", "fail first", "no segment", "all empty", "one record"]
+# where the special case of a directed segment of rec_directed goes (the other half is a random sample of the pool)
+PAIR_SIDE = {"equal neighbours": 0, "equal neighbours at the start of 5": 1, "P and -P": 1, "P, -P, Q": 0, "identity alone": 1,
+             "identity first, and first of part 2/4": 0, "identity in mid-part": 1, "opposite halves": 0, "undecodable first record": 0,
+             "undecodable last record": 1, "status not OK on entry": 0, "scalar = r": 0, "even scalar": 1, "scalar that is not short": 0}
+PAIR_SECOND = {"P and -P": 0, "undecodable first record": 2}  # from a second draw of rec_directed; 2: both halves
+
+
+class Pair:
+    def __init__(self, a, b, tag, random):
+        assert a.k == b.k and a.status_in == b.status_in
+        self.half, self.tag, self.random, self.status_in = (a, b), tag, random, a.status_in
+
+
+def pair_partner(seg, nbits, rnd):
+    """The other half of `seg`: other points of the pool under seg's scalars, shown by the model to meet nothing."""
+    for _ in range(50):
+        p = Job(rnd.sample(pool(1), len(seg.a)), list(seg.k), "partner of " + seg.tag, status_in=seg.status_in)
+        p.random = True
+        if not check_rec_claims(RecCase(1, nbits, [p], "probe")):
+            return p
+    raise AssertionError("no partner without a special case")
+
+
+def pair_random(n, nbits, rnd, tag="random"):
+    a = rec_random_seg(1, n, nbits, rnd, tag=tag)
+    return Pair(a, pair_partner(a, nbits, rnd), tag, True)
+
+
+def pair_directed(nbits, rnd):
+    """rec_directed with the special case in ONE half (PAIR_SIDE), then a second draw for the other side of two of them."""
+    pairs = []
+    for table, draw in ((PAIR_SIDE, rec_directed(1, nbits, rnd)), (PAIR_SECOND, rec_directed(1, nbits, rnd))):
+        for d in draw:
+            if d.tag not in table:
+                continue
+            side, p = table[d.tag], pair_partner(d, nbits, rnd)
+            if side == 2:  # the same record undecodable in both halves
+                p.a[d.a.index(None)] = None
+            tag = "%s in %s" % (d.tag, ("a", "b", "both")[side])
+            pairs.append(Pair(p, d, tag, False) if side == 1 else Pair(d, p, tag, False))
+    return pairs
+
+
+class PairCase:
+    def __init__(self, nbits, pairs, tag):
+        self.nbits, self.pairs, self.tag, self.J = nbits, pairs, tag, len(pairs)
+        self.half = [RecCase(1, nbits, [p.half[h] for p in pairs], "%s half %d" % (tag, h)) for h in (0, 1)]
+        self.parts = self.half[0].parts
+        self.first_chunk, self.chunks, self.lens = self.half[0].first_chunk, self.half[0].chunks, self.half[0].lens
+        self.left_out = []
+        self._ref = None
+
+    def failing(self, j):
+        return self.pairs[j].status_in != OK or not (self.half[0].valid(j) and self.half[1].valid(j))
+
+    def ref(self):
+        """Expected status per segment and output bytes per ROW (2 J rows), once: [sum a_i k_i] G, then -[sum b_i k_i] G."""
+        if self._ref is None:
+            st, out = [], []
+            for j, p in enumerate(self.pairs):
+                st.append(p.status_in if p.status_in != OK or self.chunks == 0 else INVALID if self.failing(j) else OK)
+                for h in (0, 1):
+                    m = sum(a * k for a, k in zip(p.half[h].a, p.half[h].k)) % R if not self.failing(j) else 0
+                    out.append(bytes([POISON]) * 96 if self.chunks == 0 else enc(1, gmul(1, neg_mult(1, m) if h else m)))
+            self._ref = (st, out)
+        return self._ref
+
+
+_PAIR = {}
+
+
+def pair_case(kind):
+    """The kinds of rec_case at w = 1 with an independent b array.  short: nbits = 32, J = 70; full: nbits = 128, J = 27."""
+    if kind in _PAIR:
+        return _PAIR[kind]
+    rnd = random.Random("manypoint-pair-%s" % kind)
+    nbits = REC_FULL[1] if kind == "full" else PAIR_NBITS
+    left = []
+    if kind in ("short", "full"):
+        head, J = (REC_HEAD, REC_J) if kind == "short" else ([0, 1, 33, 2, 9, 5, 3, 8], 27)
+        probe = lambda p: PairCase(nbits, [p], "probe").failing(0)  # noqa: E731
+        pairs, left = rec_lay_out(1, nbits, rnd, head, pair_directed(nbits, rnd), J, make=lambda n, tag: pair_random(n, nbits, rnd, tag), failing=probe)
+    else:
+        pairs = []
+        for s in rec_small_segs(1, kind, nbits, rnd):
+            pairs.append(Pair(s, pair_partner(s, nbits, rnd), s.tag + ("" if s.random else " in a"), s.random))
+    case = PairCase(nbits, pairs, "pair %s nbits=%d" % (kind, nbits))
+    case.left_out = [p.tag for p in left]
+    _PAIR[kind] = case
+    return case
+
+
+def check_pair_claims(case):
+    """check_rec_claims on both halves: the half that holds a directed segment confirms its claims, every random half -- the
+    partner of a directed one too -- meets nothing."""
+    return check_rec_claims(case.half[0]) + check_rec_claims(case.half[1])
+
+
+def run_rec_pair(lib, case, parts):
+    """(out (2 J + 2 rows), status (J + 1), tbl, codes (2 chunks + 1 chunks each), first_chunk) as the leg left them."""
+    J = case.J
+    pts = [np.frombuffer(b"".join(BAD_POINT[1] if a is None else enc(1, gmul(1, a)) for p in case.pairs for a in p.half[h].a) + b"\0",
+                         dtype=np.uint8).copy() for h in (0, 1)]
+    sc = np.array([dc.u32s(k) for p in case.pairs for k in p.half[0].k] + [[0] * 8], dtype=np.uint32).reshape(-1)
+    st_in = np.array([p.status_in for p in case.pairs] + [0], dtype=np.uint8)
+    seg_first = np.array(case.half[0].seg_first, dtype=np.uint64)
+    out = np.full((2 * J + 2) * 96, POISON, dtype=np.uint8)
+    status = np.full(J + 1, POISON, dtype=np.uint8)
+    tbl = np.full((2 * case.chunks + 1) * 4 * 8 * ENTRY[1], POISON_WORD, dtype=np.int32)
+    codes = np.full((2 * case.chunks + 1) * 4 * COLS, POISON, dtype=np.uint8)
+    fc = np.full(J + 1, 0x5A5A5A5A5A5A5A5A, dtype=np.uint64)
+    rc = lib["rec_pair"](J, _ptr(seg_first), _ptr(pts[0]), _ptr(pts[1]), _ptr(sc), _ptr(st_in), case.nbits, parts, _ptr(out), _ptr(status), _ptr(tbl),
+                         _ptr(codes), _ptr(fc))
+    if rc != 0:
+        raise HipError("%s parts=%d: the harness returned %d" % (case.tag, parts, rc))
+    return out.reshape(2 * J + 2, 96), status, tbl, codes, fc
+
+
+def check_rec_pair(case, parts, res, max_report=12):
+    """Every check of the paired sums on one run; returns the list of failures."""
+    out, status, tbl, codes, fc = res
+    J, C, ew = case.J, case.chunks, ENTRY[1]
+    want_st, want_out = case.ref()
+    what0 = "%s parts=%d" % (case.tag, parts)
+    bad = []
+    if fc.tolist() != case.first_chunk:
+        bad.append("%s: first_chunk %s, expected %s" % (what0, fc.tolist(), case.first_chunk))
+    if bytes(out[2 * J:].reshape(-1)) != bytes([POISON]) * 192 or status[J] != POISON:
+        bad.append("%s: output or status written behind the last segment" % what0)
+    if not (tbl[2 * C * 4 * 8 * ew:] == POISON_WORD).all() or not (codes[2 * C * 4 * COLS:] == POISON).all():
+        bad.append("%s: the guard chunk behind half 1's tables or codes written" % what0)
+    if C == 0 and (not (tbl == POISON_WORD).all() or not (codes == POISON).all()):
+        bad.append("%s: a launch without records wrote tables or codes" % what0)
+    for j, p in enumerate(case.pairs):
+        what = "%s segment %d (%s, len %d)" % (what0, j, p.tag, case.lens[j])
+        if status[j] != want_st[j]:
+            bad.append("%s: status %d, expected %d" % (what, status[j], want_st[j]))
+        for h in (0, 1):
+            if bytes(out[2 * j + h]) != want_out[2 * j + h]:
+                bad.append("%s: wrong output bytes in half %d" % (what, h))
+        if len(bad) > max_report:
+            return bad
+    for h in (0, 1):  # half h's tables and codes: the layout of an unpaired launch, at chunk offset h * chunks
+        check_rec_places(case.half[h], "%s half %d" % (what0, h), tbl[h * C * 4 * 8 * ew:(h + 1) * C * 4 * 8 * ew], codes[h * C * 4 * COLS:(h + 1) * C * 4 * COLS],
+                         bad, max_report)
+    for j in range(J):  # the same scalars: the same codes
+        if case.half[0].valid(j) and case.half[1].valid(j):
+            c0, c1 = (case.first_chunk[j] * 4 * COLS, case.first_chunk[j + 1] * 4 * COLS)
+            if not (codes[c0:c1] == codes[C * 4 * COLS + c0:C * 4 * COLS + c1]).all():
+                bad.append("%s segment %d: the codes of half 1 differ from half 0's" % (what0, j))
     return bad
 
 

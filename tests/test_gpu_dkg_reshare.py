@@ -5,7 +5,8 @@ src/lib.rs:719-767) vs Oracle A.  Byte-exact, no tolerance anywhere.
 Shapes: 70 outputs are more than one wave and no multiple of 64; n = 5 leaves most lanes of a 64-lane output with nothing, n = 67
 gives most of them one term.  The test points are [a] g1 for known scalars a (tc_g1_commitment_batch; tests/test_gpu_dkg.py checks
 it against the oracle), so what a weighted sum should be is ONE oracle multiplication per output: (sum_k w_k a_kj mod r) g1.  Every
-sum runs with the default choice of lanes per output and with TC_SUM_PARTS = 1, 4 and 64: the bytes must not depend on it."""
+sum runs with the default choice of lanes per output, with TC_SUM_PARTS = 1, 4 and 64, and with forced slices per output of the
+weighted G1 sum (TC_WSUM_SLICES = 3 at 4 lanes, 5 at 64 lanes, 64 at one lane): the bytes must not depend on any of it."""
 import contextlib
 import random
 
@@ -73,10 +74,17 @@ def rnd():
 
 @pytest.fixture(scope="module")
 def engines(engine):
-    """the session context (the default rule for the lanes per output) and one context per forced TC_SUM_PARTS"""
+    """the session context (the default rule for the lanes per output), one context per forced TC_SUM_PARTS, and three that
+    also force the slices per output of the weighted G1 sum (TC_WSUM_SLICES): 3 slices of 4 lanes (uneven slices, and empty
+    lanes at n = 5), 5 slices of 64 lanes, and one lane per slice with as many slices as the context takes.  tc_ctx_create reads
+    TC_WSUM_SLICES = 1 .. 64 and leaves anything else to the default rule, so 1000 is the default rule (one slice at one lane per
+    output) and 64 is the largest forced value: g1_wsum_slices clamps it to n, one term per slice at n = 5"""
     from conftest import engine_with_env
+    forced = [dict(TC_SUM_PARTS=p) for p in (1, 4, 64)]
+    forced += [dict(TC_SUM_PARTS=4, TC_WSUM_SLICES=3), dict(TC_SUM_PARTS=64, TC_WSUM_SLICES=5), dict(TC_SUM_PARTS=1, TC_WSUM_SLICES=1000),
+               dict(TC_SUM_PARTS=1, TC_WSUM_SLICES=64)]
     with contextlib.ExitStack() as stack:
-        yield [engine] + [stack.enter_context(engine_with_env(TC_SUM_PARTS=p)) for p in (1, 4, 64)]
+        yield [engine] + [stack.enter_context(engine_with_env(**env)) for env in forced]
 
 
 @pytest.fixture(scope="module")

@@ -9,8 +9,11 @@ column), nothing written for jobs the filter leaves alone / with *need == 0 / in
 the same bytes for every parts / share.  Covered geometry: parts 1 .. 32 (G2) and 1 .. 64 (G1) including the unsplit ladder
 kernel, short-scalar mode with nbits = 16 (G2), 32 and 80 (G1), the shared table set, the filter's shapes n = 2, 3, 4,
 share = 1 .. 8 of the comb and several workgroups with a ragged tail; the ragged sums of the records verifier (k_rec_*) over
-70 segments of 0 .. 130 records at every power of two of parts up to a wave's worth, and k_rec_gather_keys.  Invalid encodings are ordinary data; after a HIP
-error nothing more is launched."""
+70 segments of 0 .. 130 records at every power of two of parts up to a wave's worth, and k_rec_gather_keys; the PAIRED ragged
+sums of the decryption-share verifier (k_rec_*_g1_pair: A_j and -B_j byte for byte in the shipped 32-bit mode and at full
+width, half 1's tables and codes behind all of half 0's); the G1 comb of the decryption shares (k_comb_tables_g1 /
+k_comb_decrypt) at share = 0 .. 8 over one wave and over 70 ciphertexts, with its 514-entry tables, and k_g1_mul_gather over the
+same case.  Invalid encodings are ordinary data; after a HIP error nothing more is launched."""
 import os
 import sys
 
@@ -129,3 +132,33 @@ def test_rec_sum(lib, w, kind):
 def test_rec_gather_keys(lib):
     got, want = _launch(mp.run_gather, lib)
     assert got == want
+
+
+@pytest.mark.parametrize("kind", mp.PAIR_TABLES)
+def test_rec_sum_pair(lib, kind):
+    """The paired ragged sums (k_rec_tables_g1_pair / k_rec_ladder_g1_pair) through launch_rec_sum_g1_pair: out[2 j] = A_j and
+    out[2 j + 1] = -B_j byte for byte (an error common to both halves cancels in the product check of the verifier, not here), the
+    statuses, half 0's and half 1's tables and codes at their chunk offsets, the guard chunk and guard rows; parts = 1 .. 64, then
+    3 and 128 (run as parts = 1), all with the same bytes."""
+    case = mp.pair_case(kind)
+    mp.sweep(lib, case, mp.run_rec_pair, mp.check_rec_pair, case.parts, "parts", _launch)
+
+
+@pytest.mark.parametrize("n,B", mp.COMB1_SHAPES)
+def test_comb_g1(lib, n, B):
+    """The G1 comb of the decryption shares (k_comb_tables_g1 / k_comb_decrypt): share = 0 (launch_comb_decrypt, which takes one
+    holder per lane at these sizes) and every forced share = 1 .. 8 -- the wave's holder loop, lanes with fewer holders than their
+    wave's longest, lanes past the end -- leave the same outputs, statuses, ok bytes and 66 KB tables, all equal to the model."""
+    case = mp.comb1_case(n, B)
+    mp.sweep(lib, case, mp.run_comb1, mp.check_comb1, case.shares, "share", _launch)
+
+
+def test_g1_mul_gather_leaves_the_bytes_of_the_comb(lib):
+    """k_g1_mul_gather (one arena ladder per share, 630 lanes with a ragged last wave) over the comb's B = 70, n = 9 case: the
+    comb's output and status bytes, the guards untouched, every arena slot free again afterwards."""
+    case = mp.comb1_case(9, 70)
+    out, status = _launch(mp.run_g1_mul_gather, lib, case)
+    bad = mp.check_comb1_out(case, case.tag + " gather", out, status)
+    assert not bad, "\n".join(bad[:12])
+    comb = _launch(mp.run_comb1, lib, case, 8)
+    assert (out == comb[0]).all() and (status == comb[1]).all()

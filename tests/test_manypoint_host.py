@@ -12,6 +12,11 @@ signer.
     full case tables of the GPU leg through the same checkers, so tables, models and checkers are proven before a GPU run.
 (e) The ragged sums of the records verifier (k_rec_*): the model's rec_part is the library's, the tables have the shapes the
     ragged forms need, every directed segment hits what it claims, and the host leg runs every table at every parts.
+(f) The paired ragged sums (k_rec_*_g1_pair): the halves of a segment are different samples under the same scalars, a directed
+    segment has its special case in one half and a partner that meets nothing in the other, no directed segment is left out,
+    and the host leg (rec_pair_chunk / _place / _lane / _out as the kernels use them, the negated half) runs every table.
+(g) The G1 comb of the decryption shares: the model of the doubling-free pass (only the scalar 0 meets a special case), the
+    directed placements each case claims per share (by the kernel's lane order), and the host leg at share = 1 .. 8.
 """
 import ctypes
 import os
@@ -41,8 +46,10 @@ def test_manypoint_kernels_cross_compile_for_gfx950():
     with open(lib, "rb") as f:
         text = f.read()
     for name in (b"mp_msm_g2", b"mp_msm_g1", b"mp_comb", b"mp_rec_sum", b"mp_rec_gather_keys",
-                 b"k_rec_tables_g2", b"k_rec_ladder_g2", b"k_rec_tables_g1", b"k_rec_ladder_g1", b"k_rec_gather_keys"):
-        assert name in text, name  # the entries of the harness and the ragged kernels they reach
+                 b"k_rec_tables_g2", b"k_rec_ladder_g2", b"k_rec_tables_g1", b"k_rec_ladder_g1", b"k_rec_gather_keys",
+                 b"mp_rec_sum_pair", b"mp_comb_g1", b"mp_g1_mul_gather", b"k_rec_tables_g1_pair", b"k_rec_ladder_g1_pair", b"k_comb_tables_g1",
+                 b"k_comb_decrypt", b"k_g1_mul_gather"):
+        assert name in text, name  # the entries of the harness and the ragged, paired and G1 comb kernels they reach
 
 
 @pytest.fixture(scope="module")
@@ -348,3 +355,100 @@ def test_host_rec_sum(host, w, kind):
 def test_host_rec_gather_keys(host):
     got, want = mp.run_gather(host)
     assert got == want
+
+
+# ---- the paired ragged sums (k_rec_*_g1_pair; tc_records.h rec_pair_*) -------------------------------------------------------
+def test_pair_tables_have_the_shapes_the_paired_forms_need():
+    case = mp.pair_case("short")
+    assert case.nbits == mp.PAIR_NBITS == 32 and case.J == mp.REC_J > 64 and case.J % 64 and case.lens[:16] == mp.REC_HEAD
+    assert case.parts == [1, 2, 4, 8, 16, 32, 64, 3, 128] and mp.pair_case("full").nbits == 128 and mp.pair_case("full").J == 27
+    assert all(p.random for p in case.pairs[:16])
+    for kind in ("short", "full"):
+        case = mp.pair_case(kind)
+        tags = {p.tag for p in case.pairs}
+        want = {"equal neighbours in a", "P and -P in b", "P and -P in a", "identity alone in b", "identity in mid-part in b", "opposite halves in a",
+                "undecodable first record in a", "undecodable last record in b", "undecodable first record in both", "scalar = r in a",
+                "status not OK on entry in a"} | ({"even scalar in b", "scalar that is not short in a"} if kind == "short" else set())
+        assert tags >= want, (kind, want - tags)
+        st, out = case.ref()
+        for j, p in enumerate(case.pairs):
+            a, b = p.half
+            assert a.k == b.k and len(a.a) == len(b.a)
+            if not p.random or case.lens[j] > 1:  # the halves are different samples: a common error cannot hide in equal inputs
+                assert a.a != b.a or not case.lens[j], (kind, j)
+            if st[j] != mp.OK:                    # a failing segment sits between segments that are OK, identities in both rows
+                assert st[j - 1] == mp.OK and (j + 1 == case.J or st[j + 1] == mp.OK or not case.pairs[j + 1].random), (kind, j)
+                assert out[2 * j] == out[2 * j + 1] == mp.enc(1, None)
+        by_tag = {p.tag: j for j, p in enumerate(case.pairs)}
+        # a failure in ONE half fails the segment: the other half alone is valid
+        j = by_tag["undecodable first record in a"]
+        assert not case.half[0].valid(j) and case.half[1].valid(j) and st[j] == mp.INVALID
+        j = by_tag["undecodable last record in b"]
+        assert case.half[0].valid(j) and not case.half[1].valid(j) and st[j] == mp.INVALID
+        j = by_tag["scalar = r in a"]
+        assert not case.half[0].valid(j) and not case.half[1].valid(j)
+        # B is the identity while A is not: the negated half keeps the canonical encoding
+        j = by_tag["P and -P in b"]
+        assert st[j] == mp.OK and out[2 * j + 1] == bytes([0x40]) + bytes(95) and out[2 * j] != out[2 * j + 1]
+        j = by_tag["P and -P in a"]
+        assert st[j] == mp.OK and out[2 * j] == bytes([0x40]) + bytes(95) and out[2 * j + 1][0] != 0x40
+    # -B_j: the x of B_j, the other y
+    case = mp.pair_case("one record")
+    b = case.pairs[0].half[1]
+    pt = mp.gmul(1, b.a[0] * b.k[0] % R)
+    assert case.ref()[1][1] == mp.enc(1, (pt[0], mp.P - pt[1]))
+    st = mp.pair_case("fail first").ref()[0]
+    assert mp.pair_case("fail first").lens[:3] == [0, 3, 0] and st[:3] == [mp.OK, mp.INVALID, mp.OK] and mp.NOT_ENOUGH in st
+    assert mp.pair_case("no segment").J == 0 and mp.pair_case("all empty").chunks == 0
+    assert mp.pair_case("all empty").ref()[1] == [bytes([mp.POISON]) * 96] * 10  # chunks == 0: nothing is written
+
+
+def test_directed_pairs_hit_what_they_claim_and_random_halves_hit_nothing():
+    for kind in mp.PAIR_TABLES:
+        case = mp.pair_case(kind)
+        assert not mp.check_pair_claims(case), case.tag
+        assert not case.left_out, (case.tag, case.left_out)
+        for j, p in enumerate(case.pairs):  # the partner of a directed half is a random one, with claims of its own to meet nothing
+            assert p.random == all(h.random for h in p.half) and (p.random or sum(h.random for h in p.half) == 1), (case.tag, j)
+    claims = [(h, c) for p in mp.pair_case("short").pairs for h in (0, 1) if isinstance(p.half[h].claim, list) for c in p.half[h].claim]
+    assert {h for h, _ in claims} == {0, 1} and {c["merge"] for _, c in claims if "merge" in c} >= {(5, "opposite"), (5, "equal"), (0, "identity")}
+
+
+@pytest.mark.parametrize("kind", mp.PAIR_TABLES)
+def test_host_rec_sum_pair(host, kind):
+    """Every parts gives the bytes of parts = 1: A_j and -B_j, statuses, both halves' tables and codes, the guards."""
+    case = mp.pair_case(kind)
+    mp.sweep(host, case, mp.run_rec_pair, mp.check_rec_pair, case.parts, "parts")
+
+
+# ---- the G1 comb (k_comb_tables_g1 / k_comb_decrypt; tc_comb_g1.h) --------------------------------------------------------------
+def test_comb_g1_model_and_cases():
+    """The doubling-free pass in units of u gives k for every valid key, and of the key table only the scalar 0 meets a special
+    case over a point other than the identity (the guarded fallback).  Every case holds what COMB1_CLAIMS says it holds, at the
+    share it names, by the kernel's own lane order."""
+    case = mp.comb1_case(9, 70)
+    assert case.keys[:12] == [0, 1, 2, 3, 4, 5, X2, X2 - 1, X2 + 1, R - 1, R, (1 << 256) - 1] and len(case.keys) == case.N == 16
+    for k in case.keys + list(range(6, 40)) + [R - k for k in range(2, 40)]:
+        if k < R:
+            m, special = mp.comb1_model(k)
+            assert m == k and special == (k == 0), hex(k)
+    for n, B in mp.COMB1_SHAPES:
+        c = mp.comb1_case(n, B)
+        assert c.shares == list(range(9)) and {0, None} <= set(c.u)
+        for share, kinds in mp.COMB1_CLAIMS[(n, B)].items():
+            assert kinds <= mp.comb1_events(c, share), (n, B, share, kinds - mp.comb1_events(c, share))
+        flat = [i for row in c.idx for i in row]
+        if n >= 9:
+            assert {c.N, 1 << 32, (1 << 64) - 1, mp.K_ZERO, mp.K_R, mp.K_BIG} <= set(flat)
+            assert any(row.count(7) >= n - 4 for row in c.idx) and (n > 13 or any(row == sorted(row, reverse=True) and len(set(row)) == n for row in c.idx))
+    # B = 70, n = 9: at share 4 wave 2 mixes cnt = 4 with cnt = 1 and wave 3 has 18 live lanes; at share 8 cnt = 8 sits beside cnt = 1
+    assert -(-9 // 4) * 70 == 210 and 210 - 192 == 18 and -(-9 // 8) * 70 == 140
+    assert case.u[64] == 0 and case.u[69] is None and case.checked == [0, 63, 64, 69]
+    # the launcher's own rule never leaves share = 1 at these shapes: the suite forces it
+    assert all(n * B <= 131072 for n, B in mp.COMB1_SHAPES)
+
+
+@pytest.mark.parametrize("n,B", mp.COMB1_SHAPES)
+def test_host_comb_g1(host, n, B):
+    case = mp.comb1_case(n, B)
+    mp.sweep(host, case, mp.run_comb1, mp.check_comb1, case.shares[1:], "share")  # (share = 0, the launcher's choice: the device leg)
