@@ -103,6 +103,19 @@ int main() {
   }
   bdh_range_sum(1, l2.data(), 2, 3, 1, q2.data());
   rc |= q2[0] == 0x40 ? 0 : 1;
+  // a range longer than a wave at a wave's worth of parts: 70 G1 leaves of one row of 5 points (the key-share form), slots 3 .. 69
+  {
+    const size_t m = 70;
+    std::vector<int32_t> l3(m * kBlameLeafWordsG1);
+    std::vector<uint8_t> r1(96), r64(96), r3(96);
+    bdh_leaves(0, seed, 0, p1.data(), n, nullptr, m, l3.data());
+    bdh_range_sum(0, l3.data(), 3, m, 1, r1.data());
+    bdh_range_sum(0, l3.data(), 3, m, 64, r64.data());
+    bdh_range_sum(0, l3.data(), 3, m, 32, r3.data());
+    rc |= (memcmp(r1.data(), r64.data(), 96) || memcmp(r1.data(), r3.data(), 96) || r1[0] == 0x40) ? 1 : 0;
+    bdh_range_sum(0, l3.data(), 66, 67, 64, r3.data());  // leaf 66 is point 1, the identity's encoding: 63 parts without a term beside it
+    rc |= r3[0] == 0x40 ? 0 : 1;
+  }
   printf("blame_dev_host: %s\n", rc ? "FAILED" : "ok");
   return rc ? 1 : 0;
 }

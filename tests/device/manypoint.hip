@@ -6,67 +6,24 @@
 // error.  `parts` / `share` = 0 goes through the product's launcher (its own rule for the launch geometry); another value
 // launches the stage kernels directly with that value.  Tables, codes, outputs and written-only status bytes are filled
 // with 0x5A before the launch, so the caller sees what the kernels left in memory -- and what they did not touch.
+// The blame-by-bisection kernels (k_blame.hip) have a harness file of their own beside this one: manypoint_blame.hip.
 //   build: tests/manypoint_conformance.py (hipcc, keyed by a hash of the sources)
 #include <hip/hip_runtime.h>
 #include "../../threshold_crypto_amd/csrc/k_msm.hip"
 #include "../../threshold_crypto_amd/csrc/k_comb.hip"
+
+#include "manypoint_dev.h"  // Dev, arena, arena_result, kMpSlotLeak, kMpPoison
 
 #include <string.h>
 #include <vector>
 
 using namespace tc;
 
-constexpr int kMpSlotLeak = -2;  // a table slot was still marked in use after the run
-constexpr int kMpPoison = 0x5A;
-
 namespace {
-struct Dev {
-  std::vector<void*> owned;
-  hipError_t e = hipSuccess;
-  void* alloc(size_t bytes, int fill = -1) {
-    void* p = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&p, bytes ? bytes : 1);
-    if (e == hipSuccess) owned.push_back(p);
-    if (e == hipSuccess && fill >= 0 && bytes) e = hipMemset(p, fill, bytes);
-    return e == hipSuccess ? p : nullptr;
-  }
-  void* upload(const void* src, size_t bytes) {
-    void* p = alloc(bytes);
-    if (e == hipSuccess && bytes) e = hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
-    return p;
-  }
-  void download(void* dst, const void* src, size_t bytes) {
-    if (e == hipSuccess && bytes) e = hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost);
-  }
-  void after_launch() {
-    if (e == hipSuccess) e = hipGetLastError();
-  }
-  void sync() {
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-  }
-  ~Dev() {
-    for (void* p : owned) hipFree(p);
-  }
-};
 bool legal_parts(size_t parts, size_t n, size_t most) {
   return parts <= most && (parts & (parts - 1)) == 0 && (parts <= 1 || 4 * parts <= n);
 }
 size_t points_bytes(size_t n, size_t B, size_t stride, size_t point) { return (B - 1) * stride + n * point; }
-// a table arena of the product's geometry, every slot free
-TableArena arena(Dev& d) {
-  TableArena ta;
-  ta.mem = (int32_t*)d.alloc(kTableArenaWords * 4, kMpPoison);
-  ta.flags = (uint32_t*)d.alloc(kTableArenaFlags * 4, 0);
-  return ta;
-}
-// the entry's return value after a run with an arena: the first HIP error, else kMpSlotLeak when a slot flag is still set
-int arena_result(Dev& d, const TableArena& ta) {
-  std::vector<uint32_t> fl(kTableArenaFlags);
-  d.download(fl.data(), ta.flags, kTableArenaFlags * 4);
-  bool leak = false;
-  for (size_t i = 0; d.e == hipSuccess && i < fl.size(); i++) leak = leak || fl[i] != 0;
-  return d.e == hipSuccess && leak ? kMpSlotLeak : (int)d.e;
-}
 }  // namespace
 
 // G2: out (B x 192), status (B, copied in from status_in first), tbl (msm_table_bytes(n, B)), codes (msm_code_bytes(n, B)).

@@ -1,6 +1,7 @@
 // Host leg of the many-point conformance harness (tests/manypoint_conformance.py): the header routines the kernels of
 // k_msm.hip / k_comb.hip call -- job_msm_tables, job_msm_ladder_part<SPLIT>, their G1 twins, job_comb_tables, job_comb_sign,
-// job_comb_tables_g1, job_comb_decrypt, and the lane arithmetic of the ragged and the paired ragged sums (tc_records.h) --
+// job_comb_tables_g1, job_comb_decrypt, the lane arithmetic of the ragged and the paired ragged sums (tc_records.h), and the
+// routines of k_blame.hip (tc_blame_jobs.h: blame_call_seed, job_blame_leaf, blame_leaf_g1 / _g2, job_blame_range_part) --
 // run by g++ with -DTC_BOUND_CHECK over the same buffers, in the layout of tests/device/manypoint.hip: the jobs one after the
 // other, the parts of a job one after the other, then the kernel's xor tree of jac_add.  It proves the case tables, the
 // models and the checkers before any GPU time is spent.  What it cannot see is the kernels' own text (lane pairs, the
@@ -11,9 +12,11 @@
 #include "../../threshold_crypto_amd/csrc/tc_comb.h"
 #include "../../threshold_crypto_amd/csrc/tc_comb_g1.h"
 #include "../../threshold_crypto_amd/csrc/tc_records.h"
+#include "../../threshold_crypto_amd/csrc/tc_blame_jobs.h"
 
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 #include <vector>
 
 using namespace tc;
@@ -245,6 +248,80 @@ void mph_sizes(size_t n, size_t B, size_t* out4) {
   out4[2] = B * msm_chunks(n) * kMsmChunk * 8 * kMsmEntryWordsG1 * sizeof(int32_t);
   out4[3] = B * (size_t)kCombTableWords * sizeof(int32_t);
 }
+}
+
+// ---- blame by bisection (k_blame.hip; tc_blame_jobs.h): the entries of tests/device/manypoint_blame.hip ----
+namespace {
+void key_words(const uint8_t* b, uint32_t* w) {
+  for (int i = 0; i < 8; i++) w[i] = (uint32_t)b[4 * i] | ((uint32_t)b[4 * i + 1] << 8) | ((uint32_t)b[4 * i + 2] << 16) | ((uint32_t)b[4 * i + 3] << 24);
+}
+// k_blame_seed, then k_blame_leaves leaf by leaf (every lane is its own leader)
+template <class F>
+void blame_leaves(const uint8_t* key32, uint64_t call, uint64_t leaf0, const uint8_t* pts, size_t period, uint8_t* live, size_t n, uint8_t* seed_out,
+                  int32_t* leaves) {
+  uint32_t key[8], seed[8];
+  key_words(key32, key);
+  blame_call_seed(key, call, seed);
+  for (int w = 0; w < 8; w++)
+    for (int b = 0; b < 4; b++) seed_out[4 * w + b] = (uint8_t)(seed[w] >> (8 * b));
+  key_words(seed_out, key);  // (k_blame_leaves reads the seed's bytes)
+  for (size_t r = 0; r < n; r++)
+    job_blame_leaf<F>(key, leaf0 + r, pts + (period ? r % period : r) * PointIO<F>::BYTES, live ? live + r : nullptr, true, leaves + r * BlameLeaf<F>::WORDS);
+}
+// launch_blame_range_sum's normalisation, then k_blame_range_sum item by item: the parts one after the other, the xor tree, one
+// conversion.  (On the host a lane is a wave: the masked trips of job_blame_range_part are the device leg's to execute.)
+template <class F>
+void blame_sums(const int32_t* leaves, size_t N, const uint32_t* job, const uint32_t* lo, const uint32_t* hi, size_t n_items, size_t parts, uint8_t* out) {
+  const size_t most = std::is_same<F, Fq2>::value ? 32 : 64;
+  if (parts < 1 || parts > most || (parts & (parts - 1))) parts = 1;
+  for (size_t it = 0; it < n_items; it++) {
+    std::vector<Jac<F>> r(parts);
+    for (size_t g = 0; g < parts; g++) r[g] = job_blame_range_part<F>(leaves + (size_t)job[it] * N * BlameLeaf<F>::WORDS, lo[it], hi[it], g, parts);
+    PointIO<F>::encode(jac_to_affine(merge(r, parts)), out + it * PointIO<F>::BYTES);
+  }
+}
+template <class F>
+void blame_ladder(const uint8_t* pts, const uint8_t* live, const uint64_t* digits, size_t n, int32_t* leaves) {
+  for (size_t r = 0; r < n; r++) {
+    Affine<F> p = Affine<F>::infinity();
+    const bool ok = PointIO<F>::decode(pts + r * PointIO<F>::BYTES, p) && live[r] != 0;
+    if constexpr (std::is_same<F, Fq2>::value) blame_store_leaf(leaves + r * BlameLeaf<F>::WORDS, blame_leaf_g2(p, ok, digits + 4 * r));
+    else blame_store_leaf(leaves + r * BlameLeaf<F>::WORDS, blame_leaf_g1(p, ok, digits + 4 * r));
+  }
+}
+}  // namespace
+
+extern "C" {
+// leaves: n rows, live_out: n bytes (copied from live_in first), each with whatever the caller keeps behind them
+int mph_blame_leaves(int g2, const uint8_t* key32, uint64_t call, uint64_t leaf0, const uint8_t* pts, size_t n_pts, size_t period,
+                     const uint8_t* live_in, size_t n, uint8_t* seed_out, int32_t* leaves, uint8_t* live_out) {
+  if (!n || n_pts != (period ? period : n)) return 1;
+  if (live_in) memcpy(live_out, live_in, n);
+  if (g2) blame_leaves<Fq2>(key32, call, leaf0, pts, period, live_in ? live_out : nullptr, n, seed_out, leaves);
+  else blame_leaves<Fq>(key32, call, leaf0, pts, period, live_in ? live_out : nullptr, n, seed_out, leaves);
+  return 0;
+}
+int mph_blame_range_sum(int g2, const int32_t* leaves, size_t F, size_t N, const uint32_t* job, const uint32_t* lo, const uint32_t* hi, size_t n_items,
+                        size_t parts, uint8_t* out) {
+  for (size_t i = 0; i < n_items; i++)
+    if (job[i] >= F || lo[i] >= hi[i] || hi[i] > N) return 1;  // (an empty range is outside the kernel's contract)
+  if (g2) blame_sums<Fq2>(leaves, N, job, lo, hi, n_items, parts, out);
+  else blame_sums<Fq>(leaves, N, job, lo, hi, n_items, parts, out);
+  return 0;
+}
+int mph_blame_chain(int g2, const uint8_t* key32, uint64_t call, uint64_t leaf0, const uint8_t* pts, size_t n_pts, size_t period, const uint8_t* live_in,
+                    size_t n, const uint32_t* lo, const uint32_t* hi, size_t n_items, size_t parts, uint8_t* seed_out, uint8_t* live_out, uint8_t* out) {
+  std::vector<int32_t> leaves(n * (size_t)(g2 ? kBlameLeafWordsG2 : kBlameLeafWordsG1));
+  std::vector<uint32_t> job(n_items, 0);
+  const int rc = mph_blame_leaves(g2, key32, call, leaf0, pts, n_pts, period, live_in, n, seed_out, leaves.data(), live_out);
+  return rc ? rc : mph_blame_range_sum(g2, leaves.data(), 1, n, job.data(), lo, hi, n_items, parts, out);
+}
+int mph_blame_ladder(int g2, const uint8_t* pts, const uint8_t* live, const uint64_t* digits, size_t n, int32_t* leaves) {
+  if (g2) blame_ladder<Fq2>(pts, live, digits, n, leaves);
+  else blame_ladder<Fq>(pts, live, digits, n, leaves);
+  return 0;
+}
+size_t mph_blame_leaf_bytes(int g2) { return (size_t)(g2 ? kBlameLeafWordsG2 : kBlameLeafWordsG1) * sizeof(int32_t); }
 }
 
 #if defined(MP_MAIN)

@@ -52,10 +52,20 @@ The G1 comb of the decryption shares (k_comb_tables_g1 / k_comb_decrypt, tc_comb
 (k_g1_mul_gather): Comb1Case.  The launcher takes one holder per lane up to 131 072 (ciphertext, holder) pairs, so the suite
 forces share = 1 .. 8: the wave's holder loop, lanes with fewer holders than their wave's longest, lanes past the end.  The 514
 table entries per ciphertext are the model's, column by column (two doublings of the oracle's affine law per column).
+
+Blame by bisection (k_blame_seed / k_blame_leaves / k_blame_range_sum, tc_blame_jobs.h), through a harness file of its own
+(tests/device/manypoint_blame.hip; the host leg shares manypoint_host.cpp): LeavesCase, LadderCase, RangeCase and ChainCase at the end
+of this file.  The leaves never leave the device and both sums of a bisection step are built from the same (job, lo, hi), so an
+error common to both cancels in the pairing check; here every leaf is decoded from its raw words ([r_i] P_i with r from the
+oracle's ChaCha20; the limb form, the padding words, the G2 row order), the leaf ladders run at digits ChaCha20 would give once
+in 2^16 leaves or less, and every range sum is compared byte for byte at every parts -- parts beyond the length of a range
+included, where most lanes run masked trips only (the one path the host leg cannot execute: there a lane is a wave).  Nothing was
+found.
 """
 import ctypes
 import os
 import random
+import struct
 import sys
 
 import numpy as np
@@ -1738,3 +1748,548 @@ def run_gather(lib):
     if rc != 0:
         raise HipError("gather keys: the harness returned %d" % rc)
     return bytes(keys), want
+
+
+# ---- blame by bisection (k_blame.hip / tc_blame_jobs.h): the leaves, the leaf ladders at chosen digits, the range sums ----
+# The leaves never leave the device and the two sums of a bisection step are built from the same (job, lo, hi), so an error common
+# to both -- a term dropped by the partition of a range, a lane whose masked trips disturb its accumulator -- cancels in the
+# pairing check that consumes them.  Here every leaf is decoded from its raw words and every sum is compared byte for byte.
+# A leaf is a Jacobian point in limb form: rows of 16 words, X, Y, Z in G1; X.c0, X.c1, Y.c0, Y.c1, Z.c0, Z.c1 in G2.
+BLAME_KEY = bytes((3 * i + 1) & 0xff for i in range(32))
+LEAF_ROWS = {1: 3, 2: 6}   # kBlameLeafWordsG1 / G2 = 16 words per row
+WAVE_LEAVES = {1: 64, 2: 32}  # leaves per wave: one lane / one lane pair each
+BLAME_PARTS = {w: [0] + REC_PARTS[w] + REC_ILLEGAL[w] for w in (1, 2)}  # 0: blame_sum_parts' choice (the device leg only)
+BLAME_F, BLAME_N = 4, 130
+BLAME_HEAD = [1, 2, 3, 4, 5, 6, 7, 8, 9, 33, 64, 65, 130]
+
+
+def build_device_blame():
+    """tests/device/manypoint_blame.hip -> a gfx950 shared object, by the recipe of build_device."""
+    from threshold_crypto_amd import build as tcb
+    src = os.path.join(DEV, "manypoint_blame.hip")
+    return dc._build("libtc_manypoint_blame", lambda out: [dc.hipcc()] + tcb.FLAGS + ["-w", "-shared", src, "-o", out], {"manypoint_blame.hip"})
+
+
+def load_blame(path, prefix):
+    """prefix "mp_": tests/device/manypoint_blame.hip; "mph_": the host leg (build_host).  The same arguments in both."""
+    lib = ctypes.CDLL(path)
+    u64 = ctypes.c_uint64
+    sig = {"leaves": [_INT, _VP, u64, u64, _VP, _SZ, _SZ, _VP, _SZ, _VP, _VP, _VP],
+           "range_sum": [_INT, _VP, _SZ, _SZ, _VP, _VP, _VP, _SZ, _SZ, _VP],
+           "chain": [_INT, _VP, u64, u64, _VP, _SZ, _SZ, _VP, _SZ, _VP, _VP, _SZ, _SZ, _VP, _VP, _VP],
+           "ladder": [_INT, _VP, _VP, _VP, _SZ, _VP]}
+    entries = {}
+    for name, args in sig.items():
+        entries[name] = getattr(lib, prefix + "blame_" + name)
+        entries[name].argtypes, entries[name].restype = args, _INT
+    sizes = [getattr(lib, prefix + "blame_leaf_bytes")]
+    sizes[0].argtypes = [_INT]
+    if prefix == "mp_":  # (blame_sum_parts is a host function of k_blame.hip: the device harness only)
+        sizes.append(lib.mp_blame_sum_parts)
+        sizes[1].argtypes = [_INT, _SZ, _SZ, _INT]
+        entries["sum_parts"] = sizes[1]
+    for f in sizes:
+        f.restype = _SZ
+    assert [sizes[0](g2) for g2 in (0, 1)] == [LEAF_ROWS[1] * 64, LEAF_ROWS[2] * 64]
+    return dict(entries, lib=lib, host=prefix == "mph_")
+
+
+def blame_call_seed(key, call):
+    """blame_call_seed: the first 32 bytes of the oracle's ChaCha20 block `call` under the context's key."""
+    return struct.pack("<8I", *o.chacha20_block(struct.unpack("<8I", key), call)[:8])
+
+
+def digits_scalar(d):
+    return d[0] + d[1] * X + d[2] * X ** 2 + d[3] * X ** 3
+
+
+def blame_scalar(seed, leaf):
+    """blame_digits: (the four 16-bit digits of leaf number `leaf`, d0 odd; the scalar they stand for)."""
+    w0, w1 = o.chacha20_block(struct.unpack("<8I", seed), leaf)[:2]
+    d = [(w0 & 0xffff) | 1, w0 >> 16, w1 & 0xffff, w1 >> 16]
+    return d, digits_scalar(d)
+
+
+def _flat(w, v):
+    return [v] if w == 1 else list(v)
+
+
+def identity_leaf(w):
+    """Jac::infinity() = (0, 1, 0) as blame_store_leaf writes it: zero rows, and the plain digits of the Montgomery one."""
+    one = dc.encode(1).limbs + [0, 0]
+    rows = [[0] * 16 for _ in range(LEAF_ROWS[w])]
+    rows[w] = one  # Y (G2: Y.c0)
+    return [x for r in rows for x in r]
+
+
+def leaf_words(w, m, rnd):
+    """[m] G as a leaf with a random Z: (x z^2, y z^3, z), every coordinate the plain digits of its Montgomery form or of that
+    plus p -- the two representatives blame_store_fq's product below 2.1 p can have."""
+    if m % R == 0:
+        return identity_leaf(w)
+    F, pt = E[w].F, gmul(w, m)
+    z = rnd.randrange(1, P) if w == 1 else (rnd.randrange(P), rnd.randrange(1, P))
+    z2 = F.sqr(z)
+    coords = _flat(w, F.mul(pt[0], z2)) + _flat(w, F.mul(pt[1], F.mul(z2, z))) + _flat(w, z)
+    return [x for v in coords for x in dc.encode(v, k=rnd.randrange(2)).limbs + [0, 0]]
+
+
+def leaf_point(w, row, what, bad):
+    """One stored leaf (48 / 96 words) -> the affine point X / Z^2, Y / Z^3 (None: Z = 0), with the representation checks: every
+    limb inside [NORM_LO, NORM_HI] 2^28, |value| <= 2.1 p, words 14 and 15 of every row 0, c0 / c1 in rows 2 c / 2 c + 1."""
+    row = [int(x) for x in row]
+    for c in range(LEAF_ROWS[w]):
+        if row[16 * c + 14] or row[16 * c + 15]:
+            bad.append("%s: words 14, 15 of row %d: %s" % (what, c, row[16 * c + 14:16 * c + 16]))
+    cs = [coord(row[16 * c:16 * c + 16], "%s row %d" % (what, c), bad) for c in range(LEAF_ROWS[w])]
+    return E[w]._to_affine(tuple(cs) if w == 1 else ((cs[0], cs[1]), (cs[2], cs[3]), (cs[4], cs[5])))
+
+
+def check_leaf_rows(w, rows, want, what0, bad, max_report=12):
+    """rows: len(want) leaves and a guard row; want: the affine points (None: the identity, Z = 0)."""
+    if not (rows[len(want)] == POISON_WORD).all():
+        bad.append("%s: the guard row behind the leaves written" % what0)
+    for i, pt in enumerate(want):
+        if len(bad) > max_report:
+            break
+        what = "%s leaf %d" % (what0, i)
+        if (rows[i] == POISON_WORD).all():
+            bad.append("%s: not written" % what)
+            continue
+        got = leaf_point(w, rows[i], what, bad)
+        if got != pt:
+            bad.append("%s: %s" % (what, "Z != 0 in a dead slot" if pt is None else "Z = 0" if got is None else "wrong point"))
+        if pt is None and [int(x) for x in rows[i]] != identity_leaf(w):
+            bad.append("%s: the identity is not stored as (0, 1, 0)" % what)
+
+
+class LeavesCase:
+    """k_blame_leaves over n leaves: a[q]: the multiple of point q (0: the identity's encoding, None: BAD_POINT), live: n bytes or
+    None.  Identity encodings, slots that are not live and undecodable points stand first, last and in the middle of the waves (G2:
+    on both of a wave's last lane pairs), each kind in each place over the waves of n = 130."""
+    KINDS = ("identity", "not live", "bad")
+
+    def __init__(self, w, n, leaf0, period, with_live, call):
+        self.w, self.n, self.leaf0, self.period, self.call = w, n, leaf0, period, call
+        self.tag = "blame leaves w=%d n=%d leaf0=%d period=%d%s" % (w, n, leaf0, period, "" if with_live else " no live")
+        rnd = random.Random("manypoint-" + self.tag)
+        W = WAVE_LEAVES[w]
+        self.a = [rnd.choice(pool(w)) for _ in range(period or n)]
+        self.live = [1] * n if with_live else None
+        if n > 4:
+            for v in range(-(-n // W)):
+                size = min(W, n - v * W)
+                places = {0: v % 3, size - 1: (v + 1) % 3}
+                if size > 16:
+                    places.update({size // 2 - 3 + 3 * j: (v + 2 + j) % 3 for j in range(3)})
+                    if w == 2:
+                        places[size - 2] = (v + 2) % 3
+                for p, kind in places.items():
+                    self._place(v * W + p, self.KINDS[kind])
+        if with_live and n > 40:
+            self.live[20], self.live[21] = 0, 0xff     # (any non-zero byte marks a live slot)
+            if not period:
+                self.a[20] = None                    # not live AND undecodable: the byte stays as it is
+        self._ref = None
+
+    def _place(self, r, kind):
+        q = r % self.period if self.period else r
+        if kind == "not live" and self.live is not None:
+            self.live[r] = 0
+        else:
+            self.a[q] = None if kind == "bad" else 0
+
+    def kind(self, r):
+        a = self.a[r % self.period if self.period else r]
+        return "not live" if self.live is not None and not self.live[r] else "bad" if a is None else "identity" if a == 0 else "point"
+
+    def points(self):
+        return b"".join(BAD_POINT[self.w] if a is None else enc(self.w, gmul(self.w, a)) for a in self.a)
+
+    def ref(self):
+        """(seed, the multiple of every leaf, its affine point, the live bytes afterwards with the guard byte or None), once."""
+        if self._ref is None:
+            seed = blame_call_seed(BLAME_KEY, self.call)
+            live_out = None if self.live is None else list(self.live) + [POISON]
+            mults = []
+            for r in range(self.n):
+                a = self.a[r % self.period if self.period else r]
+                marked = self.live is None or self.live[r] != 0
+                if marked and a is None and live_out is not None:
+                    live_out[r] = 0
+                mults.append(a * blame_scalar(seed, self.leaf0 + r)[1] % R if marked and a is not None else 0)
+            self._ref = (seed, mults, [gmul(self.w, m) for m in mults], live_out)
+        return self._ref
+
+
+LEAVES_SHAPES = [(1, 0, 0, True), (33, (1 << 32) - 3, 0, True), (64, 0, 0, True), (65, (1 << 32) - 3, 0, True), (130, (1 << 32) - 3, 0, True),
+                 (130, 0, 52, False), (130, 7 * 52, 52, True)]  # n, leaf0, period, with live; 130 = two and a half rows of 52
+LEAVES_CALLS = [0, 1, (1 << 40) + 3]
+_LEAVES = {}
+
+
+def leaves_case(w, n, leaf0, period, with_live):
+    key = (w, n, leaf0, period, with_live)
+    if key not in _LEAVES:
+        _LEAVES[key] = LeavesCase(w, n, leaf0, period, with_live, LEAVES_CALLS[LEAVES_SHAPES.index(key[1:]) % 3])
+    return _LEAVES[key]
+
+
+def _leaves_in(case):
+    pts = np.frombuffer(case.points(), dtype=np.uint8).copy()
+    live_in = None if case.live is None else np.array(case.live + [POISON], dtype=np.uint8)
+    key = np.frombuffer(BLAME_KEY, dtype=np.uint8).copy()
+    return pts, live_in, key, np.full(32, POISON, dtype=np.uint8), np.full(case.n + 1, POISON, dtype=np.uint8)
+
+
+def run_blame_leaves(lib, case):
+    """(seed, leaves (n rows and the guard row), live (n bytes and the guard byte; all 0x5A without a live array)) as the leg left them."""
+    w, n = case.w, case.n
+    pts, live_in, key, seed, live_out = _leaves_in(case)
+    leaves = np.full((n + 1) * LEAF_ROWS[w] * 16, POISON_WORD, dtype=np.int32)
+    rc = lib["leaves"](w - 1, _ptr(key), case.call, case.leaf0, _ptr(pts), len(case.a), case.period, _ptr(live_in) if live_in is not None else None, n,
+                       _ptr(seed), _ptr(leaves), _ptr(live_out))
+    if rc != 0:
+        raise HipError("%s: the harness returned %d" % (case.tag, rc))
+    return seed, leaves.reshape(n + 1, -1), live_out
+
+
+def check_blame_leaves(case, res, max_report=12):
+    seed, leaves, live = res
+    want_seed, _, want, want_live = case.ref()
+    bad = []
+    if bytes(seed) != want_seed:
+        bad.append("%s: the seed is not the oracle's ChaCha20 block %d" % (case.tag, case.call))
+    if live.tolist() != (want_live if want_live is not None else [POISON] * (case.n + 1)):
+        diff = [i for i, (a, b) in enumerate(zip(live.tolist(), want_live or [POISON] * (case.n + 1))) if a != b]
+        bad.append("%s: live bytes (guard byte: index %d) differ at %s" % (case.tag, case.n, diff[:8]))
+    check_leaf_rows(case.w, leaves, want, case.tag, bad, max_report)
+    return bad
+
+
+# -- the leaf ladders at chosen digits --
+LADDER_DIGITS = [(1, 0, 0, 0), (0xffff, 0xffff, 0xffff, 0xffff), (1, 0xffff, 0, 0), (1, 0, 1, 0), (1, 0, 0, 1), (0xffff, 0, 0xfffe, 0), (3, 1, 2, 0xffff)]
+LADDER_RANDOM = 48
+
+
+class LadderCase:
+    """blame_leaf_g1 / blame_leaf_g2 + blame_store_leaf over rows of (multiple of the point, live, four digits): every directed
+    digit row with a random point, with the identity and with live = false, and random rows with d0 odd.  The directed rows stand
+    at lane (pair) 0 and at the last one of the full waves, at lane 0 of the ragged wave and around the middle; the rows of a wave
+    all differ."""
+
+    def __init__(self, w):
+        self.w, self.tag = w, "blame ladder w=%d" % w
+        rnd = random.Random("manypoint-" + self.tag)
+        W = WAVE_LEAVES[w]
+        directed = [(a, live, d) for d in LADDER_DIGITS for a, live in ((rnd.choice(pool(w)), 1), (0, 1), (rnd.choice(pool(w)), 0))]
+        T = len(directed) + LADDER_RANDOM
+        full = T // W
+        spots = [v * W + p for v in range(full) for p in (0, W - 1)] + [full * W]
+        mids = [v * W + p for p in sorted(range(1, W - 1), key=lambda i: abs(i - W // 2)) for v in range(full)]
+        self.spots = spots + mids[:len(directed) - len(spots)]
+        rows = [(rnd.choice(pool(w)), 1, (rnd.randrange(1 << 16) | 1,) + tuple(rnd.randrange(1 << 16) for _ in range(3))) for _ in range(T)]
+        for s, row in zip(self.spots, directed):
+            rows[s] = row
+        self.rows, self.T = rows, T
+        self._ref = None
+
+    def ref(self):
+        if self._ref is None:
+            self._ref = [gmul(self.w, a * digits_scalar(d) % R) if live else None for a, live, d in self.rows]
+        return self._ref
+
+
+_LADDER = {}
+
+
+def ladder_case(w):
+    if w not in _LADDER:
+        _LADDER[w] = LadderCase(w)
+    return _LADDER[w]
+
+
+def run_blame_ladder(lib, case):
+    w, T = case.w, case.T
+    pts = np.frombuffer(b"".join(enc(w, gmul(w, a)) for a, _, _ in case.rows), dtype=np.uint8).copy()
+    live = np.array([l for _, l, _ in case.rows], dtype=np.uint8)
+    digits = np.array([d for _, _, d in case.rows], dtype=np.uint64).reshape(-1)
+    leaves = np.full((T + 1) * LEAF_ROWS[w] * 16, POISON_WORD, dtype=np.int32)
+    rc = lib["ladder"](w - 1, _ptr(pts), _ptr(live), _ptr(digits), T, _ptr(leaves))
+    if rc != 0:
+        raise HipError("%s: the harness returned %d" % (case.tag, rc))
+    return leaves.reshape(T + 1, -1)
+
+
+def check_blame_ladder(case, leaves, max_report=12):
+    bad = []
+    check_leaf_rows(case.w, leaves, case.ref(), case.tag, bad, max_report)
+    return bad
+
+
+# -- the range sums --
+# Out of contract: an EMPTY range (lo == hi).  BlameSearch (tc_blame.h) splits at lo + ((hi - lo + 1) >> 1) and never produces
+# one, and with lo == hi == N in the last job the masked reload of leaf `lo` would read past the leaf buffer; the harnesses
+# refuse such an item instead of launching it, and no table holds one.
+def blame_item_model(mults, lo, hi, parts):
+    """job_blame_range_part (sum_part's share of [lo, hi) per part, one complete addition per term) and k_blame_range_sum's xor
+    tree on multiples mod r: (the sum; the special operands the parts meet as (part, index in the part, kind) -- a term that is the
+    identity, an accumulator back at the identity after the part's first term, equal, opposite --; merge_events' events of the
+    tree; those of them that are NOT an identity that is the sum of a part (or block of parts) without a term)."""
+    n, sums, counts, ev = hi - lo, [], [], []
+    for g in range(parts):
+        k0, k1, _ = msm_part(n, g, parts)
+        acc = 0
+        for i, k in enumerate(range(lo + k0, lo + k1)):
+            t = mults[k] % R
+            kind = "term identity" if t == 0 else None if i == 0 else "acc identity" if acc == 0 else "equal" if acc == t else \
+                "opposite" if (acc + t) % R == 0 else None
+            if kind:
+                ev.append((g, i, kind))
+            acc = (acc + t) % R
+        sums.append(acc)
+        counts.append(k1 - k0)
+    total, mev = merge_events(sums)
+    empty, d, rnd_no = set(), 1, 0
+    while d < parts:
+        empty |= {(rnd_no, g) for g in range(parts) if counts[g] == 0 or counts[g ^ d] == 0}
+        counts, d, rnd_no = [counts[g] + counts[g ^ d] for g in range(parts)], d * 2, rnd_no + 1
+    return total, ev, mev, [e for e in mev if not (e[2] == "identity" and e[:2] in empty)]
+
+
+class Item:
+    """One range [lo, hi) of job `job`.  claims: (parts, "part" / "merge", event) that blame_item_model must confirm; a random
+    item claims that it meets nothing at any parts but the identities of its empty parts."""
+
+    def __init__(self, job, lo, hi, tag, claims=None):
+        self.job, self.lo, self.hi, self.tag, self.claims, self.random = job, lo, hi, tag, claims or [], claims is None
+
+
+def _log2(p):
+    return p.bit_length() - 1
+
+
+class RangeCase:
+    """F = 4 jobs of N = 130 leaves written by the test (leaf_words), about 100 items: ranges of 1 .. 9, 33, 64, 65 and 130
+    leaves side by side in the first wave (lo even, odd, 0 and N - len; the jobs not in order), then directed items, three side
+    by side and then a random one.  Jobs 0 and 1 hold random multiples and serve the random items; every directed item has slots
+    of its own in jobs 2 and 3."""
+
+    def __init__(self, w):
+        self.w, self.tag, self.F, self.N = w, "blame range sums w=%d" % w, BLAME_F, BLAME_N
+        rnd = random.Random("manypoint-" + self.tag)
+        N = self.N
+        self.m = self._slots(rnd, self.F * N)
+        head = []
+        for i, n in enumerate(BLAME_HEAD):
+            lo = (2 * rnd.randrange((N - n) // 2 + 1), min(N - n, 2 * rnd.randrange((N - n) // 2 + 1) + 1), 0, N - n)[i % 4]
+            head.append(Item((i + 1) % 2, lo, lo + n, "head"))
+        while len(head) < 16:
+            head.append(self._random(rnd))
+        directed = [d for s in range(5) for d in self._directed(rnd, s)]
+        items = head
+        for i in range(0, len(directed) - 2, 3):
+            items += directed[i:i + 3] + [self._random(rnd)]
+        items += directed[len(directed) - len(directed) % 3:]
+        while len(items) < 101 or len(items) % 2 == 0:
+            items.append(self._random(rnd))
+        self.items = items
+        self.leaves = np.array([x for m in self.m for x in leaf_words(w, m, rnd)], dtype=np.int32)
+        self._ref = None
+
+    def _slots(self, rnd, count):
+        """`count` distinct multiples with their points: additions of pool points (pool())"""
+        w = self.w
+        base, mults, a = pool(w)[:24], [], pool(w)[-1]
+        while len(mults) < count:
+            b = base[rnd.randrange(24)]
+            pt = E[w].add(_PT[w][a], _PT[w][b])
+            a = (a + b) % R
+            if a and a not in _PT[w]:
+                _PT[w][a] = pt
+                mults.append(a)
+        return mults
+
+    def _random(self, rnd):
+        n = rnd.choice([1, 2, 3, 5, 8, 13, 21, 40, 70, 100])
+        lo = rnd.randrange(self.N - n + 1)
+        return Item(rnd.randrange(2), lo, lo + n, "random")
+
+    def _directed(self, rnd, s):
+        """The directed items of set s, each over slots of its own (jobs 2 and 3), rewritten here."""
+        self._cursor = 2 * self.N if s == 0 else self._cursor + 1  # (the sets start at even and at odd slots)
+        w, N, m = self.w, self.N, self.m
+        out = []
+
+        def region(n):
+            if self._cursor % N + n > N:
+                self._cursor += N - self._cursor % N
+            lo = self._cursor
+            self._cursor += n
+            assert self._cursor <= self.F * N
+            return lo
+
+        def item(vals, tag, claims):
+            lo = region(len(vals))
+            for i, v in enumerate(vals):
+                if v is not None:                     # (None: the random multiple that is there)
+                    m[lo + i] = v % R
+            out.append(Item(lo // N, lo % N, lo % N + len(vals), tag, claims))
+            return lo
+
+        top = MAX_PARTS[w]
+        p, q = rnd.choice(pool(w)), rnd.choice(pool(w))
+        item([0] * 5, "all identities", [(1, "part", (0, 0, "term identity")), (top, "merge", (_log2(top) - 1, 0, "identity"))])
+        item([None] + [0] * 6, "one live leaf, first", [(1, "part", (0, 1, "term identity")), (2, "merge", (0, 0, "identity"))])
+        item([0] * 6 + [None], "one live leaf, last", [(1, "part", (0, 6, "acc identity")), (2, "merge", (0, 0, "identity"))])
+        item([0] * 3 + [None] + [0] * 3, "one live leaf, in the middle", [(1, "part", (0, 3, "acc identity")), (1, "part", (0, 4, "term identity"))])
+        item([p, p], "equal neighbours", [(1, "part", (0, 1, "equal")), (2, "merge", (0, 0, "equal"))])
+        item([p, neg_mult(w, p)], "P, -P", [(1, "part", (0, 1, "opposite")), (2, "merge", (0, 0, "opposite"))])
+        item([q, neg_mult(w, q), None], "P, -P, Q", [(1, "part", (0, 1, "opposite")), (1, "part", (0, 2, "acc identity"))])
+        lo = region(8)
+        m[lo + 7] = -sum(m[lo:lo + 7]) % R
+        out.append(Item(lo // N, lo % N, lo % N + 8, "halves that cancel in the last round",
+                        [(pp, "merge", (_log2(pp) - 1, 0, "opposite")) for pp in REC_PARTS[w][1:]]))
+        lo = region(5)
+        m[lo + 2] = -(m[lo] + m[lo + 1]) % R
+        out.append(Item(lo // N, lo % N, lo % N + 5, "back at the identity in mid-part, and on", [(1, "part", (0, 2, "opposite")), (1, "part", (0, 3, "acc identity"))]))
+        return out
+
+    def mults(self, it):
+        return self.m[it.job * self.N + it.lo:it.job * self.N + it.hi]
+
+    def ref(self):
+        """The expected bytes per item, once: the oracle's encoding of [sum a_k] G."""
+        if self._ref is None:
+            self._ref = [enc(self.w, gmul(self.w, sum(self.mults(it)) % R)) for it in self.items]
+        return self._ref
+
+
+_RANGE = {}
+
+
+def range_case(w):
+    if w not in _RANGE:
+        _RANGE[w] = RangeCase(w)
+    return _RANGE[w]
+
+
+def check_blame_claims(case):
+    """Every directed item meets what it claims, at the parts it names; every random item meets nothing at any parts but the
+    identities of its empty parts.  Returns the list of failures."""
+    bad = []
+    for j, it in enumerate(case.items):
+        ms = case.mults(it)
+        what = "%s item %d (%s, [%d, %d) of job %d)" % (case.tag, j, it.tag, it.lo, it.hi, it.job)
+        for parts in REC_PARTS[case.w]:
+            total, ev, mev, unexplained = blame_item_model(ms, 0, len(ms), parts)
+            if total != sum(ms) % R:
+                bad.append("%s: the model's sum at parts=%d" % (what, parts))
+            if it.random and (ev or unexplained):
+                bad.append("%s: a random item meets %s at parts=%d" % (what, ev + unexplained, parts))
+            for cp, where, event in it.claims:
+                if cp == parts and event not in (ev if where == "part" else mev):
+                    bad.append("%s: claims %s %s at parts=%d, the model meets %s / %s" % (what, where, event, parts, ev, mev))
+    return bad
+
+
+def _items_in(items):
+    return [np.array([getattr(it, f) for it in items], dtype=np.uint32) for f in ("job", "lo", "hi")]
+
+
+def run_blame_range(lib, case, parts):
+    """(out: n_items rows and two guard rows) as the leg left them."""
+    w, n = case.w, len(case.items)
+    job, lo, hi = _items_in(case.items)
+    out = np.full((n + 2) * PT_BYTES[w], POISON, dtype=np.uint8)
+    rc = lib["range_sum"](w - 1, _ptr(case.leaves), case.F, case.N, _ptr(job), _ptr(lo), _ptr(hi), n, parts, _ptr(out))
+    if rc != 0:
+        raise HipError("%s parts=%d: the harness returned %d" % (case.tag, parts, rc))
+    return (out.reshape(n + 2, -1),)
+
+
+def check_sum_rows(case, what0, out, want, bad):
+    """out: len(want) rows and two guard rows.  No item is skipped."""
+    if not (out[len(want):] == POISON).all():
+        bad.append("%s: the guard rows behind the sums written" % what0)
+    for j, it in enumerate(case.items):
+        if bytes(out[j]) != want[j]:
+            bad.append("%s item %d (%s, [%d, %d) of job %d): wrong output bytes" % (what0, j, it.tag, it.lo, it.hi, it.job))
+
+
+def check_blame_range(case, parts, res, max_report=12):
+    bad = []
+    check_sum_rows(case, "%s parts=%d" % (case.tag, parts), res[0], case.ref(), bad)
+    return bad
+
+
+# -- k_blame_leaves -> k_blame_range_sum, the leaves staying where the first kernel left them --
+class ChainCase:
+    def __init__(self, w):
+        self.w, self.N = w, 130
+        self.leaves = leaves_case(w, *LEAVES_SHAPES[4])
+        assert self.leaves.n == self.N and self.leaves.period == 0
+        self.tag = "blame chain w=%d" % w
+        rnd = random.Random("manypoint-" + self.tag)
+        spans = [(0, 130), (0, 1), (129, 130), (1, 66), (63, 129), (64, 128), (19, 23), (127, 130), (31, 33)]
+        spans += [tuple(sorted(rnd.sample(range(131), 2))) for _ in range(12)]
+        self.items = [Item(0, lo, hi, "chain") for lo, hi in spans]
+        self.parts = [0, 1, 8, MAX_PARTS[w], 3]
+        self._ref = None
+
+    def mults(self, it):
+        return self.leaves.ref()[1][it.lo:it.hi]
+
+    def ref(self):
+        if self._ref is None:
+            self._ref = [enc(self.w, gmul(self.w, sum(self.mults(it)) % R)) for it in self.items]
+        return self._ref
+
+
+_CHAIN = {}
+
+
+def chain_case(w):
+    if w not in _CHAIN:
+        _CHAIN[w] = ChainCase(w)
+    return _CHAIN[w]
+
+
+def run_blame_chain(lib, case, parts):
+    """(out: n_items rows and two guard rows, seed, live bytes with the guard byte) as the leg left them."""
+    w, lc, n = case.w, case.leaves, len(case.items)
+    pts, live_in, key, seed, live_out = _leaves_in(lc)
+    _, lo, hi = _items_in(case.items)
+    out = np.full((n + 2) * PT_BYTES[w], POISON, dtype=np.uint8)
+    rc = lib["chain"](w - 1, _ptr(key), lc.call, lc.leaf0, _ptr(pts), len(lc.a), lc.period, _ptr(live_in), lc.n, _ptr(lo), _ptr(hi), n, parts,
+                      _ptr(seed), _ptr(live_out), _ptr(out))
+    if rc != 0:
+        raise HipError("%s parts=%d: the harness returned %d" % (case.tag, parts, rc))
+    return out.reshape(n + 2, -1), seed, live_out
+
+
+def check_blame_chain(case, parts, res, max_report=12):
+    out, seed, live = res
+    want_seed, _, _, want_live = case.leaves.ref()
+    bad = []
+    if bytes(seed) != want_seed or live.tolist() != want_live:
+        bad.append("%s parts=%d: seed or live bytes" % (case.tag, parts))
+    check_sum_rows(case, "%s parts=%d" % (case.tag, parts), out, case.ref(), bad)
+    return bad
+
+
+# -- blame_sum_parts --
+SUM_PARTS_TABLE = [(w, n_items, longest, cus) for w in (1, 2) for n_items in (1, 65536) for longest in (1, 2, 3, 4, 127, 128, 200) for cus in (0, 1, 256)]
+
+
+def blame_sum_parts_model(w, n_items, longest, cus):
+    """The documented rule: the smallest power of two of lanes (G2: lane pairs) per item that gives the launch one wave per SIMD
+    (4 SIMDs on each of `cus` CUs; 256 CUs when cus is not positive), at most half the longest range and at most a wave."""
+    want = (cus if cus > 0 else 256) * 4 * MAX_PARTS[w]  # lanes (lane pairs) of one wave per SIMD
+    need = 1
+    while n_items * need < want:
+        need *= 2
+    half = 1
+    while half * 2 * 2 <= longest:
+        half *= 2
+    return min(need, half, MAX_PARTS[w])

@@ -7,7 +7,6 @@ and a range that is all identities."""
 import ctypes
 import os
 import random
-import struct
 import subprocess
 import sys
 
@@ -15,12 +14,13 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import tc_oracle as o  # noqa: E402
+from manypoint_conformance import BLAME_KEY as KEY, blame_call_seed as call_seed, blame_scalar as scalar  # noqa: E402  (the suite's helpers)
 
 CSRC = os.path.join(ROOT, "threshold_crypto_amd", "csrc")
 SRC = os.path.join(ROOT, "tests", "blame", "blame_dev_host.cpp")
 N = 5
-KEY = bytes((3 * i + 1) & 0xff for i in range(32))
 BAD_POINT = {0: bytes([0x1f]) + b"\xff" * 95, 1: bytes([0x1f]) + b"\xff" * 191}     # x >= p: no decoder takes it
 
 
@@ -43,16 +43,6 @@ def L():
     lib.bdh_leaves.argtypes = [ctypes.c_int, ctypes.c_char_p, u64, ctypes.c_char_p, sz, vp, sz, vp]
     lib.bdh_range_sum.argtypes = [ctypes.c_int, vp, sz, sz, sz, ctypes.c_char_p]
     return lib
-
-
-def call_seed(key, call):
-    return struct.pack("<8I", *o.chacha20_block(struct.unpack("<8I", key), call)[:8])
-
-
-def scalar(seed, leaf):
-    w0, w1 = o.chacha20_block(struct.unpack("<8I", seed), leaf)[:2]
-    d = [(w0 & 0xffff) | 1, w0 >> 16, w1 & 0xffff, w1 >> 16]
-    return d, d[0] + d[1] * o.BLS_X + d[2] * o.BLS_X ** 2 + d[3] * o.BLS_X ** 3
 
 
 def test_seed_and_digits_are_the_oracles_chacha20(L):

@@ -13,7 +13,10 @@ share = 1 .. 8 of the comb and several workgroups with a ragged tail; the ragged
 sums of the decryption-share verifier (k_rec_*_g1_pair: A_j and -B_j byte for byte in the shipped 32-bit mode and at full
 width, half 1's tables and codes behind all of half 0's); the G1 comb of the decryption shares (k_comb_tables_g1 /
 k_comb_decrypt) at share = 0 .. 8 over one wave and over 70 ciphertexts, with its 514-entry tables, and k_g1_mul_gather over the
-same case.  Invalid encodings are ordinary data; after a HIP error nothing more is launched."""
+same case; the blame-by-bisection kernels of k_blame.hip through tests/device/manypoint_blame.hip (leaves at n = 1 .. 130 with
+leaf numbers across 2^32, the leaf ladders at chosen digits, range sums over 101 ranges of 1 .. 130 leaves at parts = 0 .. 64
+and twice that, leaves chained into range sums on the device, blame_sum_parts).  Invalid encodings are ordinary data; after a
+HIP error nothing more is launched."""
 import os
 import sys
 
@@ -162,3 +165,54 @@ def test_g1_mul_gather_leaves_the_bytes_of_the_comb(lib):
     assert not bad, "\n".join(bad[:12])
     comb = _launch(mp.run_comb1, lib, case, 8)
     assert (out == comb[0]).all() and (status == comb[1]).all()
+
+
+# ---- blame by bisection (k_blame.hip), through tests/device/manypoint_blame.hip ----
+@pytest.fixture(scope="module")
+def blame():
+    if _state.get("blame") is None:
+        _state["blame"] = mp.load_blame(mp.build_device_blame(), "mp_")
+    return _state["blame"]
+
+
+@pytest.mark.parametrize("w,shape", [(w, s) for w in (1, 2) for s in mp.LEAVES_SHAPES])
+def test_blame_leaves(blame, w, shape):
+    """launch_blame_seed + launch_blame_leaves with a fresh arena: the seed, every leaf decoded from its raw words ([r_i] P_i, Z = 0
+    for a dead slot, limb range, |value| <= 2.1 p, padding words, the c0 / c1 rows), the live bytes, the guard row and byte, every
+    arena slot free again -- ragged last waves, leaf numbers across 2^32, the three forms of period / live."""
+    case = mp.leaves_case(w, *shape)
+    bad = mp.check_blame_leaves(case, _launch(mp.run_blame_leaves, blame, case))
+    assert not bad, "\n".join(bad[:12])
+
+
+@pytest.mark.parametrize("w", [1, 2])
+def test_blame_ladder_at_chosen_digits(blame, w):
+    """blame_leaf_g1 / blame_leaf_g2 at digits ChaCha20 gives with probability 2^-16 or less: zeros, all ones, k2 = 0."""
+    case = mp.ladder_case(w)
+    bad = mp.check_blame_ladder(case, _launch(mp.run_blame_ladder, blame, case))
+    assert not bad, "\n".join(bad[:12])
+
+
+@pytest.mark.parametrize("w", [1, 2])
+def test_blame_range_sum(blame, w):
+    """k_blame_range_sum through launch_blame_range_sum over leaves written by the test: parts = 0 (blame_sum_parts), every power
+    of two up to a wave's worth -- most lanes of a short range are then empty and run masked trips only --, then 3 and twice the
+    maximum (run as 1): the oracle's bytes for every item, the guard rows, the same bytes at every parts."""
+    case = mp.range_case(w)
+    mp.sweep(blame, case, mp.run_blame_range, mp.check_blame_range, mp.BLAME_PARTS[w], "parts", _launch)
+
+
+@pytest.mark.parametrize("w", [1, 2])
+def test_blame_leaves_then_range_sum(blame, w):
+    """k_blame_leaves -> k_blame_range_sum in one entry, over the leaves where the first kernel left them (n = 130, leaf numbers
+    across 2^32)."""
+    case = mp.chain_case(w)
+    mp.sweep(blame, case, mp.run_blame_chain, mp.check_blame_chain, case.parts, "parts", _launch)
+
+
+def test_blame_sum_parts(blame):
+    for w, n_items, longest, cus in mp.SUM_PARTS_TABLE:
+        got = blame["sum_parts"](w - 1, n_items, longest, cus)
+        what = (w, n_items, longest, cus, got)
+        assert got == mp.blame_sum_parts_model(w, n_items, longest, cus), what
+        assert got >= 1 and got & (got - 1) == 0 and got <= mp.MAX_PARTS[w] and (got == 1 or 2 * got <= longest), what

@@ -17,6 +17,10 @@ signer.
     and the host leg (rec_pair_chunk / _place / _lane / _out as the kernels use them, the negated half) runs every table.
 (g) The G1 comb of the decryption shares: the model of the doubling-free pass (only the scalar 0 meets a special case), the
     directed placements each case claims per share (by the kernel's lane order), and the host leg at share = 1 .. 8.
+(h) Blame by bisection (k_blame.hip): tests/device/manypoint_blame.hip cross-compiles; the tables hold what the kernels' text needs
+    (ragged waves, leaf numbers across 2^32, dead slots first / last / in mid-wave, directed digit rows at lane 0 / last / middle,
+    the head of ranges, no empty range); the suite's leaf encoder and decoder agree; every directed range meets what it claims and
+    random ones meet only the identities of their empty parts; the host leg runs leaves, ladders, range sums and the chain.
 """
 import ctypes
 import os
@@ -452,3 +456,136 @@ def test_comb_g1_model_and_cases():
 def test_host_comb_g1(host, n, B):
     case = mp.comb1_case(n, B)
     mp.sweep(host, case, mp.run_comb1, mp.check_comb1, case.shares[1:], "share")  # (share = 0, the launcher's choice: the device leg)
+
+
+# ---- blame by bisection (k_blame.hip; tc_blame_jobs.h) --------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def bhost():
+    return mp.load_blame(mp.build_host(), "mph_")
+
+
+def test_blame_kernels_cross_compile_for_gfx950():
+    lib = mp.build_device_blame()
+    with open(lib, "rb") as f:
+        text = f.read()
+    for name in (b"mp_blame_leaves", b"mp_blame_range_sum", b"mp_blame_chain", b"mp_blame_ladder", b"mp_blame_sum_parts", b"k_blame_seed",
+                 b"k_blame_leaves", b"k_blame_range_sum", b"k_mp_blame_ladder"):
+        assert name in text, name
+
+
+def test_blame_tables_have_the_shapes_the_kernels_need():
+    for w in (1, 2):
+        W = mp.WAVE_LEAVES[w]
+        assert [s[0] for s in mp.LEAVES_SHAPES[:5]] == [1, 33, 64, 65, 130] and {s[1] for s in mp.LEAVES_SHAPES} >= {0, 2 ** 32 - 3}
+        assert mp.LEAVES_SHAPES[5:] == [(130, 0, 52, False), (130, 7 * 52, 52, True)]
+        cases = [mp.leaves_case(w, *s) for s in mp.LEAVES_SHAPES]
+        assert {c.call for c in cases} == {0, 1, 2 ** 40 + 3}
+        c = cases[4]   # n = 130 with a live array: every kind first, last and in the middle of a wave
+        first = {c.kind(r) for r in range(0, 130, W)}
+        last = {c.kind(r) for r in list(range(W - 1, 130, W)) + [129]}
+        mid = {c.kind(v * W + W // 2 - 3 + 3 * j) for v in range(130 // W) for j in range(3)}
+        assert first >= set(c.KINDS) and last >= set(c.KINDS) and mid >= set(c.KINDS), (first, last, mid)
+        if w == 2:   # both of a wave's last lane pairs
+            assert all(c.kind(v * W + W - 2) != "point" and c.kind(v * W + W - 1) != "point" for v in range(4))
+        assert c.leaf0 < 2 ** 32 < c.leaf0 + c.n and c.live[21] == 0xff and c.live[20] == 0 and c.a[20] is None
+        st = c.ref()
+        assert st[3][20] == 0 and st[3][21] == 0xff and st[3][130] == mp.POISON
+        cleared = [r for r in range(130) if c.live[r] and not st[3][r]]
+        assert cleared and all(c.kind(r) == "bad" for r in cleared) and sum(m != 0 for m in st[1]) > 100
+        assert cases[5].live is None and {cases[5].kind(r) for r in range(130)} == {"point", "identity", "bad"}
+        assert {cases[6].kind(r) for r in range(130)} == {"point", "identity", "bad", "not live"} and len(cases[6].a) == 52
+        # the ladder rows
+        lc = mp.ladder_case(w)
+        assert lc.T == 69 and [d for d in mp.LADDER_DIGITS if d[0] % 2 == 0] == []
+        directed = {s: lc.rows[s] for s in lc.spots}
+        assert len(directed) == 21 and {0, W - 1, (lc.T // W) * W} <= set(directed) and any(abs(s % W - W // 2) <= 1 for s in directed)
+        for d in mp.LADDER_DIGITS:
+            assert sorted((a != 0, live) for a, live, dd in directed.values() if dd == d) == [(False, 1), (True, 0), (True, 1)], d
+        assert len({r[2] for r in lc.rows}) == 7 + mp.LADDER_RANDOM and all(r[2][0] & 1 for r in lc.rows)
+        for v in range(0, lc.T, W):   # the rows of a wave all differ
+            assert len(set(lc.rows[v:v + W])) == len(lc.rows[v:v + W])
+        # the range sums
+        rc = mp.range_case(w)
+        n = len(rc.items)
+        assert n >= 100 and all(n % (W // p) for p in mp.REC_PARTS[w] if W // p > 1)
+        assert [it.hi - it.lo for it in rc.items[:13]] == mp.BLAME_HEAD and all(it.random for it in rc.items[:16])
+        head = rc.items[:13]
+        assert any(it.lo % 2 == 0 and it.lo for it in head) and any(it.lo % 2 for it in head) and any(it.lo == 0 for it in head)
+        assert any(it.hi == rc.N and it.lo for it in head) and [it.job for it in head[:4]] == [1, 0, 1, 0]
+        assert all(0 <= it.lo < it.hi <= rc.N and it.job < rc.F for it in rc.items)          # no empty range: outside the contract
+        for i in range(16, 16 + 4 * 15, 4):
+            assert [it.random for it in rc.items[i:i + 4]] == [False, False, False, True], i
+        assert {it.tag for it in rc.items} >= {"all identities", "one live leaf, first", "one live leaf, last", "one live leaf, in the middle",
+                                               "equal neighbours", "P, -P", "P, -P, Q", "halves that cancel in the last round",
+                                               "back at the identity in mid-part, and on"}
+        want = rc.ref()
+        ident = mp.enc(w, None)
+        for it, o_ in zip(rc.items, want):
+            assert (o_ == ident) == (it.tag in ("all identities", "P, -P", "halves that cancel in the last round")), it.tag
+        assert rc.leaves.size == rc.F * rc.N * mp.LEAF_ROWS[w] * 16 and len(set(rc.m[:2 * rc.N])) == 2 * rc.N
+        assert mp.BLAME_PARTS[w] == [0] + [p for p in (1, 2, 4, 8, 16, 32, 64) if p <= W] + [3, 2 * W]
+
+
+def test_leaf_words_decode_to_their_point():
+    """The test's own leaf encoder against the leaf decoder: both representatives, a random Z, the identity as (0, 1, 0)."""
+    rnd = random.Random(11)
+    for w in (1, 2):
+        for m in [0] + mp.pool(w)[:6]:
+            bad = []
+            row = mp.leaf_words(w, m, rnd)
+            assert len(row) == mp.LEAF_ROWS[w] * 16 and mp.leaf_point(w, row, "leaf", bad) == mp.gmul(w, m) and not bad
+        rows = [mp.leaf_words(w, mp.pool(w)[0], rnd) for _ in range(8)]
+        assert len({tuple(r) for r in rows}) == 8   # (another Z, another representative)
+        assert any(dc.value(r[:14]) >= mp.P for r in rows) and any(dc.value(r[:14]) < mp.P for r in rows)
+        bad = []
+        mp.leaf_point(w, mp.leaf_words(w, 5, rnd)[:-1] + [1], "leaf", bad)
+        assert bad
+
+
+def test_blame_items_hit_what_they_claim_and_random_ones_hit_nothing():
+    for w in (1, 2):
+        case = mp.range_case(w)
+        assert not mp.check_blame_claims(case), case.tag
+        assert sum(bool(it.claims) for it in case.items) == 45
+    # the model itself: parts beyond the terms leave parts without a term, whose identities are explained, and only those
+    total, ev, mev, unexplained = mp.blame_item_model([5, 7, 11], 0, 3, 8)
+    assert total == 23 and not ev and not unexplained and {e[2] for e in mev} == {"identity"}
+    assert mp.blame_item_model([5, 0, 11], 0, 3, 1)[1] == [(0, 1, "term identity")]
+    assert mp.blame_item_model([5, 0, 11], 0, 3, 4)[3]                                # the identity of a part WITH a term is not
+    assert mp.blame_item_model([5, 5], 0, 2, 2)[3] == [(0, 0, "equal"), (0, 1, "equal")]
+
+
+@pytest.mark.parametrize("w,shape", [(w, s) for w in (1, 2) for s in mp.LEAVES_SHAPES])
+def test_host_blame_leaves(bhost, w, shape):
+    case = mp.leaves_case(w, *shape)
+    bad = mp.check_blame_leaves(case, mp.run_blame_leaves(bhost, case))
+    assert not bad, "\n".join(bad[:12])
+
+
+@pytest.mark.parametrize("w", [1, 2])
+def test_host_blame_ladder_at_chosen_digits(bhost, w):
+    case = mp.ladder_case(w)
+    bad = mp.check_blame_ladder(case, mp.run_blame_ladder(bhost, case))
+    assert not bad, "\n".join(bad[:12])
+
+
+@pytest.mark.parametrize("w", [1, 2])
+def test_host_blame_range_sum(bhost, w):
+    """Every parts gives the oracle's bytes for every item -- parts beyond the terms, 3 and twice the maximum (run as 1) too."""
+    case = mp.range_case(w)
+    mp.sweep(bhost, case, mp.run_blame_range, mp.check_blame_range, mp.BLAME_PARTS[w][1:], "parts")  # (0, blame_sum_parts: the device leg)
+
+
+@pytest.mark.parametrize("w", [1, 2])
+def test_host_blame_chain(bhost, w):
+    case = mp.chain_case(w)
+    mp.sweep(bhost, case, mp.run_blame_chain, mp.check_blame_chain, case.parts[1:], "parts")
+
+
+def test_blame_sum_parts_model_is_the_documented_rule():
+    """(the product's blame_sum_parts is compared with this model in the GPU leg: it lives in k_blame.hip)"""
+    assert len(mp.SUM_PARTS_TABLE) == 2 * 2 * 7 * 3
+    assert mp.blame_sum_parts_model(1, 101, 130, 0) == 64 and mp.blame_sum_parts_model(2, 101, 130, 0) == 32
+    assert mp.blame_sum_parts_model(1, 1, 127, 256) == 32 and mp.blame_sum_parts_model(1, 65536, 200, 1) == 1
+    assert mp.blame_sum_parts_model(2, 65536, 200, 256) == 1 and mp.blame_sum_parts_model(1, 65536, 200, 256) == 1
+    assert [mp.blame_sum_parts_model(1, 1, n, 0) for n in (1, 2, 3, 4, 127, 128, 200)] == [1, 1, 1, 2, 32, 64, 64]
