@@ -433,7 +433,6 @@ TC_HD QuotNaf quot_naf(const int64_t* c) {
 }
 // (measured over the 138 generic 4-of-10 subsets, multiply-adds of the division: plain NAF 752 k, width 3 702 k, width 4 713 k)
 constexpr int kQuotWidth = 3;                      // of the NAF of q: the odd multiples P1 .. (2^(W-1) - 1) P1
-constexpr int kQuotTable = 1 << (kQuotWidth - 2);  // entries 2 .. of the lane pair's arena table; 0, 1: Q and psi(Q)
 // column `bit` of sum_j c_j psi^j(B) into acc, B and psi(B) in entries 0 and 1:  psi^2(x, y) = (PSI2_CX x, -y)
 TC_HD void quot_add_bases(G2Jac& acc, bool& started, bool& exc, const tbl_word* mem, const QuotNaf& n, int bit) {
   TC_NOUNROLL for (int j = 0; j < 4; j++) {
@@ -451,9 +450,48 @@ TC_HD void quot_add_bases(G2Jac& acc, bool& started, bool& exc, const tbl_word* 
     }
   }
 }
-// [q] T(psi) P + E(psi) P for wave-uniform q, T, E (combine_quotient_decompose).  Generic additions only: a lane that may
-// have met a special case raises exc and the caller redoes its multiplication with the complete form.
-TC_HD G2Jac g2_quotient_mul(const G2Jac& p, uint64_t q, const int64_t* T, const int64_t* E, bool& exc) {
+// the nonzero columns of the NAF of |c| (naf_recode: pos | neg)
+TC_HD uint64_t naf_columns(int64_t c) {
+  const uint64_t c1 = (uint64_t)(c < 0 ? -c : c), h = c1 >> 1;
+  return h ^ (c1 + h);  // (c ^ 3 c) >> 1 with floor(3 c / 2) = c + floor(c / 2): 64 bits hold it for every |c| < 2^63
+}
+// weight and top column of wnaf_recode<W>(d) without the digits, for every d: one step per nonzero digit.  An odd d leaves the
+// digit d mods 2^W and (d - digit) / 2^W = floor(d / 2^W) + bit W - 1 of d, which is d / 2^(W-1) halved and rounded up (shifts and
+// one addition, nothing leaves 64 bits: scalar instructions for a wave-uniform d).  Width 2 is the NAF: below 2^63 its columns
+// at once.
+template <int W>
+TC_HD void wnaf_shape(uint64_t d, int* nz, int* top) {
+  if (W == 2 && (d >> 63) == 0) {
+    const uint64_t c = naf_columns((int64_t)d);
+    *nz = __builtin_popcountll(c);
+    *top = c ? 63 - (int)__builtin_clzll(c) : 0;
+    return;
+  }
+  int n = 0, zeros = 0;
+  TC_NOUNROLL while (d) {
+    const int z = __builtin_ctzll(d);
+    d >>= z;  // (two shifts: z + W - 1 may reach 64)
+    d = ((d >> (W - 1)) + 1) >> 1;
+    zeros += z;
+    n++;
+  }
+  *nz = n;
+  *top = n ? zeros + (n - 1) * W : 0;  // the last digit's column: the zeros skipped and W columns per digit before it
+}
+// the odd multiples P1, 3 P1 .. (2N - 1) P1 of (X, Y) of p1 into entries 2 .. of the lane pair's table; returns the factor of
+// their curve over the one scaled by p1.z
+template <int N>
+TC_HD Fq2 quot_store_multiples(const G2Jac& p1, tbl_word* mem) {
+  G2Affine tab[N];
+  const Fq2 zs = g2_odd_multiples<N>(G2Affine{p1.x, p1.y, false}, tab);
+  TC_NOUNROLL for (int m = 0; m < N; m++) tbl_store_g2(mem + (2 + m) * kTblEntryWords, tab[m]);
+  return zs;
+}
+// [q] T(psi) P + E(psi) P for wave-uniform q, T, E (combine_quotient_decompose) and a wave-uniform width 2, 3 or 4 of the NAF of
+// q: the odd multiples P1 .. (2^(width-1) - 1) P1 stand in entries 2 .. 5 of the lane pair's 8-entry arena table, width 2 needs
+// P1 alone.  Generic additions only: a lane that may have met a special case raises exc and the caller redoes its
+// multiplication with the complete form.
+TC_HD G2Jac g2_quotient_mul_width(const G2Jac& p, uint64_t q, const int64_t* T, const int64_t* E, int width, bool& exc) {
   // a real Z (g2_gls_digits_mul above): P and psi(P) are affine points of one curve
   const Fq2 l = p.z.conj();
   const Fq2 l2 = l.sqr();
@@ -474,10 +512,16 @@ TC_HD G2Jac g2_quotient_mul(const G2Jac& p, uint64_t q, const int64_t* T, const 
   }
   exc = exc || !started;
   // (X, Y) of P1 is an affine point of the curve scaled once more by its Z; its odd multiples by a further factor
-  G2Affine tab[kQuotTable];
-  const Fq2 s = coord_norm(acc.z * g2_odd_multiples<kQuotTable>(G2Affine{acc.x, acc.y, false}, tab));
+  Fq2 s;
+  if (width == 2) {
+    tbl_store_g2(mem + 2 * kTblEntryWords, G2Affine{acc.x.reduce_value(), acc.y.reduce_value(), false});
+    s = acc.z;
+  } else if (width == 3) {
+    s = coord_norm(acc.z * quot_store_multiples<2>(acc, mem));
+  } else {
+    s = coord_norm(acc.z * quot_store_multiples<4>(acc, mem));
+  }
   exc = exc || maybe_zero56(s);
-  TC_NOUNROLL for (int m = 0; m < kQuotTable; m++) tbl_store_g2(mem + (2 + m) * kTblEntryWords, tab[m]);
   // the bases move onto that curve for the digits of E, which join the low columns of the ladder of q
   const Fq2 s2 = s.sqr();
   const Fq2 s3 = s2 * s;
@@ -485,7 +529,9 @@ TC_HD G2Jac g2_quotient_mul(const G2Jac& p, uint64_t q, const int64_t* T, const 
   const QuotNaf ne = quot_naf(E);
   const uint64_t any_e = ne.any();
   int8_t dig[kWnafCols];
-  wnaf_recode<kQuotWidth>(q, dig);
+  if (width == 2) wnaf_recode<2>(q, dig);
+  else if (width == 3) wnaf_recode<3>(q, dig);
+  else wnaf_recode<4>(q, dig);
   int top = any_e ? 63 - (int)__builtin_clzll(any_e) : 0;
   TC_NOUNROLL for (int col = kWnafCols - 1; col > top; col--)
     if (dig[col]) top = col;
@@ -511,6 +557,10 @@ TC_HD G2Jac g2_quotient_mul(const G2Jac& p, uint64_t q, const int64_t* T, const 
   acc.z = coord_norm(acc.z * s);
   acc.z = coord_norm(acc.z.scale(zn));
   return acc;
+}
+// the same at the width every denominator took before the digits were planned (tc_jobs.h combine_quotient_plan)
+TC_HD G2Jac g2_quotient_mul(const G2Jac& p, uint64_t q, const int64_t* T, const int64_t* E, bool& exc) {
+  return g2_quotient_mul_width(p, q, T, E, kQuotWidth, exc);
 }
 
 // [|x|] P by the 64-bit ladder (|x| has Hamming weight 6: 63 doublings, 5 additions)

@@ -303,6 +303,8 @@ TC_HD_NOINLINE G2Jac combine_divide_uniform(const G2Jac& q, uint64_t d_abs, bool
 
 // The same through the quotient of |x| by D (tc_gls.h combine_quotient_decompose): one ladder over q = |x| / D on a point
 // made from coefficients as short as D.  d_abs must be one the decomposition takes (combine_divide_takes_quotient).
+// (This entry, combine_divide_quotient_macs and combine_divide_takes_quotient keep the chain of m = 0, width 3 for the conformance
+// suite, which pins it digit by digit; no kernel calls them: a wave runs combine_divide_cheapest below.)
 TC_HD_NOINLINE G2Jac combine_divide_quotient(const G2Jac& q, uint64_t d_abs, bool& exc) {
   uint64_t qq = 0;
   int64_t T[4] = {0, 0, 0, 0}, E[4] = {0, 0, 0, 0};
@@ -327,15 +329,13 @@ TC_HD uint32_t combine_divide_uniform_macs(uint64_t d_abs) {
   uint64_t d[4];
   gls_decompose(dinv, d);
   int top = 0, nz = 0, nz2 = 0;  // nz2: look-ups that take psi^2 of an entry
+  // (the weight and the top column of each digit's width-4 NAF, tc_gls.h wnaf_shape: the digits themselves are not needed here)
   TC_NOUNROLL for (int j = 0; j < 4; j++) {
-    int8_t dig[kWnafCols];
-    wnaf4_recode(d[j], dig);
-    TC_NOUNROLL for (int col = 0; col < kWnafCols; col++)
-      if (dig[col]) {
-        nz++;
-        nz2 += j >> 1;
-        if (col > top) top = col;
-      }
+    int n = 0, t = 0;
+    wnaf_shape<4>(d[j], &n, &t);
+    nz += n;
+    nz2 += (j >> 1) * n;
+    if (t > top) top = t;
   }
   return kMacsUniformFixed + (uint32_t)top * kMacsDbl + (uint32_t)(nz - 1) * kMacsAdd + (uint32_t)nz2 * kMacsPsi2;
 }
@@ -357,9 +357,124 @@ TC_HD uint32_t combine_divide_quotient_macs(uint64_t q, const int64_t* T, const 
   top += nt.any() ? 63 - (int)__builtin_clzll(nt.any()) : 0;
   return kMacsQuotientFixed + (uint32_t)top * kMacsDbl + (uint32_t)(nz - 2) * kMacsAdd + (uint32_t)nz2 * kMacsPsi2;
 }
+// The digits of the quotient form are free in two ways: for any integer m
+//     D^-1 = sum_j (T_j (q + m) + (E_j - m T_j)) psi^j  (mod r),
+// so the ladder may run over q + m with E' = E - m T, and any NAF width may recode q + m.  The plan is the cheapest of
+// m in {0, 1} -- the two integers next to |x| / D: m = 1 rounds it up, and E' is about a bit shorter when |x| mod D > D / 2; any
+// other m moves q + m away from |x| / D and lengthens E' by |m T| -- x width in {2, 3, 4} (the odd multiples of width 4 and the
+// two bases fill 6 of the 8 entries of the lane pair's arena table) by the multiply-adds g2_quotient_mul_width executes, counted
+// as combine_divide_quotient_macs counts them: what the widths execute besides the doublings and additions (P1 alone; P1, 3 P1;
+// P1 .. 7 P1 on a common Z) is kMacsQuotientFixedOf[width - 2].  Ties go to m = 0, width 3, the chain before the plan.
+// q + m >= q >= 3 and |E'_j| <= D + 2 < 2^63 stay inside what the ladder accepts.  A function of (q, T, E) alone: wave-uniform,
+// scalar work, one loop step per nonzero digit of the four width-3 and width-4 candidates (DESIGN 4.12 has the count).
+constexpr int kQuotPlanShiftLo = 0, kQuotPlanShiftHi = 1;
+static_assert(kQuotPlanShiftLo == 0, "combine_quotient_plan starts from E and q themselves");
+constexpr uint32_t kMacsQuotientFixedOf[3] = {15890, kMacsQuotientFixed, 85666};
+struct QuotPlan {
+  int m, width;
+  uint32_t macs;
+};
+// the additions and psi^2 look-ups of the NAFs of four coefficients of psi^j, and their top column
+struct QuotCoeffCost {
+  uint32_t macs;
+  int top;
+};
+TC_HD QuotCoeffCost quot_coeff_cost(const int64_t* c) {
+  uint64_t any = 0;
+  int nz = 0, nz2 = 0;
+  TC_UNROLL for (int j = 0; j < 4; j++) {
+    const uint64_t cols = naf_columns(c[j]);
+    const int n = __builtin_popcountll(cols);
+    any |= cols;
+    nz += n;
+    nz2 += (j >> 1) * n;
+  }
+  return QuotCoeffCost{(uint32_t)nz * kMacsAdd + (uint32_t)nz2 * kMacsPsi2, any ? 63 - (int)__builtin_clzll(any) : 0};
+}
+// the ladder of q at width W beside E digits that reach column top_e: the table, the doublings, the additions of q's digits
+template <int W>
+TC_HD uint32_t quot_ladder_macs(uint64_t q, int top_e) {
+  int nz, top;
+  wnaf_shape<W>(q, &nz, &top);
+  if (top < top_e) top = top_e;
+  return kMacsQuotientFixedOf[W - 2] + (uint32_t)top * kMacsDbl + (uint32_t)nz * kMacsAdd;
+}
+// one candidate, whatever m and width (the host tests force candidates the planner does not look at)
+TC_HD uint32_t combine_quotient_candidate_macs(uint64_t q, const int64_t* T, const int64_t* E, int m, int width) {
+  int64_t Em[4];
+  TC_UNROLL for (int j = 0; j < 4; j++) Em[j] = E[j] - (int64_t)m * T[j];
+  const QuotCoeffCost ct = quot_coeff_cost(T), ce = quot_coeff_cost(Em);
+  const uint64_t qm = q + (uint64_t)(int64_t)m;
+  const uint32_t ladder = width == 2 ? quot_ladder_macs<2>(qm, ce.top) : width == 3 ? quot_ladder_macs<3>(qm, ce.top) : quot_ladder_macs<4>(qm, ce.top);
+  return (uint32_t)ct.top * kMacsDbl + ct.macs - 2 * kMacsAdd + ce.macs + ladder;
+}
+#if !defined(__HIPCC__)
+inline int g_tc_force_quot_plan = 0;  // host test build: 16 (m + 8) + width = that plan, whatever it costs; 0 = the cheapest
+#endif
+TC_HD QuotPlan combine_quotient_plan(uint64_t q, const int64_t* T, const int64_t* E) {
+#if !defined(__HIPCC__)
+  if (g_tc_force_quot_plan) {
+    const int m = g_tc_force_quot_plan / 16 - 8, width = g_tc_force_quot_plan % 16;
+    return QuotPlan{m, width, combine_quotient_candidate_macs(q, T, E, m, width)};
+  }
+#endif
+  // what no candidate changes: the ladder of P1 = T(psi) P
+  const QuotCoeffCost ct = quot_coeff_cost(T);
+  const uint32_t base = (uint32_t)ct.top * kMacsDbl + ct.macs - 2 * kMacsAdd;
+  QuotPlan best{0, kQuotWidth, 0xffffffffu};
+  int64_t Em[4] = {E[0], E[1], E[2], E[3]};
+  // (m = 0 first, then width 3 first: a later candidate replaces the plan only when it is strictly cheaper)
+  TC_UNROLL for (int m = kQuotPlanShiftLo; m <= kQuotPlanShiftHi; m++) {
+    const QuotCoeffCost ce = quot_coeff_cost(Em);
+    const uint64_t qm = q + (uint64_t)m;
+    const uint32_t fixed_m = base + ce.macs;
+    const uint32_t w3 = fixed_m + quot_ladder_macs<3>(qm, ce.top), w2 = fixed_m + quot_ladder_macs<2>(qm, ce.top), w4 = fixed_m + quot_ladder_macs<4>(qm, ce.top);
+    if (w3 < best.macs) best = QuotPlan{m, 3, w3};
+    if (w2 < best.macs) best = QuotPlan{m, 2, w2};
+    if (w4 < best.macs) best = QuotPlan{m, 4, w4};
+    TC_UNROLL for (int j = 0; j < 4; j++) Em[j] -= T[j];
+  }
+  return best;
+}
+// The planned form of the division (combine_divide_quotient below keeps the chain of m = 0, width 3): the ladder over q + m at
+// the planned width, for the wave-uniform q, T, E of a wave-uniform denominator.
+TC_HD G2Jac combine_divide_planned(const G2Jac& a, uint64_t q, const int64_t* T, const int64_t* E, const QuotPlan& plan, bool& exc) {
+  int64_t Tu[4], Eu[4];
+  TC_UNROLL for (int j = 0; j < 4; j++) {
+    Tu[j] = (int64_t)wave_uniform((uint64_t)T[j]);
+    Eu[j] = (int64_t)wave_uniform((uint64_t)(E[j] - (int64_t)plan.m * T[j]));
+  }
+  const int width = (int)wave_uniform((uint64_t)plan.width);
+  exc = exc || a.is_inf();
+  return g2_quotient_mul_width(a, wave_uniform(q + (uint64_t)(int64_t)plan.m), Tu, Eu, width, exc);
+}
 #if !defined(__HIPCC__)
 inline int g_tc_force_divide_form = 0;  // host test build: 1 = the 4-dimensional ladder, 2 = the quotient form wherever it exists
 #endif
+// [1 / d_abs] a for a wave-uniform d_abs of the generic class by the cheaper of the planned quotient form and the 4-dimensional
+// ladder: ONE decomposition and ONE plan per wave serve the choice and the ladder
+TC_HD_NOINLINE G2Jac combine_divide_cheapest(const G2Jac& a, uint64_t d_abs, bool& exc) {
+  d_abs = wave_uniform(d_abs);  // (an argument arrives in vector registers: the decomposition and the plan are scalar work from here)
+  uint64_t q = 0;
+  int64_t T[4] = {0, 0, 0, 0}, E[4] = {0, 0, 0, 0};
+  bool planned = combine_quotient_decompose(d_abs, &q, T, E);
+  QuotPlan plan{0, kQuotWidth, 0};
+  if (planned) {
+    // (the decomposition divides, which the vector unit does: its results come back to scalar registers for the plan)
+    q = wave_uniform(q);
+    TC_UNROLL for (int j = 0; j < 4; j++) {
+      T[j] = (int64_t)wave_uniform((uint64_t)T[j]);
+      E[j] = (int64_t)wave_uniform((uint64_t)E[j]);
+    }
+    plan = combine_quotient_plan(q, T, E);
+    planned = plan.macs < combine_divide_uniform_macs(d_abs);
+#if !defined(__HIPCC__)
+    if (g_tc_force_divide_form) planned = g_tc_force_divide_form == 2;
+#endif
+  }
+  if (planned) return combine_divide_planned(a, q, T, E, plan, exc);
+  return combine_divide_uniform(a, d_abs, exc);
+}
 TC_HD bool combine_divide_takes_quotient(uint64_t d_abs) {
   uint64_t q;
   int64_t T[4], E[4];
@@ -380,7 +495,8 @@ struct IsG2<Fq2> {
 };
 // The combination of a wave whose live jobs all have ONE index tuple (G2; the coefficients c_k and D are then the wave's):
 // the table-free short ladder (tc_threshold.h straus_small_uniform) and, for a generic denominator, the cheaper of the two
-// [1 / D] forms above (the ladder over |x| / D for the small denominators of node numbers, the width-4 NAF ladder otherwise).
+// [1 / D] forms above (the planned ladder over |x| / D for the small denominators of node numbers, the width-4 NAF ladder
+// otherwise: combine_divide_cheapest).
 // Lanes that raise an exception flag are recomputed by the forms every other wave runs.
 #if !defined(__HIPCC__)
 inline int g_tc_force_mixed_combine = 0;  // host test build: 1 = take the forms of a mixed wave (on the host one job is a wave)
@@ -394,7 +510,7 @@ TC_HD G2Jac combine_uniform_wave(const G2Affine* pts, const uint64_t* c_abs, uin
   const uint64_t du = wave_uniform(d_abs);
   if (combine_denominator_class(du) != kCombineClassGeneric) return combine_divide_call(a, d_abs, d_neg);
   exc = false;
-  G2Jac q = combine_divide_takes_quotient(du) ? combine_divide_quotient(a, du, exc) : combine_divide_uniform(a, du, exc);
+  G2Jac q = combine_divide_cheapest(a, du, exc);
   q.y = Fq2::select(d_neg, -q.y, q.y);
   if (wave_any(exc)) q = G2Jac::select(exc, combine_divide_call(a, d_abs, d_neg), q);
   return q;
