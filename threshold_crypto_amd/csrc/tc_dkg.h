@@ -25,6 +25,14 @@ TC_HD void fixed_base_table_entry(int e, int32_t* out28) {
   uint32_t k[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const int bit = 4 * w;
   k[bit >> 5] = (uint32_t)m << (bit & 31);  // m <= 8 and 4 | bit: never straddles a word
+  if (!limbs_lt_p<FrParams>(k)) {  // 8 16^63 = 2^255 > r, and the ladder takes scalars below r: the entry no scalar below r reaches
+    uint32_t borrow = 0;
+    TC_UNROLL for (int i = 0; i < 8; i++) {
+      const uint64_t t = (uint64_t)k[i] - FR_P[i] - borrow;
+      borrow = (uint32_t)(t >> 63);
+      k[i] = (uint32_t)t;
+    }
+  }
   const G1Affine p = jac_to_affine(g1_mul_glv(g1_generator(), k));
   const Fq x = p.x.norm(), y = p.y.norm();
   TC_UNROLL for (int i = 0; i < FQ_LIMBS; i++) {
@@ -242,8 +250,8 @@ TC_HD uint64_t dkg_rlc_rho(const uint32_t* key8, uint64_t counter) {
   const uint32_t w0 = rng.next_u32(), w1 = rng.next_u32();
   return ((uint64_t)w1 << 32) | (uint64_t)(w0 | 1u);
 }
-// scalar i of job j as 8 canonical words: c_i for i <= degree, c_g for i = degree + 1 (false, and zero, when one of the
-// values is not canonical).  xs, vals: the job's own n abscissae and n x 32 B LE values
+// scalar i of job j as 8 canonical words: c_i for i <= degree, c_g for i = degree + 1 (false, and zero -- every one of the
+// degree + 2 scalars -- when one of the values is not canonical).  xs, vals: the job's own n abscissae and n x 32 B LE values
 TC_HD bool dkg_rlc_scalar(const uint32_t* key8, size_t j, size_t n, size_t degree, const uint64_t* xs, const uint8_t* vals, size_t i,
                           uint32_t* out8) {
   Fr acc = Fr::zero();
@@ -254,9 +262,9 @@ TC_HD bool dkg_rlc_scalar(const uint32_t* key8, size_t j, size_t n, size_t degre
   TC_NOUNROLL for (size_t k = 0; k < n; k++) {
     const Fr rho = fr_from_u64(dkg_rlc_rho(key8, (uint64_t)j * n + k));
     Fr term;
+    uint32_t v[8];
+    ok &= fr_from_le32(vals + k * 32, v);  // every scalar of the job looks at the values: all of them are zero when one is not canonical
     if (i > degree) {
-      uint32_t v[8];
-      ok &= fr_from_le32(vals + k * 32, v);
       term = Fr::from_canonical(v);
     } else {
       // x_k^i, left-to-right square and multiply (i = 0: one)
