@@ -13,6 +13,8 @@
 #include <initializer_list>
 #include <new>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -78,8 +80,6 @@ struct Call {
     size_t n;
   };
   std::vector<CopyBack> outs;
-  std::vector<std::pair<void*, size_t>> wipe;
-  std::vector<std::pair<void*, size_t>> wipe_after_copy;  // secret RESULTS staged for the host: zeroed after the D2H copy
   struct Pending {
     const uint8_t* valid;
     size_t per_job, group;
@@ -111,6 +111,19 @@ struct Call {
     // launch: out of memory", by the first call that runs after the memory came back
     // (tests/test_gpu_tables.py::test_failed_device_allocation_is_an_error_and_the_context_survives).  A call starts clean.
     (void)hipGetLastError();
+  }
+  Call(const Call&) = delete;
+  Call& operator=(const Call&) = delete;
+  // A call that ends without finish() -- a TC_REQUIRE behind the frame, or an exception on its way to on_exception -- ends HERE,
+  // while everything its copies touch is still alive: both streams are drained (a deferred test may not have been joined), the
+  // secrets zeroed like finish() zeroes them, the stream drained again.  Nothing here allocates or throws.
+  ~Call() {
+    if (ended) return;
+    failed = true;
+    c->tbl_reset = true;
+    (void)hipStreamSynchronize(c->stream);
+    if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
+    close(/*copy_back=*/false, /*drain=*/true);
   }
   void fail(const std::string& m) {
     if (!failed) c->err = m;
@@ -167,8 +180,8 @@ struct Call {
     size_t n = count * sizeof(T);
     void* d = scratch(n);
     if (!d) return nullptr;
+    if (secret) this->secret(d, n);  // (listed BEFORE the bytes arrive: a list that cannot grow ends the call with nothing to zero)
     if (n && !upload(d, p, n, "H2D copy")) return nullptr;
-    if (secret) wipe.emplace_back(d, n);
     return (const T*)d;
   }
   // output operand: device pointer the kernels write; copied back in finish()
@@ -209,11 +222,64 @@ struct Call {
     c->d2h_bytes += bytes;
     return true;
   }
-  // a temporary that holds secret scalars (or a lossless recoding of them): zeroed when the call ends
+  // HOST memory of the call.  Every host byte that an asynchronous copy of the call touches after the operands are staged -- verdict
+  // and status bytes read back, job maps and descriptors uploaded -- belongs to the frame and lives until the call has ended,
+  // however it ends: never a local of an entry, which an exception would free under the copy.  (The caller's operands and
+  // results are the caller's; total_bytes and the one word of combine() read into a stack slot and wait at once.)
+  template <class T>
+  T* host(size_t count) {  // zero-initialised
+    host_bufs.emplace_back((count * sizeof(T) + 7) / 8);
+    return reinterpret_cast<T*>(host_bufs.back().data());
+  }
+  // `count` values of device memory, on the host after the next wait(): in a buffer of their own, or (fetch_into) in host()
+  // memory the caller reuses from round to round
+  template <class T>
+  const T* fetch(const T* dev, size_t count, const char* what) {
+    T* h = host<T>(count);
+    fetch_into(h, dev, count, what);
+    return h;
+  }
+  template <class T>
+  void fetch_into(T* owned, const T* dev, size_t count, const char* what) {
+    if (readback(owned, dev, count * sizeof(T), what)) host_in_flight = true;
+  }
+  // a map the host has built (tc_fallback.h returns them by value), handed to the frame; its entries stay where they are
+  const uint32_t* keep(std::vector<uint32_t>&& v) {
+    host_maps.push_back(std::move(v));
+    return host_maps.back().data();
+  }
+  // upload() out of host() / keep() memory
+  bool upload_owned(void* dst, const void* owned_src, size_t bytes, const char* what) {
+    if (!upload(dst, owned_src, bytes, what)) return false;
+    host_in_flight = true;
+    return true;
+  }
+  // the main stream drained: what fetch() asked for is there.  false: the call has failed (now or earlier)
+  bool wait() {
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    host_in_flight = false;
+    if (!failed) check(e, "stream sync");
+    return !failed;
+  }
+  // the staging slots taken while a SlotScope lives are handed out again behind it -- the buffers of one round are the next
+  // round's.  The round ends with wait(); on unwinding the frame drains the stream before anybody takes a slot again.
+  struct SlotScope {
+    tc_ctx* c;
+    size_t mark;
+    explicit SlotScope(Call& k) : c(k.c), mark(k.c->next_slot) {}
+    ~SlotScope() { c->next_slot = mark; }
+    SlotScope(const SlotScope&) = delete;
+    SlotScope& operator=(const SlotScope&) = delete;
+  };
+  // device bytes that hold a secret (scalars, a lossless recoding of them): zeroed when the call ends.  after_copy: a secret
+  // RESULT staged for the host, zeroed behind its D2H copy.  List the bytes before anything writes them.
+  void secret(void* d, size_t bytes, bool after_copy = false) {
+    if (d) (after_copy ? wipe_after_copy : wipe).emplace_back(d, bytes);
+  }
   template <class T>
   T* secret_temp(size_t count) {
     T* d = temp<T>(count);
-    if (d) wipe.emplace_back(d, count * sizeof(T));
+    secret(d, count * sizeof(T));
     return d;
   }
   // the seed of a combined entry on the device: host memory in both I/O modes (32 bytes; secret until the call returns)
@@ -311,16 +377,16 @@ struct Call {
     checks.clear();
   }
   // For the entries whose HOST decides what falls back: the deferred tests run, and the verdict bytes behind each handle
-  // (check_points' return value; a null handle -- nothing registered -- leaves its vector empty) are read back, as many as were
-  // registered.  The pending list ends empty; with nothing pending and no handle this does nothing.
-  void take_verdicts(std::initializer_list<std::pair<const uint8_t*, std::vector<uint8_t>*>> want) {
+  // (check_points' return value) are read back, as many as were registered, into memory of the frame (fetch): the host pointer
+  // of each, null for a null handle -- nothing registered, no evidence.  The pending list ends empty; with nothing pending and
+  // no handle this does nothing.
+  void take_verdicts(std::initializer_list<std::pair<const uint8_t*, const uint8_t**>> want) {
     run_checks();
-    for (auto& w : want)
+    for (auto& w : want) {
+      *w.second = nullptr;
       for (auto& p : checks)
-        if (w.first && p.valid == w.first) {
-          w.second->resize(p.n);
-          readback(w.second->data(), p.valid, p.n, "valid readback");
-        }
+        if (w.first && p.valid == w.first) *w.second = fetch(p.valid, p.n, "valid readback");
+    }
     checks.clear();
   }
   // Every entry calls begin_timing() after its allocations and before its first launch: the place to refuse a call the RUNTIME
@@ -355,22 +421,36 @@ struct Call {
   }
   int finish() {
     if (!failed) check(hipGetLastError(), "kernel launch");
-    for (auto& w : wipe) (void)hipMemsetAsync(w.first, 0, w.second, c->stream);  // zero secret scalars
-    if (!failed)
-      for (auto& o : outs)
-        if (o.n) readback(o.host, o.dev, o.n, "D2H copy");
-    for (auto& w : wipe_after_copy) (void)hipMemsetAsync(w.first, 0, w.second, c->stream);  // stream-ordered after the copies
-    if (!c->device_io || c->timing || failed) {
-      hipError_t e = hipStreamSynchronize(c->stream);
-      if (!failed) check(e, "stream sync");
-    }
+    close(/*copy_back=*/!failed, /*drain=*/!c->device_io || c->timing);
     if (c->timing && !failed) {
       float ms = 0.f;
       if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->last_ms = ms;
     }
+    return failed ? (arg_error ? TC_ERR_INVALID_ARG : TC_ERR_HIP) : TC_OK;
+  }
+
+ private:
+  std::vector<std::vector<uint64_t>> host_bufs;  // host(): 8-byte units, zeroed
+  std::vector<std::vector<uint32_t>> host_maps;  // keep()
+  // a copy that fetch() / upload_owned() queued may still be running: set by them, cleared by every synchronise of the main stream
+  bool host_in_flight = false;
+  bool ended = false;
+  std::vector<std::pair<void*, size_t>> wipe;             // secret()
+  std::vector<std::pair<void*, size_t>> wipe_after_copy;  // secret(.., after_copy)
+  // The ONE ending of a call, behind finish() and behind the destructor: the secrets zeroed, the results copied back (a call that
+  // is still good), the staged secret results zeroed behind their copies, and the stream drained -- always for a failed call and
+  // for one with a copy running against the frame's host memory (a device-I/O call otherwise returns without waiting).  Without
+  // copy_back, or once `failed` is set, nothing here allocates.
+  void close(bool copy_back, bool drain) {
+    for (auto& w : wipe) (void)hipMemsetAsync(w.first, 0, w.second, c->stream);
+    if (copy_back)
+      for (auto& o : outs)
+        if (o.n) readback(o.host, o.dev, o.n, "D2H copy");
+    for (auto& w : wipe_after_copy) (void)hipMemsetAsync(w.first, 0, w.second, c->stream);  // stream-ordered after the copies
+    if (drain || failed || host_in_flight) wait();
     if (failed && !arg_error) c->tbl_reset = true;
     if (failed) (void)hipGetLastError();  // this call's own failure has been reported through `err`: do not leave it for the caller's next HIP check
-    return failed ? (arg_error ? TC_ERR_INVALID_ARG : TC_ERR_HIP) : TC_OK;
+    ended = true;
   }
 };
 
@@ -389,8 +469,10 @@ bool total_bytes(Call& k, const uint64_t* off, size_t B, uint64_t* total) {
     *total = off[B];
     return true;
   }
+  // (eight bytes into the caller's stack slot, not into memory of the frame: the wait is the very next statement, nothing between
+  // the copy and it can throw or return)
   if (!k.readback(total, off + B, 8, "offset readback")) return false;
-  return k.check(hipStreamSynchronize(k.c->stream), "stream sync");
+  return k.wait();
 }
 
 // sum_i scalars[j][i] * points[j][i] in G2 for n >= kMsmMinPoints through the two-stage kernels (k_msm.hip);
@@ -441,7 +523,7 @@ void msm_g2(Call& k, size_t n, size_t pts_stride, const uint8_t* d_pts, const ui
   int32_t* d_tbl = k.temp<int32_t>(tc::msm_table_bytes(n, tile) / sizeof(int32_t));
   uint8_t* d_codes = k.temp<uint8_t>(tc::msm_code_bytes(n, tile));
   // the digit codes are a lossless recoding of the scalars: wiped like them when they are secret
-  if (secret_scalars && d_codes) k.wipe.emplace_back(d_codes, tc::msm_code_bytes(n, tile));
+  if (secret_scalars) k.secret(d_codes, tc::msm_code_bytes(n, tile));
   for (size_t lo = 0; lo < B && !k.failed; lo += tile) {
     const size_t cnt = (B - lo < tile) ? B - lo : tile;
     tc::MsmFilter f = filter;
@@ -462,7 +544,7 @@ void msm_g1(Call& k, size_t n, size_t pts_stride, const uint8_t* d_pts, const ui
   int32_t* d_tbl = k.temp<int32_t>(tc::msm_table_bytes_g1(n, shared ? 1 : tile) / sizeof(int32_t));
   uint8_t* d_codes = k.temp<uint8_t>(tc::msm_code_bytes(n, tile));
   // the digit codes are a lossless recoding of the scalars: wiped like them when they are secret
-  if (secret_scalars && d_codes) k.wipe.emplace_back(d_codes, tc::msm_code_bytes(n, tile));
+  if (secret_scalars) k.secret(d_codes, tc::msm_code_bytes(n, tile));
   for (size_t lo = 0; lo < B && !k.failed; lo += tile) {
     const size_t cnt = (B - lo < tile) ? B - lo : tile;
     tc::launch_msm_g1(k.c->stream, n, pts_stride, d_pts + lo * pts_stride, d_scalars + lo * n * 8, cnt, d_tbl, d_codes, d_out + lo * 96, d_st + lo,
@@ -477,25 +559,33 @@ void msm_g1(Call& k, size_t n, size_t pts_stride, const uint8_t* d_pts, const ui
 struct Compacted {
   Call& k;
   size_t R;  // rows of c_ok
-  std::vector<size_t> first;  // map i = d_maps[first[i] .. first[i + 1])
+  size_t maps = 0, first[5] = {0};     // map i = d_maps[first[i] .. first[i + 1])
+  const uint32_t* h_map[4] = {nullptr};  // ... and where it lies on the host, in memory of the frame
   uint32_t* d_maps;
   uint8_t* c_ok;
   uint8_t* c_v = nullptr;
-  Compacted(Call& call, size_t rows, std::initializer_list<const std::vector<uint32_t>*> maps) : k(call), R(rows), first(1, 0) {
-    for (auto* m : maps) first.push_back(first.back() + m->size());
-    d_maps = k.temp<uint32_t>(first.back());
+  // one to four maps, each HANDED OVER (std::move at the call site) to the frame, which holds it until its copy has run
+  // (Call::keep); host_map() is where to read one again
+  template <class... Maps>
+  Compacted(Call& call, size_t rows, Maps&&... handed) : k(call), R(rows) {
+    static_assert(sizeof...(Maps) >= 1 && sizeof...(Maps) <= 4 && (std::is_same<Maps, std::vector<uint32_t>>::value && ...),
+                  "std::move every map into Compacted");
+    (take(std::move(handed)), ...);
+    d_maps = k.temp<uint32_t>(first[maps]);
     c_ok = k.temp<uint8_t>(R);
-    size_t i = 0;
-    for (auto* m : maps) {
-      if (!k.failed) k.upload(d_maps + first[i], m->data(), m->size() * 4, "map copy");
-      i++;
-    }
+    for (size_t i = 0; i < maps && !k.failed; i++) k.upload_owned(d_maps + first[i], h_map[i], (first[i + 1] - first[i]) * 4, "map copy");
   }
+  void take(std::vector<uint32_t>&& m) {
+    first[maps + 1] = first[maps] + m.size();
+    h_map[maps++] = k.keep(std::move(m));
+  }
+  const uint32_t* host_map(size_t which) const { return h_map[which]; }
   const uint32_t* map(size_t which) const { return d_maps + first[which]; }
-  // the rows of src (stride bytes each) that map `which` names
-  uint8_t* gather(const void* src, size_t stride, size_t which) {
+  // the rows of src (stride bytes each) that map `which` names; secret: zeroed when the call ends (Call::secret)
+  uint8_t* gather(const void* src, size_t stride, size_t which, bool secret = false) {
     const size_t n = first[which + 1] - first[which];
     uint8_t* d = k.temp<uint8_t>(n * stride);
+    if (secret) k.secret(d, n * stride);
     if (!k.failed) tc::launch_gather_rows(k.c->stream, (const uint8_t*)src, stride, map(which), n, d);
     return d;
   }
@@ -508,14 +598,8 @@ struct Compacted {
     uint8_t* v = scratch();
     if (!k.failed) k.require_members(g2, pts, stride, R, v, c_ok);
   }
-  // the host maps may go out of scope after this
-  void sync() {
-    const hipError_t e = hipStreamSynchronize(k.c->stream);
-    if (!k.failed) k.check(e, "stream sync");
-  }
   void finish(uint8_t* d_ok, size_t which) {
     if (!k.failed) tc::launch_scatter_bytes(k.c->stream, c_ok, map(which), R, d_ok);
-    sync();
   }
 };
 
@@ -573,7 +657,9 @@ static void wipe_host(uint8_t* p, size_t n) {
 }
 
 // The host code allocates (std::vector, std::string); under memory pressure that throws, and an exception that crossed the C ABI
-// into Rust or ctypes would be undefined behaviour.  The context stays usable: the arena flags are reset before the next use.
+// into Rust or ctypes would be undefined behaviour.  The handler of a function-try-block runs after the entry's locals are gone:
+// the call itself has been ended by its frame by then (~Call: streams drained, secrets zeroed, arena flags marked for a reset),
+// so the context stays usable and all that is left to do here is to name the failure.
 static int on_exception(tc_ctx* ctx) noexcept {
   const char* what = "C++ exception";
   try {
@@ -585,9 +671,6 @@ static int on_exception(tc_ctx* ctx) noexcept {
   } catch (...) {
   }
   if (ctx) {
-    ctx->tbl_reset = true;
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    (void)hipGetLastError();
     try {
       ctx->err = what;
     } catch (...) {
@@ -949,7 +1032,7 @@ int tc_sign_batch(tc_ctx* ctx, const uint8_t* fr, const uint8_t* msgs, const uin
   const uint64_t* d_off = k.in(off, B + 1);
   uint8_t* d_hash = k.temp<uint8_t>(B * 192);
   uint8_t* d_frc = k.temp<uint8_t>(S * 32);
-  if (d_frc) k.wipe.emplace_back(d_frc, S * 32);
+  k.secret(d_frc, S * 32);
   uint8_t* d_out = k.out(out_g2, S * B * 192);
   uint8_t* d_st = k.out(status, S * B);
   k.begin_timing();
@@ -1080,9 +1163,9 @@ static int combine(tc_ctx* ctx, bool g2, size_t t, size_t n, const uint64_t* idx
     if (!k.failed) {
       k.check(hipMemsetAsync(d_canon, 1, B, ctx->stream), "memset");
       tc::launch_fr_idx_narrow(ctx->stream, d_idx_fr, n, t + 1, B, d_idx64, d_wide, d_canon);
-      uint32_t wide = 0;
+      uint32_t wide = 0;  // (a stack slot, like total_bytes': the wait is the next statement)
       k.readback(&wide, d_wide, 4, "readback");
-      k.check(hipStreamSynchronize(ctx->stream), "stream sync");
+      k.wait();
       k.checks.push_back({d_canon, 1, 1});  // a job that owns a non-canonical abscissa (>= r) fails like an undecodable operand
       if (wide == 0) {
         d_idx = d_idx64;
@@ -1411,7 +1494,6 @@ int tc_verify_shares_rlc_batch(tc_ctx* ctx, const uint8_t* pk_shares, size_t N, 
   k.begin_timing();
   k.check_points(false, d_pk, 96, N, N, 1, (size_t)-1);
   k.check_points(true, d_sig, 192, N, N, B, 1);
-  std::vector<uint8_t> h_okmsg(B);
   if (!k.failed) {
     tc::launch_rlc_scalars(ctx->stream, d_seed, B * N, d_r);
     // (the two-stage kernels' short-scalar mode: 16 doublings for the 64-bit random scalars)
@@ -1425,19 +1507,17 @@ int tc_verify_shares_rlc_batch(tc_ctx* ctx, const uint8_t* pk_shares, size_t N, 
     // message to the per-share fallback
     k.apply_checks(B, nullptr, nullptr, 0, d_okmsg);
     k.check(hipMemsetAsync(d_ok, 1, B * N, ctx->stream), "memset");
-    k.readback(h_okmsg.data(), d_okmsg, B, "ok readback");
-    std::vector<uint8_t> h_stS(B);
-    k.readback(h_stS.data(), d_stS, B, "status readback");
-    k.check(hipStreamSynchronize(ctx->stream), "stream sync");
+    const uint8_t* h_okmsg = k.fetch(d_okmsg, B, "ok readback");
+    const uint8_t* h_stS = k.fetch(d_stS, B, "status readback");
     std::vector<uint32_t> failed;
-    if (!k.failed)
+    if (k.wait())
       for (size_t j = 0; j < B; j++)
         if (!h_okmsg[j] || h_stS[j] != TC_JOB_OK) failed.push_back((uint32_t)j);
     if (!k.failed && !failed.empty()) {
       // per-share pairing checks for every share of the failed messages, on compacted operands
       const size_t F = failed.size(), R = F * N;
-      const tc::SlotMaps m = tc::slot_maps(failed.data(), F, N);
-      Compacted c(k, R, {&m.record, &m.job, &m.slot});
+      tc::SlotMaps m = tc::slot_maps(failed.data(), F, N);
+      Compacted c(k, R, std::move(m.record), std::move(m.job), std::move(m.slot));
       const uint8_t* c_sig = c.gather(d_sig, 192, 0);
       const uint8_t* c_hash = c.gather(d_hash, 192, 1);
       const uint8_t* c_pk = c.gather(d_pk, 96, 2);
@@ -1488,7 +1568,6 @@ static void rlc_group_checks(Call& k, const RlcWs& w, const uint8_t* d_pk, const
   tc_ctx* ctx = k.c;
   const size_t group = w.cut.group, G = w.cut.G, tail = w.cut.tail, NG = w.cut.NG;
   uint8_t *d_seed = w.d_seed, *d_r = w.d_r, *d_S = w.d_S, *d_H = w.d_H, *d_st = w.d_st, *d_okg = w.d_okg;
-  std::vector<uint8_t> h_okg(NG), h_st(2 * NG), h_vkey, h_vsig, h_vhash;
   if (k.failed) return;
   tc::launch_rlc_scalars(ctx->stream, d_seed, B, d_r);
   k.check(hipMemsetAsync(d_st, 0, 2 * NG, ctx->stream), "memset");
@@ -1503,24 +1582,24 @@ static void rlc_group_checks(Call& k, const RlcWs& w, const uint8_t* d_pk, const
   }
   tc::launch_pairing_check(ctx->stream, d_pk, 0, d_H, 192, d_g1, 0, d_S, 192, NG, d_okg, k.pairing_ws(NG));
   k.check(hipMemsetAsync(d_ok, 1, B, ctx->stream), "memset");
-  k.readback(h_okg.data(), d_okg, NG, "ok readback");
-  k.readback(h_st.data(), d_st, 2 * NG, "status readback");
+  const uint8_t* h_okg = k.fetch(d_okg, NG, "ok readback");
+  const uint8_t* h_st = k.fetch(d_st, 2 * NG, "status readback");
   // checked-input mode: a group that owns a non-member operand goes to the per-job path as well
   // (the membership tests ran beside the two sums and the group checks)
+  const uint8_t *h_vkey, *h_vsig, *h_vhash;
   k.take_verdicts({{v_key, &h_vkey}, {v_sig, &h_vsig}, {v_hash, &h_vhash}});
-  k.check(hipStreamSynchronize(ctx->stream), "stream sync");
-  if (k.failed) return;
+  if (!k.wait()) return;
   tc::BadGroups bad(w.cut, B);
-  bad.per_group(h_okg.data(), true);
-  bad.per_group(h_st.data(), false);       // the sums of the signatures
-  bad.per_group(h_st.data() + NG, false);  // and of the hash points
-  if (!h_vkey.empty() && h_vkey[0] == 0) bad.all();
-  bad.jobs({tc::bytes_or_null(h_vsig), tc::bytes_or_null(h_vhash)}, true);
-  const std::vector<uint32_t> failed = bad.failed_jobs();
+  bad.per_group(h_okg, true);
+  bad.per_group(h_st, false);       // the sums of the signatures
+  bad.per_group(h_st + NG, false);  // and of the hash points
+  if (h_vkey && h_vkey[0] == 0) bad.all();
+  bad.jobs({h_vsig, h_vhash}, true);
+  std::vector<uint32_t> failed = bad.failed_jobs();
   if (failed.empty()) return;
   // per-job pairing checks for every job of the failed groups, on compacted operands
   const size_t R = failed.size();
-  Compacted c(k, R, {&failed});
+  Compacted c(k, R, std::move(failed));
   const uint8_t* c_sig = c.gather(d_sig, 192, 0);
   const uint8_t* c_hash = c.gather(d_hash, 192, 0);
   const tc::PairingWs pws = k.pairing_ws(R);
@@ -1608,8 +1687,7 @@ struct Records {
   tc::GroupCut cut;              // groups of jobs (messages / ciphertexts)
   uint64_t longest = 0;          // the most records of one job
   const uint64_t *hr = nullptr, *d_kidx = nullptr;  // rec_off on the host; key_idx as an operand
-  std::vector<uint64_t> h_rec, h_grp, h_kidx;  // h_grp: NG + 1 values, the first record of every group
-  std::vector<uint8_t> h_pad;
+  std::vector<uint64_t> h_grp;  // NG + 1 values, the first record of every group (host arithmetic only: never copied)
   const uint8_t *d_pk = nullptr, *d_keys = nullptr;  // the key table; the key of record r
   Records(Call& call, const uint8_t* pks_, size_t K_, const uint64_t* key_idx_, size_t M_, size_t group)
       : k(call), pks(pks_), key_idx(key_idx_), K(K_), M(M_), cut(tc::group_cut(M_, group)), h_grp(cut.NG + 1) {}
@@ -1622,11 +1700,8 @@ struct Records {
   // arithmetic, tc_records.h) and is validated.  records / ok: the caller's per-record operand and output.  false: the call is
   // over -- an error, or no record at all -- and the entry returns k.finish()
   bool offsets(const uint64_t* rec_off, const void* records, const void* ok) {
-    if (k.c->device_io) {
-      h_rec.resize(M + 1);
-      if (!k.readback(h_rec.data(), rec_off, (M + 1) * 8, "offset readback") || !k.check(hipStreamSynchronize(k.c->stream), "stream sync")) return false;
-    }
-    hr = k.c->device_io ? h_rec.data() : rec_off;
+    hr = k.c->device_io ? k.fetch(rec_off, M + 1, "offset readback") : rec_off;
+    if (k.c->device_io && !k.wait()) return false;
     bool good = hr[0] == 0;
     for (size_t m = 0; m < M && good; m++) good = hr[m + 1] >= hr[m];
     if (!require(good, "offsets must start at 0 and be non-decreasing") || !require(hr[M] < (1ull << 32), "R < 2^32")) return false;
@@ -1652,19 +1727,18 @@ struct Records {
   // the pairs that fill up the last group, so that ONE launch checks every group: `count` identities of G2 at g2_tail, of G1 at g1_tail
   void pad_identities(uint8_t* g2_tail, uint8_t* g1_tail, size_t count) {
     if (count == 0) return;
-    h_pad.assign(count * (192 + 96), 0);
+    uint8_t* h_pad = k.host<uint8_t>(count * (192 + 96));
     for (size_t i = 0; i < count; i++) h_pad[i * 192] = h_pad[count * 192 + i * 96] = 0x40;  // the identity of G2 / of G1
-    k.upload(g2_tail, h_pad.data(), count * 192, "pad copy");
-    k.upload(g1_tail, h_pad.data() + count * 192, count * 96, "pad copy");
+    k.upload_owned(g2_tail, h_pad, count * 192, "pad copy");
+    k.upload_owned(g1_tail, h_pad + count * 192, count * 96, "pad copy");
   }
   // key_idx for BadGroups::named_keys: a bad key fails the groups of the records that NAME it, so the indices are needed on the
   // host only then, and only then does device I/O read them back (8 R bytes and one sync)
-  const uint64_t* host_key_idx(const std::vector<uint8_t>& h_vkey) {
-    if (!key_idx || !k.c->device_io || !tc::has_zero(h_vkey.data(), h_vkey.size())) return key_idx;
-    h_kidx.resize(R);
-    k.readback(h_kidx.data(), key_idx, R * 8, "index readback");
-    k.check(hipStreamSynchronize(k.c->stream), "stream sync");
-    return h_kidx.data();
+  const uint64_t* host_key_idx(const uint8_t* h_vkey) {  // h_vkey: the K verdicts of the key table, or null
+    if (!key_idx || !k.c->device_io || !tc::has_zero(h_vkey, K)) return key_idx;
+    const uint64_t* h_kidx = k.fetch(key_idx, R, "index readback");
+    k.wait();
+    return h_kidx;
   }
 };
 
@@ -1698,8 +1772,8 @@ static int verify_records(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint6
   const size_t pairs_most = (size_t)tc::kBlock / tc::kG2Lanes;
   const uint64_t piece = tc::rec_piece_size(R, simd_lanes / tc::kG2Lanes, pairs_most);
   const size_t NP = (size_t)tc::rec_piece_total(f.h_grp.data(), NG, piece);
-  std::vector<uint64_t> desc(2 * (M + 1) + 2 * (NP + 1) + 2 * (NG + 1));
-  uint64_t *h_seg1 = desc.data(), *h_fc1 = h_seg1 + M + 1, *h_seg2 = h_fc1 + M + 1, *h_fc2 = h_seg2 + NP + 1, *h_seg3 = h_fc2 + NP + 1,
+  const size_t desc_words = 2 * (M + 1) + 2 * (NP + 1) + 2 * (NG + 1);
+  uint64_t *h_seg1 = k.host<uint64_t>(desc_words), *h_fc1 = h_seg1 + M + 1, *h_seg2 = h_fc1 + M + 1, *h_fc2 = h_seg2 + NP + 1, *h_seg3 = h_fc2 + NP + 1,
            *h_fc3 = h_seg3 + NG + 1;
   memcpy(h_seg1, f.hr, (M + 1) * 8);
   const uint64_t C1 = tc::rec_chunk_ranges(h_seg1, M, h_fc1);
@@ -1726,7 +1800,7 @@ static int verify_records(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint6
   const size_t MP = NG * group;
   uint8_t* d_hash = k.temp<uint8_t>(MP * 192);
   const uint8_t* d_g1 = hashes ? ctx->g1_gen : ctx->g1_gen_unfix;
-  uint64_t* d_desc = k.temp<uint64_t>(desc.size());
+  uint64_t* d_desc = k.temp<uint64_t>(desc_words);
   uint8_t* d_seed = k.secret_seed(seed32);
   uint8_t* d_r = k.secret_temp<uint8_t>(R * 32);
   uint8_t* d_P = k.temp<uint8_t>(MP * 96);
@@ -1749,9 +1823,8 @@ static int verify_records(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint6
   const uint8_t* v_key = k.check_points(false, f.d_pk, 96, K, K, 1, (size_t)-1);
   const uint8_t* v_sig = k.check_points(true, d_sig, 192, 1, 1, R, 1);
   const uint8_t* v_hash = hashes ? k.check_points(true, d_hash_in, 192, 1, 1, M, 1) : nullptr;
-  std::vector<uint8_t> h_okg(NG), h_st(M + NG + NP), h_vkey, h_vsig, h_vhash;
   if (!k.failed) {
-    k.upload(d_desc, desc.data(), desc.size() * 8, "descriptor copy");
+    k.upload_owned(d_desc, h_seg1, desc_words * 8, "descriptor copy");
     k.check(hipMemsetAsync(d_st, 0, M + NG + NP, ctx->stream), "memset");
     if (!hashes) tc::launch_hash_g2(ctx->tuning, ctx->stream, d_msgs, d_off, M, d_hash, /*fix=*/false);
     else k.check(hipMemcpyAsync(d_hash, d_hash_in, M * 192, hipMemcpyDeviceToDevice, ctx->stream), "hash copy");
@@ -1775,27 +1848,27 @@ static int verify_records(tc_ctx* ctx, const uint8_t* pks, size_t K, const uint6
     // one pair per message (an empty message: P_m = identity, the factor 1), one final exponentiation per group
     tc::launch_pairing_product_check(ctx->stream, d_P, 96, d_hash, 192, group, NG, d_g1, 0, d_S, 192, d_okg, ws_groups);
     k.check(hipMemsetAsync(d_ok, 1, R, ctx->stream), "memset");
-    k.readback(h_okg.data(), d_okg, NG, "ok readback");
-    k.readback(h_st.data(), d_st, M + NG + NP, "status readback");
+    const uint8_t* h_okg = k.fetch(d_okg, NG, "ok readback");
+    const uint8_t* h_st = k.fetch(d_st, M + NG + NP, "status readback");
     // (the membership tests ran beside the sums and the group checks)
+    const uint8_t *h_vkey, *h_vsig, *h_vhash;
     k.take_verdicts({{v_key, &h_vkey}, {v_sig, &h_vsig}, {v_hash, &h_vhash}});
-    k.check(hipStreamSynchronize(ctx->stream), "stream sync");
     tc::SlotMaps maps;  // every record of the messages of the bad groups
-    if (!k.failed) {
+    if (k.wait()) {
       tc::BadGroups bad(f.cut, M);
-      bad.per_group(h_okg.data(), true);
-      bad.per_group(h_st.data() + M, false);                  // the sums of the groups,
-      bad.spans(h_seg3, h_st.data() + M + NG, false);         // of their pieces
-      bad.jobs({h_st.data()}, false);                         // and of their messages
-      bad.jobs({tc::bytes_or_null(h_vhash)}, true);
-      bad.spans(f.h_grp.data(), tc::bytes_or_null(h_vsig), true);
-      bad.named_keys(f.h_grp.data(), f.host_key_idx(h_vkey), K, tc::bytes_or_null(h_vkey));
+      bad.per_group(h_okg, true);
+      bad.per_group(h_st + M, false);           // the sums of the groups,
+      bad.spans(h_seg3, h_st + M + NG, false);  // of their pieces
+      bad.jobs({h_st}, false);                  // and of their messages
+      bad.jobs({h_vhash}, true);
+      bad.spans(f.h_grp.data(), h_vsig, true);
+      bad.named_keys(f.h_grp.data(), f.host_key_idx(h_vkey), K, h_vkey);
       maps = tc::records_of_jobs(f.hr, bad.failed_jobs());
     }
     if (!k.failed && !maps.record.empty()) {
       // the per-record check of tc_verify_g2_batch for every record of the failed groups, on compacted operands
       const size_t F = maps.record.size();
-      Compacted c(k, F, {&maps.record, &maps.job});
+      Compacted c(k, F, std::move(maps.record), std::move(maps.job));
       const uint8_t* c_sig = c.gather(d_sig, 192, 0);
       const uint8_t* c_hash = c.gather(d_hash, 192, 1);
       const uint8_t* c_pk = c.gather(f.d_keys, 96, 0);
@@ -1915,7 +1988,6 @@ int tc_ciphertext_verify_rlc_batch(tc_ctx* ctx, const uint8_t* u, const uint8_t*
   k.begin_timing();
   const uint8_t* v_u = k.check_points(false, d_u, 96, 1, 1, B, 1);
   const uint8_t* v_w = k.check_points(true, d_w, 192, 1, 1, B, 1);
-  std::vector<uint8_t> h_okg(NG), h_st(2 * B + NG), h_vu, h_vw;
   if (!k.failed) {
     k.check(hipMemsetAsync(d_st, 0, 2 * B + NG, ctx->stream), "memset");
     // an undecodable u leaves a hash that does not decode either (and a status): its group falls back
@@ -1932,25 +2004,25 @@ int tc_ciphertext_verify_rlc_batch(tc_ctx* ctx, const uint8_t* u, const uint8_t*
       tc::launch_pairing_product_check(ctx->stream, d_ru + G * group * 96, 96, d_hash + G * group * 192, 192, tail, 1, ctx->g1_gen_unfix, 0,
                                        d_W + G * 192, 192, d_okg + G, ws_tail);
     k.check(hipMemsetAsync(d_ok, 1, B, ctx->stream), "memset");
-    k.readback(h_okg.data(), d_okg, NG, "ok readback");
-    k.readback(h_st.data(), d_st, 2 * B + NG, "status readback");
+    const uint8_t* h_okg = k.fetch(d_okg, NG, "ok readback");
+    const uint8_t* h_st = k.fetch(d_st, 2 * B + NG, "status readback");
     // checked-input mode: a group that owns a non-member operand goes to the per-ciphertext path as well
     // (the membership tests ran beside the sums and the group checks)
+    const uint8_t *h_vu, *h_vw;
     k.take_verdicts({{v_u, &h_vu}, {v_w, &h_vw}});
-    k.check(hipStreamSynchronize(ctx->stream), "stream sync");
     std::vector<uint32_t> failed;
-    if (!k.failed) {
+    if (k.wait()) {
       tc::BadGroups bad(cut, B);
-      bad.per_group(h_okg.data(), true);
-      bad.per_group(h_st.data() + 2 * B, false);                 // the sums of the groups
-      bad.jobs({h_st.data(), h_st.data() + B}, false);           // the hashes and r_j u_j
-      bad.jobs({tc::bytes_or_null(h_vu), tc::bytes_or_null(h_vw)}, true);
+      bad.per_group(h_okg, true);
+      bad.per_group(h_st + 2 * B, false);      // the sums of the groups
+      bad.jobs({h_st, h_st + B}, false);       // the hashes and r_j u_j
+      bad.jobs({h_vu, h_vw}, true);
       failed = bad.failed_jobs();
     }
     if (!k.failed && !failed.empty()) {
       // the per-ciphertext check of tc_ciphertext_verify_batch for every ciphertext of the failed groups, on compacted operands
       const size_t R = failed.size();
-      Compacted c(k, R, {&failed});
+      Compacted c(k, R, std::move(failed));
       const uint8_t* c_u = c.gather(d_u, 96, 0);
       const uint8_t* c_hash = c.gather(d_hash, 192, 0);
       const uint8_t* c_w = c.gather(d_w, 192, 0);
@@ -1991,7 +2063,7 @@ static int verified_decrypt(tc_ctx* ctx, const uint8_t* sk, const uint8_t* u, co
   uint8_t* d_st = k.temp<uint8_t>(B, /*zero=*/true);
   uint8_t* d_pt = plain ? k.temp<uint8_t>(B * 96) : k.out(out_g1, B * 96);
   uint8_t* d_plain = plain ? k.out(plain, (size_t)total, /*zero=*/true) : nullptr;
-  if (plain && d_pt) k.wipe_after_copy.emplace_back(d_pt, B * 96);  // g = [sk] u opens the ciphertext: not left in a staging slot
+  if (plain) k.secret(d_pt, B * 96, /*after_copy=*/true);  // g = [sk] u opens the ciphertext: not left in a staging slot
   k.begin_timing();
   // ALWAYS, whatever tc_ctx_set_input_checks says: the pairing check cannot see a small-order component of u
   // (u = u1 + T, T in E(Fq)[h1]: e(u, H) = e(u1, H)), and [sk] u would leak sk modulo the cofactor's small factors.  The
@@ -2149,7 +2221,6 @@ int tc_verify_decryption_shares_rlc_batch(tc_ctx* ctx, const uint8_t* pk_shares,
   k.check_points(false, d_sh, 96, N, N, B, 1);
   k.check_points(false, d_u, 96, 1, 1, B, 1);
   k.check_points(true, d_w, 192, 1, 1, B, 1);
-  std::vector<uint8_t> h_okct(B), h_st(3 * B);
   if (!k.failed) {
     tc::launch_rlc_scalars_g1(ctx->stream, d_seed, B * N, d_r);
     k.check(hipMemsetAsync(d_st, 0, 3 * B, ctx->stream), "memset");
@@ -2162,18 +2233,17 @@ int tc_verify_decryption_shares_rlc_batch(tc_ctx* ctx, const uint8_t* pk_shares,
     tc::launch_pairing_check(ctx->stream, d_Dc, 96, d_hash, 192, d_P, 96, d_w, 192, B, d_okct, k.pairing_ws(B));
     k.apply_checks(B, nullptr, nullptr, 0, d_okct);  // checked-input mode: a ciphertext owning a non-member operand falls back
     k.check(hipMemsetAsync(d_ok, 1, B * N, ctx->stream), "memset");
-    k.readback(h_okct.data(), d_okct, B, "ok readback");
-    k.readback(h_st.data(), d_st, 3 * B, "status readback");
-    k.check(hipStreamSynchronize(ctx->stream), "stream sync");
+    const uint8_t* h_okct = k.fetch(d_okct, B, "ok readback");
+    const uint8_t* h_st = k.fetch(d_st, 3 * B, "status readback");
     std::vector<uint32_t> failed;
-    if (!k.failed)
+    if (k.wait())
       for (size_t j = 0; j < B; j++)
         if (!h_okct[j] || h_st[j] != TC_JOB_OK || h_st[B + j] != TC_JOB_OK || h_st[2 * B + j] != TC_JOB_OK) failed.push_back((uint32_t)j);
     if (!k.failed && !failed.empty()) {
       // per-share pairing checks for every share of the failed ciphertexts, on compacted operands
       const size_t F = failed.size(), R = F * N;
-      const tc::SlotMaps m = tc::slot_maps(failed.data(), F, N);
-      Compacted c(k, R, {&m.record, &m.job, &m.slot});
+      tc::SlotMaps m = tc::slot_maps(failed.data(), F, N);
+      Compacted c(k, R, std::move(m.record), std::move(m.job), std::move(m.slot));
       const uint8_t* c_sh = c.gather(d_sh, 96, 0);
       const uint8_t* c_hash = c.gather(d_hash, 192, 1);
       const uint8_t* c_w = c.gather(d_w, 192, 1);
@@ -2230,8 +2300,8 @@ static int verify_dshare_records(tc_ctx* ctx, const uint8_t* pks, size_t K, cons
     TC_REQUIRE(total == 0 || v);
   }
   // the segments of both sums: the ciphertexts.  One descriptor array: [rec_off | chunks of the ciphertexts]
-  std::vector<uint64_t> desc(2 * (M + 1));
-  uint64_t *h_seg = desc.data(), *h_fc = h_seg + M + 1;
+  const size_t desc_words = 2 * (M + 1);
+  uint64_t *h_seg = k.host<uint64_t>(desc_words), *h_fc = h_seg + M + 1;
   memcpy(h_seg, f.hr, (M + 1) * 8);
   const uint64_t C = tc::rec_chunk_ranges(h_seg, M, h_fc);
   const size_t parts = tc::rec_parts(2 * M, f.longest, f.simd_lanes, tc::kBlock, ctx->tuning.records_parts);  // lanes per SUM, two sums per ciphertext
@@ -2251,7 +2321,7 @@ static int verify_dshare_records(tc_ctx* ctx, const uint8_t* pks, size_t K, cons
   const uint8_t* d_hash = hashes ? d_hash_in : d_hash_own;
   uint8_t* d_ab = k.temp<uint8_t>(MP * 2 * 96);   // [A_c, -B_c]
   uint8_t* d_hw = k.temp<uint8_t>(MP * 2 * 192);  // [H_c, w_c]
-  uint64_t* d_desc = k.temp<uint64_t>(desc.size());
+  uint64_t* d_desc = k.temp<uint64_t>(desc_words);
   uint8_t* d_seed = k.secret_seed(seed32);
   uint8_t* d_r = k.secret_temp<uint8_t>(R * 32);
   uint8_t* d_st = k.temp<uint8_t>(2 * M);  // the sums of the ciphertexts | their hashes
@@ -2267,9 +2337,8 @@ static int verify_dshare_records(tc_ctx* ctx, const uint8_t* pks, size_t K, cons
   const uint8_t* v_sh = k.check_points(false, d_sh, 96, 1, 1, R, 1);
   const uint8_t* v_u = hashes ? k.check_points(true, d_hash_in, 192, 1, 1, M, 1) : k.check_points(false, d_u, 96, 1, 1, M, 1);
   const uint8_t* v_w = k.check_points(true, d_w, 192, 1, 1, M, 1);
-  std::vector<uint8_t> h_okg(NG), h_st(2 * M), h_vkey, h_vsh, h_vu, h_vw;
   if (!k.failed) {
-    k.upload(d_desc, desc.data(), desc.size() * 8, "descriptor copy");
+    k.upload_owned(d_desc, h_seg, desc_words * 8, "descriptor copy");
     k.check(hipMemsetAsync(d_st, 0, 2 * M, ctx->stream), "memset");
     if (!hashes) tc::launch_hash_g1_g2(ctx->tuning, ctx->stream, d_u, d_v, d_off, M, d_hash_own, d_st + M, /*fix=*/true);
     k.check(hipMemcpy2DAsync(d_hw, 384, d_hash, 192, 192, M, hipMemcpyDeviceToDevice, ctx->stream), "hash copy");
@@ -2285,19 +2354,19 @@ static int verify_dshare_records(tc_ctx* ctx, const uint8_t* pks, size_t K, cons
     // one final exponentiation per group                                                          (src/lib.rs:185)
     tc::launch_pairing_product_check(ctx->stream, d_ab, 96, d_hw, 192, 2 * group, NG, nullptr, 0, nullptr, 0, d_okg, ws_groups);
     k.check(hipMemsetAsync(d_ok, 1, R, ctx->stream), "memset");
-    k.readback(h_okg.data(), d_okg, NG, "ok readback");
-    k.readback(h_st.data(), d_st, 2 * M, "status readback");
+    const uint8_t* h_okg = k.fetch(d_okg, NG, "ok readback");
+    const uint8_t* h_st = k.fetch(d_st, 2 * M, "status readback");
     // (the membership tests ran beside the sums and the group checks)
+    const uint8_t *h_vkey, *h_vsh, *h_vu, *h_vw;
     k.take_verdicts({{v_key, &h_vkey}, {v_sh, &h_vsh}, {v_u, &h_vu}, {v_w, &h_vw}});
-    k.check(hipStreamSynchronize(ctx->stream), "stream sync");
     tc::SlotMaps maps;  // every record of the ciphertexts of the bad groups
-    if (!k.failed) {
+    if (k.wait()) {
       tc::BadGroups bad(f.cut, M);
-      bad.per_group(h_okg.data(), true);
-      bad.jobs({h_st.data(), h_st.data() + M}, false);  // the sums of the ciphertexts and their hashes
-      bad.jobs({tc::bytes_or_null(h_vu), tc::bytes_or_null(h_vw)}, true);
-      bad.spans(f.h_grp.data(), tc::bytes_or_null(h_vsh), true);
-      bad.named_keys(f.h_grp.data(), f.host_key_idx(h_vkey), K, tc::bytes_or_null(h_vkey));
+      bad.per_group(h_okg, true);
+      bad.jobs({h_st, h_st + M}, false);  // the sums of the ciphertexts and their hashes
+      bad.jobs({h_vu, h_vw}, true);
+      bad.spans(f.h_grp.data(), h_vsh, true);
+      bad.named_keys(f.h_grp.data(), f.host_key_idx(h_vkey), K, h_vkey);
       maps = tc::records_of_jobs(f.hr, bad.failed_jobs());
     }
     if (!k.failed && !maps.record.empty()) {
@@ -2307,7 +2376,7 @@ static int verify_dshare_records(tc_ctx* ctx, const uint8_t* pks, size_t K, cons
       // encoding that does not decode there and answers 0 -- so do these records)
       for (size_t m = 0; m < M && !hashes && !k.failed; m++)
         if (h_st[M + m] != TC_JOB_OK) k.check(hipMemsetAsync(d_hash_own + m * 192, 0xff, 192, ctx->stream), "memset");
-      Compacted c(k, F, {&maps.record, &maps.job});
+      Compacted c(k, F, std::move(maps.record), std::move(maps.job));
       const uint8_t* c_sh = c.gather(d_sh, 96, 0);
       const uint8_t* c_pk = c.gather(f.d_keys, 96, 0);
       const uint8_t* c_hash = c.gather(d_hash, 192, 1);
@@ -2359,19 +2428,20 @@ int tc_verify_decryption_share_records_prehashed_rlc_batch(tc_ctx* ctx, const ui
 }
 
 // Pass 2 of robust_combine by bisection (tc_ctx_set_blame_bisect; rule, bounds and the 2^-63 argument: tc_blame.h, DESIGN.md
-// 4.17): h_ok[f * N + i] = 0 exactly for the present shares of the failed jobs that per-share mode would answer ok = 0 for,
+// 4.17): the returned bytes (memory of the frame) h_ok[f * N + i] = 0 exactly for the present shares of the failed jobs that per-share mode would answer ok = 0 for,
 // found with range checks over leaves [r] share / [r] pk_share (k_blame.hip).  c_sh: the failed jobs' shares, uncompressed
 // (F x N); c_dec: the status bytes of their checked decode (wire) or null; d_maps: the record / job maps of pass 2.  The host
 // drives the rounds -- one batched pairing-check launch and one readback of verdict bytes each -- and builds the worklists
 // (tc::BlameSearch, one per job).  The leaves of F x N slots take F N (576 B signatures / 384 B decryption): failed jobs
 // go through in chunks under the budget the two-stage tables have (msm_table_budget; TC_MSM_BUDGET).  The engine knows
 // nothing of the entry: the RLC fallbacks could drive it the same way.
-static void blame_pass(Call& k, bool sig, bool wire, size_t N, const std::vector<uint32_t>& failed, const uint32_t* d_maps, const uint8_t* c_sh,
-                       const uint8_t* c_dec, const uint8_t* d_present, const uint8_t* d_jvalid, const uint8_t* d_pks, const uint8_t* d_hash,
-                       const uint8_t* d_w, const uint8_t* d_g1, std::vector<uint8_t>& h_ok) {
+static const uint8_t* blame_pass(Call& k, bool sig, bool wire, size_t N, const uint32_t* failed, size_t F, const uint32_t* d_maps, const uint8_t* c_sh,
+                                 const uint8_t* c_dec, const uint8_t* d_present, const uint8_t* d_jvalid, const uint8_t* d_pks, const uint8_t* d_hash,
+                                 const uint8_t* d_w, const uint8_t* d_g1) {
   tc_ctx* ctx = k.c;
-  const size_t F = failed.size(), R = F * N, PB = sig ? 192 : 96;
-  h_ok.assign(R, 1);
+  const size_t R = F * N, PB = sig ? 192 : 96;
+  uint8_t* h_ok = k.host<uint8_t>(R);
+  memset(h_ok, 1, R);
   uint8_t* c_pres = k.temp<uint8_t>(R);
   uint8_t* c_live = k.temp<uint8_t>(R);
   uint8_t* c_v = k.temp<uint8_t>(R);
@@ -2385,7 +2455,7 @@ static void blame_pass(Call& k, bool sig, bool wire, size_t N, const std::vector
   int32_t* d_leaf_pk = k.temp<int32_t>(Fc * N * leaf_pk / sizeof(int32_t));
   int32_t* d_sink = k.temp<int32_t>(tc::blame_sink_bytes() / sizeof(int32_t));
   const tc::TableArena ta = k.tables();
-  if (k.failed) return;
+  if (k.failed) return h_ok;
   // live = present, decoded, a group member where that is tested, and the job's own operands valid
   if (d_present) tc::launch_gather_bytes(ctx->stream, d_present, d_maps, R, c_pres);
   else k.check(hipMemsetAsync(c_pres, 1, R, ctx->stream), "memset");
@@ -2400,23 +2470,26 @@ static void blame_pass(Call& k, bool sig, bool wire, size_t N, const std::vector
   // this call's scalars: ChaCha20 under a seed of its own, derived from the context's key and call counter
   k.upload(d_key, ctx->blame_key, 32, "key copy");
   tc::launch_blame_seed(ctx->stream, d_key, ctx->blame_calls++, d_seed);
-  std::vector<uint8_t> h_pres, h_live, h_bad, h_verdict;
+  // memory of the frame, reused chunk after chunk and round after round (each ends with wait()): Fc * N bytes hold a chunk's
+  // present / live bytes, and the items and verdicts of a round, which grow when a round has more ranges than the last
+  uint8_t *h_pres = k.host<uint8_t>(Fc * N), *h_live = k.host<uint8_t>(Fc * N), *h_verdict = nullptr;
+  uint32_t* items = nullptr;
+  size_t items_room = 0;
+  std::vector<uint8_t> h_bad;
   std::vector<tc::BlameSearch> search;
   std::vector<tc::BlameRange> ranges;
-  std::vector<uint32_t> items, counts;
+  std::vector<uint32_t> counts;
   for (size_t f0 = 0; f0 < F && !k.failed; f0 += Fc) {
     const size_t cnt = (F - f0 < Fc) ? F - f0 : Fc, rows = cnt * N;
     // (the share leaves first: a share that does not decode clears its live byte, and its key share's leaf is the identity too)
     tc::launch_blame_leaves(ctx->stream, ta, sig, d_seed, (uint64_t)(f0 * N), c_sh + f0 * N * PB, 0, c_live + f0 * N, rows, d_leaf_s, d_sink);
     tc::launch_blame_leaves(ctx->stream, ta, false, d_seed, (uint64_t)(f0 * N), d_pks, N, c_live + f0 * N, rows, d_leaf_pk, d_sink);
-    h_pres.resize(rows);
-    h_live.resize(rows);
     h_bad.assign(rows, 0);
-    k.readback(h_pres.data(), c_pres + f0 * N, rows, "present readback");
-    k.readback(h_live.data(), c_live + f0 * N, rows, "live readback");
-    if (!k.check(hipStreamSynchronize(ctx->stream), "stream sync")) break;
+    k.fetch_into(h_pres, c_pres + f0 * N, rows, "present readback");
+    k.fetch_into(h_live, c_live + f0 * N, rows, "live readback");
+    if (!k.wait()) break;
     search.assign(cnt, tc::BlameSearch());
-    for (size_t f = 0; f < cnt; f++) search[f].start((uint32_t)N, h_pres.data() + f * N, h_live.data() + f * N, h_bad.data() + f * N);
+    for (size_t f = 0; f < cnt; f++) search[f].start((uint32_t)N, h_pres + f * N, h_live + f * N, h_bad.data() + f * N);
     while (!k.failed) {
       // one round: the pending checks of every job of the chunk in ONE launch
       ranges.clear();
@@ -2424,7 +2497,11 @@ static void blame_pass(Call& k, bool sig, bool wire, size_t N, const std::vector
       for (size_t f = 0; f < cnt; f++) counts[f] = (uint32_t)search[f].plan(ranges);
       const size_t n = ranges.size();
       if (n == 0) break;
-      items.resize(4 * n);  // job of the chunk, lo, hi, job of the call
+      if (n > items_room) {
+        items = k.host<uint32_t>(4 * n);  // job of the chunk, lo, hi, job of the call
+        h_verdict = k.host<uint8_t>(n);
+        items_room = n;
+      }
       size_t longest = 1;
       for (size_t f = 0, i = 0; f < cnt; f++)
         for (uint32_t c = 0; c < counts[f]; c++, i++) {
@@ -2434,7 +2511,7 @@ static void blame_pass(Call& k, bool sig, bool wire, size_t N, const std::vector
           items[3 * n + i] = failed[f0 + f];
           if (ranges[i].hi - ranges[i].lo > longest) longest = ranges[i].hi - ranges[i].lo;
         }
-      const size_t mark = ctx->next_slot;  // the round's buffers are the next round's: it ends with a sync
+      const Call::SlotScope round(k);  // the round's buffers are the next round's: it ends with wait()
       uint32_t* d_items = k.temp<uint32_t>(4 * n);
       uint8_t* s_sh = k.temp<uint8_t>(n * PB);
       uint8_t* s_shc = sig ? nullptr : k.temp<uint8_t>(n * 96);
@@ -2444,7 +2521,7 @@ static void blame_pass(Call& k, bool sig, bool wire, size_t N, const std::vector
       uint8_t* s_ok = k.temp<uint8_t>(n);
       const tc::PairingWs pws = k.pairing_ws(n);
       if (k.failed) break;
-      k.upload(d_items, items.data(), 16 * n, "item copy");
+      k.upload_owned(d_items, items, 16 * n, "item copy");
       tc::launch_blame_range_sum(ctx->stream, sig, d_leaf_s, N, d_items, d_items + n, d_items + 2 * n, n, tc::blame_sum_parts(sig, n, longest, ctx->cus), s_sh);
       tc::launch_blame_range_sum(ctx->stream, false, d_leaf_pk, N, d_items, d_items + n, d_items + 2 * n, n, tc::blame_sum_parts(false, n, longest, ctx->cus),
                                  s_pk);
@@ -2458,17 +2535,15 @@ static void blame_pass(Call& k, bool sig, bool wire, size_t N, const std::vector
         tc::launch_g1_scale_cofactor_fix(ctx->stream, s_sh, 96, n, s_shc);
         tc::launch_pairing_check(ctx->stream, s_shc, 96, s_hash, 192, s_pk, 96, s_w, 192, n, s_ok, pws);
       }
-      h_verdict.resize(n);
-      k.readback(h_verdict.data(), s_ok, n, "verdict readback");
-      k.check(hipStreamSynchronize(ctx->stream), "stream sync");
-      ctx->next_slot = mark;
-      if (k.failed) break;
-      for (size_t f = 0, i = 0; f < cnt; i += counts[f], f++) search[f].apply(h_verdict.data() + i);
+      k.fetch_into(h_verdict, s_ok, n, "verdict readback");
+      if (!k.wait()) break;
+      for (size_t f = 0, i = 0; f < cnt; i += counts[f], f++) search[f].apply(h_verdict + i);
       ctx->blame_rounds++;
     }
     for (size_t f = 0; f < cnt; f++) ctx->blame_checks += search[f].checks;
     for (size_t r = 0; r < rows; r++) h_ok[f0 * N + r] = h_bad[r] ? 0 : 1;
   }
+  return h_ok;
 }
 
 // ---- robust combination ------------------------------------------------------------------------------
@@ -2534,7 +2609,7 @@ static int robust_combine(tc_ctx* ctx, bool sig, bool wire, const uint8_t* commi
   uint8_t* d_out96 = sig && wire ? k.out(out, B * 96) : nullptr;
   uint8_t* d_plain = sig ? nullptr : k.out(out, (size_t)total, /*zero=*/true);  // failed jobs leave zeros
   // the N public key shares, made once per call: Commitment::evaluate(i + 1), src/lib.rs:570-573
-  std::vector<uint64_t> h_slots(N);
+  uint64_t* h_slots = k.host<uint64_t>(N);
   for (size_t i = 0; i < N; i++) h_slots[i] = i;
   uint64_t* d_pkidx = k.temp<uint64_t>(N);
   uint8_t* d_pks = k.temp<uint8_t>(N * 96);
@@ -2564,10 +2639,10 @@ static int robust_combine(tc_ctx* ctx, bool sig, bool wire, const uint8_t* commi
   RlcWs ws{};
   if (sig) ws = rlc_workspace(k, B, group, seed32);
   k.begin_timing();
-  std::vector<uint8_t> h_verdict(B), h_pkst(N), h_cval(need, 1);
+  const uint8_t *h_verdict = nullptr, *h_pkst = nullptr, *h_cval = nullptr;  // h_cval: checked-input mode only
   std::vector<uint32_t> failed;
   if (!k.failed) {
-    k.upload(d_pkidx, h_slots.data(), N * 8, "index copy");
+    k.upload_owned(d_pkidx, h_slots, N * 8, "index copy");
     tc::launch_commitment_evaluate(ctx->stream, d_commit, t, d_pkidx, N, d_pks, d_pkst);
     if (ctx->input_checks) tc::launch_subgroup_check_g1(ctx->stream, d_commit, 96, need, need, need, d_cval);
     // pass 1: the first t+1 present shares, whatever they are
@@ -2619,15 +2694,15 @@ static int robust_combine(tc_ctx* ctx, bool sig, bool wire, const uint8_t* commi
     tc::launch_invalidate_jobs(ctx->stream, d_jvalid, 1, 1, B, nullptr, nullptr, 0, d_ok1);
     if (wire) tc::launch_invalidate_jobs(ctx->stream, d_cmem, 1, 1, B, nullptr, nullptr, 0, d_ok1);
     tc::launch_robust_finish(ctx->stream, nullptr, N, need, PB, B, d_enough, d_st1, d_ok1, d_member, d_comb, d_res, d_status, d_used, d_verdict);
-    k.readback(h_verdict.data(), d_verdict, B, "verdict readback");
-    k.readback(h_pkst.data(), d_pkst, N, "status readback");
-    if (ctx->input_checks) k.readback(h_cval.data(), d_cval, need, "valid readback");
-    k.check(hipStreamSynchronize(ctx->stream), "stream sync");
+    h_verdict = k.fetch(d_verdict, B, "verdict readback");
+    h_pkst = k.fetch(d_pkst, N, "status readback");
+    if (ctx->input_checks) h_cval = k.fetch(d_cval, need, "valid readback");
+    k.wait();
   }
   bool commit_bad = false;
   if (!k.failed) {
     for (size_t i = 0; i < N; i++) commit_bad = commit_bad || h_pkst[i] != TC_JOB_OK;
-    for (size_t i = 0; i < need; i++) commit_bad = commit_bad || h_cval[i] == 0;
+    for (size_t i = 0; h_cval && i < need; i++) commit_bad = commit_bad || h_cval[i] == 0;
   }
   if (!k.failed && commit_bad) {
     // no key set, no verdict on anything: every job fails with INVALID_ENCODING and the identity, used = bad = 0
@@ -2644,8 +2719,8 @@ static int robust_combine(tc_ctx* ctx, bool sig, bool wire, const uint8_t* commi
     // operands (PublicKeyShare::verify src/lib.rs:177-179 / verify_decryption_share :182-186); the verdict of an absent slot
     // is dropped by k_robust_mark
     const size_t F = failed.size(), R = F * N;
-    const tc::SlotMaps m = tc::slot_maps(failed.data(), F, N);
-    Compacted c(k, R, {&m.record, &m.job, &m.slot, &failed});
+    tc::SlotMaps m = tc::slot_maps(failed.data(), F, N);
+    Compacted c(k, R, std::move(m.record), std::move(m.job), std::move(m.slot), std::move(failed));
     const uint32_t *d_maps = c.map(0), *d_fmap = c.map(3);  // (record | job | slot maps, R entries each, then the F failed jobs)
     uint8_t* c_ok = c.c_ok;
     // wire: the full checked decode of from_bytes (curve AND subgroup); a failure leaves the identity -- decodable input for the
@@ -2653,7 +2728,6 @@ static int robust_combine(tc_ctx* ctx, bool sig, bool wire, const uint8_t* commi
     const uint8_t* c_wire = wire ? c.gather(d_sh, SB, 0) : nullptr;
     uint8_t* c_dec = wire ? k.temp<uint8_t>(R) : nullptr;
     uint8_t* c_sh = wire ? k.temp<uint8_t>(R * PB) : c.gather(d_sh, PB, 0);
-    std::vector<uint8_t> h_ok;  // bisection: the verdicts come from the host's search
     uint8_t* c_present = k.temp<uint8_t>(R);
     uint8_t* c_bad = k.temp<uint8_t>(R);
     uint64_t* d_idx2 = k.temp<uint64_t>(F * need);
@@ -2668,8 +2742,9 @@ static int robust_combine(tc_ctx* ctx, bool sig, bool wire, const uint8_t* commi
     }
     if (bisect) {
       // which checks run is the ONLY difference: ranges of slots, halved where they fail (blame_pass), instead of every slot
-      if (!k.failed) blame_pass(k, sig, wire, N, failed, d_maps, c_sh, c_dec, d_present, d_jvalid, d_pks, d_hash, d_w, d_g1, h_ok);
-      if (!k.failed) k.upload(c_ok, h_ok.data(), R, "verdict copy");
+      // (the verdicts come from the host's search)
+      const uint8_t* h_ok = k.failed ? nullptr : blame_pass(k, sig, wire, N, c.host_map(3), F, d_maps, c_sh, c_dec, d_present, d_jvalid, d_pks, d_hash, d_w, d_g1);
+      if (!k.failed) k.upload_owned(c_ok, h_ok, R, "verdict copy");
     } else {
       // (the per-share checks read one hash point / w / key share per record; the range checks of the bisection gather theirs per round)
       const uint8_t* c_hash = c.gather(d_hash, 192, 1);
@@ -2706,7 +2781,6 @@ static int robust_combine(tc_ctx* ctx, bool sig, bool wire, const uint8_t* commi
       combine_launch(k, sig, t, need, d_idx2, nullptr, d_packed2, F, d_comb2, d_st2);
       tc::launch_robust_finish(ctx->stream, d_fmap, N, need, PB, F, d_enough2, d_st2, nullptr, nullptr, d_comb2, d_res, d_status, d_used, nullptr);
     }
-    c.sync();
     if (n_fallback) *n_fallback = F;
   }
   // the plaintext of a job that ended OK: xor_with_hash(g, v), src/lib.rs:625
@@ -2821,9 +2895,9 @@ int tc_fr_interpolate_batch(tc_ctx* ctx, size_t n, const uint8_t* xs, const uint
   uint8_t* d_out = k.out(out_coeff, B * n * 32);
   // host-I/O mode: the interpolated (secret) coefficients pass through a staging slot that outlives the call: wiped after
   // the copy back, like every other secret operand
-  if (d_out && !ctx->device_io) k.wipe_after_copy.emplace_back(d_out, B * n * 32);
+  if (!ctx->device_io) k.secret(d_out, B * n * 32, /*after_copy=*/true);
   uint32_t* d_ws = k.temp<uint32_t>(B * 2 * (n + 1) * 8);
-  if (d_ws) k.wipe.emplace_back(d_ws, B * 2 * (n + 1) * 8 * sizeof(uint32_t));
+  k.secret(d_ws, B * 2 * (n + 1) * 8 * sizeof(uint32_t));
   uint8_t* d_st = k.out(status, B);
   k.begin_timing();
   if (!k.failed)
@@ -2856,10 +2930,10 @@ int tc_fr_poly_evaluate_batch(tc_ctx* ctx, const uint8_t* coeff_fr, size_t n, co
   const uint8_t* d_x = k.in(xs_fr, M * 32);
   uint8_t* d_out = k.out(out_fr, B * M * 32);
   // host-I/O mode: the (secret) values pass through a staging slot that outlives the call: wiped after the copy back
-  if (d_out && !ctx->device_io) k.wipe_after_copy.emplace_back(d_out, B * M * 32);
+  if (!ctx->device_io) k.secret(d_out, B * M * 32, /*after_copy=*/true);
   uint8_t* d_st = k.out(status, B * M);
   uint32_t* d_mont = k.temp<uint32_t>(B * n * 8);
-  if (d_mont) k.wipe.emplace_back(d_mont, B * n * 8 * sizeof(uint32_t));
+  k.secret(d_mont, B * n * 8 * sizeof(uint32_t));
   uint8_t* d_valid = k.temp<uint8_t>(B * n);
   k.begin_timing();
   if (!k.failed) {
@@ -2883,10 +2957,10 @@ int tc_bivar_poly_row_batch(tc_ctx* ctx, const uint8_t* coeff_fr, size_t degree,
   const uint8_t* d_c = k.in(coeff_fr, ncoeff * 32, /*secret=*/true);
   const uint64_t* d_x = k.in(xs, M);
   uint8_t* d_out = k.out(out_fr, M * n * 32);
-  if (d_out && !ctx->device_io) k.wipe_after_copy.emplace_back(d_out, M * n * 32);
+  if (!ctx->device_io) k.secret(d_out, M * n * 32, /*after_copy=*/true);
   uint8_t* d_st = k.out(status, M * n);
   uint32_t* d_mont = k.temp<uint32_t>(n * n * 8);
-  if (d_mont) k.wipe.emplace_back(d_mont, n * n * 8 * sizeof(uint32_t));
+  k.secret(d_mont, n * n * 8 * sizeof(uint32_t));
   uint8_t* d_valid = k.temp<uint8_t>(n * n);
   k.begin_timing();
   if (!k.failed) {
@@ -3002,7 +3076,6 @@ int tc_dkg_verify_values_rlc_batch(tc_ctx* ctx, const uint8_t* rows, size_t degr
   uint8_t* d_ok = k.out(ok, B * n);
   k.begin_timing();
   k.check_points(false, d_rows, 96, degree + 1, degree + 1, B, 1);
-  std::vector<uint8_t> h_okjob(B);
   if (!k.failed) {
     tc::launch_dkg_rlc_scalars(ctx->stream, d_seed, d_x, d_vals, n, degree, B, d_sc, d_valid);
     tc::launch_dkg_rlc_points(ctx->stream, d_rows, degree, ctx->g1_gen, B, d_pts);
@@ -3013,22 +3086,20 @@ int tc_dkg_verify_values_rlc_batch(tc_ctx* ctx, const uint8_t* rows, size_t degr
     // checked-input mode: a job owning a non-member row point falls back (and fails there)
     k.apply_checks(B, nullptr, nullptr, 0, d_okjob);
     k.check(hipMemsetAsync(d_ok, 1, B * n, ctx->stream), "memset");
-    k.readback(h_okjob.data(), d_okjob, B, "ok readback");
-    k.check(hipStreamSynchronize(ctx->stream), "stream sync");
+    const uint8_t* h_okjob = k.fetch(d_okjob, B, "ok readback");
     std::vector<uint32_t> failed;
-    if (!k.failed)
+    if (k.wait())
       for (size_t j = 0; j < B; j++)
         if (!h_okjob[j]) failed.push_back((uint32_t)j);
     if (!k.failed && !failed.empty()) {
       // the exact kernels for every value of the failed jobs, on compacted operands: whole rows gathered by job, the verdicts
       // scattered by value
       const size_t F = failed.size(), R = F * n;
-      const tc::SlotMaps m = tc::slot_maps(failed.data(), F, n);
-      Compacted c(k, R, {&failed, &m.record});
+      tc::SlotMaps m = tc::slot_maps(failed.data(), F, n);
+      Compacted c(k, R, std::move(failed), std::move(m.record));
       const uint8_t* c_rows = c.gather(d_rows, row_bytes, 0);
       const uint64_t* c_x = reinterpret_cast<const uint64_t*>(c.gather(d_x, n * 8, 0));
-      const uint8_t* c_vals = c.gather(d_vals, n * 32, 0);
-      if (c_vals) k.wipe.emplace_back(const_cast<uint8_t*>(c_vals), R * 32);
+      const uint8_t* c_vals = c.gather(d_vals, n * 32, 0, /*secret=*/true);
       if (!k.failed) dkg_values_exact(k, c_rows, degree, c_x, c_vals, n, F, c.c_ok, /*checked=*/ctx->input_checks);
       c.finish(d_ok, 1);
       if (n_fallback) *n_fallback = F;
@@ -3146,7 +3217,7 @@ int tc_fr_sum_batch(tc_ctx* ctx, const uint8_t* vals_fr, size_t term_stride, siz
   const uint8_t* d_mask = k.in(mask, n);
   uint8_t* d_out = k.out(out_fr, B * 32);
   // host-I/O mode: the (secret) sums pass through a staging slot that outlives the call: wiped after the copy back
-  if (d_out && !ctx->device_io) k.wipe_after_copy.emplace_back(d_out, B * 32);
+  if (!ctx->device_io) k.secret(d_out, B * 32, /*after_copy=*/true);
   uint8_t* d_st = k.out(status, B);
   k.begin_timing();
   if (!k.failed) tc::launch_fr_sum(ctx->stream, d_v, term_stride, n, d_mask, B, d_out, d_st);
@@ -3177,11 +3248,11 @@ int tc_dkg_generate_batch(tc_ctx* ctx, const uint8_t* commits, size_t commit_str
   const uint8_t* d_v = share ? k.in(vals_fr, P * n_v * 32, /*secret=*/true) : nullptr;
   uint8_t* d_oc = out_commit ? k.out(out_commit, n * 96) : k.temp<uint8_t>(n * 96);
   uint8_t* d_os = k.out(out_share_fr, 32);
-  if (d_os && !ctx->device_io) k.wipe_after_copy.emplace_back(d_os, 32);
+  if (!ctx->device_io) k.secret(d_os, 32, /*after_copy=*/true);
   uint8_t* d_ps = part_status ? k.out(part_status, P) : k.temp<uint8_t>(P);
   uint8_t* d_bad = k.temp<uint8_t>(P, /*zero=*/true);
   uint8_t* d_part = share ? k.temp<uint8_t>(P * 32) : nullptr;  // the parts' contributions to the share: secret
-  if (d_part) k.wipe.emplace_back(d_part, P * 32);
+  k.secret(d_part, P * 32);
   uint8_t* d_sst = share ? k.temp<uint8_t>(P) : nullptr;
   k.begin_timing();
   g1_sum(k, true, d_c, commit_stride, P, d_acc, n, d_oc, nullptr, d_bad);
@@ -3234,7 +3305,7 @@ int tc_fr_weighted_sum_batch(tc_ctx* ctx, const uint8_t* vals_fr, size_t term_st
   const uint8_t* d_w = k.in(weights_fr, n * 32);
   const uint8_t* d_mask = k.in(mask, n);
   uint8_t* d_out = k.out(out_fr, B * 32);
-  if (d_out && !ctx->device_io) k.wipe_after_copy.emplace_back(d_out, B * 32);
+  if (!ctx->device_io) k.secret(d_out, B * 32, /*after_copy=*/true);
   uint8_t* d_st = k.out(status, B);
   k.begin_timing();
   if (!k.failed) tc::launch_fr_wsum(ctx->stream, d_v, term_stride, n, d_w, d_mask, B, d_out, d_st);
@@ -3269,13 +3340,13 @@ int tc_dkg_reshare_batch(tc_ctx* ctx, const uint8_t* old_commit, size_t t_old, c
   const uint8_t* d_v = share ? k.in(vals_fr, P * n_v * 32, /*secret=*/true) : nullptr;
   uint8_t* d_oc = out_commit ? k.out(out_commit, n * 96) : k.temp<uint8_t>(n * 96);
   uint8_t* d_os = k.out(out_share_fr, 32);
-  if (d_os && !ctx->device_io) k.wipe_after_copy.emplace_back(d_os, 32);
+  if (!ctx->device_io) k.secret(d_os, 32, /*after_copy=*/true);
   uint8_t* d_used = used ? k.out(used, P) : k.temp<uint8_t>(P);
   uint8_t* d_ps = part_status ? k.out(part_status, P) : k.temp<uint8_t>(P);
   uint8_t* d_status = status ? k.out(status, 1) : k.temp<uint8_t>(1);
   uint8_t* d_flags = k.temp<uint8_t>(3 * P + 1);  // const_st, point_bad, dup, old_bad
   uint8_t* d_part = share ? k.temp<uint8_t>(P * 32) : nullptr;  // the parts' contributions to the share: secret
-  if (d_part) k.wipe.emplace_back(d_part, P * 32);
+  k.secret(d_part, P * 32);
   uint8_t* d_sst = share ? k.temp<uint8_t>(P) : nullptr;
   uint8_t* d_w = k.temp<uint8_t>(P * 32, /*zero=*/true);  // lambda_p on S: public
   uint32_t* d_sel = k.temp<uint32_t>(t_old + 1, /*zero=*/true);  // (read by the sum whatever the verdict: never uninitialised)

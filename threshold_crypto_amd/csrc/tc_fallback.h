@@ -40,8 +40,7 @@ inline void failed_jobs_of_groups(const uint8_t* bad_group, const GroupCut& cut,
 
 // Which of cut.NG groups of B jobs go to the per-item checks.  Every group starts good and evidence is ORed in, so the order of
 // the calls does not matter.  zero_bad says which byte is the bad one: 0 (ok bytes, membership verdicts) or non-zero (status
-// bytes).  A null array is no evidence: bytes_or_null() of a verdict that nobody registered.
-inline const uint8_t* bytes_or_null(const std::vector<uint8_t>& v) { return v.empty() ? nullptr : v.data(); }
+// bytes).  A null array is no evidence: a verdict that nobody registered (Call::take_verdicts, tc_api.hip).
 inline bool has_zero(const uint8_t* v, size_t n) { return v && n && memchr(v, 0, n) != nullptr; }
 struct BadGroups {
   GroupCut cut;
