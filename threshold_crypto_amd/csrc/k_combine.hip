@@ -2,6 +2,7 @@
 #include "tc_jobs.h"
 #include "tc_launch.h"
 #include "tc_stage.h"
+#include <atomic>
 
 namespace tc {
 
@@ -166,9 +167,10 @@ __global__ __launch_bounds__(kGroupBlock) void k_combine_scatter(const uint8_t* 
 //                     what that atomic returned + the rank inside the workgroup.  For the fallback, the job's denominator
 //                     class and its rank inside the class.  On the side: perm filled with the padding marker, and the jobs
 //                     the fast path leaves counted in ws[kGwsNeed]
-//   k_combine_plan    one workgroup: subset mode or class mode (tc_jobs.h combine_subset_mode), the first slot of every group
-//                     by a prefix sum per order (tc_jobs.h combine_scan_step)
-//   k_combine_place   perm[start[group] + rank] = job
+//   k_combine_plan    one workgroup: subset mode or class mode (tc_jobs.h combine_subset_mode); subset mode: one thread per group
+//                     predicts what a job of the group executes, and the groups go in descending order of it, the second
+//                     half of a single resident round turned round (tc_jobs.h combine_order_start / combine_fold_wave)
+//   k_combine_place   perm[slot of (the group's first wave, rank)] = job
 // No workgroup waits for another; what crosses workgroups inside a launch does so as the result of an atomic.
 // Workspace words (ws): tc_jobs.h kGws*; zeroed by the launcher for every call.
 static_assert(kGroupBlock == (int)kGroupWgJobs, "one lane per job of the workgroup");
@@ -240,35 +242,38 @@ __global__ __launch_bounds__(kGroupBlock) void k_combine_group(const uint64_t* _
     }
   }
 }
-__global__ __launch_bounds__(kSubsetSlots) void k_combine_plan(size_t t, size_t B, uint32_t* __restrict__ ws_words) {
+// seats: the waves of k_combine_fast<Fq2> the device holds at once (launch_combine_g2)
+__global__ __launch_bounds__(kSubsetSlots) void k_combine_plan(size_t t, size_t B, uint32_t seats, uint32_t* __restrict__ ws_words) {
   __shared__ uint32_t count[kSubsetSlots];
-  __shared__ uint8_t order[kSubsetSlots];
+  __shared__ uint32_t cost[kSubsetSlots];
   __shared__ uint32_t ccount[kCombineClasses];
   __shared__ uint8_t corder[kCombineClasses];
-  __shared__ __attribute__((aligned(16))) uint32_t scan[2 * kSubsetSlots * kGroupOrders];
   const uint32_t s = threadIdx.x;
   const unsigned long long key = reinterpret_cast<const unsigned long long*>(ws_words)[s];
+  const bool subset = combine_subset_mode(ws_words[kGwsOverflow] != 0, ws_words[kGwsGroups], B);
   count[s] = ws_words[kGwsCount + s];
-  order[s] = key ? (uint8_t)combine_key_order(key, (int)t) : (uint8_t)(kGroupOrders - 1);
+  // (one thread per group: what a job of the group will execute, tc_jobs.h combine_key_macs; only the ranking matters)
+  cost[s] = subset && count[s] ? combine_key_macs(key, (int)t) : 0;
   if (s < kCombineClasses) {
     ccount[s] = ws_words[kGwsClassCount + s];
     corder[s] = (uint8_t)combine_class_order((int)s);
   }
   __syncthreads();
-  const bool subset = combine_subset_mode(ws_words[kGwsOverflow] != 0, ws_words[kGwsGroups], B);
-  for (int step = 0; step < combine_scan_steps(kSubsetSlots); step++) {
-    combine_scan_step(step, s, kSubsetSlots, count, order, kSubsetPad, scan);
-    __syncthreads();
-  }
-  ws_words[kGwsStart + s] = subset ? combine_scan_start(s, kSubsetSlots, count, order, kSubsetPad, scan) : 0;
+  uint32_t waves = 0;
+  const uint32_t start = combine_order_start(cost, count, kSubsetSlots, s, kSubsetPad, &waves);
+  ws_words[kGwsStart + s] = subset ? start : 0;
   if (s < kCombineClasses) ws_words[kGwsClassStart + s] = combine_group_start(ccount, corder, kCombineClasses, s, kClassPad);
-  if (s == 0) ws_words[kGwsMode] = subset ? 1u : 0u;
+  if (s == 0) {
+    ws_words[kGwsMode] = subset ? 1u : 0u;
+    ws_words[kGwsFold] = subset && combine_order_aligned(waves, seats) ? seats : 0u;
+  }
 }
 __global__ __launch_bounds__(kGroupBlock) void k_combine_place(size_t B, uint32_t* __restrict__ ws_words, size_t slots, uint32_t* __restrict__ perm) {
   const GroupWs g = group_ws(ws_words, B);
   const size_t j = (size_t)blockIdx.x * kGroupBlock + threadIdx.x;
   if (j >= B) return;
-  const size_t pos = g.ws[kGwsMode] ? (size_t)g.ws[kGwsStart + g.grp[j]] + g.rank[j] : (size_t)g.ws[kGwsClassStart + g.cls[j]] + g.crank[j];
+  const size_t pos = g.ws[kGwsMode] ? combine_order_slot(g.ws[kGwsStart + g.grp[j]], g.rank[j], kSubsetPad, g.ws[kGwsFold])
+                                    : (size_t)g.ws[kGwsClassStart + g.cls[j]] + g.crank[j];
   if (pos < slots) perm[pos] = (uint32_t)j;  // (always: the launcher sizes perm for the largest padding either mode can need)
 }
 
@@ -451,6 +456,24 @@ size_t combine_group_slots(size_t B) { return B + (size_t)kCombineClasses * kCom
 size_t combine_group_slots_g2(size_t B) { return B + (size_t)kSubsetMaxGroups * (kSubsetPad - 1); }
 size_t combine_group_ws_words(size_t B) { return (size_t)kGwsZeroWords + 2 * B + (B + 1) / 2 + (B + 3) / 4; }
 uint32_t* combine_group_need(uint32_t* gws) { return gws ? gws + kGwsNeed : nullptr; }
+// The waves of k_combine_fast<Fq2> the current device holds at once (one wave per workgroup): CUs x the occupancy the runtime
+// reports, asked for once per device.  0 when the runtime cannot say: the order is then plain descending cost.
+static uint32_t combine_g2_seats() {
+  constexpr int kDevices = 64;
+  static std::atomic<uint32_t> cache[kDevices];  // seats + 1; 0 = not asked yet
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kDevices) return 0;
+  uint32_t v = cache[dev].load(std::memory_order_relaxed);
+  if (v == 0) {
+    int per_cu = 0, cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0 ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_combine_fast<Fq2>, kBlock, 0) != hipSuccess || per_cu <= 0)
+      cus = per_cu = 0;
+    v = (uint32_t)cus * (uint32_t)per_cu + 1;
+    cache[dev].store(v, std::memory_order_relaxed);
+  }
+  return v - 1;
+}
 // gws: combine_group_ws_words(B) words, perm: combine_group_slots_g2(B) words (scratch of the caller, 8-byte aligned); pass
 // perm = nullptr to run the jobs in their own order.  With both, the grouping counts the jobs the fast path leaves in
 // combine_group_need(gws) and the Lagrange stage of the call is launched HERE, behind that count (the caller launches none)
@@ -465,7 +488,10 @@ void launch_combine_g2(hipStream_t st, TableArena ta, size_t t, size_t n_per_job
       (void)hipMemsetAsync(gws, 0, kGwsZeroWords * sizeof(uint32_t), st);
       const unsigned gb = (unsigned)((B + kGroupBlock - 1) / kGroupBlock);
       hipLaunchKernelGGL(k_combine_group, dim3(gb), dim3(kGroupBlock), 0, st, idx, n_per_job, t, B, gws, slots, perm);
-      hipLaunchKernelGGL(k_combine_plan, dim3(1), dim3(kSubsetSlots), 0, st, t, B, gws);
+      // (a test context's seats are taken and cleared: a later caller on this thread that sets nothing gets the device's own)
+      const uint32_t seats = t_combine_seats ? t_combine_seats : combine_g2_seats();
+      t_combine_seats = 0;
+      hipLaunchKernelGGL(k_combine_plan, dim3(1), dim3(kSubsetSlots), 0, st, t, B, seats, gws);
       hipLaunchKernelGGL(k_combine_place, dim3(gb), dim3(kGroupBlock), 0, st, B, gws, slots, perm);
       launch_lagrange(st, idx, n_per_job, t, B, lam, status, combine_group_need(gws), /*counted=*/true);
     } else {

@@ -635,6 +635,7 @@ tc::Tuning tuning_from_env() {
       }
     }
   }
+  if (const char* e = getenv("TC_COMBINE_SEATS")) tn.combine_seats = (uint32_t)strtoul(e, nullptr, 10);
   if (const char* o = getenv("TC_CHECKS_BESIDE")) tn.checks_beside = (o[0] >= '0' && o[0] <= '2') ? o[0] - '0' : 1;  // 0 one stream, 1 low priority, 2 normal
   return tn;
 }
@@ -1090,6 +1091,7 @@ static void combine_launch(Call& k, bool g2, size_t t, size_t n, const uint64_t*
     msm_g2(k, t + 1, n * PB, d_sh, d_lam, B, d_pt, d_st);  // large thresholds: every job, coefficients from the one-inversion kernels
   } else if (g2) {
     // t <= 3: small-index fast path first; then (t >= 1) the jobs it left, through the two-stage kernels
+    tc::t_combine_seats = ctx->tuning.combine_seats;
     tc::launch_combine_g2(ctx->stream, k.tables(), t, n, d_idx, d_sh, d_lam, B, d_pt, d_st, d_gws, d_perm, d_need,
                           k.fork_event());
     if (t >= 1) {

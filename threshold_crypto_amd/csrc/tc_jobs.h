@@ -661,6 +661,63 @@ TC_HD int combine_key_order(uint64_t key, int t) {
   for (int k = 0; k < 4; k++) idx[k] = (key >> (16 * k)) & 0xffffull;
   return combine_class_order(combine_job_class(idx, t));
 }
+// ---- what one job of a tuple will execute, predicted (multiply-adds, as profiles/combine_uniform_macs.json counts them) -----
+// The launch order of k_combine_plan ranks the groups by it; only the ranking matters.  Built from what the wave itself
+// will run: the short ladder of straus_small_uniform (one doubling per column below the top of the longest NAF, one mixed
+// addition per nonzero digit but the first), then per class
+//   generic   the cheaper of the planned quotient form and the 4-dimensional ladder, exactly as combine_divide_cheapest chooses
+//   2^a       psi^3(Q) - psi(Q), the 15 doublings of the positioning loop (all executed, 16 - a of them kept), the 47
+//             doublings and 5 additions of |x| >> 16 (combine_divide): as long as a generic chain, whatever a
+//   1         nothing
+// and the decoding, the one inversion and the encoding every job has (kMacsJobFixed: D = 1 less its short ladder).
+constexpr uint32_t kMacsJobFixed = 30002, kMacsPow2Fixed = 25088, kMacsMixedGeneric = 1540687;
+template <int K>
+TC_HD uint32_t combine_short_ladder_macs(const uint64_t* c_abs) {
+  uint64_t any = 0;
+  int nz = 0;
+  for (int k = 0; k < K; k++) {
+    uint64_t pos, neg;
+    naf_recode(c_abs[k], &pos, &neg);
+    any |= pos | neg;
+    nz += __builtin_popcountll(pos | neg);
+  }
+  const int top = any ? 63 - (int)__builtin_clzll(any) : 0;
+  return (uint32_t)top * kMacsDbl + (uint32_t)(nz > 0 ? nz - 1 : 0) * kMacsAdd;
+}
+TC_HD uint32_t combine_divide_macs(uint64_t d_abs) {
+  const int cls = combine_denominator_class(d_abs);
+  if (cls == kCombineClassOne) return 0;
+  if (cls == kCombineClassPow2) return kMacsPow2Fixed + (15 + 47) * kMacsDbl + 5 * kMacsAdd;
+  uint64_t q = 0;
+  int64_t T[4] = {0, 0, 0, 0}, E[4] = {0, 0, 0, 0};
+  const bool taken = combine_quotient_decompose(d_abs, &q, T, E);
+  const uint32_t planned = taken ? combine_quotient_plan(q, T, E).macs : 0xffffffffu;
+  // (the quotient form wins for every D below 2^13 or so -- every denominator of node numbers: no 256-bit inverse and no
+  // GLS decomposition for those in the one workgroup of k_combine_plan)
+  if (taken && d_abs < (1ull << 12)) return planned;
+  const uint32_t ladder = combine_divide_uniform_macs(d_abs);
+  return planned < ladder ? planned : ladder;
+}
+// 0: the fast path does not take the tuple
+TC_HD uint32_t combine_tuple_macs(const uint64_t* idx, int t) {
+  uint64_t c_abs[4], d_abs = 0;
+  bool c_neg[4], d_neg;
+  uint32_t ladder = 0;
+  bool applies = false;
+  if (t == 1 && (applies = lagrange_small_coeffs<2>(idx, c_abs, c_neg, &d_abs, &d_neg))) ladder = combine_short_ladder_macs<2>(c_abs);
+  if (t == 2 && (applies = lagrange_small_coeffs<3>(idx, c_abs, c_neg, &d_abs, &d_neg))) ladder = combine_short_ladder_macs<3>(c_abs);
+  if (t == 3 && (applies = lagrange_small_coeffs<4>(idx, c_abs, c_neg, &d_abs, &d_neg))) ladder = combine_short_ladder_macs<4>(c_abs);
+  if (!applies) return 0;
+  return kMacsJobFixed + ladder + combine_divide_macs(d_abs);
+}
+// the same from a group's key; the group "none" (and an empty entry) counts as a mixed wave of the generic class
+TC_HD uint32_t combine_key_macs(uint64_t key, int t) {
+  if (key == kTupleKeyNone || key == 0) return kMacsMixedGeneric;
+  uint64_t idx[4];
+  for (int k = 0; k < 4; k++) idx[k] = (key >> (16 * k)) & 0xffffull;
+  const uint32_t m = combine_tuple_macs(idx, t);
+  return m ? m : kMacsMixedGeneric;
+}
 TC_HD uint32_t combine_key_hash(uint64_t key) { return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 40); }
 TC_HD bool combine_subset_mode(bool overflow, uint32_t groups, size_t B) {
   return !overflow && groups <= kSubsetMaxGroups && (size_t)kSubsetPad * groups <= B / 8;  // padding: at most an eighth of the slots
@@ -704,9 +761,10 @@ TC_HD uint64_t group_load64(const uint64_t* p) { return *p; }
 // The call's workspace, in words (zeroed by the launcher for every call): the table's keys (64 bits each), the jobs per entry,
 // the first slot per entry, then single words.  kGwsNeed: the jobs the fast path leaves (key "none"), for the Lagrange stage
 // and the two-stage kernels behind it.
+// kGwsStart: subset mode, the group's first WAVE in the launch order; kGwsFold: the resident waves the order folds at, 0 = no fold.
 constexpr uint32_t kGwsCount = 2 * kSubsetSlots, kGwsStart = 3 * kSubsetSlots, kGwsMisc = 4 * kSubsetSlots;
 constexpr uint32_t kGwsClassCount = kGwsMisc, kGwsClassStart = kGwsMisc + 4, kGwsGroups = kGwsMisc + 8, kGwsOverflow = kGwsMisc + 9,
-                   kGwsMode = kGwsMisc + 10, kGwsNeed = kGwsMisc + 11, kGwsZeroWords = kGwsMisc + 16;
+                   kGwsMode = kGwsMisc + 10, kGwsNeed = kGwsMisc + 11, kGwsFold = kGwsMisc + 12, kGwsZeroWords = kGwsMisc + 16;
 // A workgroup takes kGroupWgJobs jobs and first counts them per key in a table of its own (twice as many entries as jobs, so a
 // probe always meets the key or an empty entry); then ONE lane per distinct key does the key's work on the call's table.
 constexpr uint32_t kGroupWgJobs = 256;
@@ -793,6 +851,41 @@ TC_HD uint32_t combine_scan_start(uint32_t s, uint32_t n, const uint32_t* count,
   uint32_t start = sum[s * kGroupOrders + order[s]] - (count[s] + pad - 1) / pad * pad;
   for (int o = 0; o < (int)order[s]; o++) start += sum[(n - 1) * kGroupOrders + o];
   return start;
+}
+
+// ---- the launch order of subset mode: by predicted cost, folded once (k_combine_plan / k_combine_place) -------
+// The dispatcher hands workgroups out in index order, one per SIMD before any SIMD gets its second, so with `seats` resident
+// waves wave k < seats / 2 shares its SIMD with wave k + seats / 2 (tools/placement_probe, profiles/placement_probe.txt), and a
+// SIMD that holds waves of lone cost a >= b is busy for a + b / 2.  The order: all waves by descending cost (combine_key_macs);
+// and when the launch is ONE resident round with a surplus (combine_order_aligned) the second half of the round is turned
+// round, so that the lightest wave of the round sits beside the heaviest -- wave d of the descending sequence goes to slot
+//     d                        d < seats / 2 (the heaviest, one per SIMD)  or  d >= seats (the cheapest: they fill what frees first)
+//     3 seats / 2 - 1 - d      otherwise
+// A group's waves stay one run, or two where the sequence folds; no wave holds two groups; the padding is what it was.
+// (The scan above orders by class alone: it stays for the host suites that pin it and for nothing else.)
+TC_HD uint32_t combine_group_waves(uint32_t count, uint32_t pad) { return (count + pad - 1) / pad; }
+// first wave of group s in the descending sequence (by cost, then by number; empty groups take nothing); *total: all waves
+TC_HD uint32_t combine_order_start(const uint32_t* cost, const uint32_t* count, uint32_t n, uint32_t s, uint32_t pad, uint32_t* total) {
+  uint32_t start = 0, all = 0;
+  for (uint32_t g = 0; g < n; g++) {
+    const uint32_t w = combine_group_waves(count[g], pad);
+    all += w;
+    if (cost[g] > cost[s] || (cost[g] == cost[s] && g < s)) start += w;
+  }
+  *total = all;
+  return start;
+}
+// one resident round with a surplus of at most 3/16 of it: in the model (tools/sim_launch_order.py, profiles/combine_order_model.txt)
+// the fold wins up to 1.18 x seats waves and loses from 1.21 x on, where the surplus no longer fits behind the cheap half; with
+// fewer waves than seats there is no pair to choose, and over several rounds plain descending cost is as good
+TC_HD bool combine_order_aligned(uint32_t waves, uint32_t seats) { return seats >= 2 && waves >= seats && (uint64_t)16 * waves <= (uint64_t)19 * seats; }
+TC_HD uint32_t combine_fold_wave(uint32_t d, uint32_t fold_seats) {
+  const uint32_t half = fold_seats / 2;  // (fold_seats = 0: no fold)
+  return d >= half && d < 2 * half ? 3 * half - 1 - d : d;
+}
+// the slot of the job of rank `rank` in a group whose first wave is `start_wave`
+TC_HD size_t combine_order_slot(uint32_t start_wave, uint32_t rank, uint32_t pad, uint32_t fold_seats) {
+  return (size_t)combine_fold_wave(start_wave + rank / pad, fold_seats) * pad + rank % pad;
 }
 
 // out = sum_{i <= t} lambda_i * share_i over the FIRST t+1 samples of the job

@@ -71,6 +71,9 @@ struct Tuning {
   // tc_decrypt_shares_*: the G1 comb from this many holders AND this many ciphertexts on (TC_COMB_G1_MIN="<holders>,<batch>": tests,
   // tools/decrypt_shares_probe.py)
   size_t comb_g1_min_holders = kCombG1MinHolders, comb_g1_min_batch = kCombG1MinBatch;
+  // the resident waves the launch order of the grouped G2 combination folds at (TC_COMBINE_SEATS=<waves>: tests); 0 = the device's own
+  // (k_combine.hip combine_g2_seats)
+  uint32_t combine_seats = 0;
 };
 
 // The G1 ladder kernels keep their per-lane table in the HBM arena and fit 256 registers (two waves per SIMD) at
@@ -169,6 +172,12 @@ uint32_t* combine_group_need(uint32_t* gws);
 void launch_combine_g2(hipStream_t st, TableArena ta, size_t t, size_t n_per_job, const uint64_t* idx, const uint8_t* shares,
                        uint32_t* lam, size_t B, uint8_t* out, uint8_t* status, uint32_t* gws,
                        uint32_t* perm, const uint32_t* need_general, hipEvent_t before_main = nullptr);
+// The launch order of that grouping folds at the waves of k_combine_fast<Fq2> the device holds at once: CUs x occupancy, which
+// launch_combine_g2 asks the runtime for once per device.  A context created under TC_COMBINE_SEATS=<waves> (Tuning::combine_seats;
+// tests: a "device" of 64 or 128 seats) puts its value here, for the calling thread, just before it launches; the launcher takes
+// it and clears it, so nothing set for one call reaches another; 0 = the device's own.  (A variable and not a parameter: the
+// launcher's signature is what the host harness of the call frame, tests/call, links its stand-ins against.)
+inline thread_local uint32_t t_combine_seats = 0;
 // shared_points: every job combines the SAME n points (points holds n of them) with its own n scalars
 void launch_lincomb_g1(hipStream_t st, size_t n, const uint8_t* scalars, const uint8_t* points, size_t B, uint8_t* out,
                        uint8_t* status, bool shared_points = false);
